@@ -2,7 +2,9 @@
 """Headline benchmark: IQ frames/sec, all 18 features, 2048-sample complex64
 frames (BASELINE.json metric), on N MI355X of one node.
 
-    python bench.py                       # N=1, defaults finish in ~2-3 min
+    python bench.py                       # N=1, the headline only
+    python bench.py --full                # and every other leg: defaults finish in ~2-3 min
+    python bench.py --dump-outputs DIR    # and the last timed step's features in DIR/*.npy
     python bench.py --gpus N              # starts its own N ranks (one fresh child process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
@@ -21,22 +23,29 @@ samples of synthetic IQ (10.47 GB), generated in HBM before the timed region
 shape (frames shard embarrassingly: no collective on the data path, weak
 scaling); the only cross-rank traffic is the timing barrier/MAX.
 
+A plain run sets up, warms up, times --steps steps and prints the line; nothing else runs on
+the GPU or the host.  `--full` adds every other leg below (CPU baselines, the D2H-inclusive
+step, the read / FMA probes, the upload path, the other BASELINE frame sizes, the binary's
+digests and the replayed profiles, and at N > 1 the fan-out and the gather); their keys are
+null in a plain line.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's
+(mods, SNR, frames, 18) float32 features) to DIR/features.npy: see dump_outputs().
+
 One JSON line on stdout (rank 0).  Extra objects:
   roofline     achieved = algorithmic bytes per launch ((8*N+72) B x frames)
                / mean launch duration from HIP events on the launch stream,
                against the 8 TB/s HBM peak (MI355X_MICROARCH.md); `traffic`
                carries the PMC-derived HBM bytes per launch when a committed
-               profile summary provides it (profiles/*.json), else null.
-               roofline.secondary.measured: the board's instruction-issue ceiling under its power cap, run
-               live after the timed region (amcx_probe_fma_rate, ~1 s of independent v_fma_f32), and this
+               profile summary provides it (profiles/*.json), else null (--full).
+               roofline.secondary.measured (--full): the board's instruction-issue ceiling under its power cap,
+               run live after the timed region (amcx_probe_fma_rate, ~1 s of independent v_fma_f32), and this
                kernel's own instruction rate against it; roofline.frac_of_measured_read_peak.
   per_rank     (N > 1) one entry per rank: rank, device, PCI bus id, ms = [mean, min, max] launch, frames per
                launch, its own wall seconds, its device's FMA ceiling -- if the aggregate is short of N x, the
                line says which rank, device or clock was slow; scaling_efficiency = value / (N x the best rank's
                own kernel-only rate), rank_balance = slowest / fastest rank's kernel-only rate.
-  h2d_fanout   (N > 1) the real-data path over all N devices from ONE process (DeviceFanOut): rank 0, before it
-               touches a GPU, runs a fresh child that uploads one configs[1] modulation (3.49 GB complex128).
-  cpu_baseline the oracle's reference-shaped per-frame evaluator on the host
+  h2d_fanout   (N > 1, --full) the real-data path over all N devices from ONE process (DeviceFanOut): rank 0, before
+               it touches a GPU, runs a fresh child that uploads one configs[1] modulation (3.49 GB complex128).
+  cpu_baseline (--full) the oracle's reference-shaped per-frame evaluator on the host
                cores (kind "port"), on the configs[0] shape, rank 0 at N=1
                only; run BEFORE the GPU is initialised (worker processes).
 """
@@ -448,21 +457,28 @@ def _valu_note(frames_per_s: float, ident=None, directory=None):
 
 def _ensure_library(local_rank: int):
     """libamcx.so is a build artefact (not in git): if this checkout lacks it, local rank 0
-    builds it (as __graft_entry__.build() does) and the other ranks wait for the file."""
+    builds it (as __graft_entry__.build() does) and the other ranks wait for the file.  A current library
+    is used as it is: nothing is written to the checkout, which may be read-only to the process running
+    the benchmark."""
     from amcpy_amd.csrc import build as b
     if local_rank == 0:
-        if Path(b.HIPCC).exists():
-            b.build(force=False, verbose=False)          # rebuilds only if sources are newer (build.stale)
-        elif not b.LIB.exists():
-            raise SystemExit("libamcx.so is missing and hipcc is not available")
-        b.LIB.with_suffix(".ready").touch()
+        if not b.stale():
+            return
+        if not Path(b.HIPCC).exists():
+            if not b.LIB.exists():
+                raise SystemExit("libamcx.so is missing and hipcc is not available")
+            return                                       # as before: without hipcc the library there is used
+        if not os.access(b.LIB.parent if b.LIB.parent.exists() else b.LIB.parent.parent, os.W_OK):
+            raise SystemExit(f"{b.LIB} is older than its sources and its directory is not writable: "
+                             "run __graft_entry__.build() (or amcpy_amd/csrc/build.py) as the checkout's owner")
+        b.build(force=False, verbose=False)
         return
     # other ranks: wait until local rank 0 has finished (a stale library must not be loaded while it is
-    # being replaced): rank 0 touches the stamp file when its build() has returned
+    # being replaced): build() links to a temporary file and renames it into place, so a library that
+    # exists and is newer than every source is complete and current
     deadline = time.time() + 300
-    stamp = b.LIB.with_suffix(".ready")
     while time.time() < deadline:
-        if b.LIB.exists() and stamp.exists() and stamp.stat().st_mtime >= b.LIB.stat().st_mtime and not b.stale():
+        if b.LIB.exists() and not b.stale():
             return
         time.sleep(0.5)
     raise SystemExit("libamcx.so was not (re)built by local rank 0 within 300 s")
@@ -615,12 +631,20 @@ def main():
     ap.add_argument("--fanout-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="self-launched ranks (--gpus N without a launcher) are killed after this many seconds")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg behind the headline as well (CPU baselines, D2H-inclusive step, read / FMA probes, "
+                         "upload path, other configs, binary digests and replays; N > 1: fan-out, gather); the --no-* "
+                         "options skip single legs of it.  Without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
     FS = args.frame_size
     if args.fanout_child > 0:
         raise SystemExit(fanout_child(args.fanout_child, args.share_gpu, FS, args.frames))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ      # torch.distributed.run, or our own parent
     world = int(os.environ.get("WORLD_SIZE", "1")) if launched else 1
@@ -633,7 +657,7 @@ def main():
         raise SystemExit(self_launch(args.gpus, sys.argv[1:], args.launch_timeout))
 
     cpu = cpu_ref_shaped = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_procs, args.cpu_seconds)      # before the GPU is touched
         cpu_ref_shaped = cpu_baseline_reference_shaped()
 
@@ -642,7 +666,7 @@ def main():
     # N > 1: the one-process fan-out over all N devices, by a fresh child of rank 0 while no rank has touched its GPU
     # yet (the others wait in the rendezvous below)
     h2d_fanout = None
-    if world > 1 and rank == 0 and not args.no_fanout and not args.no_h2d:
+    if args.full and world > 1 and rank == 0 and not args.no_fanout and not args.no_h2d:
         h2d_fanout = run_fanout_leg(world, args.share_gpu, FS, min(args.frames, N_FRAMES))
     import torch
     import torch.distributed as dist
@@ -710,31 +734,33 @@ def main():
         t = torch.tensor([wall], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
-
-    # the same step with the (F x 18) result brought to the host every step: a ring of three result buffers, the
-    # copy of step k on a second stream while steps k+1, k+2 compute (46 MB at ~28 GB/s is 1.7 ms against a 3.4 ms
-    # launch; the runtime copies with a blit kernel, which the dispatcher may hold back behind the persistent
-    # feature kernel -- with two buffers that delay stalled the next launch in some runs, with three it has a
-    # whole launch of slack)
-    RING = 3
-    outs = [out] + [torch.empty_like(out) for _ in range(RING - 1)]
-    hosts = [torch.empty(out.shape, dtype=torch.float32, pin_memory=True) for _ in range(RING)]
-    main_stream, copy_stream = torch.cuda.current_stream(), torch.cuda.Stream(device=dev)
-    computed = [torch.cuda.Event() for _ in range(RING)]
-    copied = [torch.cuda.Event() for _ in range(RING)]
-
-    def step_with_d2h(k):
-        b = k % RING
-        main_stream.wait_event(copied[b])                 # the copy that last read this buffer is done
-        features18(arena, out=outs[b], variant=args.variant)
-        computed[b].record(main_stream)
-        with torch.cuda.stream(copy_stream):
-            copy_stream.wait_event(computed[b])
-            hosts[b].copy_(outs[b], non_blocking=True)
-            copied[b].record(copy_stream)
+    if args.dump_outputs and rank == 0:                # before any later leg touches `out`
+        dump_outputs(args.dump_outputs, out)
 
     wall_d2h_ms = None
-    if not args.no_d2h:
+    if args.full and not args.no_d2h:
+        # the same step with the (F x 18) result brought to the host every step: a ring of three result buffers, the
+        # copy of step k on a second stream while steps k+1, k+2 compute (46 MB at ~28 GB/s is 1.7 ms against a 3.4 ms
+        # launch; the runtime copies with a blit kernel, which the dispatcher may hold back behind the persistent
+        # feature kernel -- with two buffers that delay stalled the next launch in some runs, with three it has a
+        # whole launch of slack)
+        RING = 3
+        outs = [out] + [torch.empty_like(out) for _ in range(RING - 1)]
+        hosts = [torch.empty(out.shape, dtype=torch.float32, pin_memory=True) for _ in range(RING)]
+        main_stream, copy_stream = torch.cuda.current_stream(), torch.cuda.Stream(device=dev)
+        computed = [torch.cuda.Event() for _ in range(RING)]
+        copied = [torch.cuda.Event() for _ in range(RING)]
+
+        def step_with_d2h(k):
+            b = k % RING
+            main_stream.wait_event(copied[b])                 # the copy that last read this buffer is done
+            features18(arena, out=outs[b], variant=args.variant)
+            computed[b].record(main_stream)
+            with torch.cuda.stream(copy_stream):
+                copy_stream.wait_event(computed[b])
+                hosts[b].copy_(outs[b], non_blocking=True)
+                copied[b].record(copy_stream)
+
         # The first overlapped steps after an idle queue are a transient: the first copy into a pinned buffer holds the
         # host for ~8 ms, and the ~28 launches after such a gap run up to 60 % long next to the copies before the
         # overlap settles at no cost at all (tools/d2h_overlap_probe.py, profiles/r3_d2h_overlap_probe.txt).  The
@@ -752,14 +778,14 @@ def main():
         wall_d2h_ms = e_first.elapsed_time(e_last) / args.steps
         assert torch.equal(hosts[(n_warm + args.steps - 1) % RING].view(torch.int32), out.cpu().view(torch.int32)), \
             "double-buffered D2H delivered a different result"
-    del outs, hosts
+        del outs, hosts
 
     # sanity: the timed output is finite
     assert torch.isfinite(out[0, N_SNR // 2, :64]).all(), "non-finite features in the timed output"
 
     # measured streaming-read ceiling next to the nominal peak (rank 0)
     read_peak = None
-    if rank == 0:
+    if args.full and rank == 0:
         lib = _lib.load()
         part = torch.empty(4096, dtype=torch.float32, device=dev)
         nbytes = arena.numel() * 8
@@ -777,14 +803,14 @@ def main():
     # the bound that binds: the board's instruction-issue rate under its power cap, measured now (every rank: a slow
     # device shows here), against the kernel's own rate
     fma = None
-    if not args.no_fma_probe:
+    if args.full and not args.no_fma_probe:
         try:
             fma = _lib.probe_fma_rate(1.0, torch.cuda.current_stream().cuda_stream)
         except Exception as exc:
             fma = {"error": repr(exc)}
 
     h2d = None
-    if rank == 0 and world == 1 and not args.no_h2d:
+    if args.full and rank == 0 and world == 1 and not args.no_h2d:
         del arena
         arena = None
         torch.cuda.empty_cache()
@@ -799,7 +825,8 @@ def main():
     other = None
     # (AFTER the upload-path leg: freeing the 21 GB configs[2] arena right before it left the driver clearing VRAM on the copy
     #  engines the uploads use -- 83 instead of 105 GB/s for the configs[1]-sized modulation, 17 instead of 57 for configs[0])
-    if rank == 0 and world == 1 and not args.no_other_configs and FS == FRAME_SIZE and args.frames == N_FRAMES and n_mods == N_MODS:
+    if (args.full and rank == 0 and world == 1 and not args.no_other_configs and FS == FRAME_SIZE and args.frames == N_FRAMES
+            and n_mods == N_MODS):
         arena = None
         torch.cuda.empty_cache()
         other = {}
@@ -816,7 +843,7 @@ def main():
     # never a hang: every rank reports whether it can take part BEFORE the collective (as run_extraction does), and
     # all of them skip it if one cannot.
     gather = None
-    if use_dist and world > 1:
+    if args.full and use_dist and world > 1:
         from amcpy_amd.sharding import gather_rows
         local, problem = None, None
         try:
@@ -861,8 +888,10 @@ def main():
     srt = sorted(launch_ms)
     alg_bytes = (8 * FS + 72) * frames_per_launch
     kname = _lib.kernel_name(FS, _lib.VARIANTS[args.variant])
-    ident = _binary_identity(kname)
-    traffic, traffic_src = _pmc_traffic(frames_per_launch, FS, ident)
+    ident, traffic, traffic_src = None, None, "not replayed in a plain run (bench.py --full)"
+    if args.full:
+        ident = _binary_identity(kname)
+        traffic, traffic_src = _pmc_traffic(frames_per_launch, FS, ident)
     achieved = alg_bytes / mean_launch_s / 1e9
     short = lambda h: h[:16] if isinstance(h, str) else h     # noqa: E731  (64 bits of a SHA-256 name a build)
     # about 3.5 KB: the driver keeps only the tail of a long line, and round 3's 7 KB `parity` block pushed h2d /
@@ -882,8 +911,8 @@ def main():
             "sharding": f"frames x{world}, no collective on the data path",
         },
         # the GPU program that was timed (tools/codeobj_gate.py --print; amcpy_amd/csrc/codeobj.json holds the tree's)
-        "binary": ({"code_object_sha256": short(ident.get("code_object_sha256")), "kernel_sha256": short(ident.get("kernel_sha256"))}
-                   if "error" not in ident else ident),
+        "binary": (None if ident is None else ident if "error" in ident else
+                   {"code_object_sha256": short(ident.get("code_object_sha256")), "kernel_sha256": short(ident.get("kernel_sha256"))}),
         "rccl_ranks": rccl_ranks,
         "launcher": ("none" if not launched else
                      "self" if os.environ.get("AMCX_BENCH_SELF_LAUNCHED") == "1" else "external") + f"/{args.dist_backend}",
@@ -899,7 +928,7 @@ def main():
             "frac_of_measured_read_peak": None if not read_peak else achieved / read_peak,
             # flat, so that a reader that keeps only this object's scalars still has the three BASELINE frame sizes
             **({} if not other else {f"frac_n{k}": v.get("frac") for k, v in other.items()}),
-            "secondary": _secondary(value / world, fma, brief=world > 1, ident=ident) if FS == FRAME_SIZE else None,
+            "secondary": _secondary(value / world, fma, brief=world > 1, ident=ident) if args.full and FS == FRAME_SIZE else None,
         },
         **({} if other is None else {"other_configs": other}),
         "wall_incl_d2h_ms": wall_d2h_ms,
@@ -940,6 +969,35 @@ def _timed_config(torch, synth, features18, dev, rank, frame_size, n_mods, n_fra
     return {"config": label, "frames_per_s": frames / mean_s, "frac": gbps / HBM_PEAK_GBPS, "achieved_GBps": gbps,
             "mean_launch_ms": mean_s * 1e3, "frames_per_launch": frames, "kernel": _lib.kernel_name(frame_size),
             "warm": warm, "steps": steps}
+
+
+DUMP_LIMIT_BYTES = 64_000_000    # --dump-outputs writes at most this much in all
+DUMP_SEED = 2048
+
+
+def dump_outputs(directory, out, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """`--dump-outputs DIR`: what the timed path computed in its last step, as a caller of features18 receives it -- the
+    (mods, SNR, frames, 18) float32 feature array -- as DIR/features.npy (46 MB for the default configs[1] shape).  When
+    that exceeds `limit`, a fixed sample of frames instead: rows drawn without replacement by a generator seeded with
+    DUMP_SEED, in ascending order, as DIR/features_sample.npy ((k, 18) float32), and their flat frame indices as
+    DIR/features_sample_rows.npy (float64, exact).  The inputs are seeded (synth.device_frames), so two builds run with the
+    same arguments can be compared file for file.  Returns {name: shape} of what was written."""
+    import numpy as np
+    import torch
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    rows = out.reshape(-1, out.shape[-1])
+    row_bytes = rows.shape[1] * 4
+    if rows.shape[0] * row_bytes + 1024 <= limit:
+        arr = out.detach().to("cpu", torch.float32).numpy()
+        np.save(d / "features.npy", arr)
+        return {"features": list(arr.shape)}
+    k = (limit - 2048) // (row_bytes + 8)               # the sample and its indices together, headers included
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=k, replace=False))
+    sample = rows[torch.from_numpy(idx).to(rows.device)].detach().to("cpu", torch.float32).numpy()
+    np.save(d / "features_sample.npy", sample)
+    np.save(d / "features_sample_rows.npy", idx.astype(np.float64))
+    return {"features_sample": list(sample.shape), "features_sample_rows": [int(k)]}
 
 
 def _secondary(frames_per_s_per_gpu: float, fma, brief: bool = False, ident=None, directory=None):

@@ -1668,7 +1668,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     import sys
     repo = Path(__file__).resolve().parents[1]
     env = _launcher_free_env()
-    flags = ["--gpus", "2", "--steps", "3", "--warmup", "2", "--frames", "64", "--dist-backend", "gloo", "--share-gpu"]
+    flags = ["--gpus", "2", "--steps", "3", "--warmup", "2", "--frames", "64", "--dist-backend", "gloo", "--share-gpu", "--full"]
     # 1. by itself
     r = subprocess.run([sys.executable, str(repo / "bench.py"), *flags], env=env, cwd=str(tmp_path),
                        capture_output=True, text=True, timeout=600)
@@ -1710,6 +1710,42 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
                              env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
         assert bad.returncode != 0 and "no GPU of its own" in bad.stderr, bad.stderr[-2000:]
         assert not [ln for ln in bad.stdout.splitlines() if ln.strip()], bad.stdout
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` line carries the headline only (the --full legs are null), `steps` / `ms_per_step` say what was
+    timed, and --dump-outputs writes exactly what features18 computes on the benchmark's own seeded arena: the same
+    bits from a second run and from the arena rebuilt here."""
+    import subprocess
+    import sys
+    torch = _torch()
+    from amcpy_amd import synth
+    from amcpy_amd.features import features18
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                            "--frames", "32", "--dump-outputs", str(d)], env=_launcher_free_env(), cwd=str(tmp_path),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 4 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["unit"] == "frames/s"
+        assert rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["metric"].startswith("IQ frames/sec")
+        total = rec["value"] * rec["ms_per_step"] * 1e-3 * rec["steps"]
+        assert abs(total - 6 * 26 * 32 * 4) < 1e-3 * total, (total, rec["value"], rec["ms_per_step"])
+        for k in ("cpu_baseline", "cpu_baseline_reference_shaped", "h2d", "wall_incl_d2h_ms", "gather", "binary"):
+            assert rec[k] is None, (k, rec[k])
+        assert "other_configs" not in rec and rec["roofline"]["secondary"] is None
+        assert rec["roofline"]["traffic"] is None and rec["roofline"]["measured_read_peak_GBps"] is None
+    a, b = (np.load(d / "features.npy") for d in dirs)
+    assert a.dtype == np.float32 and a.shape == (6, 26, 32, 18)
+    assert np.array_equal(a.view(np.int32), b.view(np.int32))
+    arena = torch.empty((6, 26, 32, 2048), dtype=torch.complex64, device="cuda")
+    for mi in range(6):
+        synth.device_frames(synth.MODS6[mi], 26, 32, 2048, device=arena.device, rank=0, mod_idx=mi, out=arena[mi])
+    want = features18(arena).cpu().numpy()
+    assert np.array_equal(a.view(np.int32), want.view(np.int32))
 
 
 def test_fma_ceiling_probe_and_host_placement_on_this_box():

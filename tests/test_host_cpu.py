@@ -1405,6 +1405,81 @@ def test_bench_scaling_block_at_eight_ranks():
     assert bench._secondary(200e6, {"error": "boom"}, ident={"error": "x"})["measured"] == {"error": "boom"}
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs): the last step's (mods, SNR, frames, 18) float32 features as they
+    are while they fit the limit; above it a fixed, sorted sample of frames with their indices, the same from call to
+    call, within the limit in all; and both options are on the command line."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", REPO / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    out = torch.from_numpy(np.random.default_rng(5).standard_normal((2, 3, 50, 18)).astype(np.float32))
+    out[0, 1, 7, 4] = float("nan")
+    assert bench.dump_outputs(tmp_path / "whole", out) == {"features": [2, 3, 50, 18]}
+    got = np.load(tmp_path / "whole" / "features.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, out.numpy(), equal_nan=True)
+    limit = 6000
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"sample{k}"
+        written = bench.dump_outputs(d, out, limit=limit)
+        assert set(written) == {"features_sample", "features_sample_rows"} and not (d / "features.npy").exists()
+        assert sum(p.stat().st_size for p in d.iterdir()) <= limit
+        runs.append((np.load(d / "features_sample.npy"), np.load(d / "features_sample_rows.npy")))
+    (a, ia), (b, ib) = runs
+    assert a.dtype == np.float32 and ia.dtype == np.float64 and a.shape == (ia.size, 18) and ia.size > 10
+    assert np.array_equal(ia, ib) and np.array_equal(a, b, equal_nan=True) and np.all(np.diff(ia) > 0)
+    assert np.array_equal(a, out.numpy().reshape(-1, 18)[ia.astype(np.int64)], equal_nan=True)
+    text = subprocess.run([sys.executable, str(REPO / "bench.py"), "--help"], capture_output=True, text=True, timeout=60).stdout
+    assert "--full" in text and "--dump-outputs" in text
+
+
+def test_bench_writes_nothing_beside_a_current_library(tmp_path, monkeypatch):
+    """bench._ensure_library with a library newer than every source (what build() leaves): every rank goes on at once and
+    nothing is written next to it -- the benchmark may run as a user to whom the checkout is read-only."""
+    import importlib.util
+    import time
+    from amcpy_amd.csrc import build as b
+    spec = importlib.util.spec_from_file_location("bench_mod", REPO / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    lib = tmp_path / "lib" / "libamcx.so"
+    lib.parent.mkdir()
+    lib.write_bytes(b"\x7fELF")
+    newest = max(p.stat().st_mtime for p in b.SOURCES + b.HEADERS + [Path(b.__file__)])
+    os.utime(lib, (newest + 60, newest + 60))
+    monkeypatch.setattr(b, "LIB", lib)
+    before = {p.name: p.stat().st_mtime_ns for p in lib.parent.iterdir()}
+    for rank in (0, 1):
+        t0 = time.time()
+        bench._ensure_library(rank)
+        assert time.time() - t0 < 5
+    assert {p.name: p.stat().st_mtime_ns for p in lib.parent.iterdir()} == before
+
+
+def test_binary_digests_only_read_the_library(tmp_path):
+    """tools/codeobj_gate.py and tools/resource_usage.py (behind bench.py --full's `binary`, `traffic` and `secondary`)
+    read a library they may not write -- a read-only checkout -- and leave its bytes and mtime as they were."""
+    import importlib.util
+    import shutil
+    mods = {}
+    for name in ("codeobj_gate", "resource_usage"):
+        spec = importlib.util.spec_from_file_location(name, REPO / "tools" / f"{name}.py")
+        mods[name] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mods[name])
+    gate = mods["codeobj_gate"]
+    lib = tmp_path / "libamcx.so"
+    shutil.copy2(gate.LIB, lib)
+    os.chmod(lib, 0o444)
+    old_ns = 1_000_000_000 * 1_000_000_000
+    os.utime(lib, ns=(old_ns, old_ns))
+    data = lib.read_bytes()
+    assert gate.digests(lib) == gate.digests(gate.LIB)
+    assert gate.kernel_digests(lib) and mods["resource_usage"].read(lib)
+    assert lib.read_bytes() == data and lib.stat().st_mtime_ns == old_ns
+
+
 def test_replayed_counters_are_bound_to_the_timed_binary(tmp_path):
     """roofline.traffic and roofline.secondary are replays of committed profiles -- and only of profiles TAKEN ON THE
     BINARY THAT IS RUNNING: every summary carries the SHA-256 of the library's gfx950 code object and of the dominant

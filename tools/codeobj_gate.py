@@ -28,7 +28,8 @@ TABLE = REPO / "amcpy_amd" / "csrc" / "codeobj.json"
 def digests(lib) -> dict:
     with tempfile.TemporaryDirectory() as d:
         fat, co, text = Path(d) / "fat.bin", Path(d) / "gfx950.co", Path(d) / "text.bin"
-        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib)], check=True)
+        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib),
+                        str(Path(d) / "lib.copy")], check=True)     # an output file: the library is only read
         subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
         subprocess.run([str(LLVM / "llvm-objcopy"), "-O", "binary", "--only-section=.text", str(co), str(text)], check=True)
@@ -40,7 +41,8 @@ def kernel_digests(lib) -> dict:
     """{demangled kernel / device function name: SHA-256 of its bytes in .text} of the gfx950 code object."""
     with tempfile.TemporaryDirectory() as d:
         fat, co = Path(d) / "fat.bin", Path(d) / "gfx950.co"
-        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib)], check=True)
+        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib),
+                        str(Path(d) / "lib.copy")], check=True)     # an output file: the library is only read
         subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
         sec = subprocess.run([str(LLVM / "llvm-readelf"), "-S", "-W", str(co)], capture_output=True, text=True, check=True).stdout

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Per-section (; MARK) instruction / scratch / barrier counts of the group kernels (N = 16384, 32768) from a -save-temps build.
 set -e
-B=/root/repo/amcpy_amd/csrc/build
+B=$(cd "$(dirname "$0")/.." && pwd)/amcpy_amd/csrc/build
 mkdir -p $B && cd $B
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-math-errno -fno-slp-vectorize $EXTRA \
   -save-temps ../amcx.hip -o $B/libamcx_tmp.so 2> $B/remarks.txt || { grep -E "error" -A5 $B/remarks.txt; exit 1; }

@@ -25,9 +25,11 @@ for line in open('gpurun_out/${TAG}_bench_block_sizes.jsonl'):
     d = json.loads(line); r = d['roofline']
     print(f'N={d[\"config\"][\"frame_size\"]:5d} {d[\"config\"][\"kernel\"]:34s} {d[\"value\"]/1e6:8.2f} M frames/s  frac {r[\"frac\"]:.4f}')" | tee gpurun_out/${TAG}_bench_block_sizes.txt
 timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver_flags.json 2> gpurun_out/${TAG}_bench_driver_flags.err || { tail -5 gpurun_out/${TAG}_bench_driver_flags.err; exit 1; }
-timeout -k 10 400 python3 bench.py > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err || { tail -5 gpurun_out/${TAG}_bench_default.err; exit 1; }
+# the line with every leg (bench.py --full) and its log go to $BENCH_DIR (default bench_results/)
+BENCH_DIR=${BENCH_DIR:-bench_results}; mkdir -p "$BENCH_DIR"
+timeout -k 10 400 python3 bench.py --full > "$BENCH_DIR/${TAG}_bench_default.json" 2> "$BENCH_DIR/${TAG}_bench_default.err" || { tail -5 "$BENCH_DIR/${TAG}_bench_default.err"; exit 1; }
 python3 -c "
-import json; d=json.load(open('gpurun_out/${TAG}_bench_default.json')); r=d['roofline']
+import json; d=json.load(open('$BENCH_DIR/${TAG}_bench_default.json')); r=d['roofline']
 print('default bench:', d['value'], d['ms_per_step'], r['frac'], r['launch_ms_min'], r['launch_ms_median'], r['launch_ms_max'], 'd2h', d['wall_incl_d2h_ms'])
 print('h2d', {k: (v if not isinstance(v, dict) else {kk: vv for kk, vv in v.items() if kk != 'what'}) for k, v in d['h2d'].items() if k != 'what'})
 print('cpu', d['cpu_baseline']['value'], d['cpu_baseline']['cores'], d['cpu_baseline_reference_shaped']['value'])"

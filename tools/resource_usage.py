@@ -34,7 +34,8 @@ def read(lib=None) -> dict:
     lib = Path(lib) if lib else REPO / "amcpy_amd" / "lib" / "libamcx.so"
     with tempfile.TemporaryDirectory() as d:
         fat, co = Path(d) / "fat.bin", Path(d) / "gfx950.co"
-        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib)], check=True)
+        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib),
+                        str(Path(d) / "lib.copy")], check=True)     # an output file: the library is only read
         subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
         notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], capture_output=True, text=True, check=True).stdout

@@ -24,11 +24,11 @@ for N in 1 2 4 8; do
     *) echo "usage: $0 weak|strong|c4" >&2; exit 2 ;;
   esac
   if [ "$N" = 1 ]; then
-    python3 bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-h2d $ARGS
+    python3 bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --full --no-cpu-baseline --no-h2d $ARGS
   elif [ "${LAUNCHER:-self}" = self ]; then
-    python3 bench.py --gpus $N --steps $STEPS --warmup $WARMUP $ARGS
+    python3 bench.py --gpus $N --steps $STEPS --warmup $WARMUP --full $ARGS
   else
     python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT \
-      bench.py --gpus $N --steps $STEPS --warmup $WARMUP $ARGS
+      bench.py --gpus $N --steps $STEPS --warmup $WARMUP --full $ARGS
   fi
 done
