@@ -12,8 +12,10 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 6          # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 7          # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
+# feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
+FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
 VARIANT_AUTO, VARIANT_BLOCK, VARIANT_WAVE = 0, 1, 2
 VARIANTS = {"auto": VARIANT_AUTO, "block": VARIANT_BLOCK, "wave": VARIANT_WAVE}
 OK, EINVAL, ENOTSUP, EHIP, ENODEV, ENOMEM, EIO = 0, -1, -2, -3, -4, -5, -6
@@ -45,6 +47,9 @@ SIGNATURES = {
     "amcx_features18_c64_ex": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32]),
     "amcx_features18_workspace_bytes": (_i64, [_i32, _i64, _i32]),
     "amcx_features18_c64_ws": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _i64]),
+    "amcx_features_c64_subset": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, C.c_uint32, _vp, _i64]),
+    "amcx_kernel_name_subset": (C.c_int, [_i32, _i32, C.c_uint32, C.c_char_p, _i32]),
+    "amcx_ctx_set_feature_mask": (C.c_int, [_vp, C.c_uint32]),
     "amcx_features18_c64_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
     "amcx_features18_c128_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
     "amcx_ctx_create": (C.c_int, [_i32, C.POINTER(_vp)]),
@@ -159,6 +164,27 @@ def kernel_name(frame_size: int, variant: int = VARIANT_AUTO) -> str:
     return buf.value.decode()
 
 
+def feature_mask(feature_ids) -> int:
+    """The mask of a set of feature ids (1 ... 18; repeats allowed).  KeyError for an unknown id, as the reference's
+    calculate_features raises, before anything is launched; ValueError for an empty set."""
+    import numbers
+    mask = 0
+    for fid in feature_ids:
+        if isinstance(fid, bool) or not isinstance(fid, numbers.Integral) or not 1 <= int(fid) <= NUM_FEATURES:
+            raise KeyError(fid)
+        mask |= 1 << (int(fid) - 1)
+    if mask == 0:
+        raise ValueError("feature_ids is empty: at least one feature id (1 ... 18) is needed")
+    return mask
+
+
+def kernel_name_subset(frame_size: int, variant: int, mask: int) -> str:
+    """amcx_kernel_name_subset: the kernel amcx_features_c64_subset runs for this mask (host-only)."""
+    buf = C.create_string_buffer(128)
+    check(load().amcx_kernel_name_subset(int(frame_size), int(variant), int(mask), buf, len(buf)))
+    return buf.value.decode()
+
+
 def numa_place(pci_bus_id: str, sysfs_root: str = "") -> tuple:
     """(node, [cpus]) local to the PCI device ``dddd:bb:dd.f`` according to ``<sysfs_root>/bus/pci/devices`` (default
     /sys): amcx_numa_place.  (-1, []) when the platform does not say.  Host-only: needs no GPU."""
@@ -190,7 +216,15 @@ class HostContext:
     def __init__(self, device: int = 0):
         self._h = C.c_void_p()
         self.device = int(device)
+        self.mask = FEATURES_ALL
         check(load().amcx_ctx_create(self.device, C.byref(self._h)))
+
+    def set_feature_mask(self, mask: int) -> None:
+        """amcx_ctx_set_feature_mask: every later call computes only these features (NaN in the other columns)."""
+        mask = int(mask)
+        if mask != self.mask:
+            check(load().amcx_ctx_set_feature_mask(self._h, mask))
+            self.mask = mask
 
     def run(self, x2, frame_size: int, out, variant: int) -> None:
         """x2: C-contiguous (F, L) complex64 / complex128 ndarray; out: (F, >=18) float32."""

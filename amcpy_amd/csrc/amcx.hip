@@ -374,6 +374,65 @@ int amcx_features18_c64(const void* iq_dev, int64_t n_frames, int32_t frame_size
                                 out_row_stride, hip_stream, AMCX_VARIANT_AUTO);
 }
 
+}  // extern "C"
+
+namespace {
+
+bool valid_feature_mask(uint32_t mask) { return mask != 0 && (mask & ~(uint32_t)AMCX_FEATURES_ALL) == 0; }
+
+// which kernel amcx_features_c64_subset runs (include/amcx.h): a plan kernel where one exists for (frame size, resolved
+// variant), the 18-feature kernel (+ the column mask) otherwise
+int subset_plan(int32_t N, int v, uint32_t mask) {
+  if ((mask & 1u) != 0 || v != AMCX_VARIANT_WAVE) return amcx::kPlanAll;
+  if (!amcx::shortk::short_supports(N) && N != 1024 && N != 2048 && N != 4096) return amcx::kPlanAll;
+  return (mask & ~amcx::kMaskCumulants) == 0 ? amcx::kPlanCumulants : amcx::kPlanNoSpectral;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
+                             float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
+                             void* workspace_dev, int64_t workspace_bytes) {
+  if (!valid_feature_mask(feature_mask)) return AMCX_EINVAL;
+  if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES) return AMCX_EINVAL;
+  const int v = resolve_variant(frame_size, variant);
+  if (v < 0) return v;
+  if (n_frames == 0) return AMCX_OK;
+  if (iq_dev == nullptr || out_dev == nullptr) return AMCX_EINVAL;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const int plan = subset_plan(frame_size, v, feature_mask);
+  if (plan == amcx::kPlanAll) {
+    const int rc = amcx_features18_c64_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride,
+                                          hip_stream, variant, workspace_dev, workspace_bytes);
+    if (rc != AMCX_OK || feature_mask == (uint32_t)AMCX_FEATURES_ALL) return rc;
+    int64_t grid = (n_frames * AMCX_NUM_FEATURES + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(amcx::amcx_mask_columns_kernel, dim3((unsigned)grid), dim3(256), 0, stream, out_dev, (long long)n_frames,
+                       (long long)out_row_stride, (unsigned)feature_mask);
+    AMCX_HIP(hipGetLastError());
+    return AMCX_OK;
+  }
+  if ((reinterpret_cast<uintptr_t>(iq_dev) & 7u) || (reinterpret_cast<uintptr_t>(out_dev) & 3u)) return AMCX_EINVAL;
+  if (on_another_device(iq_dev) || on_another_device(out_dev)) return AMCX_EINVAL;
+  const float2* iq = static_cast<const float2*>(iq_dev);
+  const bool short_n = amcx::shortk::short_supports(frame_size);
+  hipError_t e;
+  if (plan == amcx::kPlanCumulants)
+    e = short_n ? amcx::shortk::launch_short_subset<amcx::kPlanCumulants>(iq, n_frames, frame_size, row_stride_elems, out_dev,
+                                                                         out_row_stride, stream, cu_count(), feature_mask)
+                : amcx::launch_wave_subset<amcx::kPlanCumulants>(iq, n_frames, frame_size, row_stride_elems, out_dev,
+                                                                 out_row_stride, stream, cu_count(), feature_mask);
+  else
+    e = short_n ? amcx::shortk::launch_short_subset<amcx::kPlanNoSpectral>(iq, n_frames, frame_size, row_stride_elems, out_dev,
+                                                                          out_row_stride, stream, cu_count(), feature_mask)
+                : amcx::launch_wave_subset<amcx::kPlanNoSpectral>(iq, n_frames, frame_size, row_stride_elems, out_dev,
+                                                                  out_row_stride, stream, cu_count(), feature_mask);
+  if (e != hipSuccess) return hip_fail(e, "feature-subset kernel launch");
+  return AMCX_OK;
+}
+
 // ---- host-buffer entry points over a reusable context --------------------------------------
 // The context owns two streams, pinned staging slots and device scratch that only ever grow, so a
 // loop of per-frame calls (the reference's usage pattern, features.py:214-232 called once per queue
@@ -410,6 +469,7 @@ struct amcx_ctx {
     const void* pin = nullptr; const void* slab = nullptr; const void* out = nullptr; const void* out_pin = nullptr;
     const void* ws = nullptr;      // the workspace the captured kernel node points into
     size_t slot = 0;
+    uint32_t mask = AMCX_FEATURES_ALL;   // the feature mask the captured kernels were launched for
   };
   SmallGraph graphs[4];
   int graph_next = 0;               // slot the next capture replaces
@@ -418,6 +478,8 @@ struct amcx_ctx {
   // calls in flight on this context (a context serves one call at a time; the counter is there so that
   // amcx_ctx_bind_cpus can refuse to rebuild the staging pool's binding under a running upload)
   std::atomic<int> in_call{0};
+  // amcx_ctx_set_feature_mask: the features every later host-buffer call computes (read once per call)
+  std::atomic<uint32_t> feature_mask{AMCX_FEATURES_ALL};
 };
 
 }  // extern "C"
@@ -446,9 +508,12 @@ void ctx_reserve_ws(amcx_ctx* c, int32_t N, int64_t frames, int32_t variant) {
   if (want > 0 && ctx_reserve(&c->d_ws, &c->ws_cap, (size_t)want) != AMCX_OK) { c->d_ws = nullptr; c->ws_cap = 0; }
 }
 
-int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant) {
+int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant, uint32_t mask) {
   const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
   const bool have = want > 0 && c->d_ws != nullptr && c->ws_cap >= (size_t)want;
+  if (mask != (uint32_t)AMCX_FEATURES_ALL)
+    return amcx_features_c64_subset(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask,
+                                    have ? c->d_ws : nullptr, have ? want : 0);
   return amcx_features18_c64_ws(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, have ? c->d_ws : nullptr,
                                 have ? want : 0);
 }
@@ -526,6 +591,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
     explicit InCall(std::atomic<int>& c) : n(c) { n.fetch_add(1, std::memory_order_acq_rel); }
     ~InCall() { n.fetch_sub(1, std::memory_order_acq_rel); }
   } in_call(c->in_call);
+  const uint32_t mask = c->feature_mask.load(std::memory_order_acquire);
   if (kind < AMCX_SRC_F32_SPLIT) { src.im = nullptr; src.im_off = -1; }
   std::atomic<int> io_error{0};
   src.io_error = &io_error;
@@ -594,7 +660,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
       if (cand.exec && cand.frames == F && cand.frame_size == N && cand.variant == v && cand.c128 == as_c128 &&
           cand.zero_copy == zero_copy &&
           cand.pin == pinned && cand.slab == dev && cand.out == c->d_out && cand.out_pin == c->out_pin && cand.slot == slot &&
-          cand.ws == c->d_ws)
+          cand.ws == c->d_ws && cand.mask == mask)
         g = &cand;
     if (g != nullptr) {
       ++c->graph_hits;
@@ -607,7 +673,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
       int crc = AMCX_OK;
       hipError_t ce = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
       if (ce == hipSuccess && zero_copy) {
-        crc = ctx_features(c, pinned, F, N, c->out_pin, v);
+        crc = ctx_features(c, pinned, F, N, c->out_pin, v, mask);
         const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
         ce = ee;
       } else if (ce == hipSuccess) {
@@ -620,7 +686,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
           ce = hipGetLastError();
           d_rows = rounded;
         }
-        if (ce == hipSuccess) crc = ctx_features(c, d_rows, F, N, c->d_out, v);
+        if (ce == hipSuccess) crc = ctx_features(c, d_rows, F, N, c->d_out, v, mask);
         if (ce == hipSuccess && crc == AMCX_OK)
           ce = hipMemcpyAsync(c->out_pin, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
         const hipError_t ee = hipStreamEndCapture(c->stream, &graph);      // always ends the capture
@@ -637,6 +703,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
         slot_g.zero_copy = zero_copy;
         slot_g.pin = pinned; slot_g.slab = dev; slot_g.out = c->d_out; slot_g.out_pin = c->out_pin; slot_g.slot = slot;
         slot_g.ws = c->d_ws;
+        slot_g.mask = mask;
         c->graph_next = (c->graph_next + 1) % 4;
         g = &slot_g;
       }
@@ -713,7 +780,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
         if (e != hipSuccess) break;
         d_rows = rounded;
       }
-      rc = ctx_features(c, d_rows, take, N, c->d_out + (size_t)u * AMCX_NUM_FEATURES, v);
+      rc = ctx_features(c, d_rows, take, N, c->d_out + (size_t)u * AMCX_NUM_FEATURES, v, mask);
     } else {
       float2* frames = static_cast<float2*>(c->d_frames);
       e = as_c128 ? amcx::launch_pack_planes(reinterpret_cast<const double2*>(dev), (int)take, (long long)F, (long long)F,
@@ -729,7 +796,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
     st.chunks = ch + 1;
   }
   if (rc == AMCX_OK && e == hipSuccess && !rows)
-    rc = ctx_features(c, c->d_frames, F, N, c->d_out, v);
+    rc = ctx_features(c, c->d_frames, F, N, c->d_out, v, mask);
   const double t_tail = wall_now();
   st.seconds_prepare = t_loop - t_start;
   // the result comes back into pinned memory (a copy into the caller's pageable rows would be staged by the
@@ -837,6 +904,17 @@ int amcx_ctx_bind_cpus(amcx_ctx* ctx, const int32_t* cpus, int32_t n_cpus) {
   ctx->bind_cpus = v;
   if (v.empty()) ctx->numa_node = -1;
   ctx->pool.set_cpus(ctx->bind_cpus);
+  return AMCX_OK;
+}
+
+int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask) {
+  if (ctx == nullptr || !valid_feature_mask(feature_mask)) return AMCX_EINVAL;
+  // claim the context: the compare-exchange fails while a call is running on it, and no call can start to count itself in
+  // between a check and the store (a call that starts after the claim reads the mask once, whichever it finds)
+  int idle = 0;
+  if (!ctx->in_call.compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return AMCX_EINVAL;
+  ctx->feature_mask.store(feature_mask, std::memory_order_release);
+  ctx->in_call.fetch_sub(1, std::memory_order_acq_rel);
   return AMCX_OK;
 }
 
@@ -1073,6 +1151,18 @@ int amcx_kernel_name(int32_t frame_size, int32_t variant, char* buf, int32_t buf
                      : block_mode(frame_size) == amcx::kBlockBluesteinBig ? "amcx_features18_block_kernel<3>"
                                                                        : "amcx_features18_block_kernel<0>";
   snprintf(buf, (size_t)buf_len, "%s", name);
+  return AMCX_OK;
+}
+
+int amcx_kernel_name_subset(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len) {
+  if (buf == nullptr || buf_len <= 0 || !valid_feature_mask(feature_mask)) return AMCX_EINVAL;
+  const int v = resolve_variant(frame_size, variant);
+  if (v < 0) return v;
+  const int plan = subset_plan(frame_size, v, feature_mask);
+  if (plan == amcx::kPlanAll) return amcx_kernel_name(frame_size, variant, buf, buf_len);
+  snprintf(buf, (size_t)buf_len, "%s<%d, %d>",
+           amcx::shortk::short_supports(frame_size) ? "amcx_features_subset_short_kernel" : "amcx_features_subset_wave_kernel",
+           (int)frame_size, plan);
   return AMCX_OK;
 }
 

@@ -236,4 +236,17 @@ __global__ __launch_bounds__(kBlockThreads) void amcx_select_fit_scale_kernel(
   }
 }
 
+// amcx_features_c64_subset where no plan kernel exists (frame sizes other than 128 ... 4096, AMCX_VARIANT_BLOCK): the
+// 18-feature kernel has written every column, and this pass sets the ones outside `mask` to NaN in place.  Correct, not
+// faster: the work of the features that were not asked for is done and thrown away.
+__global__ __launch_bounds__(256) void amcx_mask_columns_kernel(float* __restrict__ out, long long n_rows, long long stride,
+                                                                unsigned mask) {
+  const long long n = n_rows * 18;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const long long r = i / 18;
+    const int j = (int)(i - r * 18);
+    if (!((mask >> j) & 1u)) out[r * stride + j] = __builtin_nanf("");
+  }
+}
+
 }  // namespace amcx

@@ -92,6 +92,21 @@
 #define AMCX_PRIO_OF(b) ((AMCX_PRIO_MASK >> (b)) & 1)
 
 namespace amcx {
+
+// Feature plans (include/amcx.h, feature masks).  kPlanAll is the 18-feature kernel; the other two are compiled from the same
+// code with whole sections left out, so that every feature they keep is computed by the same instructions on the same values:
+//   kPlanNoSpectral  no FFT (f1, gamma_max, is the only feature that needs it);
+//   kPlanCumulants   only the 15 moment sums of the statistics sweep -- no angle, no envelope (f10 ... f18).
+constexpr int kPlanAll = 0, kPlanNoSpectral = 1, kPlanCumulants = 2;
+constexpr unsigned kMaskAll = 0x3FFFFu, kMaskCumulants = 0x3FE00u;
+constexpr unsigned kMaskFreq = (1u << 4) | (1u << 8);    // f5, f9: the +-pi tie path
+// a column outside the mask holds NaN
+__device__ __forceinline__ void mask_columns(float (&feat)[18], unsigned mask) {
+#pragma unroll
+  for (int j = 0; j < 18; ++j)
+    if (!((mask >> j) & 1u)) feat[j] = __builtin_nanf("");
+}
+
 namespace wave {
 
 constexpr int kNumSums = 27;                    // reduced per-lane sums; the spectral peak rides in slot 27
@@ -421,6 +436,31 @@ struct StatsT {
     }
     th_b1_prev = th[1];
     rot_prev = rot;
+  }
+
+  // the cumulants plan's row: the 15 moment sums alone, each one updated by the same instructions in the same order as row()
+  __device__ __forceinline__ void moments(float re0, float im0, float re1, float im1) {
+    const float res[2] = {re0, re1}, ims[2] = {im0, im1};
+    static_for<2>([&](auto bb) {
+      constexpr int b = decltype(bb)::value;
+      const float re = res[b], im = ims[b];
+      const float q = __builtin_fmaf(im, im, kTinyPower);
+      const float P = __builtin_fmaf(re, re, q);
+      const float A = __builtin_fmaf(re, re, -q);
+      const float Bh = re * im;
+      const float AA = A * A, BB = Bh * Bh, AP = A * P;
+      const float X4 = __builtin_fmaf(-4.0f, BB, AA);
+      sA += A; sBh += Bh; sP += P; sAA += AA; sX4 += X4; sAP += AP;
+      sAB = __builtin_fmaf(A, Bh, sAB);
+      sBP = __builtin_fmaf(Bh, P, sBP);
+      sAAA = __builtin_fmaf(AA, A, sAAA);
+      sABB = __builtin_fmaf(A, BB, sABB);
+      sAAB = __builtin_fmaf(AA, Bh, sAAB);
+      sBBB = __builtin_fmaf(BB, Bh, sBBB);
+      sAAP = __builtin_fmaf(AA, P, sAAP);
+      sX4P = __builtin_fmaf(X4, P, sX4P);
+      sABP = __builtin_fmaf(AP, Bh, sABP);
+    });
   }
 
   // start a new stretch of the sums; shifts, neighbour angles and the tie tracker carry on
@@ -755,14 +795,22 @@ __device__ __forceinline__ void wave_exact_moments(const float2* __restrict__ sr
 // the same, their layout and registers were not); a flagged frame itself 0.6 frame times.  The rest of what flagged frames
 // cost was IMBALANCE between workgroups (one contiguous slice = one (modulation, SNR) cell: 5 % of noiseless QPSK
 // frames are flagged, none of BPSK's), gone with the interleaved runs of wave_body.
-template <int N>
+// MASKED (the feature-subset kernels): only the columns in `mask` are stored.
+template <int N, bool MASKED = false>
 __device__ __forceinline__ void wave_exact_cumulants(const float2* __restrict__ src, float sc, int h, int lane, bool mine,
-                                                     float* __restrict__ dst_row) {
+                                                     float* __restrict__ dst_row, unsigned mask = kMaskAll) {
   double t[15];
   wave_exact_moments<N>(src, sc, lane, t);
   if (mine) {
-    moment_features(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], (double)N,
-                    [&](int j, int twice_order, double v) { dst_row[j] = (float)__builtin_ldexp(v, h * twice_order); });
+    if constexpr (MASKED) {
+      moment_features(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], (double)N,
+                      [&](int j, int twice_order, double v) {
+                        if ((mask >> j) & 1u) dst_row[j] = (float)__builtin_ldexp(v, h * twice_order);
+                      });
+    } else {
+      moment_features(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], (double)N,
+                      [&](int j, int twice_order, double v) { dst_row[j] = (float)__builtin_ldexp(v, h * twice_order); });
+    }
   }
 }
 
@@ -778,10 +826,12 @@ __device__ __forceinline__ void wave_exact_cumulants(const float2* __restrict__ 
 // here: one launch per step; same box, through the library: +1.3 % at N = 2048, +0.6 % at 1024, +-0 at 4096, +3.0 % /
 // +0.5 % / +1.8 % at 128 / 256 / 512 -- profiles/r4_redo_in_kernel_ab.txt.  A launch boundary costs more than the 8 us of
 // the second kernel: 4 096 persistent waves drain and ramp up twice per step.)
-template <int N>
+// PLAN (kPlanAll: the 18-feature kernel) and `mask`: the feature-subset kernels (amcx_features_subset_wave_kernel below); every
+// section a plan leaves out is left out at compile time, and mask is not read by kPlanAll.
+template <int N, int PLAN = kPlanAll>
 __device__ __forceinline__ void wave_body(
     const float2* __restrict__ iq, long long n_frames, long long row_stride,
-    float* __restrict__ out, long long out_stride AMCX_STAMP_ARG) {
+    float* __restrict__ out, long long out_stride, [[maybe_unused]] unsigned mask AMCX_STAMP_ARG) {
   using C = Cfg<N>;
   constexpr int R = C::kFftRows, ROWS = C::kHeldRows;
   constexpr int kWavesPerWG = C::kWavesPerWG, kThreads = C::kThreads, kTailFrames = C::kTailFrames;
@@ -828,6 +878,7 @@ __device__ __forceinline__ void wave_body(
   };
 
   // ---- twiddle tables, once per workgroup -----------------------------------
+  if constexpr (PLAN == kPlanAll) {
   build_fft_tables<C::kFftN>(t2, t3, tid, kThreads);
   if constexpr (C::kSplit) {
     for (int e = tid; e < 128; e += kThreads) {            // T4[l][b] = W_4096^(2l+b)
@@ -835,6 +886,7 @@ __device__ __forceinline__ void wave_body(
       sincospif((float)e * (1.0f / 2048.0f), &sn, &cs);
       reinterpret_cast<float2*>(t4)[e] = make_float2(cs, -sn);
     }
+  }
   }
   __syncthreads();
 
@@ -970,11 +1022,15 @@ __device__ __forceinline__ void wave_body(
       {
         static_for<ROWS>([&](auto ii) {
           constexpr int i = decltype(ii)::value;
+          if constexpr (PLAN == kPlanCumulants) {
+            S.moments(xr[2 * i], xi[2 * i], xr[2 * i + 1], xi[2 * i + 1]);   // every other sum stays 0
+          } else {
           float a0, a1;
           S.template row<i == 0, i == ROWS - 1>(xr[2 * i], xi[2 * i], xr[2 * i + 1], xi[2 * i + 1], lane, a0, a1);
           if constexpr (!C::kSplit) {
             a_lds[(2 * i) * 64] = a0;
             a_lds[(2 * i + 1) * 64] = a1;
+          }
           }
           if constexpr (C::kFlushes == 2 && i == ROWS / 2 - 1) {
             __builtin_amdgcn_sched_barrier(0);
@@ -990,6 +1046,7 @@ __device__ __forceinline__ void wave_body(
           }
         });
       }
+      if constexpr (PLAN != kPlanCumulants) {
       asm volatile("; MARK envelope");
       __builtin_amdgcn_s_setprio(AMCX_PRIO_OF(1));
       AMCX_STAMP(0);
@@ -1005,6 +1062,7 @@ __device__ __forceinline__ void wave_body(
             S.envelope(a_lds[e * 64], mu);
           }
         });
+      }
       }
 
       // =====================================================================
@@ -1033,8 +1091,9 @@ __device__ __forceinline__ void wave_body(
       }
 
       // =====================================================================
-      // spectral peak
+      // spectral peak (the 18-feature plan only: the others leave slot 27 at the reduction's zero)
       // =====================================================================
+      if constexpr (PLAN == kPlanAll) {
       asm volatile("; MARK fft1");
       AMCX_STAMP(1);
       __builtin_amdgcn_sched_barrier(0);
@@ -1094,6 +1153,7 @@ __device__ __forceinline__ void wave_body(
 
       const float pk = wave_max_l63(peak);
       if (lane == 63) row[kNumSums] = pk;        // overwrites the zero pad slot 27 (LDS ops of a wave are in order)
+      }
     };
 
     // ---- batch finalisation: lane g turns the sums in stash row g into 18 features ----
@@ -1109,6 +1169,38 @@ __device__ __forceinline__ void wave_body(
       [[maybe_unused]] int ex_half = 0;
       float kw_shift = 0.f;
       bool tie = false, cancel = false;
+      // The cumulants plan has no angles, and is_outside_fp32_range tells an all-zero frame (kept) from one of samples too small
+      // for fp32 sums (re-run scaled) by them: a frame with sP <= 2 N kTinyPower -- never on ordinary data -- gets the full
+      // sweep's angle sums here, the wave on one frame at a time, as the 18-feature kernel computed them (an exactly zero std2 /
+      // sab2 is a per-sample property: sums of non-negative terms).
+      [[maybe_unused]] bool flat_angles = true;
+      if constexpr (PLAN == kPlanCumulants && !RG) {
+        bool tiny = false;
+        if (lane < count) {
+          const float* row = stash + (lane * C::kFlushes + (C::kFlushes - 1)) * kStashStride;
+          double sp = row[2];
+          if constexpr (C::kFlushes > 1) {
+#pragma unroll
+            for (int h = 1; h < C::kFlushes; ++h) sp += (double)row[2 - h * kStashStride];
+          }
+          tiny = sp <= 2.0 * (double)N * (double)kTinyPower;
+        }
+        unsigned long long tz = __builtin_amdgcn_ballot_w64(tiny);
+        while (tz != 0) {
+          const int idx = __builtin_ctzll(tz);
+          tz &= tz - 1;
+          float xr[2 * ROWS], xi[2 * ROWS];
+          load_frame(xr, xi, f0 + idx);
+          Stats Z;
+          static_for<ROWS>([&](auto ii) {
+            constexpr int i = decltype(ii)::value;
+            float a0, a1;
+            Z.template row<i == 0, i == ROWS - 1>(xr[2 * i], xi[2 * i], xr[2 * i + 1], xi[2 * i + 1], lane, a0, a1);
+          });
+          const bool flat = __builtin_amdgcn_ballot_w64(Z.st2 != 0.f || Z.sab2 != 0.f) == 0 && Z.Kt == 0.f;
+          if (lane == idx) flat_angles = flat;
+        }
+      }
       if (lane < count) {
         const float* row = stash + (lane * C::kFlushes + (C::kFlushes - 1)) * kStashStride;   // the frame's last row
         auto sm = [&](int k) -> double {           // sum k of the frame: its stash rows added in fp64
@@ -1141,6 +1233,9 @@ __device__ __forceinline__ void wave_body(
         F.gmax_raw = row[27]; F.Kt = row[28]; F.Kw = row[29]; F.Ka = row[30];
         F.pi_tie = row[31] != 0.0f;
         kw_shift = row[29];
+        if constexpr (PLAN == kPlanCumulants && !RG) {
+          if (!flat_angles) F.std2 = 1.0;                    // not an all-zero frame (is_outside_fp32_range: zero_frame)
+        }
         if constexpr (RG) {
           const int code = (int)row[kNumSums + 5];              // (ex + 128) * 64 + index within the block
           const int ex = (code >> 6) - 128;
@@ -1156,6 +1251,10 @@ __device__ __forceinline__ void wave_body(
         cancel = cancel && !redo;
         // flagged by the sweep (f5 came back negated) and neither NaN nor on its way to a re-run
         tie = __builtin_signbitf(feat[4]) && feat[4] == feat[4] && feat[4] != -__builtin_inff() && !redo;
+      }
+      if constexpr (PLAN != kPlanAll) {                         // the slow paths only for features that were asked for
+        if (!(mask & kMaskFreq)) tie = false;
+        if (!(mask & kMaskCumulants)) cancel = false;
       }
       // frames with a phase step within an fp32 rounding of +-pi: f5 and f9 again, the wave on one frame at a time
       unsigned long long ties = __builtin_amdgcn_ballot_w64(tie);
@@ -1173,6 +1272,7 @@ __device__ __forceinline__ void wave_body(
         if (lane == idx) { feat[4] = f5x; feat[8] = f9x; }
       }
       if (lane < count && !redo) {
+        if constexpr (PLAN != kPlanAll) mask_columns(feat, mask);
         float* dst = out + f * out_stride;
 #pragma unroll
         for (int j = 0; j < 18; ++j) dst[j] = feat[j];
@@ -1192,7 +1292,10 @@ __device__ __forceinline__ void wave_body(
           sct = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc), idx));
           hx = __builtin_amdgcn_readlane(ex_half, idx);
         }
-        wave_exact_cumulants<N>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride);
+        if constexpr (PLAN == kPlanAll)
+          wave_exact_cumulants<N>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride);
+        else
+          wave_exact_cumulants<N, true>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride, mask);
       }
       lds_wave_fence();
       return __builtin_amdgcn_ballot_w64(redo);
@@ -1259,11 +1362,23 @@ __global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) vo
     const float2* __restrict__ iq, long long n_frames, long long row_stride,
     float* __restrict__ out, long long out_stride AMCX_STAMP_ARG) {
 #ifdef AMCX_WAVE_STAMPS
-  wave_body<N>(iq, n_frames, row_stride, out, out_stride, stamp_out);
+  wave_body<N>(iq, n_frames, row_stride, out, out_stride, kMaskAll, stamp_out);
 #else
-  wave_body<N>(iq, n_frames, row_stride, out, out_stride);
+  wave_body<N>(iq, n_frames, row_stride, out, out_stride, kMaskAll);
 #endif
 }
+
+#ifndef AMCX_WAVE_STAMPS
+// The feature-subset kernels (amcx_features_c64_subset): PLAN = kPlanNoSpectral or kPlanCumulants; columns outside `mask` hold
+// NaN.  Same work distribution, batches, flush points, reduction tree and finaliser as amcx_features18_wave_kernel<N>, so the
+// columns they keep are bit-identical to it.
+template <int N, int PLAN>
+__global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features_subset_wave_kernel(
+    const float2* __restrict__ iq, long long n_frames, long long row_stride,
+    float* __restrict__ out, long long out_stride, unsigned mask) {
+  wave_body<N, PLAN>(iq, n_frames, row_stride, out, out_stride, mask);
+}
+#endif
 
 }  // namespace wave
 
@@ -1287,10 +1402,13 @@ inline const char* wave_kernel_name(int frame_size) {
 }
 
 #ifndef AMCX_WAVE_STAMPS
-template <int N>
+template <int N, int PLAN = kPlanAll>
 inline hipError_t launch_wave_n(const float2* iq, int64_t n_frames, int64_t row_stride, float* out,
-                                int64_t out_stride, hipStream_t stream, int cus) {
-  auto kern = wave::amcx_features18_wave_kernel<N>;
+                                int64_t out_stride, hipStream_t stream, int cus, unsigned mask = kMaskAll) {
+  constexpr auto kern = [] {
+    if constexpr (PLAN == kPlanAll) return wave::amcx_features18_wave_kernel<N>;
+    else return wave::amcx_features_subset_wave_kernel<N, PLAN>;
+  }();
   constexpr int lds = wave::Cfg<N>::kLdsBytes;
   // > 64 KiB of dynamic LDS needs the attribute; it is per device, so once per (kernel, device)
   static bool lds_attr_set[64] = {};
@@ -1305,9 +1423,25 @@ inline hipError_t launch_wave_n(const float2* iq, int64_t n_frames, int64_t row_
   int64_t grid = (int64_t)cus;                        // persistent: one resident workgroup per CU
   const int64_t min_slice = wave::Cfg<N>::kWavesPerWG;   // at least a frame per wave
   if (grid * min_slice > n_frames) grid = (n_frames + min_slice - 1) / min_slice;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                     (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
+  if constexpr (PLAN == kPlanAll)
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                       (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
+  else
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                       (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask);
   return hipGetLastError();
+}
+
+// the feature-subset kernels of 1024 ... 4096 (PLAN kPlanNoSpectral / kPlanCumulants)
+template <int PLAN>
+inline hipError_t launch_wave_subset(const float2* iq, int64_t n_frames, int32_t frame_size, int64_t row_stride, float* out,
+                                     int64_t out_stride, hipStream_t stream, int cus, unsigned mask) {
+  switch (frame_size) {
+    case 1024: return launch_wave_n<1024, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask);
+    case 2048: return launch_wave_n<2048, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask);
+    case 4096: return launch_wave_n<4096, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask);
+    default: return hipErrorNotSupported;
+  }
 }
 
 inline hipError_t launch_wave(const float2* iq, int64_t n_frames, int32_t frame_size,

@@ -292,8 +292,12 @@ class HipEngine:
     ``stats`` of the last call: frames, seconds, bytes over PCIe, source bytes, chunks, threads."""
 
     def __init__(self, frame_size: int, device: Optional[int] = None, chunk_bytes: int = 32 << 20,
-                 threads: Optional[int] = None, round_on_device: bool = False):
+                 threads: Optional[int] = None, round_on_device: bool = False, feature_ids=None):
         self.N = int(frame_size)
+        # feature_ids: None (all 18) or the ids to compute; the result stays (F, 18), NaN outside the set (KeyError for an
+        # unknown id, here, before anything is launched)
+        self.feature_ids = _feature_ids(feature_ids)
+        self.mask = _lib.FEATURES_ALL if self.feature_ids is None else _lib.feature_mask(self.feature_ids)
         if device is None:
             device = 0
             if _lib.torch_wanted():
@@ -314,6 +318,7 @@ class HipEngine:
         if self._ctx is None:
             self._ctx = _lib.HostContext(self.device)
             self._ctx.configure(self.threads, self.chunk_bytes, int(self.round_on_device))
+            self._ctx.set_feature_mask(self.mask)
         return self._ctx
 
     def _run_block(self, src, base_elems: int, n_snr: int, n_frames: int, strides, out: np.ndarray) -> None:
@@ -393,12 +398,13 @@ class HipEngine:
 _ENGINES = {}
 
 
-def default_engine(frame_size: int, device: Optional[int] = None, threads: Optional[int] = None) -> HipEngine:
+def default_engine(frame_size: int, device: Optional[int] = None, threads: Optional[int] = None,
+                   feature_ids=None) -> HipEngine:
     """The process's engine for (frame_size, device, threads), created on first use and kept: a context is two
     streams, three pinned slots and device scratch (~10 ms to set up, ~8 ms to tear down -- as long as a whole
     BASELINE configs[0] run takes).  :func:`release_engines` frees them."""
-    probe = HipEngine(frame_size, device, threads=threads)
-    key = (probe.N, probe.device, probe.threads)
+    probe = HipEngine(frame_size, device, threads=threads, feature_ids=feature_ids)
+    key = (probe.N, probe.device, probe.threads) + ((probe.mask,) if probe.feature_ids is not None else ())
     eng = _ENGINES.get(key)
     if eng is None:
         eng = _ENGINES[key] = probe
@@ -439,8 +445,12 @@ class DeviceFanOut:
     rows land directly in the result; no process group and no gather are involved.  A device may be listed twice
     (two contexts on it: how the one-GPU test box exercises the path)."""
 
-    def __init__(self, frame_size: int, devices, threads: Optional[int] = None, chunk_bytes: int = 32 << 20):
+    def __init__(self, frame_size: int, devices, threads: Optional[int] = None, chunk_bytes: int = 32 << 20,
+                 feature_ids=None):
         devices = [int(d) for d in devices]
+        feature_ids = _feature_ids(feature_ids)
+        if feature_ids is not None:
+            _lib.feature_mask(feature_ids)                  # KeyError for an unknown id before any device is touched
         if not devices:
             raise ValueError("DeviceFanOut needs at least one device")
         have = _lib.load().amcx_device_count()
@@ -456,7 +466,7 @@ class DeviceFanOut:
         self.engines = []
         try:
             for d, n in zip(devices, per_dev):
-                self.engines.append(HipEngine(frame_size, d, chunk_bytes, threads=n))
+                self.engines.append(HipEngine(frame_size, d, chunk_bytes, threads=n, feature_ids=feature_ids))
         except BaseException:
             for e in self.engines:                          # a later device failed: the earlier ones' contexts, pinned slots
                 e.close()                                   # and staging threads are released, not leaked
@@ -535,13 +545,39 @@ class DeviceFanOut:
             getattr(e, "close", lambda: None)()
 
 
-def default_fanout(frame_size: int, devices, threads: Optional[int] = None) -> DeviceFanOut:
+def default_fanout(frame_size: int, devices, threads: Optional[int] = None, feature_ids=None) -> DeviceFanOut:
     """The process's :class:`DeviceFanOut` for (frame_size, devices, threads), kept like :func:`default_engine`'s."""
-    key = (int(frame_size), tuple(int(d) for d in devices), max(1, int(threads or 8)))
+    ids = _feature_ids(feature_ids)
+    key = (int(frame_size), tuple(int(d) for d in devices), max(1, int(threads or 8))) + \
+        ((_lib.feature_mask(ids),) if ids is not None else ())
     eng = _ENGINES.get(key)
     if eng is None:
-        eng = _ENGINES[key] = DeviceFanOut(frame_size, devices, threads)
+        eng = _ENGINES[key] = DeviceFanOut(frame_size, devices, threads, feature_ids=ids)
     return eng
+
+
+def _feature_ids(feature_ids):
+    """None (all 18) or the sorted distinct ids of a subset; all 18 given explicitly is None too (the 18-feature path)."""
+    if feature_ids is None:
+        return None
+    ids = list(feature_ids)
+    _lib.feature_mask(ids)                                  # KeyError for an unknown id, ValueError for none
+    ids = tuple(sorted({int(f) for f in ids}))
+    return None if ids == tuple(range(1, 19)) else ids
+
+
+def _masked_compute(compute, feature_ids):
+    """An injected engine (tests: a CPU stand-in) under a feature subset: its (F, 18) result with NaN outside the set, the
+    file layout the native engine produces."""
+    if feature_ids is None:
+        return compute
+    drop = np.array([j for j in range(18) if j + 1 not in feature_ids], dtype=np.int64)
+
+    def run(block):
+        mat = np.array(compute(block), dtype=np.float32, copy=True)
+        mat[..., drop] = np.nan
+        return mat
+    return run
 
 
 def _check_container(parsed, cfg: Config):
@@ -557,15 +593,17 @@ def _check_container(parsed, cfg: Config):
 
 
 def extract_modulation(parsed: np.ndarray, cfg: Config, *, compute=None, device: Optional[int] = None,
-                       group=None) -> Optional[np.ndarray]:
+                       group=None, feature_ids=None) -> Optional[np.ndarray]:
     """All 18 features of one modulation's ``(n_snr, n_frames, L)`` array, which every rank
     holds (``run_extraction`` itself decodes on rank 0 only).  Returns float32
-    ``(n_snr, n_frames, 18)`` on rank 0 (None on other ranks)."""
+    ``(n_snr, n_frames, 18)`` on rank 0 (None on other ranks).  ``feature_ids``: only these (NaN in the other columns)."""
+    feature_ids = _feature_ids(feature_ids)
+    compute = None if compute is None else _masked_compute(compute, feature_ids)
     n_snr, n_frames, N = _check_container(parsed, cfg)
     rank, world = _rank_world()
     rows = FrameRows(parsed, n_snr, n_frames)
     if compute is None:
-        engine = HipEngine(N, device, threads=cfg.signals.num_threads)
+        engine = HipEngine(N, device, threads=cfg.signals.num_threads, feature_ids=feature_ids)
         if shard_by_frames(n_snr, n_frames, world):          # frames [k_lo, k_hi) of every snr row (sharding.py)
             k_lo, k_hi = shard_range(n_frames, rank, world)
             local = engine(FrameColumns(parsed, n_snr, n_frames, k_lo, k_hi)) if k_hi > k_lo else \
@@ -580,14 +618,16 @@ def extract_modulation(parsed: np.ndarray, cfg: Config, *, compute=None, device:
 
 
 def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_frames: Optional[int] = None,
-                       compute=None, device: Optional[int] = None) -> np.ndarray:
+                       compute=None, device: Optional[int] = None, feature_ids=None) -> np.ndarray:
     """Features of a raw complex64 sample stream on disk (GNU Radio file sink: interleaved
     float32 I/Q, no header -- what the reference's legacy reader takes with
     ``np.fromfile(..., dtype=np.complex64)`` and a fixed number of leading samples dropped,
     old/read_binary_stream.py:28,48,54-56).  The file is memory-mapped and cut into
     consecutive ``frame_size``-sample frames (a trailing partial frame is dropped); the staging
     threads read the file slot by slot, so it never has to fit in host memory.
-    Returns ``(n_frames, 18)`` float32."""
+    Returns ``(n_frames, 18)`` float32 (``feature_ids``: only these, NaN in the other columns)."""
+    feature_ids = _feature_ids(feature_ids)
+    compute = None if compute is None else _masked_compute(compute, feature_ids)
     if frame_size < 2:
         raise ValueError("frame_size must be >= 2")
     if skip_samples < 0:
@@ -601,7 +641,8 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
     if compute is None:                 # the staging threads read the file themselves, part by part
         stream = FileComplex(path, np.complex64, (1, n_frames, frame_size), 8 * skip_samples, interleaved=True)
         try:
-            return np.asarray(HipEngine(frame_size, device)(FrameRows(stream, 1, n_frames)), dtype=np.float32)
+            return np.asarray(HipEngine(frame_size, device, feature_ids=feature_ids)(FrameRows(stream, 1, n_frames)),
+                              dtype=np.float32)
         finally:
             stream.release()
     frames = np.memmap(path, dtype=np.complex64, mode="r", offset=8 * skip_samples,
@@ -619,14 +660,16 @@ def _pairs_as_complex(block: np.ndarray) -> np.ndarray:
 
 def extract_iq_pairs(dataset, frame_size: Optional[int] = None, *, first_frame: int = 0,
                      max_frames: Optional[int] = None, compute=None, device: Optional[int] = None,
-                     chunk_frames: Optional[int] = None) -> np.ndarray:
+                     chunk_frames: Optional[int] = None, feature_ids=None) -> np.ndarray:
     """Features of frames stored as float32 (I, Q) pairs, ``dataset[f, n] = (I, Q)`` -- RadioML's
     ``(F, 1024, 2)`` layout (reference old/dataset.py:50-56, old/dataset_analysis.py:22).  ``dataset``
     is anything sliceable with ``.shape`` and ``.dtype``.  A numpy array or memmap is re-viewed as
     complex64 and goes up in one native call; any other dataset (an ``h5py.Dataset``, which decodes
     chunks from the file as they are sliced) is read ``chunk_frames`` at a time by a reader thread one
     chunk ahead of the upload, so the set never has to fit in host memory.  Returns ``(n_frames, 18)``
-    float32."""
+    float32 (``feature_ids``: only these, NaN in the other columns)."""
+    feature_ids = _feature_ids(feature_ids)
+    compute = None if compute is None else _masked_compute(compute, feature_ids)
     shape = tuple(dataset.shape)
     if len(shape) != 3 or shape[2] != 2:
         raise ValueError(f"expected an (F, L, 2) dataset of (I, Q) pairs, got shape {shape}")
@@ -649,10 +692,10 @@ def extract_iq_pairs(dataset, frame_size: Optional[int] = None, *, first_frame: 
         # read it themselves, slot by slot (as extract_raw_stream does), and libhdf5 is not on the data path at all
         stream = FileComplex(dataset.file_path, np.complex64, (1, hi - lo, L), dataset.file_offset + lo * L * 8, interleaved=True)
         try:
-            return np.asarray(HipEngine(N, device)(FrameRows(stream, 1, hi - lo)), dtype=np.float32)
+            return np.asarray(HipEngine(N, device, feature_ids=feature_ids)(FrameRows(stream, 1, hi - lo)), dtype=np.float32)
         finally:
             stream.release()
-    engine = HipEngine(N, device)
+    engine = HipEngine(N, device, feature_ids=feature_ids)
     if isinstance(dataset, np.ndarray):
         return engine(_pairs_as_complex(dataset[lo:hi]))
     step = int(chunk_frames or max(1, (256 << 20) // (L * 8)))
@@ -665,7 +708,7 @@ def extract_iq_pairs(dataset, frame_size: Optional[int] = None, *, first_frame: 
 
 def extract_radioml_hdf5(path, *, key: str = "X", frame_size: Optional[int] = None, first_frame: int = 0,
                          max_frames: Optional[int] = None, device: Optional[int] = None, compute=None,
-                         chunk_frames: Optional[int] = None) -> np.ndarray:
+                         chunk_frames: Optional[int] = None, feature_ids=None) -> np.ndarray:
     """``extract_iq_pairs`` on dataset ``key`` of a RadioML-style HDF5 file (``GOLD_XYZ_OSC.0001_1024.hdf5``:
     ``X`` float32 (2 555 904, 1024, 2), reference old/dataset.py:43-56).  The file is opened with the HDF5 C library
     through ``amcpy_amd.hdf5_min`` (ctypes) where one is found, otherwise with ``h5py``, which the reference lists for
@@ -674,7 +717,8 @@ def extract_radioml_hdf5(path, *, key: str = "X", frame_size: Optional[int] = No
     themselves; a chunked or compressed one is decoded by the library ``chunk_frames`` rows at a time on a reader thread
     ahead of the upload.  Neither library there: ImportError that says so."""
     from . import hdf5_min
-    kw = dict(first_frame=first_frame, max_frames=max_frames, device=device, compute=compute, chunk_frames=chunk_frames)
+    kw = dict(first_frame=first_frame, max_frames=max_frames, device=device, compute=compute, chunk_frames=chunk_frames,
+              feature_ids=feature_ids)
     if hdf5_min.available():                      # the C library itself: a contiguous X then bypasses it altogether
         with hdf5_min.File(path) as fh:
             return extract_iq_pairs(fh[key], frame_size, **kw)
@@ -813,7 +857,7 @@ def _placement(world: int, device: Optional[int]) -> bool:
     return len({h for h, _ in where}) == 1
 
 
-def _provenance(cfg: Config, mat_path: Path, key: str) -> dict:
+def _provenance(cfg: Config, mat_path: Path, key: str, feature_ids=None) -> dict:
     """What a feature file was computed FROM and FOR: the shape (n_snr, n_frames, 18) says neither the frame size nor
     which SNR labels or which input container -- a file written for another ``--frame-size``, or for a container that
     has since been replaced, has the right shape and stale numbers."""
@@ -822,9 +866,12 @@ def _provenance(cfg: Config, mat_path: Path, key: str) -> dict:
         src = {"input_size": st.st_size, "input_mtime_ns": st.st_mtime_ns}
     except OSError:
         src = {"input_size": None, "input_mtime_ns": None}
-    return {"frame_size": int(cfg.signals.frame_size), "num_frames": int(cfg.signals.num_frames),
-            "snr_values": [[int(k), str(v)] for k, v in cfg.signals.snr_values.items()],
-            "input": str(Path(mat_path).name), "variable": key, **src}
+    rec = {"frame_size": int(cfg.signals.frame_size), "num_frames": int(cfg.signals.num_frames),
+           "snr_values": [[int(k), str(v)] for k, v in cfg.signals.snr_values.items()],
+           "input": str(Path(mat_path).name), "variable": key, **src}
+    if feature_ids is not None:                             # a subset run only: a full run's record is what it always was
+        rec["features"] = [int(f) for f in feature_ids]
+    return rec
 
 
 def _provenance_path(out_path: Path) -> Path:
@@ -838,7 +885,8 @@ def _already_extracted(out_path: Path, key: str, shape, provenance: Optional[dic
     of ``shape`` (and the ``Modulation`` string) -- only the variable headers are read (``scipy.io.whosmat``) -- AND the
     provenance record written beside it equals ``provenance`` (frame size, SNR labels, frame count, the input
     container's name, size and modification time).  A file that is cut short, was written for another frame size / SNR
-    grid / container, or has no record (written before records existed, or by the reference) does not qualify."""
+    grid / container, or has no record (written before records existed, or by the reference) does not qualify; nor does one
+    computed for a feature subset that does not cover the one asked for (no "features" in a record: all 18)."""
     import json
     import scipy.io
     try:
@@ -850,13 +898,18 @@ def _already_extracted(out_path: Path, key: str, shape, provenance: Optional[dic
             return False
         if provenance is None:
             return True
-        return json.loads(_provenance_path(out_path).read_text()) == provenance
+        # the features: a record without the key holds all 18; a file serves a request whose ids its record covers
+        have = json.loads(_provenance_path(out_path).read_text())
+        want = dict(provenance)
+        have_ids, want_ids = have.pop("features", None), want.pop("features", None)
+        covers = have_ids is None or (want_ids is not None and set(want_ids) <= set(have_ids))
+        return have == want and covers
     except Exception:
         return False
 
 
 def run_extraction(cfg: Config, *, compute=None, device: Optional[int] = None, devices=None,
-                   verbose: bool = True, resume: bool = False) -> None:
+                   verbose: bool = True, resume: bool = False, feature_ids=None) -> None:
     """Drop-in for the reference's ``run_extraction(cfg)``: writes one
     ``{mod}_features.mat`` per entry of ``cfg.signals.modulations_with_noise``.
     ``devices``: several GPU indices driven from THIS process (:class:`DeviceFanOut`; not together with a process
@@ -864,9 +917,14 @@ def run_extraction(cfg: Config, *, compute=None, device: Optional[int] = None, d
     ``resume``: modulations whose feature file is already there, complete, of this configuration's shape AND recorded
     (``{mod}_features.provenance.json`` beside it) as computed for this frame size, these SNR labels and this very input
     container (name, size, modification time) are skipped -- the per-modulation file is the path's natural resume unit (the reference recomputes everything,
-    all-or-nothing per file; a file is written by ONE savemat call at the end of its modulation, here as there)."""
+    all-or-nothing per file; a file is written by ONE savemat call at the end of its modulation, here as there).
+    ``feature_ids``: only these features (KeyError for an unknown id, before anything runs); the files keep the
+    reference's ``(n_snr, n_frames, 18)`` float32 layout with NaN in the other columns, and the record beside each file
+    lists them (``"features"``) -- a full run's record does not change.  ``resume`` trusts a file whose recorded set
+    covers the one asked for."""
     import scipy.io
 
+    feature_ids = _feature_ids(feature_ids)
     rank, world = _rank_world()
     cfg.paths.ensure_dirs()
     mat_path = cfg.paths.mat_data / cfg.paths.mat_filename
@@ -882,11 +940,11 @@ def run_extraction(cfg: Config, *, compute=None, device: Optional[int] = None, d
         if len(devices) == 1:
             device, devices = devices[0], None
     if compute is not None:
-        engine = compute
+        engine = compute = _masked_compute(compute, feature_ids)
     elif devices:
-        engine = default_fanout(N, devices, threads)
+        engine = default_fanout(N, devices, threads, feature_ids)
     else:
-        engine = default_engine(N, device, threads)
+        engine = default_engine(N, device, threads, feature_ids)
     mods = list(cfg.signals.modulations_with_noise)
     if resume:
         todo = mods
@@ -894,7 +952,8 @@ def run_extraction(cfg: Config, *, compute=None, device: Optional[int] = None, d
             shape = (len(cfg.signals.snr_values), cfg.signals.num_frames, 18)
             todo = [m for m in mods if not _already_extracted(cfg.paths.calculated_features / f"{m}_features.mat",
                                                               cfg.signals.mat_info[m], shape,
-                                                              _provenance(cfg, mat_path, cfg.signals.mat_info[m]))]
+                                                              _provenance(cfg, mat_path, cfg.signals.mat_info[m],
+                                                                          feature_ids))]
             if verbose and len(todo) < len(mods):
                 print(f"resume: {len(mods) - len(todo)} of {len(mods)} feature files are complete, computing {todo}")
         if world > 1:                                       # every rank loops over the same modulations
@@ -933,7 +992,7 @@ def run_extraction(cfg: Config, *, compute=None, device: Optional[int] = None, d
     direct = compute is None and os.environ.get("AMCX_DIRECT_FILE", "1") != "0"
     # what each file is computed from, taken BEFORE the container is read: a container replaced mid-run leaves a record
     # that no longer matches it
-    provenance = {m: _provenance(cfg, mat_path, cfg.signals.mat_info[m]) for m in mods}
+    provenance = {m: _provenance(cfg, mat_path, cfg.signals.mat_info[m], feature_ids) for m in mods}
     writer = ThreadPoolExecutor(max_workers=1, thread_name_prefix="amcx-writer") if rank == 0 else None
     writes = []
     published: List[Path] = []          # rank 0: shared files not yet removed

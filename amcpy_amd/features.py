@@ -30,7 +30,12 @@ def _variant(v) -> int:
     return _lib.VARIANTS[v] if isinstance(v, str) else int(v)
 
 
-def features18(iq, out=None, *, frame_size: int | None = None, variant="auto"):
+def _mask(feature_ids):
+    """None (all 18: the 18-feature entry points) or the feature mask of ``feature_ids`` (KeyError for an unknown id)."""
+    return None if feature_ids is None else _lib.feature_mask(feature_ids)
+
+
+def features18(iq, out=None, *, frame_size: int | None = None, variant="auto", feature_ids=None):
     """All 18 features of every frame of a complex64 CUDA(HIP) tensor.
 
     iq   : torch.complex64 tensor on a GPU, shape (..., L) with unit stride in the
@@ -39,10 +44,15 @@ def features18(iq, out=None, *, frame_size: int | None = None, variant="auto"):
            (n_snr, n_frames, L) container).  Only the first ``frame_size``
            samples of each row are used (feature_extraction.py:68).
     out  : optional float32 tensor (..., >=18) on the same device.
+    feature_ids : None (all 18), or the ids (1 ... 18) to compute: amcx_features_c64_subset runs only the work they
+           need; the output stays 18 wide, the columns asked for bit-identical to the full computation and the others
+           NaN.  An unknown id raises ``KeyError`` before anything is launched.
     Returns the float32 tensor (..., 18); the launch is asynchronous on the
     current torch stream.
     """
     import torch
+
+    mask = _mask(feature_ids)
 
     _lib.require_torch_runtime()
     if not isinstance(iq, torch.Tensor) or iq.dtype != torch.complex64:
@@ -84,7 +94,13 @@ def features18(iq, out=None, *, frame_size: int | None = None, variant="auto"):
         # stream-ordered pool, which knows nothing of what torch has cached, and a failed allocation there silently
         # selects the O(N^2) form (~100x slower at N = 32767).  torch raises if it cannot provide the bytes.
         need = int(lib.amcx_features18_workspace_bytes(N, n_frames, v)) if n_frames > 0 else 0
-        if need > 0:
+        if mask is not None:
+            ws = torch.empty(need, dtype=torch.uint8, device=iq.device) if need > 0 else None
+            _lib.check(lib.amcx_features_c64_subset(iq.data_ptr(), n_frames, N, row_stride, oflat.data_ptr(), out_stride,
+                                                    stream, v, mask, None if ws is None else ws.data_ptr(), need))
+            if ws is not None:
+                ws.record_stream(torch.cuda.current_stream(iq.device))
+        elif need > 0:
             ws = torch.empty(need, dtype=torch.uint8, device=iq.device)
             _lib.check(lib.amcx_features18_c64_ws(iq.data_ptr(), n_frames, N, row_stride, oflat.data_ptr(), out_stride,
                                                   stream, v, ws.data_ptr(), need))
@@ -124,11 +140,13 @@ def _host_context(device: int) -> "_lib.HostContext":
 
 
 def features18_host(frames: np.ndarray, *, frame_size: int | None = None, device: int = 0,
-                    variant="auto") -> np.ndarray:
+                    variant="auto", feature_ids=None) -> np.ndarray:
     """numpy (..., L) complex -> numpy (..., 18) float32 via the GPU.
 
     complex128 input (MATLAB doubles) is uploaded as it is and rounded to complex64,
-    the engine's input type, on the GPU.  Raises if no MI355X is present (AMCX_ENODEV)."""
+    the engine's input type, on the GPU.  ``feature_ids``: as :func:`features18` (NaN in the
+    columns not asked for).  Raises if no MI355X is present (AMCX_ENODEV)."""
+    mask = _mask(feature_ids)
     x = np.asarray(frames)
     if not np.iscomplexobj(x):
         x = x.astype(np.complex64)
@@ -143,7 +161,9 @@ def features18_host(frames: np.ndarray, *, frame_size: int | None = None, device
     else:
         x2 = np.ascontiguousarray(x.reshape(-1, L), dtype=np.complex64)
     out = np.empty((x2.shape[0], _lib.NUM_FEATURES), dtype=np.float32)
-    _host_context(int(device)).run(x2, N, out, _variant(variant))
+    ctx = _host_context(int(device))
+    ctx.set_feature_mask(_lib.FEATURES_ALL if mask is None else mask)
+    ctx.run(x2, N, out, _variant(variant))
     return out.reshape(lead + (_lib.NUM_FEATURES,))
 
 
@@ -151,7 +171,9 @@ def calculate_features(feature_ids: Iterable[int], signal, *, device: int = 0,
                        variant="auto") -> List[float]:
     """Drop-in for the reference's ``calculate_features`` (features.py:214-232):
     values in the order of ``feature_ids`` (repeats and subsets allowed); an id
-    outside 1..18 raises ``KeyError`` before anything is launched."""
+    outside 1..18 raises ``KeyError`` before anything is launched.  Only the
+    features asked for are computed (features18_host(feature_ids=...)); the values
+    are bit-identical to those of a full computation."""
     ids = list(feature_ids)
     for fid in ids:
         if fid not in FEATURE_IDS:
@@ -159,5 +181,7 @@ def calculate_features(feature_ids: Iterable[int], signal, *, device: int = 0,
     sig = np.asarray(signal)
     if sig.ndim != 1:
         raise ValueError("signal must be one frame (1-D complex array)")
-    row = features18_host(sig[None, :], device=device, variant=variant)[0]
+    if not ids:
+        return []
+    row = features18_host(sig[None, :], device=device, variant=variant, feature_ids=ids)[0]
     return [float(row[fid - 1]) for fid in ids]

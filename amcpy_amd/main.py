@@ -1,5 +1,5 @@
 """`python -m amcpy_amd extract [--root DIR] [--frame-size N] [--num-frames F] [--snr-values L ...]
-                              [--device D | --devices 0,1,...|all] [--resume]`
+                              [--device D | --devices 0,1,...|all] [--resume] [--features all|used|3,5,...]`
 
 The `extract` sub-command of the reference's CLI (src/amcpy/main.py:32,85-87,
 160-175), and only that one: plot/train/eval/quantize are outside the hot path
@@ -39,7 +39,31 @@ def build_parser() -> argparse.ArgumentParser:
                     help="skip modulations whose {mod}_features.mat is already complete for this configuration")
     ex.add_argument("--devices", default=None, metavar="0,1,...|all",
                     help="several GPUs from this one process, frames cut across them (one engine and host thread each)")
+    ex.add_argument("--features", default="all", metavar="all|used|3,5,...",
+                    help="features to compute (default all).  'used': the columns the reference's preprocess_data and "
+                         "evaluate_by_snr read (FeatureConfig.used + 1); or a comma-separated list of ids 1 ... 18.  The "
+                         "files keep their (n_snr, n_frames, 18) float32 layout with NaN in the other columns; `plot` "
+                         "needs all 18")
     return ap
+
+
+def resolve_features(spec: str, cfg: Config):
+    """--features: None (all 18) or the tuple of ids.  'used' = the columns the reference's preprocess_data and
+    evaluate_by_snr read: FeatureConfig.used is taken there as 0-based column indices, so they are the ids used + 1."""
+    spec = str(spec).strip().lower()
+    if spec == "all":
+        return None
+    if spec == "used":
+        return tuple(sorted({int(c) + 1 for c in cfg.features.used}))
+    try:
+        ids = [int(t) for t in spec.split(",") if t.strip() != ""]
+    except ValueError:
+        raise SystemExit(f"--features {spec!r}: expected all, used or a comma-separated list of ids 1 ... 18")
+    bad = [i for i in ids if not 1 <= i <= 18]
+    if not ids or bad:
+        raise SystemExit(f"--features {spec!r}: expected all, used or a comma-separated list of ids 1 ... 18")
+    ids = tuple(sorted(set(ids)))
+    return None if ids == tuple(range(1, 19)) else ids
 
 
 def _parse_devices(spec: str):
@@ -121,7 +145,8 @@ def _run_as_rank(cfg, args) -> None:
     else:
         dist.init_process_group(backend, store=store, rank=rank, world_size=world)
     try:
-        run_extraction(cfg, device=dev, verbose=rank == 0, resume=args.resume)
+        run_extraction(cfg, device=dev, verbose=rank == 0, resume=args.resume,
+                       feature_ids=resolve_features(args.features, cfg))
     finally:
         dist.destroy_process_group()
 
@@ -154,10 +179,11 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
         if skip_torch:
             _lib.load(skip_torch=True)
         from .feature_extraction import run_extraction
+        ids = resolve_features(args.features, cfg)
         if args.devices is not None:
-            run_extraction(cfg, devices=_parse_devices(args.devices), resume=args.resume)
+            run_extraction(cfg, devices=_parse_devices(args.devices), resume=args.resume, feature_ids=ids)
         else:
-            run_extraction(cfg, device=args.device, resume=args.resume)
+            run_extraction(cfg, device=args.device, resume=args.resume, feature_ids=ids)
     return 0
 
 

@@ -87,9 +87,16 @@ extern "C" {
  * (amcx_probe_fma_rate);
  * 5 = frame sizes 16384 and 32768 (AMCX_MAX_FRAME_SIZE 32768, AMCX_MAX_BLOCK_FRAME_SIZE);
  * 6 = EVERY frame size 2 ... 32768: AMCX_MAX_BLOCK_FRAME_SIZE 32768 (8193 ... 32767 were AMCX_ENOTSUP but for 16384);
- * amcx_features18_c64_ws / amcx_features18_workspace_bytes. */
-#define AMCX_ABI_VERSION 6
+ * amcx_features18_c64_ws / amcx_features18_workspace_bytes;
+ * 7 = feature subsets: AMCX_FEATURES_*, amcx_features_c64_subset, amcx_ctx_set_feature_mask, amcx_kernel_name_subset. */
+#define AMCX_ABI_VERSION 7
 #define AMCX_NUM_FEATURES 18
+
+/* FEATURE MASKS (ABI 7): bit j - 1 stands for feature id j (1 gamma_max ... 18 |C63|).  The reference's default selection,
+ * FeatureConfig.used = (2, 4, 6, 8, 12, 14) read as 0-based columns, is sum(1 << c) = 0x5154 (ids 3, 5, 7, 9, 13, 15). */
+#define AMCX_FEATURES_ALL 0x3FFFF
+#define AMCX_FEATURES_NO_SPECTRAL 0x3FFFE  /* f2 ... f18: everything but gamma_max, the only feature that needs the FFT */
+#define AMCX_FEATURES_CUMULANTS 0x3FE00    /* f10 ... f18: the moment sums alone (no FFT, no angle, no envelope) */
 
 /* error codes */
 #define AMCX_OK 0
@@ -177,6 +184,22 @@ int amcx_features18_c64_ws(const void* iq_dev, int64_t n_frames, int32_t frame_s
                            void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes);
 
 /*
+ * ABI 7.  Only the features in feature_mask (FEATURE MASKS above), same rules and arguments as amcx_features18_c64_ws
+ * (workspace_dev may be NULL).  The output stays 18 wide: a column in the mask holds the feature BIT-IDENTICAL to what
+ * amcx_features18_c64_ws writes for the same frame, frame size and variant; a column outside it holds NaN.  A mask of 0, or
+ * one with a bit at or above bit 18, is AMCX_EINVAL before any HIP call.  The kernel is chosen by the mask:
+ *   bit 0 set (gamma_max asked for)              the 18-feature kernel;
+ *   mask within AMCX_FEATURES_CUMULANTS          the CUMULANTS plan: a streaming reduction of the 15 moment sums;
+ *   otherwise                                    the NO-SPECTRAL plan: the 18-feature kernel without its FFT.
+ * The plans exist for AMCX_VARIANT_WAVE / AUTO at 128 ... 4096 (amcx_kernel_name_subset names them).  Every other frame
+ * size, and AMCX_VARIANT_BLOCK, runs the 18-feature kernel and then a pass that writes NaN outside the mask: correct, no
+ * faster.
+ */
+int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
+                             float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
+                             void* workspace_dev, int64_t workspace_bytes);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -229,6 +252,17 @@ int amcx_ctx_features18_c128_host(amcx_ctx* ctx, const void* iq_host, int64_t n_
  * AMCX_ENOTSUP / AMCX_EINVAL.
  */
 int amcx_kernel_name(int32_t frame_size, int32_t variant, char* buf, int32_t buf_len);
+
+/* ABI 7: the same for amcx_features_c64_subset with this feature_mask (host-only, no GPU needed): a plan kernel
+ * (amcx_features_subset_wave_kernel<N, P> / amcx_features_subset_short_kernel<N, P>, P = 1 no-spectral, 2 cumulants), or
+ * the 18-feature kernel amcx_kernel_name names (followed by amcx_mask_columns_kernel unless the mask is
+ * AMCX_FEATURES_ALL).  AMCX_EINVAL for an invalid mask. */
+int amcx_kernel_name_subset(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len);
+
+/* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
+ * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
+ * default, the 18-feature path).  AMCX_EINVAL for an invalid mask or while a call is running on the context. */
+int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask);
 
 /*
  * The real-data path: all 18 features of every frame of a HOST container indexed
