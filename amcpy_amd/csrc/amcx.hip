@@ -7,7 +7,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
+#include <mutex>
 #include <new>
+#include <vector>
 
 #include "amcx_block_kernel.h"
 #include "amcx_stream_kernel.h"
@@ -63,6 +65,64 @@ int cu_count() {
   }
   if (dev >= 0 && dev < 64) cus[dev] = n;
   return n;
+}
+
+// ---- rings of stash rows (amcx_wave_kernel.h, wave_body RING) ---------------------------------------
+// A launch of a wave kernel that finalises 64 frames per wave at a time parks its stash rows in a ring in global memory
+// (amcx::wave_ring_bytes).  Two launches that may overlap must never share one.  A context owns its ring (amcx_ctx::d_ring:
+// its launches all go to its own stream).  The context-free entries take theirs from this pool, keyed by (device, stream):
+// launches on one stream run one after the other.  A ring is allocated on the first call of a stream and kept; finding it
+// later is a short list under a mutex.  No ring -- nullptr, and the launch runs the kernel's LDS form, same results -- for
+//   * a stream that is being captured: the graph may be replayed on any stream, beside an eager launch on this one;
+//   * hipStreamPerThread: one handle, a different stream in every thread;
+//   * a full pool or a failed allocation;
+//   * a process started with AMCX_WAVE_RING=0.
+struct RingSource {
+  float* own = nullptr;     // the caller's ring (a context's), of own_bytes
+  size_t own_bytes = 0;
+  bool pool = false;        // none of its own: take one from the pool
+};
+struct PoolRing { int device; hipStream_t stream; void* p; size_t bytes; };
+std::mutex g_ring_mu;
+std::vector<PoolRing> g_rings;
+constexpr size_t kPoolRingsPerDevice = 16;
+
+float* pool_ring(hipStream_t stream, size_t bytes) {
+  if (stream == hipStreamPerThread) return nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  if (cap != hipStreamCaptureStatusNone) return nullptr;
+  std::lock_guard<std::mutex> lock(g_ring_mu);
+  size_t on_dev = 0;
+  for (PoolRing& r : g_rings) {
+    if (r.device != dev) continue;
+    ++on_dev;
+    if (r.stream != stream) continue;
+    if (r.bytes >= bytes) return static_cast<float*>(r.p);
+    (void)hipFree(r.p);                        // (waits for the device: nothing still runs on the old one)
+    r.p = nullptr; r.bytes = 0;
+    if (hipMalloc(&r.p, bytes) != hipSuccess) { (void)hipGetLastError(); r.p = nullptr; return nullptr; }
+    r.bytes = bytes;
+    return static_cast<float*>(r.p);
+  }
+  if (on_dev >= kPoolRingsPerDevice) return nullptr;
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  g_rings.push_back(PoolRing{dev, stream, p, bytes});
+  return static_cast<float*>(p);
+}
+
+// the ring for one launch of frame size N on `stream`, or nullptr
+float* ring_for(const RingSource& rs, int32_t N, hipStream_t stream) {
+  // AMCX_WAVE_RING=0 (read once per process): no rings, every launch runs the LDS form -- for tests and A/B runs
+  static const bool off = [] { const char* t = getenv("AMCX_WAVE_RING"); return t != nullptr && t[0] == '0'; }();
+  if (off) return nullptr;
+  const size_t need = amcx::wave_ring_bytes(N, cu_count());
+  if (need == 0) return nullptr;
+  if (rs.own != nullptr) return rs.own_bytes >= need ? rs.own : nullptr;
+  return rs.pool ? pool_ring(stream, need) : nullptr;
 }
 
 // include/amcx.h, DEVICE OWNERSHIP: a device pointer must live on the current device.  Pointers the
@@ -245,6 +305,11 @@ __global__ __launch_bounds__(256) void amcx_probe_read_kernel(const float4* __re
   if (threadIdx.x == 0) partial[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
 }
 
+
+int features18_ws(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems, float* out_dev,
+                  int64_t out_row_stride, void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes,
+                  const RingSource& rings);
+
 }  // namespace
 
 extern "C" {
@@ -291,6 +356,19 @@ int64_t amcx_features18_workspace_bytes(int32_t frame_size, int64_t n_frames, in
 int amcx_features18_c64_ws(const void* iq_dev, int64_t n_frames, int32_t frame_size,
                            int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
                            void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes) {
+  RingSource rings;
+  rings.pool = true;
+  return features18_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
+                       workspace_dev, workspace_bytes, rings);
+}
+
+}  // extern "C"
+
+namespace {
+
+int features18_ws(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems, float* out_dev,
+                  int64_t out_row_stride, void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes,
+                  const RingSource& rings) {
   if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES)
     return AMCX_EINVAL;
   const int v = resolve_variant(frame_size, variant);
@@ -315,7 +393,8 @@ int amcx_features18_c64_ws(const void* iq_dev, int64_t n_frames, int32_t frame_s
     else if (amcx::shortk::short_supports(frame_size))       // 128, 256, 512: four frames per wave (amcx_short_kernel.h)
       e = amcx::shortk::launch_short(iq, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, stream, cu_count());
     else
-      e = amcx::launch_wave(iq, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, stream, cu_count());
+      e = amcx::launch_wave(iq, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, stream, cu_count(),
+                            ring_for(rings, frame_size, stream));
     if (e != hipSuccess) return hip_fail(e, "wave kernel launch");
     // every throughput kernel (N = 128 ... 4096 one wave per frame, N = 8192 the quad, 16384 / 32768 the group) has re-run the frames outside its
     // fp32 sums' range itself -- one launch, rows final -- and finished frames with a phase step within an angle rounding
@@ -326,6 +405,10 @@ int amcx_features18_c64_ws(const void* iq_dev, int64_t n_frames, int32_t frame_s
   return launch_block(iq, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, stream, workspace_dev,
                       workspace_bytes < 0 ? 0 : workspace_bytes);
 }
+
+}  // namespace
+
+extern "C" {
 
 int amcx_features18_c64_ex(const void* iq_dev, int64_t n_frames, int32_t frame_size,
                            int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
@@ -388,13 +471,9 @@ int subset_plan(int32_t N, int v, uint32_t mask) {
   return (mask & ~amcx::kMaskCumulants) == 0 ? amcx::kPlanCumulants : amcx::kPlanNoSpectral;
 }
 
-}  // namespace
-
-extern "C" {
-
-int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
-                             float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
-                             void* workspace_dev, int64_t workspace_bytes) {
+int features_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
+                    float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
+                    void* workspace_dev, int64_t workspace_bytes, const RingSource& rings) {
   if (!valid_feature_mask(feature_mask)) return AMCX_EINVAL;
   if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES) return AMCX_EINVAL;
   const int v = resolve_variant(frame_size, variant);
@@ -404,8 +483,8 @@ int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   const int plan = subset_plan(frame_size, v, feature_mask);
   if (plan == amcx::kPlanAll) {
-    const int rc = amcx_features18_c64_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride,
-                                          hip_stream, variant, workspace_dev, workspace_bytes);
+    const int rc = features18_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride,
+                                 hip_stream, variant, workspace_dev, workspace_bytes, rings);
     if (rc != AMCX_OK || feature_mask == (uint32_t)AMCX_FEATURES_ALL) return rc;
     int64_t grid = (n_frames * AMCX_NUM_FEATURES + 255) / 256;
     if (grid > 8192) grid = 8192;
@@ -418,19 +497,33 @@ int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame
   if (on_another_device(iq_dev) || on_another_device(out_dev)) return AMCX_EINVAL;
   const float2* iq = static_cast<const float2*>(iq_dev);
   const bool short_n = amcx::shortk::short_supports(frame_size);
+  float* const ring = short_n ? nullptr : ring_for(rings, frame_size, stream);
   hipError_t e;
   if (plan == amcx::kPlanCumulants)
     e = short_n ? amcx::shortk::launch_short_subset<amcx::kPlanCumulants>(iq, n_frames, frame_size, row_stride_elems, out_dev,
                                                                          out_row_stride, stream, cu_count(), feature_mask)
                 : amcx::launch_wave_subset<amcx::kPlanCumulants>(iq, n_frames, frame_size, row_stride_elems, out_dev,
-                                                                 out_row_stride, stream, cu_count(), feature_mask);
+                                                                 out_row_stride, stream, cu_count(), ring, feature_mask);
   else
     e = short_n ? amcx::shortk::launch_short_subset<amcx::kPlanNoSpectral>(iq, n_frames, frame_size, row_stride_elems, out_dev,
                                                                           out_row_stride, stream, cu_count(), feature_mask)
                 : amcx::launch_wave_subset<amcx::kPlanNoSpectral>(iq, n_frames, frame_size, row_stride_elems, out_dev,
-                                                                  out_row_stride, stream, cu_count(), feature_mask);
+                                                                  out_row_stride, stream, cu_count(), ring, feature_mask);
   if (e != hipSuccess) return hip_fail(e, "feature-subset kernel launch");
   return AMCX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
+                             float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
+                             void* workspace_dev, int64_t workspace_bytes) {
+  RingSource rings;
+  rings.pool = true;
+  return features_subset(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
+                         feature_mask, workspace_dev, workspace_bytes, rings);
 }
 
 // ---- host-buffer entry points over a reusable context --------------------------------------
@@ -452,6 +545,7 @@ struct amcx_ctx {
   void* d_slab = nullptr;  size_t slab_cap = 0;  // 2 x slot: uploaded chunks
   void* d_frames = nullptr; size_t frames_cap = 0;   // plane-major sources: the frame-major complex64 image
   void* d_ws = nullptr; size_t ws_cap = 0;           // the any-size path's FFT workspace (frame sizes above 8192, amcx_features18_c64_ws)
+  void* d_ring = nullptr; size_t ring_cap = 0;       // the wave kernels' ring of stash rows (RingSource): this context's launches only
   hipEvent_t up_done[3] = {nullptr, nullptr, nullptr};
   hipEvent_t slab_free[2] = {nullptr, nullptr};
   float* out_pin = nullptr; size_t out_pin_cap = 0;   // the result lands in pinned memory first
@@ -506,16 +600,23 @@ int ctx_reserve(void** p, size_t* cap, size_t bytes) {
 void ctx_reserve_ws(amcx_ctx* c, int32_t N, int64_t frames, int32_t variant) {
   const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
   if (want > 0 && ctx_reserve(&c->d_ws, &c->ws_cap, (size_t)want) != AMCX_OK) { c->d_ws = nullptr; c->ws_cap = 0; }
+  // likewise the ring of the wave kernels that take one; without it they run their LDS form
+  // (one size per device, whatever the call's frame count: never reallocated, so the ring a captured graph points into stays)
+  const size_t ring = resolve_variant(N, variant) == AMCX_VARIANT_WAVE ? amcx::wave_ring_bytes(N, cu_count()) : 0;
+  if (ring > 0 && ctx_reserve(&c->d_ring, &c->ring_cap, ring) != AMCX_OK) { c->d_ring = nullptr; c->ring_cap = 0; }
 }
 
 int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant, uint32_t mask) {
   const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
   const bool have = want > 0 && c->d_ws != nullptr && c->ws_cap >= (size_t)want;
+  RingSource rings;
+  rings.own = static_cast<float*>(c->d_ring);
+  rings.own_bytes = c->ring_cap;
   if (mask != (uint32_t)AMCX_FEATURES_ALL)
-    return amcx_features_c64_subset(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask,
-                                    have ? c->d_ws : nullptr, have ? want : 0);
-  return amcx_features18_c64_ws(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, have ? c->d_ws : nullptr,
-                                have ? want : 0);
+    return features_subset(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask,
+                           have ? c->d_ws : nullptr, have ? want : 0, rings);
+  return features18_ws(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, have ? c->d_ws : nullptr,
+                       have ? want : 0, rings);
 }
 
 struct DeviceGuard {
@@ -968,6 +1069,7 @@ int amcx_ctx_destroy(amcx_ctx* c) {
   if (c->d_slab) (void)hipFree(c->d_slab);
   if (c->d_frames) (void)hipFree(c->d_frames);
   if (c->d_ws) (void)hipFree(c->d_ws);
+  if (c->d_ring) (void)hipFree(c->d_ring);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->out_pin) (void)hipHostFree(c->out_pin);
   for (auto& g : c->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);

@@ -18,7 +18,8 @@
 //     64 samples' value); the envelope alone needs a second sweep over |x|,
 //     because f4 needs mean|a - mu| with the exact mu;
 //   * the fp64 scalar algebra that turns 27 sums into 18 features runs once
-//     per batch of kFramesPerWave frames with one frame per lane.
+//     per batch with one frame per lane: kFramesPerWave frames from the LDS stash, or, at N = 2048,
+//     kFinaliseFrames = 64 from a ring of stash rows in global memory (THE RING, below).
 //
 // Index maps (verified against np.fft.fft with the LDS bank rules in
 // tools/wave_fft_model.py).  A frame is ROWS = N/128 rows of 128 samples:
@@ -62,6 +63,29 @@
 // landed 2,2,1,1 on the SIMDs, profiles/r1a.)  LDS per workgroup at N = 2048:
 // factor tables 1920 + 14336 B, 16 x 8672 B exchange, 16 x 528 B stash = 159.6 KB.
 // Algorithmic HBM bytes per frame: 8*N read + 72 written.
+//
+// THE RING (N = 2048).  Four frames per batch is not a tuned number: it is what 160 KB of LDS leave for the stash once
+// sixteen waves have their exchange buffers.  The finaliser's instruction stream -- 473 VALU instructions, about 250 of them
+// fp64, when no frame is flagged -- then ran once per four frames with 4 of 64 lanes active: 118 instructions per frame,
+// 7.3 % of a wave's cycles in the stamped build (profiles/r8_finaliser_share.txt).  The stash cannot grow in LDS, so the
+// product kernel parks its rows in global memory instead: every wave of the grid owns kFinaliseFrames x kFlushes rows of
+// kStashStride floats (4 096 waves x 64 x 132 B = 34.6 MB), writes a frame's row where it wrote the LDS row -- store_sums and
+// lane 63's scalars, ordinary vector stores -- and, when 64 rows are full or its work is exhausted, finalises them one per
+// lane: 31 sums and scalars per lane loaded together ahead of the algebra, behind a release / acquire fence.  A wave reads
+// only what it wrote itself, in program order: no atomics, no traffic between waves, no barrier.  (The ring does not stay in
+// L2 -- 4.3 MB per XCD against 4 MB with the frames streaming through: the rows go out and come back, HBM traffic 1.007 ->
+// 1.023 x the algorithmic bytes, profiles/r8_finaliser64_pmc.json.)  A wave still takes its frames in runs of kRunFrames = 4
+// (the work distribution is unchanged), so lane g's frame is no longer f0 + g: a row carries its frame's index as two words
+// of bits (slot 32, and slot 31 above the tie flag).  Per-frame arithmetic is untouched and every row is bit-identical.
+// The slow paths run behind the batch that flagged the frame as before; the re-run of out-of-range frames keeps its four
+// LDS stash rows, so the workgroup's LDS is what it was.  Registers: 128 VGPRs, three spilled dwords, 16 B of scratch, one
+// reload per frame in the frame loop (the parent: four, 20 B, two) -- with the |x| parking address formed per frame in this
+// form (wave_body, a_park), which the allocator otherwise spills and reloads at the top of the frame.
+// Who owns a ring is the launch code's matter (amcx.hip, RingSource): two launches that may overlap never share one.  A
+// launch that has none runs amcx_features18_wave_lds_kernel<2048>, the same body with RING = false: the four-frame LDS form,
+// instruction for instruction the kernel of before, same results.  Same box, alternating, through the library:
+// +2.5 % frames/s (profiles/r8_finaliser64_ab.txt); -112 VALU instructions per frame (profiles/r8_finaliser64_pmc.json).
+// N = 1024 and N = 4096 keep their batches of eight from LDS (Cfg<N>::kFinaliseFrames = kFramesPerWave): not tried yet.
 #pragma once
 
 #include <type_traits>
@@ -132,6 +156,11 @@ struct Cfg {
   // moves the worst scaled error of the N = 4096 sweep from 5.8e-6 to 6.9e-6
   static constexpr int kFlushes = N == 4096 ? 2 : 1;
   static constexpr int kStashBytes = kFramesPerWave * kFlushes * kStashStride * 4;
+  // frames finalised together, one per lane, where the launch has a ring of stash rows in global memory (wave_body, RING):
+  // the wave still takes its frames in runs of kRunFrames, and the LDS stash keeps its kFramesPerWave rows for the re-runs
+  static constexpr int kFinaliseFrames = N == 2048 ? 64 : kFramesPerWave;
+  static constexpr bool kHasRing = kFinaliseFrames > kFramesPerWave;
+  static constexpr int kRingFloatsPerWave = kFinaliseFrames * kFlushes * kStashStride;
   // frames per grab over the last stretch of a workgroup's slice (levels the waves' finish)
   static constexpr int kTailChunk = 2;
   // frames per interleaved run of a workgroup (wave_body: work distribution)
@@ -161,7 +190,8 @@ struct Cfg {
   static_assert(kLdsBytes <= 163840, "one workgroup per CU must fit in 160 KiB of LDS");
   // the envelope's second sweep reads |x| back from the exchange buffer, or, when the frame is too
   // large to park there, takes the square roots again from the registers
-  static_assert(kFramesPerWave <= 64, "one frame per lane in the finaliser");
+  static_assert(kFramesPerWave <= 64 && kFinaliseFrames <= 64, "one frame per lane in the finaliser");
+  static_assert(kFinaliseFrames % kFramesPerWave == 0, "a batch is whole runs");
   static_assert(kSplit || 2 * kRows * 64 * 4 <= kExchangeBytes, "|x| parking must fit the exchange buffer");
 };
 
@@ -828,11 +858,12 @@ __device__ __forceinline__ void wave_exact_cumulants(const float2* __restrict__ 
 // the second kernel: 4 096 persistent waves drain and ramp up twice per step.)
 // PLAN (kPlanAll: the 18-feature kernel) and `mask`: the feature-subset kernels (amcx_features_subset_wave_kernel below); every
 // section a plan leaves out is left out at compile time, and mask is not read by kPlanAll.
-template <int N, int PLAN = kPlanAll>
+template <int N, int PLAN = kPlanAll, bool RING = Cfg<N>::kHasRing>
 __device__ __forceinline__ void wave_body(
     const float2* __restrict__ iq, long long n_frames, long long row_stride,
-    float* __restrict__ out, long long out_stride, [[maybe_unused]] unsigned mask AMCX_STAMP_ARG) {
+    float* __restrict__ out, long long out_stride, [[maybe_unused]] unsigned mask, [[maybe_unused]] float* ring AMCX_STAMP_ARG) {
   using C = Cfg<N>;
+  static_assert(!RING || C::kHasRing, "no ring form at this frame size");
   constexpr int R = C::kFftRows, ROWS = C::kHeldRows;
   constexpr int kWavesPerWG = C::kWavesPerWG, kThreads = C::kThreads, kTailFrames = C::kTailFrames;
   constexpr int kFramesPerWave = C::kFramesPerWave, kTailChunk = C::kTailChunk;
@@ -847,6 +878,13 @@ __device__ __forceinline__ void wave_body(
   char* ex = smem + C::kTableBytes + wave * kExchangeBytes;
   float* stash = reinterpret_cast<float*>(smem + C::kTableBytes + kWavesPerWG * kExchangeBytes) +
                  wave * (kFramesPerWave * C::kFlushes * kStashStride);
+  // RING: this wave's kFinaliseFrames x kFlushes stash rows in global memory.  Only this wave writes and reads them, in
+  // program order, so they need no atomics and live in L2.
+  constexpr int kBatch = RING ? C::kFinaliseFrames : kFramesPerWave;
+  [[maybe_unused]] float* ring_w = nullptr;
+  if constexpr (RING) ring_w = ring + ((long long)blockIdx.x * kWavesPerWG + wave) * (long long)C::kRingFloatsPerWave;
+  [[maybe_unused]] int filled = 0;            // RING: rows of the ring that hold a frame
+  [[maybe_unused]] long long batch_f = 0;     // RING: lane g's frame of the batch finalised last
 
   // ---- work distribution ------------------------------------------------------
   // The frames are cut into runs of kRunFrames; workgroup w owns runs w, w + G, w + 2 G, ... (G workgroups) and its
@@ -924,10 +962,19 @@ __device__ __forceinline__ void wave_body(
         if (lane == 0) t = __hip_atomic_fetch_add(&counters[1], (unsigned)kTailChunk, __ATOMIC_RELAXED,
                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
         t = __builtin_amdgcn_readfirstlane(t);
-        if ((long long)t >= tail_len) break;
-        f0 = frame_of(body_len + t);
-        const long long left = tail_len - t;
-        n_here = left < kTailChunk ? (int)left : kTailChunk;
+        if constexpr (!RING) {
+          if ((long long)t >= tail_len) break;
+          f0 = frame_of(body_len + t);
+          const long long left = tail_len - t;
+          n_here = left < kTailChunk ? (int)left : kTailChunk;
+        } else if ((long long)t >= tail_len) {
+          f0 = 0;
+          n_here = 0;                              // finalise what the ring still holds, then leave
+        } else {
+          f0 = frame_of(body_len + t);
+          const long long left = tail_len - t;
+          n_here = left < kTailChunk ? (int)left : kTailChunk;
+        }
       }
     }
 
@@ -943,8 +990,27 @@ __device__ __forceinline__ void wave_body(
         xr[2 * i] = v.x; xi[2 * i] = v.y; xr[2 * i + 1] = v.z; xi[2 * i + 1] = v.w;
       });
     };
-    // one frame, registers -> stash row g
-    auto frame = [&](const float (&xr)[2 * ROWS], const float (&xi)[2 * ROWS], int g) {
+    // one frame, registers -> stash row g: of the LDS stash, or (to_ring) of the wave's ring, where the row also carries
+    // the frame's index `fidx`: a batch of the ring is sixteen runs, not f0 + lane
+    auto frame = [&](const float (&xr)[2 * ROWS], const float (&xi)[2 * ROWS], int g, [[maybe_unused]] long long fidx,
+                     auto to_ring) {
+      constexpr bool TO_RING = decltype(to_ring)::value;
+      float* const rows = [&]() -> float* {
+        if constexpr (TO_RING) return ring_w;
+        else return stash;
+      }();
+      // RING: the |x| parking address formed here, per frame (the lane index through an empty asm, as in store_sums): kept in a
+      // register across the loop it is the value the allocator spills, and reloads at the top of the frame behind the
+      // frame's own loads
+      float* const a_park = [&]() -> float* {
+        if constexpr (RING) {
+          int ln = lane;
+          asm volatile("" : "+v"(ln));
+          return reinterpret_cast<float*>(ex) + ln;
+        } else {
+          return a_lds;
+        }
+      }();
       asm volatile("; MARK load");
       __builtin_amdgcn_s_setprio(AMCX_PRIO_OF(0));
       AMCX_STAMP(7);
@@ -1028,8 +1094,8 @@ __device__ __forceinline__ void wave_body(
           float a0, a1;
           S.template row<i == 0, i == ROWS - 1>(xr[2 * i], xi[2 * i], xr[2 * i + 1], xi[2 * i + 1], lane, a0, a1);
           if constexpr (!C::kSplit) {
-            a_lds[(2 * i) * 64] = a0;
-            a_lds[(2 * i + 1) * 64] = a1;
+            a_park[(2 * i) * 64] = a0;
+            a_park[(2 * i + 1) * 64] = a1;
           }
           }
           if constexpr (C::kFlushes == 2 && i == ROWS / 2 - 1) {
@@ -1040,7 +1106,7 @@ __device__ __forceinline__ void wave_body(
                              S.st1, S.st2, S.sab1, S.sab2, S.sw1, S.sw2, S.sw3, S.sw4, 0.f};
             float q7[7];
             reduce_sums(r28, q7);
-            store_sums(q7, stash + (g * C::kFlushes) * kStashStride);
+            store_sums(q7, rows + (g * C::kFlushes) * kStashStride);
             S.clear_sums();
             __builtin_amdgcn_sched_barrier(0);
           }
@@ -1059,7 +1125,7 @@ __device__ __forceinline__ void wave_body(
           if constexpr (C::kSplit) {
             S.envelope(__builtin_amdgcn_sqrtf(__builtin_fmaf(xr[e], xr[e], __builtin_fmaf(xi[e], xi[e], kTinyPower))), mu);
           } else {
-            S.envelope(a_lds[e * 64], mu);
+            S.envelope(a_park[e * 64], mu);
           }
         });
       }
@@ -1073,7 +1139,7 @@ __device__ __forceinline__ void wave_body(
       __builtin_amdgcn_s_setprio(AMCX_PRIO_OF(2));
       AMCX_STAMP(3);
       __builtin_amdgcn_sched_barrier(0);
-      float* const row = stash + (g * C::kFlushes + (C::kFlushes - 1)) * kStashStride;   // the frame's last row
+      float* const row = rows + (g * C::kFlushes + (C::kFlushes - 1)) * kStashStride;   // the frame's last row
       float r7[7];
       {
         float r28[28] = {S.sA, S.sBh, S.sP, S.sAA, S.sX4, S.sAB, S.sAP, S.sBP, S.sAAA, S.sABB,
@@ -1087,7 +1153,14 @@ __device__ __forceinline__ void wave_body(
         row[kNumSums + 1] = S.Kt;
         row[kNumSums + 2] = S.Kw;
         row[kNumSums + 3] = S.Ka;
-        row[kNumSums + 4] = tie != 0 ? 1.0f : 0.0f;
+        if constexpr (TO_RING) {
+          // two words of bits, not float values (frame counts pass 2^24): the tie flag rides in bit 0 of the upper one
+          const unsigned long long fu = (unsigned long long)fidx;
+          row[kNumSums + 4] = __builtin_bit_cast(float, ((unsigned)(fu >> 32) << 1) | (tie != 0 ? 1u : 0u));
+          row[kNumSums + 5] = __builtin_bit_cast(float, (unsigned)fu);
+        } else {
+          row[kNumSums + 4] = tie != 0 ? 1.0f : 0.0f;
+        }
       }
 
       // =====================================================================
@@ -1159,12 +1232,50 @@ __device__ __forceinline__ void wave_body(
     // ---- batch finalisation: lane g turns the sums in stash row g into 18 features ----
     // range_tag true: the rows are those of frames re-run on a pre-scaled copy (rerun_scaled below).
     // Returns the lanes whose frame is outside the fp32 sums' range and has NOT been stored.
+    // RING: the batch's rows are read from the wave's ring (FROM_RING), those of re-run frames from the LDS stash as ever.
     auto finalise = [&](auto range_tag, int count) -> unsigned long long {
       constexpr bool RG = decltype(range_tag)::value;
+      constexpr bool FROM_RING = RING && !RG;
       bool redo = false;
       lds_wave_fence();
+      // the frame's last row of this lane
+      auto lane_row = [&]() -> const float* {
+        if constexpr (RING) {
+          // (the lane index through an empty asm, as in store_sums: the address is formed here and not spilled in the prologue)
+          int ln = lane;
+          asm volatile("" : "+v"(ln));
+          if constexpr (FROM_RING) return ring_w + (ln * C::kFlushes + (C::kFlushes - 1)) * kStashStride;
+          else return stash + (ln * C::kFlushes + (C::kFlushes - 1)) * kStashStride;
+        } else {
+          return stash + (lane * C::kFlushes + (C::kFlushes - 1)) * kStashStride;
+        }
+      };
       float feat[18];
       long long f = 0;
+      if constexpr (FROM_RING) {
+        // the fence that orders the loads of the rows after this wave's own stores of them
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (lane < count) {
+          const float* row = lane_row();
+          const unsigned hi_tie = __builtin_bit_cast(unsigned, row[kNumSums + 4]);
+          f = (long long)(((unsigned long long)(hi_tie >> 1) << 32) | __builtin_bit_cast(unsigned, row[kNumSums + 5]));
+        }
+      }
+      // RING: the frame of the batch's lane idx (uniform)
+      [[maybe_unused]] auto frame_of_lane = [&](long long fl, int idx) -> long long {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(fl & 0xffffffffLL), idx);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)fl >> 32), idx);
+        return (long long)(((unsigned long long)hi << 32) | lo);
+      };
+      if constexpr (RG && RING) {
+        // a re-run row's code names the lane of the batch whose frame it is
+        int src = 0;
+        if (lane < count) src = (int)lane_row()[kNumSums + 5] & 63;
+        const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(src * 4, (int)(unsigned)(batch_f & 0xffffffffLL));
+        const unsigned hi = (unsigned)__builtin_amdgcn_ds_bpermute(src * 4, (int)(unsigned)((unsigned long long)batch_f >> 32));
+        f = (long long)(((unsigned long long)hi << 32) | lo);
+      }
       [[maybe_unused]] float sc = 1.0f;
       [[maybe_unused]] int ex_half = 0;
       float kw_shift = 0.f;
@@ -1177,7 +1288,7 @@ __device__ __forceinline__ void wave_body(
       if constexpr (PLAN == kPlanCumulants && !RG) {
         bool tiny = false;
         if (lane < count) {
-          const float* row = stash + (lane * C::kFlushes + (C::kFlushes - 1)) * kStashStride;
+          const float* row = lane_row();
           double sp = row[2];
           if constexpr (C::kFlushes > 1) {
 #pragma unroll
@@ -1190,7 +1301,8 @@ __device__ __forceinline__ void wave_body(
           const int idx = __builtin_ctzll(tz);
           tz &= tz - 1;
           float xr[2 * ROWS], xi[2 * ROWS];
-          load_frame(xr, xi, f0 + idx);
+          if constexpr (RING) load_frame(xr, xi, frame_of_lane(f, idx));
+          else load_frame(xr, xi, f0 + idx);
           Stats Z;
           static_for<ROWS>([&](auto ii) {
             constexpr int i = decltype(ii)::value;
@@ -1202,12 +1314,25 @@ __device__ __forceinline__ void wave_body(
         }
       }
       if (lane < count) {
-        const float* row = stash + (lane * C::kFlushes + (C::kFlushes - 1)) * kStashStride;   // the frame's last row
+        const float* row = lane_row();
+        // value k of the row h flushes before the frame's last one.  FROM_RING: the lane's rows come in with loads issued
+        // together, ahead of the algebra
+        [[maybe_unused]] float rb[FROM_RING ? C::kFlushes * kStashStride : 1];
+        if constexpr (FROM_RING) {
+#pragma unroll
+          for (int h = 0; h < C::kFlushes; ++h)
+#pragma unroll
+            for (int k = 0; k < kStashStride; ++k) rb[h * kStashStride + k] = row[k - h * kStashStride];
+        }
+        auto rd = [&](int k, int h) -> float {
+          if constexpr (FROM_RING) return rb[h * kStashStride + k];
+          else return row[k - h * kStashStride];
+        };
         auto sm = [&](int k) -> double {           // sum k of the frame: its stash rows added in fp64
-          double t = row[k];
+          double t = rd(k, 0);
           if constexpr (C::kFlushes > 1) {
 #pragma unroll
-            for (int h = 1; h < C::kFlushes; ++h) t += (double)row[k - h * kStashStride];
+            for (int h = 1; h < C::kFlushes; ++h) t += (double)rd(k, h);
           }
           return t;
         };
@@ -1215,10 +1340,10 @@ __device__ __forceinline__ void wave_body(
           float s15[15];
 #pragma unroll
           for (int k = 0; k < 15; ++k) {
-            s15[k] = row[k];
+            s15[k] = rd(k, 0);
             if constexpr (C::kFlushes > 1) {
 #pragma unroll
-              for (int h = 1; h < C::kFlushes; ++h) s15[k] += row[k - h * kStashStride];
+              for (int h = 1; h < C::kFlushes; ++h) s15[k] += rd(k, h);
             }
           }
           cancel = cancellation_suspect(s15, (float)N, (float)cancel_kappa(N));
@@ -1230,9 +1355,10 @@ __device__ __forceinline__ void wave_body(
         F.sa = sm(15); F.sad1 = sm(16); F.sad2 = sm(17); F.sad4 = sm(18);
         F.std1 = sm(19); F.std2 = sm(20); F.sab1 = sm(21); F.sab2 = sm(22);
         F.swd1 = sm(23); F.swd2 = sm(24); F.swd3 = sm(25); F.swd4 = sm(26);
-        F.gmax_raw = row[27]; F.Kt = row[28]; F.Kw = row[29]; F.Ka = row[30];
-        F.pi_tie = row[31] != 0.0f;
-        kw_shift = row[29];
+        F.gmax_raw = rd(27, 0); F.Kt = rd(28, 0); F.Kw = rd(29, 0); F.Ka = rd(30, 0);
+        if constexpr (FROM_RING) F.pi_tie = (__builtin_bit_cast(unsigned, rd(31, 0)) & 1u) != 0;
+        else F.pi_tie = rd(31, 0) != 0.0f;
+        kw_shift = rd(29, 0);
         if constexpr (PLAN == kPlanCumulants && !RG) {
           if (!flat_angles) F.std2 = 1.0;                    // not an all-zero frame (is_outside_fp32_range: zero_frame)
         }
@@ -1242,11 +1368,11 @@ __device__ __forceinline__ void wave_body(
           cancel = finalize_features<true>(F, N, feat, ex) && cancel;
           sc = __builtin_bit_cast(float, (127 - ex) << 23);     // the 2^-ex the frame was multiplied by
           ex_half = ex / 2;
-          f = f0 + (code & 63);
+          if constexpr (!RING) f = f0 + (code & 63);
         } else {
           cancel = finalize_features(F, N, feat) && cancel;
           if (is_outside_fp32_range(F, N)) redo = true;         // re-run below, in this kernel; the row is not stored
-          f = f0 + lane;
+          if constexpr (!RING) f = f0 + lane;
         }
         cancel = cancel && !redo;
         // flagged by the sweep (f5 came back negated) and neither NaN nor on its way to a re-run
@@ -1298,6 +1424,7 @@ __device__ __forceinline__ void wave_body(
           wave_exact_cumulants<N, true>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride, mask);
       }
       lds_wave_fence();
+      if constexpr (FROM_RING) batch_f = f;
       return __builtin_amdgcn_ballot_w64(redo);
     };
 
@@ -1310,7 +1437,13 @@ __device__ __forceinline__ void wave_body(
           const int idx = __builtin_ctzll(todo);
           todo &= todo - 1;
           float xr[2 * ROWS], xi[2 * ROWS];
-          load_frame(xr, xi, f0 + idx);
+          if constexpr (RING) {
+            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(batch_f & 0xffffffffLL), idx);
+            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)batch_f >> 32), idx);
+            load_frame(xr, xi, (long long)(((unsigned long long)hi << 32) | lo));
+          } else {
+            load_frame(xr, xi, f0 + idx);
+          }
           float m = 0.f;                                       // largest |component|: NaNs drop out of the maximum
           static_for<2 * ROWS>([&](auto ee) {
             constexpr int e = decltype(ee)::value;
@@ -1324,7 +1457,7 @@ __device__ __forceinline__ void wave_body(
             constexpr int e = decltype(ee)::value;
             xr[e] *= sc; xi[e] *= sc;
           });
-          frame(xr, xi, cnt);
+          frame(xr, xi, cnt, 0, std::false_type{});
           if (lane == 63)
             stash[(cnt * C::kFlushes + (C::kFlushes - 1)) * kStashStride + kNumSums + 5] = (float)((ex + 128) * 64 + idx);
         }
@@ -1334,16 +1467,29 @@ __device__ __forceinline__ void wave_body(
     for (int g = 0; g < n_here; ++g) {
       float xr[2 * ROWS], xi[2 * ROWS];
       load_frame(xr, xi, f0 + g);
-      frame(xr, xi, g);
+      if constexpr (RING) frame(xr, xi, filled + g, f0 + g, std::true_type{});
+      else frame(xr, xi, g, 0, std::false_type{});
+    }
+    [[maybe_unused]] int batch = n_here;
+    if constexpr (RING) {
+      // finalise when the ring has no room for another run, or the work is exhausted (n_here == 0)
+      filled += n_here;
+      if (n_here != 0 && filled + kFramesPerWave <= kBatch) continue;
+      if (filled == 0) break;
+      batch = filled;
     }
 
     AMCX_STAMP(4);
     asm volatile("; MARK finalize");
     __builtin_amdgcn_s_setprio(AMCX_PRIO_OF(5));
-    const unsigned long long left_over = finalise(std::false_type{}, n_here);
+    const unsigned long long left_over = finalise(std::false_type{}, batch);
     asm volatile("; MARK redo");
     if (left_over != 0) rerun_scaled(left_over);              // frames outside the fp32 sums' range: never on ordinary data
     AMCX_STAMP(5);
+    if constexpr (RING) {
+      filled = 0;
+      if (n_here == 0) break;
+    }
   }
 #ifdef AMCX_WAVE_STAMPS
   if (lane == 0) {
@@ -1357,16 +1503,32 @@ __device__ __forceinline__ void wave_body(
 #endif
 }
 
+#ifdef AMCX_WAVE_STAMPS
+// (the diagnostic builds: one signature at every size; `ring` is not read where the size takes none)
 template <int N>
 __global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features18_wave_kernel(
     const float2* __restrict__ iq, long long n_frames, long long row_stride,
-    float* __restrict__ out, long long out_stride AMCX_STAMP_ARG) {
-#ifdef AMCX_WAVE_STAMPS
-  wave_body<N>(iq, n_frames, row_stride, out, out_stride, kMaskAll, stamp_out);
-#else
-  wave_body<N>(iq, n_frames, row_stride, out, out_stride, kMaskAll);
-#endif
+    float* __restrict__ out, long long out_stride, float* ring AMCX_STAMP_ARG) {
+  wave_body<N>(iq, n_frames, row_stride, out, out_stride, kMaskAll, ring, stamp_out);
 }
+#else
+// Two overloads, one instantiated per size: without a ring (N = 1024, 4096: the kernels of before, byte for byte) and with
+// one (N = 2048: Cfg<N>::kRingFloatsPerWave floats per wave of the grid).
+template <int N>
+__global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features18_wave_kernel(
+    const float2* __restrict__ iq, long long n_frames, long long row_stride,
+    float* __restrict__ out, long long out_stride) {
+  static_assert(!Cfg<N>::kHasRing, "this size's kernel takes a ring; its LDS form is amcx_features18_wave_lds_kernel");
+  wave_body<N, kPlanAll, false>(iq, n_frames, row_stride, out, out_stride, kMaskAll, nullptr);
+}
+template <int N>
+__global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features18_wave_kernel(
+    const float2* __restrict__ iq, long long n_frames, long long row_stride,
+    float* __restrict__ out, long long out_stride, float* ring) {
+  static_assert(Cfg<N>::kHasRing, "no ring form at this frame size");
+  wave_body<N, kPlanAll, true>(iq, n_frames, row_stride, out, out_stride, kMaskAll, ring);
+}
+#endif
 
 #ifndef AMCX_WAVE_STAMPS
 // The feature-subset kernels (amcx_features_c64_subset): PLAN = kPlanNoSpectral or kPlanCumulants; columns outside `mask` hold
@@ -1376,7 +1538,31 @@ template <int N, int PLAN>
 __global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features_subset_wave_kernel(
     const float2* __restrict__ iq, long long n_frames, long long row_stride,
     float* __restrict__ out, long long out_stride, unsigned mask) {
-  wave_body<N, PLAN>(iq, n_frames, row_stride, out, out_stride, mask);
+  static_assert(!Cfg<N>::kHasRing, "this size's kernel takes a ring; its LDS form is amcx_features_subset_wave_lds_kernel");
+  wave_body<N, PLAN, false>(iq, n_frames, row_stride, out, out_stride, mask, nullptr);
+}
+template <int N, int PLAN>
+__global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features_subset_wave_kernel(
+    const float2* __restrict__ iq, long long n_frames, long long row_stride,
+    float* __restrict__ out, long long out_stride, unsigned mask, float* ring) {
+  static_assert(Cfg<N>::kHasRing, "no ring form at this frame size");
+  wave_body<N, PLAN, true>(iq, n_frames, row_stride, out, out_stride, mask, ring);
+}
+
+// The same kernels without a ring, for the frame sizes whose product form takes one (Cfg<N>::kHasRing): batches of
+// kFramesPerWave frames finalised from the LDS stash.  Same per-frame instructions, same results; a launch that has no ring
+// (launch_wave_n) runs these.
+template <int N>
+__global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features18_wave_lds_kernel(
+    const float2* __restrict__ iq, long long n_frames, long long row_stride,
+    float* __restrict__ out, long long out_stride) {
+  wave_body<N, kPlanAll, false>(iq, n_frames, row_stride, out, out_stride, kMaskAll, nullptr);
+}
+template <int N, int PLAN>
+__global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features_subset_wave_lds_kernel(
+    const float2* __restrict__ iq, long long n_frames, long long row_stride,
+    float* __restrict__ out, long long out_stride, unsigned mask) {
+  wave_body<N, PLAN, false>(iq, n_frames, row_stride, out, out_stride, mask, nullptr);
 }
 #endif
 
@@ -1402,57 +1588,120 @@ inline const char* wave_kernel_name(int frame_size) {
 }
 
 #ifndef AMCX_WAVE_STAMPS
-template <int N, int PLAN = kPlanAll>
-inline hipError_t launch_wave_n(const float2* iq, int64_t n_frames, int64_t row_stride, float* out,
-                                int64_t out_stride, hipStream_t stream, int cus, unsigned mask = kMaskAll) {
-  constexpr auto kern = [] {
-    if constexpr (PLAN == kPlanAll) return wave::amcx_features18_wave_kernel<N>;
-    else return wave::amcx_features_subset_wave_kernel<N, PLAN>;
-  }();
-  constexpr int lds = wave::Cfg<N>::kLdsBytes;
-  // > 64 KiB of dynamic LDS needs the attribute; it is per device, so once per (kernel, device)
-  static bool lds_attr_set[64] = {};
+// bytes of ring a launch of frame size N over `cus` workgroups needs (0: that size's kernel takes none)
+inline size_t wave_ring_bytes(int frame_size, int cus) {
+  auto of = [&](auto cfg) -> size_t {
+    using C = decltype(cfg);
+    return C::kHasRing ? (size_t)cus * C::kWavesPerWG * C::kRingFloatsPerWave * sizeof(float) : 0;
+  };
+  switch (frame_size) {
+    case 1024: return of(wave::Cfg<1024>{});
+    case 2048: return of(wave::Cfg<2048>{});
+    case 4096: return of(wave::Cfg<4096>{});
+    default: return 0;
+  }
+}
+
+// > 64 KiB of dynamic LDS needs the attribute; it is per device, so once per (kernel, device)
+template <class K>
+inline hipError_t wave_lds_attr(K kern, int lds, bool (&set)[64]) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !lds_attr_set[dev]) {
+  if (dev < 0 || dev >= 64 || !set[dev]) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) lds_attr_set[dev] = true;   // benign race: idempotent
+    if (dev >= 0 && dev < 64) set[dev] = true;   // benign race: idempotent
   }
+  return hipSuccess;
+}
+
+// `ring`: wave_ring_bytes(N, cus) bytes that no other launch in flight uses, or nullptr -- then a frame size whose kernel
+// takes a ring runs its LDS form (amcx_features18_wave_lds_kernel), same results
+template <int N, int PLAN = kPlanAll>
+inline hipError_t launch_wave_n(const float2* iq, int64_t n_frames, int64_t row_stride, float* out,
+                                int64_t out_stride, hipStream_t stream, int cus, float* ring, unsigned mask = kMaskAll) {
+  using Plain18 = void (*)(const float2*, long long, long long, float*, long long);
+  using Ring18 = void (*)(const float2*, long long, long long, float*, long long, float*);
+  using PlainSub = void (*)(const float2*, long long, long long, float*, long long, unsigned);
+  using RingSub = void (*)(const float2*, long long, long long, float*, long long, unsigned, float*);
+  constexpr bool kRing = wave::Cfg<N>::kHasRing;
+  // the size's product kernel: the overload with a ring where it takes one
+  constexpr auto kern = [] {
+    if constexpr (PLAN == kPlanAll) {
+      if constexpr (kRing) return static_cast<Ring18>(wave::amcx_features18_wave_kernel<N>);
+      else return static_cast<Plain18>(wave::amcx_features18_wave_kernel<N>);
+    } else {
+      if constexpr (kRing) return static_cast<RingSub>(wave::amcx_features_subset_wave_kernel<N, PLAN>);
+      else return static_cast<PlainSub>(wave::amcx_features_subset_wave_kernel<N, PLAN>);
+    }
+  }();
+  constexpr int lds = wave::Cfg<N>::kLdsBytes;
+  const bool lds_form = wave::Cfg<N>::kHasRing && ring == nullptr;
+  static bool lds_attr_set[64] = {};
+  hipError_t e = hipSuccess;
+  if (!lds_form) e = wave_lds_attr(kern, lds, lds_attr_set);
+  if (e != hipSuccess) return e;
   int64_t grid = (int64_t)cus;                        // persistent: one resident workgroup per CU
   const int64_t min_slice = wave::Cfg<N>::kWavesPerWG;   // at least a frame per wave
   if (grid * min_slice > n_frames) grid = (n_frames + min_slice - 1) / min_slice;
-  if constexpr (PLAN == kPlanAll)
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                       (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
-  else
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                       (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask);
+  if constexpr (wave::Cfg<N>::kHasRing) {
+    if (lds_form) {
+      constexpr auto kern_lds = [] {
+        if constexpr (PLAN == kPlanAll) return wave::amcx_features18_wave_lds_kernel<N>;
+        else return wave::amcx_features_subset_wave_lds_kernel<N, PLAN>;
+      }();
+      static bool lds_attr_set_lds[64] = {};
+      e = wave_lds_attr(kern_lds, lds, lds_attr_set_lds);
+      if (e != hipSuccess) return e;
+      if constexpr (PLAN == kPlanAll)
+        hipLaunchKernelGGL(kern_lds, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                           (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
+      else
+        hipLaunchKernelGGL(kern_lds, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                           (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask);
+      return hipGetLastError();
+    }
+  }
+  if constexpr (kRing) {
+    if constexpr (PLAN == kPlanAll)
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride, ring);
+    else
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask, ring);
+  } else {
+    if constexpr (PLAN == kPlanAll)
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
+    else
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
+                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask);
+  }
   return hipGetLastError();
 }
 
 // the feature-subset kernels of 1024 ... 4096 (PLAN kPlanNoSpectral / kPlanCumulants)
 template <int PLAN>
 inline hipError_t launch_wave_subset(const float2* iq, int64_t n_frames, int32_t frame_size, int64_t row_stride, float* out,
-                                     int64_t out_stride, hipStream_t stream, int cus, unsigned mask) {
+                                     int64_t out_stride, hipStream_t stream, int cus, float* ring, unsigned mask) {
   switch (frame_size) {
-    case 1024: return launch_wave_n<1024, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask);
-    case 2048: return launch_wave_n<2048, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask);
-    case 4096: return launch_wave_n<4096, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask);
+    case 1024: return launch_wave_n<1024, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring, mask);
+    case 2048: return launch_wave_n<2048, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring, mask);
+    case 4096: return launch_wave_n<4096, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring, mask);
     default: return hipErrorNotSupported;
   }
 }
 
 inline hipError_t launch_wave(const float2* iq, int64_t n_frames, int32_t frame_size,
                               int64_t row_stride, float* out, int64_t out_stride,
-                              hipStream_t stream, int cus) {
+                              hipStream_t stream, int cus, float* ring) {
   switch (frame_size) {
     // (128, 256 and 512 ran here until late in round 5 -- 8 / 4 / 2 frames sharing one run of FFT passes 2-3 -- and have a
     //  kernel of their own now, amcx_short_kernel.h: +34 % / +13 % / +2.5 ... 5 %)
-    case 1024: return launch_wave_n<1024>(iq, n_frames, row_stride, out, out_stride, stream, cus);
-    case 2048: return launch_wave_n<2048>(iq, n_frames, row_stride, out, out_stride, stream, cus);
-    case 4096: return launch_wave_n<4096>(iq, n_frames, row_stride, out, out_stride, stream, cus);
+    case 1024: return launch_wave_n<1024>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring);
+    case 2048: return launch_wave_n<2048>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring);
+    case 4096: return launch_wave_n<4096>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring);
     default: return hipErrorNotSupported;       // 128, 256, 512, 8192, 16384, 32768 have kernels of their own (amcx.hip)
   }
 }

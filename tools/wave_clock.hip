@@ -25,10 +25,12 @@ void run(const char* label, const float2* d_iq, long long F, float* d_out, unsig
          double seconds, long long row_stride = N) {
   using namespace amcx::wave;
   auto kern = amcx_features18_wave_kernel<N>;
+  float* d_ring = nullptr;   // the wave's ring of stash rows, where the kernel takes one (Cfg<N>::kHasRing)
+  if (Cfg<N>::kHasRing) CHECK(hipMalloc(&d_ring, (size_t)grid * Cfg<N>::kWavesPerWG * Cfg<N>::kRingFloatsPerWave * sizeof(float)));
   constexpr int kLdsBytes = Cfg<N>::kLdsBytes;
   CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
   auto launch = [&]() {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg<N>::kThreads), kLdsBytes, 0, d_iq, F, row_stride, d_out, 18LL, d_st);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg<N>::kThreads), kLdsBytes, 0, d_iq, F, row_stride, d_out, 18LL, d_ring, d_st);
   };
   // >= `seconds` of back-to-back launches
   const auto t0 = std::chrono::steady_clock::now();
@@ -102,6 +104,7 @@ void run(const char* label, const float2* d_iq, long long F, float* d_out, unsig
            g_valu_per_frame);
   printf("\n");
   fflush(stdout);
+  if (d_ring) CHECK(hipFree(d_ring));
 }
 
 static int g_only = -1;        // run only this configuration (index below), all if < 0

@@ -11,12 +11,14 @@
 template <int N> void run(const float2* d_iq, long long F, float* d_out, unsigned long long* d_st, int grid) {
   using namespace amcx::wave;
   auto kern = amcx_features18_wave_kernel<N>;
+  float* d_ring = nullptr;   // the wave's ring of stash rows, where the kernel takes one (Cfg<N>::kHasRing)
+  if (Cfg<N>::kHasRing) CHECK(hipMalloc(&d_ring, (size_t)grid * Cfg<N>::kWavesPerWG * Cfg<N>::kRingFloatsPerWave * sizeof(float)));
   constexpr int kLdsBytes = Cfg<N>::kLdsBytes;
   CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
   hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
   for (int rep = 0; rep < 3; ++rep) {
     CHECK(hipEventRecord(e0));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg<N>::kThreads), kLdsBytes, 0, d_iq, F, (long long)N, d_out, 18LL, d_st);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg<N>::kThreads), kLdsBytes, 0, d_iq, F, (long long)N, d_out, 18LL, d_ring, d_st);
     CHECK(hipEventRecord(e1)); CHECK(hipEventSynchronize(e1));
   }
   float ms; CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -44,13 +46,26 @@ template <int N> void run(const float2* d_iq, long long F, float* d_out, unsigne
   double frames_per_wave = (double)F / nw;
   printf("N=%d  kernel %.3f ms  (%.1f M frames/s)  mean wave lifetime %.1f us -> s_memtime clock %.2f GHz; cycles per frame per wave: %.0f\n", N, ms, F / ms / 1e3, real_us, tot / nw / real_us / 1e3, tot / nw / frames_per_wave);
   for (int k = 0; k < kStampSections; ++k) if (s[k] > 0) printf("   %-44s %6.1f %%   %8.0f cycles/frame\n", names[k], 100.0 * s[k] / tot, s[k] / nw / frames_per_wave);
+  if (d_ring) CHECK(hipFree(d_ring));
 }
-int main() {
+// wave_stamps [FILE]: FILE holds raw complex64 samples (e.g. a slice of bench.py's arena written with numpy's tofile), tiled over
+// the buffer in place of the Gaussian noise -- the finaliser's share depends on how many frames take its slow paths
+int main(int argc, char** argv) {
   const long long F = 6 * 26 * 4096 / 2;   // 319488 frames, 5.2 GB
   std::vector<float2> h(F * 2048);
-  std::mt19937 rng(1); std::normal_distribution<float> nd(0.f, 1.f);
-  for (long long i = 0; i < 2048LL * 4096; ++i) h[i] = make_float2(nd(rng), nd(rng));
-  for (long long i = 2048LL * 4096; i < F * 2048; ++i) h[i] = h[i % (2048LL * 4096)];
+  long long seed_n = 2048LL * 4096;
+  if (argc > 1) {
+    FILE* fp = fopen(argv[1], "rb");
+    if (!fp) { printf("cannot read %s\n", argv[1]); return 1; }
+    seed_n = (long long)fread(h.data(), 8, (size_t)(F * 2048), fp);
+    fclose(fp);
+    if (seed_n < 4096) { printf("%s: too short\n", argv[1]); return 1; }
+    printf("input: %lld samples of %s, tiled\n", seed_n, argv[1]);
+  } else {
+    std::mt19937 rng(1); std::normal_distribution<float> nd(0.f, 1.f);
+    for (long long i = 0; i < seed_n; ++i) h[i] = make_float2(nd(rng), nd(rng));
+  }
+  for (long long i = seed_n; i < F * 2048; ++i) h[i] = h[i % seed_n];
   float2* d_iq; float* d_out; unsigned long long* d_st;
   CHECK(hipMalloc(&d_iq, F * 2048 * 8)); CHECK(hipMalloc(&d_out, 2 * F * 18 * 4)); CHECK(hipMalloc(&d_st, 256 * 16 * 8 * 8));
   CHECK(hipMemcpy(d_iq, h.data(), F * 2048 * 8, hipMemcpyHostToDevice));
