@@ -12,7 +12,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 7          # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 8          # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -20,6 +20,8 @@ VARIANT_AUTO, VARIANT_BLOCK, VARIANT_WAVE = 0, 1, 2
 VARIANTS = {"auto": VARIANT_AUTO, "block": VARIANT_BLOCK, "wave": VARIANT_WAVE}
 OK, EINVAL, ENOTSUP, EHIP, ENODEV, ENOMEM, EIO = 0, -1, -2, -3, -4, -5, -6
 SRC_C64, SRC_C128, SRC_F32_SPLIT, SRC_F64_SPLIT = 0, 1, 2, 3
+ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2                # AMCX_ACT_* (ABI 8)
+ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
 
 
 class UploadStats(C.Structure):
@@ -81,6 +83,10 @@ SIGNATURES = {
     "amcx_standardize_workspace_bytes": (_i64, [_i64, _i32]),
     "amcx_standardize_fit_transform_f32": (C.c_int, [_vp, _i64, _i64, _i32, C.POINTER(_i32), _i32, _vp, _i64,
                                                      _vp, _vp, _vp, _i64, _vp]),
+    "amcx_mlp_params_floats": (_i64, [C.POINTER(_i32), _i32]),
+    "amcx_mlp_classify_f32": (C.c_int, [_vp, _i64, _i64, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, C.POINTER(_i32), _i32,
+                                        _i32, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "amcx_mlp_kernel_name": (C.c_int, [C.POINTER(_i32), _i32, C.c_char_p, _i32]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@
 #include "amcx_group_kernel.h"
 #include "amcx_short_kernel.h"
 #include "amcx_post_kernels.h"
+#include "amcx_mlp_kernel.h"
 #include "amcx_pack_kernel.h"
 #include "amcx_upload.h"
 
@@ -1477,6 +1478,77 @@ int amcx_select_scale_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
   hipLaunchKernelGGL(amcx::amcx_select_scale_kernel, dim3((unsigned)grid), dim3(amcx::kBlockThreads), 0,
                      static_cast<hipStream_t>(hip_stream), x_dev, (long long)n_rows, (long long)row_stride,
                      cols_dev, (int)n_sel, mean_dev, scale_dev, out_dev, (long long)out_stride);
+  AMCX_HIP(hipGetLastError());
+  return AMCX_OK;
+}
+
+// widths[0 .. n_linear]: every width 1 ... 32, 1 ... 6 layers
+static bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
+  if (widths == nullptr || n_linear < 1 || n_linear > amcx::kMlpMaxLinear) return false;
+  for (int l = 0; l <= n_linear; ++l)
+    if (widths[l] < 1 || widths[l] > amcx::kMlpMaxWidth) return false;
+  return true;
+}
+
+int64_t amcx_mlp_params_floats(const int32_t* widths_host, int32_t n_linear) {
+  if (!mlp_shape_ok(widths_host, n_linear)) return -1;
+  int64_t n = 0;
+  for (int l = 0; l < n_linear; ++l) n += (int64_t)widths_host[l + 1] * widths_host[l] + widths_host[l + 1];
+  return n;
+}
+
+int amcx_mlp_kernel_name(const int32_t* widths_host, int32_t n_linear, char* buf, int32_t buf_len) {
+  if (buf == nullptr || buf_len <= 0 || !mlp_shape_ok(widths_host, n_linear)) return AMCX_EINVAL;
+  snprintf(buf, (size_t)buf_len, "%s", "amcx_mlp_classify_kernel");      // one kernel: widths are run-time values
+  return AMCX_OK;
+}
+
+int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols,
+                          const int32_t* cols_host, int32_t n_sel, const double* mean_dev, const double* scale_dev,
+                          const float* params_dev, const int32_t* widths_host, int32_t n_linear, int32_t activation,
+                          int32_t* labels_dev, float* probs_dev, int64_t probs_stride, int64_t rows_per_group,
+                          int64_t* counts_dev, void* hip_stream) {
+  if (n_rows < 0 || n_cols < 1 || n_cols > amcx::kStatMaxCols || row_stride < n_cols || cols_host == nullptr ||
+      !mlp_shape_ok(widths_host, n_linear) || n_sel != widths_host[0])
+    return AMCX_EINVAL;
+  if (activation != AMCX_ACT_RELU && activation != AMCX_ACT_TANH && activation != AMCX_ACT_SIGMOID) return AMCX_EINVAL;
+  if ((mean_dev == nullptr) != (scale_dev == nullptr)) return AMCX_EINVAL;
+  amcx::SelectCols sel;
+  sel.n = n_sel;
+  for (int j = 0; j < amcx::kStatMaxCols; ++j) sel.c[j] = 0;
+  for (int j = 0; j < n_sel; ++j) {
+    if (cols_host[j] < 0 || cols_host[j] >= n_cols) return AMCX_EINVAL;
+    sel.c[j] = cols_host[j];
+  }
+  const int n_cls = widths_host[n_linear];
+  if (probs_dev != nullptr && probs_stride < n_cls) return AMCX_EINVAL;
+  if (rows_per_group < 0 || (rows_per_group == 0 && counts_dev != nullptr)) return AMCX_EINVAL;
+  if (rows_per_group > 0 && n_rows % rows_per_group != 0) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (x_dev == nullptr || params_dev == nullptr) return AMCX_EINVAL;
+  if (labels_dev == nullptr && probs_dev == nullptr && counts_dev == nullptr) return AMCX_OK;
+  if (on_another_device(x_dev) || on_another_device(params_dev) || (labels_dev && on_another_device(labels_dev)) ||
+      (probs_dev && on_another_device(probs_dev)) || (counts_dev && on_another_device(counts_dev)))
+    return AMCX_EINVAL;
+  amcx::MlpShape shape;
+  shape.n_linear = n_linear;
+  shape.act = activation;
+  for (int l = 0; l <= amcx::kMlpMaxLinear; ++l) shape.w[l] = l <= n_linear ? widths_host[l] : 0;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (counts_dev != nullptr) {
+    const int64_t bins = (n_rows / rows_per_group) * (int64_t)(n_cls + 1);
+    const int64_t zgrid = (bins + 255) / 256;
+    hipLaunchKernelGGL(amcx::amcx_mlp_zero_counts_kernel, dim3((unsigned)(zgrid < 1024 ? zgrid : 1024)), dim3(256), 0, st,
+                       reinterpret_cast<unsigned long long*>(counts_dev), (long long)bins);
+  }
+  const int64_t tiles = (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows;
+  int64_t grid = tiles;
+  const int64_t cap = (int64_t)cu_count() * 4;             // every workgroup stages the parameters once, then walks tiles
+  if (grid > cap) grid = cap;
+  hipLaunchKernelGGL(amcx::amcx_mlp_classify_kernel, dim3((unsigned)grid), dim3(amcx::kMlpThreads), 0, st, x_dev,
+                     (long long)n_rows, (long long)row_stride, sel, mean_dev, scale_dev, params_dev, shape, labels_dev,
+                     probs_dev, (long long)probs_stride, (long long)(counts_dev ? rows_per_group : 1),
+                     reinterpret_cast<unsigned long long*>(counts_dev), (long long)tiles);
   AMCX_HIP(hipGetLastError());
   return AMCX_OK;
 }

@@ -2,8 +2,9 @@
                               [--device D | --devices 0,1,...|all] [--resume] [--features all|used|3,5,...]`
 
 The `extract` sub-command of the reference's CLI (src/amcpy/main.py:32,85-87,
-160-175), and only that one: plot/train/eval/quantize are outside the hot path
-(SURVEY.md section 8).  The reference's dispatcher calls ``cmd_extract(cfg, args)``
+160-175); plot/train/quantize are outside the hot path.
+`python -m amcpy_amd classify --root DIR --model ID|PATH [--mode training|test] [--from-iq] [--device D]` is the
+evaluation half of the reference's `eval` (nn_model.evaluate_by_snr) on the GPU: amcpy_amd/classifier.py.  The reference's dispatcher calls ``cmd_extract(cfg, args)``
 on a one-argument function (main.py:175 vs :85) and raises TypeError as
 written; this entry point takes the same defaults and simply works.
 
@@ -44,6 +45,20 @@ def build_parser() -> argparse.ArgumentParser:
                          "evaluate_by_snr read (FeatureConfig.used + 1); or a comma-separated list of ids 1 ... 18.  The "
                          "files keep their (n_snr, n_frames, 18) float32 layout with NaN in the other columns; `plot` "
                          "needs all 18")
+    cl = sub.add_parser("classify", help="classify every (modulation, SNR, frame) on the GPU and write the accuracy table")
+    cl.add_argument("--root", type=Path, default=None, help="project root (default: cwd)")
+    cl.add_argument("--model", required=True, metavar="ID|PATH",
+                    help="the id of ann/model-{ID}.pt under the root (the file the reference's training writes), or a "
+                         "path to a .pt checkpoint / .npz model")
+    cl.add_argument("--mode", choices=("training", "test"), default="test",
+                    help="rows the scaler is fitted on, as the reference's preprocess_data: training_snr or all_snr (default)")
+    cl.add_argument("--from-iq", action="store_true",
+                    help="run the extraction first (the used features only) instead of reading calculated-features/")
+    cl.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
+    cl.add_argument("--frame-size", type=int, default=None)
+    cl.add_argument("--num-frames", type=int, default=None)
+    cl.add_argument("--snr-values", nargs="+", default=None, metavar="LABEL",
+                    help="SNR labels of the container's first axis, in order (default: the 16 of SignalConfig)")
     return ap
 
 
@@ -165,6 +180,11 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
     if args.snr_values is not None:
         sig = replace(sig, snr_values={i: str(v) for i, v in enumerate(args.snr_values)})
     cfg = replace(cfg, signals=sig)
+    if args.command == "classify":
+        # tensors on torch's runtime: this command never skips the import
+        from .classifier import run_classification
+        run_classification(cfg, args.model, mode=args.mode, from_iq=args.from_iq, device=args.device)
+        return 0
     if args.command == "extract":
         if args.devices is not None and args.device is not None:
             raise SystemExit("--device and --devices exclude each other")

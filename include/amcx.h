@@ -88,8 +88,9 @@ extern "C" {
  * 5 = frame sizes 16384 and 32768 (AMCX_MAX_FRAME_SIZE 32768, AMCX_MAX_BLOCK_FRAME_SIZE);
  * 6 = EVERY frame size 2 ... 32768: AMCX_MAX_BLOCK_FRAME_SIZE 32768 (8193 ... 32767 were AMCX_ENOTSUP but for 16384);
  * amcx_features18_c64_ws / amcx_features18_workspace_bytes;
- * 7 = feature subsets: AMCX_FEATURES_*, amcx_features_c64_subset, amcx_ctx_set_feature_mask, amcx_kernel_name_subset. */
-#define AMCX_ABI_VERSION 7
+ * 7 = feature subsets: AMCX_FEATURES_*, amcx_features_c64_subset, amcx_ctx_set_feature_mask, amcx_kernel_name_subset;
+ * 8 = classification on the device: AMCX_ACT_*, amcx_mlp_params_floats, amcx_mlp_classify_f32, amcx_mlp_kernel_name. */
+#define AMCX_ABI_VERSION 8
 #define AMCX_NUM_FEATURES 18
 
 /* FEATURE MASKS (ABI 7): bit j - 1 stands for feature id j (1 gamma_max ... 18 |C63|).  The reference's default selection,
@@ -484,6 +485,51 @@ int amcx_standardize_fit_transform_f32(const float* x_dev, int64_t n_rows, int64
                                        float* out_dev, int64_t out_stride, double* mean_dev,
                                        double* scale_dev, void* workspace_dev, int64_t workspace_bytes,
                                        void* hip_stream);
+
+/*
+ * ABI 8.  CLASSIFICATION: the reference's AMCClassifier in eval() mode (nn_model.py:28-75: Linear, BatchNorm1d,
+ * activation, Dropout (identity in eval), ..., Linear, Softmax) and the `model(x_t).argmax(1)` plus accuracy count of
+ * its evaluate_by_snr (nn_model.py:250-259), as ONE launch over the device-resident (n_rows x n_cols) float32 matrix.
+ *
+ * The network is n_linear (1 ... 6) dense layers of widths widths_host[0 .. n_linear] (n_linear + 1 entries, each
+ * 1 ... 32; widths_host[0] == n_sel inputs, widths_host[n_linear] classes), the activation (AMCX_ACT_*) between them
+ * and softmax behind the last.  params_dev is the PACKED PARAMETER BLOCK, float32, no padding, amcx_mlp_params_floats
+ * floats in all (sum over layers of out * in + out; -1 for an invalid shape): for layer l = 0 ... n_linear - 1
+ *     W'[out][in] row-major (out = widths[l + 1], in = widths[l]), then b'[out].
+ * BATCHNORM FOLD (the caller's, in float64, rounded once to float32): a Linear (W, b) followed by an eval-mode
+ * BatchNorm1d (gamma, beta, running mean mu, running variance var, eps = 1e-5) is the one dense layer
+ *     g = gamma / sqrt(var + eps);   W'[o][k] = W[o][k] * g[o];   b'[o] = (b[o] - mu[o]) * g[o] + beta[o];
+ * a Linear without BatchNorm is W' = W, b' = b.
+ *
+ * Per row r:  h[j] = float(float(x[r][cols_host[j]] - mean_dev[j]) / scale_dev[j]), the two float32 roundings of
+ * amcx_select_scale_f32 (mean / scale: n_sel doubles in DEVICE memory, e.g. as amcx_standardize_fit_transform_f32 left
+ * them -- no host round trip; both null: the rows are standardised already, columns are picked only; one null:
+ * AMCX_EINVAL).  Every layer: out[o] = b'[o] + sum_k W'[o][k] h[k], float32 FMAs in the order k = 0 ... in - 1, so a
+ * row's result does not depend on how rows are batched.  Softmax subtracts the row maximum; the label is the first
+ * maximum, as torch.argmax.
+ *
+ * Outputs, each pointer may be null: labels_dev[r] (int32); probs_dev[r * probs_stride + c] (float32,
+ * probs_stride >= classes); counts_dev[group][classes + 1] (int64), groups being consecutive blocks of rows_per_group
+ * rows (amcx_group_stats_f32's convention; n_rows must be a whole number of groups; rows_per_group 0 only with
+ * counts_dev null).  counts_dev is zeroed by the call itself (a small launch on hip_stream ahead of the classifier's);
+ * nothing is allocated, so the call can be captured in a graph.
+ * NaN RULE, a deliberate difference from the reference: a row whose probabilities are not all finite (a NaN feature of
+ * a constant frame, a column a feature subset left NaN, an inf) keeps its probabilities as they come out (NaN), gets
+ * label -1 and is counted in the extra last bin, counts[group][classes].  The reference's argmax answers class 0
+ * (BPSK) for such a row.
+ * n_rows == 0 is AMCX_OK and a no-op.  Arguments are checked before any HIP call.  amcx_mlp_kernel_name: the kernel
+ * that runs for this shape (host-only).
+ */
+#define AMCX_ACT_RELU 0
+#define AMCX_ACT_TANH 1
+#define AMCX_ACT_SIGMOID 2
+int64_t amcx_mlp_params_floats(const int32_t* widths_host, int32_t n_linear);
+int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols,
+                          const int32_t* cols_host, int32_t n_sel, const double* mean_dev, const double* scale_dev,
+                          const float* params_dev, const int32_t* widths_host, int32_t n_linear, int32_t activation,
+                          int32_t* labels_dev, float* probs_dev, int64_t probs_stride, int64_t rows_per_group,
+                          int64_t* counts_dev, void* hip_stream);
+int amcx_mlp_kernel_name(const int32_t* widths_host, int32_t n_linear, char* buf, int32_t buf_len);
 
 #ifdef __cplusplus
 }
