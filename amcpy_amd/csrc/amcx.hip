@@ -13,14 +13,69 @@
 
 #include "amcx_block_kernel.h"
 #include "amcx_stream_kernel.h"
-#include "amcx_wave_kernel.h"
-#include "amcx_quad_kernel.h"
-#include "amcx_group_kernel.h"
-#include "amcx_short_kernel.h"
+#include "amcx_launch.h"
 #include "amcx_post_kernels.h"
 #include "amcx_mlp_kernel.h"
 #include "amcx_pack_kernel.h"
 #include "amcx_upload.h"
+
+// ---- host-buffer entry points over a reusable context --------------------------------------
+// The context owns two streams, pinned staging slots and device scratch that only ever grow, so a
+// loop of per-frame calls (the reference's usage pattern, features.py:214-232 called once per queue
+// item) pays two small copies and the launches, not hipMalloc/hipFree/stream creation per call, and
+// a whole container goes up through the staged, overlapped path (ctx_run_strided).
+struct amcx_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  float* d_out = nullptr; size_t out_cap = 0;
+  // strided containers (amcx_ctx_features18_strided_host): staging pool, three pinned slots, a second stream
+  amcx::Pool pool;
+  int threads = 0;                               // 0: not yet sized
+  size_t slot_bytes = size_t(32) << 20;
+  bool round_on_device = false;
+  hipStream_t copy_stream = nullptr;
+  char* pin = nullptr;     size_t pin_cap = 0;   // kPinSlots x slot
+  void* d_slab = nullptr;  size_t slab_cap = 0;  // 2 x slot: uploaded chunks
+  void* d_frames = nullptr; size_t frames_cap = 0;   // plane-major sources: the frame-major complex64 image
+  void* d_ws = nullptr; size_t ws_cap = 0;           // the any-size path's FFT workspace (frame sizes above 8192, amcx_features18_c64_ws)
+  void* d_ring = nullptr; size_t ring_cap = 0;       // the wave kernels' ring of stash rows (RingSource): this context's launches only
+  hipEvent_t up_done[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t slab_free[2] = {nullptr, nullptr};
+  float* out_pin = nullptr; size_t out_pin_cap = 0;   // the result lands in pinned memory first
+  amcx_upload_stats stats = {};
+  // host placement (amcx_upload.h, NumaPlace): the CPUs local to this device; staging threads, the calling thread for the
+  // duration of a threaded upload, and with it the pinned slots it allocates, stay on them.  Empty: nothing is bound.
+  char pci_bus_id[32] = {0};
+  int numa_node = -1;
+  std::vector<int> bind_cpus;
+  // small row-major calls (a loop of per-frame calculate_features calls): the copy in, the launches and the copy
+  // out as ONE instantiated graph per (frames, frame size, variant, element type, buffers), relaunched
+  struct GraphKey {
+    int64_t frames = 0; int32_t frame_size = 0, variant = 0; bool c128 = false, zero_copy = false;
+    const void* pin = nullptr; const void* slab = nullptr; const void* out = nullptr; const void* out_pin = nullptr;
+    const void* ws = nullptr;      // the workspace the captured kernel node points into
+    size_t slot = 0;
+    uint32_t mask = AMCX_FEATURES_ALL;   // the feature mask the captured kernels were launched for
+    bool operator==(const GraphKey& o) const {
+      return frames == o.frames && frame_size == o.frame_size && variant == o.variant && c128 == o.c128 &&
+             zero_copy == o.zero_copy && pin == o.pin && slab == o.slab && out == o.out && out_pin == o.out_pin &&
+             ws == o.ws && slot == o.slot && mask == o.mask;
+    }
+  };
+  struct SmallGraph {
+    hipGraphExec_t exec = nullptr;
+    GraphKey key;
+  };
+  SmallGraph graphs[4];
+  int graph_next = 0;               // slot the next capture replaces
+  int graph_hits = 0, graph_misses = 0;
+  bool graphs_ok = true;            // false: capture failed once, or the calls vary too much for a cache of four
+  // calls in flight on this context (a context serves one call at a time; the counter is there so that
+  // amcx_ctx_bind_cpus can refuse to rebuild the staging pool's binding under a running upload)
+  std::atomic<int> in_call{0};
+  // amcx_ctx_set_feature_mask: the features every later host-buffer call computes (read once per call)
+  std::atomic<uint32_t> feature_mask{AMCX_FEATURES_ALL};
+};
 
 namespace {
 
@@ -56,15 +111,16 @@ int resolve_variant(int32_t frame_size, int32_t variant) {
 
 // CUs of the calling thread's current device (cached per device: a node may mix partitioned and whole GPUs)
 int cu_count() {
-  static int cus[64] = {};   // benign race: every writer of a slot stores the same value
+  static std::atomic<int> cus[amcx::kMaxDevices];   // every writer of a slot stores the same value
   int dev = 0, n = 0;
   if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
-  if (dev >= 0 && dev < 64 && cus[dev] > 0) return cus[dev];
+  const bool known = dev >= 0 && dev < amcx::kMaxDevices;
+  if (known && (n = cus[dev].load(std::memory_order_relaxed)) > 0) return n;
   if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
     (void)hipGetLastError();
     return 256;
   }
-  if (dev >= 0 && dev < 64) cus[dev] = n;
+  if (known) cus[dev].store(n, std::memory_order_relaxed);
   return n;
 }
 
@@ -157,29 +213,13 @@ StreamPlan stream_plan(int32_t N, int64_t n_frames) {
   StreamPlan p;
   p.M = amcx::stream::conv_length(N);
   p.chirped = !is_pow2(N);
-  p.grid = cu_count();                                   // one resident workgroup per CU, grid-stride beyond
-  if (p.grid > n_frames) p.grid = n_frames;
-  if (p.grid < 1) p.grid = 1;
+  p.grid = amcx::persistent_grid(cu_count(), 1, n_frames, 1);   // one resident workgroup per CU, grid-stride beyond
   return p;
 }
 
-int set_stream_lds_once(const void* kern, int which) {
-  static bool attr_set[3][64] = {};                      // once per (kernel, device), to the most any frame size asks for
-  int dev = 0;
-  AMCX_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_set[which][dev]) {
-    const size_t most = which == 0 ? amcx::stream::lds_bytes(amcx::stream::kMaxN)
-                        : which == 1 ? amcx::stream::lds_bytes_fft(amcx::stream::kMaxN)
-                                     : (size_t)amcx::stream::kTileBytes + amcx::stream::kFftTabBytes;
-    AMCX_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
-    if (dev >= 0 && dev < 64) attr_set[which][dev] = true;   // benign race: idempotent
-  }
-  return AMCX_OK;
-}
-
-int launch_stream(const float2* iq, int64_t n_frames, int32_t N, int64_t row_stride, float* out,
-                  int64_t out_stride, hipStream_t stream, void* ws, int64_t ws_bytes) {
-  StreamPlan p = stream_plan(N, n_frames);
+int launch_stream(const amcx::Frames& a, int32_t N, void* ws, int64_t ws_bytes) {
+  namespace st = amcx::stream;
+  StreamPlan p = stream_plan(N, a.n_frames);
   const int64_t per = (int64_t)p.M * (int64_t)sizeof(float2);
   int64_t fit = ws != nullptr && ws_bytes > 0 ? ws_bytes / per - (p.chirped ? 1 : 0) : 0;   // workgroups the workspace has room for
   if (fit >= 1 && (reinterpret_cast<uintptr_t>(ws) & 7u) == 0) {
@@ -188,67 +228,50 @@ int launch_stream(const float2* iq, int64_t n_frames, int32_t N, int64_t row_str
     const float2* bspec = nullptr;
     float2* bufs = base;
     if (p.chirped) {
-      auto chirp = amcx::stream::amcx_stream_chirp_kernel;
-      const int rc = set_stream_lds_once(reinterpret_cast<const void*>(chirp), 2);
-      if (rc != AMCX_OK) return rc;
-      hipLaunchKernelGGL(chirp, dim3(1), dim3(amcx::stream::kThreads),
-                         (size_t)amcx::stream::kTileBytes + amcx::stream::kFftTabBytes, stream, base, (int)N, p.M);
-      AMCX_HIP(hipGetLastError());
+      constexpr auto chirp = st::amcx_stream_chirp_kernel;
+      constexpr int lds = st::kTileBytes + st::kFftTabBytes;
+      AMCX_HIP(amcx::lds_attr_once<chirp>(lds));
+      AMCX_HIP(amcx::launch(chirp, 1, st::kThreads, lds, a.stream, base, N, p.M));
       bspec = base;
       bufs = base + p.M;
     }
-    auto kern = amcx::stream::amcx_features18_stream_kernel<true>;
-    const int rc = set_stream_lds_once(reinterpret_cast<const void*>(kern), 1);
-    if (rc != AMCX_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(amcx::stream::kThreads), amcx::stream::lds_bytes_fft(N), stream,
-                       iq, (long long)n_frames, (int)N, (long long)row_stride, out, (long long)out_stride, bspec, bufs, p.M);
-    AMCX_HIP(hipGetLastError());
+    constexpr auto kern = st::amcx_features18_stream_kernel<true>;
+    AMCX_HIP(amcx::lds_attr_once<kern>((int)st::lds_bytes_fft(st::kMaxN)));
+    AMCX_HIP(amcx::launch(kern, p.grid, st::kThreads, st::lds_bytes_fft(N), a.stream, a.iq, a.n_frames, N, a.row_stride, a.out,
+                          a.out_stride, bspec, bufs, p.M));
     return AMCX_OK;
   }
-  auto kern = amcx::stream::amcx_features18_stream_kernel<false>;
-  const int rc = set_stream_lds_once(reinterpret_cast<const void*>(kern), 0);
-  if (rc != AMCX_OK) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(amcx::stream::kThreads), amcx::stream::lds_bytes(N), stream, iq,
-                     (long long)n_frames, (int)N, (long long)row_stride, out, (long long)out_stride,
-                     static_cast<const float2*>(nullptr), static_cast<float2*>(nullptr), 0);
-  AMCX_HIP(hipGetLastError());
+  constexpr auto kern = st::amcx_features18_stream_kernel<false>;
+  AMCX_HIP(amcx::lds_attr_once<kern>((int)st::lds_bytes(st::kMaxN)));
+  AMCX_HIP(amcx::launch(kern, p.grid, st::kThreads, st::lds_bytes(N), a.stream, a.iq, a.n_frames, N, a.row_stride, a.out,
+                        a.out_stride, nullptr, nullptr, 0));
   return AMCX_OK;
 }
 
-int launch_block(const float2* iq, int64_t n_frames, int32_t N, int64_t row_stride, float* out,
-                 int64_t out_stride, hipStream_t stream, void* ws = nullptr, int64_t ws_bytes = 0) {
-  if (N > amcx::kBlockMaxN) return launch_stream(iq, n_frames, N, row_stride, out, out_stride, stream, ws, ws_bytes);
-  const int mode = block_mode(N);
-  const size_t lds = (mode == amcx::kBlockBluestein      ? (size_t)16 * amcx::bluestein_length(N)
-                      : mode == amcx::kBlockBluesteinBig ? (size_t)8 * amcx::kBluesteinBigM
+template <int MODE>
+int launch_block_mode(const amcx::Frames& a, int32_t N) {
+  constexpr auto kern = amcx::amcx_features18_block_kernel<MODE>;
+  constexpr int kMaxLds = 16 * amcx::kBlockMaxN + amcx::kBlockScratchBytes + amcx::kBlockTwiddleBytes;
+  const size_t lds = (MODE == amcx::kBlockBluestein      ? (size_t)16 * amcx::bluestein_length(N)
+                      : MODE == amcx::kBlockBluesteinBig ? (size_t)8 * amcx::kBluesteinBigM
                                                          : (size_t)16 * N) +
                      amcx::kBlockScratchBytes + amcx::kBlockTwiddleBytes;
-  auto kern = mode == amcx::kBlockPow2           ? amcx::amcx_features18_block_kernel<amcx::kBlockPow2>
-              : mode == amcx::kBlockBluestein    ? amcx::amcx_features18_block_kernel<amcx::kBlockBluestein>
-              : mode == amcx::kBlockBluesteinBig ? amcx::amcx_features18_block_kernel<amcx::kBlockBluesteinBig>
-                                                 : amcx::amcx_features18_block_kernel<amcx::kBlockDirect>;
-  // > 64 KiB of dynamic LDS needs the attribute.  It is set once per (kernel, device) to the most any
-  // frame size can ask for, never per launch: two host threads launching different N would otherwise
-  // race between one's attribute and the other's launch.
-  {
-    static bool attr_set[4][64] = {};
-    constexpr int kMaxLds = 16 * amcx::kBlockMaxN + amcx::kBlockScratchBytes + amcx::kBlockTwiddleBytes;
-    int dev = 0;
-    AMCX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[mode][dev]) {
-      AMCX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-      if (dev >= 0 && dev < 64) attr_set[mode][dev] = true;   // benign race: idempotent
-    }
-  }
+  AMCX_HIP(amcx::lds_attr_once<kern>(kMaxLds));
   // enough workgroups to fill every CU at the occupancy LDS allows, grid-stride beyond
   const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
-  int64_t grid = (int64_t)cu_count() * (per_cu > 8 ? 8 : per_cu) * 4;
-  if (grid > n_frames) grid = n_frames;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(amcx::kBlockThreads), lds, stream, iq,
-                     (long long)n_frames, (int)N, (long long)row_stride, out, (long long)out_stride);
-  AMCX_HIP(hipGetLastError());
+  const int64_t grid = amcx::persistent_grid(a.cus, (per_cu > 8 ? 8 : per_cu) * 4, a.n_frames, 1);
+  AMCX_HIP(amcx::launch(kern, grid, amcx::kBlockThreads, lds, a.stream, a.iq, a.n_frames, N, a.row_stride, a.out, a.out_stride));
   return AMCX_OK;
+}
+
+int launch_block(const amcx::Frames& a, int32_t N, void* ws = nullptr, int64_t ws_bytes = 0) {
+  if (N > amcx::kBlockMaxN) return launch_stream(a, N, ws, ws_bytes);
+  switch (block_mode(N)) {
+    case amcx::kBlockPow2: return launch_block_mode<amcx::kBlockPow2>(a, N);
+    case amcx::kBlockBluestein: return launch_block_mode<amcx::kBlockBluestein>(a, N);
+    case amcx::kBlockBluesteinBig: return launch_block_mode<amcx::kBlockBluesteinBig>(a, N);
+    default: return launch_block_mode<amcx::kBlockDirect>(a, N);
+  }
 }
 
 // The instruction-issue ceiling under the board's power cap: 16 wavefronts per CU (4 per SIMD, the N = 2048 kernel's
@@ -306,124 +329,23 @@ __global__ __launch_bounds__(256) void amcx_probe_read_kernel(const float4* __re
   if (threadIdx.x == 0) partial[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
 }
 
+// ---- the feature entry: one validation, one dispatch ------------------------------------------------------------------
+bool valid_feature_mask(uint32_t mask) { return mask != 0 && (mask & ~(uint32_t)AMCX_FEATURES_ALL) == 0; }
 
-int features18_ws(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems, float* out_dev,
-                  int64_t out_row_stride, void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes,
-                  const RingSource& rings);
-
-}  // namespace
-
-extern "C" {
-
-int amcx_abi_version(void) { return AMCX_ABI_VERSION; }
-
-const char* amcx_strerror(int code) {
-  switch (code) {
-    case AMCX_OK: return "ok";
-    case AMCX_EINVAL: return "invalid argument (null pointer, negative count, stride or frame_size out of range)";
-    case AMCX_ENOTSUP: return "kernel variant does not support this frame_size";
-    case AMCX_EHIP: return "HIP runtime error (see amcx_last_hip_error)";
-    case AMCX_ENODEV: return "no usable gfx950 device";
-    case AMCX_ENOMEM: return "device memory allocation failed";
-    case AMCX_EIO: return "reading the container's file failed (see amcx_last_hip_error for the errno text)";
-    default: return "unknown amcx error code";
-  }
+// which kernel a feature mask runs (include/amcx.h): a plan kernel where one exists for (frame size, resolved
+// variant), the 18-feature kernel (+ the column mask) otherwise
+int subset_plan(int32_t N, int v, uint32_t mask) {
+  if ((mask & 1u) != 0 || v != AMCX_VARIANT_WAVE || !amcx::has_plan_kernels(N)) return amcx::kPlanAll;
+  return (mask & ~amcx::kMaskCumulants) == 0 ? amcx::kPlanCumulants : amcx::kPlanNoSpectral;
 }
 
-const char* amcx_last_hip_error(void) { return g_hip_err; }
-
-int amcx_device_count(void) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e == hipErrorNoDevice) return 0;
-  if (e != hipSuccess) return hip_fail(e, "hipGetDeviceCount");
-  int ok = 0;
-  for (int d = 0; d < n; ++d) {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, d) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ++ok;
-  }
-  return ok;
-}
-
-int64_t amcx_features18_workspace_bytes(int32_t frame_size, int64_t n_frames, int32_t variant) {
-  if (n_frames < 0) return -1;
-  const int v = resolve_variant(frame_size, variant);
-  if (v < 0) return -1;
-  if (v != AMCX_VARIANT_BLOCK || frame_size <= amcx::kBlockMaxN || n_frames == 0) return 0;
-  const StreamPlan p = stream_plan(frame_size, n_frames);
-  return (p.grid + (p.chirped ? 1 : 0)) * (int64_t)p.M * (int64_t)sizeof(float2);
-}
-
-int amcx_features18_c64_ws(const void* iq_dev, int64_t n_frames, int32_t frame_size,
-                           int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
-                           void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes) {
-  RingSource rings;
-  rings.pool = true;
-  return features18_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
-                       workspace_dev, workspace_bytes, rings);
-}
-
-}  // extern "C"
-
-namespace {
-
-int features18_ws(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems, float* out_dev,
-                  int64_t out_row_stride, void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes,
-                  const RingSource& rings) {
-  if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES)
-    return AMCX_EINVAL;
-  const int v = resolve_variant(frame_size, variant);
-  if (v < 0) return v;
-  if (n_frames == 0) return AMCX_OK;
-  if (iq_dev == nullptr || out_dev == nullptr) return AMCX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(iq_dev) & 7u) || (reinterpret_cast<uintptr_t>(out_dev) & 3u))
-    return AMCX_EINVAL;
-  if (on_another_device(iq_dev) || on_another_device(out_dev)) return AMCX_EINVAL;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const float2* iq = static_cast<const float2*>(iq_dev);
-  if (v == AMCX_VARIANT_WAVE) {
-    // N = 8192: four waves per frame (amcx_quad_kernel.h); 16384 / 32768: eight / sixteen (amcx_group_kernel.h); 128 / 256 / 512:
-    // four frames per wave (amcx_short_kernel.h); every other wave size: one wave per frame
-    hipError_t e;
-    if (frame_size == amcx::quad::kN)
-      e = amcx::quad::launch_quad(iq, n_frames, row_stride_elems, out_dev, out_row_stride, stream, cu_count());
-    else if (frame_size == amcx::group::G<8>::kN)
-      e = amcx::group::launch_group<8>(iq, n_frames, row_stride_elems, out_dev, out_row_stride, stream, cu_count());
-    else if (frame_size == amcx::group::G<16>::kN)
-      e = amcx::group::launch_group<16>(iq, n_frames, row_stride_elems, out_dev, out_row_stride, stream, cu_count());
-    else if (amcx::shortk::short_supports(frame_size))       // 128, 256, 512: four frames per wave (amcx_short_kernel.h)
-      e = amcx::shortk::launch_short(iq, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, stream, cu_count());
-    else
-      e = amcx::launch_wave(iq, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, stream, cu_count(),
-                            ring_for(rings, frame_size, stream));
-    if (e != hipSuccess) return hip_fail(e, "wave kernel launch");
-    // every throughput kernel (N = 128 ... 4096 one wave per frame, N = 8192 the quad, 16384 / 32768 the group) has re-run the frames outside its
-    // fp32 sums' range itself -- one launch, rows final -- and finished frames with a phase step within an angle rounding
-    // of +-pi in its finaliser.
-    return AMCX_OK;
-  }
-  if (workspace_dev != nullptr && on_another_device(workspace_dev)) return AMCX_EINVAL;
-  return launch_block(iq, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, stream, workspace_dev,
-                      workspace_bytes < 0 ? 0 : workspace_bytes);
-}
-
-}  // namespace
-
-extern "C" {
-
-int amcx_features18_c64_ex(const void* iq_dev, int64_t n_frames, int32_t frame_size,
-                           int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
-                           void* hip_stream, int32_t variant) {
-  // The any-size path above 8192 samples runs its FFT form through a workspace from the stream-ordered allocator
-  // (as amcx_group_stats_f32 does) -- unless the stream is being captured into a graph, or the allocator has nothing:
-  // then the DFT by its definition, which needs none (amcx_stream_kernel.h).  Everything else allocates nothing.
-  const int64_t want = n_frames > 0 && iq_dev != nullptr && out_dev != nullptr && row_stride_elems >= frame_size &&
-                               out_row_stride >= AMCX_NUM_FEATURES
-                           ? amcx_features18_workspace_bytes(frame_size, n_frames, variant) : 0;
-  if (want <= 0)
-    return amcx_features18_c64_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream,
-                                  variant, nullptr, 0);
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+// The any-size path above 8192 samples runs its FFT form through a workspace from the stream-ordered allocator
+// (as amcx_group_stats_f32 does) -- unless the stream is being captured into a graph, or the allocator has nothing:
+// then the DFT by its definition, which needs none (amcx_stream_kernel.h).  Everything else allocates nothing.
+int launch_block_own_ws(const amcx::Frames& a, int32_t N) {
+  const hipStream_t st = a.stream;
+  const int64_t want = amcx_features18_workspace_bytes(N, a.n_frames, AMCX_VARIANT_BLOCK);
+  if (want <= 0) return launch_block(a, N);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
   void* ws = nullptr;
@@ -439,11 +361,10 @@ int amcx_features18_c64_ex(const void* iq_dev, int64_t n_frames, int32_t frame_s
     static std::atomic<bool> said{false};
     if (verbose && !said.exchange(true))
       fprintf(stderr, "amcx: frame_size %d runs the DFT by its definition (O(N^2)): %s; amcx_features18_c64_ws with %lld "
-                      "bytes of workspace selects the FFT form\n", (int)frame_size,
+                      "bytes of workspace selects the FFT form\n", (int)N,
               cap != hipStreamCaptureStatusNone ? "the stream is being captured" : "hipMallocAsync had no workspace", (long long)want);
   }
-  const int rc = amcx_features18_c64_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride,
-                                        hip_stream, variant, ws, ws != nullptr ? want : 0);
+  const int rc = launch_block(a, N, ws, ws != nullptr ? want : 0);
   if (ws != nullptr) {
     const hipError_t fe = hipFreeAsync(ws, st);
     if (rc == AMCX_OK) AMCX_HIP(fe);
@@ -451,136 +372,63 @@ int amcx_features18_c64_ex(const void* iq_dev, int64_t n_frames, int32_t frame_s
   return rc;
 }
 
-int amcx_features18_c64(const void* iq_dev, int64_t n_frames, int32_t frame_size,
-                        int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
-                        void* hip_stream) {
-  return amcx_features18_c64_ex(iq_dev, n_frames, frame_size, row_stride_elems, out_dev,
-                                out_row_stride, hip_stream, AMCX_VARIANT_AUTO);
-}
+// where the any-size path's workspace comes from: the caller's (or none), or launch_block_own_ws
+struct Workspace {
+  void* dev = nullptr;
+  int64_t bytes = 0;
+  bool own = false;
+};
 
-}  // extern "C"
-
-namespace {
-
-bool valid_feature_mask(uint32_t mask) { return mask != 0 && (mask & ~(uint32_t)AMCX_FEATURES_ALL) == 0; }
-
-// which kernel amcx_features_c64_subset runs (include/amcx.h): a plan kernel where one exists for (frame size, resolved
-// variant), the 18-feature kernel (+ the column mask) otherwise
-int subset_plan(int32_t N, int v, uint32_t mask) {
-  if ((mask & 1u) != 0 || v != AMCX_VARIANT_WAVE) return amcx::kPlanAll;
-  if (!amcx::shortk::short_supports(N) && N != 1024 && N != 2048 && N != 4096) return amcx::kPlanAll;
-  return (mask & ~amcx::kMaskCumulants) == 0 ? amcx::kPlanCumulants : amcx::kPlanNoSpectral;
-}
-
-int features_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
-                    float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
-                    void* workspace_dev, int64_t workspace_bytes, const RingSource& rings) {
+// Behind amcx_features18_c64_ws / _ex, amcx_features_c64_subset and the contexts (ctx_features); feature_mask is
+// AMCX_FEATURES_ALL for the 18-feature entries.  The order of the checks is part of the ABI (tests/c_abi/abi_check.c).
+int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems, float* out_dev,
+                 int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask, const Workspace& ws,
+                 const RingSource& rings) {
   if (!valid_feature_mask(feature_mask)) return AMCX_EINVAL;
   if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES) return AMCX_EINVAL;
   const int v = resolve_variant(frame_size, variant);
   if (v < 0) return v;
   if (n_frames == 0) return AMCX_OK;
   if (iq_dev == nullptr || out_dev == nullptr) return AMCX_EINVAL;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const int plan = subset_plan(frame_size, v, feature_mask);
-  if (plan == amcx::kPlanAll) {
-    const int rc = features18_ws(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride,
-                                 hip_stream, variant, workspace_dev, workspace_bytes, rings);
-    if (rc != AMCX_OK || feature_mask == (uint32_t)AMCX_FEATURES_ALL) return rc;
-    int64_t grid = (n_frames * AMCX_NUM_FEATURES + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(amcx::amcx_mask_columns_kernel, dim3((unsigned)grid), dim3(256), 0, stream, out_dev, (long long)n_frames,
-                       (long long)out_row_stride, (unsigned)feature_mask);
-    AMCX_HIP(hipGetLastError());
-    return AMCX_OK;
-  }
   if ((reinterpret_cast<uintptr_t>(iq_dev) & 7u) || (reinterpret_cast<uintptr_t>(out_dev) & 3u)) return AMCX_EINVAL;
   if (on_another_device(iq_dev) || on_another_device(out_dev)) return AMCX_EINVAL;
-  const float2* iq = static_cast<const float2*>(iq_dev);
-  const bool short_n = amcx::shortk::short_supports(frame_size);
-  float* const ring = short_n ? nullptr : ring_for(rings, frame_size, stream);
-  hipError_t e;
-  if (plan == amcx::kPlanCumulants)
-    e = short_n ? amcx::shortk::launch_short_subset<amcx::kPlanCumulants>(iq, n_frames, frame_size, row_stride_elems, out_dev,
-                                                                         out_row_stride, stream, cu_count(), feature_mask)
-                : amcx::launch_wave_subset<amcx::kPlanCumulants>(iq, n_frames, frame_size, row_stride_elems, out_dev,
-                                                                 out_row_stride, stream, cu_count(), ring, feature_mask);
-  else
-    e = short_n ? amcx::shortk::launch_short_subset<amcx::kPlanNoSpectral>(iq, n_frames, frame_size, row_stride_elems, out_dev,
-                                                                          out_row_stride, stream, cu_count(), feature_mask)
-                : amcx::launch_wave_subset<amcx::kPlanNoSpectral>(iq, n_frames, frame_size, row_stride_elems, out_dev,
-                                                                  out_row_stride, stream, cu_count(), ring, feature_mask);
-  if (e != hipSuccess) return hip_fail(e, "feature-subset kernel launch");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const amcx::Frames frames{static_cast<const float2*>(iq_dev), n_frames, row_stride_elems, out_dev, out_row_stride, stream, cu_count()};
+  const int plan = subset_plan(frame_size, v, feature_mask);
+  int rc;
+  if (v == AMCX_VARIANT_WAVE) {
+    // Every throughput kernel (amcx_launch.h, THE FRAME-SIZE TABLE) has re-run the frames outside its fp32 sums' range
+    // itself -- one launch, rows final -- and finished frames with a phase step within an angle rounding of +-pi in its
+    // finaliser.
+    float* const ring = ring_for(rings, frame_size, stream);
+    auto launch_plan = [&](auto plan_c) {       // (subset_plan names a plan only where the size has its kernels)
+      return amcx::for_frame_size(frame_size, [&](auto size) {
+        using S = decltype(size);
+        constexpr int kPlan = S::kPlanStem != nullptr ? decltype(plan_c)::value : amcx::kPlanAll;
+        return S::template launch<kPlan>(frames, ring, feature_mask);
+      });
+    };
+    using std::integral_constant;               // (kPlanAll stands first: KERNEL ORDER, amcx_launch.h)
+    const hipError_t e = plan == amcx::kPlanAll         ? launch_plan(integral_constant<int, amcx::kPlanAll>{})
+                         : plan == amcx::kPlanCumulants ? launch_plan(integral_constant<int, amcx::kPlanCumulants>{})
+                                                        : launch_plan(integral_constant<int, amcx::kPlanNoSpectral>{});
+    if (e != hipSuccess) return hip_fail(e, plan == amcx::kPlanAll ? "wave kernel launch" : "feature-subset kernel launch");
+    rc = AMCX_OK;
+  } else if (ws.own) {
+    rc = launch_block_own_ws(frames, frame_size);
+  } else {
+    if (ws.dev != nullptr && on_another_device(ws.dev)) return AMCX_EINVAL;
+    rc = launch_block(frames, frame_size, ws.dev, ws.bytes < 0 ? 0 : ws.bytes);
+  }
+  // a plan kernel has written NaN into the columns outside the mask itself
+  if (rc != AMCX_OK || plan != amcx::kPlanAll || feature_mask == (uint32_t)AMCX_FEATURES_ALL) return rc;
+  int64_t grid = (n_frames * AMCX_NUM_FEATURES + 255) / 256;
+  if (grid > 8192) grid = 8192;
+  AMCX_HIP(amcx::launch(amcx::amcx_mask_columns_kernel, grid, 256, 0, stream, out_dev, n_frames, out_row_stride, feature_mask));
   return AMCX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
-                             float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
-                             void* workspace_dev, int64_t workspace_bytes) {
-  RingSource rings;
-  rings.pool = true;
-  return features_subset(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
-                         feature_mask, workspace_dev, workspace_bytes, rings);
-}
-
-// ---- host-buffer entry points over a reusable context --------------------------------------
-// The context owns two streams, pinned staging slots and device scratch that only ever grow, so a
-// loop of per-frame calls (the reference's usage pattern, features.py:214-232 called once per queue
-// item) pays two small copies and the launches, not hipMalloc/hipFree/stream creation per call, and
-// a whole container goes up through the staged, overlapped path (ctx_run_strided).
-struct amcx_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  float* d_out = nullptr; size_t out_cap = 0;
-  // strided containers (amcx_ctx_features18_strided_host): staging pool, three pinned slots, a second stream
-  amcx::Pool pool;
-  int threads = 0;                               // 0: not yet sized
-  size_t slot_bytes = size_t(32) << 20;
-  bool round_on_device = false;
-  hipStream_t copy_stream = nullptr;
-  char* pin = nullptr;     size_t pin_cap = 0;   // kPinSlots x slot
-  void* d_slab = nullptr;  size_t slab_cap = 0;  // 2 x slot: uploaded chunks
-  void* d_frames = nullptr; size_t frames_cap = 0;   // plane-major sources: the frame-major complex64 image
-  void* d_ws = nullptr; size_t ws_cap = 0;           // the any-size path's FFT workspace (frame sizes above 8192, amcx_features18_c64_ws)
-  void* d_ring = nullptr; size_t ring_cap = 0;       // the wave kernels' ring of stash rows (RingSource): this context's launches only
-  hipEvent_t up_done[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t slab_free[2] = {nullptr, nullptr};
-  float* out_pin = nullptr; size_t out_pin_cap = 0;   // the result lands in pinned memory first
-  amcx_upload_stats stats = {};
-  // host placement (amcx_upload.h, NumaPlace): the CPUs local to this device; staging threads, the calling thread for the
-  // duration of a threaded upload, and with it the pinned slots it allocates, stay on them.  Empty: nothing is bound.
-  char pci_bus_id[32] = {0};
-  int numa_node = -1;
-  std::vector<int> bind_cpus;
-  // small row-major calls (a loop of per-frame calculate_features calls): the copy in, the launches and the copy
-  // out as ONE instantiated graph per (frames, frame size, variant, element type, buffers), relaunched
-  struct SmallGraph {
-    hipGraphExec_t exec = nullptr;
-    int64_t frames = 0; int32_t frame_size = 0, variant = 0; bool c128 = false, zero_copy = false;
-    const void* pin = nullptr; const void* slab = nullptr; const void* out = nullptr; const void* out_pin = nullptr;
-    const void* ws = nullptr;      // the workspace the captured kernel node points into
-    size_t slot = 0;
-    uint32_t mask = AMCX_FEATURES_ALL;   // the feature mask the captured kernels were launched for
-  };
-  SmallGraph graphs[4];
-  int graph_next = 0;               // slot the next capture replaces
-  int graph_hits = 0, graph_misses = 0;
-  bool graphs_ok = true;            // false: capture failed once, or the calls vary too much for a cache of four
-  // calls in flight on this context (a context serves one call at a time; the counter is there so that
-  // amcx_ctx_bind_cpus can refuse to rebuild the staging pool's binding under a running upload)
-  std::atomic<int> in_call{0};
-  // amcx_ctx_set_feature_mask: the features every later host-buffer call computes (read once per call)
-  std::atomic<uint32_t> feature_mask{AMCX_FEATURES_ALL};
-};
-
-}  // extern "C"
-
-namespace {
-
+// ---- host-buffer entry points over a reusable context: the helpers ---------------------------------------------------------
 int ctx_reserve(void** p, size_t* cap, size_t bytes) {
   if (*cap >= bytes) return AMCX_OK;
   if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
@@ -609,15 +457,12 @@ void ctx_reserve_ws(amcx_ctx* c, int32_t N, int64_t frames, int32_t variant) {
 
 int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant, uint32_t mask) {
   const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
-  const bool have = want > 0 && c->d_ws != nullptr && c->ws_cap >= (size_t)want;
+  Workspace ws;
+  if (want > 0 && c->d_ws != nullptr && c->ws_cap >= (size_t)want) { ws.dev = c->d_ws; ws.bytes = want; }
   RingSource rings;
   rings.own = static_cast<float*>(c->d_ring);
   rings.own_bytes = c->ring_cap;
-  if (mask != (uint32_t)AMCX_FEATURES_ALL)
-    return features_subset(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask,
-                           have ? c->d_ws : nullptr, have ? want : 0, rings);
-  return features18_ws(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, have ? c->d_ws : nullptr,
-                       have ? want : 0, rings);
+  return run_features(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask, ws, rings);
 }
 
 struct DeviceGuard {
@@ -674,6 +519,219 @@ int strided_prepare(amcx_ctx* c, size_t slot, size_t dslot, size_t frames_bytes,
   return rc;
 }
 
+// a staging thread could not read the container's file
+int io_fail(int err) {
+  snprintf(g_hip_err, sizeof g_hip_err, "reading the container's file: %s", strerror(err));
+  return AMCX_EIO;
+}
+
+// One call of ctx_run_strided: what its prologue worked out, for run_small_graph and run_chunked.
+struct StridedCall {
+  amcx::Source src;
+  amcx::RunMap map;
+  std::atomic<int> io_error{0};
+  int64_t S = 0, K = 0, F = 0;
+  int32_t N = 0;
+  int v = 0;                       // the resolved variant
+  uint32_t mask = AMCX_FEATURES_ALL;
+  bool rows = false, inner_snr = false, as_c128 = false, threaded = false;
+  size_t esz = 8;                  // staged bytes per element
+  int64_t unit = 0, n_units = 0;   // staged elements per chunk unit (a frame / a plane), and how many
+  size_t total_staged = 0, slot = 0, dslot = 0;
+  float* out_host = nullptr;
+  int64_t out_row_stride = 0;
+  amcx_upload_stats st = {};
+  double t_start = 0, t_loop = 0;
+};
+
+// rows of complex128 in a device slot, rounded to complex64 into the room behind the slot
+hipError_t round_rows_on_device(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, const void** d_rows) {
+  float2* rounded = reinterpret_cast<float2*>(dev + q.slot);
+  *d_rows = rounded;
+  return amcx::launch(amcx::amcx_c128_to_c64_kernel, 2048, 256, 0, c->stream, reinterpret_cast<const double2*>(dev), frames,
+                      q.N, q.N, rounded);
+}
+
+// the result is in pinned memory: spread it over the caller's row stride, and close the call's statistics
+void finish_strided(amcx_ctx* c, StridedCall& q, bool copy_out, double t_tail) {
+  if (copy_out) {
+    if (q.out_row_stride == AMCX_NUM_FEATURES) {
+      memcpy(q.out_host, c->out_pin, sizeof(float) * AMCX_NUM_FEATURES * (size_t)q.F);
+    } else {
+      for (int64_t g = 0; g < q.F; ++g)
+        memcpy(q.out_host + (size_t)g * (size_t)q.out_row_stride, c->out_pin + (size_t)g * AMCX_NUM_FEATURES,
+               sizeof(float) * AMCX_NUM_FEATURES);
+    }
+  }
+  q.st.seconds_tail = wall_now() - t_tail;
+  q.st.seconds = wall_now() - q.t_start;
+  c->stats = q.st;
+}
+
+// ---- small row-major calls: one graph launch ------------------------------------------------------------------
+// A per-frame loop (the reference's calculate_features per queue item, features.py:214-232) is launch-bound: copy in,
+// one or two conversions / kernels, copy out, a synchronisation -- seven runtime calls around 10 us of
+// GPU work.  Captured once per shape into a graph on the compute stream, a call is: stage into the pinned slot,
+// hipGraphLaunch, hipStreamSynchronize.  Anything that does not fit (several chunks, planes, staging threads) and any
+// failure to capture takes the general path (run_chunked): then this returns false.  True: *rc is the call's result.
+// (The workspace and the ring were reserved before this: ctx_reserve_ws.)
+bool run_small_graph(amcx_ctx* c, StridedCall& q, amcx::Pool& inline_pool, int* rc) {
+  if (!q.rows || q.threaded || q.total_staged > q.slot || !c->graphs_ok || getenv("AMCX_NO_GRAPH") != nullptr) return false;   // one chunk
+  char* pinned = c->pin;
+  char* dev = static_cast<char*>(c->d_slab);
+  const size_t bytes = (size_t)q.n_units * (size_t)q.unit * q.esz;
+  const size_t out_bytes = sizeof(float) * AMCX_NUM_FEATURES * (size_t)q.F;
+  const double t0 = wall_now();
+  amcx::stage_runs(inline_pool, pinned, q.src, q.map, 0, q.n_units, q.as_c128);
+  q.st.seconds_staging += wall_now() - t0;
+  if (q.io_error.load() != 0) { *rc = io_fail(q.io_error.load()); return true; }
+  amcx_ctx::GraphKey key;
+  key.frames = q.F; key.frame_size = q.N; key.variant = q.v; key.c128 = q.as_c128;
+  // a few frames of complex64: the kernels read the pinned slot and write the pinned result themselves (host memory
+  // from hipHostMalloc is mapped into the device's address space) -- two copy nodes fewer in the graph
+  key.zero_copy = !q.as_c128 && bytes <= (size_t(64) << 10) && getenv("AMCX_NO_ZERO_COPY") == nullptr;
+  key.pin = pinned; key.slab = dev; key.out = c->d_out; key.out_pin = c->out_pin; key.ws = c->d_ws; key.slot = q.slot;
+  key.mask = q.mask;
+  amcx_ctx::SmallGraph* g = nullptr;
+  for (auto& cand : c->graphs)
+    if (cand.exec && cand.key == key) g = &cand;
+  if (g != nullptr) {
+    ++c->graph_hits;
+  } else {
+    ++c->graph_misses;
+    if (c->graph_misses > 64 && c->graph_misses > 4 * c->graph_hits) c->graphs_ok = false;   // shapes keep changing
+    amcx_ctx::SmallGraph& slot_g = c->graphs[c->graph_next];
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    int crc = AMCX_OK;
+    hipError_t ce = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
+    if (ce == hipSuccess && key.zero_copy) {
+      crc = ctx_features(c, pinned, q.F, q.N, c->out_pin, q.v, q.mask);
+      ce = hipStreamEndCapture(c->stream, &graph);
+    } else if (ce == hipSuccess) {
+      ce = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, c->stream);
+      const void* d_rows = dev;
+      if (ce == hipSuccess && q.as_c128) ce = round_rows_on_device(c, q, dev, q.F, &d_rows);
+      if (ce == hipSuccess) crc = ctx_features(c, d_rows, q.F, q.N, c->d_out, q.v, q.mask);
+      if (ce == hipSuccess && crc == AMCX_OK)
+        ce = hipMemcpyAsync(c->out_pin, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+      const hipError_t ee = hipStreamEndCapture(c->stream, &graph);      // always ends the capture
+      if (ce == hipSuccess) ce = ee;
+    }
+    if (ce == hipSuccess && crc == AMCX_OK && graph != nullptr) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (graph != nullptr) (void)hipGraphDestroy(graph);
+    if (ce != hipSuccess || crc != AMCX_OK || exec == nullptr) {
+      (void)hipGetLastError();
+      c->graphs_ok = false;                 // the general path takes this call and every later one
+      return false;
+    }
+    if (slot_g.exec) (void)hipGraphExecDestroy(slot_g.exec);
+    slot_g.exec = exec;
+    slot_g.key = key;
+    c->graph_next = (c->graph_next + 1) % 4;
+    g = &slot_g;
+  }
+  q.st.seconds_prepare = q.t_loop - q.t_start;
+  const double t_tail = wall_now();
+  const hipError_t e = hipGraphLaunch(g->exec, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess || e2 != hipSuccess) {
+    *rc = hip_fail(e != hipSuccess ? e : e2, "amcx_ctx_features18 (graph launch)");
+    return true;
+  }
+  q.st.pcie_bytes = (int64_t)bytes; q.st.chunks = 1;
+  finish_strided(c, q, true, t_tail);
+  *rc = AMCX_OK;
+  return true;
+}
+
+// ---- the general path: chunks staged by the pool, uploaded on the copy stream, computed on the compute stream ------------
+int run_chunked(amcx_ctx* c, StridedCall& q, amcx::Pool& pool) {
+  amcx_upload_stats& st = q.st;
+  const int64_t F = q.F, unit = q.unit, n_units = q.n_units;
+  const int32_t N = q.N;
+  const size_t esz = q.esz, slot = q.slot;
+  int rc = AMCX_OK;
+  hipError_t e = hipSuccess;
+  const int64_t units_per_slot = (int64_t)(slot / ((size_t)unit * esz));
+  int64_t u = 0;
+  for (int ch = 0; u < n_units && rc == AMCX_OK; ++ch) {
+    // the first chunks are small so that the link starts early and staging overlaps it from the start:
+    // 2, 2, 4, 4, 8, 8 ... MiB staged, up to whole slots (a 16 MB modulation of BASELINE configs[0] is five chunks)
+    int64_t take = units_per_slot;
+    if (ch < 12) {
+      const int64_t ramp = (int64_t)((size_t(2) << 20 << (ch / 2)) / ((size_t)unit * esz));
+      if (ramp < take) take = ramp;
+    }
+    if (take < 1) take = 1;
+    if (take > n_units - u) take = n_units - u;
+    const int ps = ch % kPinSlots, ds = ch & 1;
+    char* pinned = c->pin + (size_t)ps * slot;
+    char* dev = static_cast<char*>(c->d_slab) + (size_t)ds * q.dslot;
+    const size_t bytes = (size_t)take * (size_t)unit * esz;
+    if (ch >= kPinSlots) {                                  // the upload that last read this pinned slot is done
+      const double t0 = wall_now();
+      e = hipEventSynchronize(c->up_done[ps]);
+      st.seconds_waiting += wall_now() - t0;
+      if (e != hipSuccess) break;
+    }
+    {
+      const double t0 = wall_now();
+      // rows: run = frame g; planes: a plane is map.cnt_b runs
+      const int64_t per_unit = q.rows ? 1 : q.map.cnt_b;
+      amcx::stage_runs(pool, pinned, q.src, q.map, u * per_unit, (u + take) * per_unit, q.as_c128);
+      st.seconds_staging += wall_now() - t0;
+      if (q.io_error.load() != 0) {                        // nothing of this chunk is queued; what is in flight is drained below
+        rc = io_fail(q.io_error.load());
+        break;
+      }
+    }
+    if (ch >= 2) { e = hipStreamWaitEvent(c->copy_stream, c->slab_free[ds], 0); if (e != hipSuccess) break; }
+    e = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, c->copy_stream);
+    if (e != hipSuccess) break;
+    e = hipEventRecord(c->up_done[ps], c->copy_stream);
+    if (e != hipSuccess) break;
+    e = hipStreamWaitEvent(c->stream, c->up_done[ps], 0);
+    if (e != hipSuccess) break;
+    st.pcie_bytes += (int64_t)bytes;
+    if (q.rows) {
+      const void* d_rows = dev;
+      if (q.as_c128) { e = round_rows_on_device(c, q, dev, take, &d_rows); if (e != hipSuccess) break; }
+      rc = ctx_features(c, d_rows, take, N, c->d_out + (size_t)u * AMCX_NUM_FEATURES, q.v, q.mask);
+    } else {
+      float2* frames = static_cast<float2*>(c->d_frames);
+      const int S = (int)q.S, inner = q.inner_snr ? 1 : 0;
+      e = q.as_c128 ? amcx::launch_pack_planes(reinterpret_cast<const double2*>(dev), (int)take, (long long)F, (long long)F,
+                                               S, (long long)q.K, inner, frames, (long long)N, (int)u, c->stream)
+                    : amcx::launch_pack_planes(reinterpret_cast<const float2*>(dev), (int)take, (long long)F, (long long)F,
+                                               S, (long long)q.K, inner, frames, (long long)N, (int)u, c->stream);
+      if (e != hipSuccess) break;
+    }
+    if (rc != AMCX_OK) break;
+    e = hipEventRecord(c->slab_free[ds], c->stream);
+    if (e != hipSuccess) break;
+    u += take;
+    st.chunks = ch + 1;
+  }
+  if (rc == AMCX_OK && e == hipSuccess && !q.rows)
+    rc = ctx_features(c, c->d_frames, F, N, c->d_out, q.v, q.mask);
+  const double t_tail = wall_now();
+  st.seconds_prepare = q.t_loop - q.t_start;
+  // the result comes back into pinned memory (a copy into the caller's pageable rows would be staged by the
+  // runtime, ~100 us for 72 KB) and is spread over the caller's row stride by the host
+  if (rc == AMCX_OK && e == hipSuccess)
+    e = hipMemcpyAsync(c->out_pin, c->d_out, sizeof(float) * AMCX_NUM_FEATURES * (size_t)F, hipMemcpyDeviceToHost, c->stream);
+  if (rc == AMCX_OK && e != hipSuccess) rc = hip_fail(e, "amcx_ctx_features18_strided_host");
+  // success or not, nothing of this call is in flight when it returns (every upload is ordered before the
+  // compute stream's last kernel by an event, so on success that stream alone says so)
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  hipError_t e1 = (rc == AMCX_OK && e2 == hipSuccess) ? hipSuccess : hipStreamSynchronize(c->copy_stream);
+  if (rc == AMCX_OK && (e1 != hipSuccess || e2 != hipSuccess))
+    rc = hip_fail(e1 != hipSuccess ? e1 : e2, "amcx_ctx_features18_strided_host (sync)");
+  finish_strided(c, q, rc == AMCX_OK, t_tail);
+  return rc;
+}
+
 // src: memory (re / im) or a file (fd, byte offsets); src.kind is checked here, src.io_error is set here
 int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
                     int32_t N, int64_t ss, int64_t sk, int64_t sn, float* out_host, int64_t out_row_stride,
@@ -693,238 +751,51 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
     explicit InCall(std::atomic<int>& c) : n(c) { n.fetch_add(1, std::memory_order_acq_rel); }
     ~InCall() { n.fetch_sub(1, std::memory_order_acq_rel); }
   } in_call(c->in_call);
-  const uint32_t mask = c->feature_mask.load(std::memory_order_acquire);
+  StridedCall q;
+  q.mask = c->feature_mask.load(std::memory_order_acquire);
   if (kind < AMCX_SRC_F32_SPLIT) { src.im = nullptr; src.im_off = -1; }
-  std::atomic<int> io_error{0};
-  src.io_error = &io_error;
-  const int64_t F = S * K;
-  bool rows = false, inner_snr = false;
-  amcx::RunMap map;
-  if (!classify_layout(S, K, N, ss, sk, sn, &rows, &inner_snr, &map)) return AMCX_ENOTSUP;
+  src.io_error = &q.io_error;
+  q.src = src;
+  q.S = S; q.K = K; q.N = N; q.v = v; q.out_host = out_host; q.out_row_stride = out_row_stride;
+  const int64_t F = q.F = S * K;
+  if (!classify_layout(S, K, N, ss, sk, sn, &q.rows, &q.inner_snr, &q.map)) return AMCX_ENOTSUP;
+  const bool rows = q.rows;
   if (!rows && S > 0x7fffffffLL) return AMCX_EINVAL;             // the transposition kernel indexes the snr axis with an int
-  const bool as_c128 = c->round_on_device && kind == AMCX_SRC_C128;
-  const size_t esz = as_c128 ? 16 : 8;
+  const bool as_c128 = q.as_c128 = c->round_on_device && kind == AMCX_SRC_C128;
+  const size_t esz = q.esz = as_c128 ? 16 : 8;
   const size_t src_esz = kind == AMCX_SRC_C64 ? 8 : kind == AMCX_SRC_C128 ? 16 : kind == AMCX_SRC_F32_SPLIT ? 4 : 8;
-  const int64_t unit = rows ? N : F;                      // staged elements per chunk unit (a frame / a plane)
-  const int64_t n_units = rows ? F : N;
+  const int64_t unit = q.unit = rows ? N : F;             // staged elements per chunk unit (a frame / a plane)
+  const int64_t n_units = q.n_units = rows ? F : N;
   size_t slot = c->slot_bytes;
-  const size_t total_staged = (size_t)unit * esz * (size_t)n_units;
+  const size_t total_staged = q.total_staged = (size_t)unit * esz * (size_t)n_units;
   if (slot > total_staged) slot = total_staged;                   // a per-frame call pins kilobytes, not 3 x 32 MiB
   if (slot < (size_t)unit * esz) slot = (size_t)unit * esz;       // a slot holds at least one frame / one plane
   if (slot > (size_t(4) << 30)) return AMCX_ENOMEM;               // > 4 GiB per plane: split the call by snr
   slot = (slot + 4095) & ~size_t(4095);
+  q.slot = slot;
 
   DeviceGuard guard;
   AMCX_HIP(guard.enter(c->device));
-  const double t_start = wall_now();
+  q.t_start = wall_now();
   // rows of complex128 rounded on the device: each device slot is followed by room for its rounded rows
-  const size_t dslot = (rows && as_c128) ? slot + slot / 2 : slot;
-  const bool threaded = total_staged >= (size_t(1) << 20);        // below 1 MiB a condition-variable wake costs more than the copy
+  q.dslot = (rows && as_c128) ? slot + slot / 2 : slot;
+  const bool threaded = q.threaded = total_staged >= (size_t(1) << 20);   // below 1 MiB a condition-variable wake costs more than the copy
   // an upload worth its staging threads runs on the device's own socket, this thread included: it stages, and the pinned
   // slots strided_prepare may allocate are placed where it runs (a per-frame call is not worth two affinity system calls)
   static const std::vector<int> kNoCpus;
   amcx::AffinityGuard on_local_cpus(threaded ? c->bind_cpus : kNoCpus);
-  int rc = strided_prepare(c, slot, dslot, rows ? 0 : (size_t)F * N * 8, sizeof(float) * AMCX_NUM_FEATURES * (size_t)F,
+  int rc = strided_prepare(c, slot, q.dslot, rows ? 0 : (size_t)F * N * 8, sizeof(float) * AMCX_NUM_FEATURES * (size_t)F,
                            threaded);
   if (rc != AMCX_OK) return rc;
-  ctx_reserve_ws(c, N, F, v);                                      // (frame sizes above 8192 only) before any capture below
+  ctx_reserve_ws(c, N, F, v);                                      // workspace and ring, before any capture below
   amcx::Pool inline_pool;                                          // size 1: stage_runs runs on the caller
-  amcx_upload_stats st = {};
   amcx::Pool& pool = threaded ? c->pool : inline_pool;
+  amcx_upload_stats& st = q.st;
   st.frames = F; st.threads = pool.size(); st.plane_major = rows ? 0 : 1; st.from_file = src.fd >= 0 ? 1 : 0;
   st.source_bytes = F * (int64_t)N * (int64_t)src_esz * ((kind >= AMCX_SRC_F32_SPLIT && src.has_im()) ? 2 : 1);
-
-  hipError_t e = hipSuccess;
-  const double t_loop = wall_now();
-  // ---- small row-major calls: one graph launch ------------------------------------------------------------------
-  // A per-frame loop (the reference's calculate_features per queue item, features.py:214-232) is launch-bound: copy in,
-  // one or two conversions / kernels, copy out, a synchronisation -- seven runtime calls around 10 us of
-  // GPU work.  Captured once per shape into a graph on the compute stream, a call is: stage into the pinned slot,
-  // hipGraphLaunch, hipStreamSynchronize.  Anything that does not fit (several chunks, planes, staging threads) and any
-  // failure to capture takes the general path below.
-  if (rows && !threaded && total_staged <= slot && c->graphs_ok && getenv("AMCX_NO_GRAPH") == nullptr) {   // one chunk
-    char* pinned = c->pin;
-    char* dev = static_cast<char*>(c->d_slab);
-    const size_t bytes = (size_t)n_units * (size_t)unit * esz;
-    const size_t out_bytes = sizeof(float) * AMCX_NUM_FEATURES * (size_t)F;
-    double t0 = wall_now();
-    amcx::stage_runs(inline_pool, pinned, src, map, 0, n_units, as_c128);
-    st.seconds_staging += wall_now() - t0;
-    if (io_error.load() != 0) {
-      snprintf(g_hip_err, sizeof g_hip_err, "reading the container's file: %s", strerror(io_error.load()));
-      return AMCX_EIO;
-    }
-    // a few frames of complex64: the kernels read the pinned slot and write the pinned result themselves (host memory
-    // from hipHostMalloc is mapped into the device's address space) -- two copy nodes fewer in the graph
-    const bool zero_copy = !as_c128 && bytes <= (size_t(64) << 10) && getenv("AMCX_NO_ZERO_COPY") == nullptr;
-    amcx_ctx::SmallGraph* g = nullptr;
-    for (auto& cand : c->graphs)
-      if (cand.exec && cand.frames == F && cand.frame_size == N && cand.variant == v && cand.c128 == as_c128 &&
-          cand.zero_copy == zero_copy &&
-          cand.pin == pinned && cand.slab == dev && cand.out == c->d_out && cand.out_pin == c->out_pin && cand.slot == slot &&
-          cand.ws == c->d_ws && cand.mask == mask)
-        g = &cand;
-    if (g != nullptr) {
-      ++c->graph_hits;
-    } else {
-      ++c->graph_misses;
-      if (c->graph_misses > 64 && c->graph_misses > 4 * c->graph_hits) c->graphs_ok = false;   // shapes keep changing
-      amcx_ctx::SmallGraph& slot_g = c->graphs[c->graph_next];
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
-      int crc = AMCX_OK;
-      hipError_t ce = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
-      if (ce == hipSuccess && zero_copy) {
-        crc = ctx_features(c, pinned, F, N, c->out_pin, v, mask);
-        const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-        ce = ee;
-      } else if (ce == hipSuccess) {
-        ce = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, c->stream);
-        const void* d_rows = dev;
-        if (ce == hipSuccess && as_c128) {
-          float2* rounded = reinterpret_cast<float2*>(dev + slot);
-          hipLaunchKernelGGL(amcx::amcx_c128_to_c64_kernel, dim3(2048), dim3(256), 0, c->stream,
-                             reinterpret_cast<const double2*>(dev), (long long)F, (int)N, (long long)N, rounded);
-          ce = hipGetLastError();
-          d_rows = rounded;
-        }
-        if (ce == hipSuccess) crc = ctx_features(c, d_rows, F, N, c->d_out, v, mask);
-        if (ce == hipSuccess && crc == AMCX_OK)
-          ce = hipMemcpyAsync(c->out_pin, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-        const hipError_t ee = hipStreamEndCapture(c->stream, &graph);      // always ends the capture
-        if (ce == hipSuccess) ce = ee;
-      }
-      if (ce == hipSuccess && crc == AMCX_OK && graph != nullptr) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      if (graph != nullptr) (void)hipGraphDestroy(graph);
-      if (ce != hipSuccess || crc != AMCX_OK || exec == nullptr) {
-        (void)hipGetLastError();
-        c->graphs_ok = false;                 // the general path takes this call and every later one
-      } else {
-        if (slot_g.exec) (void)hipGraphExecDestroy(slot_g.exec);
-        slot_g.exec = exec; slot_g.frames = F; slot_g.frame_size = N; slot_g.variant = v; slot_g.c128 = as_c128;
-        slot_g.zero_copy = zero_copy;
-        slot_g.pin = pinned; slot_g.slab = dev; slot_g.out = c->d_out; slot_g.out_pin = c->out_pin; slot_g.slot = slot;
-        slot_g.ws = c->d_ws;
-        slot_g.mask = mask;
-        c->graph_next = (c->graph_next + 1) % 4;
-        g = &slot_g;
-      }
-    }
-    if (g != nullptr) {
-      st.seconds_prepare = t_loop - t_start;
-      const double t_tail = wall_now();
-      e = hipGraphLaunch(g->exec, c->stream);
-      const hipError_t e2 = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, "amcx_ctx_features18 (graph launch)");
-      if (out_row_stride == AMCX_NUM_FEATURES) {
-        memcpy(out_host, c->out_pin, out_bytes);
-      } else {
-        for (int64_t gi = 0; gi < F; ++gi)
-          memcpy(out_host + (size_t)gi * (size_t)out_row_stride, c->out_pin + (size_t)gi * AMCX_NUM_FEATURES,
-                 sizeof(float) * AMCX_NUM_FEATURES);
-      }
-      st.pcie_bytes = (int64_t)bytes; st.chunks = 1;
-      st.seconds_tail = wall_now() - t_tail;
-      st.seconds = wall_now() - t_start;
-      c->stats = st;
-      return AMCX_OK;
-    }
-  }
-  const int64_t units_per_slot = (int64_t)(slot / ((size_t)unit * esz));
-  int64_t u = 0;
-  for (int ch = 0; u < n_units && rc == AMCX_OK; ++ch) {
-    // the first chunks are small so that the link starts early and staging overlaps it from the start:
-    // 2, 2, 4, 4, 8, 8 ... MiB staged, up to whole slots (a 16 MB modulation of BASELINE configs[0] is five chunks)
-    int64_t take = units_per_slot;
-    if (ch < 12) {
-      const int64_t ramp = (int64_t)((size_t(2) << 20 << (ch / 2)) / ((size_t)unit * esz));
-      if (ramp < take) take = ramp;
-    }
-    if (take < 1) take = 1;
-    if (take > n_units - u) take = n_units - u;
-    const int ps = ch % kPinSlots, ds = ch & 1;
-    char* pinned = c->pin + (size_t)ps * slot;
-    char* dev = static_cast<char*>(c->d_slab) + (size_t)ds * dslot;
-    const size_t bytes = (size_t)take * (size_t)unit * esz;
-    if (ch >= kPinSlots) {                                  // the upload that last read this pinned slot is done
-      const double t0 = wall_now();
-      e = hipEventSynchronize(c->up_done[ps]);
-      st.seconds_waiting += wall_now() - t0;
-      if (e != hipSuccess) break;
-    }
-    {
-      const double t0 = wall_now();
-      // rows: run = frame g; planes: a plane is map.cnt_b runs
-      const int64_t per_unit = rows ? 1 : map.cnt_b;
-      amcx::stage_runs(pool, pinned, src, map, u * per_unit, (u + take) * per_unit, as_c128);
-      st.seconds_staging += wall_now() - t0;
-      if (io_error.load() != 0) {                          // nothing of this chunk is queued; what is in flight is drained below
-        snprintf(g_hip_err, sizeof g_hip_err, "reading the container's file: %s", strerror(io_error.load()));
-        rc = AMCX_EIO;
-        break;
-      }
-    }
-    if (ch >= 2) { e = hipStreamWaitEvent(c->copy_stream, c->slab_free[ds], 0); if (e != hipSuccess) break; }
-    e = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, c->copy_stream);
-    if (e != hipSuccess) break;
-    e = hipEventRecord(c->up_done[ps], c->copy_stream);
-    if (e != hipSuccess) break;
-    e = hipStreamWaitEvent(c->stream, c->up_done[ps], 0);
-    if (e != hipSuccess) break;
-    st.pcie_bytes += (int64_t)bytes;
-    if (rows) {
-      const void* d_rows = dev;
-      if (as_c128) {
-        float2* rounded = reinterpret_cast<float2*>(dev + slot);
-        hipLaunchKernelGGL(amcx::amcx_c128_to_c64_kernel, dim3(2048), dim3(256), 0, c->stream,
-                           reinterpret_cast<const double2*>(dev), (long long)take, (int)N, (long long)N, rounded);
-        e = hipGetLastError();
-        if (e != hipSuccess) break;
-        d_rows = rounded;
-      }
-      rc = ctx_features(c, d_rows, take, N, c->d_out + (size_t)u * AMCX_NUM_FEATURES, v, mask);
-    } else {
-      float2* frames = static_cast<float2*>(c->d_frames);
-      e = as_c128 ? amcx::launch_pack_planes(reinterpret_cast<const double2*>(dev), (int)take, (long long)F, (long long)F,
-                                             (int)S, (long long)K, inner_snr ? 1 : 0, frames, (long long)N, (int)u, c->stream)
-                  : amcx::launch_pack_planes(reinterpret_cast<const float2*>(dev), (int)take, (long long)F, (long long)F,
-                                             (int)S, (long long)K, inner_snr ? 1 : 0, frames, (long long)N, (int)u, c->stream);
-      if (e != hipSuccess) break;
-    }
-    if (rc != AMCX_OK) break;
-    e = hipEventRecord(c->slab_free[ds], c->stream);
-    if (e != hipSuccess) break;
-    u += take;
-    st.chunks = ch + 1;
-  }
-  if (rc == AMCX_OK && e == hipSuccess && !rows)
-    rc = ctx_features(c, c->d_frames, F, N, c->d_out, v, mask);
-  const double t_tail = wall_now();
-  st.seconds_prepare = t_loop - t_start;
-  // the result comes back into pinned memory (a copy into the caller's pageable rows would be staged by the
-  // runtime, ~100 us for 72 KB) and is spread over the caller's row stride by the host
-  if (rc == AMCX_OK && e == hipSuccess)
-    e = hipMemcpyAsync(c->out_pin, c->d_out, sizeof(float) * AMCX_NUM_FEATURES * (size_t)F, hipMemcpyDeviceToHost, c->stream);
-  if (rc == AMCX_OK && e != hipSuccess) rc = hip_fail(e, "amcx_ctx_features18_strided_host");
-  // success or not, nothing of this call is in flight when it returns (every upload is ordered before the
-  // compute stream's last kernel by an event, so on success that stream alone says so)
-  hipError_t e2 = hipStreamSynchronize(c->stream);
-  hipError_t e1 = (rc == AMCX_OK && e2 == hipSuccess) ? hipSuccess : hipStreamSynchronize(c->copy_stream);
-  if (rc == AMCX_OK && (e1 != hipSuccess || e2 != hipSuccess))
-    rc = hip_fail(e1 != hipSuccess ? e1 : e2, "amcx_ctx_features18_strided_host (sync)");
-  if (rc == AMCX_OK) {
-    if (out_row_stride == AMCX_NUM_FEATURES) {
-      memcpy(out_host, c->out_pin, sizeof(float) * AMCX_NUM_FEATURES * (size_t)F);
-    } else {
-      for (int64_t g = 0; g < F; ++g)
-        memcpy(out_host + (size_t)g * (size_t)out_row_stride, c->out_pin + (size_t)g * AMCX_NUM_FEATURES,
-               sizeof(float) * AMCX_NUM_FEATURES);
-    }
-  }
-  st.seconds_tail = wall_now() - t_tail;
-  st.seconds = wall_now() - t_start;
-  c->stats = st;
-  return rc;
+  q.t_loop = wall_now();
+  if (run_small_graph(c, q, pool, &rc)) return rc;
+  return run_chunked(c, q, pool);
 }
 
 // the row-major host entries (amcx_ctx_features18_c64_host / _c128_host and their one-shot forms): a single-snr
@@ -939,9 +810,161 @@ int ctx_run(amcx_ctx* c, const void* iq_host, bool is_c128, int64_t n_frames, in
   return ctx_run_strided(c, src, 1, n_frames, frame_size, 0, row_stride_elems, 1, out_host, out_row_stride, variant);
 }
 
+int stage_any(amcx::Source src, int64_t n_snr, int64_t n_frames,
+                     int32_t frame_size, int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
+                     int64_t first_unit, int64_t n_units, void* dst, int64_t dst_bytes, int32_t threads,
+                     int32_t* plane_major, int32_t* inner_snr_out) {
+  const int32_t kind = src.kind;
+  if (n_snr < 0 || n_frames < 0 || stride_snr < 0 || stride_frame < 0 || stride_sample < 0 || first_unit < 0 ||
+      n_units < 0 || threads < 0 || threads > 256 || kind < AMCX_SRC_C64 || kind > AMCX_SRC_F64_SPLIT ||
+      frame_size < AMCX_MIN_FRAME_SIZE || frame_size > AMCX_MAX_FRAME_SIZE)
+    return AMCX_EINVAL;
+  if (n_frames > 0 && n_snr > (int64_t(1) << 40) / n_frames) return AMCX_EINVAL;
+  bool rows = false, inner_snr = false;
+  amcx::RunMap map;
+  if (!classify_layout(n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, &rows, &inner_snr, &map))
+    return AMCX_ENOTSUP;
+  if (plane_major) *plane_major = rows ? 0 : 1;
+  if (inner_snr_out) *inner_snr_out = inner_snr ? 1 : 0;
+  const int64_t F = n_snr * n_frames, unit = rows ? frame_size : F, total_units = rows ? F : frame_size;
+  if (first_unit + n_units > total_units) return AMCX_EINVAL;
+  if (n_units == 0 || unit == 0) return AMCX_OK;
+  if ((src.fd < 0 && src.re == nullptr) || dst == nullptr || dst_bytes < n_units * unit * 8) return AMCX_EINVAL;
+  if (kind < AMCX_SRC_F32_SPLIT) { src.im = nullptr; src.im_off = -1; }
+  std::atomic<int> io_error{0};
+  src.io_error = &io_error;
+  amcx::Pool pool;
+  pool.resize(threads < 1 ? 1 : threads);
+  const int64_t per_unit = rows ? 1 : map.cnt_b;
+  amcx::stage_runs(pool, static_cast<char*>(dst), src, map, first_unit * per_unit, (first_unit + n_units) * per_unit, false);
+  if (io_error.load() != 0) return io_fail(io_error.load());
+  return AMCX_OK;
+}
+
+// one-shot forms: a context for the duration of the call
+int one_shot(const void* iq_host, bool is_c128, int64_t n_frames, int32_t frame_size,
+                    int64_t row_stride_elems, float* out_host, int64_t out_row_stride, int32_t device,
+                    int32_t variant) {
+  // argument errors are reported before a device is looked for (tests/test_host_cpu.py runs without one)
+  if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES)
+    return AMCX_EINVAL;
+  const int v = resolve_variant(frame_size, variant);
+  if (v < 0) return v;
+  if (n_frames == 0) return AMCX_OK;
+  if (iq_host == nullptr || out_host == nullptr) return AMCX_EINVAL;
+  amcx_ctx* c = nullptr;
+  int rc = amcx_ctx_create(device, &c);
+  if (rc != AMCX_OK) return rc;
+  rc = ctx_run(c, iq_host, is_c128, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, v);
+  (void)amcx_ctx_destroy(c);
+  return rc;
+}
+
+// how a statistics call is cut: chunks per group and rows per chunk (whole tiles)
+void stats_plan(int64_t n_groups, int64_t rows_per_group, int n_cols, int64_t* chunks, int64_t* rows_per_chunk) {
+  const int64_t tile = amcx::stat_tile_rows(n_cols);
+  const int64_t tiles = (rows_per_group + tile - 1) / tile;
+  const int64_t target = 1024;                               // workgroups wanted in all (4 per CU, one resident round); the same on any device
+  int64_t want = (target + n_groups - 1) / n_groups;
+  if (want > tiles) want = tiles;
+  if (want < 1) want = 1;
+  const int64_t tiles_per_chunk = (tiles + want - 1) / want;
+  *rows_per_chunk = tiles_per_chunk * tile;
+  *chunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
+}
+
+bool stats_args_ok(int64_t n_groups, int64_t rows_per_group, int64_t row_stride, int32_t n_cols) {
+  return n_groups >= 0 && rows_per_group >= 1 && n_cols >= 1 && n_cols <= amcx::kStatMaxCols &&
+         row_stride >= n_cols && row_stride <= (1 << 20) && n_groups <= 0x7fffffffLL;
+}
+
+// widths[0 .. n_linear]: every width 1 ... 32, 1 ... 6 layers
+bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
+  if (widths == nullptr || n_linear < 1 || n_linear > amcx::kMlpMaxLinear) return false;
+  for (int l = 0; l <= n_linear; ++l)
+    if (widths[l] < 1 || widths[l] > amcx::kMlpMaxWidth) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int amcx_abi_version(void) { return AMCX_ABI_VERSION; }
+
+const char* amcx_strerror(int code) {
+  switch (code) {
+    case AMCX_OK: return "ok";
+    case AMCX_EINVAL: return "invalid argument (null pointer, negative count, stride or frame_size out of range)";
+    case AMCX_ENOTSUP: return "kernel variant does not support this frame_size";
+    case AMCX_EHIP: return "HIP runtime error (see amcx_last_hip_error)";
+    case AMCX_ENODEV: return "no usable gfx950 device";
+    case AMCX_ENOMEM: return "device memory allocation failed";
+    case AMCX_EIO: return "reading the container's file failed (see amcx_last_hip_error for the errno text)";
+    default: return "unknown amcx error code";
+  }
+}
+
+const char* amcx_last_hip_error(void) { return g_hip_err; }
+
+int amcx_device_count(void) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e == hipErrorNoDevice) return 0;
+  if (e != hipSuccess) return hip_fail(e, "hipGetDeviceCount");
+  int ok = 0;
+  for (int d = 0; d < n; ++d) {
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, d) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ++ok;
+  }
+  return ok;
+}
+
+int64_t amcx_features18_workspace_bytes(int32_t frame_size, int64_t n_frames, int32_t variant) {
+  if (n_frames < 0) return -1;
+  const int v = resolve_variant(frame_size, variant);
+  if (v < 0) return -1;
+  if (v != AMCX_VARIANT_BLOCK || frame_size <= amcx::kBlockMaxN || n_frames == 0) return 0;
+  const StreamPlan p = stream_plan(frame_size, n_frames);
+  return (p.grid + (p.chirped ? 1 : 0)) * (int64_t)p.M * (int64_t)sizeof(float2);
+}
+
+int amcx_features18_c64_ws(const void* iq_dev, int64_t n_frames, int32_t frame_size,
+                           int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
+                           void* hip_stream, int32_t variant, void* workspace_dev, int64_t workspace_bytes) {
+  return amcx_features_c64_subset(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
+                                  AMCX_FEATURES_ALL, workspace_dev, workspace_bytes);
+}
+
+int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems,
+                             float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
+                             void* workspace_dev, int64_t workspace_bytes) {
+  Workspace ws;
+  ws.dev = workspace_dev;
+  ws.bytes = workspace_bytes;
+  RingSource rings;
+  rings.pool = true;
+  return run_features(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
+                      feature_mask, ws, rings);
+}
+
+int amcx_features18_c64_ex(const void* iq_dev, int64_t n_frames, int32_t frame_size,
+                           int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
+                           void* hip_stream, int32_t variant) {
+  Workspace ws;
+  ws.own = true;                   // (launch_block_own_ws: asked for only once the arguments have passed)
+  RingSource rings;
+  rings.pool = true;
+  return run_features(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
+                      AMCX_FEATURES_ALL, ws, rings);
+}
+
+int amcx_features18_c64(const void* iq_dev, int64_t n_frames, int32_t frame_size,
+                        int64_t row_stride_elems, float* out_dev, int64_t out_row_stride,
+                        void* hip_stream) {
+  return amcx_features18_c64_ex(iq_dev, n_frames, frame_size, row_stride_elems, out_dev,
+                                out_row_stride, hip_stream, AMCX_VARIANT_AUTO);
+}
 
 int amcx_ctx_create(int32_t device, amcx_ctx** ctx_out) {
   if (ctx_out == nullptr) return AMCX_EINVAL;
@@ -1104,40 +1127,6 @@ int amcx_ctx_features18_strided_file(amcx_ctx* ctx, int32_t fd, int64_t re_offse
                          out_host, out_row_stride, variant);
 }
 
-static int stage_any(amcx::Source src, int64_t n_snr, int64_t n_frames,
-                     int32_t frame_size, int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
-                     int64_t first_unit, int64_t n_units, void* dst, int64_t dst_bytes, int32_t threads,
-                     int32_t* plane_major, int32_t* inner_snr_out) {
-  const int32_t kind = src.kind;
-  if (n_snr < 0 || n_frames < 0 || stride_snr < 0 || stride_frame < 0 || stride_sample < 0 || first_unit < 0 ||
-      n_units < 0 || threads < 0 || threads > 256 || kind < AMCX_SRC_C64 || kind > AMCX_SRC_F64_SPLIT ||
-      frame_size < AMCX_MIN_FRAME_SIZE || frame_size > AMCX_MAX_FRAME_SIZE)
-    return AMCX_EINVAL;
-  if (n_frames > 0 && n_snr > (int64_t(1) << 40) / n_frames) return AMCX_EINVAL;
-  bool rows = false, inner_snr = false;
-  amcx::RunMap map;
-  if (!classify_layout(n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, &rows, &inner_snr, &map))
-    return AMCX_ENOTSUP;
-  if (plane_major) *plane_major = rows ? 0 : 1;
-  if (inner_snr_out) *inner_snr_out = inner_snr ? 1 : 0;
-  const int64_t F = n_snr * n_frames, unit = rows ? frame_size : F, total_units = rows ? F : frame_size;
-  if (first_unit + n_units > total_units) return AMCX_EINVAL;
-  if (n_units == 0 || unit == 0) return AMCX_OK;
-  if ((src.fd < 0 && src.re == nullptr) || dst == nullptr || dst_bytes < n_units * unit * 8) return AMCX_EINVAL;
-  if (kind < AMCX_SRC_F32_SPLIT) { src.im = nullptr; src.im_off = -1; }
-  std::atomic<int> io_error{0};
-  src.io_error = &io_error;
-  amcx::Pool pool;
-  pool.resize(threads < 1 ? 1 : threads);
-  const int64_t per_unit = rows ? 1 : map.cnt_b;
-  amcx::stage_runs(pool, static_cast<char*>(dst), src, map, first_unit * per_unit, (first_unit + n_units) * per_unit, false);
-  if (io_error.load() != 0) {
-    snprintf(g_hip_err, sizeof g_hip_err, "reading the container's file: %s", strerror(io_error.load()));
-    return AMCX_EIO;
-  }
-  return AMCX_OK;
-}
-
 int amcx_stage_host(const void* re, const void* im, int32_t kind, int64_t n_snr, int64_t n_frames,
                     int32_t frame_size, int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
                     int64_t first_unit, int64_t n_units, void* dst, int64_t dst_bytes, int32_t threads,
@@ -1212,25 +1201,6 @@ int amcx_ctx_features18_c128_host(amcx_ctx* ctx, const void* iq_host, int64_t n_
   return ctx_run(ctx, iq_host, true, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, variant);
 }
 
-// one-shot forms: a context for the duration of the call
-static int one_shot(const void* iq_host, bool is_c128, int64_t n_frames, int32_t frame_size,
-                    int64_t row_stride_elems, float* out_host, int64_t out_row_stride, int32_t device,
-                    int32_t variant) {
-  // argument errors are reported before a device is looked for (tests/test_host_cpu.py runs without one)
-  if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES)
-    return AMCX_EINVAL;
-  const int v = resolve_variant(frame_size, variant);
-  if (v < 0) return v;
-  if (n_frames == 0) return AMCX_OK;
-  if (iq_host == nullptr || out_host == nullptr) return AMCX_EINVAL;
-  amcx_ctx* c = nullptr;
-  int rc = amcx_ctx_create(device, &c);
-  if (rc != AMCX_OK) return rc;
-  rc = ctx_run(c, iq_host, is_c128, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, v);
-  (void)amcx_ctx_destroy(c);
-  return rc;
-}
-
 int amcx_features18_c64_host(const void* iq_host, int64_t n_frames, int32_t frame_size,
                              int64_t row_stride_elems, float* out_host, int64_t out_row_stride,
                              int32_t device, int32_t variant) {
@@ -1247,8 +1217,11 @@ int amcx_kernel_name(int32_t frame_size, int32_t variant, char* buf, int32_t buf
   if (buf == nullptr || buf_len <= 0) return AMCX_EINVAL;
   const int v = resolve_variant(frame_size, variant);
   if (v < 0) return v;
-  const char* name = (v == AMCX_VARIANT_WAVE) ? amcx::wave_kernel_name(frame_size)
-                     : frame_size > amcx::kBlockMaxN                   ? "amcx_features18_stream_kernel"     /* <true> with a workspace, <false> without */
+  if (v == AMCX_VARIANT_WAVE) {
+    amcx::wave_kernel_name(frame_size, amcx::kPlanAll, buf, (size_t)buf_len);
+    return AMCX_OK;
+  }
+  const char* name = frame_size > amcx::kBlockMaxN                   ? "amcx_features18_stream_kernel"     /* <true> with a workspace, <false> without */
                      : block_mode(frame_size) == amcx::kBlockPow2      ? "amcx_features18_block_kernel<1>"
                      : block_mode(frame_size) == amcx::kBlockBluestein ? "amcx_features18_block_kernel<2>"
                      : block_mode(frame_size) == amcx::kBlockBluesteinBig ? "amcx_features18_block_kernel<3>"
@@ -1263,9 +1236,7 @@ int amcx_kernel_name_subset(int32_t frame_size, int32_t variant, uint32_t featur
   if (v < 0) return v;
   const int plan = subset_plan(frame_size, v, feature_mask);
   if (plan == amcx::kPlanAll) return amcx_kernel_name(frame_size, variant, buf, buf_len);
-  snprintf(buf, (size_t)buf_len, "%s<%d, %d>",
-           amcx::shortk::short_supports(frame_size) ? "amcx_features_subset_short_kernel" : "amcx_features_subset_wave_kernel",
-           (int)frame_size, plan);
+  amcx::wave_kernel_name(frame_size, plan, buf, (size_t)buf_len);
   return AMCX_OK;
 }
 
@@ -1349,24 +1320,6 @@ int amcx_probe_read_bw(const void* src_dev, int64_t n_bytes, float* partial_dev,
                      (long long)(n_bytes / 16), partial_dev);
   AMCX_HIP(hipGetLastError());
   return AMCX_OK;
-}
-
-// how a statistics call is cut: chunks per group and rows per chunk (whole tiles)
-static void stats_plan(int64_t n_groups, int64_t rows_per_group, int n_cols, int64_t* chunks, int64_t* rows_per_chunk) {
-  const int64_t tile = amcx::stat_tile_rows(n_cols);
-  const int64_t tiles = (rows_per_group + tile - 1) / tile;
-  const int64_t target = 1024;                               // workgroups wanted in all (4 per CU, one resident round); the same on any device
-  int64_t want = (target + n_groups - 1) / n_groups;
-  if (want > tiles) want = tiles;
-  if (want < 1) want = 1;
-  const int64_t tiles_per_chunk = (tiles + want - 1) / want;
-  *rows_per_chunk = tiles_per_chunk * tile;
-  *chunks = (tiles + tiles_per_chunk - 1) / tiles_per_chunk;
-}
-
-static bool stats_args_ok(int64_t n_groups, int64_t rows_per_group, int64_t row_stride, int32_t n_cols) {
-  return n_groups >= 0 && rows_per_group >= 1 && n_cols >= 1 && n_cols <= amcx::kStatMaxCols &&
-         row_stride >= n_cols && row_stride <= (1 << 20) && n_groups <= 0x7fffffffLL;
 }
 
 int64_t amcx_group_stats_workspace_bytes(int64_t n_groups, int64_t rows_per_group, int32_t n_cols) {
@@ -1480,14 +1433,6 @@ int amcx_select_scale_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
                      cols_dev, (int)n_sel, mean_dev, scale_dev, out_dev, (long long)out_stride);
   AMCX_HIP(hipGetLastError());
   return AMCX_OK;
-}
-
-// widths[0 .. n_linear]: every width 1 ... 32, 1 ... 6 layers
-static bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
-  if (widths == nullptr || n_linear < 1 || n_linear > amcx::kMlpMaxLinear) return false;
-  for (int l = 0; l <= n_linear; ++l)
-    if (widths[l] < 1 || widths[l] > amcx::kMlpMaxWidth) return false;
-  return true;
 }
 
 int64_t amcx_mlp_params_floats(const int32_t* widths_host, int32_t n_linear) {

@@ -642,28 +642,5 @@ __global__ __launch_bounds__(64 * W, 1) void amcx_features18_group_kernel(
   }
 }
 
-template <int W>
-inline hipError_t launch_group(const float2* iq, int64_t n_frames, int64_t row_stride, float* out,
-                               int64_t out_stride, hipStream_t stream, int cus) {
-  using Cg = G<W>;
-  auto kern = amcx_features18_group_kernel<W>;
-  static bool lds_attr_set[64] = {};                        // > 64 KiB of dynamic LDS needs the attribute, once per device
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !lds_attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cg::kLdsBytes);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) lds_attr_set[dev] = true;     // benign race: idempotent
-  }
-  const int64_t n_batches = (n_frames + Cg::kBatch - 1) / Cg::kBatch;
-  int64_t grid = (int64_t)cus;                              // persistent: one resident workgroup per CU
-  if (grid > n_batches) grid = n_batches;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(Cg::kThreads), Cg::kLdsBytes, stream, iq,
-                     (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
-  return hipGetLastError();
-}
-
 }  // namespace group
 }  // namespace amcx

@@ -56,7 +56,7 @@ constexpr int kOffFlag = kOffMx + kWavesPerQuad * 4;         // != 0: this workg
 // Re-run mask: bit k = frame k of the workgroup's own contiguous run is outside the fp32 sums' range.  Set by the wave
 // with quarter 0 (the only finaliser), read by all four waves behind a barrier: the list is the same in every wave by
 // construction, and nothing is read back from the caller's result matrix.  2 KiB cover 16 384 frames per workgroup =
-// 8.4 M frames (550 GB) per launch of 512 workgroups; launch_quad cuts longer inputs into several launches.
+// 8.4 M frames (550 GB) per launch of 512 workgroups; QuadSize::launch (amcx_launch.h) cuts longer inputs into several launches.
 constexpr int kMaskWords = 512;
 constexpr long long kMaskFrames = 32LL * kMaskWords;
 constexpr int kOffMask = kOffFlag + 4;
@@ -613,32 +613,6 @@ __global__ __launch_bounds__(kThreads, 2) void amcx_features18_quad_kernel(
       }
     }
   }
-}
-
-inline hipError_t launch_quad(const float2* iq, int64_t n_frames, int64_t row_stride, float* out,
-                              int64_t out_stride, hipStream_t stream, int cus) {
-  const int64_t full_grid = (int64_t)cus * kWGsPerCU;        // persistent: two resident workgroups per CU
-  // a workgroup's re-run mask covers kMaskFrames frames of its own run: longer inputs (more than 8.4 M frames of
-  // 64 KiB at 512 workgroups -- beyond one device's memory unless rows overlap) go as several launches
-  int64_t per_launch = full_grid * kMaskFrames;
-  // tests only: cut at this many frames (any cut is valid; the real one needs more frames than a device holds).  Read ONCE
-  // per process (a function-local static: getenv on every launch raced with setenv / putenv from other threads --
-  // Python writes os.environ while DeviceFanOut's threads launch with the GIL released)
-  static const long long test_split = [] { const char* t = getenv("AMCX_TEST_QUAD_SPLIT"); return t ? atoll(t) : 0LL; }();
-  if (test_split >= kBatch && test_split < per_launch) per_launch = test_split / kBatch * kBatch;
-  for (int64_t f0 = 0; f0 < n_frames; f0 += per_launch) {
-    const int64_t n_here = n_frames - f0 < per_launch ? n_frames - f0 : per_launch;
-    const int64_t n_batches = (n_here + kBatch - 1) / kBatch;
-    int64_t grid = full_grid;
-    if (grid > n_batches) grid = n_batches;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(amcx_features18_quad_kernel, dim3((unsigned)grid), dim3(kThreads), kLdsBytes, stream,
-                       iq + f0 * row_stride, (long long)n_here, (long long)row_stride, out + f0 * out_stride,
-                       (long long)out_stride);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
 }
 
 }  // namespace quad

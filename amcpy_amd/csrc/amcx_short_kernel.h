@@ -112,54 +112,5 @@ __global__ __launch_bounds__(SCfg<N>::kThreads, SCfg<N>::kWavesPerWG / 4) void a
 #include "amcx_short_kernel_body.h"
 }
 
-template <int N, int PLAN = kPlanAll>
-inline hipError_t launch_short_n(const float2* iq, int64_t n_frames, int64_t row_stride, float* out,
-                                 int64_t out_stride, hipStream_t stream, int cus, unsigned mask = kMaskAll) {
-  using C = SCfg<N>;
-  constexpr auto kern = [] {
-    if constexpr (PLAN == kPlanAll) return amcx_features18_short_kernel<N>;
-    else return amcx_features_subset_short_kernel<N, PLAN>;
-  }();
-  static bool lds_attr_set[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; }
-  if (dev < 0 || dev >= 64 || !lds_attr_set[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             C::kLdsBytes);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) lds_attr_set[dev] = true;       // benign race: idempotent
-  }
-  const int64_t n_pass = (n_frames + kQuad - 1) / kQuad;
-  int64_t grid = cus;                                         // persistent: one resident workgroup per CU
-  const int64_t need = (n_pass + C::kWavesPerWG - 1) / C::kWavesPerWG;
-  if (grid > need) grid = need;
-  if (grid < 1) grid = 1;
-  if constexpr (PLAN == kPlanAll)
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::kThreads), C::kLdsBytes, stream, iq, (long long)n_frames,
-                       (long long)row_stride, out, (long long)out_stride);
-  else
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::kThreads), C::kLdsBytes, stream, iq, (long long)n_frames,
-                       (long long)row_stride, out, (long long)out_stride, mask);
-  return hipGetLastError();
-}
-
-// the feature-subset kernels of 128, 256 and 512 (PLAN kPlanNoSpectral / kPlanCumulants)
-template <int PLAN>
-inline hipError_t launch_short_subset(const float2* iq, int64_t n_frames, int32_t frame_size, int64_t row_stride, float* out,
-                                      int64_t out_stride, hipStream_t stream, int cus, unsigned mask) {
-  return frame_size == 128   ? launch_short_n<128, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask)
-         : frame_size == 256 ? launch_short_n<256, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask)
-                             : launch_short_n<512, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, mask);
-}
-
-inline bool short_supports(int frame_size) { return frame_size == 128 || frame_size == 256 || frame_size == 512; }
-
-inline hipError_t launch_short(const float2* iq, int64_t n_frames, int32_t frame_size, int64_t row_stride, float* out,
-                               int64_t out_stride, hipStream_t stream, int cus) {
-  return frame_size == 128   ? launch_short_n<128>(iq, n_frames, row_stride, out, out_stride, stream, cus)
-         : frame_size == 256 ? launch_short_n<256>(iq, n_frames, row_stride, out, out_stride, stream, cus)
-                             : launch_short_n<512>(iq, n_frames, row_stride, out, out_stride, stream, cus);
-}
-
 }  // namespace shortk
 }  // namespace amcx

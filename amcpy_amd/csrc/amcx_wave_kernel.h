@@ -1551,7 +1551,7 @@ __global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) vo
 
 // The same kernels without a ring, for the frame sizes whose product form takes one (Cfg<N>::kHasRing): batches of
 // kFramesPerWave frames finalised from the LDS stash.  Same per-frame instructions, same results; a launch that has no ring
-// (launch_wave_n) runs these.
+// (amcx_launch.h, WaveSize::launch) runs these.
 template <int N>
 __global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) void amcx_features18_wave_lds_kernel(
     const float2* __restrict__ iq, long long n_frames, long long row_stride,
@@ -1567,145 +1567,5 @@ __global__ __launch_bounds__(Cfg<N>::kThreads, (Cfg<N>::kWavesPerWG + 3) / 4) vo
 #endif
 
 }  // namespace wave
-
-inline bool wave_supports(int frame_size) {
-  return frame_size >= 128 && frame_size <= 32768 && (frame_size & (frame_size - 1)) == 0;
-}
-
-inline const char* wave_kernel_name(int frame_size) {
-  switch (frame_size) {
-    case 128: return "amcx_features18_short_kernel<128>";      // four frames per wave: amcx_short_kernel.h
-    case 256: return "amcx_features18_short_kernel<256>";
-    case 512: return "amcx_features18_short_kernel<512>";
-    case 1024: return "amcx_features18_wave_kernel<1024>";
-    case 2048: return "amcx_features18_wave_kernel<2048>";
-    case 4096: return "amcx_features18_wave_kernel<4096>";
-    case 8192: return "amcx_features18_quad_kernel";
-    case 16384: return "amcx_features18_group_kernel<8>";
-    case 32768: return "amcx_features18_group_kernel<16>";
-    default: return "";
-  }
-}
-
-#ifndef AMCX_WAVE_STAMPS
-// bytes of ring a launch of frame size N over `cus` workgroups needs (0: that size's kernel takes none)
-inline size_t wave_ring_bytes(int frame_size, int cus) {
-  auto of = [&](auto cfg) -> size_t {
-    using C = decltype(cfg);
-    return C::kHasRing ? (size_t)cus * C::kWavesPerWG * C::kRingFloatsPerWave * sizeof(float) : 0;
-  };
-  switch (frame_size) {
-    case 1024: return of(wave::Cfg<1024>{});
-    case 2048: return of(wave::Cfg<2048>{});
-    case 4096: return of(wave::Cfg<4096>{});
-    default: return 0;
-  }
-}
-
-// > 64 KiB of dynamic LDS needs the attribute; it is per device, so once per (kernel, device)
-template <class K>
-inline hipError_t wave_lds_attr(K kern, int lds, bool (&set)[64]) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) set[dev] = true;   // benign race: idempotent
-  }
-  return hipSuccess;
-}
-
-// `ring`: wave_ring_bytes(N, cus) bytes that no other launch in flight uses, or nullptr -- then a frame size whose kernel
-// takes a ring runs its LDS form (amcx_features18_wave_lds_kernel), same results
-template <int N, int PLAN = kPlanAll>
-inline hipError_t launch_wave_n(const float2* iq, int64_t n_frames, int64_t row_stride, float* out,
-                                int64_t out_stride, hipStream_t stream, int cus, float* ring, unsigned mask = kMaskAll) {
-  using Plain18 = void (*)(const float2*, long long, long long, float*, long long);
-  using Ring18 = void (*)(const float2*, long long, long long, float*, long long, float*);
-  using PlainSub = void (*)(const float2*, long long, long long, float*, long long, unsigned);
-  using RingSub = void (*)(const float2*, long long, long long, float*, long long, unsigned, float*);
-  constexpr bool kRing = wave::Cfg<N>::kHasRing;
-  // the size's product kernel: the overload with a ring where it takes one
-  constexpr auto kern = [] {
-    if constexpr (PLAN == kPlanAll) {
-      if constexpr (kRing) return static_cast<Ring18>(wave::amcx_features18_wave_kernel<N>);
-      else return static_cast<Plain18>(wave::amcx_features18_wave_kernel<N>);
-    } else {
-      if constexpr (kRing) return static_cast<RingSub>(wave::amcx_features_subset_wave_kernel<N, PLAN>);
-      else return static_cast<PlainSub>(wave::amcx_features_subset_wave_kernel<N, PLAN>);
-    }
-  }();
-  constexpr int lds = wave::Cfg<N>::kLdsBytes;
-  const bool lds_form = wave::Cfg<N>::kHasRing && ring == nullptr;
-  static bool lds_attr_set[64] = {};
-  hipError_t e = hipSuccess;
-  if (!lds_form) e = wave_lds_attr(kern, lds, lds_attr_set);
-  if (e != hipSuccess) return e;
-  int64_t grid = (int64_t)cus;                        // persistent: one resident workgroup per CU
-  const int64_t min_slice = wave::Cfg<N>::kWavesPerWG;   // at least a frame per wave
-  if (grid * min_slice > n_frames) grid = (n_frames + min_slice - 1) / min_slice;
-  if constexpr (wave::Cfg<N>::kHasRing) {
-    if (lds_form) {
-      constexpr auto kern_lds = [] {
-        if constexpr (PLAN == kPlanAll) return wave::amcx_features18_wave_lds_kernel<N>;
-        else return wave::amcx_features_subset_wave_lds_kernel<N, PLAN>;
-      }();
-      static bool lds_attr_set_lds[64] = {};
-      e = wave_lds_attr(kern_lds, lds, lds_attr_set_lds);
-      if (e != hipSuccess) return e;
-      if constexpr (PLAN == kPlanAll)
-        hipLaunchKernelGGL(kern_lds, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                           (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
-      else
-        hipLaunchKernelGGL(kern_lds, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                           (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask);
-      return hipGetLastError();
-    }
-  }
-  if constexpr (kRing) {
-    if constexpr (PLAN == kPlanAll)
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride, ring);
-    else
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask, ring);
-  } else {
-    if constexpr (PLAN == kPlanAll)
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride);
-    else
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(wave::Cfg<N>::kThreads), lds, stream, iq,
-                         (long long)n_frames, (long long)row_stride, out, (long long)out_stride, mask);
-  }
-  return hipGetLastError();
-}
-
-// the feature-subset kernels of 1024 ... 4096 (PLAN kPlanNoSpectral / kPlanCumulants)
-template <int PLAN>
-inline hipError_t launch_wave_subset(const float2* iq, int64_t n_frames, int32_t frame_size, int64_t row_stride, float* out,
-                                     int64_t out_stride, hipStream_t stream, int cus, float* ring, unsigned mask) {
-  switch (frame_size) {
-    case 1024: return launch_wave_n<1024, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring, mask);
-    case 2048: return launch_wave_n<2048, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring, mask);
-    case 4096: return launch_wave_n<4096, PLAN>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring, mask);
-    default: return hipErrorNotSupported;
-  }
-}
-
-inline hipError_t launch_wave(const float2* iq, int64_t n_frames, int32_t frame_size,
-                              int64_t row_stride, float* out, int64_t out_stride,
-                              hipStream_t stream, int cus, float* ring) {
-  switch (frame_size) {
-    // (128, 256 and 512 ran here until late in round 5 -- 8 / 4 / 2 frames sharing one run of FFT passes 2-3 -- and have a
-    //  kernel of their own now, amcx_short_kernel.h: +34 % / +13 % / +2.5 ... 5 %)
-    case 1024: return launch_wave_n<1024>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring);
-    case 2048: return launch_wave_n<2048>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring);
-    case 4096: return launch_wave_n<4096>(iq, n_frames, row_stride, out, out_stride, stream, cus, ring);
-    default: return hipErrorNotSupported;       // 128, 256, 512, 8192, 16384, 32768 have kernels of their own (amcx.hip)
-  }
-}
-
-#endif
 
 }  // namespace amcx

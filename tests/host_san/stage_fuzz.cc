@@ -100,7 +100,7 @@ Box make_box(Rng& rng, bool want_unit_axis, bool big = false) {
   return b;
 }
 
-// stage units [first, first + count) of the box the way amcx.hip's stage_any / ctx_run_strided do, and check every value
+// stage units [first, first + count) of the box the way amcx.hip's stage_any / ctx_run_strided (run_small_graph, run_chunked) do, and check every value
 void stage_and_check(const Box& b, const amcx::Source& src, amcx::Pool& pool, int64_t first, int64_t count,
                      bool rows, bool inner, const amcx::RunMap& map) {
   const int64_t F = b.S * b.K, unit = rows ? b.N : F, per_unit = rows ? 1 : map.cnt_b;

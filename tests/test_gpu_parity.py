@@ -2122,7 +2122,7 @@ def test_any_size_path_inside_a_graph_capture():
 
 
 def test_quad_launch_cut_into_several(tmp_path):
-    """launch_quad cuts an input longer than its workgroups' re-run masks cover (8.4 M frames of 64 KiB: more than a device
+    """QuadSize::launch (amcx_launch.h) cuts an input longer than its workgroups' re-run masks cover (8.4 M frames of 64 KiB: more than a device
     holds) into several launches.  With the cut forced at 52 frames (AMCX_TEST_QUAD_SPLIT, which the library reads once per
     process: the cut run is a process of its own) 211 frames go as five launches: same rows as one launch, an
     out-of-range frame on either side of a cut included."""
