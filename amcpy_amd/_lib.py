@@ -12,14 +12,15 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 8          # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 9          # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
 VARIANT_AUTO, VARIANT_BLOCK, VARIANT_WAVE = 0, 1, 2
 VARIANTS = {"auto": VARIANT_AUTO, "block": VARIANT_BLOCK, "wave": VARIANT_WAVE}
 OK, EINVAL, ENOTSUP, EHIP, ENODEV, ENOMEM, EIO = 0, -1, -2, -3, -4, -5, -6
-SRC_C64, SRC_C128, SRC_F32_SPLIT, SRC_F64_SPLIT = 0, 1, 2, 3
+SRC_C64, SRC_C128, SRC_F32_SPLIT, SRC_F64_SPLIT, SRC_SC16 = 0, 1, 2, 3, 4
+SC16_SCALE = 2.0 ** -15                                 # the default sc16 scale: int16 onto [-1, 1) (ABI 9)
 ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2                # AMCX_ACT_* (ABI 8)
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
 
@@ -51,6 +52,11 @@ SIGNATURES = {
     "amcx_features18_c64_ws": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _i64]),
     "amcx_features_c64_subset": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, C.c_uint32, _vp, _i64]),
     "amcx_kernel_name_subset": (C.c_int, [_i32, _i32, C.c_uint32, C.c_char_p, _i32]),
+    "amcx_features_sc16_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "amcx_features_sc16": (C.c_int, [_vp, _i64, _i32, _i64, C.c_float, _vp, _i64, _vp, _i32, C.c_uint32, _vp, _i64]),
+    "amcx_kernel_name_sc16": (C.c_int, [_i32, _i32, C.c_uint32, C.c_char_p, _i32]),
+    "amcx_ctx_set_sc16_scale": (C.c_int, [_vp, C.c_float]),
+    "amcx_ctx_features18_sc16_host": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _i32]),
     "amcx_ctx_set_feature_mask": (C.c_int, [_vp, C.c_uint32]),
     "amcx_features18_c64_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
     "amcx_features18_c128_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
@@ -191,6 +197,13 @@ def kernel_name_subset(frame_size: int, variant: int, mask: int) -> str:
     return buf.value.decode()
 
 
+def kernel_name_sc16(frame_size: int, variant: int = VARIANT_AUTO, mask: int = FEATURES_ALL) -> str:
+    """amcx_kernel_name_sc16: the kernel amcx_features_sc16 runs (host-only)."""
+    buf = C.create_string_buffer(128)
+    check(load().amcx_kernel_name_sc16(int(frame_size), int(variant), int(mask), buf, len(buf)))
+    return buf.value.decode()
+
+
 def numa_place(pci_bus_id: str, sysfs_root: str = "") -> tuple:
     """(node, [cpus]) local to the PCI device ``dddd:bb:dd.f`` according to ``<sysfs_root>/bus/pci/devices`` (default
     /sys): amcx_numa_place.  (-1, []) when the platform does not say.  Host-only: needs no GPU."""
@@ -223,6 +236,7 @@ class HostContext:
         self._h = C.c_void_p()
         self.device = int(device)
         self.mask = FEATURES_ALL
+        self.sc16_scale = SC16_SCALE
         check(load().amcx_ctx_create(self.device, C.byref(self._h)))
 
     def set_feature_mask(self, mask: int) -> None:
@@ -232,10 +246,21 @@ class HostContext:
             check(load().amcx_ctx_set_feature_mask(self._h, mask))
             self.mask = mask
 
+    def set_sc16_scale(self, scale: float) -> None:
+        """amcx_ctx_set_sc16_scale: what every later sc16 call multiplies an int16 component by."""
+        scale = C.c_float(scale).value
+        if scale != self.sc16_scale:
+            check(load().amcx_ctx_set_sc16_scale(self._h, scale))
+            self.sc16_scale = scale
+
     def run(self, x2, frame_size: int, out, variant: int) -> None:
-        """x2: C-contiguous (F, L) complex64 / complex128 ndarray; out: (F, >=18) float32."""
+        """x2: C-contiguous (F, L) complex64 / complex128 ndarray, or (F, L, 2) int16 (sc16); out: (F, >=18) float32."""
         import numpy as np
         lib = load()
+        if x2.dtype == np.int16:
+            check(lib.amcx_ctx_features18_sc16_host(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1],
+                                                    out.ctypes.data, out.shape[1], int(variant)))
+            return
         entry = lib.amcx_ctx_features18_c128_host if x2.dtype == np.complex128 else lib.amcx_ctx_features18_c64_host
         check(entry(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1],
                     out.ctypes.data, out.shape[1], int(variant)))

@@ -11,6 +11,7 @@
 #include <new>
 #include <vector>
 
+#include "amcx_sc16_kernels.h"     // FIRST: KERNEL ORDER, amcx_launch.h
 #include "amcx_block_kernel.h"
 #include "amcx_stream_kernel.h"
 #include "amcx_launch.h"
@@ -52,6 +53,7 @@ struct amcx_ctx {
   // out as ONE instantiated graph per (frames, frame size, variant, element type, buffers), relaunched
   struct GraphKey {
     int64_t frames = 0; int32_t frame_size = 0, variant = 0; bool c128 = false, zero_copy = false;
+    bool sc16 = false; float sc16_scale = 0.f;   // the element kind, and the scale the captured kernel node carries as an argument
     const void* pin = nullptr; const void* slab = nullptr; const void* out = nullptr; const void* out_pin = nullptr;
     const void* ws = nullptr;      // the workspace the captured kernel node points into
     size_t slot = 0;
@@ -59,7 +61,7 @@ struct amcx_ctx {
     bool operator==(const GraphKey& o) const {
       return frames == o.frames && frame_size == o.frame_size && variant == o.variant && c128 == o.c128 &&
              zero_copy == o.zero_copy && pin == o.pin && slab == o.slab && out == o.out && out_pin == o.out_pin &&
-             ws == o.ws && slot == o.slot && mask == o.mask;
+             ws == o.ws && slot == o.slot && mask == o.mask && sc16 == o.sc16 && sc16_scale == o.sc16_scale;
     }
   };
   struct SmallGraph {
@@ -75,6 +77,8 @@ struct amcx_ctx {
   std::atomic<int> in_call{0};
   // amcx_ctx_set_feature_mask: the features every later host-buffer call computes (read once per call)
   std::atomic<uint32_t> feature_mask{AMCX_FEATURES_ALL};
+  // amcx_ctx_set_sc16_scale: what an int16 component of an sc16 source is multiplied by (read once per call)
+  std::atomic<float> sc16_scale{0x1p-15f};
 };
 
 namespace {
@@ -379,24 +383,63 @@ struct Workspace {
   bool own = false;
 };
 
-// Behind amcx_features18_c64_ws / _ex, amcx_features_c64_subset and the contexts (ctx_features); feature_mask is
-// AMCX_FEATURES_ALL for the 18-feature entries.  The order of the checks is part of the ABI (tests/c_abi/abi_check.c).
+// sc16 frames (include/amcx.h, amcx_features_sc16): iq_dev holds int16 pairs, a component's value is (float)int16 * scale
+struct Sc16In {
+  float scale;
+};
+inline int64_t sc16_widened_bytes(int32_t N, int64_t n_frames) { return (8 * (int64_t)N * n_frames + 255) / 256 * 256; }
+// (defined behind run_features: KERNEL ORDER, amcx_launch.h)
+hipError_t launch_sc16_plan(const amcx::Frames& frames, int32_t N, int plan, float* ring, uint32_t mask);
+hipError_t launch_sc16_widen(const amcx::Frames& frames, int32_t N, float2* dst);
+
+// Behind amcx_features18_c64_ws / _ex, amcx_features_c64_subset, amcx_features_sc16 and the contexts (ctx_features);
+// feature_mask is AMCX_FEATURES_ALL for the 18-feature entries.  The order of the checks is part of the ABI
+// (tests/c_abi/abi_check.c).  sc16: the frames are sc16, not complex64 -- a kernel over sc16 where the size has one, otherwise
+// widened into the head of the workspace, the complex64 path with the rest of it.
 int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems, float* out_dev,
-                 int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask, const Workspace& ws,
-                 const RingSource& rings) {
+                 int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask, const Workspace& ws_in,
+                 const RingSource& rings, const Sc16In* sc16 = nullptr) {
   if (!valid_feature_mask(feature_mask)) return AMCX_EINVAL;
+  if (sc16 != nullptr && !(sc16->scale > 0.0f && sc16->scale <= 3.4028235e38f)) return AMCX_EINVAL;   // NaN, inf, <= 0
   if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES) return AMCX_EINVAL;
   const int v = resolve_variant(frame_size, variant);
   if (v < 0) return v;
   if (n_frames == 0) return AMCX_OK;
   if (iq_dev == nullptr || out_dev == nullptr) return AMCX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(iq_dev) & 7u) || (reinterpret_cast<uintptr_t>(out_dev) & 3u)) return AMCX_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(iq_dev) & (sc16 != nullptr ? 3u : 7u)) || (reinterpret_cast<uintptr_t>(out_dev) & 3u))
+    return AMCX_EINVAL;
+  const bool typed = sc16 != nullptr && v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(frame_size);
+  Workspace ws = ws_in;
+  if (sc16 != nullptr && !typed) {      // the widened copy takes the head of the caller's workspace
+    const int64_t head = sc16_widened_bytes(frame_size, n_frames);
+    if (ws.own || ws.dev == nullptr || ws.bytes < head || (reinterpret_cast<uintptr_t>(ws.dev) & 7u)) return AMCX_EINVAL;
+    ws.dev = static_cast<char*>(ws_in.dev) + head;
+    ws.bytes = ws_in.bytes - head;
+    if (ws.bytes == 0) ws.dev = nullptr;
+  }
   if (on_another_device(iq_dev) || on_another_device(out_dev)) return AMCX_EINVAL;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const amcx::Frames frames{static_cast<const float2*>(iq_dev), n_frames, row_stride_elems, out_dev, out_row_stride, stream, cu_count()};
+  amcx::Frames frames{static_cast<const float2*>(iq_dev), n_frames, row_stride_elems, out_dev, out_row_stride, stream, cu_count()};
+  if (sc16 != nullptr) {
+    frames.iq = nullptr;
+    frames.iq16 = static_cast<const amcx::wave::sc16*>(iq_dev);
+    frames.scale = sc16->scale;
+    if (!typed) {
+      if (on_another_device(ws_in.dev)) return AMCX_EINVAL;
+      float2* const wide = static_cast<float2*>(ws_in.dev);
+      if (const hipError_t e = launch_sc16_widen(frames, frame_size, wide); e != hipSuccess) return hip_fail(e, "sc16 widening kernel launch");
+      frames.iq = wide;
+      frames.iq16 = nullptr;
+      frames.row_stride = frame_size;
+    }
+  }
   const int plan = subset_plan(frame_size, v, feature_mask);
   int rc;
-  if (v == AMCX_VARIANT_WAVE) {
+  if (typed) {
+    const hipError_t e = launch_sc16_plan(frames, frame_size, plan, ring_for(rings, frame_size, stream), feature_mask);
+    if (e != hipSuccess) return hip_fail(e, "sc16 kernel launch");
+    rc = AMCX_OK;
+  } else if (v == AMCX_VARIANT_WAVE) {
     // Every throughput kernel (amcx_launch.h, THE FRAME-SIZE TABLE) has re-run the frames outside its fp32 sums' range
     // itself -- one launch, rows final -- and finished frames with a phase step within an angle rounding of +-pi in its
     // finaliser.
@@ -428,6 +471,28 @@ int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64
   return AMCX_OK;
 }
 
+// the sc16 kernel of (frame size, plan): amcx_launch.h, THE FRAME-SIZE TABLE
+hipError_t launch_sc16_plan(const amcx::Frames& frames, int32_t N, int plan, float* ring, uint32_t mask) {
+  auto launch_plan = [&](auto plan_c) {
+    return amcx::for_frame_size(N, [&](auto size) {
+      using S = decltype(size);
+      if constexpr (S::kSc16Stem != nullptr) return S::template launch<decltype(plan_c)::value, amcx::wave::sc16>(frames, ring, mask);
+      else return hipErrorNotSupported;
+    });
+  };
+  using std::integral_constant;
+  return plan == amcx::kPlanAll         ? launch_plan(integral_constant<int, amcx::kPlanAll>{})
+         : plan == amcx::kPlanCumulants ? launch_plan(integral_constant<int, amcx::kPlanCumulants>{})
+                                        : launch_plan(integral_constant<int, amcx::kPlanNoSpectral>{});
+}
+
+// sc16 rows -> packed complex64 rows of N samples at dst (amcx_sc16_kernels.h)
+hipError_t launch_sc16_widen(const amcx::Frames& frames, int32_t N, float2* dst) {
+  const int64_t grid = amcx::persistent_grid(frames.cus, 8, frames.n_frames * N, 256);
+  return amcx::launch(amcx::amcx_sc16_to_c64_kernel, grid, 256, 0, frames.stream, frames.iq16, frames.n_frames, N,
+                      frames.row_stride, frames.scale, dst);
+}
+
 // ---- host-buffer entry points over a reusable context: the helpers ---------------------------------------------------------
 int ctx_reserve(void** p, size_t* cap, size_t bytes) {
   if (*cap >= bytes) return AMCX_OK;
@@ -455,14 +520,16 @@ void ctx_reserve_ws(amcx_ctx* c, int32_t N, int64_t frames, int32_t variant) {
   if (ring > 0 && ctx_reserve(&c->d_ring, &c->ring_cap, ring) != AMCX_OK) { c->d_ring = nullptr; c->ring_cap = 0; }
 }
 
-int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant, uint32_t mask) {
+// sc16: `rows` are sc16 and the size has a kernel that reads them (sc16_typed); otherwise complex64
+int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant, uint32_t mask,
+                 const Sc16In* sc16 = nullptr) {
   const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
   Workspace ws;
   if (want > 0 && c->d_ws != nullptr && c->ws_cap >= (size_t)want) { ws.dev = c->d_ws; ws.bytes = want; }
   RingSource rings;
   rings.own = static_cast<float*>(c->d_ring);
   rings.own_bytes = c->ring_cap;
-  return run_features(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask, ws, rings);
+  return run_features(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask, ws, rings, sc16);
 }
 
 struct DeviceGuard {
@@ -535,6 +602,8 @@ struct StridedCall {
   int v = 0;                       // the resolved variant
   uint32_t mask = AMCX_FEATURES_ALL;
   bool rows = false, inner_snr = false, as_c128 = false, threaded = false;
+  bool sc16 = false, sc16_typed = false;   // an sc16 source; a kernel of this size reads it (otherwise it is widened on the device)
+  Sc16In sc16_in = {1.0f};
   size_t esz = 8;                  // staged bytes per element
   int64_t unit = 0, n_units = 0;   // staged elements per chunk unit (a frame / a plane), and how many
   size_t total_staged = 0, slot = 0, dslot = 0;
@@ -550,6 +619,27 @@ hipError_t round_rows_on_device(amcx_ctx* c, const StridedCall& q, char* dev, in
   *d_rows = rounded;
   return amcx::launch(amcx::amcx_c128_to_c64_kernel, 2048, 256, 0, c->stream, reinterpret_cast<const double2*>(dev), frames,
                       q.N, q.N, rounded);
+}
+
+// rows of sc16 in a device slot, widened to complex64 into the room behind the slot (the frame sizes and variants that have
+// no sc16 kernel)
+hipError_t widen_rows_on_device(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, const void** d_rows) {
+  float2* wide = reinterpret_cast<float2*>(dev + q.slot);
+  *d_rows = wide;
+  amcx::Frames fr{nullptr, frames, q.N, nullptr, 0, c->stream, cu_count()};
+  fr.iq16 = reinterpret_cast<const amcx::wave::sc16*>(dev);
+  fr.scale = q.sc16_in.scale;
+  return launch_sc16_widen(fr, q.N, wide);
+}
+
+// the feature kernels over the rows of one chunk at `dev`: complex64, complex128 (rounded first) or sc16 (read by the
+// kernel, or widened first)
+int chunk_features(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, float* out, hipError_t* e) {
+  const void* d_rows = dev;
+  if (q.as_c128) *e = round_rows_on_device(c, q, dev, frames, &d_rows);
+  else if (q.sc16 && !q.sc16_typed) *e = widen_rows_on_device(c, q, dev, frames, &d_rows);
+  if (*e != hipSuccess) return AMCX_OK;
+  return ctx_features(c, d_rows, frames, q.N, out, q.v, q.mask, q.sc16_typed ? &q.sc16_in : nullptr);
 }
 
 // the result is in pinned memory: spread it over the caller's row stride, and close the call's statistics
@@ -589,9 +679,10 @@ bool run_small_graph(amcx_ctx* c, StridedCall& q, amcx::Pool& inline_pool, int* 
   key.frames = q.F; key.frame_size = q.N; key.variant = q.v; key.c128 = q.as_c128;
   // a few frames of complex64: the kernels read the pinned slot and write the pinned result themselves (host memory
   // from hipHostMalloc is mapped into the device's address space) -- two copy nodes fewer in the graph
-  key.zero_copy = !q.as_c128 && bytes <= (size_t(64) << 10) && getenv("AMCX_NO_ZERO_COPY") == nullptr;
+  key.zero_copy = !q.as_c128 && !(q.sc16 && !q.sc16_typed) && bytes <= (size_t(64) << 10) && getenv("AMCX_NO_ZERO_COPY") == nullptr;
   key.pin = pinned; key.slab = dev; key.out = c->d_out; key.out_pin = c->out_pin; key.ws = c->d_ws; key.slot = q.slot;
   key.mask = q.mask;
+  key.sc16 = q.sc16; key.sc16_scale = q.sc16 ? q.sc16_in.scale : 0.f;
   amcx_ctx::SmallGraph* g = nullptr;
   for (auto& cand : c->graphs)
     if (cand.exec && cand.key == key) g = &cand;
@@ -606,13 +697,11 @@ bool run_small_graph(amcx_ctx* c, StridedCall& q, amcx::Pool& inline_pool, int* 
     int crc = AMCX_OK;
     hipError_t ce = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
     if (ce == hipSuccess && key.zero_copy) {
-      crc = ctx_features(c, pinned, q.F, q.N, c->out_pin, q.v, q.mask);
+      crc = ctx_features(c, pinned, q.F, q.N, c->out_pin, q.v, q.mask, q.sc16 ? &q.sc16_in : nullptr);
       ce = hipStreamEndCapture(c->stream, &graph);
     } else if (ce == hipSuccess) {
       ce = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, c->stream);
-      const void* d_rows = dev;
-      if (ce == hipSuccess && q.as_c128) ce = round_rows_on_device(c, q, dev, q.F, &d_rows);
-      if (ce == hipSuccess) crc = ctx_features(c, d_rows, q.F, q.N, c->d_out, q.v, q.mask);
+      if (ce == hipSuccess) crc = chunk_features(c, q, dev, q.F, c->d_out, &ce);
       if (ce == hipSuccess && crc == AMCX_OK)
         ce = hipMemcpyAsync(c->out_pin, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
       const hipError_t ee = hipStreamEndCapture(c->stream, &graph);      // always ends the capture
@@ -695,9 +784,8 @@ int run_chunked(amcx_ctx* c, StridedCall& q, amcx::Pool& pool) {
     if (e != hipSuccess) break;
     st.pcie_bytes += (int64_t)bytes;
     if (q.rows) {
-      const void* d_rows = dev;
-      if (q.as_c128) { e = round_rows_on_device(c, q, dev, take, &d_rows); if (e != hipSuccess) break; }
-      rc = ctx_features(c, d_rows, take, N, c->d_out + (size_t)u * AMCX_NUM_FEATURES, q.v, q.mask);
+      rc = chunk_features(c, q, dev, take, c->d_out + (size_t)u * AMCX_NUM_FEATURES, &e);
+      if (e != hipSuccess) break;
     } else {
       float2* frames = static_cast<float2*>(c->d_frames);
       const int S = (int)q.S, inner = q.inner_snr ? 1 : 0;
@@ -739,10 +827,11 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
   if (c == nullptr) return AMCX_EINVAL;
   const int32_t kind = src.kind;
   if (S < 0 || K < 0 || ss < 0 || sk < 0 || sn < 0 || out_row_stride < AMCX_NUM_FEATURES ||
-      kind < AMCX_SRC_C64 || kind > AMCX_SRC_F64_SPLIT)
+      kind < AMCX_SRC_C64 || kind > AMCX_SRC_SC16)
     return AMCX_EINVAL;
   const int v = resolve_variant(N, variant);
   if (v < 0) return v;
+  if (kind == AMCX_SRC_SC16 && sn != 1) return AMCX_ENOTSUP;        // sc16: row layouts only
   if (S == 0 || K == 0) return AMCX_OK;
   if (S > (int64_t(1) << 40) / K) return AMCX_EINVAL;
   if ((src.fd < 0 && src.re == nullptr) || (src.fd >= 0 && src.re_off < 0) || out_host == nullptr) return AMCX_EINVAL;
@@ -753,7 +842,7 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
   } in_call(c->in_call);
   StridedCall q;
   q.mask = c->feature_mask.load(std::memory_order_acquire);
-  if (kind < AMCX_SRC_F32_SPLIT) { src.im = nullptr; src.im_off = -1; }
+  if (kind < AMCX_SRC_F32_SPLIT || kind == AMCX_SRC_SC16) { src.im = nullptr; src.im_off = -1; }
   src.io_error = &q.io_error;
   q.src = src;
   q.S = S; q.K = K; q.N = N; q.v = v; q.out_host = out_host; q.out_row_stride = out_row_stride;
@@ -762,8 +851,12 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
   const bool rows = q.rows;
   if (!rows && S > 0x7fffffffLL) return AMCX_EINVAL;             // the transposition kernel indexes the snr axis with an int
   const bool as_c128 = q.as_c128 = c->round_on_device && kind == AMCX_SRC_C128;
-  const size_t esz = q.esz = as_c128 ? 16 : 8;
-  const size_t src_esz = kind == AMCX_SRC_C64 ? 8 : kind == AMCX_SRC_C128 ? 16 : kind == AMCX_SRC_F32_SPLIT ? 4 : 8;
+  q.sc16 = kind == AMCX_SRC_SC16;
+  q.sc16_typed = q.sc16 && v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(N);
+  q.sc16_in.scale = c->sc16_scale.load(std::memory_order_acquire);
+  const size_t esz = q.esz = amcx::staged_elem_bytes(kind, as_c128);
+  const size_t src_esz = kind == AMCX_SRC_C64 ? 8 : kind == AMCX_SRC_C128 ? 16 : kind == AMCX_SRC_F32_SPLIT ? 4
+                         : kind == AMCX_SRC_SC16 ? 4 : 8;
   const int64_t unit = q.unit = rows ? N : F;             // staged elements per chunk unit (a frame / a plane)
   const int64_t n_units = q.n_units = rows ? F : N;
   size_t slot = c->slot_bytes;
@@ -778,7 +871,8 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
   AMCX_HIP(guard.enter(c->device));
   q.t_start = wall_now();
   // rows of complex128 rounded on the device: each device slot is followed by room for its rounded rows
-  q.dslot = (rows && as_c128) ? slot + slot / 2 : slot;
+  // ... and rows of sc16 widened on the device by room for twice their bytes
+  q.dslot = (rows && as_c128) ? slot + slot / 2 : (q.sc16 && !q.sc16_typed) ? 3 * slot : slot;
   const bool threaded = q.threaded = total_staged >= (size_t(1) << 20);   // below 1 MiB a condition-variable wake costs more than the copy
   // an upload worth its staging threads runs on the device's own socket, this thread included: it stages, and the pinned
   // slots strided_prepare may allocate are placed where it runs (a per-frame call is not worth two affinity system calls)
@@ -800,13 +894,13 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
 
 // the row-major host entries (amcx_ctx_features18_c64_host / _c128_host and their one-shot forms): a single-snr
 // container whose frames are row_stride_elems apart -- the row path of the strided engine
-int ctx_run(amcx_ctx* c, const void* iq_host, bool is_c128, int64_t n_frames, int32_t frame_size,
+int ctx_run(amcx_ctx* c, const void* iq_host, int32_t kind, int64_t n_frames, int32_t frame_size,
             int64_t row_stride_elems, float* out_host, int64_t out_row_stride, int32_t variant) {
   if (c == nullptr) return AMCX_EINVAL;
   if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES) return AMCX_EINVAL;
   amcx::Source src;
   src.re = static_cast<const char*>(iq_host);
-  src.kind = is_c128 ? AMCX_SRC_C128 : AMCX_SRC_C64;
+  src.kind = kind;
   return ctx_run_strided(c, src, 1, n_frames, frame_size, 0, row_stride_elems, 1, out_host, out_row_stride, variant);
 }
 
@@ -816,7 +910,7 @@ int stage_any(amcx::Source src, int64_t n_snr, int64_t n_frames,
                      int32_t* plane_major, int32_t* inner_snr_out) {
   const int32_t kind = src.kind;
   if (n_snr < 0 || n_frames < 0 || stride_snr < 0 || stride_frame < 0 || stride_sample < 0 || first_unit < 0 ||
-      n_units < 0 || threads < 0 || threads > 256 || kind < AMCX_SRC_C64 || kind > AMCX_SRC_F64_SPLIT ||
+      n_units < 0 || threads < 0 || threads > 256 || kind < AMCX_SRC_C64 || kind > AMCX_SRC_SC16 ||
       frame_size < AMCX_MIN_FRAME_SIZE || frame_size > AMCX_MAX_FRAME_SIZE)
     return AMCX_EINVAL;
   if (n_frames > 0 && n_snr > (int64_t(1) << 40) / n_frames) return AMCX_EINVAL;
@@ -824,13 +918,16 @@ int stage_any(amcx::Source src, int64_t n_snr, int64_t n_frames,
   amcx::RunMap map;
   if (!classify_layout(n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, &rows, &inner_snr, &map))
     return AMCX_ENOTSUP;
+  if (kind == AMCX_SRC_SC16 && !rows) return AMCX_ENOTSUP;         // sc16: row layouts only
   if (plane_major) *plane_major = rows ? 0 : 1;
   if (inner_snr_out) *inner_snr_out = inner_snr ? 1 : 0;
   const int64_t F = n_snr * n_frames, unit = rows ? frame_size : F, total_units = rows ? F : frame_size;
   if (first_unit + n_units > total_units) return AMCX_EINVAL;
   if (n_units == 0 || unit == 0) return AMCX_OK;
-  if ((src.fd < 0 && src.re == nullptr) || dst == nullptr || dst_bytes < n_units * unit * 8) return AMCX_EINVAL;
-  if (kind < AMCX_SRC_F32_SPLIT) { src.im = nullptr; src.im_off = -1; }
+  if ((src.fd < 0 && src.re == nullptr) || dst == nullptr ||
+      dst_bytes < n_units * unit * (int64_t)amcx::staged_elem_bytes(kind, false))
+    return AMCX_EINVAL;
+  if (kind < AMCX_SRC_F32_SPLIT || kind == AMCX_SRC_SC16) { src.im = nullptr; src.im_off = -1; }
   std::atomic<int> io_error{0};
   src.io_error = &io_error;
   amcx::Pool pool;
@@ -855,7 +952,7 @@ int one_shot(const void* iq_host, bool is_c128, int64_t n_frames, int32_t frame_
   amcx_ctx* c = nullptr;
   int rc = amcx_ctx_create(device, &c);
   if (rc != AMCX_OK) return rc;
-  rc = ctx_run(c, iq_host, is_c128, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, v);
+  rc = ctx_run(c, iq_host, is_c128 ? AMCX_SRC_C128 : AMCX_SRC_C64, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, v);
   (void)amcx_ctx_destroy(c);
   return rc;
 }
@@ -946,6 +1043,27 @@ int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame
   rings.pool = true;
   return run_features(iq_dev, n_frames, frame_size, row_stride_elems, out_dev, out_row_stride, hip_stream, variant,
                       feature_mask, ws, rings);
+}
+
+int64_t amcx_features_sc16_workspace_bytes(int32_t frame_size, int64_t n_frames, int32_t variant) {
+  if (n_frames < 0) return -1;
+  const int v = resolve_variant(frame_size, variant);
+  if (v < 0) return -1;
+  if (n_frames == 0 || (v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(frame_size))) return 0;
+  return sc16_widened_bytes(frame_size, n_frames) + amcx_features18_workspace_bytes(frame_size, n_frames, variant);
+}
+
+int amcx_features_sc16(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_samples, float scale,
+                       float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
+                       void* workspace_dev, int64_t workspace_bytes) {
+  Workspace ws;
+  ws.dev = workspace_dev;
+  ws.bytes = workspace_bytes;
+  RingSource rings;
+  rings.pool = true;
+  const Sc16In in{scale};
+  return run_features(iq_dev, n_frames, frame_size, row_stride_samples, out_dev, out_row_stride, hip_stream, variant,
+                      feature_mask, ws, rings, &in);
 }
 
 int amcx_features18_c64_ex(const void* iq_dev, int64_t n_frames, int32_t frame_size,
@@ -1039,6 +1157,15 @@ int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask) {
   int idle = 0;
   if (!ctx->in_call.compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return AMCX_EINVAL;
   ctx->feature_mask.store(feature_mask, std::memory_order_release);
+  ctx->in_call.fetch_sub(1, std::memory_order_acq_rel);
+  return AMCX_OK;
+}
+
+int amcx_ctx_set_sc16_scale(amcx_ctx* ctx, float scale) {
+  if (ctx == nullptr || !(scale > 0.0f && scale <= 3.4028235e38f)) return AMCX_EINVAL;
+  int idle = 0;                     // claimed as amcx_ctx_set_feature_mask claims it
+  if (!ctx->in_call.compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return AMCX_EINVAL;
+  ctx->sc16_scale.store(scale, std::memory_order_release);
   ctx->in_call.fetch_sub(1, std::memory_order_acq_rel);
   return AMCX_OK;
 }
@@ -1192,13 +1319,19 @@ int amcx_pack_planes_c64(const void* slab_dev, int32_t src_kind, int32_t n_plane
 int amcx_ctx_features18_c64_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames, int32_t frame_size,
                                  int64_t row_stride_elems, float* out_host, int64_t out_row_stride,
                                  int32_t variant) {
-  return ctx_run(ctx, iq_host, false, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, variant);
+  return ctx_run(ctx, iq_host, AMCX_SRC_C64, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, variant);
+}
+
+int amcx_ctx_features18_sc16_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames, int32_t frame_size,
+                                  int64_t row_stride_samples, float* out_host, int64_t out_row_stride,
+                                  int32_t variant) {
+  return ctx_run(ctx, iq_host, AMCX_SRC_SC16, n_frames, frame_size, row_stride_samples, out_host, out_row_stride, variant);
 }
 
 int amcx_ctx_features18_c128_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames, int32_t frame_size,
                                   int64_t row_stride_elems, float* out_host, int64_t out_row_stride,
                                   int32_t variant) {
-  return ctx_run(ctx, iq_host, true, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, variant);
+  return ctx_run(ctx, iq_host, AMCX_SRC_C128, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, variant);
 }
 
 int amcx_features18_c64_host(const void* iq_host, int64_t n_frames, int32_t frame_size,
@@ -1237,6 +1370,16 @@ int amcx_kernel_name_subset(int32_t frame_size, int32_t variant, uint32_t featur
   const int plan = subset_plan(frame_size, v, feature_mask);
   if (plan == amcx::kPlanAll) return amcx_kernel_name(frame_size, variant, buf, buf_len);
   amcx::wave_kernel_name(frame_size, plan, buf, (size_t)buf_len);
+  return AMCX_OK;
+}
+
+int amcx_kernel_name_sc16(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len) {
+  if (buf == nullptr || buf_len <= 0 || !valid_feature_mask(feature_mask)) return AMCX_EINVAL;
+  const int v = resolve_variant(frame_size, variant);
+  if (v < 0) return v;
+  if (v != AMCX_VARIANT_WAVE || !amcx::has_sc16_kernels(frame_size))     // widened, then the complex64 kernel
+    return amcx_kernel_name_subset(frame_size, variant, feature_mask, buf, buf_len);
+  amcx::wave_kernel_name(frame_size, subset_plan(frame_size, v, feature_mask), buf, (size_t)buf_len, true);
   return AMCX_OK;
 }
 

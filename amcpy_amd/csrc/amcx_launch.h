@@ -13,6 +13,7 @@
 #include "amcx_quad_kernel.h"
 #include "amcx_group_kernel.h"
 #include "amcx_short_kernel.h"
+#include "amcx_sc16_kernels.h"
 
 namespace amcx {
 
@@ -60,22 +61,37 @@ struct Frames {
   int64_t out_stride;
   hipStream_t stream;
   int cus;
+  // sc16 frames (include/amcx.h, amcx_features_sc16): read through iq16 instead of iq, a sample's components times `scale`
+  const wave::sc16* iq16 = nullptr;
+  float scale = 1.0f;
 };
 template <class... Tail>
 using FeatureKernel = void (*)(const float2*, long long, long long, float*, long long, Tail...);
+// the sc16 kernels: the scale stands behind the five common arguments
+template <class... Tail>
+using Sc16Kernel = void (*)(const wave::sc16*, long long, long long, float*, long long, float, Tail...);
 
 template <class... Tail>
 inline hipError_t launch_frames(FeatureKernel<Tail...> kern, int64_t grid, int threads, int lds, const Frames& a, Tail... tail) {
   return launch(kern, grid, threads, (size_t)lds, a.stream, a.iq, a.n_frames, a.row_stride, a.out, a.out_stride, tail...);
+}
+template <class... Tail>
+inline hipError_t launch_frames(Sc16Kernel<Tail...> kern, int64_t grid, int threads, int lds, const Frames& a, Tail... tail) {
+  return launch(kern, grid, threads, (size_t)lds, a.stream, a.iq16, a.n_frames, a.row_stride, a.out, a.out_stride, a.scale,
+                tail...);
 }
 
 // ---- the kernel families -----------------------------------------------------------------------------------------------
 // One struct per family, what THE FRAME-SIZE TABLE hands out: the kernel's name (kStem, and kNameArg in angle brackets
 // where it is not 0), kPlanStem where the family has feature-plan kernels (amcx_features_c64_subset) and nullptr where the
 // 18-feature kernel and a column mask serve, the bytes of ring a launch over `cus` CUs takes, and launch<PLAN>().
+// kSc16Stem / kSc16PlanStem: the family's kernels over sc16 frames, which launch<PLAN, wave::sc16>() runs (nullptr: none --
+// amcx_features_sc16 widens into its workspace and runs the complex64 kernel).
 // `ring`: ring_bytes(cus) bytes that no other launch in flight uses, or nullptr.  `mask`: read by the plan kernels only.
 struct SizeDefaults {                            // no plan kernels, no ring, no template argument in the name
   static constexpr const char* kPlanStem = nullptr;
+  static constexpr const char* kSc16Stem = nullptr;
+  static constexpr const char* kSc16PlanStem = nullptr;
   static constexpr int kNameArg = 0;
   static constexpr size_t ring_bytes(int) { return 0; }
 };
@@ -85,14 +101,26 @@ template <int N>
 struct ShortSize : SizeDefaults {
   static constexpr const char* kStem = "amcx_features18_short_kernel";
   static constexpr const char* kPlanStem = "amcx_features_subset_short_kernel";
+  static constexpr const char* kSc16Stem = "amcx_features18_short_sc16_kernel";
+  static constexpr const char* kSc16PlanStem = "amcx_features_subset_short_sc16_kernel";
   static constexpr int kNameArg = N;
 
-  template <int PLAN>
+  template <int PLAN, class E = float2>
   static hipError_t launch(const Frames& a, float*, unsigned mask) {
     using C = shortk::SCfg<N>;
     const int64_t n_pass = (a.n_frames + shortk::kQuad - 1) / shortk::kQuad;
     const int64_t grid = persistent_grid(a.cus, 1, n_pass, C::kWavesPerWG);      // one resident workgroup per CU
-    if constexpr (PLAN == kPlanAll) {
+    if constexpr (std::is_same_v<E, wave::sc16>) {
+      if constexpr (PLAN == kPlanAll) {
+        constexpr Sc16Kernel<> kern = shortk::amcx_features18_short_sc16_kernel<N>;
+        if (const hipError_t e = lds_attr_once<kern>(C::kLdsBytes); e != hipSuccess) return e;
+        return launch_frames(kern, grid, C::kThreads, C::kLdsBytes, a);
+      } else {
+        constexpr Sc16Kernel<unsigned> kern = shortk::amcx_features_subset_short_sc16_kernel<N, PLAN>;
+        if (const hipError_t e = lds_attr_once<kern>(C::kLdsBytes); e != hipSuccess) return e;
+        return launch_frames(kern, grid, C::kThreads, C::kLdsBytes, a, mask);
+      }
+    } else if constexpr (PLAN == kPlanAll) {
       constexpr FeatureKernel<> kern = shortk::amcx_features18_short_kernel<N>;
       if (const hipError_t e = lds_attr_once<kern>(C::kLdsBytes); e != hipSuccess) return e;
       return launch_frames(kern, grid, C::kThreads, C::kLdsBytes, a);
@@ -110,6 +138,8 @@ struct WaveSize : SizeDefaults {
   using C = wave::Cfg<N>;
   static constexpr const char* kStem = "amcx_features18_wave_kernel";
   static constexpr const char* kPlanStem = "amcx_features_subset_wave_kernel";
+  static constexpr const char* kSc16Stem = "amcx_features18_wave_sc16_kernel";
+  static constexpr const char* kSc16PlanStem = "amcx_features_subset_wave_sc16_kernel";
   static constexpr int kNameArg = N;
   static constexpr size_t ring_bytes(int cus) {
     return C::kHasRing ? (size_t)cus * C::kWavesPerWG * C::kRingFloatsPerWave * sizeof(float) : 0;
@@ -128,14 +158,29 @@ struct WaveSize : SizeDefaults {
     }
   }
 
+  // ... and its form over sc16 frames
+  template <int PLAN, bool LDS_FORM, class... Tail>
+  static constexpr Sc16Kernel<Tail...> kernel_sc16() {
+    if constexpr (LDS_FORM) {
+      if constexpr (PLAN == kPlanAll) return wave::amcx_features18_wave_sc16_lds_kernel<N>;
+      else return wave::amcx_features_subset_wave_sc16_lds_kernel<N, PLAN>;
+    } else {
+      if constexpr (PLAN == kPlanAll) return wave::amcx_features18_wave_sc16_kernel<N>;
+      else return wave::amcx_features_subset_wave_sc16_kernel<N, PLAN>;
+    }
+  }
+
   // A launch that has no ring runs the LDS form of a size whose kernel takes one (amcx_features18_wave_lds_kernel): same results.
-  template <int PLAN>
+  template <int PLAN, class E = float2>
   static hipError_t launch(const Frames& a, float* ring, unsigned mask) {
     // persistent: one resident workgroup per CU; at least a frame per wave
     const int64_t grid = persistent_grid(a.cus, 1, a.n_frames, C::kWavesPerWG);
     auto run = [&](auto lds_form, auto tail) {
       return std::apply([&](auto... t) {
-        constexpr auto kern = kernel<PLAN, decltype(lds_form)::value, decltype(t)...>();
+        constexpr auto kern = [] {
+          if constexpr (std::is_same_v<E, wave::sc16>) return kernel_sc16<PLAN, decltype(lds_form)::value, decltype(t)...>();
+          else return kernel<PLAN, decltype(lds_form)::value, decltype(t)...>();
+        }();
         if (const hipError_t e = lds_attr_once<kern>(C::kLdsBytes); e != hipSuccess) return e;
         return launch_frames(kern, grid, C::kThreads, C::kLdsBytes, a, t...);
       }, tail);
@@ -233,18 +278,23 @@ inline bool wave_supports(int frame_size) {
 inline bool has_plan_kernels(int frame_size) {
   return for_frame_size(frame_size, [](auto size) { return decltype(size)::kPlanStem != nullptr; });
 }
+inline bool has_sc16_kernels(int frame_size) {
+  return for_frame_size(frame_size, [](auto size) { return decltype(size)::kSc16Stem != nullptr; });
+}
 // bytes of ring a launch of this frame size over `cus` workgroups needs (0: that size's kernel takes none)
 inline size_t wave_ring_bytes(int frame_size, int cus) {
   return for_frame_size(frame_size, [&](auto size) { return decltype(size)::ring_bytes(cus); });
 }
 // "stem<arg>" of the 18-feature kernel, or "stem<arg, plan>" of a plan kernel
-inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len) {
+// (sc16: of the size's sc16 kernels where it has them -- has_sc16_kernels -- and of the complex64 kernel otherwise)
+inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bool sc16 = false) {
   for_frame_size(frame_size, [&](auto size) {
     using S = decltype(size);
+    const bool typed = sc16 && S::kSc16Stem != nullptr;
     if constexpr (S::kPlanStem != nullptr) {
-      if (plan != kPlanAll) return snprintf(buf, len, "%s<%d, %d>", S::kPlanStem, S::kNameArg, plan);
+      if (plan != kPlanAll) return snprintf(buf, len, "%s<%d, %d>", typed ? S::kSc16PlanStem : S::kPlanStem, S::kNameArg, plan);
     }
-    if constexpr (S::kNameArg != 0) return snprintf(buf, len, "%s<%d>", S::kStem, S::kNameArg);
+    if constexpr (S::kNameArg != 0) return snprintf(buf, len, "%s<%d>", typed ? S::kSc16Stem : S::kStem, S::kNameArg);
     else return snprintf(buf, len, "%s", S::kStem);
   });
 }
@@ -255,6 +305,10 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len) {
 // --kernels, bench.py), so the order of before is kept where those distances depend on it: the 18-feature kernels of the
 // sizes that have plan kernels come first, as when their launchers stood in the kernel headers; amcx.hip names the stream
 // and block kernels next, and the dispatch of its entry (run_features) everything else.  Nothing calls this.
+// The sc16 kernels (ABI 9) stand in FRONT of all of them, as explicit specialisations in a header amcx.hip includes first
+// (amcx_sc16_kernels.h says why): code added behind the first existing kernel would move distances that existing kernels hold.
+// That specialisations are laid out there is what hipcc does today, not a rule it documents: tools/codeobj_gate.py --kernels
+// against the parent commit is what guards it, and the only thing that will notice when a compiler lays them out elsewhere.
 inline void kernel_order_anchor() {
   for_frame_size(0, [](auto size) {
     using S = decltype(size);

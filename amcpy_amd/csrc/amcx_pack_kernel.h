@@ -70,6 +70,8 @@ __global__ __launch_bounds__(256) void amcx_c128_to_c64_kernel(const double2* __
   }
 }
 
+// (sc16 -> complex64, row-packed: amcx_sc16_to_c64_kernel, amcx_sc16_kernels.h)
+
 template <class SRC>
 inline hipError_t launch_pack_planes(const SRC* slab, int n_planes, long long P, long long plane_stride, int S,
                                      long long K, int inner_snr, float2* dst, long long dst_stride, int n0,

@@ -102,6 +102,7 @@ __global__ __launch_bounds__(SCfg<N>::kThreads, SCfg<N>::kWavesPerWG / 4) void a
     float* __restrict__ out, long long out_stride) {
   constexpr int PLAN = kPlanAll;
   [[maybe_unused]] constexpr unsigned mask = kMaskAll;
+  [[maybe_unused]] constexpr float in_scale = 1.0f;           // (read by the sc16 kernels' loader only)
 #include "amcx_short_kernel_body.h"
 }
 
@@ -109,6 +110,7 @@ template <int N, int PLAN>
 __global__ __launch_bounds__(SCfg<N>::kThreads, SCfg<N>::kWavesPerWG / 4) void amcx_features_subset_short_kernel(
     const float2* __restrict__ iq, long long n_frames, long long row_stride,
     float* __restrict__ out, long long out_stride, unsigned mask) {
+  [[maybe_unused]] constexpr float in_scale = 1.0f;
 #include "amcx_short_kernel_body.h"
 }
 

@@ -1,6 +1,7 @@
-// The body of the N = 128 / 256 / 512 kernels (amcx_short_kernel.h), included INSIDE amcx_features18_short_kernel<N> and
-// amcx_features_subset_short_kernel<N, PLAN>, where N, PLAN (amcx_wave_kernel.h: kPlanAll / kPlanNoSpectral / kPlanCumulants),
-// mask and the kernel arguments are in scope: the 18-feature kernel is compiled from this text exactly as it was when it
+// The body of the N = 128 / 256 / 512 kernels (amcx_short_kernel.h), included INSIDE amcx_features18_short_kernel<N>,
+// amcx_features_subset_short_kernel<N, PLAN> and their sc16 forms, where N, PLAN (amcx_wave_kernel.h: kPlanAll /
+// kPlanNoSpectral / kPlanCumulants), mask, in_scale and the kernel arguments are in scope (iq points to float2 or sc16
+// elements: amcx_wave_kernel.h, THE SAMPLE LOADER): the 18-feature kernel is compiled from this text exactly as it was when it
 // was written inside the kernel (as an inlined device function the scalar control flow came out in another order).
 // Not a header of its own.
   using C = SCfg<N>;
@@ -67,10 +68,10 @@
     constexpr int FIRST = decltype(first)::value;
     long long f = p * kQuad + fq;
     if (f >= n_frames) f = n_frames - 1;                      // a pass past the end reads the last frame again (not stored)
-    const float2* src = iq + f * row_stride + 2 * l;
+    const auto* src = iq + f * row_stride + 2 * l;
     static_for<sizeof(v) / sizeof(v[0])>([&](auto jj) {
       constexpr int j = decltype(jj)::value;
-      v[j] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src + 32 * (FIRST + j)));
+      v[j] = load_pair_nt(src + 32 * (FIRST + j), in_scale);
     });
   };
   using HeadRows = std::integral_constant<int, 0>;
@@ -119,7 +120,7 @@
       const float sct = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc), idx));
       const float kwt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, kw_shift), idx));
       float f5x, f9x;
-      wave_exact_frequency<kN>(iq + (f0 + idx) * row_stride, sct, kwt, lane, f5x, f9x);
+      wave_exact_frequency<kN>(iq + (f0 + idx) * row_stride, sct, kwt, lane, f5x, f9x, in_scale);
       if (lane == idx) { feat[4] = f5x; feat[8] = f9x; }
     }
     if (lane < count) {
@@ -135,10 +136,11 @@
       const float sct = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc), idx));
       const int hx = __builtin_amdgcn_readlane(ex_half, idx);
       if constexpr (PLAN == kPlanAll)
-        wave_exact_cumulants<kN>(iq + (f0 + idx) * row_stride, sct, hx, lane, lane == idx, out + (f0 + idx) * out_stride);
+        wave_exact_cumulants<kN>(iq + (f0 + idx) * row_stride, sct, hx, lane, lane == idx, out + (f0 + idx) * out_stride, kMaskAll,
+                                 in_scale);
       else
         wave_exact_cumulants<kN, true>(iq + (f0 + idx) * row_stride, sct, hx, lane, lane == idx, out + (f0 + idx) * out_stride,
-                                       mask);
+                                       mask, in_scale);
     }
     lds_wave_fence();
   };

@@ -255,7 +255,8 @@ class Pool {
 
 // ---- source description ---------------------------------------------------------------------------
 // kinds as in include/amcx.h (AMCX_SRC_*): interleaved complex64 / complex128, or split real / imaginary
-// arrays of float32 / float64 (im == nullptr: a real signal, imaginary part zero)
+// arrays of float32 / float64 (im == nullptr: a real signal, imaginary part zero), or sc16 -- interleaved int16 pairs,
+// 4 bytes per element, which go up as they lie and are never widened on the host (the kernels read them, or the device widens)
 //
 // A source is memory (re / im pointers) or a FILE (fd >= 0; re_off / im_off are byte offsets of the same arrays,
 // im_off < 0: no imaginary part).  A file is read with pread by the staging threads themselves, 16 K elements at a
@@ -272,7 +273,9 @@ struct Source {
   std::atomic<int>* io_error = nullptr;     // set to an errno (EIO for a short file) by the first read that fails
   bool has_im() const { return fd >= 0 ? im_off >= 0 : im != nullptr; }
 };
-enum { kSrcC64 = 0, kSrcC128 = 1, kSrcF32Split = 2, kSrcF64Split = 3 };
+enum { kSrcC64 = 0, kSrcC128 = 1, kSrcF32Split = 2, kSrcF64Split = 3, kSrcSc16 = 4 };
+// bytes of a STAGED element: sc16 and (as_c128) complex128 as they lie, everything else as complex64
+inline size_t staged_elem_bytes(int kind, bool as_c128) { return kind == kSrcSc16 ? 4 : as_c128 ? 16 : 8; }
 
 // run i of the source starts at element (i / cnt_b) * stride_a + (i % cnt_b) * stride_b and is
 // run_len contiguous elements long; staged runs are packed back to back
@@ -378,6 +381,8 @@ inline void stage_elems_file(char* dst, const Source& s, int64_t off, int64_t co
   bool ok = true;
   if (s.kind == kSrcC64) {
     ok = read_exact(s.fd, dst, (size_t)count * 8, s.re_off + off * 8);
+  } else if (s.kind == kSrcSc16) {
+    ok = read_exact(s.fd, dst, (size_t)count * 4, s.re_off + off * 4);
   } else if (s.kind == kSrcC128 && as_c128) {
     ok = read_exact(s.fd, dst, (size_t)count * 16, s.re_off + off * 16);
   } else {
@@ -408,7 +413,8 @@ inline void stage_elems_file(char* dst, const Source& s, int64_t off, int64_t co
 }
 
 // count elements starting at source element `off` -> dst.  as_c128: complex128 copied as it is
-// (16 bytes per element, rounded later on the device); otherwise dst is complex64.
+// (16 bytes per element, rounded later on the device); sc16 is copied as it is (4 bytes per element); otherwise dst is
+// complex64.
 inline void stage_elems(char* dst, const Source& s, int64_t off, int64_t count, bool as_c128) {
   if (s.fd >= 0) {
     stage_elems_file(dst, s, off, count, as_c128);
@@ -418,6 +424,9 @@ inline void stage_elems(char* dst, const Source& s, int64_t off, int64_t count, 
   switch (s.kind) {
     case kSrcC64:
       memcpy(dst, s.re + off * 8, (size_t)count * 8);
+      return;
+    case kSrcSc16:
+      memcpy(dst, s.re + off * 4, (size_t)count * 4);
       return;
     case kSrcC128:
       if (as_c128) memcpy(dst, s.re + off * 16, (size_t)count * 16);
@@ -450,7 +459,7 @@ inline void stage_runs(Pool& pool, char* dst, const Source& s, const RunMap& m, 
                        bool as_c128) {
   const int64_t total = (run1 - run0) * m.run_len;
   if (total <= 0) return;
-  const size_t esz = as_c128 ? 16 : 8;
+  const size_t esz = staged_elem_bytes(s.kind, as_c128);
   // parts of >= 256 KiB staged, about four per thread, so late wakers and slow cores even out
   int64_t parts = pool.size() > 1 ? (int64_t)pool.size() * 4 : 1;
   const int64_t min_elems = (int64_t)(256 * 1024 / esz);

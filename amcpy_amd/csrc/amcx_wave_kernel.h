@@ -714,9 +714,41 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
-template <int N>
-__device__ __forceinline__ void wave_exact_frequency(const float2* __restrict__ src, float sc, float Kw_f, int lane,
-                                                     float& f5, float& f9) {
+// ---------------------------------------------------------------------------
+// THE SAMPLE LOADER.  The wave and short kernels read samples from global memory at three seams -- load_frame / load_rows,
+// wave_exact_frequency, wave_exact_moments -- and everything behind them sees float registers.  The element type E of a
+// frame is float2 (complex64, the samples as they lie) or sc16 (include/amcx.h: two little-endian int16, I then Q): the
+// sample's value is then complex64((float)I * in_scale, (float)Q * in_scale), ONE float32 multiplication per component
+// (int16 -> float32 is exact; the library is built with -ffp-contract=off), so a kernel over sc16 equals, bit for bit, the
+// complex64 kernel over the frame widened that way -- slow paths included, which re-read the frame through these same
+// functions.  in_scale is not read where E is float2.  An sc16 row need only be 4-byte aligned.
+typedef short2 sc16;
+typedef float v4f_t __attribute__((ext_vector_type(4)));
+typedef short v4s_t __attribute__((ext_vector_type(4)));
+typedef v4s_t v4s_a4_t __attribute__((aligned(4)));
+
+__device__ __forceinline__ v4f_t widen_pair(const v4s_t v, float in_scale) {
+  v4f_t r;
+  r.x = (float)v.x * in_scale; r.y = (float)v.y * in_scale; r.z = (float)v.z * in_scale; r.w = (float)v.w * in_scale;
+  return r;
+}
+// one sample
+__device__ __forceinline__ float2 load_sample(const float2* p, float) { return *p; }
+__device__ __forceinline__ float2 load_sample(const sc16* p, float in_scale) {
+  const sc16 v = *p;
+  return make_float2((float)v.x * in_scale, (float)v.y * in_scale);
+}
+// two adjacent samples (re, im, re, im), every byte read once -> non-temporal
+__device__ __forceinline__ v4f_t load_pair_nt(const float2* p, float) {
+  return __builtin_nontemporal_load(reinterpret_cast<const v4f_t*>(p));
+}
+__device__ __forceinline__ v4f_t load_pair_nt(const sc16* p, float in_scale) {
+  return widen_pair(__builtin_nontemporal_load(reinterpret_cast<const v4s_a4_t*>(p)), in_scale);
+}
+
+template <int N, class E = float2>
+__device__ __forceinline__ void wave_exact_frequency(const E* __restrict__ src, float sc, float Kw_f, int lane,
+                                                     float& f5, float& f9, [[maybe_unused]] float in_scale = 1.0f) {
   // lane l takes steps l + 64 j, eight of them per trip so that their sixteen loads are in flight together:
   // the frame comes back from L2 / Infinity Cache / HBM under the full streaming load of the chip, ~2 us a
   // round trip, and a rolled loop of dependent round trips held the wave 120 us per frame.  ONE sweep: the
@@ -734,8 +766,8 @@ __device__ __forceinline__ void wave_exact_frequency(const float2* __restrict__ 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int n = lane + 64 * (U * t + u);
-      p[u] = src[n];
-      q[u] = src[n + 1 < N ? n + 1 : N - 1];
+      p[u] = load_sample(src + n, in_scale);
+      q[u] = load_sample(src + (n + 1 < N ? n + 1 : N - 1), in_scale);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -758,8 +790,9 @@ __device__ __forceinline__ void wave_exact_frequency(const float2* __restrict__ 
 // evaluation of the same samples (features.py:46-58) to ~1e-16 of the summands' scale.  t: sA, sBh, sP, sAA, sX4, sAB,
 // sAP, sBP, sAAA, sABB, sAAB, sBBB, sAAP, sX4P, sABP (FrameSums' order), the totals in every lane.  sc: the power of two
 // a re-run multiplies the frame by (1 in the throughput pass).
-template <int N>
-__device__ __forceinline__ void wave_exact_moments(const float2* __restrict__ src, float sc, int lane, double (&t)[15]) {
+template <int N, class E = float2>
+__device__ __forceinline__ void wave_exact_moments(const E* __restrict__ src, float sc, int lane, double (&t)[15],
+                                                   [[maybe_unused]] float in_scale = 1.0f) {
   // lane l takes the sample pairs (2 l, 2 l + 1) + 128 j, one global_load_dwordx4 each, kG of them per trip of a ROLLED
   // loop, the next trip's requested before this one's are used.  Compact on purpose: this code runs for one frame in
   // ~150, cold every time -- what it costs is its instruction-cache misses and the round trips of the re-read, not its
@@ -768,13 +801,23 @@ __device__ __forceinline__ void wave_exact_moments(const float2* __restrict__ sr
   typedef const __attribute__((address_space(1))) v4f* gv4f;   // (a function argument: without this the loads are flat_load)
   constexpr int kAll = N / 128, kWant = N >= 4096 ? 8 : 4, kG = kAll < kWant ? kAll : kWant, kTrips = kAll / kG;
   static_assert(kAll >= 1 && kAll % kG == 0, "frame sizes are powers of two >= 128");
-  gv4f const base = (gv4f)reinterpret_cast<const v4f*>(src + 2 * lane);
+  // the pair of the lane at 128 k samples into the frame (sc16: one global_load_dwordx2, widened here)
+  auto pair_at = [&](int k) -> v4f {
+    if constexpr (std::is_same_v<E, float2>) {
+      gv4f const base = (gv4f)reinterpret_cast<const v4f*>(src + 2 * lane);
+      return base[64 * k];
+    } else {
+      typedef const __attribute__((address_space(1))) v4s_a4_t* gv4s;
+      gv4s const base = (gv4s)reinterpret_cast<const v4s_a4_t*>(src + 2 * lane);
+      return widen_pair(base[64 * k], in_scale);
+    }
+  };
   double a[15];
 #pragma unroll
   for (int k = 0; k < 15; ++k) a[k] = 0.0;
   v4f nxt[kG];
 #pragma unroll
-  for (int u = 0; u < kG; ++u) nxt[u] = base[64 * u];
+  for (int u = 0; u < kG; ++u) nxt[u] = pair_at(u);
 #pragma unroll 1
   for (int tr = 0; tr < kTrips; ++tr) {
     v4f p[kG];
@@ -782,7 +825,7 @@ __device__ __forceinline__ void wave_exact_moments(const float2* __restrict__ sr
     for (int u = 0; u < kG; ++u) p[u] = nxt[u];
     if (tr + 1 < kTrips) {
 #pragma unroll
-      for (int u = 0; u < kG; ++u) nxt[u] = base[64 * (kG * (tr + 1) + u)];
+      for (int u = 0; u < kG; ++u) nxt[u] = pair_at(kG * (tr + 1) + u);
     }
 #pragma unroll
     for (int u = 0; u < 2 * kG; ++u) {
@@ -826,11 +869,12 @@ __device__ __forceinline__ void wave_exact_moments(const float2* __restrict__ sr
 // cost was IMBALANCE between workgroups (one contiguous slice = one (modulation, SNR) cell: 5 % of noiseless QPSK
 // frames are flagged, none of BPSK's), gone with the interleaved runs of wave_body.
 // MASKED (the feature-subset kernels): only the columns in `mask` are stored.
-template <int N, bool MASKED = false>
-__device__ __forceinline__ void wave_exact_cumulants(const float2* __restrict__ src, float sc, int h, int lane, bool mine,
-                                                     float* __restrict__ dst_row, unsigned mask = kMaskAll) {
+template <int N, bool MASKED = false, class E = float2>
+__device__ __forceinline__ void wave_exact_cumulants(const E* __restrict__ src, float sc, int h, int lane, bool mine,
+                                                     float* __restrict__ dst_row, unsigned mask = kMaskAll,
+                                                     [[maybe_unused]] float in_scale = 1.0f) {
   double t[15];
-  wave_exact_moments<N>(src, sc, lane, t);
+  wave_exact_moments<N>(src, sc, lane, t, in_scale);
   if (mine) {
     if constexpr (MASKED) {
       moment_features(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], (double)N,
@@ -858,10 +902,12 @@ __device__ __forceinline__ void wave_exact_cumulants(const float2* __restrict__ 
 // the second kernel: 4 096 persistent waves drain and ramp up twice per step.)
 // PLAN (kPlanAll: the 18-feature kernel) and `mask`: the feature-subset kernels (amcx_features_subset_wave_kernel below); every
 // section a plan leaves out is left out at compile time, and mask is not read by kPlanAll.
-template <int N, int PLAN = kPlanAll, bool RING = Cfg<N>::kHasRing>
+// E: the element type of a frame, float2 or sc16 (THE SAMPLE LOADER above); in_scale: the sc16 scale, not read for float2.
+template <int N, int PLAN = kPlanAll, bool RING = Cfg<N>::kHasRing, class E = float2>
 __device__ __forceinline__ void wave_body(
-    const float2* __restrict__ iq, long long n_frames, long long row_stride,
-    float* __restrict__ out, long long out_stride, [[maybe_unused]] unsigned mask, [[maybe_unused]] float* ring AMCX_STAMP_ARG) {
+    const E* __restrict__ iq, long long n_frames, long long row_stride,
+    float* __restrict__ out, long long out_stride, [[maybe_unused]] unsigned mask, [[maybe_unused]] float* ring AMCX_STAMP_ARG,
+    [[maybe_unused]] float in_scale = 1.0f) {
   using C = Cfg<N>;
   static_assert(!RING || C::kHasRing, "no ring form at this frame size");
   constexpr int R = C::kFftRows, ROWS = C::kHeldRows;
@@ -978,15 +1024,14 @@ __device__ __forceinline__ void wave_body(
       }
     }
 
-    // lane l gets samples 128 i + 2 l + {0,1} of each row: kRows x global_load_dwordx4; every
-    // byte is read once -> non-temporal
+    // lane l gets samples 128 i + 2 l + {0,1} of each row: kRows x global_load_dwordx4 (sc16: dwordx2, widened by
+    // load_pair_nt); every byte is read once -> non-temporal
     auto load_frame = [&](float (&xr)[2 * ROWS], float (&xi)[2 * ROWS], long long f) {
-      const float2* src = iq + f * row_stride + 2 * lane;
+      const E* src = iq + f * row_stride + 2 * lane;
       static_for<ROWS>([&](auto ii) {
         constexpr int i = decltype(ii)::value;
         typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f* p = reinterpret_cast<const v4f*>(src + 128 * i);
-        const v4f v = __builtin_nontemporal_load(p);
+        const v4f v = load_pair_nt(src + 128 * i, in_scale);
         xr[2 * i] = v.x; xi[2 * i] = v.y; xr[2 * i + 1] = v.z; xi[2 * i + 1] = v.w;
       });
     };
@@ -1394,7 +1439,7 @@ __device__ __forceinline__ void wave_body(
         if constexpr (RG) sct = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc), idx));
         const float kwt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, kw_shift), idx));
         float f5x, f9x;
-        wave_exact_frequency<N>(iq + ft * row_stride, sct, kwt, lane, f5x, f9x);
+        wave_exact_frequency<N>(iq + ft * row_stride, sct, kwt, lane, f5x, f9x, in_scale);
         if (lane == idx) { feat[4] = f5x; feat[8] = f9x; }
       }
       if (lane < count && !redo) {
@@ -1419,9 +1464,9 @@ __device__ __forceinline__ void wave_body(
           hx = __builtin_amdgcn_readlane(ex_half, idx);
         }
         if constexpr (PLAN == kPlanAll)
-          wave_exact_cumulants<N>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride);
+          wave_exact_cumulants<N>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride, kMaskAll, in_scale);
         else
-          wave_exact_cumulants<N, true>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride, mask);
+          wave_exact_cumulants<N, true>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride, mask, in_scale);
       }
       lds_wave_fence();
       if constexpr (FROM_RING) batch_f = f;

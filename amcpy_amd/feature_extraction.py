@@ -58,6 +58,7 @@ import numpy as np
 
 from . import _lib
 from .config import Config
+from .features import SC16, _sc16_scale, sc16_view
 from .sharding import collectives_forced, gather_frame_columns, gather_rows, shard_by_frames, shard_range, sharded_features
 
 
@@ -111,7 +112,8 @@ class FileComplex:
     """A complex ``(n_snr, n_frames, L)`` container that is still in its FILE: the byte offsets of its real and
     imaginary arrays (column-major float32 / float64, how a level-5 .mat stores an uncompressed complex variable;
     ``imag_offset`` None: a real signal), or of ONE interleaved complex array (``interleaved=True``: a raw
-    complex64 / complex128 stream, C-ordered; with ``order="F"`` the {real, imag} compound dataset of a MATLAB -v7.3
+    complex64 / complex128 stream, or a stream of sc16 samples -- ``store_dtype=features.SC16``, int16 (I, Q) pairs --
+    C-ordered; with ``order="F"`` the {real, imag} compound dataset of a MATLAB -v7.3
     file, whose bytes are the column-major variable).  Nothing is read or mapped here: the engine's staging threads pread
     the file block by block on their way to the pinned slots (``amcx_ctx_features18_strided_file``), so the
     variable never exists in host memory outside the page cache.  Indexing (tests, injected engines) goes
@@ -124,8 +126,8 @@ class FileComplex:
         self.interleaved = bool(interleaved)
         if not self.interleaved and self.store not in (np.float32, np.float64):
             raise TypeError(f"split containers hold float32 or float64, got {self.store}")
-        if self.interleaved and self.store not in (np.complex64, np.complex128):
-            raise TypeError(f"interleaved containers hold complex64 or complex128, got {self.store}")
+        if self.interleaved and self.store not in (np.complex64, np.complex128, SC16):
+            raise TypeError(f"interleaved containers hold complex64, complex128 or sc16, got {self.store}")
         self.shape, self.ndim = tuple(int(x) for x in shape), len(shape)
         self.real_offset, self.imag_offset = int(real_offset), (None if imag_offset is None else int(imag_offset))
         self.dtype = self.store if self.interleaved else \
@@ -257,17 +259,18 @@ def _native_source(arr):
     copied first."""
     if isinstance(arr, FileComplex):
         if arr.interleaved:
-            kind = _lib.SRC_C64 if arr.store == np.complex64 else _lib.SRC_C128
+            kind = _lib.SRC_SC16 if arr.store == SC16 else _lib.SRC_C64 if arr.store == np.complex64 else _lib.SRC_C128
         else:
             kind = _lib.SRC_F32_SPLIT if arr.store == np.float32 else _lib.SRC_F64_SPLIT
         return arr, arr.real_offset, arr.imag_offset, kind, list(arr.strides_elems), arr.store.itemsize, arr.fileno()
     if isinstance(arr, SplitComplex):
         re, im = arr.real, arr.imag
         kind = _lib.SRC_F32_SPLIT if re.dtype == np.float32 else _lib.SRC_F64_SPLIT
-    elif isinstance(arr, np.ndarray) and arr.dtype in (np.complex64, np.complex128, np.float32, np.float64):
+    elif isinstance(arr, np.ndarray) and arr.dtype in (np.complex64, np.complex128, np.float32, np.float64, SC16):
         re, im = arr, None
         kind = {np.dtype(np.complex64): _lib.SRC_C64, np.dtype(np.complex128): _lib.SRC_C128,
-                np.dtype(np.float32): _lib.SRC_F32_SPLIT, np.dtype(np.float64): _lib.SRC_F64_SPLIT}[arr.dtype]
+                np.dtype(np.float32): _lib.SRC_F32_SPLIT, np.dtype(np.float64): _lib.SRC_F64_SPLIT,
+                SC16: _lib.SRC_SC16}[arr.dtype]
     else:
         return None
     item = re.itemsize
@@ -282,7 +285,9 @@ def _native_source(arr):
 class HipEngine:
     """``engine(frames) -> (F, 18) float32`` through device memory.
 
-    ``frames`` is an (F, L) array / memmap, or a :class:`FrameRows` over an (n_snr, n_frames, L)
+    ``frames`` is an (F, L) array / memmap -- complex, real, or sc16: (F, L) of ``features.SC16`` or (F, L, 2) int16
+    (I, Q) pairs, which go up as they lie, 4 bytes per sample, and are multiplied by ``sc16_scale`` on the device
+    (amcx_features_sc16) -- or a :class:`FrameRows` over an (n_snr, n_frames, L)
     container in any memory order (ndarray or :class:`SplitComplex`).  The container is read where it
     lies by ``amcx_ctx_features18_strided_host``: host threads stage contiguous runs -- sample planes
     of a Fortran-ordered container, rows of a C-ordered one -- into three pinned slots (rounding
@@ -292,8 +297,10 @@ class HipEngine:
     ``stats`` of the last call: frames, seconds, bytes over PCIe, source bytes, chunks, threads."""
 
     def __init__(self, frame_size: int, device: Optional[int] = None, chunk_bytes: int = 32 << 20,
-                 threads: Optional[int] = None, round_on_device: bool = False, feature_ids=None):
+                 threads: Optional[int] = None, round_on_device: bool = False, feature_ids=None,
+                 sc16_scale: float = _lib.SC16_SCALE):
         self.N = int(frame_size)
+        self.sc16_scale = _sc16_scale(sc16_scale)
         # feature_ids: None (all 18) or the ids to compute; the result stays (F, 18), NaN outside the set (KeyError for an
         # unknown id, here, before anything is launched)
         self.feature_ids = _feature_ids(feature_ids)
@@ -319,6 +326,7 @@ class HipEngine:
             self._ctx = _lib.HostContext(self.device)
             self._ctx.configure(self.threads, self.chunk_bytes, int(self.round_on_device))
             self._ctx.set_feature_mask(self.mask)
+            self._ctx.set_sc16_scale(self.sc16_scale)
         return self._ctx
 
     def _run_block(self, src, base_elems: int, n_snr: int, n_frames: int, strides, out: np.ndarray) -> None:
@@ -352,6 +360,8 @@ class HipEngine:
             rows = frames
         else:
             arr = frames if isinstance(frames, SplitComplex) else np.asarray(frames)
+            if not isinstance(arr, SplitComplex) and arr.dtype == np.int16:
+                arr = sc16_view(arr)                         # (F, L, 2) int16 pairs -> (F, L) sc16 samples, no copy
             if arr.ndim != 2:
                 raise ValueError(f"expected (F, L) frames, got shape {arr.shape}")
             rows = FrameRows(arr[None] if not isinstance(arr, SplitComplex) else
@@ -374,7 +384,8 @@ class HipEngine:
         if src is None:
             # integer / half / exotic dtypes, negative or sub-element strides, no contiguous axis: one
             # C-ordered copy of the part that is used, then the row path
-            block = np.ascontiguousarray(rows.to_array(), dtype=np.complex64 if rows.dtype == np.complex64 else np.complex128)
+            # (sc16 stays sc16: the library takes its row layouts only)
+            block = np.ascontiguousarray(rows.to_array(), dtype=rows.dtype if rows.dtype in (np.complex64, SC16) else np.complex128)
             rows = FrameRows(block[None], 1, F)
             src = _native_source(rows.parsed)
         ss, sk, sn = src[4]
@@ -618,11 +629,13 @@ def extract_modulation(parsed: np.ndarray, cfg: Config, *, compute=None, device:
 
 
 def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_frames: Optional[int] = None,
-                       compute=None, device: Optional[int] = None, feature_ids=None) -> np.ndarray:
+                       compute=None, device: Optional[int] = None, feature_ids=None, sample_format: str = "cf32",
+                       scale: float = _lib.SC16_SCALE) -> np.ndarray:
     """Features of a raw complex64 sample stream on disk (GNU Radio file sink: interleaved
     float32 I/Q, no header -- what the reference's legacy reader takes with
     ``np.fromfile(..., dtype=np.complex64)`` and a fixed number of leading samples dropped,
-    old/read_binary_stream.py:28,48,54-56).  The file is memory-mapped and cut into
+    old/read_binary_stream.py:28,48,54-56), or, ``sample_format="sc16"``, of a stream of int16 (I, Q) pairs (UHD sc16,
+    SigMF ci16_le), each component multiplied by ``scale`` on the device.  The file is memory-mapped and cut into
     consecutive ``frame_size``-sample frames (a trailing partial frame is dropped); the staging
     threads read the file slot by slot, so it never has to fit in host memory.
     Returns ``(n_frames, 18)`` float32 (``feature_ids``: only these, NaN in the other columns)."""
@@ -632,21 +645,30 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
         raise ValueError("frame_size must be >= 2")
     if skip_samples < 0:
         raise ValueError("skip_samples must be >= 0")
-    n_total = Path(path).stat().st_size // 8 - skip_samples
+    if sample_format not in ("cf32", "sc16"):
+        raise ValueError("sample_format is 'cf32' or 'sc16'")
+    store = np.dtype(np.complex64) if sample_format == "cf32" else SC16
+    scale = _sc16_scale(scale) if sample_format == "sc16" else _lib.SC16_SCALE      # (not read for cf32)
+    n_total = Path(path).stat().st_size // store.itemsize - skip_samples
     n_frames = max(0, n_total // frame_size)
     if max_frames is not None:
         n_frames = min(n_frames, int(max_frames))
     if n_frames == 0:
         return np.empty((0, 18), dtype=np.float32)
     if compute is None:                 # the staging threads read the file themselves, part by part
-        stream = FileComplex(path, np.complex64, (1, n_frames, frame_size), 8 * skip_samples, interleaved=True)
+        stream = FileComplex(path, store, (1, n_frames, frame_size), store.itemsize * skip_samples, interleaved=True)
         try:
-            return np.asarray(HipEngine(frame_size, device, feature_ids=feature_ids)(FrameRows(stream, 1, n_frames)),
-                              dtype=np.float32)
+            engine = HipEngine(frame_size, device, feature_ids=feature_ids, sc16_scale=scale)
+            return np.asarray(engine(FrameRows(stream, 1, n_frames)), dtype=np.float32)
         finally:
             stream.release()
-    frames = np.memmap(path, dtype=np.complex64, mode="r", offset=8 * skip_samples,
+    frames = np.memmap(path, dtype=store, mode="r", offset=store.itemsize * skip_samples,
                        shape=(n_frames, frame_size))
+    if sample_format == "sc16":         # an injected engine (tests) sees the complex64 frames the device computes on
+        wide = np.empty(frames.shape, dtype=np.complex64)
+        wide.real = frames["i"].astype(np.float32) * np.float32(scale)
+        wide.imag = frames["q"].astype(np.float32) * np.float32(scale)
+        frames = wide
     return np.asarray(compute(frames), dtype=np.float32)
 
 

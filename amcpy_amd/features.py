@@ -8,7 +8,9 @@ with the same argument meaning, result order and ``KeyError`` for an unknown
 id -- computed by the HIP kernels behind the C ABI (include/amcx.h), never on
 the CPU.  The batch entry points the extraction driver uses are
 :func:`features18` (torch tensor in HBM -> torch tensor in HBM, asynchronous on
-the current stream) and :func:`features18_host` (numpy in, numpy out).
+the current stream) and :func:`features18_host` (numpy in, numpy out);
+:func:`features18_sc16` / :func:`features18_sc16_host` take 16-bit integer IQ
+(int16 (I, Q) pairs: UHD sc16, SigMF ci16_le) as it lies, half the bytes.
 
 Feature ids (reference config.py:118-137): 1 gamma_max, 2 sigma_ap,
 3 sigma_dp, 4 sigma_aa, 5 sigma_af, 6 X, 7 X2, 8 mu42^a, 9 mu42^f,
@@ -124,6 +126,87 @@ def features18_iq_pairs(iq_pairs, **kw):
     return features18(torch.view_as_complex(iq_pairs), **kw)
 
 
+# one sc16 sample as numpy sees it: two little-endian int16, I then Q (include/amcx.h, amcx_features_sc16)
+SC16 = np.dtype([("i", "<i2"), ("q", "<i2")])
+
+
+def _sc16_scale(scale) -> float:
+    """``scale`` as the float32 the library multiplies by; ValueError unless it is finite and > 0."""
+    s = float(np.float32(scale))
+    if not (np.isfinite(s) and s > 0.0):
+        raise ValueError(f"scale must be a finite float32 > 0, got {scale!r}")
+    return s
+
+
+def sc16_view(pairs: np.ndarray) -> np.ndarray:
+    """(..., L, 2) int16 -> (..., L) view of :data:`SC16` samples (no copy).  TypeError for another dtype or a last
+    dimension that is not 2, ValueError for pairs that are not interleaved in memory."""
+    if not isinstance(pairs, np.ndarray) or pairs.dtype != np.int16 or pairs.ndim < 2 or pairs.shape[-1] != 2:
+        raise TypeError("expected an int16 array whose last dimension is (I, Q)")
+    if pairs.strides[-1] != 2 or any(st % 4 for st in pairs.strides[:-1]):
+        raise ValueError("(I, Q) int16 pairs must be interleaved in memory")
+    return pairs.view(SC16)[..., 0]
+
+
+def features18_sc16(iq, out=None, *, scale=_lib.SC16_SCALE, frame_size: int | None = None, variant="auto",
+                    feature_ids=None):
+    """The features of every frame of 16-bit integer IQ in GPU memory, read as it lies (amcx_features_sc16).
+
+    iq    : torch.int16 tensor on a GPU, shape (..., L, 2): I then Q, interleaved (unit stride in the last dimension, 2
+            in the one before it), frames uniformly strided as for :func:`features18`.
+    scale : a finite float32 > 0.  The frame's value is complex64(float32(I) * scale, float32(Q) * scale), and the
+            result is BIT-IDENTICAL to :func:`features18` (same variant and feature_ids) on that complex64 frame.
+    out, frame_size, variant, feature_ids: as :func:`features18`.
+    At 128 ... 4096 (wave / auto) kernels read the int16 themselves; every other size and variant widens the frames
+    into a workspace from torch's allocator and runs the complex64 path."""
+    import torch
+
+    mask = _lib.FEATURES_ALL if feature_ids is None else _lib.feature_mask(feature_ids)
+    scale = _sc16_scale(scale)
+    if not isinstance(iq, torch.Tensor) or iq.dtype != torch.int16:
+        raise TypeError("iq must be a torch.int16 tensor")
+    if iq.dim() < 2 or iq.shape[-1] != 2:
+        raise TypeError("iq must have shape (..., L, 2): the last dimension is (I, Q)")
+    L = iq.shape[-2]
+    if iq.stride(-1) != 1 or (L > 1 and iq.stride(-2) != 2):
+        raise ValueError("(I, Q) pairs must be interleaved in memory")
+    if not iq.is_cuda:
+        raise ValueError("iq must live in GPU memory (use features18_sc16_host for numpy input)")
+    N = L if frame_size is None else int(frame_size)
+    if N > L:
+        raise ValueError(f"frame_size {N} exceeds row length {L}")
+    lead = iq.shape[:-2]
+    n_frames = int(np.prod(lead)) if lead else 1
+    flat = iq.reshape(n_frames, L, 2) if iq.dim() != 3 else iq
+    if flat.data_ptr() != iq.data_ptr() or (n_frames > 1 and flat.stride(0) % 2):
+        raise ValueError("frames must be uniformly strided (no copy is made)")
+    row_stride = flat.stride(0) // 2 if n_frames > 1 else max(L, N)
+    if out is None:
+        out = torch.empty(lead + (_lib.NUM_FEATURES,), dtype=torch.float32, device=iq.device)
+    else:
+        if out.dtype != torch.float32 or out.device != iq.device:
+            raise TypeError("out must be float32 on the same device")
+        if tuple(out.shape[:-1]) != tuple(lead) or out.shape[-1] < _lib.NUM_FEATURES:
+            raise ValueError("out must have shape (..., >=18) matching iq")
+    oflat = out.reshape(n_frames, out.shape[-1]) if out.dim() != 2 else out
+    if oflat.data_ptr() != out.data_ptr() or oflat.stride(-1) != 1:
+        raise ValueError("out must be uniformly strided with unit stride in the last dimension")
+    out_stride = oflat.stride(0) if n_frames > 1 else out.shape[-1]
+    _lib.require_torch_runtime()
+    lib = _lib.load()
+    v = _variant(variant)
+    with torch.cuda.device(iq.device):
+        stream = torch.cuda.current_stream(iq.device).cuda_stream
+        # the widened copy and the any-size path's FFT workspace, from torch's allocator (see features18)
+        need = int(lib.amcx_features_sc16_workspace_bytes(N, n_frames, v)) if n_frames > 0 else 0
+        ws = torch.empty(need, dtype=torch.uint8, device=iq.device) if need > 0 else None
+        _lib.check(lib.amcx_features_sc16(iq.data_ptr(), n_frames, N, row_stride, scale, oflat.data_ptr(), out_stride,
+                                          stream, v, mask, None if ws is None else ws.data_ptr(), max(need, 0)))
+        if ws is not None:
+            ws.record_stream(torch.cuda.current_stream(iq.device))
+    return out[..., :_lib.NUM_FEATURES]
+
+
 _tls = threading.local()
 
 
@@ -163,6 +246,29 @@ def features18_host(frames: np.ndarray, *, frame_size: int | None = None, device
     out = np.empty((x2.shape[0], _lib.NUM_FEATURES), dtype=np.float32)
     ctx = _host_context(int(device))
     ctx.set_feature_mask(_lib.FEATURES_ALL if mask is None else mask)
+    ctx.run(x2, N, out, _variant(variant))
+    return out.reshape(lead + (_lib.NUM_FEATURES,))
+
+
+def features18_sc16_host(frames: np.ndarray, *, scale=_lib.SC16_SCALE, frame_size: int | None = None, device: int = 0,
+                         variant="auto", feature_ids=None) -> np.ndarray:
+    """numpy (..., L, 2) int16 (I, Q) pairs -> numpy (..., 18) float32 via the GPU.  The samples cross the link as
+    they lie, 4 bytes each, and are never widened on the host; the result equals :func:`features18_sc16`'s."""
+    mask = _mask(feature_ids)
+    scale = _sc16_scale(scale)
+    x = frames
+    if not isinstance(x, np.ndarray) or x.dtype != np.int16 or x.ndim < 2 or x.shape[-1] != 2:
+        raise TypeError("expected an int16 array whose last dimension is (I, Q)")
+    L = x.shape[-2]
+    N = L if frame_size is None else int(frame_size)
+    if N > L:
+        raise ValueError(f"frame_size {N} exceeds row length {L}")
+    lead = x.shape[:-2]
+    x2 = np.ascontiguousarray(x.reshape(-1, L, 2))
+    out = np.empty((x2.shape[0], _lib.NUM_FEATURES), dtype=np.float32)
+    ctx = _host_context(int(device))
+    ctx.set_feature_mask(_lib.FEATURES_ALL if mask is None else mask)
+    ctx.set_sc16_scale(scale)
     ctx.run(x2, N, out, _variant(variant))
     return out.reshape(lead + (_lib.NUM_FEATURES,))
 

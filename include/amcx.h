@@ -89,8 +89,11 @@ extern "C" {
  * 6 = EVERY frame size 2 ... 32768: AMCX_MAX_BLOCK_FRAME_SIZE 32768 (8193 ... 32767 were AMCX_ENOTSUP but for 16384);
  * amcx_features18_c64_ws / amcx_features18_workspace_bytes;
  * 7 = feature subsets: AMCX_FEATURES_*, amcx_features_c64_subset, amcx_ctx_set_feature_mask, amcx_kernel_name_subset;
- * 8 = classification on the device: AMCX_ACT_*, amcx_mlp_params_floats, amcx_mlp_classify_f32, amcx_mlp_kernel_name. */
-#define AMCX_ABI_VERSION 8
+ * 8 = classification on the device: AMCX_ACT_*, amcx_mlp_params_floats, amcx_mlp_classify_f32, amcx_mlp_kernel_name;
+ * 9 = frames of 16-bit integer IQ (sc16): amcx_features_sc16, amcx_features_sc16_workspace_bytes, amcx_kernel_name_sc16,
+ * AMCX_SRC_SC16 for the strided host / file entries and amcx_stage_host / _file, amcx_ctx_set_sc16_scale,
+ * amcx_ctx_features18_sc16_host. */
+#define AMCX_ABI_VERSION 9
 #define AMCX_NUM_FEATURES 18
 
 /* FEATURE MASKS (ABI 7): bit j - 1 stands for feature id j (1 gamma_max ... 18 |C63|).  The reference's default selection,
@@ -201,6 +204,35 @@ int amcx_features_c64_subset(const void* iq_dev, int64_t n_frames, int32_t frame
                              void* workspace_dev, int64_t workspace_bytes);
 
 /*
+ * ABI 9.  Frames of 16-bit integer IQ (UHD sc16, SigMF ci16_le), read as they lie: half the bytes of complex64.
+ *   - A sample is two little-endian int16, I then Q, interleaved (numpy int16 of shape (..., L, 2)); row_stride_samples
+ *     counts samples of 4 bytes, any value >= frame_size; only the first frame_size samples of a row are read.  iq_dev
+ *     must be 4-byte aligned.
+ *   - The frame's value is complex64((float)I * scale, (float)Q * scale): int16 -> float32 is exact, and the product is
+ *     ONE float32 multiplication per component, nothing fused into it.  scale is a finite float32 > 0 (2^-15 maps the
+ *     int16 range onto [-1, 1)); NaN, infinite, 0 or negative is AMCX_EINVAL, checked beside the other arguments, before
+ *     a device is looked for.
+ *   - The features are those amcx_features_c64_subset writes for the SAME variant and feature_mask on that complex64
+ *     frame, BIT FOR BIT: the NaN / inf / 0 pattern, the range re-run, the +-pi-tie path, the fp64 cancellation path and
+ *     the NaN of the columns not asked for included.  Every slow path re-reads the frame through the same loader and the
+ *     same multiplication.
+ *   - AMCX_VARIANT_WAVE / AUTO at 128 ... 4096 run kernels that read sc16 themselves (amcx_kernel_name_sc16 names them:
+ *     "...sc16..."), and need no workspace.  Every other frame size, and AMCX_VARIANT_BLOCK, widens the frames into the
+ *     head of the workspace (8 * frame_size * n_frames bytes rounded up to 256; workspace_dev must then be 8-byte aligned:
+ *     the copy is complex64 -- otherwise AMCX_EINVAL) and runs the complex64 path on the copy,
+ *     handing it the rest of the workspace under the rules of amcx_features18_c64_ws.
+ *     amcx_features_sc16_workspace_bytes is 0 where a kernel reads sc16 itself, otherwise the widened copy plus
+ *     amcx_features18_workspace_bytes (-1 for arguments amcx_features_sc16 refuses); a workspace smaller than the widened
+ *     copy, where one is needed, is AMCX_EINVAL.
+ * Asynchronous on the caller's stream, allocates nothing, and can be captured into a graph wherever
+ * amcx_features_c64_subset can.
+ */
+int64_t amcx_features_sc16_workspace_bytes(int32_t frame_size, int64_t n_frames, int32_t variant);
+int amcx_features_sc16(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_samples, float scale,
+                       float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask,
+                       void* workspace_dev, int64_t workspace_bytes);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -246,6 +278,15 @@ int amcx_ctx_features18_c64_host(amcx_ctx* ctx, const void* iq_host, int64_t n_f
 int amcx_ctx_features18_c128_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames,
                                   int32_t frame_size, int64_t row_stride_elems, float* out_host,
                                   int64_t out_row_stride, int32_t variant);
+/* ABI 9: rows of sc16 (amcx_features_sc16: int16 I, int16 Q; row_stride_samples in samples of 4 bytes) in host memory.
+ * They go over the link as they lie, 4 bytes per sample, and are never widened on the host; the device runs what
+ * amcx_features_sc16 runs, with the context's scale (amcx_ctx_set_sc16_scale) and feature mask. */
+int amcx_ctx_features18_sc16_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames,
+                                  int32_t frame_size, int64_t row_stride_samples, float* out_host,
+                                  int64_t out_row_stride, int32_t variant);
+/* ABI 9: what every later sc16 call of this context multiplies an int16 component by (default 2^-15).  AMCX_EINVAL for a
+ * scale that is NaN, infinite, 0 or negative, or while a call is running on the context. */
+int amcx_ctx_set_sc16_scale(amcx_ctx* ctx, float scale);
 
 /*
  * Name of the kernel `variant` resolves to for this frame_size (as it shows in
@@ -259,6 +300,9 @@ int amcx_kernel_name(int32_t frame_size, int32_t variant, char* buf, int32_t buf
  * the 18-feature kernel amcx_kernel_name names (followed by amcx_mask_columns_kernel unless the mask is
  * AMCX_FEATURES_ALL).  AMCX_EINVAL for an invalid mask. */
 int amcx_kernel_name_subset(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len);
+/* ABI 9: the same for amcx_features_sc16 -- an sc16 kernel at 128 ... 4096 (WAVE / AUTO), otherwise the complex64 kernel
+ * that runs on the widened copy. */
+int amcx_kernel_name_sc16(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len);
 
 /* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
  * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
@@ -277,6 +321,10 @@ int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask);
  *             separate real arrays with the same strides (how a MATLAB v5 file stores a complex
  *             variable; im == NULL: a real signal).  Doubles are rounded to float32 to nearest even
  *             (== numpy astype), by the staging threads on their way to pinned memory.
+ *             AMCX_SRC_SC16 (ABI 9): `re` points at interleaved (I, Q) int16, an element is one sample of 4 bytes,
+ *             `im` is ignored; the value of a sample is amcx_features_sc16's with the context's scale
+ *             (amcx_ctx_set_sc16_scale).  Staged and uploaded as it lies (upload_stats.pcie_bytes = 4 bytes per
+ *             sample).  Row layouts only (stride_sample == 1): a plane-major layout is AMCX_ENOTSUP.
  *   strides   in ELEMENTS of the source (complex elements for the interleaved kinds), all >= 0.
  *             One of them must be 1:
  *               stride_sample == 1 (C order)        rows go up in chunks of whole frames and the
@@ -296,6 +344,7 @@ int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask);
 #define AMCX_SRC_C128 1
 #define AMCX_SRC_F32_SPLIT 2
 #define AMCX_SRC_F64_SPLIT 3
+#define AMCX_SRC_SC16 4
 int amcx_ctx_features18_strided_host(amcx_ctx* ctx, const void* re, const void* im, int32_t kind,
                                      int64_t n_snr, int64_t n_frames, int32_t frame_size,
                                      int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
@@ -307,7 +356,8 @@ int amcx_ctx_features18_strided_host(amcx_ctx* ctx, const void* re, const void* 
  * A unit is a frame (row-major containers: dst[unit][sample]) or a sample plane (plane-major:
  * dst[unit][position], position order as amcx_pack_planes_c64's inner_snr says); *plane_major and
  * *inner_snr report which (either may be NULL).  For callers that run their own copy engine -- and
- * how the staging and rounding logic is tested where there is no GPU.
+ * how the staging and rounding logic is tested where there is no GPU.  AMCX_SRC_SC16: rows only, staged as packed sc16
+ * (4 bytes per sample, dst_bytes accordingly).
  */
 int amcx_stage_host(const void* re, const void* im, int32_t kind, int64_t n_snr, int64_t n_frames,
                     int32_t frame_size, int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
