@@ -45,21 +45,25 @@ What is different underneath:
 from __future__ import annotations
 
 import functools
+import json
 import os
 import socket
 import tempfile
-import threading
 import time
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import closing
 from pathlib import Path
-from typing import Callable, Iterator, List, Optional, Tuple
+from typing import Callable, List, Optional
 
 import numpy as np
 
 from . import _lib
 from .config import Config
-from .features import SC16, _sc16_scale, sc16_view
-from .sharding import collectives_forced, gather_frame_columns, gather_rows, shard_by_frames, shard_range, sharded_features
+from .features import SC16, _sc16_scale
+from .frame_sources import (FileComplex, FrameColumns, FrameRows, SplitComplex, _native_source,  # noqa: F401 (re-exported)
+                            as_frame_rows)
+from .sharding import FrameCut, collectives_forced, sharded_features
 
 
 def _process_group_up() -> bool:
@@ -80,203 +84,6 @@ def _rank_world():
     except Exception:
         pass
     return 0, 1
-
-
-# ----------------------------------------------------------------------------
-# frame sources: rows of the C-order flattening (snr-major) of a container array
-# ----------------------------------------------------------------------------
-class SplitComplex:
-    """A complex ``(n_snr, n_frames, L)`` container held as two real arrays of equal shape, strides
-    and dtype (float32 / float64) -- how a MATLAB v5 file stores a complex variable, so a
-    memory-mapped .mat goes to the GPU without a complex array being built (amcpy_amd/matfile.py).
-    ``imag`` may be None (a real signal).  Indexing returns an ordinary complex ndarray."""
-
-    def __init__(self, real: np.ndarray, imag: Optional[np.ndarray]):
-        if imag is not None and (imag.shape != real.shape or imag.strides != real.strides or imag.dtype != real.dtype):
-            raise ValueError("real and imaginary parts must agree in shape, strides and dtype")
-        if real.dtype not in (np.float32, np.float64):
-            raise TypeError(f"split containers hold float32 or float64, got {real.dtype}")
-        self.real, self.imag = real, imag
-        self.source = None            # "mapped": views of a memory-mapped file every process can map for itself
-        self.shape, self.ndim = real.shape, real.ndim
-        self.dtype = np.dtype(np.complex64 if real.dtype == np.float32 else np.complex128)
-
-    def __getitem__(self, idx) -> np.ndarray:
-        out = np.asarray(self.real[idx]).astype(self.dtype)
-        if self.imag is not None:
-            out.imag = self.imag[idx]
-        return out
-
-
-class FileComplex:
-    """A complex ``(n_snr, n_frames, L)`` container that is still in its FILE: the byte offsets of its real and
-    imaginary arrays (column-major float32 / float64, how a level-5 .mat stores an uncompressed complex variable;
-    ``imag_offset`` None: a real signal), or of ONE interleaved complex array (``interleaved=True``: a raw
-    complex64 / complex128 stream, or a stream of sc16 samples -- ``store_dtype=features.SC16``, int16 (I, Q) pairs --
-    C-ordered; with ``order="F"`` the {real, imag} compound dataset of a MATLAB -v7.3
-    file, whose bytes are the column-major variable).  Nothing is read or mapped here: the engine's staging threads pread
-    the file block by block on their way to the pinned slots (``amcx_ctx_features18_strided_file``), so the
-    variable never exists in host memory outside the page cache.  Indexing (tests, injected engines) goes
-    through a memory mapping.  ``release()`` closes the descriptor."""
-
-    def __init__(self, path, store_dtype, shape, real_offset: int, imag_offset: Optional[int] = None, *,
-                 interleaved: bool = False, order: Optional[str] = None):
-        self.path = Path(path)
-        self.store = np.dtype(store_dtype)
-        self.interleaved = bool(interleaved)
-        if not self.interleaved and self.store not in (np.float32, np.float64):
-            raise TypeError(f"split containers hold float32 or float64, got {self.store}")
-        if self.interleaved and self.store not in (np.complex64, np.complex128, SC16):
-            raise TypeError(f"interleaved containers hold complex64, complex128 or sc16, got {self.store}")
-        self.shape, self.ndim = tuple(int(x) for x in shape), len(shape)
-        self.real_offset, self.imag_offset = int(real_offset), (None if imag_offset is None else int(imag_offset))
-        self.dtype = self.store if self.interleaved else \
-            np.dtype(np.complex64 if self.store == np.float32 else np.complex128)
-        # element strides: column-major for the split arrays of a .mat (and a -v7.3 compound), row-major for a raw stream
-        self.order = order if order is not None else ("C" if self.interleaved else "F")
-        if self.order not in ("C", "F"):
-            raise ValueError("order is 'C' or 'F'")
-        st, acc = [], 1
-        for n in (self.shape if self.order == "F" else self.shape[::-1]):
-            st.append(acc)
-            acc *= n
-        self.strides_elems = tuple(st if self.order == "F" else st[::-1])
-        self.source = "file"
-        self._fd, self._view, self._lock = None, None, threading.Lock()
-
-    def fileno(self) -> int:
-        with self._lock:
-            if self._fd is None:
-                self._fd = os.open(str(self.path), os.O_RDONLY)
-            return self._fd
-
-    def release(self) -> None:
-        with self._lock:
-            if self._fd is not None:
-                os.close(self._fd)
-                self._fd = None
-            self._view = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def _mapped(self):
-        if self._view is None:
-            re = np.memmap(self.path, dtype=self.store, mode="r", offset=self.real_offset, shape=self.shape, order=self.order)
-            if self.interleaved:
-                self._view = re
-            else:
-                im = None if self.imag_offset is None else \
-                    np.memmap(self.path, dtype=self.store, mode="r", offset=self.imag_offset, shape=self.shape, order=self.order)
-                self._view = SplitComplex(re, im)
-        return self._view
-
-    def __getitem__(self, idx) -> np.ndarray:
-        return np.asarray(self._mapped()[idx])
-
-
-class FrameRows:
-    """Frames ``[lo, hi)`` of ``parsed[:n_snr, :n_frames]`` flattened snr-major
-    (frame g = snr * n_frames + k, the order feature_extraction.py:64-72 enqueues
-    them in), WITHOUT materialising the flattening: for the Fortran-ordered arrays
-    ``loadmat`` returns, ``reshape`` would be a full transposing copy."""
-
-    def __init__(self, parsed, n_snr: int, n_frames: int, lo: int = 0, hi: Optional[int] = None):
-        self.parsed, self.n_snr, self.n_frames = parsed, n_snr, n_frames
-        self.lo = lo
-        self.hi = n_snr * n_frames if hi is None else hi
-        self.dtype = parsed.dtype
-
-    @property
-    def shape(self):
-        return (self.hi - self.lo, self.parsed.shape[2])
-
-    def slice(self, lo: int, hi: int) -> "FrameRows":
-        return FrameRows(self.parsed, self.n_snr, self.n_frames, self.lo + lo, self.lo + hi)
-
-    def blocks(self) -> Iterator[Tuple[int, int, int, int]]:
-        """``(s0, s1, k0, k1)`` rectangles of the (snr, frame) grid that tile ``[lo, hi)`` in order:
-        at most a partial first snr row, a run of whole rows, a partial last row."""
-        a = self.lo
-        while a < self.hi:
-            s, k = divmod(a, self.n_frames)
-            if k == 0 and self.hi - a >= self.n_frames:
-                m = (self.hi - a) // self.n_frames
-                yield s, s + m, 0, self.n_frames
-                a += m * self.n_frames
-            else:
-                take = min(self.hi - a, self.n_frames - k)
-                yield s, s + 1, k, k + take
-                a += take
-
-    def gather(self, dst: np.ndarray, g0: int, g1: int, n: int) -> None:
-        """dst[(g1-g0), n] <- the first n samples of frames [g0, g1) of this range (host copy:
-        tests and injected engines; the production engine never calls it)."""
-        row = 0
-        for s0, s1, k0, k1 in self.slice(g0, g1).blocks():
-            for s in range(s0, s1):
-                np.copyto(dst[row:row + k1 - k0], self.parsed[s, k0:k1, :n], casting="same_kind")
-                row += k1 - k0
-
-    def to_array(self) -> np.ndarray:
-        out = np.empty(self.shape, dtype=self.dtype)
-        self.gather(out, 0, self.shape[0], self.shape[1])
-        return out
-
-
-class FrameColumns(FrameRows):
-    """Frames ``[k_lo, k_hi)`` of EVERY snr row of ``parsed[:n_snr, :n_frames]``, snr-major (row
-    ``s * (k_hi - k_lo) + (k - k_lo)``): a rank's share when a container is cut along its frame axis
-    (``sharding.shard_by_frames``).  In a column-major container that is one contiguous run of every sample
-    plane -- what the staging threads read from the file or copy at full rate."""
-
-    def __init__(self, parsed, n_snr: int, n_frames: int, k_lo: int, k_hi: int):
-        super().__init__(parsed, n_snr, n_frames, 0, n_snr * max(0, k_hi - k_lo))
-        self.k_lo, self.k_hi = k_lo, max(k_lo, k_hi)
-
-    def slice(self, lo: int, hi: int) -> "FrameRows":
-        if (lo, hi) != (0, self.hi):
-            raise NotImplementedError("a frame-axis share is taken whole")
-        return self
-
-    def blocks(self) -> Iterator[Tuple[int, int, int, int]]:
-        if self.k_hi > self.k_lo and self.n_snr:
-            yield 0, self.n_snr, self.k_lo, self.k_hi
-
-    def gather(self, dst: np.ndarray, g0: int, g1: int, n: int) -> None:
-        w = self.k_hi - self.k_lo
-        for g in range(g0, g1):                           # host copy: tests and injected engines only
-            s, k = divmod(g, w)
-            np.copyto(dst[g - g0], self.parsed[s, self.k_lo + k, :n], casting="same_kind")
-
-
-def _native_source(arr):
-    """(keepalive, re_ptr, im_ptr, kind, element strides, bytes per element, fd) of a container the
-    native engine can read in place -- pointers, or byte offsets into the file ``fd`` -- or None if it has to be
-    copied first."""
-    if isinstance(arr, FileComplex):
-        if arr.interleaved:
-            kind = _lib.SRC_SC16 if arr.store == SC16 else _lib.SRC_C64 if arr.store == np.complex64 else _lib.SRC_C128
-        else:
-            kind = _lib.SRC_F32_SPLIT if arr.store == np.float32 else _lib.SRC_F64_SPLIT
-        return arr, arr.real_offset, arr.imag_offset, kind, list(arr.strides_elems), arr.store.itemsize, arr.fileno()
-    if isinstance(arr, SplitComplex):
-        re, im = arr.real, arr.imag
-        kind = _lib.SRC_F32_SPLIT if re.dtype == np.float32 else _lib.SRC_F64_SPLIT
-    elif isinstance(arr, np.ndarray) and arr.dtype in (np.complex64, np.complex128, np.float32, np.float64, SC16):
-        re, im = arr, None
-        kind = {np.dtype(np.complex64): _lib.SRC_C64, np.dtype(np.complex128): _lib.SRC_C128,
-                np.dtype(np.float32): _lib.SRC_F32_SPLIT, np.dtype(np.float64): _lib.SRC_F64_SPLIT,
-                SC16: _lib.SRC_SC16}[arr.dtype]
-    else:
-        return None
-    item = re.itemsize
-    if any(st < 0 or st % item for st in re.strides):
-        return None
-    return (re, im), re.ctypes.data, (None if im is None else im.ctypes.data), kind, [st // item for st in re.strides], item, None
 
 
 # ----------------------------------------------------------------------------
@@ -356,17 +163,7 @@ class HipEngine:
         self.stats["from_file"] = max(self.stats.get("from_file", 0), st["from_file"])
 
     def __call__(self, frames) -> np.ndarray:
-        if isinstance(frames, FrameRows):
-            rows = frames
-        else:
-            arr = frames if isinstance(frames, SplitComplex) else np.asarray(frames)
-            if not isinstance(arr, SplitComplex) and arr.dtype == np.int16:
-                arr = sc16_view(arr)                         # (F, L, 2) int16 pairs -> (F, L) sc16 samples, no copy
-            if arr.ndim != 2:
-                raise ValueError(f"expected (F, L) frames, got shape {arr.shape}")
-            rows = FrameRows(arr[None] if not isinstance(arr, SplitComplex) else
-                             SplitComplex(arr.real[None], None if arr.imag is None else arr.imag[None]),
-                             1, arr.shape[0])
+        rows = as_frame_rows(frames)
         F, L = rows.shape
         if L < self.N:
             raise ValueError(f"rows of {L} samples are shorter than frame_size {self.N}")
@@ -454,7 +251,9 @@ class DeviceFanOut:
     every modulation over the devices: along its FRAME axis when that balances (``sharding.shard_by_frames`` -- one
     contiguous run per sample plane of a column-major .mat), along the snr-major flattening otherwise.  Each device's
     rows land directly in the result; no process group and no gather are involved.  A device may be listed twice
-    (two contexts on it: how the one-GPU test box exercises the path)."""
+    (two contexts on it: how the one-GPU test box exercises the path).  ``frames`` is whatever one :class:`HipEngine`
+    takes (``as_frame_rows``), a :class:`SplitComplex` and (F, L, 2) int16 pairs -- at the engines' default
+    ``sc16_scale`` -- included."""
 
     def __init__(self, frame_size: int, devices, threads: Optional[int] = None, chunk_bytes: int = 32 << 20,
                  feature_ids=None):
@@ -500,36 +299,16 @@ class DeviceFanOut:
         """What each engine's context bound itself to (amcx_ctx_placement), in device order."""
         return [e._context().placement() for e in self.engines]
 
-    def shares(self, rows: FrameRows):
-        """[(rows of device i, where they go)]: ``("columns", k_lo, k_hi)`` or ``("rows", lo, hi)``."""
-        W = len(self.engines)
-        whole = type(rows) is FrameRows and rows.lo == 0 and rows.hi == rows.n_snr * rows.n_frames
-        if whole and shard_by_frames(rows.n_snr, rows.n_frames, W):
-            cuts = [shard_range(rows.n_frames, r, W) for r in range(W)]
-            return [(FrameColumns(rows.parsed, rows.n_snr, rows.n_frames, a, b), ("columns", a, b)) for a, b in cuts]
-        F = rows.shape[0]
-        cuts = [shard_range(F, r, W) for r in range(W)]
-        return [(rows.slice(a, b), ("rows", a, b)) for a, b in cuts]
-
     def __call__(self, frames) -> np.ndarray:
-        if not isinstance(frames, FrameRows):
-            arr = np.asarray(frames)
-            if arr.ndim != 2:
-                raise ValueError(f"expected (F, L) frames, got shape {arr.shape}")
-            frames = FrameRows(arr[None], 1, arr.shape[0])
-        rows = frames
+        rows = as_frame_rows(frames)
         F = rows.shape[0]
         out = np.empty((F, 18), dtype=np.float32)
         if F == 0:
             return out
         t0 = time.perf_counter()
-        shares = self.shares(rows)
-
-        def one(i):
-            part, where = shares[i]
-            return self.engines[i](part) if part.shape[0] else np.empty((0, 18), dtype=np.float32)
-
-        futs = [self._pool.submit(one, i) for i in range(len(shares))]
+        cut = _frame_cut(rows, len(self.engines))
+        shares = [_share(rows, cut, i) for i in range(cut.world)]
+        futs = [self._pool.submit(_features_of, e, part) for e, part in zip(self.engines, shares)]
         failures = []
         for i, fut in enumerate(futs):                      # every device finishes (or fails) before anything is raised
             try:
@@ -537,15 +316,11 @@ class DeviceFanOut:
             except Exception as exc:
                 failures.append(f"device {self.devices[i]}: {type(exc).__name__}: {exc}")
                 continue
-            kind, a, b = shares[i][1]
-            if kind == "rows":
-                out[a:b] = blk
-            elif b > a:
-                out.reshape(rows.n_snr, rows.n_frames, 18)[:, a:b] = blk.reshape(rows.n_snr, b - a, 18)
+            cut.place(out, i, blk)
         if failures:
             raise RuntimeError("feature extraction failed on " + "; ".join(failures))
         self.stats = {"seconds": time.perf_counter() - t0, "devices": list(self.devices),
-                      "frames_per_device": [sh[0].shape[0] for sh in shares],
+                      "frames_per_device": [part.shape[0] for part in shares],
                       "bytes_uploaded": sum(e.stats.get("bytes_uploaded", 0) for e in self.engines),
                       "source_bytes": sum(e.stats.get("source_bytes", 0) for e in self.engines)}
         return out
@@ -591,6 +366,45 @@ def _masked_compute(compute, feature_ids):
     return run
 
 
+def _subset(feature_ids, compute):
+    """The prologue of every entry point: ``(_feature_ids(feature_ids), the injected engine masked to them or None)``."""
+    feature_ids = _feature_ids(feature_ids)
+    return feature_ids, (None if compute is None else _masked_compute(compute, feature_ids))
+
+
+def _frame_cut(rows: FrameRows, world: int) -> FrameCut:
+    """The cut of ``rows`` over ``world`` workers: a whole container's, or the flat one of any other range."""
+    if type(rows) is FrameRows and rows.lo == 0 and rows.hi == rows.n_snr * rows.n_frames:
+        return FrameCut(rows.n_snr, rows.n_frames, world)
+    return FrameCut.flat(rows.shape[0], world)
+
+
+def _share(rows: FrameRows, cut: FrameCut, rank: int) -> FrameRows:
+    """Worker ``rank``'s source under ``cut``: its frames of every snr row, or its range of the flattening."""
+    lo, hi = cut.range(rank)
+    if cut.by_frames:
+        return FrameColumns(rows.parsed, rows.n_snr, rows.n_frames, lo, hi)
+    return rows.slice(lo, hi)
+
+
+def _features_of(engine, part: FrameRows) -> np.ndarray:
+    """``engine(part)`` as float32; an empty share does not reach the engine."""
+    if part.shape[0] == 0:
+        return np.empty((0, 18), dtype=np.float32)
+    return np.asarray(engine(part), dtype=np.float32)
+
+
+def _file_stream_features(path, store, offset: int, n_frames: int, N: int, device, feature_ids,
+                          sc16_scale: float = _lib.SC16_SCALE) -> np.ndarray:
+    """An interleaved stream ``offset`` bytes into a file: the staging threads read it themselves, part by part."""
+    stream = FileComplex(path, store, (1, n_frames, N), offset, interleaved=True)
+    try:
+        engine = HipEngine(N, device, feature_ids=feature_ids, sc16_scale=sc16_scale)
+        return np.asarray(engine(FrameRows(stream, 1, n_frames)), dtype=np.float32)
+    finally:
+        stream.release()
+
+
 def _check_container(parsed, cfg: Config):
     n_snr = len(cfg.signals.snr_values)
     n_frames = cfg.signals.num_frames
@@ -608,21 +422,14 @@ def extract_modulation(parsed: np.ndarray, cfg: Config, *, compute=None, device:
     """All 18 features of one modulation's ``(n_snr, n_frames, L)`` array, which every rank
     holds (``run_extraction`` itself decodes on rank 0 only).  Returns float32
     ``(n_snr, n_frames, 18)`` on rank 0 (None on other ranks).  ``feature_ids``: only these (NaN in the other columns)."""
-    feature_ids = _feature_ids(feature_ids)
-    compute = None if compute is None else _masked_compute(compute, feature_ids)
+    feature_ids, compute = _subset(feature_ids, compute)
     n_snr, n_frames, N = _check_container(parsed, cfg)
     rank, world = _rank_world()
     rows = FrameRows(parsed, n_snr, n_frames)
     if compute is None:
         engine = HipEngine(N, device, threads=cfg.signals.num_threads, feature_ids=feature_ids)
-        if shard_by_frames(n_snr, n_frames, world):          # frames [k_lo, k_hi) of every snr row (sharding.py)
-            k_lo, k_hi = shard_range(n_frames, rank, world)
-            local = engine(FrameColumns(parsed, n_snr, n_frames, k_lo, k_hi)) if k_hi > k_lo else \
-                np.empty((0, 18), dtype=np.float32)
-            return gather_frame_columns(local, n_snr, n_frames, rank, world, group)
-        lo, hi = shard_range(n_snr * n_frames, rank, world)
-        local = engine(rows.slice(lo, hi)) if hi > lo else np.empty((0, 18), dtype=np.float32)
-        mat = gather_rows(local, n_snr * n_frames, rank, world, group)
+        cut = _frame_cut(rows, world)
+        mat = cut.gather(_features_of(engine, _share(rows, cut, rank)), rank, group)
     else:                           # injected engine (tests): plain (F, L) arrays
         mat = sharded_features(rows.to_array(), N, compute, rank, world, group)
     return None if mat is None else mat.reshape(n_snr, n_frames, 18)
@@ -639,8 +446,7 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
     consecutive ``frame_size``-sample frames (a trailing partial frame is dropped); the staging
     threads read the file slot by slot, so it never has to fit in host memory.
     Returns ``(n_frames, 18)`` float32 (``feature_ids``: only these, NaN in the other columns)."""
-    feature_ids = _feature_ids(feature_ids)
-    compute = None if compute is None else _masked_compute(compute, feature_ids)
+    feature_ids, compute = _subset(feature_ids, compute)
     if frame_size < 2:
         raise ValueError("frame_size must be >= 2")
     if skip_samples < 0:
@@ -655,13 +461,9 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
         n_frames = min(n_frames, int(max_frames))
     if n_frames == 0:
         return np.empty((0, 18), dtype=np.float32)
-    if compute is None:                 # the staging threads read the file themselves, part by part
-        stream = FileComplex(path, store, (1, n_frames, frame_size), store.itemsize * skip_samples, interleaved=True)
-        try:
-            engine = HipEngine(frame_size, device, feature_ids=feature_ids, sc16_scale=scale)
-            return np.asarray(engine(FrameRows(stream, 1, n_frames)), dtype=np.float32)
-        finally:
-            stream.release()
+    if compute is None:
+        return _file_stream_features(path, store, store.itemsize * skip_samples, n_frames, frame_size, device,
+                                     feature_ids, scale)
     frames = np.memmap(path, dtype=store, mode="r", offset=store.itemsize * skip_samples,
                        shape=(n_frames, frame_size))
     if sample_format == "sc16":         # an injected engine (tests) sees the complex64 frames the device computes on
@@ -690,8 +492,7 @@ def extract_iq_pairs(dataset, frame_size: Optional[int] = None, *, first_frame: 
     chunks from the file as they are sliced) is read ``chunk_frames`` at a time by a reader thread one
     chunk ahead of the upload, so the set never has to fit in host memory.  Returns ``(n_frames, 18)``
     float32 (``feature_ids``: only these, NaN in the other columns)."""
-    feature_ids = _feature_ids(feature_ids)
-    compute = None if compute is None else _masked_compute(compute, feature_ids)
+    feature_ids, compute = _subset(feature_ids, compute)
     shape = tuple(dataset.shape)
     if len(shape) != 3 or shape[2] != 2:
         raise ValueError(f"expected an (F, L, 2) dataset of (I, Q) pairs, got shape {shape}")
@@ -712,11 +513,8 @@ def extract_iq_pairs(dataset, frame_size: Optional[int] = None, *, first_frame: 
     if (isinstance(dataset, hdf5_min.Dataset) and N == L and dataset.file_offset is not None and dataset.little_endian):
         # a contiguous dataset is a raw interleaved complex64 stream at a known place in the file: the staging threads
         # read it themselves, slot by slot (as extract_raw_stream does), and libhdf5 is not on the data path at all
-        stream = FileComplex(dataset.file_path, np.complex64, (1, hi - lo, L), dataset.file_offset + lo * L * 8, interleaved=True)
-        try:
-            return np.asarray(HipEngine(N, device, feature_ids=feature_ids)(FrameRows(stream, 1, hi - lo)), dtype=np.float32)
-        finally:
-            stream.release()
+        return _file_stream_features(dataset.file_path, np.complex64, dataset.file_offset + lo * L * 8, hi - lo, N, device,
+                                     feature_ids)
     engine = HipEngine(N, device, feature_ids=feature_ids)
     if isinstance(dataset, np.ndarray):
         return engine(_pairs_as_complex(dataset[lo:hi]))
@@ -909,7 +707,6 @@ def _already_extracted(out_path: Path, key: str, shape, provenance: Optional[dic
     container's name, size and modification time).  A file that is cut short, was written for another frame size / SNR
     grid / container, or has no record (written before records existed, or by the reference) does not qualify; nor does one
     computed for a feature subset that does not cover the one asked for (no "features" in a record: all 18)."""
-    import json
     import scipy.io
     try:
         seen = {name: (tuple(shp), cls) for name, shp, cls in scipy.io.whosmat(str(out_path))}
@@ -930,6 +727,209 @@ def _already_extracted(out_path: Path, key: str, shape, provenance: Optional[dic
         return False
 
 
+def _extraction_engine(cfg: Config, world: int, compute, device, devices, feature_ids):
+    """``engine(FrameRows) -> (F, 18)``: the injected ``compute`` over plain arrays, a fan-out over ``devices``, or one engine."""
+    N, threads = cfg.signals.frame_size, max(1, int(cfg.signals.num_threads))
+    if devices is not None:
+        devices = [int(d) for d in devices]
+        if compute is not None or device is not None:
+            raise ValueError("devices= stands in for device= / compute=")
+        if world > 1:
+            raise ValueError("devices= drives several GPUs from one process; with a process group of several ranks "
+                             "every rank takes its one device=")
+        if len(devices) == 1:
+            device, devices = devices[0], None
+    if compute is not None:
+        return lambda rows: compute(rows.to_array())
+    if devices:
+        return default_fanout(N, devices, threads, feature_ids)
+    return default_engine(N, device, threads, feature_ids)
+
+
+def _modulations_to_do(cfg: Config, mat_path: Path, rank: int, world: int, resume: bool, feature_ids, verbose: bool):
+    """The configuration's modulations, less (``resume``) those rank 0 finds done; every rank gets rank 0's answer."""
+    mods = list(cfg.signals.modulations_with_noise)
+    if not resume:
+        return mods
+    todo = mods
+    if rank == 0:
+        shape = (len(cfg.signals.snr_values), cfg.signals.num_frames, 18)
+        todo = [m for m in mods if not _already_extracted(
+            cfg.paths.calculated_features / f"{m}_features.mat", cfg.signals.mat_info[m], shape,
+            _provenance(cfg, mat_path, cfg.signals.mat_info[m], feature_ids))]
+        if verbose and len(todo) < len(mods):
+            print(f"resume: {len(mods) - len(todo)} of {len(mods)} feature files are complete, computing {todo}")
+    if world > 1:
+        import torch.distributed as dist
+        box = [todo]
+        dist.broadcast_object_list(box, src=0)
+        todo = box[0]
+    return todo
+
+
+class _FeatureWriter:
+    """Rank 0's one writer thread, and what each file is computed from -- taken here, BEFORE the container is read: a
+    container replaced mid-run leaves a record that no longer matches it."""
+
+    def __init__(self, cfg: Config, mat_path: Path, mods, feature_ids, rank: int, verbose: bool):
+        import scipy.io
+        self.cfg, self.verbose, self._savemat = cfg, verbose, scipy.io.savemat
+        self.provenance = {m: _provenance(cfg, mat_path, cfg.signals.mat_info[m], feature_ids) for m in mods}
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="amcx-writer") if rank == 0 else None
+        self._writes = []
+
+    def submit(self, mod: str, feats: np.ndarray, t0: float) -> None:
+        self._writes.append(self._pool.submit(self._save, mod, feats, t0))
+
+    def _save(self, mod: str, feats: np.ndarray, t0: float) -> None:
+        out_path = self.cfg.paths.calculated_features / f"{mod}_features.mat"
+        # written aside and renamed: an interrupted run never leaves a partial file under the final name (what
+        # resume= and every downstream loader look at)
+        tmp_path = out_path.with_name(f"{out_path.stem}.{os.getpid()}.tmp.mat")
+        record = _provenance_path(out_path)
+        try:
+            record.unlink(missing_ok=True)                  # never a fresh record beside an old file, or an old one beside a new
+            self._savemat(str(tmp_path), {"Modulation": mod, self.cfg.signals.mat_info[mod]: feats})
+            os.replace(tmp_path, out_path)
+            record.write_text(json.dumps(self.provenance[mod]) + "\n")
+        finally:
+            tmp_path.unlink(missing_ok=True)
+        if self.verbose:
+            print(f"[{mod}] {feats.shape[0] * feats.shape[1]} frames in "
+                  f"{time.perf_counter() - t0:.2f}s -> {out_path}")
+
+    def close(self, reraise: bool = True) -> None:
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+        for w in self._writes if reraise else ():
+            w.result()                                      # a failed savemat raises here
+
+
+def _single_process_loop(cfg: Config, mat_path: Path, mods, direct: bool, engine, writer: _FeatureWriter) -> None:
+    """One process, no collectives: reader threads ahead of the GPU, the writer thread behind it."""
+    from .matfile import BufferPool, compressed_variable_bytes
+    # A compressed container is inflate-bound: three reader threads run ahead (zlib releases the GIL).  An
+    # uncompressed variable is only LOCATED here: the native engine's staging threads read it from the file
+    # on their way to the pinned slots.  With an injected engine (tests) it is read with preadv into two
+    # pairs of buffers that take turns: reading is faster than first-touching fresh pages, mapped or allocated.
+    pool = BufferPool()
+    depth = _read_ahead(compressed_variable_bytes(mat_path), len(mods))
+    with closing(_prefetched(mods, lambda m: _load_variable(mat_path, cfg.signals.mat_info[m], pool, direct), depth)) as feed:
+        for mod, fut in feed:
+            t0 = time.perf_counter()
+            parsed = fut.result()                           # the reader threads are up to `depth` variables ahead
+            try:
+                n_snr, n_frames, _ = _check_container(parsed, cfg)
+                feats = _features_of(engine, FrameRows(parsed, n_snr, n_frames)).reshape(n_snr, n_frames, 18)
+            finally:
+                getattr(parsed, "release", lambda: None)()
+            del parsed
+            writer.submit(mod, feats, t0)
+
+
+# What the steps of the rank loop share.  mapped: variables rank 0's reader thread has already mapped; published: rank
+# 0's shared files not yet removed (run_extraction's list: it removes what a failure leaves behind)
+_RankRun = namedtuple("_RankRun", "cfg mat_path direct rank world engine shared_host mapped published")
+
+
+def decode_locally(run: _RankRun, mod: str):
+    """Reader of ranks on different hosts: each decodes for itself, as the reference's children do."""
+    parsed = _load_variable(run.mat_path, run.cfg.signals.mat_info[mod], None, run.direct)
+    return (parsed,) + _check_container(parsed, run.cfg)[:2]
+
+
+def decode_and_publish(run: _RankRun, mod: str):
+    """Rank 0's reader when all ranks share its host -> ``(path of the published copy or "", n_snr, n_frames)``."""
+    parsed, n_snr, n_frames = decode_locally(run, mod)
+    if getattr(parsed, "source", None) in ("mapped", "file"):
+        run.mapped[mod] = parsed                            # every rank reads / maps the variable itself: nothing to publish
+        return "", n_snr, n_frames
+    sig = run.cfg.signals
+    path = _publish_container(parsed, n_snr, n_frames, sig.frame_size, max(1, int(sig.num_threads)))
+    run.published.append(path)                              # (several reader threads publish at once: the path stays local)
+    return str(path), n_snr, n_frames
+
+
+def _rank_reader(run: _RankRun):
+    """What this rank's reader thread does ahead of its GPU; on a shared host only rank 0 has one (None elsewhere)."""
+    return decode_locally if not run.shared_host else decode_and_publish if run.rank == 0 else None
+
+
+def _announce(run: _RankRun, mod: str, fut):
+    """Step 1, shared host only (else None): every rank learns ``(published path or "", n_snr, n_frames)``, or that rank
+    0 could not read the modulation -- then all raise."""
+    if not run.shared_host:
+        return None
+    import torch.distributed as dist
+    meta = [None]
+    if run.rank == 0:
+        try:
+            meta = [("ok",) + fut.result()]
+        except Exception as exc:                            # every rank must leave the collective
+            meta = [("error", repr(exc), 0, 0)]
+    dist.broadcast_object_list(meta, src=0)
+    status, shared, n_snr, n_frames = meta[0]
+    if status != "ok":
+        raise RuntimeError(f"rank 0 could not read {run.cfg.signals.mat_info[mod]!r} from {run.mat_path}: {shared}")
+    return shared, n_snr, n_frames
+
+
+def _compute_share(run: _RankRun, mod: str, fut, where):
+    """Step 2: this rank's share -> ``(cut, local rows, failure)``.  Nothing raises: a failure is kept, as a string, until
+    every rank has reported.  The container is let go of on return, so nobody maps a shared file past step 3."""
+    cut = local = None
+    try:
+        if where is None:
+            parsed, n_snr, n_frames = fut.result()
+        else:
+            shared, n_snr, n_frames = where
+            if shared:
+                parsed = np.load(shared, mmap_mode="r")
+            else:                                           # mapped straight from the container, by every rank
+                parsed = run.mapped.pop(mod, None) if run.rank == 0 else None
+                if parsed is None:
+                    parsed = _load_variable(run.mat_path, run.cfg.signals.mat_info[mod], None, run.direct)
+                _check_container(parsed, run.cfg)
+        cut = FrameCut(n_snr, n_frames, run.world)          # the same answer on every rank
+        local = _features_of(run.engine, _share(FrameRows(parsed, n_snr, n_frames), cut, run.rank))
+        # a wrong row count would raise inside the gather on THIS rank only and leave the others in the
+        # collective: it is reported with the status word instead
+        if local.shape != (cut.rows(run.rank), 18):
+            raise RuntimeError(f"engine returned {local.shape} for {cut.rows(run.rank)} frames")
+    except Exception as exc:
+        return cut, local, f"{type(exc).__name__}: {exc}"
+    return cut, local, None
+
+
+def _agree_and_gather(run: _RankRun, mod: str, where, cut, local, failure):
+    """Step 3: one status word per rank BEFORE the data collective -- all ranks raise together, or all gather.  The
+    all-gather is also the point after which nobody maps the shared file any more: rank 0 removes it."""
+    import torch.distributed as dist
+    statuses = [None] * run.world
+    dist.all_gather_object(statuses, failure)
+    if where is not None and run.rank == 0 and where[0]:
+        Path(where[0]).unlink(missing_ok=True)
+        run.published.remove(Path(where[0]))
+    bad = [(r, s) for r, s in enumerate(statuses) if s is not None]
+    if bad:
+        raise RuntimeError(f"feature extraction of {mod!r} failed on " + "; ".join(f"rank {r}: {s}" for r, s in bad))
+    return cut.gather(local, run.rank)
+
+
+def _rank_loop(run: _RankRun, mods, writer: _FeatureWriter) -> None:
+    """Several ranks (or one, under ``collectives_forced``): the three steps per modulation; rank 0 writes."""
+    reader = _rank_reader(run)
+    feed = ((m, None) for m in mods) if reader is None else _prefetched(mods, functools.partial(reader, run))
+    with closing(feed):                                     # waits for a decode / publish still in flight
+        for mod, fut in feed:
+            t0 = time.perf_counter()
+            where = _announce(run, mod, fut)
+            cut, local, failure = _compute_share(run, mod, fut, where)
+            mat = _agree_and_gather(run, mod, where, cut, local, failure)
+            if run.rank == 0:
+                writer.submit(mod, mat.reshape(cut.n_snr, cut.n_frames, 18), t0)
+
+
 def run_extraction(cfg: Config, *, compute=None, device: Optional[int] = None, devices=None,
                    verbose: bool = True, resume: bool = False, feature_ids=None) -> None:
     """Drop-in for the reference's ``run_extraction(cfg)``: writes one
@@ -944,195 +944,28 @@ def run_extraction(cfg: Config, *, compute=None, device: Optional[int] = None, d
     reference's ``(n_snr, n_frames, 18)`` float32 layout with NaN in the other columns, and the record beside each file
     lists them (``"features"``) -- a full run's record does not change.  ``resume`` trusts a file whose recorded set
     covers the one asked for."""
-    import scipy.io
-
-    feature_ids = _feature_ids(feature_ids)
+    native = compute is None
+    feature_ids, compute = _subset(feature_ids, compute)
     rank, world = _rank_world()
     cfg.paths.ensure_dirs()
     mat_path = cfg.paths.mat_data / cfg.paths.mat_filename
-    N = cfg.signals.frame_size
-    threads = max(1, int(cfg.signals.num_threads))
-    if devices is not None:
-        devices = [int(d) for d in devices]
-        if compute is not None or device is not None:
-            raise ValueError("devices= stands in for device= / compute=")
-        if world > 1:
-            raise ValueError("devices= drives several GPUs from one process; with a process group of several ranks "
-                             "every rank takes its one device=")
-        if len(devices) == 1:
-            device, devices = devices[0], None
-    if compute is not None:
-        engine = compute = _masked_compute(compute, feature_ids)
-    elif devices:
-        engine = default_fanout(N, devices, threads, feature_ids)
-    else:
-        engine = default_engine(N, device, threads, feature_ids)
-    mods = list(cfg.signals.modulations_with_noise)
-    if resume:
-        todo = mods
-        if rank == 0:
-            shape = (len(cfg.signals.snr_values), cfg.signals.num_frames, 18)
-            todo = [m for m in mods if not _already_extracted(cfg.paths.calculated_features / f"{m}_features.mat",
-                                                              cfg.signals.mat_info[m], shape,
-                                                              _provenance(cfg, mat_path, cfg.signals.mat_info[m],
-                                                                          feature_ids))]
-            if verbose and len(todo) < len(mods):
-                print(f"resume: {len(mods) - len(todo)} of {len(mods)} feature files are complete, computing {todo}")
-        if world > 1:                                       # every rank loops over the same modulations
-            import torch.distributed as dist
-            box = [todo]
-            dist.broadcast_object_list(box, src=0)
-            todo = box[0]
-        mods = todo
+    engine = _extraction_engine(cfg, world, compute, device, devices, feature_ids)
+    mods = _modulations_to_do(cfg, mat_path, rank, world, resume, feature_ids, verbose)
     t_start = time.perf_counter()
-
-    def run(rows: FrameRows) -> np.ndarray:
-        if rows.shape[0] == 0:
-            return np.empty((0, 18), dtype=np.float32)
-        mat = engine(rows) if compute is None else compute(rows.to_array())
-        return np.asarray(mat, dtype=np.float32)
-
-    def save(mod: str, key: str, feats: np.ndarray, t0: float) -> None:
-        out_path = cfg.paths.calculated_features / f"{mod}_features.mat"
-        # written aside and renamed: an interrupted run never leaves a partial file under the final name (what
-        # resume= and every downstream loader look at)
-        tmp_path = out_path.with_name(f"{out_path.stem}.{os.getpid()}.tmp.mat")
-        record = _provenance_path(out_path)
-        try:
-            record.unlink(missing_ok=True)                  # never a fresh record beside an old file, or an old one beside a new
-            scipy.io.savemat(str(tmp_path), {"Modulation": mod, key: feats})
-            os.replace(tmp_path, out_path)
-            record.write_text(__import__("json").dumps(provenance[mod]) + "\n")
-        finally:
-            tmp_path.unlink(missing_ok=True)
-        if verbose:
-            print(f"[{mod}] {feats.shape[0] * feats.shape[1]} frames in "
-                  f"{time.perf_counter() - t0:.2f}s -> {out_path}")
-
     # uncompressed variables go from the file to the pinned slots inside the native engine (AMCX_DIRECT_FILE=0: read /
     # map them in Python first, the round-3 path kept for A/B runs); an injected engine gets arrays
-    direct = compute is None and os.environ.get("AMCX_DIRECT_FILE", "1") != "0"
-    # what each file is computed from, taken BEFORE the container is read: a container replaced mid-run leaves a record
-    # that no longer matches it
-    provenance = {m: _provenance(cfg, mat_path, cfg.signals.mat_info[m], feature_ids) for m in mods}
-    writer = ThreadPoolExecutor(max_workers=1, thread_name_prefix="amcx-writer") if rank == 0 else None
-    writes = []
-    published: List[Path] = []          # rank 0: shared files not yet removed
-    feed = None
+    direct = native and os.environ.get("AMCX_DIRECT_FILE", "1") != "0"
+    writer = _FeatureWriter(cfg, mat_path, mods, feature_ids, rank, verbose)
+    published: List[Path] = []
     try:
         if world == 1 and not (collectives_forced() and _process_group_up()):
-            from .matfile import BufferPool, compressed_variable_bytes
-            # A compressed container is inflate-bound: three reader threads run ahead (zlib releases the GIL).  An
-            # uncompressed variable is only LOCATED here: the native engine's staging threads read it from the file
-            # on their way to the pinned slots.  With an injected engine (tests) it is read with preadv into two
-            # pairs of buffers that take turns: reading is faster than first-touching fresh pages, mapped or allocated.
-            pool = BufferPool()
-            depth = _read_ahead(compressed_variable_bytes(mat_path), len(mods))
-            feed = _prefetched(mods, lambda m: _load_variable(mat_path, cfg.signals.mat_info[m], pool, direct),
-                               depth)
-            for mod, fut in feed:
-                t0 = time.perf_counter()
-                key = cfg.signals.mat_info[mod]
-                parsed = fut.result()                   # the reader threads are up to three variables ahead
-                try:
-                    n_snr, n_frames, _ = _check_container(parsed, cfg)
-                    feats = run(FrameRows(parsed, n_snr, n_frames)).reshape(n_snr, n_frames, 18)
-                finally:
-                    getattr(parsed, "release", lambda: None)()
-                del parsed
-                writes.append(writer.submit(save, mod, key, feats, t0))
+            _single_process_loop(cfg, mat_path, mods, direct, engine, writer)
         else:
-            import torch.distributed as dist
             shared_host = _placement(world, getattr(engine, "device", None))
-            mapped = {}                                 # rank 0: variables its reader thread has already mapped
-
-            def decode_and_publish(mod):                # rank 0's reader thread
-                parsed = _load_variable(mat_path, cfg.signals.mat_info[mod], None, direct)
-                n_snr, n_frames, _ = _check_container(parsed, cfg)
-                if getattr(parsed, "source", None) in ("mapped", "file"):
-                    mapped[mod] = parsed                # every rank reads / maps the variable itself: nothing to publish
-                    return "", n_snr, n_frames
-                path = _publish_container(parsed, n_snr, n_frames, N, threads)
-                published.append(path)
-                return str(path), n_snr, n_frames
-
-            def decode_locally(mod):                    # ranks on different hosts: as the reference's children do
-                parsed = _load_variable(mat_path, cfg.signals.mat_info[mod], None, direct)
-                n_snr, n_frames, _ = _check_container(parsed, cfg)
-                return parsed, n_snr, n_frames
-
-            if not shared_host:
-                feed = _prefetched(mods, decode_locally)
-            elif rank == 0:
-                feed = _prefetched(mods, decode_and_publish)
-            else:
-                feed = ((m, None) for m in mods)
-            for mod, fut in feed:
-                t0 = time.perf_counter()
-                key = cfg.signals.mat_info[mod]
-                # 1. the modulation: every rank learns where it is, or that rank 0 could not read it
-                meta, parsed = [None], None
-                if shared_host:
-                    if rank == 0:
-                        try:
-                            meta = [("ok",) + fut.result()]
-                        except Exception as exc:        # every rank must leave the collective
-                            meta = [("error", repr(exc), 0, 0)]
-                    dist.broadcast_object_list(meta, src=0)
-                    status, shared, n_snr, n_frames = meta[0]
-                    if status != "ok":
-                        raise RuntimeError(f"rank 0 could not read {key!r} from {mat_path}: {shared}")
-                # 2. this rank's frame range; a failure is kept until every rank has reported
-                local, failure, by_frames = None, None, False
-                try:
-                    if not shared_host:
-                        parsed, n_snr, n_frames = fut.result()
-                    elif shared:
-                        parsed = np.load(shared, mmap_mode="r")
-                    else:                               # mapped straight from the container, by every rank
-                        parsed = mapped.pop(mod, None) if rank == 0 else None
-                        if parsed is None:
-                            parsed = _load_variable(mat_path, key, None, direct)
-                        _check_container(parsed, cfg)
-                    F = n_snr * n_frames
-                    by_frames = shard_by_frames(n_snr, n_frames, world)     # the same answer on every rank
-                    if by_frames:
-                        k_lo, k_hi = shard_range(n_frames, rank, world)
-                        local = run(FrameColumns(parsed, n_snr, n_frames, k_lo, k_hi))
-                        expect = n_snr * (k_hi - k_lo)
-                    else:
-                        lo, hi = shard_range(F, rank, world)
-                        local = run(FrameRows(parsed, n_snr, n_frames, lo, hi))
-                        expect = hi - lo
-                    # a wrong row count would raise inside the gather on THIS rank only and leave the others in the
-                    # collective: it is reported with the status word instead
-                    if local.shape != (expect, 18):
-                        raise RuntimeError(f"engine returned {local.shape} for {expect} frames")
-                except Exception as exc:
-                    failure = f"{type(exc).__name__}: {exc}"
-                del parsed
-                # 3. one status word per rank BEFORE the data collective: all ranks raise together
-                # (the all-gather is also the point after which nobody maps the shared file any more)
-                statuses = [None] * world
-                dist.all_gather_object(statuses, failure)
-                if shared_host and rank == 0 and shared:
-                    Path(shared).unlink(missing_ok=True)
-                    published.remove(Path(shared))
-                bad = [(r, s) for r, s in enumerate(statuses) if s is not None]
-                if bad:
-                    raise RuntimeError(f"feature extraction of {mod!r} failed on " +
-                                       "; ".join(f"rank {r}: {s}" for r, s in bad))
-                mat = gather_frame_columns(local, n_snr, n_frames, rank, world) if by_frames else \
-                    gather_rows(local, F, rank, world)
-                if rank == 0:
-                    writes.append(writer.submit(save, mod, key, mat.reshape(n_snr, n_frames, 18), t0))
-        for w in writes:
-            w.result()                                  # a failed savemat raises here
+            _rank_loop(_RankRun(cfg, mat_path, direct, rank, world, engine, shared_host, {}, published), mods, writer)
+        writer.close()                                      # a failed savemat raises here
     finally:
-        if feed is not None and hasattr(feed, "close"):
-            feed.close()                                # waits for a decode / publish still in flight
-        if writer is not None:
-            writer.shutdown(wait=True)
+        writer.close(reraise=False)
         for path in list(published):
             Path(path).unlink(missing_ok=True)
     if verbose and rank == 0:

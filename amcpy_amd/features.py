@@ -37,6 +37,41 @@ def _mask(feature_ids):
     return None if feature_ids is None else _lib.feature_mask(feature_ids)
 
 
+def _frame_size(frame_size, L: int) -> int:
+    N = L if frame_size is None else int(frame_size)
+    if N > L:
+        raise ValueError(f"frame_size {N} exceeds row length {L}")
+    return N
+
+
+def _flat_frames(iq, L: int, N: int, tail: tuple = ()):
+    """Flatten the frame tensor (..., L) + tail without a copy -> (lead, n_frames, row_stride in samples).
+    ``tail``: the trailing dimensions of one sample -- () for complex64, (2,) for int16 (I, Q) pairs."""
+    per = 2 if tail else 1                                  # tensor elements per sample
+    lead = iq.shape[:iq.dim() - 1 - len(tail)]
+    n_frames = int(np.prod(lead)) if lead else 1
+    flat = iq.reshape((n_frames, L) + tail) if iq.dim() != 2 + len(tail) else iq
+    if flat.data_ptr() != iq.data_ptr() or (n_frames > 1 and (flat.stride(0) % per if tail else flat.stride(1) != 1)):
+        raise ValueError("frames must be uniformly strided (no copy is made)")
+    return lead, n_frames, (flat.stride(0) // per if n_frames > 1 else max(L, N))
+
+
+def _out_frames(iq, out, lead, n_frames: int):
+    """Make or validate ``out`` for frames of ``iq`` with leading shape ``lead`` -> (out, oflat, out_stride)."""
+    import torch
+    if out is None:
+        out = torch.empty(lead + (_lib.NUM_FEATURES,), dtype=torch.float32, device=iq.device)
+    else:
+        if out.dtype != torch.float32 or out.device != iq.device:
+            raise TypeError("out must be float32 on the same device")
+        if tuple(out.shape[:-1]) != tuple(lead) or out.shape[-1] < _lib.NUM_FEATURES:
+            raise ValueError("out must have shape (..., >=18) matching iq")
+    oflat = out.reshape(n_frames, out.shape[-1]) if out.dim() != 2 else out
+    if oflat.data_ptr() != out.data_ptr() or oflat.stride(-1) != 1:
+        raise ValueError("out must be uniformly strided with unit stride in the last dimension")
+    return out, oflat, (oflat.stride(0) if n_frames > 1 else out.shape[-1])
+
+
 def features18(iq, out=None, *, frame_size: int | None = None, variant="auto", feature_ids=None):
     """All 18 features of every frame of a complex64 CUDA(HIP) tensor.
 
@@ -64,28 +99,11 @@ def features18(iq, out=None, *, frame_size: int | None = None, variant="auto", f
     if iq.dim() < 1:
         raise ValueError("iq needs at least one dimension")
     L = iq.shape[-1]
-    N = L if frame_size is None else int(frame_size)
-    if N > L:
-        raise ValueError(f"frame_size {N} exceeds row length {L}")
-    lead = iq.shape[:-1]
-    n_frames = int(np.prod(lead)) if lead else 1
+    N = _frame_size(frame_size, L)
     if iq.stride(-1) != 1 and L > 1:
         raise ValueError("last dimension must have unit stride")
-    flat = iq.reshape(n_frames, L) if iq.dim() != 2 else iq
-    if flat.data_ptr() != iq.data_ptr() or (n_frames > 1 and flat.stride(1) != 1):
-        raise ValueError("frames must be uniformly strided (no copy is made)")
-    row_stride = flat.stride(0) if n_frames > 1 else max(L, N)
-    if out is None:
-        out = torch.empty(lead + (_lib.NUM_FEATURES,), dtype=torch.float32, device=iq.device)
-    else:
-        if out.dtype != torch.float32 or out.device != iq.device:
-            raise TypeError("out must be float32 on the same device")
-        if tuple(out.shape[:-1]) != tuple(lead) or out.shape[-1] < _lib.NUM_FEATURES:
-            raise ValueError("out must have shape (..., >=18) matching iq")
-    oflat = out.reshape(n_frames, out.shape[-1]) if out.dim() != 2 else out
-    if oflat.data_ptr() != out.data_ptr() or oflat.stride(-1) != 1:
-        raise ValueError("out must be uniformly strided with unit stride in the last dimension")
-    out_stride = oflat.stride(0) if n_frames > 1 else out.shape[-1]
+    lead, n_frames, row_stride = _flat_frames(iq, L, N)
+    out, oflat, out_stride = _out_frames(iq, out, lead, n_frames)
     lib = _lib.load()
     v = _variant(variant)
     with torch.cuda.device(iq.device):
@@ -172,26 +190,9 @@ def features18_sc16(iq, out=None, *, scale=_lib.SC16_SCALE, frame_size: int | No
         raise ValueError("(I, Q) pairs must be interleaved in memory")
     if not iq.is_cuda:
         raise ValueError("iq must live in GPU memory (use features18_sc16_host for numpy input)")
-    N = L if frame_size is None else int(frame_size)
-    if N > L:
-        raise ValueError(f"frame_size {N} exceeds row length {L}")
-    lead = iq.shape[:-2]
-    n_frames = int(np.prod(lead)) if lead else 1
-    flat = iq.reshape(n_frames, L, 2) if iq.dim() != 3 else iq
-    if flat.data_ptr() != iq.data_ptr() or (n_frames > 1 and flat.stride(0) % 2):
-        raise ValueError("frames must be uniformly strided (no copy is made)")
-    row_stride = flat.stride(0) // 2 if n_frames > 1 else max(L, N)
-    if out is None:
-        out = torch.empty(lead + (_lib.NUM_FEATURES,), dtype=torch.float32, device=iq.device)
-    else:
-        if out.dtype != torch.float32 or out.device != iq.device:
-            raise TypeError("out must be float32 on the same device")
-        if tuple(out.shape[:-1]) != tuple(lead) or out.shape[-1] < _lib.NUM_FEATURES:
-            raise ValueError("out must have shape (..., >=18) matching iq")
-    oflat = out.reshape(n_frames, out.shape[-1]) if out.dim() != 2 else out
-    if oflat.data_ptr() != out.data_ptr() or oflat.stride(-1) != 1:
-        raise ValueError("out must be uniformly strided with unit stride in the last dimension")
-    out_stride = oflat.stride(0) if n_frames > 1 else out.shape[-1]
+    N = _frame_size(frame_size, L)
+    lead, n_frames, row_stride = _flat_frames(iq, L, N, (2,))
+    out, oflat, out_stride = _out_frames(iq, out, lead, n_frames)
     _lib.require_torch_runtime()
     lib = _lib.load()
     v = _variant(variant)
@@ -222,6 +223,14 @@ def _host_context(device: int) -> "_lib.HostContext":
     return ctx
 
 
+def _run_on_host_context(ctx, x2: np.ndarray, N: int, lead, variant, mask) -> np.ndarray:
+    """The flattened frames ``x2`` through the context ``ctx`` -> (lead..., 18) float32."""
+    out = np.empty((x2.shape[0], _lib.NUM_FEATURES), dtype=np.float32)
+    ctx.set_feature_mask(_lib.FEATURES_ALL if mask is None else mask)
+    ctx.run(x2, N, out, _variant(variant))
+    return out.reshape(tuple(lead) + (_lib.NUM_FEATURES,))
+
+
 def features18_host(frames: np.ndarray, *, frame_size: int | None = None, device: int = 0,
                     variant="auto", feature_ids=None) -> np.ndarray:
     """numpy (..., L) complex -> numpy (..., 18) float32 via the GPU.
@@ -234,20 +243,14 @@ def features18_host(frames: np.ndarray, *, frame_size: int | None = None, device
     if not np.iscomplexobj(x):
         x = x.astype(np.complex64)
     L = x.shape[-1]
-    N = L if frame_size is None else int(frame_size)
-    if N > L:
-        raise ValueError(f"frame_size {N} exceeds row length {L}")
+    N = _frame_size(frame_size, L)
     lead = x.shape[:-1]
     if x.dtype == np.complex128:
         # MATLAB doubles: uploaded as they are, rounded to complex64 on the GPU
         x2 = np.ascontiguousarray(x.reshape(-1, L))
     else:
         x2 = np.ascontiguousarray(x.reshape(-1, L), dtype=np.complex64)
-    out = np.empty((x2.shape[0], _lib.NUM_FEATURES), dtype=np.float32)
-    ctx = _host_context(int(device))
-    ctx.set_feature_mask(_lib.FEATURES_ALL if mask is None else mask)
-    ctx.run(x2, N, out, _variant(variant))
-    return out.reshape(lead + (_lib.NUM_FEATURES,))
+    return _run_on_host_context(_host_context(int(device)), x2, N, lead, variant, mask)
 
 
 def features18_sc16_host(frames: np.ndarray, *, scale=_lib.SC16_SCALE, frame_size: int | None = None, device: int = 0,
@@ -260,17 +263,12 @@ def features18_sc16_host(frames: np.ndarray, *, scale=_lib.SC16_SCALE, frame_siz
     if not isinstance(x, np.ndarray) or x.dtype != np.int16 or x.ndim < 2 or x.shape[-1] != 2:
         raise TypeError("expected an int16 array whose last dimension is (I, Q)")
     L = x.shape[-2]
-    N = L if frame_size is None else int(frame_size)
-    if N > L:
-        raise ValueError(f"frame_size {N} exceeds row length {L}")
+    N = _frame_size(frame_size, L)
     lead = x.shape[:-2]
     x2 = np.ascontiguousarray(x.reshape(-1, L, 2))
-    out = np.empty((x2.shape[0], _lib.NUM_FEATURES), dtype=np.float32)
     ctx = _host_context(int(device))
-    ctx.set_feature_mask(_lib.FEATURES_ALL if mask is None else mask)
     ctx.set_sc16_scale(scale)
-    ctx.run(x2, N, out, _variant(variant))
-    return out.reshape(lead + (_lib.NUM_FEATURES,))
+    return _run_on_host_context(ctx, x2, N, lead, variant, mask)
 
 
 def calculate_features(feature_ids: Iterable[int], signal, *, device: int = 0,

@@ -76,35 +76,64 @@ def gather_blocks(local: np.ndarray, counts, rank: int, world: int, group=None):
     return [blk[:counts[r]].cpu().numpy() for r, blk in enumerate(parts)]
 
 
+class FrameCut:
+    """THE cut of a whole (n_snr, n_frames) container over ``world`` workers -- ranks, or the devices of one process --
+    along its frame axis when :func:`shard_by_frames` says so, else along the snr-major flattening; and the way back.
+    ``FrameCut.flat(F, world)``: any other range of F rows (a slice, an (F, L) array) goes by the flattening."""
+
+    def __init__(self, n_snr: int, n_frames: int, world: int, by_frames: Optional[bool] = None):
+        self.n_snr, self.n_frames, self.world = int(n_snr), int(n_frames), int(world)
+        self.frames = self.n_snr * self.n_frames
+        self.by_frames = shard_by_frames(n_snr, n_frames, world) if by_frames is None else bool(by_frames)
+
+    @classmethod
+    def flat(cls, frames: int, world: int) -> "FrameCut":
+        return cls(1, frames, world, by_frames=False)
+
+    def range(self, rank: int) -> Tuple[int, int]:
+        """``(k_lo, k_hi)`` along the frame axis (``by_frames``), else ``(lo, hi)`` along the flattening."""
+        return shard_range(self.n_frames if self.by_frames else self.frames, rank, self.world)
+
+    def rows(self, rank: int) -> int:
+        """How many result rows ``rank`` returns."""
+        lo, hi = self.range(rank)
+        return (self.n_snr if self.by_frames else 1) * (hi - lo)
+
+    def place(self, out: np.ndarray, rank: int, block: np.ndarray) -> None:
+        """Write ``rank``'s (rows(rank), C) block into the snr-major (frames, C) result ``out`` (C-contiguous)."""
+        lo, hi = self.range(rank)
+        if self.by_frames:
+            out.reshape(self.n_snr, self.n_frames, out.shape[1])[:, lo:hi] = block.reshape(self.n_snr, hi - lo, out.shape[1])
+        else:
+            out[lo:hi] = block
+
+    def gather(self, local: np.ndarray, rank: int, group=None) -> Optional[np.ndarray]:
+        """:func:`gather_blocks` of every rank's block, placed: the (frames, C) float32 result on rank 0, None elsewhere."""
+        blocks = gather_blocks(local, [self.rows(r) for r in range(self.world)], rank, self.world, group)
+        if blocks is None:
+            return None
+        out = np.empty((self.frames, local.shape[1]), dtype=np.float32)
+        for r, blk in enumerate(blocks):
+            self.place(out, r, blk)
+        return out
+
+
 def gather_rows(local: np.ndarray, n_frames: int, rank: int, world: int, group=None) -> Optional[np.ndarray]:
     """Collect every rank's (n_local, 18) block of the contiguous cut (:func:`shard_range`) on rank 0 as
-    (n_frames, 18): :func:`gather_blocks` + concatenation.  Returns the full matrix on rank 0 and None elsewhere."""
+    (n_frames, 18): ``FrameCut.flat(...).gather``.  Returns the full matrix on rank 0 and None elsewhere."""
     if world == 1 and not collectives_forced():
         return local
-    ranges = [shard_range(n_frames, r, world) for r in range(world)]
-    lo, hi = ranges[rank]
+    lo, hi = shard_range(n_frames, rank, world)
     if local.shape[0] != hi - lo:
         raise RuntimeError(f"rank {rank} holds {local.shape[0]} rows for [{lo}, {hi})")
-    blocks = gather_blocks(local, [b - a for a, b in ranges], rank, world, group)
-    if blocks is None:
-        return None
-    out = np.empty((n_frames, local.shape[1]), dtype=np.float32)
-    for (a, b), blk in zip(ranges, blocks):
-        out[a:b] = blk
-    return out
+    return FrameCut.flat(n_frames, world).gather(local, rank, group)
 
 
 def gather_frame_columns(local: np.ndarray, n_snr: int, n_frames: int, rank: int, world: int, group=None):
     """The frame-axis cut (:func:`shard_by_frames`): rank r holds the (n_snr * K_r, C) rows of frames
     ``shard_range(n_frames, r, world)`` of every snr row, snr-major; rank 0 gets (n_snr, n_frames, C), others None."""
-    ranges = [shard_range(n_frames, r, world) for r in range(world)]
-    blocks = gather_blocks(local, [n_snr * (b - a) for a, b in ranges], rank, world, group)
-    if blocks is None:
-        return None
-    out = np.empty((n_snr, n_frames, local.shape[1]), dtype=np.float32)
-    for (a, b), blk in zip(ranges, blocks):
-        out[:, a:b] = blk.reshape(n_snr, b - a, -1)
-    return out
+    out = FrameCut(n_snr, n_frames, world, by_frames=True).gather(local, rank, group)
+    return None if out is None else out.reshape(n_snr, n_frames, local.shape[1])
 
 
 def all_gather_rows(local, n_frames: int, rank: int, world: int, group=None):
