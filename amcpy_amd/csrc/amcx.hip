@@ -1,5 +1,7 @@
 // libamcx.so -- C ABI (include/amcx.h) over the gfx950 feature kernels.
 // Build: hipcc --offload-arch=gfx950 -O3 -fPIC -shared (see build.py).
+// This file: the feature dispatch (run_features and the launchers amcx_launch.h does not hold), the post-processing and
+// classifier entries, and extern "C".  The contexts and their upload engine: amcx_ctx.h; the probes: amcx_probe.h.
 #include "../../include/amcx.h"
 
 #include <hip/hip_runtime.h>
@@ -19,67 +21,6 @@
 #include "amcx_mlp_kernel.h"
 #include "amcx_pack_kernel.h"
 #include "amcx_upload.h"
-
-// ---- host-buffer entry points over a reusable context --------------------------------------
-// The context owns two streams, pinned staging slots and device scratch that only ever grow, so a
-// loop of per-frame calls (the reference's usage pattern, features.py:214-232 called once per queue
-// item) pays two small copies and the launches, not hipMalloc/hipFree/stream creation per call, and
-// a whole container goes up through the staged, overlapped path (ctx_run_strided).
-struct amcx_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  float* d_out = nullptr; size_t out_cap = 0;
-  // strided containers (amcx_ctx_features18_strided_host): staging pool, three pinned slots, a second stream
-  amcx::Pool pool;
-  int threads = 0;                               // 0: not yet sized
-  size_t slot_bytes = size_t(32) << 20;
-  bool round_on_device = false;
-  hipStream_t copy_stream = nullptr;
-  char* pin = nullptr;     size_t pin_cap = 0;   // kPinSlots x slot
-  void* d_slab = nullptr;  size_t slab_cap = 0;  // 2 x slot: uploaded chunks
-  void* d_frames = nullptr; size_t frames_cap = 0;   // plane-major sources: the frame-major complex64 image
-  void* d_ws = nullptr; size_t ws_cap = 0;           // the any-size path's FFT workspace (frame sizes above 8192, amcx_features18_c64_ws)
-  void* d_ring = nullptr; size_t ring_cap = 0;       // the wave kernels' ring of stash rows (RingSource): this context's launches only
-  hipEvent_t up_done[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t slab_free[2] = {nullptr, nullptr};
-  float* out_pin = nullptr; size_t out_pin_cap = 0;   // the result lands in pinned memory first
-  amcx_upload_stats stats = {};
-  // host placement (amcx_upload.h, NumaPlace): the CPUs local to this device; staging threads, the calling thread for the
-  // duration of a threaded upload, and with it the pinned slots it allocates, stay on them.  Empty: nothing is bound.
-  char pci_bus_id[32] = {0};
-  int numa_node = -1;
-  std::vector<int> bind_cpus;
-  // small row-major calls (a loop of per-frame calculate_features calls): the copy in, the launches and the copy
-  // out as ONE instantiated graph per (frames, frame size, variant, element type, buffers), relaunched
-  struct GraphKey {
-    int64_t frames = 0; int32_t frame_size = 0, variant = 0; bool c128 = false, zero_copy = false;
-    bool sc16 = false; float sc16_scale = 0.f;   // the element kind, and the scale the captured kernel node carries as an argument
-    const void* pin = nullptr; const void* slab = nullptr; const void* out = nullptr; const void* out_pin = nullptr;
-    const void* ws = nullptr;      // the workspace the captured kernel node points into
-    size_t slot = 0;
-    uint32_t mask = AMCX_FEATURES_ALL;   // the feature mask the captured kernels were launched for
-    bool operator==(const GraphKey& o) const {
-      return frames == o.frames && frame_size == o.frame_size && variant == o.variant && c128 == o.c128 &&
-             zero_copy == o.zero_copy && pin == o.pin && slab == o.slab && out == o.out && out_pin == o.out_pin &&
-             ws == o.ws && slot == o.slot && mask == o.mask && sc16 == o.sc16 && sc16_scale == o.sc16_scale;
-    }
-  };
-  struct SmallGraph {
-    hipGraphExec_t exec = nullptr;
-    GraphKey key;
-  };
-  SmallGraph graphs[4];
-  int graph_next = 0;               // slot the next capture replaces
-  int graph_hits = 0, graph_misses = 0;
-  bool graphs_ok = true;            // false: capture failed once, or the calls vary too much for a cache of four
-  // calls in flight on this context (a context serves one call at a time; the counter is there so that
-  // amcx_ctx_bind_cpus can refuse to rebuild the staging pool's binding under a running upload)
-  std::atomic<int> in_call{0};
-  // amcx_ctx_set_feature_mask: the features every later host-buffer call computes (read once per call)
-  std::atomic<uint32_t> feature_mask{AMCX_FEATURES_ALL};
-  // amcx_ctx_set_sc16_scale: what an int16 component of an sc16 source is multiplied by (read once per call)
-  std::atomic<float> sc16_scale{0x1p-15f};
-};
 
 namespace {
 
@@ -278,61 +219,6 @@ int launch_block(const amcx::Frames& a, int32_t N, void* ws = nullptr, int64_t w
   }
 }
 
-// The instruction-issue ceiling under the board's power cap: 16 wavefronts per CU (4 per SIMD, the N = 2048 kernel's
-// occupancy), each running `iters` trips of 32 independent v_fma_f32 (8 chains x 4) on registers -- no memory traffic.
-// Lane 0 of every wave leaves its shader-clock cycles and its 100 MHz real-time ticks, from which the clock follows.
-__global__ __launch_bounds__(1024) void amcx_probe_fma_kernel(int iters, float* sink, unsigned long long* ticks) {
-  float a0 = (float)threadIdx.x, a1 = a0 + 1.f, a2 = a0 + 2.f, a3 = a0 + 3.f, a4 = a0 + 4.f, a5 = a0 + 5.f,
-        a6 = a0 + 6.f, a7 = a0 + 7.f;
-  const float b0 = 1.0001f, b1 = 0.9999f;
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
-  for (int i = 0; i < iters; ++i) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      asm volatile(
-          "v_fma_f32 %0, %0, %8, %9\n v_fma_f32 %1, %1, %8, %9\n v_fma_f32 %2, %2, %8, %9\n v_fma_f32 %3, %3, %8, %9\n"
-          "v_fma_f32 %4, %4, %8, %9\n v_fma_f32 %5, %5, %8, %9\n v_fma_f32 %6, %6, %8, %9\n v_fma_f32 %7, %7, %8, %9\n"
-          : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b0), "v"(b1));
-  }
-  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-  const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-  const float s = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
-  if (s == 12345.678f) sink[0] = s;                       // keeps the chains alive; never true in practice
-  if ((threadIdx.x & 63) == 0) {
-    const long long w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    ticks[2 * w] = t1 - t0;
-    ticks[2 * w + 1] = r1 - r0;
-  }
-}
-
-__global__ __launch_bounds__(256) void amcx_probe_read_kernel(const float4* __restrict__ src,
-                                                             long long n_vec, float* partial) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  float acc = 0.f;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  // four independent 16-byte loads in flight per lane and iteration
-  for (; i + 3 * stride < n_vec; i += 4 * stride) {
-    const v4f a = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src + i));
-    const v4f b = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src + i + stride));
-    const v4f c = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src + i + 2 * stride));
-    const v4f d = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src + i + 3 * stride));
-    acc += ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((c.x + c.y) + (c.z + c.w)) +
-           ((d.x + d.y) + (d.z + d.w));
-  }
-  for (; i < n_vec; i += stride) {
-    const float4 v = src[i];
-    acc += (v.x + v.y) + (v.z + v.w);
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  __shared__ float s[4];
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-}
-
 // ---- the feature entry: one validation, one dispatch ------------------------------------------------------------------
 bool valid_feature_mask(uint32_t mask) { return mask != 0 && (mask & ~(uint32_t)AMCX_FEATURES_ALL) == 0; }
 
@@ -341,6 +227,22 @@ bool valid_feature_mask(uint32_t mask) { return mask != 0 && (mask & ~(uint32_t)
 int subset_plan(int32_t N, int v, uint32_t mask) {
   if ((mask & 1u) != 0 || v != AMCX_VARIANT_WAVE || !amcx::has_plan_kernels(N)) return amcx::kPlanAll;
   return (mask & ~amcx::kMaskCumulants) == 0 ? amcx::kPlanCumulants : amcx::kPlanNoSpectral;
+}
+
+// f(the run-time plan as an integral_constant)  (kPlanAll stands first: KERNEL ORDER, amcx_launch.h)
+template <class F>
+auto with_plan(int plan, F&& f) {
+  using std::integral_constant;
+  return plan == amcx::kPlanAll         ? f(integral_constant<int, amcx::kPlanAll>{})
+         : plan == amcx::kPlanCumulants ? f(integral_constant<int, amcx::kPlanCumulants>{})
+                                        : f(integral_constant<int, amcx::kPlanNoSpectral>{});
+}
+
+// sc16 frames of this size are read by a kernel of their own (resolved variant v); false: widened to complex64 first
+bool sc16_typed(int32_t N, int v) {
+  // (called out of line, as the parent's callers did: the library exports its inline host helpers -- build.py sets no
+  //  visibility -- and amcx::has_sc16_kernels stays in that list)
+  [[clang::noinline]] return v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(N);
 }
 
 // The any-size path above 8192 samples runs its FFT form through a workspace from the stream-ordered allocator
@@ -408,7 +310,7 @@ int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64
   if (iq_dev == nullptr || out_dev == nullptr) return AMCX_EINVAL;
   if ((reinterpret_cast<uintptr_t>(iq_dev) & (sc16 != nullptr ? 3u : 7u)) || (reinterpret_cast<uintptr_t>(out_dev) & 3u))
     return AMCX_EINVAL;
-  const bool typed = sc16 != nullptr && v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(frame_size);
+  const bool typed = sc16 != nullptr && sc16_typed(frame_size, v);
   Workspace ws = ws_in;
   if (sc16 != nullptr && !typed) {      // the widened copy takes the head of the caller's workspace
     const int64_t head = sc16_widened_bytes(frame_size, n_frames);
@@ -444,17 +346,13 @@ int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64
     // itself -- one launch, rows final -- and finished frames with a phase step within an angle rounding of +-pi in its
     // finaliser.
     float* const ring = ring_for(rings, frame_size, stream);
-    auto launch_plan = [&](auto plan_c) {       // (subset_plan names a plan only where the size has its kernels)
+    const hipError_t e = with_plan(plan, [&](auto plan_c) {       // (subset_plan names a plan only where the size has its kernels)
       return amcx::for_frame_size(frame_size, [&](auto size) {
         using S = decltype(size);
         constexpr int kPlan = S::kPlanStem != nullptr ? decltype(plan_c)::value : amcx::kPlanAll;
         return S::template launch<kPlan>(frames, ring, feature_mask);
       });
-    };
-    using std::integral_constant;               // (kPlanAll stands first: KERNEL ORDER, amcx_launch.h)
-    const hipError_t e = plan == amcx::kPlanAll         ? launch_plan(integral_constant<int, amcx::kPlanAll>{})
-                         : plan == amcx::kPlanCumulants ? launch_plan(integral_constant<int, amcx::kPlanCumulants>{})
-                                                        : launch_plan(integral_constant<int, amcx::kPlanNoSpectral>{});
+    });
     if (e != hipSuccess) return hip_fail(e, plan == amcx::kPlanAll ? "wave kernel launch" : "feature-subset kernel launch");
     rc = AMCX_OK;
   } else if (ws.own) {
@@ -473,17 +371,13 @@ int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64
 
 // the sc16 kernel of (frame size, plan): amcx_launch.h, THE FRAME-SIZE TABLE
 hipError_t launch_sc16_plan(const amcx::Frames& frames, int32_t N, int plan, float* ring, uint32_t mask) {
-  auto launch_plan = [&](auto plan_c) {
+  return with_plan(plan, [&](auto plan_c) {
     return amcx::for_frame_size(N, [&](auto size) {
       using S = decltype(size);
       if constexpr (S::kSc16Stem != nullptr) return S::template launch<decltype(plan_c)::value, amcx::wave::sc16>(frames, ring, mask);
       else return hipErrorNotSupported;
     });
-  };
-  using std::integral_constant;
-  return plan == amcx::kPlanAll         ? launch_plan(integral_constant<int, amcx::kPlanAll>{})
-         : plan == amcx::kPlanCumulants ? launch_plan(integral_constant<int, amcx::kPlanCumulants>{})
-                                        : launch_plan(integral_constant<int, amcx::kPlanNoSpectral>{});
+  });
 }
 
 // sc16 rows -> packed complex64 rows of N samples at dst (amcx_sc16_kernels.h)
@@ -493,469 +387,12 @@ hipError_t launch_sc16_widen(const amcx::Frames& frames, int32_t N, float2* dst)
                       frames.row_stride, frames.scale, dst);
 }
 
-// ---- host-buffer entry points over a reusable context: the helpers ---------------------------------------------------------
-int ctx_reserve(void** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return AMCX_OK;
-  if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-  // grow geometrically so a slowly growing batch size does not reallocate every call
-  size_t want = bytes < (size_t(1) << 20) ? bytes : bytes + bytes / 4;
-  if (hipMalloc(p, want) != hipSuccess) {
-    (void)hipGetLastError();
-    if (want == bytes || hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return AMCX_ENOMEM; }
-    want = bytes;
-  }
-  *cap = want;
-  return AMCX_OK;
-}
+}  // namespace
 
-// The context's own workspace for a call of `frames` frames (nothing for the frame sizes that need none).  Reserved
-// BEFORE any capture begins: a captured kernel node points into it, and an allocation inside a capture is not allowed.
-// A context that cannot have it runs the workspace-free form.
-void ctx_reserve_ws(amcx_ctx* c, int32_t N, int64_t frames, int32_t variant) {
-  const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
-  if (want > 0 && ctx_reserve(&c->d_ws, &c->ws_cap, (size_t)want) != AMCX_OK) { c->d_ws = nullptr; c->ws_cap = 0; }
-  // likewise the ring of the wave kernels that take one; without it they run their LDS form
-  // (one size per device, whatever the call's frame count: never reallocated, so the ring a captured graph points into stays)
-  const size_t ring = resolve_variant(N, variant) == AMCX_VARIANT_WAVE ? amcx::wave_ring_bytes(N, cu_count()) : 0;
-  if (ring > 0 && ctx_reserve(&c->d_ring, &c->ring_cap, ring) != AMCX_OK) { c->d_ring = nullptr; c->ring_cap = 0; }
-}
+#include "amcx_ctx.h"      // the contexts and their upload engine, built on run_features (KERNEL ORDER: it names the packing kernels)
+#include "amcx_probe.h"    // the two probes: plain kernels, the last of .text as they always were
 
-// sc16: `rows` are sc16 and the size has a kernel that reads them (sc16_typed); otherwise complex64
-int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant, uint32_t mask,
-                 const Sc16In* sc16 = nullptr) {
-  const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
-  Workspace ws;
-  if (want > 0 && c->d_ws != nullptr && c->ws_cap >= (size_t)want) { ws.dev = c->d_ws; ws.bytes = want; }
-  RingSource rings;
-  rings.own = static_cast<float*>(c->d_ring);
-  rings.own_bytes = c->ring_cap;
-  return run_features(rows, frames, N, N, out, AMCX_NUM_FEATURES, c->stream, variant, mask, ws, rings, sc16);
-}
-
-struct DeviceGuard {
-  int prev = -1;
-  hipError_t enter(int dev) {
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) { prev = -1; return e; }
-    return hipSetDevice(dev);
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-// ---- strided host containers ----------------------------------------------------------------------
-constexpr int kPinSlots = 3;
-
-using amcx::classify_layout;      // amcx_upload.h: which axis is contiguous decides how a container goes up
-
-double wall_now() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-int strided_prepare(amcx_ctx* c, size_t slot, size_t dslot, size_t frames_bytes, size_t out_bytes, bool threaded) {
-  if (c->threads == 0) {
-    unsigned hw = std::thread::hardware_concurrency();
-    if (!c->bind_cpus.empty()) hw = (unsigned)amcx::allowed_subset(c->bind_cpus).size();   // this device's share of the host
-    c->threads = (int)(hw == 0 ? 4 : hw > 8 ? 8 : hw);
-  }
-  if (threaded) c->pool.resize(c->threads);      // the staging threads start with the first call that has work for them
-  if (c->copy_stream == nullptr) AMCX_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  for (auto& ev : c->up_done) if (ev == nullptr) AMCX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  for (auto& ev : c->slab_free) if (ev == nullptr) AMCX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  if (c->pin_cap < kPinSlots * slot) {
-    if (c->pin) { (void)hipHostFree(c->pin); c->pin = nullptr; c->pin_cap = 0; }
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->pin), kPinSlots * slot, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      c->pin = nullptr;
-      return AMCX_ENOMEM;
-    }
-    c->pin_cap = kPinSlots * slot;
-  }
-  if (c->out_pin_cap < out_bytes) {
-    if (c->out_pin) { (void)hipHostFree(c->out_pin); c->out_pin = nullptr; c->out_pin_cap = 0; }
-    const size_t want = out_bytes + out_bytes / 4 + 4096;
-    if (hipHostMalloc(reinterpret_cast<void**>(&c->out_pin), want, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      c->out_pin = nullptr;
-      return AMCX_ENOMEM;
-    }
-    c->out_pin_cap = want;
-  }
-  int rc = ctx_reserve(&c->d_slab, &c->slab_cap, 2 * dslot);
-  if (rc == AMCX_OK && frames_bytes) rc = ctx_reserve(&c->d_frames, &c->frames_cap, frames_bytes);
-  if (rc == AMCX_OK) rc = ctx_reserve(reinterpret_cast<void**>(&c->d_out), &c->out_cap, out_bytes);
-  return rc;
-}
-
-// a staging thread could not read the container's file
-int io_fail(int err) {
-  snprintf(g_hip_err, sizeof g_hip_err, "reading the container's file: %s", strerror(err));
-  return AMCX_EIO;
-}
-
-// One call of ctx_run_strided: what its prologue worked out, for run_small_graph and run_chunked.
-struct StridedCall {
-  amcx::Source src;
-  amcx::RunMap map;
-  std::atomic<int> io_error{0};
-  int64_t S = 0, K = 0, F = 0;
-  int32_t N = 0;
-  int v = 0;                       // the resolved variant
-  uint32_t mask = AMCX_FEATURES_ALL;
-  bool rows = false, inner_snr = false, as_c128 = false, threaded = false;
-  bool sc16 = false, sc16_typed = false;   // an sc16 source; a kernel of this size reads it (otherwise it is widened on the device)
-  Sc16In sc16_in = {1.0f};
-  size_t esz = 8;                  // staged bytes per element
-  int64_t unit = 0, n_units = 0;   // staged elements per chunk unit (a frame / a plane), and how many
-  size_t total_staged = 0, slot = 0, dslot = 0;
-  float* out_host = nullptr;
-  int64_t out_row_stride = 0;
-  amcx_upload_stats st = {};
-  double t_start = 0, t_loop = 0;
-};
-
-// rows of complex128 in a device slot, rounded to complex64 into the room behind the slot
-hipError_t round_rows_on_device(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, const void** d_rows) {
-  float2* rounded = reinterpret_cast<float2*>(dev + q.slot);
-  *d_rows = rounded;
-  return amcx::launch(amcx::amcx_c128_to_c64_kernel, 2048, 256, 0, c->stream, reinterpret_cast<const double2*>(dev), frames,
-                      q.N, q.N, rounded);
-}
-
-// rows of sc16 in a device slot, widened to complex64 into the room behind the slot (the frame sizes and variants that have
-// no sc16 kernel)
-hipError_t widen_rows_on_device(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, const void** d_rows) {
-  float2* wide = reinterpret_cast<float2*>(dev + q.slot);
-  *d_rows = wide;
-  amcx::Frames fr{nullptr, frames, q.N, nullptr, 0, c->stream, cu_count()};
-  fr.iq16 = reinterpret_cast<const amcx::wave::sc16*>(dev);
-  fr.scale = q.sc16_in.scale;
-  return launch_sc16_widen(fr, q.N, wide);
-}
-
-// the feature kernels over the rows of one chunk at `dev`: complex64, complex128 (rounded first) or sc16 (read by the
-// kernel, or widened first)
-int chunk_features(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, float* out, hipError_t* e) {
-  const void* d_rows = dev;
-  if (q.as_c128) *e = round_rows_on_device(c, q, dev, frames, &d_rows);
-  else if (q.sc16 && !q.sc16_typed) *e = widen_rows_on_device(c, q, dev, frames, &d_rows);
-  if (*e != hipSuccess) return AMCX_OK;
-  return ctx_features(c, d_rows, frames, q.N, out, q.v, q.mask, q.sc16_typed ? &q.sc16_in : nullptr);
-}
-
-// the result is in pinned memory: spread it over the caller's row stride, and close the call's statistics
-void finish_strided(amcx_ctx* c, StridedCall& q, bool copy_out, double t_tail) {
-  if (copy_out) {
-    if (q.out_row_stride == AMCX_NUM_FEATURES) {
-      memcpy(q.out_host, c->out_pin, sizeof(float) * AMCX_NUM_FEATURES * (size_t)q.F);
-    } else {
-      for (int64_t g = 0; g < q.F; ++g)
-        memcpy(q.out_host + (size_t)g * (size_t)q.out_row_stride, c->out_pin + (size_t)g * AMCX_NUM_FEATURES,
-               sizeof(float) * AMCX_NUM_FEATURES);
-    }
-  }
-  q.st.seconds_tail = wall_now() - t_tail;
-  q.st.seconds = wall_now() - q.t_start;
-  c->stats = q.st;
-}
-
-// ---- small row-major calls: one graph launch ------------------------------------------------------------------
-// A per-frame loop (the reference's calculate_features per queue item, features.py:214-232) is launch-bound: copy in,
-// one or two conversions / kernels, copy out, a synchronisation -- seven runtime calls around 10 us of
-// GPU work.  Captured once per shape into a graph on the compute stream, a call is: stage into the pinned slot,
-// hipGraphLaunch, hipStreamSynchronize.  Anything that does not fit (several chunks, planes, staging threads) and any
-// failure to capture takes the general path (run_chunked): then this returns false.  True: *rc is the call's result.
-// (The workspace and the ring were reserved before this: ctx_reserve_ws.)
-bool run_small_graph(amcx_ctx* c, StridedCall& q, amcx::Pool& inline_pool, int* rc) {
-  if (!q.rows || q.threaded || q.total_staged > q.slot || !c->graphs_ok || getenv("AMCX_NO_GRAPH") != nullptr) return false;   // one chunk
-  char* pinned = c->pin;
-  char* dev = static_cast<char*>(c->d_slab);
-  const size_t bytes = (size_t)q.n_units * (size_t)q.unit * q.esz;
-  const size_t out_bytes = sizeof(float) * AMCX_NUM_FEATURES * (size_t)q.F;
-  const double t0 = wall_now();
-  amcx::stage_runs(inline_pool, pinned, q.src, q.map, 0, q.n_units, q.as_c128);
-  q.st.seconds_staging += wall_now() - t0;
-  if (q.io_error.load() != 0) { *rc = io_fail(q.io_error.load()); return true; }
-  amcx_ctx::GraphKey key;
-  key.frames = q.F; key.frame_size = q.N; key.variant = q.v; key.c128 = q.as_c128;
-  // a few frames of complex64: the kernels read the pinned slot and write the pinned result themselves (host memory
-  // from hipHostMalloc is mapped into the device's address space) -- two copy nodes fewer in the graph
-  key.zero_copy = !q.as_c128 && !(q.sc16 && !q.sc16_typed) && bytes <= (size_t(64) << 10) && getenv("AMCX_NO_ZERO_COPY") == nullptr;
-  key.pin = pinned; key.slab = dev; key.out = c->d_out; key.out_pin = c->out_pin; key.ws = c->d_ws; key.slot = q.slot;
-  key.mask = q.mask;
-  key.sc16 = q.sc16; key.sc16_scale = q.sc16 ? q.sc16_in.scale : 0.f;
-  amcx_ctx::SmallGraph* g = nullptr;
-  for (auto& cand : c->graphs)
-    if (cand.exec && cand.key == key) g = &cand;
-  if (g != nullptr) {
-    ++c->graph_hits;
-  } else {
-    ++c->graph_misses;
-    if (c->graph_misses > 64 && c->graph_misses > 4 * c->graph_hits) c->graphs_ok = false;   // shapes keep changing
-    amcx_ctx::SmallGraph& slot_g = c->graphs[c->graph_next];
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    int crc = AMCX_OK;
-    hipError_t ce = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
-    if (ce == hipSuccess && key.zero_copy) {
-      crc = ctx_features(c, pinned, q.F, q.N, c->out_pin, q.v, q.mask, q.sc16 ? &q.sc16_in : nullptr);
-      ce = hipStreamEndCapture(c->stream, &graph);
-    } else if (ce == hipSuccess) {
-      ce = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, c->stream);
-      if (ce == hipSuccess) crc = chunk_features(c, q, dev, q.F, c->d_out, &ce);
-      if (ce == hipSuccess && crc == AMCX_OK)
-        ce = hipMemcpyAsync(c->out_pin, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-      const hipError_t ee = hipStreamEndCapture(c->stream, &graph);      // always ends the capture
-      if (ce == hipSuccess) ce = ee;
-    }
-    if (ce == hipSuccess && crc == AMCX_OK && graph != nullptr) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (graph != nullptr) (void)hipGraphDestroy(graph);
-    if (ce != hipSuccess || crc != AMCX_OK || exec == nullptr) {
-      (void)hipGetLastError();
-      c->graphs_ok = false;                 // the general path takes this call and every later one
-      return false;
-    }
-    if (slot_g.exec) (void)hipGraphExecDestroy(slot_g.exec);
-    slot_g.exec = exec;
-    slot_g.key = key;
-    c->graph_next = (c->graph_next + 1) % 4;
-    g = &slot_g;
-  }
-  q.st.seconds_prepare = q.t_loop - q.t_start;
-  const double t_tail = wall_now();
-  const hipError_t e = hipGraphLaunch(g->exec, c->stream);
-  const hipError_t e2 = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess || e2 != hipSuccess) {
-    *rc = hip_fail(e != hipSuccess ? e : e2, "amcx_ctx_features18 (graph launch)");
-    return true;
-  }
-  q.st.pcie_bytes = (int64_t)bytes; q.st.chunks = 1;
-  finish_strided(c, q, true, t_tail);
-  *rc = AMCX_OK;
-  return true;
-}
-
-// ---- the general path: chunks staged by the pool, uploaded on the copy stream, computed on the compute stream ------------
-int run_chunked(amcx_ctx* c, StridedCall& q, amcx::Pool& pool) {
-  amcx_upload_stats& st = q.st;
-  const int64_t F = q.F, unit = q.unit, n_units = q.n_units;
-  const int32_t N = q.N;
-  const size_t esz = q.esz, slot = q.slot;
-  int rc = AMCX_OK;
-  hipError_t e = hipSuccess;
-  const int64_t units_per_slot = (int64_t)(slot / ((size_t)unit * esz));
-  int64_t u = 0;
-  for (int ch = 0; u < n_units && rc == AMCX_OK; ++ch) {
-    // the first chunks are small so that the link starts early and staging overlaps it from the start:
-    // 2, 2, 4, 4, 8, 8 ... MiB staged, up to whole slots (a 16 MB modulation of BASELINE configs[0] is five chunks)
-    int64_t take = units_per_slot;
-    if (ch < 12) {
-      const int64_t ramp = (int64_t)((size_t(2) << 20 << (ch / 2)) / ((size_t)unit * esz));
-      if (ramp < take) take = ramp;
-    }
-    if (take < 1) take = 1;
-    if (take > n_units - u) take = n_units - u;
-    const int ps = ch % kPinSlots, ds = ch & 1;
-    char* pinned = c->pin + (size_t)ps * slot;
-    char* dev = static_cast<char*>(c->d_slab) + (size_t)ds * q.dslot;
-    const size_t bytes = (size_t)take * (size_t)unit * esz;
-    if (ch >= kPinSlots) {                                  // the upload that last read this pinned slot is done
-      const double t0 = wall_now();
-      e = hipEventSynchronize(c->up_done[ps]);
-      st.seconds_waiting += wall_now() - t0;
-      if (e != hipSuccess) break;
-    }
-    {
-      const double t0 = wall_now();
-      // rows: run = frame g; planes: a plane is map.cnt_b runs
-      const int64_t per_unit = q.rows ? 1 : q.map.cnt_b;
-      amcx::stage_runs(pool, pinned, q.src, q.map, u * per_unit, (u + take) * per_unit, q.as_c128);
-      st.seconds_staging += wall_now() - t0;
-      if (q.io_error.load() != 0) {                        // nothing of this chunk is queued; what is in flight is drained below
-        rc = io_fail(q.io_error.load());
-        break;
-      }
-    }
-    if (ch >= 2) { e = hipStreamWaitEvent(c->copy_stream, c->slab_free[ds], 0); if (e != hipSuccess) break; }
-    e = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, c->copy_stream);
-    if (e != hipSuccess) break;
-    e = hipEventRecord(c->up_done[ps], c->copy_stream);
-    if (e != hipSuccess) break;
-    e = hipStreamWaitEvent(c->stream, c->up_done[ps], 0);
-    if (e != hipSuccess) break;
-    st.pcie_bytes += (int64_t)bytes;
-    if (q.rows) {
-      rc = chunk_features(c, q, dev, take, c->d_out + (size_t)u * AMCX_NUM_FEATURES, &e);
-      if (e != hipSuccess) break;
-    } else {
-      float2* frames = static_cast<float2*>(c->d_frames);
-      const int S = (int)q.S, inner = q.inner_snr ? 1 : 0;
-      e = q.as_c128 ? amcx::launch_pack_planes(reinterpret_cast<const double2*>(dev), (int)take, (long long)F, (long long)F,
-                                               S, (long long)q.K, inner, frames, (long long)N, (int)u, c->stream)
-                    : amcx::launch_pack_planes(reinterpret_cast<const float2*>(dev), (int)take, (long long)F, (long long)F,
-                                               S, (long long)q.K, inner, frames, (long long)N, (int)u, c->stream);
-      if (e != hipSuccess) break;
-    }
-    if (rc != AMCX_OK) break;
-    e = hipEventRecord(c->slab_free[ds], c->stream);
-    if (e != hipSuccess) break;
-    u += take;
-    st.chunks = ch + 1;
-  }
-  if (rc == AMCX_OK && e == hipSuccess && !q.rows)
-    rc = ctx_features(c, c->d_frames, F, N, c->d_out, q.v, q.mask);
-  const double t_tail = wall_now();
-  st.seconds_prepare = q.t_loop - q.t_start;
-  // the result comes back into pinned memory (a copy into the caller's pageable rows would be staged by the
-  // runtime, ~100 us for 72 KB) and is spread over the caller's row stride by the host
-  if (rc == AMCX_OK && e == hipSuccess)
-    e = hipMemcpyAsync(c->out_pin, c->d_out, sizeof(float) * AMCX_NUM_FEATURES * (size_t)F, hipMemcpyDeviceToHost, c->stream);
-  if (rc == AMCX_OK && e != hipSuccess) rc = hip_fail(e, "amcx_ctx_features18_strided_host");
-  // success or not, nothing of this call is in flight when it returns (every upload is ordered before the
-  // compute stream's last kernel by an event, so on success that stream alone says so)
-  hipError_t e2 = hipStreamSynchronize(c->stream);
-  hipError_t e1 = (rc == AMCX_OK && e2 == hipSuccess) ? hipSuccess : hipStreamSynchronize(c->copy_stream);
-  if (rc == AMCX_OK && (e1 != hipSuccess || e2 != hipSuccess))
-    rc = hip_fail(e1 != hipSuccess ? e1 : e2, "amcx_ctx_features18_strided_host (sync)");
-  finish_strided(c, q, rc == AMCX_OK, t_tail);
-  return rc;
-}
-
-// src: memory (re / im) or a file (fd, byte offsets); src.kind is checked here, src.io_error is set here
-int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
-                    int32_t N, int64_t ss, int64_t sk, int64_t sn, float* out_host, int64_t out_row_stride,
-                    int32_t variant) {
-  if (c == nullptr) return AMCX_EINVAL;
-  const int32_t kind = src.kind;
-  if (S < 0 || K < 0 || ss < 0 || sk < 0 || sn < 0 || out_row_stride < AMCX_NUM_FEATURES ||
-      kind < AMCX_SRC_C64 || kind > AMCX_SRC_SC16)
-    return AMCX_EINVAL;
-  const int v = resolve_variant(N, variant);
-  if (v < 0) return v;
-  if (kind == AMCX_SRC_SC16 && sn != 1) return AMCX_ENOTSUP;        // sc16: row layouts only
-  if (S == 0 || K == 0) return AMCX_OK;
-  if (S > (int64_t(1) << 40) / K) return AMCX_EINVAL;
-  if ((src.fd < 0 && src.re == nullptr) || (src.fd >= 0 && src.re_off < 0) || out_host == nullptr) return AMCX_EINVAL;
-  struct InCall {
-    std::atomic<int>& n;
-    explicit InCall(std::atomic<int>& c) : n(c) { n.fetch_add(1, std::memory_order_acq_rel); }
-    ~InCall() { n.fetch_sub(1, std::memory_order_acq_rel); }
-  } in_call(c->in_call);
-  StridedCall q;
-  q.mask = c->feature_mask.load(std::memory_order_acquire);
-  if (kind < AMCX_SRC_F32_SPLIT || kind == AMCX_SRC_SC16) { src.im = nullptr; src.im_off = -1; }
-  src.io_error = &q.io_error;
-  q.src = src;
-  q.S = S; q.K = K; q.N = N; q.v = v; q.out_host = out_host; q.out_row_stride = out_row_stride;
-  const int64_t F = q.F = S * K;
-  if (!classify_layout(S, K, N, ss, sk, sn, &q.rows, &q.inner_snr, &q.map)) return AMCX_ENOTSUP;
-  const bool rows = q.rows;
-  if (!rows && S > 0x7fffffffLL) return AMCX_EINVAL;             // the transposition kernel indexes the snr axis with an int
-  const bool as_c128 = q.as_c128 = c->round_on_device && kind == AMCX_SRC_C128;
-  q.sc16 = kind == AMCX_SRC_SC16;
-  q.sc16_typed = q.sc16 && v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(N);
-  q.sc16_in.scale = c->sc16_scale.load(std::memory_order_acquire);
-  const size_t esz = q.esz = amcx::staged_elem_bytes(kind, as_c128);
-  const size_t src_esz = kind == AMCX_SRC_C64 ? 8 : kind == AMCX_SRC_C128 ? 16 : kind == AMCX_SRC_F32_SPLIT ? 4
-                         : kind == AMCX_SRC_SC16 ? 4 : 8;
-  const int64_t unit = q.unit = rows ? N : F;             // staged elements per chunk unit (a frame / a plane)
-  const int64_t n_units = q.n_units = rows ? F : N;
-  size_t slot = c->slot_bytes;
-  const size_t total_staged = q.total_staged = (size_t)unit * esz * (size_t)n_units;
-  if (slot > total_staged) slot = total_staged;                   // a per-frame call pins kilobytes, not 3 x 32 MiB
-  if (slot < (size_t)unit * esz) slot = (size_t)unit * esz;       // a slot holds at least one frame / one plane
-  if (slot > (size_t(4) << 30)) return AMCX_ENOMEM;               // > 4 GiB per plane: split the call by snr
-  slot = (slot + 4095) & ~size_t(4095);
-  q.slot = slot;
-
-  DeviceGuard guard;
-  AMCX_HIP(guard.enter(c->device));
-  q.t_start = wall_now();
-  // rows of complex128 rounded on the device: each device slot is followed by room for its rounded rows
-  // ... and rows of sc16 widened on the device by room for twice their bytes
-  q.dslot = (rows && as_c128) ? slot + slot / 2 : (q.sc16 && !q.sc16_typed) ? 3 * slot : slot;
-  const bool threaded = q.threaded = total_staged >= (size_t(1) << 20);   // below 1 MiB a condition-variable wake costs more than the copy
-  // an upload worth its staging threads runs on the device's own socket, this thread included: it stages, and the pinned
-  // slots strided_prepare may allocate are placed where it runs (a per-frame call is not worth two affinity system calls)
-  static const std::vector<int> kNoCpus;
-  amcx::AffinityGuard on_local_cpus(threaded ? c->bind_cpus : kNoCpus);
-  int rc = strided_prepare(c, slot, q.dslot, rows ? 0 : (size_t)F * N * 8, sizeof(float) * AMCX_NUM_FEATURES * (size_t)F,
-                           threaded);
-  if (rc != AMCX_OK) return rc;
-  ctx_reserve_ws(c, N, F, v);                                      // workspace and ring, before any capture below
-  amcx::Pool inline_pool;                                          // size 1: stage_runs runs on the caller
-  amcx::Pool& pool = threaded ? c->pool : inline_pool;
-  amcx_upload_stats& st = q.st;
-  st.frames = F; st.threads = pool.size(); st.plane_major = rows ? 0 : 1; st.from_file = src.fd >= 0 ? 1 : 0;
-  st.source_bytes = F * (int64_t)N * (int64_t)src_esz * ((kind >= AMCX_SRC_F32_SPLIT && src.has_im()) ? 2 : 1);
-  q.t_loop = wall_now();
-  if (run_small_graph(c, q, pool, &rc)) return rc;
-  return run_chunked(c, q, pool);
-}
-
-// the row-major host entries (amcx_ctx_features18_c64_host / _c128_host and their one-shot forms): a single-snr
-// container whose frames are row_stride_elems apart -- the row path of the strided engine
-int ctx_run(amcx_ctx* c, const void* iq_host, int32_t kind, int64_t n_frames, int32_t frame_size,
-            int64_t row_stride_elems, float* out_host, int64_t out_row_stride, int32_t variant) {
-  if (c == nullptr) return AMCX_EINVAL;
-  if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES) return AMCX_EINVAL;
-  amcx::Source src;
-  src.re = static_cast<const char*>(iq_host);
-  src.kind = kind;
-  return ctx_run_strided(c, src, 1, n_frames, frame_size, 0, row_stride_elems, 1, out_host, out_row_stride, variant);
-}
-
-int stage_any(amcx::Source src, int64_t n_snr, int64_t n_frames,
-                     int32_t frame_size, int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
-                     int64_t first_unit, int64_t n_units, void* dst, int64_t dst_bytes, int32_t threads,
-                     int32_t* plane_major, int32_t* inner_snr_out) {
-  const int32_t kind = src.kind;
-  if (n_snr < 0 || n_frames < 0 || stride_snr < 0 || stride_frame < 0 || stride_sample < 0 || first_unit < 0 ||
-      n_units < 0 || threads < 0 || threads > 256 || kind < AMCX_SRC_C64 || kind > AMCX_SRC_SC16 ||
-      frame_size < AMCX_MIN_FRAME_SIZE || frame_size > AMCX_MAX_FRAME_SIZE)
-    return AMCX_EINVAL;
-  if (n_frames > 0 && n_snr > (int64_t(1) << 40) / n_frames) return AMCX_EINVAL;
-  bool rows = false, inner_snr = false;
-  amcx::RunMap map;
-  if (!classify_layout(n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, &rows, &inner_snr, &map))
-    return AMCX_ENOTSUP;
-  if (kind == AMCX_SRC_SC16 && !rows) return AMCX_ENOTSUP;         // sc16: row layouts only
-  if (plane_major) *plane_major = rows ? 0 : 1;
-  if (inner_snr_out) *inner_snr_out = inner_snr ? 1 : 0;
-  const int64_t F = n_snr * n_frames, unit = rows ? frame_size : F, total_units = rows ? F : frame_size;
-  if (first_unit + n_units > total_units) return AMCX_EINVAL;
-  if (n_units == 0 || unit == 0) return AMCX_OK;
-  if ((src.fd < 0 && src.re == nullptr) || dst == nullptr ||
-      dst_bytes < n_units * unit * (int64_t)amcx::staged_elem_bytes(kind, false))
-    return AMCX_EINVAL;
-  if (kind < AMCX_SRC_F32_SPLIT || kind == AMCX_SRC_SC16) { src.im = nullptr; src.im_off = -1; }
-  std::atomic<int> io_error{0};
-  src.io_error = &io_error;
-  amcx::Pool pool;
-  pool.resize(threads < 1 ? 1 : threads);
-  const int64_t per_unit = rows ? 1 : map.cnt_b;
-  amcx::stage_runs(pool, static_cast<char*>(dst), src, map, first_unit * per_unit, (first_unit + n_units) * per_unit, false);
-  if (io_error.load() != 0) return io_fail(io_error.load());
-  return AMCX_OK;
-}
-
-// one-shot forms: a context for the duration of the call
-int one_shot(const void* iq_host, bool is_c128, int64_t n_frames, int32_t frame_size,
-                    int64_t row_stride_elems, float* out_host, int64_t out_row_stride, int32_t device,
-                    int32_t variant) {
-  // argument errors are reported before a device is looked for (tests/test_host_cpu.py runs without one)
-  if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES)
-    return AMCX_EINVAL;
-  const int v = resolve_variant(frame_size, variant);
-  if (v < 0) return v;
-  if (n_frames == 0) return AMCX_OK;
-  if (iq_host == nullptr || out_host == nullptr) return AMCX_EINVAL;
-  amcx_ctx* c = nullptr;
-  int rc = amcx_ctx_create(device, &c);
-  if (rc != AMCX_OK) return rc;
-  rc = ctx_run(c, iq_host, is_c128 ? AMCX_SRC_C128 : AMCX_SRC_C64, n_frames, frame_size, row_stride_elems, out_host, out_row_stride, v);
-  (void)amcx_ctx_destroy(c);
-  return rc;
-}
+namespace {
 
 // how a statistics call is cut: chunks per group and rows per chunk (whole tiles)
 void stats_plan(int64_t n_groups, int64_t rows_per_group, int n_cols, int64_t* chunks, int64_t* rows_per_chunk) {
@@ -980,6 +417,17 @@ bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
   if (widths == nullptr || n_linear < 1 || n_linear > amcx::kMlpMaxLinear) return false;
   for (int l = 0; l <= n_linear; ++l)
     if (widths[l] < 1 || widths[l] > amcx::kMlpMaxWidth) return false;
+  return true;
+}
+
+// the columns a post-processing entry selects (n_sel in range already); false: one of them is not a column of the input
+bool make_select_cols(const int32_t* cols_host, int32_t n_sel, int32_t n_cols, amcx::SelectCols* sel) {
+  sel->n = n_sel;
+  for (int j = 0; j < amcx::kStatMaxCols; ++j) sel->c[j] = 0;
+  for (int j = 0; j < n_sel; ++j) {
+    if (cols_host[j] < 0 || cols_host[j] >= n_cols) return false;
+    sel->c[j] = cols_host[j];
+  }
   return true;
 }
 
@@ -1049,7 +497,7 @@ int64_t amcx_features_sc16_workspace_bytes(int32_t frame_size, int64_t n_frames,
   if (n_frames < 0) return -1;
   const int v = resolve_variant(frame_size, variant);
   if (v < 0) return -1;
-  if (n_frames == 0 || (v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(frame_size))) return 0;
+  if (n_frames == 0 || sc16_typed(frame_size, v)) return 0;
   return sc16_widened_bytes(frame_size, n_frames) + amcx_features18_workspace_bytes(frame_size, n_frames, variant);
 }
 
@@ -1097,7 +545,7 @@ int amcx_ctx_create(int32_t device, amcx_ctx** ctx_out) {
   amcx_ctx* c = new (std::nothrow) amcx_ctx();
   if (c == nullptr) return AMCX_ENOMEM;
   c->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+  hipError_t e = c->stream.create();
   if (e != hipSuccess) { delete c; return hip_fail(e, "hipStreamCreateWithFlags"); }
   // Warm the runtime HERE, under the creating thread's own affinity mask: the first pinned allocation and the first
   // copy on a stream may start HIP / HSA helper threads, and a thread inherits its creator's mask for good.  Left to the
@@ -1105,15 +553,13 @@ int amcx_ctx_create(int32_t device, amcx_ctx** ctx_out) {
   // the device's socket for the duration of a threaded upload) and stay on those CPUs.  Best effort: a failure here
   // surfaces where the real allocation is made.
   {
-    void* warm_pin = nullptr;
-    void* warm_dev = nullptr;
-    if (hipHostMalloc(&warm_pin, 4096, hipHostMallocDefault) == hipSuccess && hipMalloc(&warm_dev, 4096) == hipSuccess) {
-      memset(warm_pin, 0, 4096);
-      if (hipMemcpyAsync(warm_dev, warm_pin, 4096, hipMemcpyHostToDevice, c->stream) == hipSuccess)
+    PinnedBuffer warm_pin;
+    DeviceBuffer warm_dev;
+    if (warm_pin.reserve(4096) == AMCX_OK && warm_dev.reserve(4096) == AMCX_OK) {
+      memset(warm_pin.p, 0, 4096);
+      if (hipMemcpyAsync(warm_dev.p, warm_pin.p, 4096, hipMemcpyHostToDevice, c->stream) == hipSuccess)
         (void)hipStreamSynchronize(c->stream);
     }
-    if (warm_dev != nullptr) (void)hipFree(warm_dev);
-    if (warm_pin != nullptr) (void)hipHostFree(warm_pin);
     (void)hipGetLastError();
   }
   // which CPUs are local to this device: from the kernel's PCI tree, unless AMCX_NUMA=0 (AMCX_SYSFS_ROOT: another tree)
@@ -1143,7 +589,8 @@ int amcx_ctx_bind_cpus(amcx_ctx* ctx, const int32_t* cpus, int32_t n_cpus) {
     v.push_back((int)cpus[i]);
   }
   // not while an upload runs on this context: its staging threads are reading the list this call replaces
-  if (ctx->in_call.load(std::memory_order_acquire) != 0) return AMCX_EINVAL;
+  const amcx::CallGate::Token idle = ctx->gate.claim_idle();
+  if (!idle) return AMCX_EINVAL;
   ctx->bind_cpus = v;
   if (v.empty()) ctx->numa_node = -1;
   ctx->pool.set_cpus(ctx->bind_cpus);
@@ -1152,21 +599,17 @@ int amcx_ctx_bind_cpus(amcx_ctx* ctx, const int32_t* cpus, int32_t n_cpus) {
 
 int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask) {
   if (ctx == nullptr || !valid_feature_mask(feature_mask)) return AMCX_EINVAL;
-  // claim the context: the compare-exchange fails while a call is running on it, and no call can start to count itself in
-  // between a check and the store (a call that starts after the claim reads the mask once, whichever it finds)
-  int idle = 0;
-  if (!ctx->in_call.compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return AMCX_EINVAL;
+  const amcx::CallGate::Token idle = ctx->gate.claim_idle();     // fails while a call is running on the context
+  if (!idle) return AMCX_EINVAL;
   ctx->feature_mask.store(feature_mask, std::memory_order_release);
-  ctx->in_call.fetch_sub(1, std::memory_order_acq_rel);
   return AMCX_OK;
 }
 
 int amcx_ctx_set_sc16_scale(amcx_ctx* ctx, float scale) {
   if (ctx == nullptr || !(scale > 0.0f && scale <= 3.4028235e38f)) return AMCX_EINVAL;
-  int idle = 0;                     // claimed as amcx_ctx_set_feature_mask claims it
-  if (!ctx->in_call.compare_exchange_strong(idle, 1, std::memory_order_acq_rel)) return AMCX_EINVAL;
+  const amcx::CallGate::Token idle = ctx->gate.claim_idle();
+  if (!idle) return AMCX_EINVAL;
   ctx->sc16_scale.store(scale, std::memory_order_release);
-  ctx->in_call.fetch_sub(1, std::memory_order_acq_rel);
   return AMCX_OK;
 }
 
@@ -1212,19 +655,8 @@ int amcx_ctx_destroy(amcx_ctx* c) {
   if (c == nullptr) return AMCX_OK;
   DeviceGuard guard;
   (void)guard.enter(c->device);
-  if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-  if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-  for (auto ev : c->up_done) if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : c->slab_free) if (ev) (void)hipEventDestroy(ev);
-  if (c->d_out) (void)hipFree(c->d_out);
-  if (c->d_slab) (void)hipFree(c->d_slab);
-  if (c->d_frames) (void)hipFree(c->d_frames);
-  if (c->d_ws) (void)hipFree(c->d_ws);
-  if (c->d_ring) (void)hipFree(c->d_ring);
-  if (c->pin) (void)hipHostFree(c->pin);
-  if (c->out_pin) (void)hipHostFree(c->out_pin);
-  for (auto& g : c->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  delete c;                                     // joins the staging threads
+  for (hipStream_t s : {c->stream.s, c->copy_stream.s}) if (s != nullptr) (void)hipStreamSynchronize(s);
+  delete c;                                     // every member frees itself (amcx_ctx, MEMBER ORDER); joins the staging threads
   return AMCX_OK;
 }
 
@@ -1232,11 +664,7 @@ int amcx_ctx_features18_strided_host(amcx_ctx* ctx, const void* re, const void* 
                                      int64_t n_snr, int64_t n_frames, int32_t frame_size,
                                      int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
                                      float* out_host, int64_t out_row_stride, int32_t variant) {
-  amcx::Source src;
-  src.re = static_cast<const char*>(re);
-  src.im = static_cast<const char*>(im);
-  src.kind = kind;
-  return ctx_run_strided(ctx, src, n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample,
+  return ctx_run_strided(ctx, amcx::Source::memory(re, im, kind), n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample,
                          out_host, out_row_stride, variant);
 }
 
@@ -1245,12 +673,7 @@ int amcx_ctx_features18_strided_file(amcx_ctx* ctx, int32_t fd, int64_t re_offse
                                      int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
                                      float* out_host, int64_t out_row_stride, int32_t variant) {
   if (fd < 0 || re_offset < 0) return AMCX_EINVAL;
-  amcx::Source src;
-  src.fd = fd;
-  src.re_off = re_offset;
-  src.im_off = im_offset;
-  src.kind = kind;
-  return ctx_run_strided(ctx, src, n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample,
+  return ctx_run_strided(ctx, amcx::Source::file(fd, re_offset, im_offset, kind), n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample,
                          out_host, out_row_stride, variant);
 }
 
@@ -1258,11 +681,7 @@ int amcx_stage_host(const void* re, const void* im, int32_t kind, int64_t n_snr,
                     int32_t frame_size, int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
                     int64_t first_unit, int64_t n_units, void* dst, int64_t dst_bytes, int32_t threads,
                     int32_t* plane_major, int32_t* inner_snr_out) {
-  amcx::Source src;
-  src.re = static_cast<const char*>(re);
-  src.im = static_cast<const char*>(im);
-  src.kind = kind;
-  return stage_any(src, n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, first_unit, n_units, dst,
+  return stage_any(amcx::Source::memory(re, im, kind), n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, first_unit, n_units, dst,
                    dst_bytes, threads, plane_major, inner_snr_out);
 }
 
@@ -1271,12 +690,7 @@ int amcx_stage_file(int32_t fd, int64_t re_offset, int64_t im_offset, int32_t ki
                     int64_t first_unit, int64_t n_units, void* dst, int64_t dst_bytes, int32_t threads,
                     int32_t* plane_major, int32_t* inner_snr_out) {
   if (fd < 0 || re_offset < 0) return AMCX_EINVAL;
-  amcx::Source src;
-  src.fd = fd;
-  src.re_off = re_offset;
-  src.im_off = im_offset;
-  src.kind = kind;
-  return stage_any(src, n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, first_unit, n_units, dst,
+  return stage_any(amcx::Source::file(fd, re_offset, im_offset, kind), n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, first_unit, n_units, dst,
                    dst_bytes, threads, plane_major, inner_snr_out);
 }
 
@@ -1377,91 +791,9 @@ int amcx_kernel_name_sc16(int32_t frame_size, int32_t variant, uint32_t feature_
   if (buf == nullptr || buf_len <= 0 || !valid_feature_mask(feature_mask)) return AMCX_EINVAL;
   const int v = resolve_variant(frame_size, variant);
   if (v < 0) return v;
-  if (v != AMCX_VARIANT_WAVE || !amcx::has_sc16_kernels(frame_size))     // widened, then the complex64 kernel
+  if (!sc16_typed(frame_size, v))     // widened, then the complex64 kernel
     return amcx_kernel_name_subset(frame_size, variant, feature_mask, buf, buf_len);
   amcx::wave_kernel_name(frame_size, subset_plan(frame_size, v, feature_mask), buf, (size_t)buf_len, true);
-  return AMCX_OK;
-}
-
-int amcx_probe_fma_rate(double seconds, void* hip_stream, double* wave_instr_per_s, double* clock_ghz) {
-  if (!(seconds > 0.0) || seconds > 60.0 || wave_instr_per_s == nullptr) return AMCX_EINVAL;
-  *wave_instr_per_s = 0.0;
-  if (clock_ghz) *clock_ghz = 0.0;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const int grid = cu_count();
-  if (grid <= 0) return AMCX_ENODEV;
-  const long long n_waves = (long long)grid * 16;
-  constexpr int kIters = 32768;                            // x 32 instructions x 4096 waves: ~5 ms a launch
-  float* sink = nullptr;
-  unsigned long long* ticks = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-  int rc = AMCX_OK;
-  auto fail = [&](hipError_t e, const char* what) { rc = hip_fail(e, what); };
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&sink), 4);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ticks), (size_t)n_waves * 16);
-  if (e == hipSuccess) e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
-  if (e == hipSuccess) e = hipEventCreate(&e2);
-  if (e != hipSuccess) {
-    fail(e, "fma probe setup");
-  } else {
-    auto launch = [&]() { hipLaunchKernelGGL(amcx_probe_fma_kernel, dim3((unsigned)grid), dim3(1024), 0, stream, kIters, sink, ticks); };
-    // one launch to learn its length, then `seconds` of back-to-back launches: the first half lets the board's power
-    // management settle the clock, the second half is timed
-    (void)hipEventRecord(e0, stream);
-    launch();
-    (void)hipEventRecord(e1, stream);
-    e = hipEventSynchronize(e1);
-    float one_ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&one_ms, e0, e1);
-    if (e != hipSuccess) {
-      fail(e, "fma probe launch");
-    } else {
-      if (!(one_ms > 0.01f)) one_ms = 0.01f;
-      long long n = (long long)(seconds * 1e3 / 2.0 / one_ms);
-      if (n < 1) n = 1;
-      if (n > 100000) n = 100000;
-      for (long long i = 0; i < n; ++i) launch();
-      (void)hipEventRecord(e1, stream);
-      for (long long i = 0; i < n; ++i) launch();
-      (void)hipEventRecord(e2, stream);
-      e = hipEventSynchronize(e2);
-      float ms = 0.f;
-      if (e == hipSuccess) e = hipEventElapsedTime(&ms, e1, e2);
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e != hipSuccess || !(ms > 0.f)) {
-        fail(e, "fma probe timing");
-      } else {
-        *wave_instr_per_s = (double)n * (double)n_waves * (double)kIters * 32.0 / ((double)ms * 1e-3);
-        if (clock_ghz) {
-          std::vector<unsigned long long> h((size_t)n_waves * 2);
-          e = hipMemcpy(h.data(), ticks, h.size() * 8, hipMemcpyDeviceToHost);
-          if (e == hipSuccess) {
-            double cyc = 0.0, real = 0.0;
-            for (long long w = 0; w < n_waves; ++w) { cyc += (double)h[(size_t)(2 * w)]; real += (double)h[(size_t)(2 * w + 1)]; }
-            if (real > 0.0) *clock_ghz = cyc / (real * 10.0);       // s_memrealtime ticks at 100 MHz
-          } else {
-            fail(e, "fma probe read-back");
-          }
-        }
-      }
-    }
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (e2) (void)hipEventDestroy(e2);
-  if (sink) (void)hipFree(sink);
-  if (ticks) (void)hipFree(ticks);
-  return rc;
-}
-
-int amcx_probe_read_bw(const void* src_dev, int64_t n_bytes, float* partial_dev, void* hip_stream) {
-  if (src_dev == nullptr || partial_dev == nullptr || n_bytes < 0 || (n_bytes & 15)) return AMCX_EINVAL;
-  if (n_bytes == 0) return AMCX_OK;
-  hipLaunchKernelGGL(amcx_probe_read_kernel, dim3(4096), dim3(256), 0,
-                     static_cast<hipStream_t>(hip_stream), static_cast<const float4*>(src_dev),
-                     (long long)(n_bytes / 16), partial_dev);
-  AMCX_HIP(hipGetLastError());
   return AMCX_OK;
 }
 
@@ -1534,12 +866,7 @@ int amcx_standardize_fit_transform_f32(const float* x_dev, int64_t n_rows, int64
       n_cols < 1 || n_cols > amcx::kStatMaxCols || row_stride < n_cols)
     return AMCX_EINVAL;
   amcx::SelectCols sel;
-  sel.n = n_sel;
-  for (int j = 0; j < amcx::kStatMaxCols; ++j) sel.c[j] = 0;
-  for (int j = 0; j < n_sel; ++j) {
-    if (cols_host[j] < 0 || cols_host[j] >= n_cols) return AMCX_EINVAL;
-    sel.c[j] = cols_host[j];
-  }
+  if (!make_select_cols(cols_host, n_sel, n_cols, &sel)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
   if (!x_dev || !out_dev || !mean_dev || !scale_dev || !workspace_dev) return AMCX_EINVAL;
   if (on_another_device(x_dev) || on_another_device(out_dev)) return AMCX_EINVAL;
@@ -1602,12 +929,7 @@ int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
   if (activation != AMCX_ACT_RELU && activation != AMCX_ACT_TANH && activation != AMCX_ACT_SIGMOID) return AMCX_EINVAL;
   if ((mean_dev == nullptr) != (scale_dev == nullptr)) return AMCX_EINVAL;
   amcx::SelectCols sel;
-  sel.n = n_sel;
-  for (int j = 0; j < amcx::kStatMaxCols; ++j) sel.c[j] = 0;
-  for (int j = 0; j < n_sel; ++j) {
-    if (cols_host[j] < 0 || cols_host[j] >= n_cols) return AMCX_EINVAL;
-    sel.c[j] = cols_host[j];
-  }
+  if (!make_select_cols(cols_host, n_sel, n_cols, &sel)) return AMCX_EINVAL;
   const int n_cls = widths_host[n_linear];
   if (probs_dev != nullptr && probs_stride < n_cls) return AMCX_EINVAL;
   if (rows_per_group < 0 || (rows_per_group == 0 && counts_dev != nullptr)) return AMCX_EINVAL;

@@ -253,6 +253,40 @@ class Pool {
   bool stop_ = false;
 };
 
+// ---- "a call is running on this context" ----------------------------------------------------------
+// One counter, two operations.  A call holds enter()'s token for its duration.  A setter of something calls read (the
+// CPU list, the feature mask, the sc16 scale) holds claim_idle()'s: it gets one only while no call is inside and no other
+// claim is held, and while it holds it -- a few stores, at most a rebuilt staging pool -- enter() waits.  So what a
+// claimant writes is never read by a call at the same time, and the tokens order the two (acquire / release).
+class CallGate {
+ public:
+  class Token {                                    // leaves (or gives the claim back) when it goes out of scope
+   public:
+    Token(std::atomic<int>* n, int by) : n_(n), by_(by) {}
+    Token(Token&& o) noexcept : n_(o.n_), by_(o.by_) { o.n_ = nullptr; }
+    ~Token() { if (n_ != nullptr) n_->fetch_sub(by_, std::memory_order_acq_rel); }
+    explicit operator bool() const { return n_ != nullptr; }
+   private:
+    std::atomic<int>* n_;
+    int by_;
+  };
+  Token enter() {
+    for (;;) {
+      int n = n_.load(std::memory_order_relaxed);
+      if (n >= 0 && n_.compare_exchange_weak(n, n + 1, std::memory_order_acq_rel)) return Token(&n_, 1);
+      if (n < 0) std::this_thread::yield();
+    }
+  }
+  Token claim_idle() {                             // an empty token (false): a call is inside, or another claim is held
+    int idle = 0;
+    return n_.compare_exchange_strong(idle, kClaimed, std::memory_order_acq_rel) ? Token(&n_, kClaimed) : Token(nullptr, 0);
+  }
+
+ private:
+  static constexpr int kClaimed = -1;
+  std::atomic<int> n_{0};                          // calls inside, or kClaimed
+};
+
 // ---- source description ---------------------------------------------------------------------------
 // kinds as in include/amcx.h (AMCX_SRC_*): interleaved complex64 / complex128, or split real / imaginary
 // arrays of float32 / float64 (im == nullptr: a real signal, imaginary part zero), or sc16 -- interleaved int16 pairs,
@@ -264,6 +298,7 @@ class Pool {
 // container never exists in host memory outside the page cache.  First-touching the pages of a fresh mapping of a
 // 436 MB variable costs 30 ms however many threads fault, reading it into a fresh buffer as much again for the
 // buffer's own pages (profiles/r3_read_probe.txt); pread into 256 KB that every thread reuses has neither cost.
+enum { kSrcC64 = 0, kSrcC128 = 1, kSrcF32Split = 2, kSrcF64Split = 3, kSrcSc16 = 4 };
 struct Source {
   const char* re = nullptr;
   const char* im = nullptr;
@@ -272,8 +307,20 @@ struct Source {
   int64_t re_off = 0, im_off = -1;
   std::atomic<int>* io_error = nullptr;     // set to an errno (EIO for a short file) by the first read that fails
   bool has_im() const { return fd >= 0 ? im_off >= 0 : im != nullptr; }
+  // The two ways a Source is made.  Only the split kinds have an imaginary array: whatever a caller passes for one of
+  // the interleaved kinds (complex64, complex128, sc16) is dropped here, once.
+  static bool split(int kind) { return kind == kSrcF32Split || kind == kSrcF64Split; }
+  static Source memory(const void* re, const void* im, int kind) {
+    Source s;
+    s.kind = kind; s.re = static_cast<const char*>(re); s.im = split(kind) ? static_cast<const char*>(im) : nullptr;
+    return s;
+  }
+  static Source file(int fd, int64_t re_off, int64_t im_off, int kind) {
+    Source s;
+    s.kind = kind; s.fd = fd; s.re_off = re_off; s.im_off = split(kind) ? im_off : -1;
+    return s;
+  }
 };
-enum { kSrcC64 = 0, kSrcC128 = 1, kSrcF32Split = 2, kSrcF64Split = 3, kSrcSc16 = 4 };
 // bytes of a STAGED element: sc16 and (as_c128) complex128 as they lie, everything else as complex64
 inline size_t staged_elem_bytes(int kind, bool as_c128) { return kind == kSrcSc16 ? 4 : as_c128 ? 16 : 8; }
 

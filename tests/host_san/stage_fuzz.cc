@@ -1,5 +1,5 @@
 // Host-only harness for the staging half of the real-data path (amcpy_amd/csrc/amcx_upload.h: the fork-join
-// Pool, stage_runs over memory and file sources, classify_layout), built by tests/test_host_cpu.py three ways --
+// Pool, stage_runs over memory and file sources, classify_layout, the Source constructors, CallGate), built by tests/test_host_cpu.py three ways --
 //   g++ -O1 -g -fsanitize=address,undefined     g++ -O1 -g -fsanitize=thread     g++ -O2
 // -- and run in the CPU suite.  No HIP, no GPU.  The reference's own threading defect is of exactly this class
 // (worker threads sharing one queue and one output array, exceptions swallowed: feature_extraction.py:22-39,74),
@@ -51,14 +51,12 @@ struct Box {
       default: out[0] = (float)re64[e]; out[1] = has_im ? (float)im64[e] : 0.f; break;
     }
   }
+  // (an interleaved kind is handed its own array as "imaginary part", as a careless caller might: Source::memory drops it)
   amcx::Source memory() const {
-    amcx::Source src;
-    src.kind = kind;
     const bool f32 = kind == amcx::kSrcC64 || kind == amcx::kSrcF32Split;
-    src.re = f32 ? reinterpret_cast<const char*>(re32.data()) : reinterpret_cast<const char*>(re64.data());
-    if (has_im && kind >= amcx::kSrcF32Split)
-      src.im = f32 ? reinterpret_cast<const char*>(im32.data()) : reinterpret_cast<const char*>(im64.data());
-    return src;
+    const void* re = f32 ? static_cast<const void*>(re32.data()) : static_cast<const void*>(re64.data());
+    const void* im = f32 ? static_cast<const void*>(im32.data()) : static_cast<const void*>(im64.data());
+    return amcx::Source::memory(re, kind < amcx::kSrcF32Split ? re : has_im ? im : nullptr, kind);
   }
   size_t re_bytes() const {
     const bool f32 = kind == amcx::kSrcC64 || kind == amcx::kSrcF32Split;
@@ -100,7 +98,7 @@ Box make_box(Rng& rng, bool want_unit_axis, bool big = false) {
   return b;
 }
 
-// stage units [first, first + count) of the box the way amcx.hip's stage_any / ctx_run_strided (run_small_graph, run_chunked) do, and check every value
+// stage units [first, first + count) of the box the way amcx_ctx.h's stage_any / ctx_run_strided (run_small_graph, run_chunked) do, and check every value
 void stage_and_check(const Box& b, const amcx::Source& src, amcx::Pool& pool, int64_t first, int64_t count,
                      bool rows, bool inner, const amcx::RunMap& map) {
   const int64_t F = b.S * b.K, unit = rows ? b.N : F, per_unit = rows ? 1 : map.cnt_b;
@@ -149,12 +147,11 @@ int fuzz_layouts(Rng& rng, const std::string& dir, int cases) {
       fwrite(mem.re, 1, b.re_bytes(), fh);
       if (b.im_bytes()) fwrite(mem.im, 1, b.im_bytes(), fh);
       fclose(fh);
-      amcx::Source f;
-      f.kind = b.kind;
-      f.fd = open(path.c_str(), O_RDONLY);
+      // (an interleaved kind is handed an offset for an imaginary array it does not have: Source::file drops it)
+      amcx::Source f = amcx::Source::file(open(path.c_str(), O_RDONLY), 24,
+                                          b.im_bytes() || b.kind < amcx::kSrcF32Split ? (int64_t)(24 + b.re_bytes()) : -1, b.kind);
       if (f.fd < 0) die("cannot open the scratch file");
-      f.re_off = 24;
-      f.im_off = b.im_bytes() ? (int64_t)(24 + b.re_bytes()) : -1;
+      if (f.has_im() != (b.im_bytes() != 0) || mem.has_im() != f.has_im()) die("the imaginary part of a source", b.kind);
       std::atomic<int> io_error{0};
       f.io_error = &io_error;
       stage_and_check(b, f, pool, first, count, rows, inner, map);
@@ -296,6 +293,70 @@ void placement(const char* dir) {
   if (none.bound()) die("empty guard bound");
 }
 
+// Source::memory / Source::file: for every kind, an imaginary part exactly where the kind is split AND the caller gave one
+void source_constructors() {
+  const char x[16] = {0};
+  for (int kind = amcx::kSrcC64; kind <= amcx::kSrcSc16; ++kind) {
+    const bool split = kind == amcx::kSrcF32Split || kind == amcx::kSrcF64Split;
+    const amcx::Source m = amcx::Source::memory(x, x, kind), f = amcx::Source::file(3, 24, 48, kind);
+    if (m.has_im() != split || (m.im != nullptr) != split || m.re != x || m.kind != kind || m.fd >= 0) die("Source::memory", kind);
+    if (f.has_im() != split || (f.im_off >= 0) != split || f.re_off != 24 || f.fd != 3 || f.kind != kind || f.im != nullptr)
+      die("Source::file", kind);
+    if (amcx::Source::memory(x, nullptr, kind).has_im() || amcx::Source::file(3, 24, -1, kind).has_im())
+      die("a real signal grew an imaginary part", kind);
+  }
+}
+
+// CallGate: four threads enter() and leave as calls do, two claim_idle() as amcx_ctx_bind_cpus does and, holding the claim,
+// replace a PLAIN vector that every call reads -- nothing but the gate orders the two, so ThreadSanitizer reporting
+// nothing on that vector is the point.  A claim must never be held while a call is inside, and both must get their turn.
+void call_gate() {
+  amcx::CallGate gate;
+  std::vector<int> cpus(8, 0);
+  std::atomic<int> inside{0};
+  std::atomic<bool> claimed{false}, stop{false};
+  std::atomic<long long> calls{0}, claims{0};
+  std::vector<std::thread> threads;
+  for (int t = 0; t < 4; ++t)
+    threads.emplace_back([&] {
+      while (!stop.load()) {
+        {
+          const amcx::CallGate::Token in_call = gate.enter();
+          inside.fetch_add(1);
+          if (claimed.load()) die("a call entered under a claim");
+          for (int v : cpus) if (v != cpus.front()) die("a call read a half-replaced list", v, cpus.front());
+          inside.fetch_sub(1);
+        }
+        calls.fetch_add(1);
+        std::this_thread::yield();
+      }
+    });
+  for (int t = 0; t < 2; ++t)
+    threads.emplace_back([&, t] {
+      for (int it = 1; !stop.load(); ++it) {
+        {
+          const amcx::CallGate::Token idle = gate.claim_idle();
+          if (!idle) continue;
+          if (claimed.exchange(true)) die("two claims at once");
+          if (inside.load() != 0) die("a claim succeeded while a call was inside", inside.load());
+          cpus.assign((size_t)(4 + (it & 7)), 2 * it + t);             // a vector assignment, as bind_cpus does
+          claimed.store(false);
+        }
+        claims.fetch_add(1);
+        std::this_thread::yield();
+      }
+    });
+  const auto t0 = std::chrono::steady_clock::now();
+  while (calls.load() < 2000 || claims.load() < 200) {
+    if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) die("the call gate starves one side", calls.load(), claims.load());
+    std::this_thread::sleep_for(std::chrono::microseconds(200));
+  }
+  stop.store(true);
+  for (auto& th : threads) th.join();
+  if (calls.load() == 0 || claims.load() == 0) die("no progress", calls.load(), claims.load());
+  if (!gate.claim_idle()) die("the gate is not idle at the end");
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -308,8 +369,10 @@ int main(int argc, char** argv) {
   hammer_pool(rng);
   concurrent_pools(rng);
   placement(dir);
+  source_constructors();
+  call_gate();
   rmdir(dir);
-  printf("STAGE_FUZZ_OK seed %llu: 60 layouts (%d also from a file, each truncated once), 1000 pool runs, 3 concurrent pools, placement\n",
+  printf("STAGE_FUZZ_OK seed %llu: 60 layouts (%d also from a file, each truncated once), 1000 pool runs, 3 concurrent pools, placement, sources, call gate\n",
          seed, files);
   return 0;
 }

@@ -1975,6 +1975,68 @@ def test_small_host_calls_replay_a_graph():
     ctx.close()
 
 
+def test_one_context_through_every_buffer():
+    """ONE context through a sequence of calls that allocates every buffer it owns, reuses each at the same size and
+    grows each at least once, and meets the graphs it captured before a growth again after it -- twice over, every
+    result bit for bit what a FRESH context that served nothing else gives for the same input.  The steps: the
+    zero-copy graph (1 x 128 complex64); the graph with the widening node and the room behind the slot (3 x 1000
+    sc16); the context's workspace allocated (2 x 8193) and grown (2 x 16385); the ring, and a graph whose node points
+    into it (4 x 2048); a threaded upload of 36 chunks of 64 KiB, the pinned and device slots reused many times and
+    the output buffers grown (2304 x 128); a plane-major (Fortran-ordered) complex128 container, which takes d_frames;
+    then the first, second and fifth again: after the growths a stale graph must not be replayed.  (The ABI reports no
+    graph hits or misses; that calls of these shapes do run as graphs is test_small_host_calls_replay_a_graph's to hold.)"""
+    from amcpy_amd import _lib
+    rng = np.random.default_rng(1207)
+
+    def noise(F, N, dtype=np.complex64):
+        return (rng.standard_normal((F, N)) + 1j * rng.standard_normal((F, N))).astype(dtype)
+
+    def rows(x, N):
+        def call(ctx):
+            out = np.full((x.shape[0], 18), -1.0, dtype=np.float32)
+            ctx.run(x, N, out, _lib.VARIANT_AUTO)
+            return out
+        return call
+
+    S, K, L, N7 = 2, 40, 300, 256
+    box = np.asfortranarray((rng.standard_normal((S, K, L)) + 1j * rng.standard_normal((S, K, L))).astype(np.complex128))
+    assert box.strides == (16, 16 * S, 16 * S * K)
+
+    def planes(ctx):
+        out = np.full((S * K, 18), -1.0, dtype=np.float32)
+        ctx.run_strided(box.ctypes.data, None, _lib.SRC_C128, S, K, N7, (1, S, S * K), out)
+        assert ctx.upload_stats()["plane_major"] == 1
+        return out
+
+    def many_chunks(ctx, x=noise(2304, 128)):
+        out = rows(x, 128)(ctx)
+        st = ctx.upload_stats()
+        assert st["chunks"] >= 36 and st["threads"] == 3 and st["plane_major"] == 0, st
+        return out
+
+    sc16 = rng.integers(-32768, 32768, size=(3, 1000, 2), dtype=np.int16)
+    steps = [rows(noise(1, 128), 128), rows(sc16, 1000), rows(noise(2, 8193), 8193), rows(noise(2, 16385), 16385),
+             rows(noise(4, 2048), 2048), many_chunks, planes]
+    order = [0, 1, 2, 3, 4, 5, 6, 0, 1, 4]
+
+    def context():
+        ctx = _lib.HostContext(0)
+        ctx.configure(threads=3, slot_bytes=65536)
+        return ctx
+
+    want = []
+    for step in steps:                                         # each through a context of its own
+        fresh = context()
+        want.append(step(fresh))
+        fresh.close()
+        assert np.isfinite(want[-1]).all()
+    ctx = context()
+    for rep in range(2):
+        for pos, i in enumerate(order):
+            assert np.array_equal(steps[i](ctx), want[i], equal_nan=True), (rep, pos, i)
+    ctx.close()
+
+
 # ----------------------------------------------------------------------------
 # round 5, third session: every frame size up to 32768 (ABI 6, amcx_stream_kernel.h)
 # ----------------------------------------------------------------------------
