@@ -12,7 +12,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 9          # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 10         # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -21,6 +21,9 @@ VARIANTS = {"auto": VARIANT_AUTO, "block": VARIANT_BLOCK, "wave": VARIANT_WAVE}
 OK, EINVAL, ENOTSUP, EHIP, ENODEV, ENOMEM, EIO = 0, -1, -2, -3, -4, -5, -6
 SRC_C64, SRC_C128, SRC_F32_SPLIT, SRC_F64_SPLIT, SRC_SC16 = 0, 1, 2, 3, 4
 SC16_SCALE = 2.0 ** -15                                 # the default sc16 scale: int16 onto [-1, 1) (ABI 9)
+SRC_CI8, SRC_CU8 = 8, 9                                  # 8-bit IQ (ABI 10); 5, 6 and 7 are no kinds
+IQ8_CI8, IQ8_CU8 = 0, 1                                  # AMCX_IQ8_*: the format argument of the 8-bit entries
+IQ8_SCALE = 2.0 ** -7                                    # the default 8-bit scale: int8 onto [-1, 1)
 ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2                # AMCX_ACT_* (ABI 8)
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
 
@@ -57,6 +60,11 @@ SIGNATURES = {
     "amcx_kernel_name_sc16": (C.c_int, [_i32, _i32, C.c_uint32, C.c_char_p, _i32]),
     "amcx_ctx_set_sc16_scale": (C.c_int, [_vp, C.c_float]),
     "amcx_ctx_features18_sc16_host": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _i32]),
+    "amcx_features_iq8_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "amcx_features_iq8": (C.c_int, [_vp, _i64, _i32, _i64, _i32, C.c_float, _vp, _i64, _vp, _i32, C.c_uint32, _vp, _i64]),
+    "amcx_kernel_name_iq8": (C.c_int, [_i32, _i32, C.c_uint32, C.c_char_p, _i32]),
+    "amcx_ctx_set_iq8_scale": (C.c_int, [_vp, C.c_float]),
+    "amcx_ctx_features18_iq8_host": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp, _i64, _i32]),
     "amcx_ctx_set_feature_mask": (C.c_int, [_vp, C.c_uint32]),
     "amcx_features18_c64_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
     "amcx_features18_c128_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
@@ -204,6 +212,13 @@ def kernel_name_sc16(frame_size: int, variant: int = VARIANT_AUTO, mask: int = F
     return buf.value.decode()
 
 
+def kernel_name_iq8(frame_size: int, variant: int = VARIANT_AUTO, mask: int = FEATURES_ALL) -> str:
+    """amcx_kernel_name_iq8: the feature kernel amcx_features_iq8 runs behind its widening kernel (host-only)."""
+    buf = C.create_string_buffer(128)
+    check(load().amcx_kernel_name_iq8(int(frame_size), int(variant), int(mask), buf, len(buf)))
+    return buf.value.decode()
+
+
 def numa_place(pci_bus_id: str, sysfs_root: str = "") -> tuple:
     """(node, [cpus]) local to the PCI device ``dddd:bb:dd.f`` according to ``<sysfs_root>/bus/pci/devices`` (default
     /sys): amcx_numa_place.  (-1, []) when the platform does not say.  Host-only: needs no GPU."""
@@ -237,6 +252,7 @@ class HostContext:
         self.device = int(device)
         self.mask = FEATURES_ALL
         self.sc16_scale = SC16_SCALE
+        self.iq8_scale = IQ8_SCALE
         check(load().amcx_ctx_create(self.device, C.byref(self._h)))
 
     def set_feature_mask(self, mask: int) -> None:
@@ -253,10 +269,23 @@ class HostContext:
             check(load().amcx_ctx_set_sc16_scale(self._h, scale))
             self.sc16_scale = scale
 
+    def set_iq8_scale(self, scale: float) -> None:
+        """amcx_ctx_set_iq8_scale: what every later 8-bit call multiplies a component by."""
+        scale = C.c_float(scale).value
+        if scale != self.iq8_scale:
+            check(load().amcx_ctx_set_iq8_scale(self._h, scale))
+            self.iq8_scale = scale
+
     def run(self, x2, frame_size: int, out, variant: int) -> None:
-        """x2: C-contiguous (F, L) complex64 / complex128 ndarray, or (F, L, 2) int16 (sc16); out: (F, >=18) float32."""
+        """x2: C-contiguous (F, L) complex64 / complex128 ndarray, or (F, L, 2) int16 (sc16) / int8 (ci8) / uint8 (cu8);
+        out: (F, >=18) float32."""
         import numpy as np
         lib = load()
+        if x2.dtype == np.int8 or x2.dtype == np.uint8:
+            check(lib.amcx_ctx_features18_iq8_host(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1],
+                                                   IQ8_CI8 if x2.dtype == np.int8 else IQ8_CU8, out.ctypes.data,
+                                                   out.shape[1], int(variant)))
+            return
         if x2.dtype == np.int16:
             check(lib.amcx_ctx_features18_sc16_host(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1],
                                                     out.ctypes.data, out.shape[1], int(variant)))

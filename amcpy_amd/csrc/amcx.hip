@@ -13,7 +13,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_sc16_kernels.h"     // FIRST: KERNEL ORDER, amcx_launch.h
+#include "amcx_iq8_kernels.h"      // FIRST, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
+#include "amcx_sc16_kernels.h"
 #include "amcx_block_kernel.h"
 #include "amcx_stream_kernel.h"
 #include "amcx_launch.h"
@@ -285,35 +286,53 @@ struct Workspace {
   bool own = false;
 };
 
-// sc16 frames (include/amcx.h, amcx_features_sc16): iq_dev holds int16 pairs, a component's value is (float)int16 * scale
-struct Sc16In {
+// Integer frames: iq_dev holds int16 pairs (include/amcx.h, amcx_features_sc16) or, iq8 >= 0, pairs of bytes in the format
+// AMCX_IQ8_CI8 / AMCX_IQ8_CU8 (amcx_features_iq8); a component's value is (float)integer * scale
+struct IntIn {
   float scale;
+  int32_t iq8 = -1;
+  bool is_iq8() const { return iq8 >= 0; }
+  unsigned flip() const { return iq8 == AMCX_IQ8_CU8 ? 0x80u : 0x00u; }     // amcx_iq8_kernels.h
 };
+inline bool int_scale_ok(float scale) { return scale > 0.0f && scale <= 3.4028235e38f; }   // not NaN, inf, <= 0
+inline bool iq8_format_ok(int32_t format) { return format == AMCX_IQ8_CI8 || format == AMCX_IQ8_CU8; }
 inline int64_t sc16_widened_bytes(int32_t N, int64_t n_frames) { return (8 * (int64_t)N * n_frames + 255) / 256 * 256; }
+// the widened copy of 8-bit frames: sc16 where an sc16 kernel reads it (typed), complex64 otherwise
+inline int64_t iq8_widened_bytes(int32_t N, int64_t n_frames, bool typed) {
+  return ((typed ? 4 : 8) * (int64_t)N * n_frames + 255) / 256 * 256;
+}
 // (defined behind run_features: KERNEL ORDER, amcx_launch.h)
 hipError_t launch_sc16_plan(const amcx::Frames& frames, int32_t N, int plan, float* ring, uint32_t mask);
 hipError_t launch_sc16_widen(const amcx::Frames& frames, int32_t N, float2* dst);
+hipError_t launch_iq8_widen(const void* src, int64_t n_frames, int32_t N, int64_t src_stride, const IntIn& in, bool to_sc16,
+                            void* dst, hipStream_t stream);
 
-// Behind amcx_features18_c64_ws / _ex, amcx_features_c64_subset, amcx_features_sc16 and the contexts (ctx_features);
+// Behind amcx_features18_c64_ws / _ex, amcx_features_c64_subset, amcx_features_sc16, amcx_features_iq8 and the contexts (ctx_features);
 // feature_mask is AMCX_FEATURES_ALL for the 18-feature entries.  The order of the checks is part of the ABI
 // (tests/c_abi/abi_check.c).  sc16: the frames are sc16, not complex64 -- a kernel over sc16 where the size has one, otherwise
-// widened into the head of the workspace, the complex64 path with the rest of it.
+// widened into the head of the workspace, the complex64 path with the rest of it.  8-bit frames are ALWAYS widened into the
+// head of the workspace first: to sc16 where the size has an sc16 kernel, which then runs, to complex64 otherwise.
 int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_elems, float* out_dev,
                  int64_t out_row_stride, void* hip_stream, int32_t variant, uint32_t feature_mask, const Workspace& ws_in,
-                 const RingSource& rings, const Sc16In* sc16 = nullptr) {
+                 const RingSource& rings, const IntIn* sc16 = nullptr) {
   if (!valid_feature_mask(feature_mask)) return AMCX_EINVAL;
-  if (sc16 != nullptr && !(sc16->scale > 0.0f && sc16->scale <= 3.4028235e38f)) return AMCX_EINVAL;   // NaN, inf, <= 0
+  if (sc16 != nullptr && !int_scale_ok(sc16->scale)) return AMCX_EINVAL;
+  const bool iq8 = sc16 != nullptr && sc16->is_iq8();
+  // (amcx_features_iq8 alone: what can be said of its format and of the addresses it was given, before the no-op)
+  if (iq8 && (!iq8_format_ok(sc16->iq8) || (reinterpret_cast<uintptr_t>(iq_dev) & 1u) || (reinterpret_cast<uintptr_t>(ws_in.dev) & 7u)))
+    return AMCX_EINVAL;
   if (n_frames < 0 || row_stride_elems < frame_size || out_row_stride < AMCX_NUM_FEATURES) return AMCX_EINVAL;
   const int v = resolve_variant(frame_size, variant);
   if (v < 0) return v;
   if (n_frames == 0) return AMCX_OK;
   if (iq_dev == nullptr || out_dev == nullptr) return AMCX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(iq_dev) & (sc16 != nullptr ? 3u : 7u)) || (reinterpret_cast<uintptr_t>(out_dev) & 3u))
+  if ((reinterpret_cast<uintptr_t>(iq_dev) & (iq8 ? 1u : sc16 != nullptr ? 3u : 7u)) || (reinterpret_cast<uintptr_t>(out_dev) & 3u))
     return AMCX_EINVAL;
   const bool typed = sc16 != nullptr && sc16_typed(frame_size, v);
+  const bool widens = sc16 != nullptr && (iq8 || !typed);
   Workspace ws = ws_in;
-  if (sc16 != nullptr && !typed) {      // the widened copy takes the head of the caller's workspace
-    const int64_t head = sc16_widened_bytes(frame_size, n_frames);
+  if (widens) {      // the widened copy takes the head of the caller's workspace
+    const int64_t head = iq8 ? iq8_widened_bytes(frame_size, n_frames, typed) : sc16_widened_bytes(frame_size, n_frames);
     if (ws.own || ws.dev == nullptr || ws.bytes < head || (reinterpret_cast<uintptr_t>(ws.dev) & 7u)) return AMCX_EINVAL;
     ws.dev = static_cast<char*>(ws_in.dev) + head;
     ws.bytes = ws_in.bytes - head;
@@ -326,12 +345,20 @@ int run_features(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64
     frames.iq = nullptr;
     frames.iq16 = static_cast<const amcx::wave::sc16*>(iq_dev);
     frames.scale = sc16->scale;
-    if (!typed) {
+    if (widens) {
       if (on_another_device(ws_in.dev)) return AMCX_EINVAL;
-      float2* const wide = static_cast<float2*>(ws_in.dev);
-      if (const hipError_t e = launch_sc16_widen(frames, frame_size, wide); e != hipSuccess) return hip_fail(e, "sc16 widening kernel launch");
-      frames.iq = wide;
-      frames.iq16 = nullptr;
+      if (iq8) {
+        const hipError_t e = launch_iq8_widen(iq_dev, n_frames, frame_size, row_stride_elems, *sc16, typed, ws_in.dev, stream);
+        if (e != hipSuccess) return hip_fail(e, "8-bit widening kernel launch");
+        frames.iq16 = static_cast<const amcx::wave::sc16*>(ws_in.dev);       // (read only where typed)
+      } else {
+        const hipError_t e = launch_sc16_widen(frames, frame_size, static_cast<float2*>(ws_in.dev));
+        if (e != hipSuccess) return hip_fail(e, "sc16 widening kernel launch");
+      }
+      if (!typed) {
+        frames.iq = static_cast<const float2*>(ws_in.dev);
+        frames.iq16 = nullptr;
+      }
       frames.row_stride = frame_size;
     }
   }
@@ -385,6 +412,19 @@ hipError_t launch_sc16_widen(const amcx::Frames& frames, int32_t N, float2* dst)
   const int64_t grid = amcx::persistent_grid(frames.cus, 8, frames.n_frames * N, 256);
   return amcx::launch(amcx::amcx_sc16_to_c64_kernel, grid, 256, 0, frames.stream, frames.iq16, frames.n_frames, N,
                       frames.row_stride, frames.scale, dst);
+}
+
+// 8-bit rows -> packed sc16 / complex64 rows of N samples at dst (amcx_iq8_kernels.h): an item of 8 samples per thread
+hipError_t launch_iq8_widen(const void* src, int64_t n_frames, int32_t N, int64_t src_stride, const IntIn& in, bool to_sc16,
+                            void* dst, hipStream_t stream) {
+  const int64_t items = n_frames * ((N + amcx::kIq8Item - 1) / amcx::kIq8Item);
+  const int64_t grid = amcx::persistent_grid(cu_count(), 8, items, 256);
+  const uint8_t* const bytes = static_cast<const uint8_t*>(src);
+  if (to_sc16)
+    return amcx::launch(amcx::amcx_iq8_to_sc16_kernel, grid, 256, 0, stream, bytes, n_frames, N, src_stride, in.flip(),
+                        static_cast<short2*>(dst));
+  return amcx::launch(amcx::amcx_iq8_to_c64_kernel, grid, 256, 0, stream, bytes, n_frames, N, src_stride, in.flip(), in.scale,
+                      static_cast<float2*>(dst));
 }
 
 }  // namespace
@@ -509,7 +549,29 @@ int amcx_features_sc16(const void* iq_dev, int64_t n_frames, int32_t frame_size,
   ws.bytes = workspace_bytes;
   RingSource rings;
   rings.pool = true;
-  const Sc16In in{scale};
+  const IntIn in{scale};
+  return run_features(iq_dev, n_frames, frame_size, row_stride_samples, out_dev, out_row_stride, hip_stream, variant,
+                      feature_mask, ws, rings, &in);
+}
+
+int64_t amcx_features_iq8_workspace_bytes(int32_t frame_size, int64_t n_frames, int32_t variant) {
+  if (n_frames < 0) return -1;
+  const int v = resolve_variant(frame_size, variant);
+  if (v < 0) return -1;
+  if (n_frames == 0) return 0;
+  if (sc16_typed(frame_size, v)) return iq8_widened_bytes(frame_size, n_frames, true);
+  return iq8_widened_bytes(frame_size, n_frames, false) + amcx_features18_workspace_bytes(frame_size, n_frames, variant);
+}
+
+int amcx_features_iq8(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_samples, int32_t format,
+                      float scale, float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant,
+                      uint32_t feature_mask, void* workspace_dev, int64_t workspace_bytes) {
+  Workspace ws;
+  ws.dev = workspace_dev;
+  ws.bytes = workspace_bytes;
+  RingSource rings;
+  rings.pool = true;
+  const IntIn in{scale, format < 0 ? INT32_MAX : format};      // (a format below 0 is a bad format, not sc16)
   return run_features(iq_dev, n_frames, frame_size, row_stride_samples, out_dev, out_row_stride, hip_stream, variant,
                       feature_mask, ws, rings, &in);
 }
@@ -605,8 +667,16 @@ int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask) {
   return AMCX_OK;
 }
 
+int amcx_ctx_set_iq8_scale(amcx_ctx* ctx, float scale) {
+  if (ctx == nullptr || !int_scale_ok(scale)) return AMCX_EINVAL;
+  const amcx::CallGate::Token idle = ctx->gate.claim_idle();
+  if (!idle) return AMCX_EINVAL;
+  ctx->iq8_scale.store(scale, std::memory_order_release);
+  return AMCX_OK;
+}
+
 int amcx_ctx_set_sc16_scale(amcx_ctx* ctx, float scale) {
-  if (ctx == nullptr || !(scale > 0.0f && scale <= 3.4028235e38f)) return AMCX_EINVAL;
+  if (ctx == nullptr || !int_scale_ok(scale)) return AMCX_EINVAL;
   const amcx::CallGate::Token idle = ctx->gate.claim_idle();
   if (!idle) return AMCX_EINVAL;
   ctx->sc16_scale.store(scale, std::memory_order_release);
@@ -742,6 +812,14 @@ int amcx_ctx_features18_sc16_host(amcx_ctx* ctx, const void* iq_host, int64_t n_
   return ctx_run(ctx, iq_host, AMCX_SRC_SC16, n_frames, frame_size, row_stride_samples, out_host, out_row_stride, variant);
 }
 
+int amcx_ctx_features18_iq8_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames, int32_t frame_size,
+                                 int64_t row_stride_samples, int32_t format, float* out_host, int64_t out_row_stride,
+                                 int32_t variant) {
+  if (!iq8_format_ok(format)) return AMCX_EINVAL;
+  return ctx_run(ctx, iq_host, format == AMCX_IQ8_CU8 ? AMCX_SRC_CU8 : AMCX_SRC_CI8, n_frames, frame_size, row_stride_samples,
+                 out_host, out_row_stride, variant);
+}
+
 int amcx_ctx_features18_c128_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames, int32_t frame_size,
                                   int64_t row_stride_elems, float* out_host, int64_t out_row_stride,
                                   int32_t variant) {
@@ -795,6 +873,10 @@ int amcx_kernel_name_sc16(int32_t frame_size, int32_t variant, uint32_t feature_
     return amcx_kernel_name_subset(frame_size, variant, feature_mask, buf, buf_len);
   amcx::wave_kernel_name(frame_size, subset_plan(frame_size, v, feature_mask), buf, (size_t)buf_len, true);
   return AMCX_OK;
+}
+
+int amcx_kernel_name_iq8(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len) {
+  return amcx_kernel_name_sc16(frame_size, variant, feature_mask, buf, buf_len);     // widened to what that kernel reads
 }
 
 int64_t amcx_group_stats_workspace_bytes(int64_t n_groups, int64_t rows_per_group, int32_t n_cols) {

@@ -99,12 +99,13 @@ struct __attribute__((visibility("hidden"))) amcx_ctx {
   struct GraphKey {
     int64_t frames = 0; int32_t frame_size = 0, variant = 0; bool c128 = false, zero_copy = false;
     bool sc16 = false; float sc16_scale = 0.f;   // the element kind, and the scale the captured kernel node carries as an argument
+    int32_t iq8_kind = 0; float iq8_scale = 0.f; // likewise AMCX_SRC_CI8 / _CU8 (0: neither) and the 8-bit scale
     uint64_t generation = 0;             // buffers_generation at capture: every address a captured node holds
     uint32_t mask = AMCX_FEATURES_ALL;   // the feature mask the captured kernels were launched for
     bool operator==(const GraphKey& o) const {
       return frames == o.frames && frame_size == o.frame_size && variant == o.variant && c128 == o.c128 &&
              zero_copy == o.zero_copy && generation == o.generation && mask == o.mask && sc16 == o.sc16 &&
-             sc16_scale == o.sc16_scale;
+             sc16_scale == o.sc16_scale && iq8_kind == o.iq8_kind && iq8_scale == o.iq8_scale;
     }
   };
   struct SmallGraph { GraphExec exec; GraphKey key; };
@@ -129,6 +130,8 @@ struct __attribute__((visibility("hidden"))) amcx_ctx {
   std::atomic<uint32_t> feature_mask{AMCX_FEATURES_ALL};
   // amcx_ctx_set_sc16_scale: what an int16 component of an sc16 source is multiplied by (read once per call)
   std::atomic<float> sc16_scale{0x1p-15f};
+  // amcx_ctx_set_iq8_scale: the same for a component of an 8-bit source
+  std::atomic<float> iq8_scale{0x1p-7f};
 };
 
 namespace {
@@ -148,7 +151,7 @@ void ctx_reserve_ws(amcx_ctx* c, int32_t N, int64_t frames, int32_t variant) {
 
 // sc16: `rows` are sc16 and the size has a kernel that reads them (sc16_typed); otherwise complex64
 int ctx_features(amcx_ctx* c, const void* rows, int64_t frames, int32_t N, float* out, int32_t variant, uint32_t mask,
-                 const Sc16In* sc16 = nullptr) {
+                 const IntIn* sc16 = nullptr) {
   const int64_t want = amcx_features18_workspace_bytes(N, frames, variant);
   Workspace ws;
   if (want > 0 && c->d_ws.p != nullptr && c->d_ws.cap >= (size_t)want) { ws.dev = c->d_ws.p; ws.bytes = want; }
@@ -211,8 +214,9 @@ struct StridedCall {
   int v = 0;                       // the resolved variant
   uint32_t mask = AMCX_FEATURES_ALL;
   bool rows = false, inner_snr = false, as_c128 = false, threaded = false;
-  bool sc16 = false, sc16_typed = false;   // an sc16 source; a kernel of this size reads it (otherwise it is widened on the device)
-  Sc16In sc16_in = {1.0f};
+  bool sc16 = false, sc16_typed = false;   // an sc16 source; a kernel of this size reads sc16 (otherwise it is widened on the device)
+  bool iq8 = false;                        // an 8-bit source: widened on the device, to sc16 where sc16_typed, else to complex64
+  IntIn sc16_in = {1.0f};                  // the scale of either; of an 8-bit source its format too (the kernels see sc16 or complex64)
   size_t esz = 8;                  // staged bytes per element
   int64_t unit = 0, n_units = 0;   // staged elements per chunk unit (a frame / a plane), and how many
   size_t total_staged = 0, slot = 0, dslot = 0;
@@ -221,14 +225,15 @@ struct StridedCall {
   amcx_upload_stats st = {};
   double t_start = 0, t_loop = 0;
   // uploaded rows that no kernel reads as they lie: convert_rows_on_device
-  bool converts() const { return as_c128 || (sc16 && !sc16_typed); }
+  bool converts() const { return as_c128 || iq8 || (sc16 && !sc16_typed); }
 };
 
 // The rows of a device slot converted to complex64 into the room behind the slot: complex128 rounded, sc16 widened (the
-// frame sizes and variants that have no sc16 kernel).
+// frame sizes and variants that have no sc16 kernel); 8-bit rows widened to sc16 (sc16_typed) or to complex64.
 hipError_t convert_rows_on_device(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, const void** d_rows) {
   float2* const wide = reinterpret_cast<float2*>(dev + q.slot);
   *d_rows = wide;
+  if (q.iq8) return launch_iq8_widen(dev, frames, q.N, q.N, q.sc16_in, q.sc16_typed, wide, c->stream);
   if (q.as_c128)
     return amcx::launch(amcx::amcx_c128_to_c64_kernel, 2048, 256, 0, c->stream, reinterpret_cast<const double2*>(dev), frames,
                         q.N, q.N, wide);
@@ -238,13 +243,14 @@ hipError_t convert_rows_on_device(amcx_ctx* c, const StridedCall& q, char* dev, 
   return launch_sc16_widen(fr, q.N, wide);
 }
 
-// the feature kernels over the rows of one chunk at `dev`: complex64, complex128 (rounded first) or sc16 (read by the
-// kernel, or widened first)
+// the feature kernels over the rows of one chunk at `dev`: complex64, complex128 (rounded first), sc16 (read by the
+// kernel, or widened first) or 8-bit (widened first, to what the kernel reads)
 int chunk_features(amcx_ctx* c, const StridedCall& q, char* dev, int64_t frames, float* out, hipError_t* e) {
   const void* d_rows = dev;
   if (q.converts()) *e = convert_rows_on_device(c, q, dev, frames, &d_rows);
   if (*e != hipSuccess) return AMCX_OK;
-  return ctx_features(c, d_rows, frames, q.N, out, q.v, q.mask, q.sc16_typed ? &q.sc16_in : nullptr);
+  const IntIn as_sc16{q.sc16_in.scale};
+  return ctx_features(c, d_rows, frames, q.N, out, q.v, q.mask, q.sc16_typed ? &as_sc16 : nullptr);
 }
 
 // the result is in pinned memory: spread it over the caller's row stride, and close the call's statistics
@@ -292,6 +298,7 @@ bool run_small_graph(amcx_ctx* c, StridedCall& q, amcx::Pool& inline_pool, int* 
   key.generation = c->buffers_generation;
   key.mask = q.mask;
   key.sc16 = q.sc16; key.sc16_scale = q.sc16 ? q.sc16_in.scale : 0.f;
+  key.iq8_kind = q.iq8 ? q.src.kind : 0; key.iq8_scale = q.iq8 ? q.sc16_in.scale : 0.f;
   amcx_ctx::SmallGraph* g = nullptr;
   for (auto& cand : c->graphs)
     if (cand.exec.x && cand.key == key) g = &cand;
@@ -436,11 +443,11 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
   if (c == nullptr) return AMCX_EINVAL;
   const int32_t kind = src.kind;
   if (S < 0 || K < 0 || ss < 0 || sk < 0 || sn < 0 || out_row_stride < AMCX_NUM_FEATURES ||
-      kind < AMCX_SRC_C64 || kind > AMCX_SRC_SC16)
+      !amcx::src_kind_ok(kind))
     return AMCX_EINVAL;
   const int v = resolve_variant(N, variant);
   if (v < 0) return v;
-  if (kind == AMCX_SRC_SC16 && sn != 1) return AMCX_ENOTSUP;        // sc16: row layouts only
+  if (amcx::src_as_it_lies(kind) && sn != 1) return AMCX_ENOTSUP;   // sc16, ci8, cu8: row layouts only
   if (S == 0 || K == 0) return AMCX_OK;
   if (S > (int64_t(1) << 40) / K) return AMCX_EINVAL;
   if ((src.fd < 0 && src.re == nullptr) || (src.fd >= 0 && src.re_off < 0) || out_host == nullptr) return AMCX_EINVAL;
@@ -456,11 +463,13 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
   if (!rows && S > 0x7fffffffLL) return AMCX_EINVAL;             // the transposition kernel indexes the snr axis with an int
   const bool as_c128 = q.as_c128 = c->round_on_device && kind == AMCX_SRC_C128;
   q.sc16 = kind == AMCX_SRC_SC16;
-  q.sc16_typed = q.sc16 && sc16_typed(N, v);
-  q.sc16_in.scale = c->sc16_scale.load(std::memory_order_acquire);
+  q.iq8 = amcx::src_iq8(kind);
+  q.sc16_typed = (q.sc16 || q.iq8) && sc16_typed(N, v);
+  q.sc16_in.scale = (q.iq8 ? c->iq8_scale : c->sc16_scale).load(std::memory_order_acquire);
+  if (q.iq8) q.sc16_in.iq8 = kind == AMCX_SRC_CU8 ? AMCX_IQ8_CU8 : AMCX_IQ8_CI8;
   const size_t esz = q.esz = amcx::staged_elem_bytes(kind, as_c128);
   const size_t src_esz = kind == AMCX_SRC_C64 ? 8 : kind == AMCX_SRC_C128 ? 16 : kind == AMCX_SRC_F32_SPLIT ? 4
-                         : kind == AMCX_SRC_SC16 ? 4 : 8;
+                         : kind == AMCX_SRC_SC16 ? 4 : q.iq8 ? 2 : 8;
   const int64_t unit = q.unit = rows ? N : F;             // staged elements per chunk unit (a frame / a plane)
   const int64_t n_units = q.n_units = rows ? F : N;
   size_t slot = c->slot_bytes;
@@ -475,8 +484,8 @@ int ctx_run_strided(amcx_ctx* c, amcx::Source src, int64_t S, int64_t K,
   AMCX_HIP(guard.enter(c->device));
   q.t_start = wall_now();
   // rows of complex128 rounded on the device: each device slot is followed by room for its rounded rows
-  // ... and rows of sc16 widened on the device by room for twice their bytes
-  q.dslot = (rows && as_c128) ? slot + slot / 2 : (q.sc16 && !q.sc16_typed) ? 3 * slot : slot;
+  // ... rows of sc16 widened on the device by room for twice their bytes, 8-bit rows by twice (sc16) or four times (complex64)
+  q.dslot = (rows && as_c128) ? slot + slot / 2 : q.iq8 ? (q.sc16_typed ? 3 : 5) * slot : (q.sc16 && !q.sc16_typed) ? 3 * slot : slot;
   const bool threaded = q.threaded = total_staged >= (size_t(1) << 20);   // below 1 MiB a condition-variable wake costs more than the copy
   // an upload worth its staging threads runs on the device's own socket, this thread included: it stages, and the pinned
   // slots strided_prepare may allocate are placed where it runs (a per-frame call is not worth two affinity system calls)
@@ -511,7 +520,7 @@ int stage_any(amcx::Source src, int64_t n_snr, int64_t n_frames, int32_t frame_s
               int32_t* plane_major, int32_t* inner_snr_out) {
   const int32_t kind = src.kind;
   if (n_snr < 0 || n_frames < 0 || stride_snr < 0 || stride_frame < 0 || stride_sample < 0 || first_unit < 0 ||
-      n_units < 0 || threads < 0 || threads > 256 || kind < AMCX_SRC_C64 || kind > AMCX_SRC_SC16 ||
+      n_units < 0 || threads < 0 || threads > 256 || !amcx::src_kind_ok(kind) ||
       frame_size < AMCX_MIN_FRAME_SIZE || frame_size > AMCX_MAX_FRAME_SIZE)
     return AMCX_EINVAL;
   if (n_frames > 0 && n_snr > (int64_t(1) << 40) / n_frames) return AMCX_EINVAL;
@@ -519,7 +528,7 @@ int stage_any(amcx::Source src, int64_t n_snr, int64_t n_frames, int32_t frame_s
   amcx::RunMap map;
   if (!classify_layout(n_snr, n_frames, frame_size, stride_snr, stride_frame, stride_sample, &rows, &inner_snr, &map))
     return AMCX_ENOTSUP;
-  if (kind == AMCX_SRC_SC16 && !rows) return AMCX_ENOTSUP;         // sc16: row layouts only
+  if (amcx::src_as_it_lies(kind) && !rows) return AMCX_ENOTSUP;    // sc16, ci8, cu8: row layouts only
   if (plane_major) *plane_major = rows ? 0 : 1;
   if (inner_snr_out) *inner_snr_out = inner_snr ? 1 : 0;
   const int64_t F = n_snr * n_frames, unit = rows ? frame_size : F, total_units = rows ? F : frame_size;

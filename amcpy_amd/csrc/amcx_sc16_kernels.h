@@ -12,6 +12,8 @@
 // amcx_c128_to_c64_kernel changed the stream and group kernels).  An explicit specialisation is a plain function: defined
 // here, ahead of every other kernel of the library, these stand at the head of .text, and everything that was there before
 // keeps its distance to everything else -- tools/codeobj_gate.py --kernels, profiles/r10_sc16_codeobj_kernels.txt.
+// (Since ABI 10 amcx_iq8_kernels.h is included in front of this header, for the same reason: its two kernels shift these and
+//  everything behind them by the same amount.)
 #pragma once
 
 #include "amcx_short_kernel.h"

@@ -298,7 +298,12 @@ class CallGate {
 // container never exists in host memory outside the page cache.  First-touching the pages of a fresh mapping of a
 // 436 MB variable costs 30 ms however many threads fault, reading it into a fresh buffer as much again for the
 // buffer's own pages (profiles/r3_read_probe.txt); pread into 256 KB that every thread reuses has neither cost.
-enum { kSrcC64 = 0, kSrcC128 = 1, kSrcF32Split = 2, kSrcF64Split = 3, kSrcSc16 = 4 };
+// ... or 8-bit IQ (ci8 / cu8: interleaved pairs of bytes, 2 bytes per element), which goes up as it lies too and is widened by
+// the device (amcx_iq8_kernels.h).  Kinds 5, 6 and 7 are not kinds.
+enum { kSrcC64 = 0, kSrcC128 = 1, kSrcF32Split = 2, kSrcF64Split = 3, kSrcSc16 = 4, kSrcCi8 = 8, kSrcCu8 = 9 };
+inline bool src_kind_ok(int kind) { return (kind >= kSrcC64 && kind <= kSrcSc16) || kind == kSrcCi8 || kind == kSrcCu8; }
+inline bool src_iq8(int kind) { return kind == kSrcCi8 || kind == kSrcCu8; }
+inline bool src_as_it_lies(int kind) { return kind == kSrcSc16 || src_iq8(kind); }     // integer IQ: row layouts only
 struct Source {
   const char* re = nullptr;
   const char* im = nullptr;
@@ -321,8 +326,8 @@ struct Source {
     return s;
   }
 };
-// bytes of a STAGED element: sc16 and (as_c128) complex128 as they lie, everything else as complex64
-inline size_t staged_elem_bytes(int kind, bool as_c128) { return kind == kSrcSc16 ? 4 : as_c128 ? 16 : 8; }
+// bytes of a STAGED element: 8-bit IQ, sc16 and (as_c128) complex128 as they lie, everything else as complex64
+inline size_t staged_elem_bytes(int kind, bool as_c128) { return src_iq8(kind) ? 2 : kind == kSrcSc16 ? 4 : as_c128 ? 16 : 8; }
 
 // run i of the source starts at element (i / cnt_b) * stride_a + (i % cnt_b) * stride_b and is
 // run_len contiguous elements long; staged runs are packed back to back
@@ -430,6 +435,8 @@ inline void stage_elems_file(char* dst, const Source& s, int64_t off, int64_t co
     ok = read_exact(s.fd, dst, (size_t)count * 8, s.re_off + off * 8);
   } else if (s.kind == kSrcSc16) {
     ok = read_exact(s.fd, dst, (size_t)count * 4, s.re_off + off * 4);
+  } else if (src_iq8(s.kind)) {
+    ok = read_exact(s.fd, dst, (size_t)count * 2, s.re_off + off * 2);
   } else if (s.kind == kSrcC128 && as_c128) {
     ok = read_exact(s.fd, dst, (size_t)count * 16, s.re_off + off * 16);
   } else {
@@ -460,8 +467,8 @@ inline void stage_elems_file(char* dst, const Source& s, int64_t off, int64_t co
 }
 
 // count elements starting at source element `off` -> dst.  as_c128: complex128 copied as it is
-// (16 bytes per element, rounded later on the device); sc16 is copied as it is (4 bytes per element); otherwise dst is
-// complex64.
+// (16 bytes per element, rounded later on the device); sc16 and 8-bit IQ are copied as they are (4 / 2 bytes per element);
+// otherwise dst is complex64.
 inline void stage_elems(char* dst, const Source& s, int64_t off, int64_t count, bool as_c128) {
   if (s.fd >= 0) {
     stage_elems_file(dst, s, off, count, as_c128);
@@ -474,6 +481,10 @@ inline void stage_elems(char* dst, const Source& s, int64_t off, int64_t count, 
       return;
     case kSrcSc16:
       memcpy(dst, s.re + off * 4, (size_t)count * 4);
+      return;
+    case kSrcCi8:
+    case kSrcCu8:
+      memcpy(dst, s.re + off * 2, (size_t)count * 2);
       return;
     case kSrcC128:
       if (as_c128) memcpy(dst, s.re + off * 16, (size_t)count * 16);

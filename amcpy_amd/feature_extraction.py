@@ -60,7 +60,7 @@ import numpy as np
 
 from . import _lib
 from .config import Config
-from .features import SC16, _sc16_scale
+from .features import CI8, CU8, SC16, _iq8_scale, _sc16_scale
 from .frame_sources import (FileComplex, FrameColumns, FrameRows, SplitComplex, _native_source,  # noqa: F401 (re-exported)
                             as_frame_rows)
 from .sharding import FrameCut, collectives_forced, sharded_features
@@ -94,7 +94,8 @@ class HipEngine:
 
     ``frames`` is an (F, L) array / memmap -- complex, real, or sc16: (F, L) of ``features.SC16`` or (F, L, 2) int16
     (I, Q) pairs, which go up as they lie, 4 bytes per sample, and are multiplied by ``sc16_scale`` on the device
-    (amcx_features_sc16) -- or a :class:`FrameRows` over an (n_snr, n_frames, L)
+    (amcx_features_sc16), or 8-bit: (F, L) of ``features.CI8`` / ``CU8`` or (F, L, 2) int8 / uint8 pairs, 2 bytes per sample
+    over the link, widened by the device and multiplied by ``iq8_scale`` (amcx_features_iq8) -- or a :class:`FrameRows` over an (n_snr, n_frames, L)
     container in any memory order (ndarray or :class:`SplitComplex`).  The container is read where it
     lies by ``amcx_ctx_features18_strided_host``: host threads stage contiguous runs -- sample planes
     of a Fortran-ordered container, rows of a C-ordered one -- into three pinned slots (rounding
@@ -105,9 +106,10 @@ class HipEngine:
 
     def __init__(self, frame_size: int, device: Optional[int] = None, chunk_bytes: int = 32 << 20,
                  threads: Optional[int] = None, round_on_device: bool = False, feature_ids=None,
-                 sc16_scale: float = _lib.SC16_SCALE):
+                 sc16_scale: float = _lib.SC16_SCALE, iq8_scale: float = _lib.IQ8_SCALE):
         self.N = int(frame_size)
         self.sc16_scale = _sc16_scale(sc16_scale)
+        self.iq8_scale = _iq8_scale(iq8_scale)
         # feature_ids: None (all 18) or the ids to compute; the result stays (F, 18), NaN outside the set (KeyError for an
         # unknown id, here, before anything is launched)
         self.feature_ids = _feature_ids(feature_ids)
@@ -134,6 +136,7 @@ class HipEngine:
             self._ctx.configure(self.threads, self.chunk_bytes, int(self.round_on_device))
             self._ctx.set_feature_mask(self.mask)
             self._ctx.set_sc16_scale(self.sc16_scale)
+            self._ctx.set_iq8_scale(self.iq8_scale)
         return self._ctx
 
     def _run_block(self, src, base_elems: int, n_snr: int, n_frames: int, strides, out: np.ndarray) -> None:
@@ -181,8 +184,9 @@ class HipEngine:
         if src is None:
             # integer / half / exotic dtypes, negative or sub-element strides, no contiguous axis: one
             # C-ordered copy of the part that is used, then the row path
-            # (sc16 stays sc16: the library takes its row layouts only)
-            block = np.ascontiguousarray(rows.to_array(), dtype=rows.dtype if rows.dtype in (np.complex64, SC16) else np.complex128)
+            # (sc16 stays sc16, 8-bit stays 8-bit: the library takes their row layouts only)
+            block = np.ascontiguousarray(rows.to_array(),
+                                         dtype=rows.dtype if rows.dtype in (np.complex64, SC16, CI8, CU8) else np.complex128)
             rows = FrameRows(block[None], 1, F)
             src = _native_source(rows.parsed)
         ss, sk, sn = src[4]
@@ -252,11 +256,11 @@ class DeviceFanOut:
     contiguous run per sample plane of a column-major .mat), along the snr-major flattening otherwise.  Each device's
     rows land directly in the result; no process group and no gather are involved.  A device may be listed twice
     (two contexts on it: how the one-GPU test box exercises the path).  ``frames`` is whatever one :class:`HipEngine`
-    takes (``as_frame_rows``), a :class:`SplitComplex` and (F, L, 2) int16 pairs -- at the engines' default
-    ``sc16_scale`` -- included."""
+    takes (``as_frame_rows``), a :class:`SplitComplex`, (F, L, 2) int16 pairs -- at the engines' default
+    ``sc16_scale`` -- and int8 / uint8 pairs -- at ``iq8_scale`` -- included."""
 
     def __init__(self, frame_size: int, devices, threads: Optional[int] = None, chunk_bytes: int = 32 << 20,
-                 feature_ids=None):
+                 feature_ids=None, iq8_scale: float = _lib.IQ8_SCALE):
         devices = [int(d) for d in devices]
         feature_ids = _feature_ids(feature_ids)
         if feature_ids is not None:
@@ -276,7 +280,8 @@ class DeviceFanOut:
         self.engines = []
         try:
             for d, n in zip(devices, per_dev):
-                self.engines.append(HipEngine(frame_size, d, chunk_bytes, threads=n, feature_ids=feature_ids))
+                self.engines.append(HipEngine(frame_size, d, chunk_bytes, threads=n, feature_ids=feature_ids,
+                                              iq8_scale=iq8_scale))
         except BaseException:
             for e in self.engines:                          # a later device failed: the earlier ones' contexts, pinned slots
                 e.close()                                   # and staging threads are released, not leaked
@@ -395,11 +400,11 @@ def _features_of(engine, part: FrameRows) -> np.ndarray:
 
 
 def _file_stream_features(path, store, offset: int, n_frames: int, N: int, device, feature_ids,
-                          sc16_scale: float = _lib.SC16_SCALE) -> np.ndarray:
+                          sc16_scale: float = _lib.SC16_SCALE, iq8_scale: float = _lib.IQ8_SCALE) -> np.ndarray:
     """An interleaved stream ``offset`` bytes into a file: the staging threads read it themselves, part by part."""
     stream = FileComplex(path, store, (1, n_frames, N), offset, interleaved=True)
     try:
-        engine = HipEngine(N, device, feature_ids=feature_ids, sc16_scale=sc16_scale)
+        engine = HipEngine(N, device, feature_ids=feature_ids, sc16_scale=sc16_scale, iq8_scale=iq8_scale)
         return np.asarray(engine(FrameRows(stream, 1, n_frames)), dtype=np.float32)
     finally:
         stream.release()
@@ -437,12 +442,13 @@ def extract_modulation(parsed: np.ndarray, cfg: Config, *, compute=None, device:
 
 def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_frames: Optional[int] = None,
                        compute=None, device: Optional[int] = None, feature_ids=None, sample_format: str = "cf32",
-                       scale: float = _lib.SC16_SCALE) -> np.ndarray:
+                       scale: float = _lib.SC16_SCALE, scale8: float = _lib.IQ8_SCALE) -> np.ndarray:
     """Features of a raw complex64 sample stream on disk (GNU Radio file sink: interleaved
     float32 I/Q, no header -- what the reference's legacy reader takes with
     ``np.fromfile(..., dtype=np.complex64)`` and a fixed number of leading samples dropped,
     old/read_binary_stream.py:28,48,54-56), or, ``sample_format="sc16"``, of a stream of int16 (I, Q) pairs (UHD sc16,
-    SigMF ci16_le), each component multiplied by ``scale`` on the device.  The file is memory-mapped and cut into
+    SigMF ci16_le), each component multiplied by ``scale`` on the device, or, ``"ci8"`` / ``"cu8"``, of a stream of int8 /
+    uint8 (I, Q) pairs (HackRF / RTL-SDR recordings; cu8: zero level 128), each component multiplied by ``scale8``.  The file is memory-mapped and cut into
     consecutive ``frame_size``-sample frames (a trailing partial frame is dropped); the staging
     threads read the file slot by slot, so it never has to fit in host memory.
     Returns ``(n_frames, 18)`` float32 (``feature_ids``: only these, NaN in the other columns)."""
@@ -451,10 +457,11 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
         raise ValueError("frame_size must be >= 2")
     if skip_samples < 0:
         raise ValueError("skip_samples must be >= 0")
-    if sample_format not in ("cf32", "sc16"):
-        raise ValueError("sample_format is 'cf32' or 'sc16'")
-    store = np.dtype(np.complex64) if sample_format == "cf32" else SC16
-    scale = _sc16_scale(scale) if sample_format == "sc16" else _lib.SC16_SCALE      # (not read for cf32)
+    if sample_format not in _STREAM_STORES:
+        raise ValueError("sample_format is 'cf32', 'sc16', 'ci8' or 'cu8'")
+    store = _STREAM_STORES[sample_format]
+    scale = _sc16_scale(scale) if sample_format == "sc16" else _lib.SC16_SCALE      # (not read for the other formats)
+    scale8 = _iq8_scale(scale8) if store in (CI8, CU8) else _lib.IQ8_SCALE          # (likewise)
     n_total = Path(path).stat().st_size // store.itemsize - skip_samples
     n_frames = max(0, n_total // frame_size)
     if max_frames is not None:
@@ -463,15 +470,25 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
         return np.empty((0, 18), dtype=np.float32)
     if compute is None:
         return _file_stream_features(path, store, store.itemsize * skip_samples, n_frames, frame_size, device,
-                                     feature_ids, scale)
+                                     feature_ids, scale, scale8)
     frames = np.memmap(path, dtype=store, mode="r", offset=store.itemsize * skip_samples,
                        shape=(n_frames, frame_size))
-    if sample_format == "sc16":         # an injected engine (tests) sees the complex64 frames the device computes on
-        wide = np.empty(frames.shape, dtype=np.complex64)
-        wide.real = frames["i"].astype(np.float32) * np.float32(scale)
-        wide.imag = frames["q"].astype(np.float32) * np.float32(scale)
-        frames = wide
+    if sample_format != "cf32":         # an injected engine (tests) sees the complex64 frames the device computes on
+        frames = widen_integer_frames(frames, scale if sample_format == "sc16" else scale8)
     return np.asarray(compute(frames), dtype=np.float32)
+
+
+_STREAM_STORES = {"cf32": np.dtype(np.complex64), "sc16": SC16, "ci8": CI8, "cu8": CU8}
+
+
+def widen_integer_frames(frames: np.ndarray, scale: float) -> np.ndarray:
+    """(..., L) ``SC16`` / ``CI8`` / ``CU8`` samples -> the complex64 frames the device computes on (host copy: tests and
+    injected engines): complex64(float32(i) * scale, float32(q) * scale), cu8 components around the zero level 128."""
+    zero = 128 if frames.dtype == CU8 else 0
+    wide = np.empty(frames.shape, dtype=np.complex64)
+    for part, name in ((wide.real, "i"), (wide.imag, "q")):
+        part[...] = (frames[name].astype(np.int16) - zero).astype(np.float32) * np.float32(scale)
+    return wide
 
 
 def _pairs_as_complex(block: np.ndarray) -> np.ndarray:

@@ -10,7 +10,9 @@ the CPU.  The batch entry points the extraction driver uses are
 :func:`features18` (torch tensor in HBM -> torch tensor in HBM, asynchronous on
 the current stream) and :func:`features18_host` (numpy in, numpy out);
 :func:`features18_sc16` / :func:`features18_sc16_host` take 16-bit integer IQ
-(int16 (I, Q) pairs: UHD sc16, SigMF ci16_le) as it lies, half the bytes.
+(int16 (I, Q) pairs: UHD sc16, SigMF ci16_le) as it lies, half the bytes;
+:func:`features18_iq8` / :func:`features18_iq8_host` take 8-bit IQ (int8 pairs:
+ci8; uint8 pairs: cu8), a quarter of the bytes, which the device widens first.
 
 Feature ids (reference config.py:118-137): 1 gamma_max, 2 sigma_ap,
 3 sigma_dp, 4 sigma_aa, 5 sigma_af, 6 X, 7 X2, 8 mu42^a, 9 mu42^f,
@@ -208,6 +210,84 @@ def features18_sc16(iq, out=None, *, scale=_lib.SC16_SCALE, frame_size: int | No
     return out[..., :_lib.NUM_FEATURES]
 
 
+# one 8-bit sample as numpy sees it: two bytes, I then Q (include/amcx.h, amcx_features_iq8) -- int8 (ci8), or uint8
+# around the zero level 128 (cu8)
+CI8 = np.dtype([("i", "i1"), ("q", "i1")])
+CU8 = np.dtype([("i", "u1"), ("q", "u1")])
+
+
+def _iq8_scale(scale) -> float:
+    return _sc16_scale(scale)
+
+
+def iq8_view(pairs: np.ndarray) -> np.ndarray:
+    """(..., L, 2) int8 / uint8 -> (..., L) view of :data:`CI8` / :data:`CU8` samples (no copy).  TypeError for another
+    dtype or a last dimension that is not 2, ValueError for pairs that are not interleaved in memory."""
+    if not isinstance(pairs, np.ndarray) or pairs.dtype not in (np.int8, np.uint8) or pairs.ndim < 2 or pairs.shape[-1] != 2:
+        raise TypeError("expected an int8 or uint8 array whose last dimension is (I, Q)")
+    if pairs.strides[-1] != 1 or any(st % 2 for st in pairs.strides[:-1]) or (pairs.shape[-2] > 1 and pairs.strides[-2] != 2):
+        raise ValueError("(I, Q) byte pairs must be interleaved in memory")
+    return pairs.view(CI8 if pairs.dtype == np.int8 else CU8)[..., 0]
+
+
+def features18_iq8(iq, out=None, *, scale=_lib.IQ8_SCALE, frame_size: int | None = None, variant="auto",
+                   feature_ids=None, chunk_frames: int | None = None):
+    """The features of every frame of 8-bit IQ in GPU memory (amcx_features_iq8): widened on the device, then the
+    kernels :func:`features18_sc16` (128 ... 4096, wave / auto) or :func:`features18` run.
+
+    iq    : torch.int8 (ci8) or torch.uint8 (cu8: zero level 128) tensor on a GPU, shape (..., L, 2): I then Q,
+            interleaved, frames uniformly strided as for :func:`features18`.  The dtype picks the format.
+    scale : a finite float32 > 0.  The frame's value is complex64(float32(i) * scale, float32(q) * scale), i, q in
+            -128 ... 127, and the result is BIT-IDENTICAL to :func:`features18_sc16` on the int16 of the same values and to
+            :func:`features18` on that complex64 frame (same variant and feature_ids).
+    chunk_frames : frames per library call.  All calls share ONE workspace from torch's allocator, which holds the widened
+            copy of a chunk -- so a resident 8-bit arena need not find a multiple of its own size.  Default (None): all
+            frames in one call, the widened copy 2 x (sc16) or 4 x (complex64) the 8-bit frames: a default of 64 MiB
+            chunks measured x0.37 ... 0.51 of sc16's rate where one call reaches x0.72 ... 0.77
+            (profiles/r14_iq8_bench.json: calls of a few thousand frames are launch-bound).  Frames are independent: the
+            result does not depend on it, bit for bit.
+    out, frame_size, variant, feature_ids: as :func:`features18`."""
+    import torch
+
+    mask = _lib.FEATURES_ALL if feature_ids is None else _lib.feature_mask(feature_ids)
+    scale = _iq8_scale(scale)
+    if not isinstance(iq, torch.Tensor) or iq.dtype not in (torch.int8, torch.uint8):
+        raise TypeError("iq must be a torch.int8 (ci8) or torch.uint8 (cu8) tensor")
+    if iq.dim() < 2 or iq.shape[-1] != 2:
+        raise TypeError("iq must have shape (..., L, 2): the last dimension is (I, Q)")
+    L = iq.shape[-2]
+    if iq.stride(-1) != 1 or (L > 1 and iq.stride(-2) != 2):
+        raise ValueError("(I, Q) pairs must be interleaved in memory")
+    if not iq.is_cuda:
+        raise ValueError("iq must live in GPU memory (use features18_iq8_host for numpy input)")
+    N = _frame_size(frame_size, L)
+    if chunk_frames is not None and int(chunk_frames) < 1:
+        raise ValueError("chunk_frames must be at least 1")
+    lead, n_frames, row_stride = _flat_frames(iq, L, N, (2,))
+    out, oflat, out_stride = _out_frames(iq, out, lead, n_frames)
+    _lib.require_torch_runtime()
+    lib = _lib.load()
+    v = _variant(variant)
+    fmt = _lib.IQ8_CI8 if iq.dtype == torch.int8 else _lib.IQ8_CU8
+    if n_frames == 0:
+        _lib.check(lib.amcx_features_iq8(None, 0, N, row_stride, fmt, scale, None, out_stride, None, v, mask, None, 0))
+        return out[..., :_lib.NUM_FEATURES]
+    per_call = n_frames if chunk_frames is None else min(int(chunk_frames), n_frames)
+    with torch.cuda.device(iq.device):
+        cur = torch.cuda.current_stream(iq.device)
+        need = int(lib.amcx_features_iq8_workspace_bytes(N, per_call, v))
+        if need < 0:                       # the call itself says what is wrong with the arguments
+            need = 0
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=iq.device)
+        for f0 in range(0, n_frames, per_call):
+            n = min(per_call, n_frames - f0)
+            _lib.check(lib.amcx_features_iq8(iq.data_ptr() + 2 * f0 * row_stride, n, N, row_stride, fmt, scale,
+                                             oflat.data_ptr() + 4 * f0 * out_stride, out_stride, cur.cuda_stream, v, mask,
+                                             ws.data_ptr(), need))
+        ws.record_stream(cur)
+    return out[..., :_lib.NUM_FEATURES]
+
+
 _tls = threading.local()
 
 
@@ -289,3 +369,21 @@ def calculate_features(feature_ids: Iterable[int], signal, *, device: int = 0,
         return []
     row = features18_host(sig[None, :], device=device, variant=variant, feature_ids=ids)[0]
     return [float(row[fid - 1]) for fid in ids]
+
+
+def features18_iq8_host(frames: np.ndarray, *, scale=_lib.IQ8_SCALE, frame_size: int | None = None, device: int = 0,
+                        variant="auto", feature_ids=None) -> np.ndarray:
+    """numpy (..., L, 2) int8 (ci8) / uint8 (cu8) (I, Q) pairs -> numpy (..., 18) float32 via the GPU.  The samples cross
+    the link as they lie, 2 bytes each, and are widened by the device; the result equals :func:`features18_iq8`'s."""
+    mask = _mask(feature_ids)
+    scale = _iq8_scale(scale)
+    x = frames
+    if not isinstance(x, np.ndarray) or x.dtype not in (np.int8, np.uint8) or x.ndim < 2 or x.shape[-1] != 2:
+        raise TypeError("expected an int8 or uint8 array whose last dimension is (I, Q)")
+    L = x.shape[-2]
+    N = _frame_size(frame_size, L)
+    lead = x.shape[:-2]
+    x2 = np.ascontiguousarray(x.reshape(-1, L, 2))
+    ctx = _host_context(int(device))
+    ctx.set_iq8_scale(scale)
+    return _run_on_host_context(ctx, x2, N, lead, variant, mask)

@@ -10,7 +10,7 @@ from typing import Iterator, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .features import SC16, sc16_view
+from .features import CI8, CU8, SC16, iq8_view, sc16_view
 
 
 class SplitComplex:
@@ -40,8 +40,8 @@ class FileComplex:
     """A complex ``(n_snr, n_frames, L)`` container that is still in its FILE: the byte offsets of its real and
     imaginary arrays (column-major float32 / float64, how a level-5 .mat stores an uncompressed complex variable;
     ``imag_offset`` None: a real signal), or of ONE interleaved complex array (``interleaved=True``: a raw
-    complex64 / complex128 stream, or a stream of sc16 samples -- ``store_dtype=features.SC16``, int16 (I, Q) pairs --
-    C-ordered; with ``order="F"`` the {real, imag} compound dataset of a MATLAB -v7.3
+    complex64 / complex128 stream, or a stream of sc16 samples -- ``store_dtype=features.SC16``, int16 (I, Q) pairs -- or of
+    8-bit samples -- ``features.CI8`` / ``features.CU8`` -- C-ordered; with ``order="F"`` the {real, imag} compound dataset of a MATLAB -v7.3
     file, whose bytes are the column-major variable).  Nothing is read or mapped here: the engine's staging threads pread
     the file block by block on their way to the pinned slots (``amcx_ctx_features18_strided_file``), so the
     variable never exists in host memory outside the page cache.  Indexing (tests, injected engines) goes
@@ -54,8 +54,8 @@ class FileComplex:
         self.interleaved = bool(interleaved)
         if not self.interleaved and self.store not in (np.float32, np.float64):
             raise TypeError(f"split containers hold float32 or float64, got {self.store}")
-        if self.interleaved and self.store not in (np.complex64, np.complex128, SC16):
-            raise TypeError(f"interleaved containers hold complex64, complex128 or sc16, got {self.store}")
+        if self.interleaved and self.store not in (np.complex64, np.complex128, SC16, CI8, CU8):
+            raise TypeError(f"interleaved containers hold complex64, complex128, sc16, ci8 or cu8, got {self.store}")
         self.shape, self.ndim = tuple(int(x) for x in shape), len(shape)
         self.real_offset, self.imag_offset = int(real_offset), (None if imag_offset is None else int(imag_offset))
         self.dtype = self.store if self.interleaved else \
@@ -187,18 +187,19 @@ def _native_source(arr):
     copied first."""
     if isinstance(arr, FileComplex):
         if arr.interleaved:
-            kind = _lib.SRC_SC16 if arr.store == SC16 else _lib.SRC_C64 if arr.store == np.complex64 else _lib.SRC_C128
+            kind = {SC16: _lib.SRC_SC16, CI8: _lib.SRC_CI8, CU8: _lib.SRC_CU8,
+                    np.dtype(np.complex64): _lib.SRC_C64}.get(arr.store, _lib.SRC_C128)
         else:
             kind = _lib.SRC_F32_SPLIT if arr.store == np.float32 else _lib.SRC_F64_SPLIT
         return arr, arr.real_offset, arr.imag_offset, kind, list(arr.strides_elems), arr.store.itemsize, arr.fileno()
     if isinstance(arr, SplitComplex):
         re, im = arr.real, arr.imag
         kind = _lib.SRC_F32_SPLIT if re.dtype == np.float32 else _lib.SRC_F64_SPLIT
-    elif isinstance(arr, np.ndarray) and arr.dtype in (np.complex64, np.complex128, np.float32, np.float64, SC16):
+    elif isinstance(arr, np.ndarray) and arr.dtype in (np.complex64, np.complex128, np.float32, np.float64, SC16, CI8, CU8):
         re, im = arr, None
         kind = {np.dtype(np.complex64): _lib.SRC_C64, np.dtype(np.complex128): _lib.SRC_C128,
                 np.dtype(np.float32): _lib.SRC_F32_SPLIT, np.dtype(np.float64): _lib.SRC_F64_SPLIT,
-                SC16: _lib.SRC_SC16}[arr.dtype]
+                SC16: _lib.SRC_SC16, CI8: _lib.SRC_CI8, CU8: _lib.SRC_CU8}[arr.dtype]
     else:
         return None
     item = re.itemsize
@@ -209,12 +210,15 @@ def _native_source(arr):
 
 def as_frame_rows(frames) -> FrameRows:
     """What a caller may hand an engine, as :class:`FrameRows`, without a copy: one passes through; an (F, L) array,
-    memmap or :class:`SplitComplex` -- (F, L, 2) int16 pairs re-viewed as ``SC16`` -- becomes a one-snr container."""
+    memmap or :class:`SplitComplex` -- (F, L, 2) int16 / int8 / uint8 pairs re-viewed as ``SC16`` / ``CI8`` / ``CU8`` -- becomes
+    a one-snr container."""
     if isinstance(frames, FrameRows):
         return frames
     arr = frames if isinstance(frames, SplitComplex) else np.asarray(frames)
     if not isinstance(arr, SplitComplex) and arr.dtype == np.int16:
         arr = sc16_view(arr)                                 # (F, L, 2) int16 pairs -> (F, L) sc16 samples, no copy
+    elif not isinstance(arr, SplitComplex) and arr.dtype in (np.int8, np.uint8):
+        arr = iq8_view(arr)                                  # (F, L, 2) byte pairs -> (F, L) ci8 / cu8 samples, no copy
     if arr.ndim != 2:
         raise ValueError(f"expected (F, L) frames, got shape {arr.shape}")
     if isinstance(arr, SplitComplex):

@@ -7,6 +7,9 @@ The `extract` sub-command of the reference's CLI (src/amcpy/main.py:32,85-87,
 evaluation half of the reference's `eval` (nn_model.evaluate_by_snr) on the GPU: amcpy_amd/classifier.py.  The reference's dispatcher calls ``cmd_extract(cfg, args)``
 on a one-argument function (main.py:175 vs :85) and raises TypeError as
 written; this entry point takes the same defaults and simply works.
+`python -m amcpy_amd recording FILE --frame-size N [--format cf32|sc16|ci8|cu8] [--scale S] [--features ...] [--device D]
+[--out PATH]` takes ONE recording -- a SigMF recording (its meta file says the format: no --format), or a raw sample
+stream -- and writes `features` (F, 18) and `frame_start` (F,) into a .mat file: amcpy_amd/sigmf.py, extract_raw_stream.
 
 Several GPUs, ONE command (the reference's caller runs one command and the parallelism happens inside,
 feature_extraction.py:89-97): ``--devices 0,1,2,3`` / ``--devices all`` drives one engine per device from one
@@ -59,7 +62,53 @@ def build_parser() -> argparse.ArgumentParser:
     cl.add_argument("--num-frames", type=int, default=None)
     cl.add_argument("--snr-values", nargs="+", default=None, metavar="LABEL",
                     help="SNR labels of the container's first axis, in order (default: the 16 of SignalConfig)")
+    rec = sub.add_parser("recording", help="the features of one recording: a SigMF recording or a raw sample stream")
+    rec.add_argument("file", type=Path, metavar="FILE",
+                     help="X.sigmf-meta, X.sigmf-data or the stem X of a SigMF recording; or a raw stream (then --format)")
+    rec.add_argument("--frame-size", type=int, required=True)
+    rec.add_argument("--format", choices=("cf32", "sc16", "ci8", "cu8"), default=None,
+                     help="the samples of a raw stream (a SigMF recording names its own)")
+    rec.add_argument("--scale", type=float, default=None,
+                     help="what an integer component is multiplied by (default 2^-15 for sc16, 2^-7 for ci8 / cu8)")
+    rec.add_argument("--features", default="all", metavar="all|used|3,5,...", help="as for extract")
+    rec.add_argument("--device", type=int, default=None, help="GPU index (default: device 0)")
+    rec.add_argument("--out", type=Path, default=None, help="the .mat file to write (default: FILE's stem + _features.mat)")
     return ap
+
+
+def run_recording(args, compute=None) -> Path:
+    """The `recording` command: features and frame_start of args.file -> args.out (written aside, then renamed)."""
+    import numpy as np
+    from scipy.io import savemat
+    from . import sigmf
+    from .feature_extraction import extract_raw_stream
+    ids = resolve_features(args.features, Config())
+    path = Path(args.file)
+    if sigmf.is_sigmf(path):
+        if args.format is not None:
+            raise SystemExit("--format: a SigMF recording names its own datatype")
+        feats, frame_start = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
+                                                 compute=compute)
+        stem = Path(sigmf._stem(path))
+    else:
+        if args.format is None:
+            raise SystemExit(f"{path} is no SigMF recording: --format cf32|sc16|ci8|cu8 says what its samples are")
+        kw = {} if args.scale is None else {"scale" if args.format == "sc16" else "scale8": args.scale}
+        feats = extract_raw_stream(path, args.frame_size, device=args.device, feature_ids=ids, sample_format=args.format,
+                                   compute=compute, **kw)
+        frame_start = args.frame_size * np.arange(feats.shape[0], dtype=np.int64)
+        stem = path.with_suffix("")
+    out = Path(args.out) if args.out is not None else stem.with_name(stem.name + "_features.mat")
+    aside = out.with_name(out.name + f".{os.getpid()}.tmp")
+    try:
+        with open(aside, "wb") as fh:
+            savemat(fh, {"features": feats, "frame_start": frame_start})
+        os.replace(aside, out)
+    finally:
+        if aside.exists():
+            aside.unlink()
+    print(f"{out}: {feats.shape[0]} frames of {args.frame_size} samples")
+    return out
 
 
 def resolve_features(spec: str, cfg: Config):
@@ -171,6 +220,12 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
     (`python -m amcpy_amd`, amcpy_amd/__main__.py) asks for, a second faster.  An in-process caller keeps the
     default: the library then binds to torch's runtime and the tensor entry points stay usable afterwards."""
     args = build_parser().parse_args(argv)
+    if args.command == "recording":           # one file in, one file out: no project root, no torch
+        from . import _lib
+        if skip_torch:
+            _lib.load(skip_torch=True)
+        run_recording(args)
+        return 0
     cfg = Config() if args.root is None else Config(paths=Paths(root=args.root))
     sig = cfg.signals
     if args.frame_size is not None:

@@ -92,8 +92,11 @@ extern "C" {
  * 8 = classification on the device: AMCX_ACT_*, amcx_mlp_params_floats, amcx_mlp_classify_f32, amcx_mlp_kernel_name;
  * 9 = frames of 16-bit integer IQ (sc16): amcx_features_sc16, amcx_features_sc16_workspace_bytes, amcx_kernel_name_sc16,
  * AMCX_SRC_SC16 for the strided host / file entries and amcx_stage_host / _file, amcx_ctx_set_sc16_scale,
- * amcx_ctx_features18_sc16_host. */
-#define AMCX_ABI_VERSION 9
+ * amcx_ctx_features18_sc16_host;
+ * 10 = frames of 8-bit IQ (ci8, cu8), widened on the device: AMCX_IQ8_*, amcx_features_iq8, amcx_features_iq8_workspace_bytes,
+ * amcx_kernel_name_iq8, AMCX_SRC_CI8 / AMCX_SRC_CU8 for the strided host / file entries and amcx_stage_host / _file,
+ * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host. */
+#define AMCX_ABI_VERSION 10
 #define AMCX_NUM_FEATURES 18
 
 /* FEATURE MASKS (ABI 7): bit j - 1 stands for feature id j (1 gamma_max ... 18 |C63|).  The reference's default selection,
@@ -233,6 +236,37 @@ int amcx_features_sc16(const void* iq_dev, int64_t n_frames, int32_t frame_size,
                        void* workspace_dev, int64_t workspace_bytes);
 
 /*
+ * ABI 10.  Frames of 8-bit IQ, what the cheap receivers write (cu8: the RTL-SDR family; ci8: HackRF- and Airspy-class tools,
+ * SigMF ci8 / cu8): a quarter of the bytes of complex64.  No feature kernel reads 8-bit samples: the device widens the
+ * frames first, with one small kernel, and runs the kernels that exist.
+ *   - A sample is two bytes, I then Q.  AMCX_IQ8_CI8: the bytes are int8.  AMCX_IQ8_CU8: the bytes are uint8 around the zero
+ *     level 128, a component is (int8)(byte ^ 0x80), i.e. byte - 128.  (The other convention for cu8, a zero level of 127.5,
+ *     is not offered: it has no integer form, and a caller who wants it subtracts 0.5 * scale from the mean himself.)  Any
+ *     other format is AMCX_EINVAL.  row_stride_samples counts samples of 2 bytes, any value >= frame_size; only the first
+ *     frame_size samples of a row are read.  iq_dev must be 2-byte aligned.
+ *   - The frame's value is complex64((float)i * scale, (float)q * scale), i and q in -128 ... 127: ONE float32 multiplication
+ *     per component.  scale follows amcx_features_sc16's rules (finite float32 > 0, otherwise AMCX_EINVAL, checked before a
+ *     device is looked for); 2^-7 maps the range onto [-1, 1).
+ *   - The widening to int16 is sign extension, so the features are amcx_features_sc16's on (int16)x with the same scale,
+ *     variant and feature_mask BIT FOR BIT, and thereby amcx_features_c64_subset's on the widened complex64 frame, every
+ *     slow path and the NaN of the columns not asked for included.
+ *   - A workspace is ALWAYS needed (for n_frames > 0), 8-byte aligned: its head takes the widened copy -- sc16,
+ *     4 * frame_size * n_frames bytes rounded up to 256, where amcx_features_sc16 runs an sc16 kernel (128 ... 4096 with
+ *     AMCX_VARIANT_WAVE / AUTO); complex64, 8 * frame_size * n_frames rounded up to 256, everywhere else -- and the rest is
+ *     handed on as amcx_features_sc16 hands it on.  amcx_features_iq8_workspace_bytes says how much: the head, plus
+ *     amcx_features18_workspace_bytes where the copy is complex64; 0 for n_frames == 0, -1 for arguments amcx_features_iq8
+ *     refuses.  No workspace, one smaller than the head, or one that is not 8-byte aligned is AMCX_EINVAL.  A caller whose
+ *     8-bit data outlives one call and who wants the resident rate keeps the widened sc16 instead (README).
+ * Asynchronous on the caller's stream, allocates nothing, and can be captured into a graph wherever amcx_features_sc16 can.
+ */
+#define AMCX_IQ8_CI8 0
+#define AMCX_IQ8_CU8 1
+int64_t amcx_features_iq8_workspace_bytes(int32_t frame_size, int64_t n_frames, int32_t variant);
+int amcx_features_iq8(const void* iq_dev, int64_t n_frames, int32_t frame_size, int64_t row_stride_samples, int32_t format,
+                      float scale, float* out_dev, int64_t out_row_stride, void* hip_stream, int32_t variant,
+                      uint32_t feature_mask, void* workspace_dev, int64_t workspace_bytes);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -287,6 +321,15 @@ int amcx_ctx_features18_sc16_host(amcx_ctx* ctx, const void* iq_host, int64_t n_
 /* ABI 9: what every later sc16 call of this context multiplies an int16 component by (default 2^-15).  AMCX_EINVAL for a
  * scale that is NaN, infinite, 0 or negative, or while a call is running on the context. */
 int amcx_ctx_set_sc16_scale(amcx_ctx* ctx, float scale);
+/* ABI 10: rows of 8-bit IQ (amcx_features_iq8: format AMCX_IQ8_CI8 / AMCX_IQ8_CU8, row_stride_samples in samples of 2 bytes)
+ * in host memory.  They go over the link as they lie, 2 bytes per sample; the device widens them and runs what
+ * amcx_features_iq8 runs, with the context's 8-bit scale (amcx_ctx_set_iq8_scale) and feature mask. */
+int amcx_ctx_features18_iq8_host(amcx_ctx* ctx, const void* iq_host, int64_t n_frames, int32_t frame_size,
+                                 int64_t row_stride_samples, int32_t format, float* out_host, int64_t out_row_stride,
+                                 int32_t variant);
+/* ABI 10: what every later 8-bit call of this context multiplies a component by (default 2^-7); rules as
+ * amcx_ctx_set_sc16_scale. */
+int amcx_ctx_set_iq8_scale(amcx_ctx* ctx, float scale);
 
 /*
  * Name of the kernel `variant` resolves to for this frame_size (as it shows in
@@ -303,6 +346,9 @@ int amcx_kernel_name_subset(int32_t frame_size, int32_t variant, uint32_t featur
 /* ABI 9: the same for amcx_features_sc16 -- an sc16 kernel at 128 ... 4096 (WAVE / AUTO), otherwise the complex64 kernel
  * that runs on the widened copy. */
 int amcx_kernel_name_sc16(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len);
+/* ABI 10: the same for amcx_features_iq8, the FEATURE kernel that runs behind amcx_iq8_to_sc16_kernel /
+ * amcx_iq8_to_c64_kernel: amcx_kernel_name_sc16's answer. */
+int amcx_kernel_name_iq8(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len);
 
 /* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
  * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
@@ -325,6 +371,10 @@ int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask);
  *             `im` is ignored; the value of a sample is amcx_features_sc16's with the context's scale
  *             (amcx_ctx_set_sc16_scale).  Staged and uploaded as it lies (upload_stats.pcie_bytes = 4 bytes per
  *             sample).  Row layouts only (stride_sample == 1): a plane-major layout is AMCX_ENOTSUP.
+ *             AMCX_SRC_CI8 / AMCX_SRC_CU8 (ABI 10): `re` points at interleaved (I, Q) bytes, an element is one sample of 2
+ *             bytes, `im` is ignored; the value of a sample is amcx_features_iq8's with the context's 8-bit scale
+ *             (amcx_ctx_set_iq8_scale).  Staged and uploaded as it lies (upload_stats.pcie_bytes = 2 bytes per sample),
+ *             widened by the device.  Row layouts only, as sc16.  Kinds 5, 6 and 7 are no kinds: AMCX_EINVAL.
  *   strides   in ELEMENTS of the source (complex elements for the interleaved kinds), all >= 0.
  *             One of them must be 1:
  *               stride_sample == 1 (C order)        rows go up in chunks of whole frames and the
@@ -345,6 +395,8 @@ int amcx_ctx_set_feature_mask(amcx_ctx* ctx, uint32_t feature_mask);
 #define AMCX_SRC_F32_SPLIT 2
 #define AMCX_SRC_F64_SPLIT 3
 #define AMCX_SRC_SC16 4
+#define AMCX_SRC_CI8 8      /* (5, 6 and 7 stay AMCX_EINVAL) */
+#define AMCX_SRC_CU8 9
 int amcx_ctx_features18_strided_host(amcx_ctx* ctx, const void* re, const void* im, int32_t kind,
                                      int64_t n_snr, int64_t n_frames, int32_t frame_size,
                                      int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
@@ -357,7 +409,7 @@ int amcx_ctx_features18_strided_host(amcx_ctx* ctx, const void* re, const void* 
  * dst[unit][position], position order as amcx_pack_planes_c64's inner_snr says); *plane_major and
  * *inner_snr report which (either may be NULL).  For callers that run their own copy engine -- and
  * how the staging and rounding logic is tested where there is no GPU.  AMCX_SRC_SC16: rows only, staged as packed sc16
- * (4 bytes per sample, dst_bytes accordingly).
+ * (4 bytes per sample, dst_bytes accordingly); AMCX_SRC_CI8 / _CU8 likewise, 2 bytes per sample.
  */
 int amcx_stage_host(const void* re, const void* im, int32_t kind, int64_t n_snr, int64_t n_frames,
                     int32_t frame_size, int64_t stride_snr, int64_t stride_frame, int64_t stride_sample,
