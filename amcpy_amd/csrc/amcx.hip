@@ -13,7 +13,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_iq8_kernels.h"      // FIRST, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
+#include "amcx_ddc_kernel.h"       // FIRST, then the 8-bit widening kernels, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
+#include "amcx_iq8_kernels.h"
 #include "amcx_sc16_kernels.h"
 #include "amcx_block_kernel.h"
 #include "amcx_stream_kernel.h"
@@ -460,6 +461,12 @@ bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
   return true;
 }
 
+// resident workgroups per CU of a down-converter launch (amcx_ddc_kernel.h): what its LDS leaves room for, eight at most
+int ddc_wgs_per_cu(int n_taps, int decim) {
+  const int fit = (int)((size_t)(160 * 1024) / amcx::ddc_lds_bytes(n_taps, decim));
+  return fit < 1 ? 1 : fit > 8 ? 8 : fit;
+}
+
 // the columns a post-processing entry selects (n_sel in range already); false: one of them is not a column of the input
 bool make_select_cols(const int32_t* cols_host, int32_t n_sel, int32_t n_cols, amcx::SelectCols* sel) {
   sel->n = n_sel;
@@ -877,6 +884,59 @@ int amcx_kernel_name_sc16(int32_t frame_size, int32_t variant, uint32_t feature_
 
 int amcx_kernel_name_iq8(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len) {
   return amcx_kernel_name_sc16(frame_size, variant, feature_mask, buf, buf_len);     // widened to what that kernel reads
+}
+
+// ---- the digital down-converter (amcx_ddc_kernel.h) ------------------------------------------------------------------
+int64_t amcx_tune_decimate_out_samples(int64_t n_samples, int32_t n_taps, int32_t decim) {
+  if (n_taps < 1 || n_taps > amcx::kDdcMaxTaps || decim < 1 || decim > amcx::kDdcMaxDecim) return -1;
+  if (n_samples < 0 || n_samples >= (int64_t(1) << 40)) return -1;
+  return n_samples < n_taps ? 0 : (n_samples - n_taps) / decim + 1;
+}
+
+int amcx_tune_decimate_plan(int32_t n_taps, int32_t decim, int32_t* tile_outputs, int32_t* max_workgroups) {
+  if (amcx_tune_decimate_out_samples(0, n_taps, decim) < 0) return AMCX_EINVAL;
+  if (tile_outputs != nullptr) *tile_outputs = amcx::ddc_tile_outputs(n_taps, decim);
+  if (max_workgroups != nullptr) *max_workgroups = cu_count() * ddc_wgs_per_cu(n_taps, decim);
+  return AMCX_OK;
+}
+
+int amcx_tune_decimate(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0,
+                       uint64_t phase_step, const float* taps_dev, int32_t n_taps, int32_t decim, void* out_c64_dev,
+                       int64_t out_capacity_samples, void* hip_stream) {
+  const bool integer = src_kind == AMCX_SRC_SC16 || src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8;
+  if (src_kind != AMCX_SRC_C64 && !integer) return AMCX_EINVAL;
+  if (integer && !int_scale_ok(scale)) return AMCX_EINVAL;
+  const int64_t M = amcx_tune_decimate_out_samples(n_samples, n_taps, decim);
+  if (M < 0 || out_capacity_samples < M) return AMCX_EINVAL;
+  if (M == 0) return AMCX_OK;
+  if (src_dev == nullptr || taps_dev == nullptr || out_c64_dev == nullptr) return AMCX_EINVAL;
+  const unsigned src_align = src_kind == AMCX_SRC_C64 ? 7u : src_kind == AMCX_SRC_SC16 ? 3u : 1u;
+  if ((reinterpret_cast<uintptr_t>(src_dev) & src_align) || (reinterpret_cast<uintptr_t>(taps_dev) & 3u) ||
+      (reinterpret_cast<uintptr_t>(out_c64_dev) & 7u))
+    return AMCX_EINVAL;
+  if (on_another_device(src_dev) || on_another_device(taps_dev) || on_another_device(out_c64_dev)) return AMCX_EINVAL;
+  const int tile = amcx::ddc_tile_outputs(n_taps, decim);
+  const int64_t n_tiles = (M + tile - 1) / tile;
+  const int64_t grid = amcx::persistent_grid(cu_count(), ddc_wgs_per_cu(n_taps, decim), n_tiles, 1);
+  const auto kern = src_kind == AMCX_SRC_C64 ? amcx::amcx_ddc_c64_kernel
+                    : src_kind == AMCX_SRC_SC16 ? amcx::amcx_ddc_sc16_kernel : amcx::amcx_ddc_iq8_kernel;
+  const unsigned flip4 = src_kind == AMCX_SRC_CU8 ? 0x80808080u : 0u;
+  const hipError_t e = amcx::launch(kern, grid, amcx::kDdcThreads, amcx::ddc_lds_bytes(n_taps, decim),
+                                    static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), integer ? scale : 1.0f,
+                                    flip4, (unsigned long long)phase0, (unsigned long long)phase_step, taps_dev, n_taps, decim,
+                                    static_cast<float2*>(out_c64_dev), (long long)M, tile, (long long)n_tiles);
+  if (e != hipSuccess) return hip_fail(e, "down-converter kernel launch");
+  return AMCX_OK;
+}
+
+int amcx_kernel_name_ddc(int32_t src_kind, char* buf, int32_t buf_len) {
+  if (buf == nullptr || buf_len <= 0) return AMCX_EINVAL;
+  const char* const name = src_kind == AMCX_SRC_C64    ? "amcx_ddc_c64_kernel"
+                           : src_kind == AMCX_SRC_SC16 ? "amcx_ddc_sc16_kernel"
+                           : src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8 ? "amcx_ddc_iq8_kernel" : nullptr;
+  if (name == nullptr) return AMCX_EINVAL;
+  snprintf(buf, (size_t)buf_len, "%s", name);
+  return AMCX_OK;
 }
 
 int64_t amcx_group_stats_workspace_bytes(int64_t n_groups, int64_t rows_per_group, int32_t n_cols) {

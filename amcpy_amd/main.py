@@ -8,8 +8,10 @@ evaluation half of the reference's `eval` (nn_model.evaluate_by_snr) on the GPU:
 on a one-argument function (main.py:175 vs :85) and raises TypeError as
 written; this entry point takes the same defaults and simply works.
 `python -m amcpy_amd recording FILE --frame-size N [--format cf32|sc16|ci8|cu8] [--scale S] [--features ...] [--device D]
-[--out PATH]` takes ONE recording -- a SigMF recording (its meta file says the format: no --format), or a raw sample
+[--out PATH] [--shift-hz F --decimate D [--taps T] | --annotation K [--oversample R]]` takes ONE recording -- a SigMF recording (its meta file says the format: no --format), or a raw sample
 stream -- and writes `features` (F, 18) and `frame_start` (F,) into a .mat file: amcpy_amd/sigmf.py, extract_raw_stream.
+The tuning flags (SigMF only) put the device's down-converter in front: the emitter moved to 0 Hz, low-passed and decimated
+(amcpy_amd/ddc.py; sigmf.extract_sigmf, tune=).
 
 Several GPUs, ONE command (the reference's caller runs one command and the parallelism happens inside,
 feature_extraction.py:89-97): ``--devices 0,1,2,3`` / ``--devices all`` drives one engine per device from one
@@ -73,10 +75,36 @@ def build_parser() -> argparse.ArgumentParser:
     rec.add_argument("--features", default="all", metavar="all|used|3,5,...", help="as for extract")
     rec.add_argument("--device", type=int, default=None, help="GPU index (default: device 0)")
     rec.add_argument("--out", type=Path, default=None, help="the .mat file to write (default: FILE's stem + _features.mat)")
+    rec.add_argument("--shift-hz", type=float, default=None, metavar="F",
+                     help="tune first: add F Hz to every frequency (an emitter at +f wants -f); needs --decimate")
+    rec.add_argument("--decimate", type=int, default=None, metavar="D", help="... low-pass and keep every D-th sample")
+    rec.add_argument("--taps", type=int, default=None, metavar="T", help="taps of the low-pass (default 16 D + 1)")
+    rec.add_argument("--annotation", type=int, default=None, metavar="K",
+                     help="tune to the band of the recording's annotation K instead (its frequency edges)")
+    rec.add_argument("--oversample", type=float, default=None, metavar="R",
+                     help="with --annotation: decimate to R times the annotation's bandwidth (default 2)")
     return ap
 
 
-def run_recording(args, compute=None) -> Path:
+def recording_tune(args):
+    """The `recording` command's tuning flags -> the ``tune`` of sigmf.extract_sigmf, or None.  The two forms exclude each
+    other, and each flag needs the one it belongs to."""
+    manual = args.shift_hz is not None or args.decimate is not None or args.taps is not None
+    by_annotation = args.annotation is not None or args.oversample is not None
+    if manual and by_annotation:
+        raise SystemExit("--shift-hz / --decimate / --taps and --annotation / --oversample exclude each other")
+    if manual:
+        if args.decimate is None:
+            raise SystemExit("--shift-hz and --taps need --decimate")
+        return {"shift_hz": 0.0 if args.shift_hz is None else args.shift_hz, "decimate": args.decimate, "taps": args.taps}
+    if by_annotation:
+        if args.annotation is None:
+            raise SystemExit("--oversample needs --annotation")
+        return {"annotation": args.annotation, "oversample": 2.0 if args.oversample is None else args.oversample}
+    return None
+
+
+def run_recording(args, compute=None, tune_compute=None) -> Path:
     """The `recording` command: features and frame_start of args.file -> args.out (written aside, then renamed)."""
     import numpy as np
     from scipy.io import savemat
@@ -84,13 +112,16 @@ def run_recording(args, compute=None) -> Path:
     from .feature_extraction import extract_raw_stream
     ids = resolve_features(args.features, Config())
     path = Path(args.file)
+    tune = recording_tune(args)
     if sigmf.is_sigmf(path):
         if args.format is not None:
             raise SystemExit("--format: a SigMF recording names its own datatype")
         feats, frame_start = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
-                                                 compute=compute)
+                                                 compute=compute, tune=tune, tune_compute=tune_compute)
         stem = Path(sigmf._stem(path))
     else:
+        if tune is not None:
+            raise SystemExit("the tuning flags need a SigMF recording (its meta file holds the sample rate)")
         if args.format is None:
             raise SystemExit(f"{path} is no SigMF recording: --format cf32|sc16|ci8|cu8 says what its samples are")
         kw = {} if args.scale is None else {"scale" if args.format == "sc16" else "scale8": args.scale}
@@ -220,9 +251,9 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
     (`python -m amcpy_amd`, amcpy_amd/__main__.py) asks for, a second faster.  An in-process caller keeps the
     default: the library then binds to torch's runtime and the tensor entry points stay usable afterwards."""
     args = build_parser().parse_args(argv)
-    if args.command == "recording":           # one file in, one file out: no project root, no torch
+    if args.command == "recording":           # one file in, one file out: no project root, no torch (unless it tunes)
         from . import _lib
-        if skip_torch:
+        if skip_torch and recording_tune(args) is None:
             _lib.load(skip_torch=True)
         run_recording(args)
         return 0

@@ -8,6 +8,9 @@ Written from the field names of the SigMF specification with the stdlib ``json``
     captures core:sample_start    index of the segment's first sample, counted over the samples of the data file
              core:header_bytes    bytes in front of the segment's first sample that are no samples
 
+With ``tune=`` (:func:`extract_sigmf`) also ``core:sample_rate``, a capture's ``core:frequency`` and an annotation's
+``core:sample_start`` / ``core:freq_lower_edge`` / ``core:freq_upper_edge``: :func:`tune_from_annotation`.
+
 A capture segment runs to the next one's ``core:sample_start`` (the last: to the end of the file).  Frames never straddle a
 segment boundary: each segment is cut into consecutive frames and its partial tail is dropped, since whatever made the tool
 begin a new capture -- a retune, a gap, a header -- lies between the two.  Archives (``.sigmf`` tar files), several channels,
@@ -89,8 +92,117 @@ def read_meta(path) -> dict:
             "scale": scale, "segments": segments}
 
 
+def tune_from_annotation(meta: dict, k: int, oversample=2.0) -> tuple:
+    """Where annotation ``k`` of the parsed meta file says its emitter is -> ``(shift_hz, decimate)`` for ``tune=``.
+
+    The annotation's band ``core:freq_lower_edge ... core:freq_upper_edge`` is set against the ``core:frequency`` of the
+    capture that holds its ``core:sample_start`` (the last capture that starts at or before it) and the recording's
+    ``core:sample_rate`` fs:  ``shift_hz = capture frequency - band centre`` (what moves the centre to 0 Hz) and
+    ``decimate = max(1, floor(fs / (oversample * bandwidth)))``, 4096 at most.  Pure arithmetic on the JSON; ValueError
+    names the field that is missing."""
+    glob = meta.get("global") or {}
+    anns = meta.get("annotations") or []
+    if not 0 <= int(k) < len(anns):
+        raise ValueError(f"annotation {k}: the recording has {len(anns)}")
+    ann = anns[int(k)]
+    for key in ("core:freq_lower_edge", "core:freq_upper_edge"):
+        if key not in ann:
+            raise ValueError(f"annotation {k} has no {key}")
+    if "core:sample_rate" not in glob:
+        raise ValueError("no global core:sample_rate")
+    lo, hi, fs = float(ann["core:freq_lower_edge"]), float(ann["core:freq_upper_edge"]), float(glob["core:sample_rate"])
+    r = float(oversample)
+    if not (hi > lo and fs > 0.0 and r > 0.0):
+        raise ValueError(f"annotation {k}: needs freq_upper_edge > freq_lower_edge, sample_rate > 0 and oversample > 0")
+    at = int(ann.get("core:sample_start", 0))
+    held = [c for c in (meta.get("captures") or []) if int(c.get("core:sample_start", 0)) <= at]
+    if not held or "core:frequency" not in held[-1]:
+        raise ValueError(f"annotation {k}: the capture that holds sample {at} has no core:frequency")
+    shift_hz = float(held[-1]["core:frequency"]) - (lo + hi) / 2.0
+    return shift_hz, int(min(4096, max(1, np.floor(fs / (r * (hi - lo))))))
+
+
+def resolve_tune(meta: dict, tune: dict) -> tuple:
+    """``tune`` of :func:`extract_sigmf` -> ``(shift in cycles per sample, decimate, float32 taps)``."""
+    from fractions import Fraction
+    from .ddc import design_lowpass
+    known = {"shift_hz", "decimate", "taps", "annotation", "oversample"}
+    if not isinstance(tune, dict) or set(tune) - known:
+        raise ValueError(f"tune: a dict of {sorted(known)}")
+    if "annotation" in tune:
+        if "shift_hz" in tune or "decimate" in tune:
+            raise ValueError("tune: either annotation (and oversample) or shift_hz and decimate")
+        shift_hz, D = tune_from_annotation(meta, tune["annotation"], tune.get("oversample", 2.0))
+    else:
+        if "decimate" not in tune or "oversample" in tune:
+            raise ValueError("tune: either annotation (and oversample) or shift_hz and decimate")
+        shift_hz, D = float(tune.get("shift_hz", 0.0)), int(tune["decimate"])
+    shift = Fraction(0)
+    if shift_hz != 0.0:
+        fs = (meta.get("global") or {}).get("core:sample_rate")
+        if fs is None or float(fs) <= 0.0:
+            raise ValueError("tune: a shift in Hz needs the global core:sample_rate")
+        shift = Fraction(shift_hz) / Fraction(float(fs))
+    taps = tune.get("taps")
+    if taps is None or isinstance(taps, (int, np.integer)):
+        taps = design_lowpass(D, taps)
+    return shift, D, np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+
+
+# the plain numpy dtype and trailing shape of one stored sample, for the tuned path's chunks
+_PLAIN = {"cf32": (np.dtype("<c8"), ()), "sc16": (np.dtype("<i2"), (2,)), "ci8": (np.dtype("i1"), (2,)), "cu8": (np.dtype("u1"), (2,))}
+
+
+def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, chunk_samples):
+    """The tuned path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.ddc.Channelizer` in chunks."""
+    from .ddc import Channelizer
+    shift, D, taps = resolve_tune(rec["meta"], tune)
+    fmt = rec["sample_format"]
+    plain, tail = _PLAIN[fmt]
+    on_gpu = tune_compute is None
+    if on_gpu:
+        import torch                                       # this path alone: the untuned one stays torch-free
+        from .features import features18
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    parts, starts = [], []
+    for start, off, n_samples in rec["segments"]:
+        if left is not None and left <= 0:
+            break
+        if n_samples == 0:
+            continue
+        # (mode "c": private pages, never written -- torch.from_numpy wants a writable array, and "r+" would want a writable file)
+        src = np.memmap(rec["data_path"], dtype=plain, mode="c", offset=off, shape=(n_samples,) + tail)
+        chan = Channelizer(taps, D, shift, fmt, scale, compute=tune_compute)
+        ys, have = [], 0
+        for c0 in range(0, n_samples, chunk_samples):
+            chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
+            y = chan.push(torch.from_numpy(chunk).to(dev) if on_gpu else chunk)
+            ys.append(y)
+            have += int(y.shape[0])
+            if left is not None and have >= left * N:
+                break
+        n = have // N if left is None else min(have // N, left)
+        if n == 0:
+            continue
+        if left is not None:
+            left -= n
+        if on_gpu:
+            frames = torch.cat(ys)[:n * N].view(n, N)
+            if compute is None:
+                parts.append(features18(frames, feature_ids=feature_ids).cpu().numpy())
+            else:
+                parts.append(np.asarray(compute(frames.cpu().numpy()), dtype=np.float32))
+        else:
+            parts.append(np.asarray(compute(np.concatenate(ys)[:n * N].reshape(n, N)), dtype=np.float32))
+        starts.append(start + N * D * np.arange(n, dtype=np.int64))
+    if not parts:
+        return np.empty((0, 18), dtype=np.float32), np.empty((0,), dtype=np.int64)
+    return np.concatenate(parts), np.concatenate(starts)
+
+
 def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, feature_ids=None, scale=None,
-                  max_frames: Optional[int] = None, compute=None):
+                  max_frames: Optional[int] = None, compute=None, tune=None, tune_compute=None,
+                  chunk_samples: int = 1 << 24):
     """Features of a SigMF recording -> ``(features, frame_start)``: (F, 18) float32 and (F,) int64.
 
     Every capture segment is cut into consecutive ``frame_size``-sample frames (its partial tail is dropped: no frame
@@ -98,7 +210,17 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     threads read it and the samples cross the link as they lie (8, 4 or 2 bytes each).  ``frame_start[k]`` is the
     sample index (``core:sample_start`` counting) of frame k's first sample.  ``scale``: what an integer component is
     multiplied by (default 2^-15 for ci16_le, 2^-7 for ci8 / cu8; cf32_le has none).  ``feature_ids``: only these (NaN in
-    the other columns).  ``compute``: an injected engine (tests), which sees the widened complex64 frames."""
+    the other columns).  ``compute``: an injected engine (tests), which sees the widened complex64 frames.
+
+    ``tune``: the emitter is off centre and narrower than the recorded band -- ``dict(shift_hz=F, decimate=D, taps=None)``
+    (add F Hz to every frequency -- an emitter at +f wants F = -f --, low-pass, keep every D-th sample; ``taps``: None
+    for :func:`amcpy_amd.ddc.design_lowpass`'s default, a tap count, or the taps), or ``dict(annotation=k, oversample=r)``
+    (:func:`tune_from_annotation`).  Every segment is then read in chunks of ``chunk_samples``, copied to the device as it
+    lies and pushed through a :class:`amcpy_amd.ddc.Channelizer` (the phase starts at 0 with every segment); the
+    decimated stream is cut into ``frame_size`` frames (its partial tail dropped, nothing straddles a capture) and the
+    features are computed on the resident result.  ``frame_start[k]`` is ``segment start + k * frame_size * D``, the first
+    input sample that contributes to frame k.  ``tune_compute``: an injected down-converter over numpy chunks (tests, as
+    :class:`amcpy_amd.ddc.Channelizer`'s ``compute``); ``compute`` then sees the decimated complex64 frames."""
     from .feature_extraction import FileComplex, FrameRows, HipEngine, _subset, widen_integer_frames
     from .features import _sc16_scale
     feature_ids, compute = _subset(feature_ids, compute)
@@ -109,6 +231,8 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     store, fmt = rec["store"], rec["sample_format"]
     scale = rec["scale"] if scale is None or fmt == "cf32" else _sc16_scale(scale)
     left = None if max_frames is None else max(0, int(max_frames))
+    if tune is not None:
+        return _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, max(1, int(chunk_samples)))
     parts, starts = [], []
     engine = None
     try:

@@ -96,7 +96,11 @@ extern "C" {
  * 10 = frames of 8-bit IQ (ci8, cu8), widened on the device: AMCX_IQ8_*, amcx_features_iq8, amcx_features_iq8_workspace_bytes,
  * amcx_kernel_name_iq8, AMCX_SRC_CI8 / AMCX_SRC_CU8 for the strided host / file entries and amcx_stage_host / _file,
  * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host. */
-#define AMCX_ABI_VERSION 10
+#define AMCX_ABI_VERSION 11
+/* The define, version by version (a binding may look for the line of the version it was written against):
+ *   ABI 10: #define AMCX_ABI_VERSION 10   -- 8-bit IQ (ci8, cu8), widened on the device
+ *   ABI 11: the line above               -- the digital down-converter: amcx_tune_decimate, amcx_tune_decimate_out_samples,
+ *                                            amcx_tune_decimate_plan, amcx_kernel_name_ddc */
 #define AMCX_NUM_FEATURES 18
 
 /* FEATURE MASKS (ABI 7): bit j - 1 stands for feature id j (1 gamma_max ... 18 |C63|).  The reference's default selection,
@@ -267,6 +271,42 @@ int amcx_features_iq8(const void* iq_dev, int64_t n_frames, int32_t frame_size, 
                       uint32_t feature_mask, void* workspace_dev, int64_t workspace_bytes);
 
 /*
+ * ABI 11.  THE DIGITAL DOWN-CONVERTER: tune, low-pass and decimate a recording where it lies.  A receiver records a band several
+ * times wider than the emitter, which sits off centre; the features want it at 0 Hz and filling its band.
+ *   - src_dev is ONE contiguous stream of n_samples samples, src_kind AMCX_SRC_C64, AMCX_SRC_SC16, AMCX_SRC_CI8 or AMCX_SRC_CU8
+ *     (defined below; every other kind is AMCX_EINVAL).  A sample's value x[n] is what ABI 9 / 10 define: for the integer
+ *     kinds complex64((float)i * scale, (float)q * scale), cu8 as byte - 128; scale is ignored for complex64.
+ *   - taps_dev: n_taps REAL float32 taps h[0 .. n_taps - 1] in device memory; decim: the decimation factor D.  With T = n_taps:
+ *         phi(n) = (phase0 + n * phase_step) mod 2^64        (uint64 arithmetic, exact; n counts THIS CALL's input samples)
+ *         v[n]   = x[n] * exp(+2 pi j * phi(n) / 2^64)
+ *         y[m]   = sum_{k = 0 .. T-1} h[k] * v[m D + T - 1 - k],   m = 0 ... M - 1,   M = n_samples < T ? 0 : (n_samples - T) / D + 1
+ *     i.e. numpy.convolve(v, h, "valid")[::D]; y is packed complex64 at out_c64_dev, which has room for out_capacity_samples.
+ *     To move a signal at +f Hz to 0: phase_step = round(-f / fs * 2^64) mod 2^64.  A caller that continues a stream passes
+ *     phase0 + consumed * phase_step.  The angle is formed from the top 32 bits of phi (1.5e-9 rad, far below an fp32 sine's
+ *     rounding); range reduction is integer and exact.
+ *   - limits: 1 <= n_taps <= 2048, 1 <= decim <= 4096 (decim > n_taps is legal: samples are skipped), 0 <= n_samples < 2^40.
+ *     Alignment: src 8 / 4 / 2 bytes (c64 / sc16 / 8-bit), taps 4, out 8.
+ *   - POSITION INDEPENDENCE: the bits of y[m] depend only on its T input samples, the taps and phi at those samples -- not on m's
+ *     place in the call, on n_samples, on the grid or on which load read the samples; each output is summed in one fixed order
+ *     of k.  A stream cut into calls at any multiple of D, with phase0 advanced, gives the one-call result bit for bit.
+ *   - phi = 0 IS EXACT: the mixer value is exactly 1 + 0j there (for every phi < 2^32).  With phase0 = phase_step = 0, T = 1,
+ *     h = {1}, D = 1 the output is the widened input bit for bit.
+ *   - accuracy: |y[m] - exact| <= (T + 8) 2^-24 sum_k |h[k]| |x[m D + T - 1 - k]| (tests/test_gpu_ddc.py).
+ * Asynchronous on the caller's stream, allocates nothing, capturable in a graph.  The checks come before any device call, in
+ * this order: src_kind; scale (integer kinds only: finite float32 > 0); n_taps, decim and n_samples ranges; out_capacity_samples
+ * >= M; M == 0 is AMCX_OK here, null pointers allowed; null pointers and alignment; a pointer on another device.
+ * amcx_tune_decimate_out_samples: M, or -1 for arguments the entry refuses.
+ * amcx_tune_decimate_plan (host-only): how a call is cut -- *tile_outputs consecutive outputs per tile (a tile's input span,
+ * (tile - 1) D + T samples, is staged in LDS), a persistent grid of at most *max_workgroups workgroups on the current device
+ * (256 CUs assumed where there is none); either pointer may be NULL.  AMCX_EINVAL for n_taps / decim out of range.
+ */
+int64_t amcx_tune_decimate_out_samples(int64_t n_samples, int32_t n_taps, int32_t decim);
+int amcx_tune_decimate(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0,
+                       uint64_t phase_step, const float* taps_dev, int32_t n_taps, int32_t decim, void* out_c64_dev,
+                       int64_t out_capacity_samples, void* hip_stream);
+int amcx_tune_decimate_plan(int32_t n_taps, int32_t decim, int32_t* tile_outputs, int32_t* max_workgroups);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -349,6 +389,9 @@ int amcx_kernel_name_sc16(int32_t frame_size, int32_t variant, uint32_t feature_
 /* ABI 10: the same for amcx_features_iq8, the FEATURE kernel that runs behind amcx_iq8_to_sc16_kernel /
  * amcx_iq8_to_c64_kernel: amcx_kernel_name_sc16's answer. */
 int amcx_kernel_name_iq8(int32_t frame_size, int32_t variant, uint32_t feature_mask, char* buf, int32_t buf_len);
+/* ABI 11: the kernel amcx_tune_decimate runs for this src_kind (host-only): amcx_ddc_c64_kernel, amcx_ddc_sc16_kernel, or
+ * amcx_ddc_iq8_kernel for both 8-bit kinds.  AMCX_EINVAL for another kind. */
+int amcx_kernel_name_ddc(int32_t src_kind, char* buf, int32_t buf_len);
 
 /* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
  * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
