@@ -13,7 +13,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_ddc_kernel.h"       // FIRST, then the 8-bit widening kernels, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
+#include "amcx_bank_kernel.h"      // FIRST (it includes the down-converter's header in front of its own kernels), ...
+#include "amcx_ddc_kernel.h"       // ... then the 8-bit widening kernels, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
 #include "amcx_iq8_kernels.h"
 #include "amcx_sc16_kernels.h"
 #include "amcx_block_kernel.h"
@@ -465,6 +466,22 @@ bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
 int ddc_wgs_per_cu(int n_taps, int decim) {
   const int fit = (int)((size_t)(160 * 1024) / amcx::ddc_lds_bytes(n_taps, decim));
   return fit < 1 ? 1 : fit > 8 ? 8 : fit;
+}
+
+// resident workgroups per CU of a filter-bank launch (amcx_bank_kernel.h): what its LDS leaves room for, four at most
+int bank_wgs_per_cu(int n_taps, int channels, int decim) {
+  const int fit = (int)((size_t)(160 * 1024) / amcx::bank_lds_bytes(n_taps, channels, decim));
+  return fit < 1 ? 1 : fit > 4 ? 4 : fit;
+}
+
+template <auto Kern, class... A>
+int bank_launch(int64_t grid, size_t lds, hipStream_t stream, A... args) {
+  // the most a bank kernel ever asks for: C = 2 (tile 2048), T = 4096, D = 2
+  if (const hipError_t e = amcx::lds_attr_once<Kern>((int)amcx::bank_lds_bytes(amcx::kBankMaxTaps, 2, 2)); e != hipSuccess)
+    return hip_fail(e, "filter-bank kernel attribute");
+  if (const hipError_t e = amcx::launch(Kern, grid, amcx::kBankThreads, lds, stream, args...); e != hipSuccess)
+    return hip_fail(e, "filter-bank kernel launch");
+  return AMCX_OK;
 }
 
 // the columns a post-processing entry selects (n_sel in range already); false: one of them is not a column of the input
@@ -934,6 +951,75 @@ int amcx_kernel_name_ddc(int32_t src_kind, char* buf, int32_t buf_len) {
   const char* const name = src_kind == AMCX_SRC_C64    ? "amcx_ddc_c64_kernel"
                            : src_kind == AMCX_SRC_SC16 ? "amcx_ddc_sc16_kernel"
                            : src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8 ? "amcx_ddc_iq8_kernel" : nullptr;
+  if (name == nullptr) return AMCX_EINVAL;
+  snprintf(buf, (size_t)buf_len, "%s", name);
+  return AMCX_OK;
+}
+
+// ---- the polyphase filter bank (amcx_bank_kernel.h) -------------------------------------------------------------------
+int64_t amcx_filter_bank_out_samples(int64_t n_samples, int32_t n_taps, int32_t channels, int32_t decim) {
+  if (channels < 2 || channels > amcx::kBankMaxChannels || (channels & (channels - 1)) != 0) return -1;
+  if (n_taps < 1 || n_taps > amcx::kBankMaxTaps || decim < 1 || decim > channels) return -1;
+  if (n_samples < 0 || n_samples >= (int64_t(1) << 40)) return -1;
+  return n_samples < n_taps ? 0 : (n_samples - n_taps) / decim + 1;
+}
+
+int amcx_filter_bank_plan(int32_t n_taps, int32_t channels, int32_t decim, int32_t* tile_outputs, int32_t* max_workgroups,
+                          int32_t* lds_bytes) {
+  if (amcx_filter_bank_out_samples(0, n_taps, channels, decim) < 0) return AMCX_EINVAL;
+  if (tile_outputs != nullptr) *tile_outputs = amcx::bank_tile_outputs(channels);
+  if (max_workgroups != nullptr) *max_workgroups = cu_count() * bank_wgs_per_cu(n_taps, channels, decim);
+  if (lds_bytes != nullptr) *lds_bytes = (int32_t)amcx::bank_lds_bytes(n_taps, channels, decim);
+  return AMCX_OK;
+}
+
+int amcx_filter_bank(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0,
+                     uint64_t phase_step, uint64_t sample_index0, const float* taps_dev, int32_t n_taps, int32_t channels,
+                     int32_t decim, void* out_c64_dev, int64_t out_channel_stride, int64_t out_capacity_samples,
+                     void* hip_stream) {
+  const bool integer = src_kind == AMCX_SRC_SC16 || src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8;
+  if (src_kind != AMCX_SRC_C64 && !integer) return AMCX_EINVAL;
+  if (integer && !int_scale_ok(scale)) return AMCX_EINVAL;
+  const int64_t M = amcx_filter_bank_out_samples(n_samples, n_taps, channels, decim);
+  if (M < 0) return AMCX_EINVAL;
+  if (out_channel_stride < M || out_channel_stride > (INT64_MAX - M) / (channels - 1)) return AMCX_EINVAL;
+  if (out_capacity_samples < (int64_t)(channels - 1) * out_channel_stride + M) return AMCX_EINVAL;
+  if (M == 0) return AMCX_OK;
+  if (src_dev == nullptr || taps_dev == nullptr || out_c64_dev == nullptr) return AMCX_EINVAL;
+  const unsigned src_align = src_kind == AMCX_SRC_C64 ? 7u : src_kind == AMCX_SRC_SC16 ? 3u : 1u;
+  if ((reinterpret_cast<uintptr_t>(src_dev) & src_align) || (reinterpret_cast<uintptr_t>(taps_dev) & 3u) ||
+      (reinterpret_cast<uintptr_t>(out_c64_dev) & 7u))
+    return AMCX_EINVAL;
+  if (on_another_device(src_dev) || on_another_device(taps_dev) || on_another_device(out_c64_dev)) return AMCX_EINVAL;
+  const int tile = amcx::bank_tile_outputs(channels);
+  const int64_t n_tiles = (M + tile - 1) / tile;
+  const int64_t grid = amcx::persistent_grid(cu_count(), bank_wgs_per_cu(n_taps, channels, decim), n_tiles, 1);
+  const size_t lds = amcx::bank_lds_bytes(n_taps, channels, decim);
+  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const char* const src = static_cast<const char*>(src_dev);
+  float2* const out = static_cast<float2*>(out_c64_dev);
+  const float sc = integer ? scale : 1.0f;
+  const unsigned flip4 = src_kind == AMCX_SRC_CU8 ? 0x80808080u : 0u;
+  const unsigned long long p0 = phase0, ps = phase_step;
+  const int a0 = (int)(sample_index0 & (uint64_t)(channels - 1));
+  int logC = 0;
+  while ((1 << logC) < channels) ++logC;
+  const long long stride = out_channel_stride, m = M, nt = n_tiles;
+  if (src_kind == AMCX_SRC_C64)
+    return bank_launch<amcx::amcx_bank_c64_kernel>(grid, lds, stream, src, sc, flip4, p0, ps, a0, taps_dev, n_taps, logC, decim, out,
+                                                    stride, m, tile, nt);
+  if (src_kind == AMCX_SRC_SC16)
+    return bank_launch<amcx::amcx_bank_sc16_kernel>(grid, lds, stream, src, sc, flip4, p0, ps, a0, taps_dev, n_taps, logC, decim, out,
+                                                     stride, m, tile, nt);
+  return bank_launch<amcx::amcx_bank_iq8_kernel>(grid, lds, stream, src, sc, flip4, p0, ps, a0, taps_dev, n_taps, logC, decim, out,
+                                                  stride, m, tile, nt);
+}
+
+int amcx_kernel_name_bank(int32_t src_kind, char* buf, int32_t buf_len) {
+  if (buf == nullptr || buf_len <= 0) return AMCX_EINVAL;
+  const char* const name = src_kind == AMCX_SRC_C64    ? "amcx_bank_c64_kernel"
+                           : src_kind == AMCX_SRC_SC16 ? "amcx_bank_sc16_kernel"
+                           : src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8 ? "amcx_bank_iq8_kernel" : nullptr;
   if (name == nullptr) return AMCX_EINVAL;
   snprintf(buf, (size_t)buf_len, "%s", name);
   return AMCX_OK;

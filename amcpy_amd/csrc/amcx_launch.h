@@ -308,6 +308,8 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bo
 // The sc16 kernels (ABI 9) stand in FRONT of all of them, as explicit specialisations in a header amcx.hip includes first
 // (amcx_sc16_kernels.h says why): code added behind the first existing kernel would move distances that existing kernels hold.
 // The 8-bit widening kernels (ABI 10, amcx_iq8_kernels.h) are plain kernels in a header included in front of that one: the head of the head.
+// The down-converter's kernels (ABI 11, amcx_ddc_kernel.h) stand in front of those, and the filter bank's (ABI 12, amcx_bank_kernel.h:
+// it includes the down-converter's header, whose loaders and mixer it uses, in front of its own kernels) are included first of all.
 // That specialisations are laid out there is what hipcc does today, not a rule it documents: tools/codeobj_gate.py --kernels
 // against the parent commit is what guards it, and the only thing that will notice when a compiler lays them out elsewhere.
 inline void kernel_order_anchor() {

@@ -8,7 +8,8 @@ evaluation half of the reference's `eval` (nn_model.evaluate_by_snr) on the GPU:
 on a one-argument function (main.py:175 vs :85) and raises TypeError as
 written; this entry point takes the same defaults and simply works.
 `python -m amcpy_amd recording FILE --frame-size N [--format cf32|sc16|ci8|cu8] [--scale S] [--features ...] [--device D]
-[--out PATH] [--shift-hz F --decimate D [--taps T] | --annotation K [--oversample R]]` takes ONE recording -- a SigMF recording (its meta file says the format: no --format), or a raw sample
+[--out PATH] [--shift-hz F --decimate D [--taps T] | --annotation K [--oversample R] | --channels C [--oversample 1|2]
+[--taps-per-channel P] [--shift-hz F]]` takes ONE recording -- a SigMF recording (its meta file says the format: no --format), or a raw sample
 stream -- and writes `features` (F, 18) and `frame_start` (F,) into a .mat file: amcpy_amd/sigmf.py, extract_raw_stream.
 The tuning flags (SigMF only) put the device's down-converter in front: the emitter moved to 0 Hz, low-passed and decimated
 (amcpy_amd/ddc.py; sigmf.extract_sigmf, tune=).
@@ -82,13 +83,26 @@ def build_parser() -> argparse.ArgumentParser:
     rec.add_argument("--annotation", type=int, default=None, metavar="K",
                      help="tune to the band of the recording's annotation K instead (its frequency edges)")
     rec.add_argument("--oversample", type=float, default=None, metavar="R",
-                     help="with --annotation: decimate to R times the annotation's bandwidth (default 2)")
+                     help="with --annotation: decimate to R times the annotation's bandwidth (default 2); with --channels: "
+                          "1 (critically sampled, the default) or 2")
+    rec.add_argument("--channels", type=int, default=None, metavar="C",
+                     help="every channel of a raster of C (a power of two, 2 ... 256) through the polyphase filter bank; "
+                          "--shift-hz then offsets the raster")
+    rec.add_argument("--taps-per-channel", type=int, default=None, metavar="P",
+                     help="with --channels: the prototype low-pass has C P taps (default 16)")
     return ap
 
 
 def recording_tune(args):
     """The `recording` command's tuning flags -> the ``tune`` of sigmf.extract_sigmf, or None.  The two forms exclude each
-    other, and each flag needs the one it belongs to."""
+    other, and each flag needs the one it belongs to.  With --channels (:func:`recording_channelize`) there is no tuning:
+    --shift-hz and --oversample then belong to the filter bank."""
+    if args.channels is not None:
+        if args.decimate is not None or args.taps is not None or args.annotation is not None:
+            raise SystemExit("--channels excludes --decimate / --taps / --annotation")
+        return None
+    if args.taps_per_channel is not None:
+        raise SystemExit("--taps-per-channel needs --channels")
     manual = args.shift_hz is not None or args.decimate is not None or args.taps is not None
     by_annotation = args.annotation is not None or args.oversample is not None
     if manual and by_annotation:
@@ -104,8 +118,23 @@ def recording_tune(args):
     return None
 
 
-def run_recording(args, compute=None, tune_compute=None) -> Path:
-    """The `recording` command: features and frame_start of args.file -> args.out (written aside, then renamed)."""
+def recording_channelize(args):
+    """The `recording` command's filter-bank flags -> the ``channelize`` of sigmf.extract_sigmf, or None."""
+    if args.channels is None:
+        return None
+    recording_tune(args)                                   # the flags --channels excludes
+    over = 1 if args.oversample is None else args.oversample
+    if over not in (1, 2):
+        raise SystemExit("--oversample with --channels is 1 or 2")
+    return {"channels": args.channels, "oversample": int(over),
+            "taps_per_channel": 16 if args.taps_per_channel is None else args.taps_per_channel,
+            "shift_hz": 0.0 if args.shift_hz is None else args.shift_hz}
+
+
+def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> Path:
+    """The `recording` command: features and frame_start of args.file -> args.out (written aside, then renamed).  With
+    --channels: features (C, K, 18), and channel_freq_hz (C,) where the meta file gives a sample rate (offset by the first
+    capture's core:frequency where it has one)."""
     import numpy as np
     from scipy.io import savemat
     from . import sigmf
@@ -113,14 +142,26 @@ def run_recording(args, compute=None, tune_compute=None) -> Path:
     ids = resolve_features(args.features, Config())
     path = Path(args.file)
     tune = recording_tune(args)
+    channelize = recording_channelize(args)
+    extra = {}
     if sigmf.is_sigmf(path):
         if args.format is not None:
             raise SystemExit("--format: a SigMF recording names its own datatype")
         feats, frame_start = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
-                                                 compute=compute, tune=tune, tune_compute=tune_compute)
+                                                 compute=compute, tune=tune, tune_compute=tune_compute, channelize=channelize,
+                                                 bank_compute=bank_compute)
         stem = Path(sigmf._stem(path))
+        if channelize is not None:
+            from fractions import Fraction
+            from .bank import channel_frequencies
+            meta = sigmf.read_meta(path)["meta"]
+            rate = meta.get("global", {}).get("core:sample_rate")
+            if rate:
+                center = float((meta.get("captures") or [{}])[0].get("core:frequency", 0.0))
+                shift = Fraction(channelize["shift_hz"]) / Fraction(float(rate))
+                extra["channel_freq_hz"] = channel_frequencies(channelize["channels"], float(rate), center, shift)
     else:
-        if tune is not None:
+        if tune is not None or channelize is not None:
             raise SystemExit("the tuning flags need a SigMF recording (its meta file holds the sample rate)")
         if args.format is None:
             raise SystemExit(f"{path} is no SigMF recording: --format cf32|sc16|ci8|cu8 says what its samples are")
@@ -133,12 +174,15 @@ def run_recording(args, compute=None, tune_compute=None) -> Path:
     aside = out.with_name(out.name + f".{os.getpid()}.tmp")
     try:
         with open(aside, "wb") as fh:
-            savemat(fh, {"features": feats, "frame_start": frame_start})
+            savemat(fh, {"features": feats, "frame_start": frame_start, **extra})
         os.replace(aside, out)
     finally:
         if aside.exists():
             aside.unlink()
-    print(f"{out}: {feats.shape[0]} frames of {args.frame_size} samples")
+    if channelize is not None:
+        print(f"{out}: {feats.shape[0]} channels, {feats.shape[1]} frames of {args.frame_size} samples each")
+    else:
+        print(f"{out}: {feats.shape[0]} frames of {args.frame_size} samples")
     return out
 
 
@@ -253,7 +297,7 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
     args = build_parser().parse_args(argv)
     if args.command == "recording":           # one file in, one file out: no project root, no torch (unless it tunes)
         from . import _lib
-        if skip_torch and recording_tune(args) is None:
+        if skip_torch and recording_tune(args) is None and recording_channelize(args) is None:
             _lib.load(skip_torch=True)
         run_recording(args)
         return 0

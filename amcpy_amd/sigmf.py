@@ -200,9 +200,81 @@ def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune
     return np.concatenate(parts), np.concatenate(starts)
 
 
+def resolve_channelize(meta: dict, channelize: dict) -> tuple:
+    """``channelize`` of :func:`extract_sigmf` -> ``(shift in cycles per sample, channels, decim, float32 taps)``."""
+    from fractions import Fraction
+    from .bank import design_bank_lowpass
+    known = {"channels", "oversample", "taps_per_channel", "taps", "shift_hz"}
+    if not isinstance(channelize, dict) or set(channelize) - known or "channels" not in channelize:
+        raise ValueError(f"channelize: a dict of {sorted(known)}, channels among them")
+    C, over = int(channelize["channels"]), channelize.get("oversample", 1)
+    if over not in (1, 2):
+        raise ValueError(f"channelize: oversample is 1 (critically sampled) or 2, not {over!r}")
+    shift_hz = float(channelize.get("shift_hz", 0.0))
+    shift = Fraction(0)
+    if shift_hz != 0.0:
+        rate = meta.get("global", {}).get("core:sample_rate")
+        if not rate:
+            raise ValueError("channelize: a shift in Hz needs the global core:sample_rate")
+        shift = Fraction(shift_hz) / Fraction(float(rate))
+    taps = channelize.get("taps")
+    if taps is None:
+        taps = design_bank_lowpass(C, int(channelize.get("taps_per_channel", 16)))
+    elif "taps_per_channel" in channelize:
+        raise ValueError("channelize: either taps or taps_per_channel")
+    return shift, C, C // int(over), np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+
+
+def _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, compute, bank_compute, chunk_samples):
+    """The filter-bank path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.bank.FilterBank` in chunks."""
+    from .bank import FilterBank
+    shift, C, D, taps = resolve_channelize(rec["meta"], channelize)
+    fmt = rec["sample_format"]
+    plain, tail = _PLAIN[fmt]
+    on_gpu = bank_compute is None
+    if on_gpu:
+        import torch                                       # this path alone: the untuned one stays torch-free
+        from .features import features18
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    parts, starts = [], []
+    for start, off, n_samples in rec["segments"]:
+        if left is not None and left <= 0:
+            break
+        if n_samples == 0:
+            continue
+        src = np.memmap(rec["data_path"], dtype=plain, mode="c", offset=off, shape=(n_samples,) + tail)
+        bank = FilterBank(taps, C, D, shift, fmt, scale, compute=bank_compute)
+        ys, have = [], 0
+        for c0 in range(0, n_samples, chunk_samples):
+            chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
+            y = bank.push(torch.from_numpy(chunk).to(dev) if on_gpu else chunk)
+            ys.append(y)
+            have += int(y.shape[1])
+            if left is not None and have >= left * N:
+                break
+        n = have // N if left is None else min(have // N, left)
+        if n == 0:
+            continue
+        if left is not None:
+            left -= n
+        if on_gpu:
+            frames = torch.cat(ys, dim=1)[:, :n * N].contiguous().view(C * n, N)          # row c * n + k: channel c, frame k
+            if compute is None:
+                got = features18(frames, feature_ids=feature_ids).cpu().numpy()
+            else:
+                got = np.asarray(compute(frames.cpu().numpy()), dtype=np.float32)
+        else:
+            got = np.asarray(compute(np.ascontiguousarray(np.concatenate(ys, axis=1)[:, :n * N]).reshape(C * n, N)), dtype=np.float32)
+        parts.append(got.reshape(C, n, 18))
+        starts.append(start + N * D * np.arange(n, dtype=np.int64))
+    if not parts:
+        return np.empty((C, 0, 18), dtype=np.float32), np.empty((0,), dtype=np.int64)
+    return np.concatenate(parts, axis=1), np.concatenate(starts)
+
+
 def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, feature_ids=None, scale=None,
                   max_frames: Optional[int] = None, compute=None, tune=None, tune_compute=None,
-                  chunk_samples: int = 1 << 24):
+                  chunk_samples: int = 1 << 24, channelize=None, bank_compute=None):
     """Features of a SigMF recording -> ``(features, frame_start)``: (F, 18) float32 and (F,) int64.
 
     Every capture segment is cut into consecutive ``frame_size``-sample frames (its partial tail is dropped: no frame
@@ -220,7 +292,15 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     decimated stream is cut into ``frame_size`` frames (its partial tail dropped, nothing straddles a capture) and the
     features are computed on the resident result.  ``frame_start[k]`` is ``segment start + k * frame_size * D``, the first
     input sample that contributes to frame k.  ``tune_compute``: an injected down-converter over numpy chunks (tests, as
-    :class:`amcpy_amd.ddc.Channelizer`'s ``compute``); ``compute`` then sees the decimated complex64 frames."""
+    :class:`amcpy_amd.ddc.Channelizer`'s ``compute``); ``compute`` then sees the decimated complex64 frames.
+
+    ``channelize`` (not together with ``tune``): the recording holds emitters on a raster --
+    ``dict(channels=C, oversample=1|2, taps_per_channel=16, taps=None, shift_hz=0.0)``.  Every segment is read in chunks and
+    pushed through a :class:`amcpy_amd.bank.FilterBank` of C channels, D = C / oversample (the sample index starts at 0 with
+    every segment); every channel's stream is cut into frames.  Returns ``(features (C, K, 18), frame_start (K,))`` with
+    ``frame_start[k] = segment start + k * frame_size * D``; ``max_frames`` counts frames per channel.  ``bank_compute``: an
+    injected bank over numpy chunks (tests, as :class:`amcpy_amd.bank.FilterBank`'s ``compute``); ``compute`` then sees
+    the (C * n, frame_size) complex64 frames of a segment, channel-major."""
     from .feature_extraction import FileComplex, FrameRows, HipEngine, _subset, widen_integer_frames
     from .features import _sc16_scale
     feature_ids, compute = _subset(feature_ids, compute)
@@ -231,6 +311,11 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     store, fmt = rec["store"], rec["sample_format"]
     scale = rec["scale"] if scale is None or fmt == "cf32" else _sc16_scale(scale)
     left = None if max_frames is None else max(0, int(max_frames))
+    if tune is not None and channelize is not None:
+        raise ValueError("tune and channelize exclude each other: one emitter, or every channel of a raster")
+    if channelize is not None:
+        return _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, compute, bank_compute,
+                                    max(1, int(chunk_samples)))
     if tune is not None:
         return _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, max(1, int(chunk_samples)))
     parts, starts = [], []

@@ -95,12 +95,15 @@ extern "C" {
  * amcx_ctx_features18_sc16_host;
  * 10 = frames of 8-bit IQ (ci8, cu8), widened on the device: AMCX_IQ8_*, amcx_features_iq8, amcx_features_iq8_workspace_bytes,
  * amcx_kernel_name_iq8, AMCX_SRC_CI8 / AMCX_SRC_CU8 for the strided host / file entries and amcx_stage_host / _file,
- * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host. */
-#define AMCX_ABI_VERSION 11
-/* The define, version by version (a binding may look for the line of the version it was written against):
- *   ABI 10: #define AMCX_ABI_VERSION 10   -- 8-bit IQ (ci8, cu8), widened on the device
- *   ABI 11: the line above               -- the digital down-converter: amcx_tune_decimate, amcx_tune_decimate_out_samples,
- *                                            amcx_tune_decimate_plan, amcx_kernel_name_ddc */
+ * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host;
+ * 11 = the digital down-converter; 12 = the polyphase filter bank (both listed behind the define). */
+#define AMCX_ABI_VERSION 12
+/* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
+ *   ABI 12: the line above               -- the polyphase filter bank: amcx_filter_bank, amcx_filter_bank_out_samples,
+ *                                            amcx_filter_bank_plan, amcx_kernel_name_bank
+ *   ABI 11: #define AMCX_ABI_VERSION 11   -- the digital down-converter: amcx_tune_decimate, amcx_tune_decimate_out_samples,
+ *                                            amcx_tune_decimate_plan, amcx_kernel_name_ddc
+ *   ABI 10: #define AMCX_ABI_VERSION 10   -- 8-bit IQ (ci8, cu8), widened on the device */
 #define AMCX_NUM_FEATURES 18
 
 /* FEATURE MASKS (ABI 7): bit j - 1 stands for feature id j (1 gamma_max ... 18 |C63|).  The reference's default selection,
@@ -307,6 +310,50 @@ int amcx_tune_decimate(const void* src_dev, int32_t src_kind, int64_t n_samples,
 int amcx_tune_decimate_plan(int32_t n_taps, int32_t decim, int32_t* tile_outputs, int32_t* max_workgroups);
 
 /*
+ * ABI 12.  THE POLYPHASE FILTER BANK: every channel of a raster from ONE pass over a recording.  A wideband recording holds many
+ * emitters on a channel raster; C calls of amcx_tune_decimate read it C times and spend T / D FMAs per input sample each.
+ * The bank reads it once: 2 P FMAs per input sample and one C-point transform per output instant.
+ *   - src_dev, src_kind, n_samples, scale, phase0, phase_step, taps_dev: as amcx_tune_decimate (the same sample values, the same
+ *     mixer).  C = channels, a power of two 2 ... 256; T = n_taps, 1 ... 4096; P = ceil(T / C) taps per branch (a tap index >= T
+ *     does not exist: it is never read, and no sample is read for it); D = decim, 1 ... C, any integer (D = C: critically
+ *     sampled, D = C / 2: 2x oversampled); 0 <= n_samples < 2^40; sample_index0: the absolute index of src[0] in the stream.
+ *         phi(n)  = (phase0 + n * phase_step) mod 2^64                  (n counts THIS CALL's samples)
+ *         v[n]    = x[n] * exp(+2 pi j * phi(n) / 2^64)                  (phi < 2^32: v = x, the product is skipped)
+ *         a(n)    = (sample_index0 + n) mod C
+ *         n_m     = m D + T - 1,   M = n_samples < T ? 0 : (n_samples - T) / D + 1
+ *         y[c,m]  = sum_{k < T} h[k] * v[n_m - k] * exp(-2 pi j * c * a(n_m - k) / C)      c = 0 ... C - 1, m = 0 ... M - 1
+ *         out[c * out_channel_stride + m] = y[c,m]                       (packed complex64, CHANNEL-MAJOR, stride >= M)
+ *     Channel c is centred at +c / C cycles per sample of the pre-mixed stream -- FFT order: c > C / 2 are negative
+ *     frequencies; the pre-mixer offsets the whole raster.  By definition channel c is amcx_tune_decimate with
+ *     phase_step_c = phase_step - c 2^64 / C and phase0_c = phase0 - c (sample_index0 mod C) 2^64 / C, both mod 2^64.
+ *   - computed as branch sums u_m[p] = sum_{q < P, p + q C < T} h[p + q C] v[n_m - p - q C] (one product, then one FMA per
+ *     component in ascending q), and y[., m] = the unnormalised C-point DFT with kernel e^{+2 pi j c r / C} of
+ *     g[r] = u_m[(r + a(n_m)) mod C]; radix 2, twiddles exact at +-1 and +-j (amcx_bank_kernel.h).
+ *   - POSITION INDEPENDENCE: the bits of y[c,m] depend only on the T samples, the taps, phi at those samples and a(n_m) -- not on
+ *     m's place in the call, the tile, the grid, the lane or which load read a sample.  A stream cut into calls at any multiple
+ *     of D, with phase0 and sample_index0 advanced, gives the one-call result bit for bit.
+ *   - the four formats give the same bits as the complex64 call on the widened samples.
+ *   - EXACT CASE: phase0 = phase_step = 0, T = 1, h = {1}, D = 1, C = 2 or 4: y[c,n] is x[n] times an exact power of j.
+ *   - accuracy: |y - exact| <= (P + 8 + 7 log2 C) 2^-24 sum_k |h[k]| |x[n_m - k]| (tests/bank_ref.py).
+ * Asynchronous on the caller's stream, allocates nothing, capturable in a graph.  out_capacity_samples is the capacity of the
+ * whole buffer: (C - 1) * out_channel_stride + M must fit.  The checks come before any device call, in this order: src_kind;
+ * scale (integer kinds only); channels (a power of two in range), n_taps, decim and n_samples ranges; out_channel_stride >= M,
+ * and the capacity; M == 0 is AMCX_OK here, null pointers allowed; null pointers and alignment (src 8 / 4 / 2, taps 4, out 8);
+ * a pointer on another device.
+ * amcx_filter_bank_out_samples: M, or -1 for arguments the entry refuses.
+ * amcx_filter_bank_plan (host-only): *tile_outputs consecutive output instants per tile, a persistent grid of at most
+ * *max_workgroups workgroups on the current device (256 CUs assumed where there is none), *lds_bytes of dynamic LDS per
+ * workgroup; any pointer may be NULL.  AMCX_EINVAL for channels / n_taps / decim out of range.
+ */
+int64_t amcx_filter_bank_out_samples(int64_t n_samples, int32_t n_taps, int32_t channels, int32_t decim);
+int amcx_filter_bank(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0,
+                     uint64_t phase_step, uint64_t sample_index0, const float* taps_dev, int32_t n_taps,
+                     int32_t channels, int32_t decim, void* out_c64_dev, int64_t out_channel_stride,
+                     int64_t out_capacity_samples, void* hip_stream);
+int amcx_filter_bank_plan(int32_t n_taps, int32_t channels, int32_t decim, int32_t* tile_outputs,
+                          int32_t* max_workgroups, int32_t* lds_bytes);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -392,6 +439,9 @@ int amcx_kernel_name_iq8(int32_t frame_size, int32_t variant, uint32_t feature_m
 /* ABI 11: the kernel amcx_tune_decimate runs for this src_kind (host-only): amcx_ddc_c64_kernel, amcx_ddc_sc16_kernel, or
  * amcx_ddc_iq8_kernel for both 8-bit kinds.  AMCX_EINVAL for another kind. */
 int amcx_kernel_name_ddc(int32_t src_kind, char* buf, int32_t buf_len);
+/* ABI 12: the kernel amcx_filter_bank runs for this src_kind (host-only): amcx_bank_c64_kernel, amcx_bank_sc16_kernel, or
+ * amcx_bank_iq8_kernel for both 8-bit kinds; AMCX_EINVAL for any other kind. */
+int amcx_kernel_name_bank(int32_t src_kind, char* buf, int32_t buf_len);
 
 /* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
  * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
