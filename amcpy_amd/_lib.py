@@ -12,7 +12,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 12         # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 13         # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -74,6 +74,10 @@ SIGNATURES = {
                                    _i64, _vp]),
     "amcx_filter_bank_plan": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "amcx_kernel_name_bank": (C.c_int, [_i32, C.c_char_p, _i32]),
+    "amcx_resample_out_samples": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "amcx_resample": (C.c_int, [_vp, _i32, _i64, C.c_float, C.c_uint64, C.c_uint64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "amcx_resample_plan": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "amcx_kernel_name_resample": (C.c_char_p, [_i32]),
     "amcx_ctx_set_feature_mask": (C.c_int, [_vp, C.c_uint32]),
     "amcx_features18_c64_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
     "amcx_features18_c128_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
@@ -254,6 +258,22 @@ def filter_bank_plan(n_taps: int, channels: int, decim: int) -> tuple:
     tile, grid, lds = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     check(load().amcx_filter_bank_plan(int(n_taps), int(channels), int(decim), C.byref(tile), C.byref(grid), C.byref(lds)))
     return tile.value, grid.value, lds.value
+
+
+def kernel_name_resample(src_kind: int) -> str:
+    """amcx_kernel_name_resample: the kernel amcx_resample runs for this source kind (host-only)."""
+    name = load().amcx_kernel_name_resample(int(src_kind))
+    if name is None:
+        raise ValueError(f"amcx: no resampler kernel for source kind {src_kind}")
+    return name.decode()
+
+
+def resample_plan(n_taps: int, interp: int, decim: int) -> tuple:
+    """amcx_resample_plan -> (outputs per tile, most samples a tile stages, most workgroups of the persistent grid, bytes of
+    LDS) (host-only)."""
+    tile, span, grid, lds = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(load().amcx_resample_plan(int(n_taps), int(interp), int(decim), C.byref(tile), C.byref(span), C.byref(grid), C.byref(lds)))
+    return tile.value, span.value, grid.value, lds.value
 
 
 def numa_place(pci_bus_id: str, sysfs_root: str = "") -> tuple:

@@ -13,7 +13,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_bank_kernel.h"      // FIRST (it includes the down-converter's header in front of its own kernels), ...
+#include "amcx_resample_kernel.h"  // FIRST (it includes the down-converter's header in front of its own kernels), the bank's next, ...
+#include "amcx_bank_kernel.h"
 #include "amcx_ddc_kernel.h"       // ... then the 8-bit widening kernels, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
 #include "amcx_iq8_kernels.h"
 #include "amcx_sc16_kernels.h"
@@ -465,6 +466,12 @@ bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
 // resident workgroups per CU of a down-converter launch (amcx_ddc_kernel.h): what its LDS leaves room for, eight at most
 int ddc_wgs_per_cu(int n_taps, int decim) {
   const int fit = (int)((size_t)(160 * 1024) / amcx::ddc_lds_bytes(n_taps, decim));
+  return fit < 1 ? 1 : fit > 8 ? 8 : fit;
+}
+
+// resident workgroups per CU of a resampler launch (amcx_resample_kernel.h): what its LDS leaves room for, eight at most
+int rs_wgs_per_cu(int n_taps, int interp, int decim) {
+  const int fit = (int)((size_t)(160 * 1024) / amcx::rs_lds_bytes(n_taps, interp, decim));
   return fit < 1 ? 1 : fit > 8 ? 8 : fit;
 }
 
@@ -1023,6 +1030,66 @@ int amcx_kernel_name_bank(int32_t src_kind, char* buf, int32_t buf_len) {
   if (name == nullptr) return AMCX_EINVAL;
   snprintf(buf, (size_t)buf_len, "%s", name);
   return AMCX_OK;
+}
+
+// ---- the rational resampler (amcx_resample_kernel.h) --------------------------------------------------------------------
+int64_t amcx_resample_out_samples(int64_t n_samples, int32_t n_taps, int32_t interp, int32_t decim, int32_t phase_index0) {
+  if (n_taps < 1 || n_taps > amcx::kRsMaxTaps || interp < 1 || interp > amcx::kRsMaxInterp || decim < 1 ||
+      decim > amcx::kRsMaxDecim)
+    return -1;
+  if (phase_index0 < 0 || phase_index0 >= interp) return -1;
+  if (n_samples < 0 || n_samples >= (int64_t(1) << 40)) return -1;
+  const int64_t P = amcx::rs_phase_taps(n_taps, interp);
+  if (n_samples < P) return 0;
+  const int64_t last = (n_samples - P + 1) * interp - 1 - phase_index0;      // the largest t with n(t) <= n_samples - 1, less tau0
+  return last < 0 ? 0 : last / decim + 1;
+}
+
+int amcx_resample_plan(int32_t n_taps, int32_t interp, int32_t decim, int32_t* tile_outputs, int32_t* max_span_samples,
+                       int32_t* max_workgroups, int32_t* lds_bytes) {
+  if (amcx_resample_out_samples(0, n_taps, interp, decim, 0) < 0) return AMCX_EINVAL;
+  if (tile_outputs != nullptr) *tile_outputs = amcx::rs_tile_outputs(n_taps, interp, decim);
+  if (max_span_samples != nullptr) *max_span_samples = amcx::rs_max_span(n_taps, interp, decim);
+  if (max_workgroups != nullptr) *max_workgroups = cu_count() * rs_wgs_per_cu(n_taps, interp, decim);
+  if (lds_bytes != nullptr) *lds_bytes = (int32_t)amcx::rs_lds_bytes(n_taps, interp, decim);
+  return AMCX_OK;
+}
+
+int amcx_resample(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0, uint64_t phase_step,
+                  const float* taps_dev, int32_t n_taps, int32_t interp, int32_t decim, int32_t phase_index0,
+                  void* out_c64_dev, int64_t out_capacity_samples, void* hip_stream) {
+  const bool integer = src_kind == AMCX_SRC_SC16 || src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8;
+  if (src_kind != AMCX_SRC_C64 && !integer) return AMCX_EINVAL;
+  if (integer && !int_scale_ok(scale)) return AMCX_EINVAL;
+  const int64_t M = amcx_resample_out_samples(n_samples, n_taps, interp, decim, phase_index0);
+  if (M < 0 || out_capacity_samples < M) return AMCX_EINVAL;
+  if (M == 0) return AMCX_OK;
+  if (src_dev == nullptr || taps_dev == nullptr || out_c64_dev == nullptr) return AMCX_EINVAL;
+  const unsigned src_align = src_kind == AMCX_SRC_C64 ? 7u : src_kind == AMCX_SRC_SC16 ? 3u : 1u;
+  if ((reinterpret_cast<uintptr_t>(src_dev) & src_align) || (reinterpret_cast<uintptr_t>(taps_dev) & 3u) ||
+      (reinterpret_cast<uintptr_t>(out_c64_dev) & 7u))
+    return AMCX_EINVAL;
+  if (on_another_device(src_dev) || on_another_device(taps_dev) || on_another_device(out_c64_dev)) return AMCX_EINVAL;
+  const int tile = amcx::rs_tile_outputs(n_taps, interp, decim);
+  const int64_t n_tiles = (M + tile - 1) / tile;
+  const int64_t grid = amcx::persistent_grid(cu_count(), rs_wgs_per_cu(n_taps, interp, decim), n_tiles, 1);
+  const auto kern = src_kind == AMCX_SRC_C64 ? amcx::amcx_resample_c64_kernel
+                    : src_kind == AMCX_SRC_SC16 ? amcx::amcx_resample_sc16_kernel : amcx::amcx_resample_iq8_kernel;
+  const unsigned flip4 = src_kind == AMCX_SRC_CU8 ? 0x80808080u : 0u;
+  const hipError_t e = amcx::launch(kern, grid, amcx::kRsThreads, amcx::rs_lds_bytes(n_taps, interp, decim),
+                                    static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), integer ? scale : 1.0f,
+                                    flip4, (unsigned long long)phase0, (unsigned long long)phase_step, taps_dev, n_taps, interp,
+                                    decim, phase_index0, amcx::rs_phase_taps(n_taps, interp),
+                                    amcx::rs_max_span(n_taps, interp, decim), static_cast<float2*>(out_c64_dev), (long long)M,
+                                    tile, (long long)n_tiles);
+  if (e != hipSuccess) return hip_fail(e, "resampler kernel launch");
+  return AMCX_OK;
+}
+
+const char* amcx_kernel_name_resample(int32_t src_kind) {
+  return src_kind == AMCX_SRC_C64    ? "amcx_resample_c64_kernel"
+         : src_kind == AMCX_SRC_SC16 ? "amcx_resample_sc16_kernel"
+         : src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8 ? "amcx_resample_iq8_kernel" : nullptr;
 }
 
 int64_t amcx_group_stats_workspace_bytes(int64_t n_groups, int64_t rows_per_group, int32_t n_cols) {

@@ -8,11 +8,13 @@ evaluation half of the reference's `eval` (nn_model.evaluate_by_snr) on the GPU:
 on a one-argument function (main.py:175 vs :85) and raises TypeError as
 written; this entry point takes the same defaults and simply works.
 `python -m amcpy_amd recording FILE --frame-size N [--format cf32|sc16|ci8|cu8] [--scale S] [--features ...] [--device D]
-[--out PATH] [--shift-hz F --decimate D [--taps T] | --annotation K [--oversample R] | --channels C [--oversample 1|2]
+[--out PATH] [--shift-hz F --decimate D [--taps T] | --shift-hz F --resample L/D [--taps T] | --annotation K [--oversample R]
+[--rational] | --channels C [--oversample 1|2]
 [--taps-per-channel P] [--shift-hz F]]` takes ONE recording -- a SigMF recording (its meta file says the format: no --format), or a raw sample
 stream -- and writes `features` (F, 18) and `frame_start` (F,) into a .mat file: amcpy_amd/sigmf.py, extract_raw_stream.
 The tuning flags (SigMF only) put the device's down-converter in front: the emitter moved to 0 Hz, low-passed and decimated
-(amcpy_amd/ddc.py; sigmf.extract_sigmf, tune=).
+(amcpy_amd/ddc.py; sigmf.extract_sigmf, tune=); --resample L/D and --rational put the rational resampler there instead
+(amcpy_amd/resample.py): the rate changes by L / D, and the output file also records `interp` and `decim`.
 
 Several GPUs, ONE command (the reference's caller runs one command and the parallelism happens inside,
 feature_extraction.py:89-97): ``--devices 0,1,2,3`` / ``--devices all`` drives one engine per device from one
@@ -80,6 +82,12 @@ def build_parser() -> argparse.ArgumentParser:
                      help="tune first: add F Hz to every frequency (an emitter at +f wants -f); needs --decimate")
     rec.add_argument("--decimate", type=int, default=None, metavar="D", help="... low-pass and keep every D-th sample")
     rec.add_argument("--taps", type=int, default=None, metavar="T", help="taps of the low-pass (default 16 D + 1)")
+    rec.add_argument("--resample", default=None, metavar="L/D",
+                     help="instead of --decimate: change the rate by L / D through the rational resampler (L 1 ... 256, D 1 ... "
+                          "4096; --taps then defaults to 16 max(L, D) + 1)")
+    rec.add_argument("--rational", action="store_true",
+                     help="with --annotation: the fraction L / D closest to R times the bandwidth over the sample rate, through "
+                          "the rational resampler, instead of the next integer decimation")
     rec.add_argument("--annotation", type=int, default=None, metavar="K",
                      help="tune to the band of the recording's annotation K instead (its frequency edges)")
     rec.add_argument("--oversample", type=float, default=None, metavar="R",
@@ -98,23 +106,34 @@ def recording_tune(args):
     other, and each flag needs the one it belongs to.  With --channels (:func:`recording_channelize`) there is no tuning:
     --shift-hz and --oversample then belong to the filter bank."""
     if args.channels is not None:
-        if args.decimate is not None or args.taps is not None or args.annotation is not None:
-            raise SystemExit("--channels excludes --decimate / --taps / --annotation")
+        if (args.decimate is not None or args.taps is not None or args.annotation is not None or args.resample is not None
+                or args.rational):
+            raise SystemExit("--channels excludes --decimate / --resample / --rational / --taps / --annotation")
         return None
     if args.taps_per_channel is not None:
         raise SystemExit("--taps-per-channel needs --channels")
-    manual = args.shift_hz is not None or args.decimate is not None or args.taps is not None
-    by_annotation = args.annotation is not None or args.oversample is not None
+    manual = args.shift_hz is not None or args.decimate is not None or args.taps is not None or args.resample is not None
+    by_annotation = args.annotation is not None or args.oversample is not None or args.rational
     if manual and by_annotation:
-        raise SystemExit("--shift-hz / --decimate / --taps and --annotation / --oversample exclude each other")
+        raise SystemExit("--shift-hz / --decimate / --resample / --taps and --annotation / --oversample / --rational exclude "
+                         "each other")
+    if args.resample is not None:
+        if args.decimate is not None:
+            raise SystemExit("--resample and --decimate exclude each other")
+        try:
+            L, D = (int(v) for v in str(args.resample).split("/"))
+        except ValueError:
+            raise SystemExit(f"--resample {args.resample!r}: expected L/D, two integers")
+        return {"shift_hz": 0.0 if args.shift_hz is None else args.shift_hz, "resample": (L, D), "taps": args.taps}
     if manual:
         if args.decimate is None:
-            raise SystemExit("--shift-hz and --taps need --decimate")
+            raise SystemExit("--shift-hz and --taps need --decimate or --resample")
         return {"shift_hz": 0.0 if args.shift_hz is None else args.shift_hz, "decimate": args.decimate, "taps": args.taps}
     if by_annotation:
         if args.annotation is None:
-            raise SystemExit("--oversample needs --annotation")
-        return {"annotation": args.annotation, "oversample": 2.0 if args.oversample is None else args.oversample}
+            raise SystemExit("--oversample and --rational need --annotation")
+        tune = {"annotation": args.annotation, "oversample": 2.0 if args.oversample is None else args.oversample}
+        return {**tune, "rational": True} if args.rational else tune
     return None
 
 
@@ -147,6 +166,9 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> P
     if sigmf.is_sigmf(path):
         if args.format is not None:
             raise SystemExit("--format: a SigMF recording names its own datatype")
+        if sigmf.is_rational_tune(tune):                      # resolved once: L and D go into the output file
+            tune = sigmf.resolve_resample(sigmf.read_meta(path)["meta"], tune)
+            extra["interp"], extra["decim"] = np.int64(tune[1]), np.int64(tune[2])
         feats, frame_start = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
                                                  compute=compute, tune=tune, tune_compute=tune_compute, channelize=channelize,
                                                  bank_compute=bank_compute)

@@ -92,8 +92,16 @@ def read_meta(path) -> dict:
             "scale": scale, "segments": segments}
 
 
-def tune_from_annotation(meta: dict, k: int, oversample=2.0) -> tuple:
-    """Where annotation ``k`` of the parsed meta file says its emitter is -> ``(shift_hz, decimate)`` for ``tune=``.
+def tune_from_annotation(meta: dict, k: int, oversample=2.0, rational: bool = False) -> tuple:
+    """Where annotation ``k`` of the parsed meta file says its emitter is -> ``(shift_hz, decimate)`` for ``tune=``, or,
+    ``rational=True``, ``(shift_hz, (L, D))`` with ``L / D = rational_ratio(oversample * bandwidth / fs, 255, 255)``
+    (:func:`amcpy_amd.resample.rational_ratio`, exact arithmetic on the floats' values): the integer ``decimate`` delivers
+    anything between ``oversample`` and twice that, the fraction what was asked for.  L and D stay within 255
+    (``resample.DESIGN_MAX``): the largest for which :func:`amcpy_amd.resample.design_resample_lowpass`'s default,
+    ``16 max(L, D) + 1`` taps, fits the kernel's 4096 -- so a filter exists for whatever comes back; the fraction is within
+    ``1 / (2 * 255 * D)`` of the ratio wanted, 0.2 % of it at worst for ratios from 0.05 up (a host test sweeps them).
+    ValueError for a ratio outside ``[1 / 255, 255]``: a band narrower than ``fs / (255 * oversample)`` wants a
+    down-converter first.
 
     The annotation's band ``core:freq_lower_edge ... core:freq_upper_edge`` is set against the ``core:frequency`` of the
     capture that holds its ``core:sample_start`` (the last capture that starts at or before it) and the recording's
@@ -119,6 +127,10 @@ def tune_from_annotation(meta: dict, k: int, oversample=2.0) -> tuple:
     if not held or "core:frequency" not in held[-1]:
         raise ValueError(f"annotation {k}: the capture that holds sample {at} has no core:frequency")
     shift_hz = float(held[-1]["core:frequency"]) - (lo + hi) / 2.0
+    if rational:
+        from fractions import Fraction
+        from .resample import DESIGN_MAX, rational_ratio
+        return shift_hz, rational_ratio(Fraction(r) * Fraction(hi - lo) / Fraction(fs), DESIGN_MAX, DESIGN_MAX)
     return shift_hz, int(min(4096, max(1, np.floor(fs / (r * (hi - lo))))))
 
 
@@ -149,14 +161,65 @@ def resolve_tune(meta: dict, tune: dict) -> tuple:
     return shift, D, np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
 
 
+class ResolvedResample(tuple):
+    """``(shift in cycles per sample, L, D, float32 taps)``: what :func:`resolve_resample` returns, and takes back unchanged
+    as a ``tune`` of :func:`extract_sigmf` (a caller that needs L and D resolves once and passes the result on)."""
+    __slots__ = ()
+
+
+def resolve_resample(meta: dict, tune) -> ResolvedResample:
+    """The rational forms of ``tune`` -- ``dict(annotation=k, oversample=r, rational=True, taps=None)`` or ``dict(shift_hz=F,
+    resample=(L, D), taps=None)`` -- -> ``(shift in cycles per sample, L, D, float32 taps)``.  ``taps``: None for
+    :func:`amcpy_amd.resample.design_resample_lowpass`'s default, a tap count, or the taps at the upsampled rate."""
+    from fractions import Fraction
+    from .resample import design_resample_lowpass, out_samples
+    if isinstance(tune, ResolvedResample):
+        return tune
+    if "annotation" in tune:
+        if set(tune) - {"annotation", "oversample", "rational", "taps"}:
+            raise ValueError("tune: annotation, oversample, rational and taps, or shift_hz, resample and taps")
+        shift_hz, (L, D) = tune_from_annotation(meta, tune["annotation"], tune.get("oversample", 2.0), rational=True)
+    else:
+        if set(tune) - {"shift_hz", "resample", "taps", "rational"} or "resample" not in tune:
+            raise ValueError("tune: annotation, oversample, rational and taps, or shift_hz, resample and taps")
+        shift_hz = float(tune.get("shift_hz", 0.0))
+        L, D = (int(v) for v in tune["resample"])
+    shift = Fraction(0)
+    if shift_hz != 0.0:
+        fs = (meta.get("global") or {}).get("core:sample_rate")
+        if fs is None or float(fs) <= 0.0:
+            raise ValueError("tune: a shift in Hz needs the global core:sample_rate")
+        shift = Fraction(shift_hz) / Fraction(float(fs))
+    taps = tune.get("taps")
+    if taps is None or isinstance(taps, (int, np.integer)):
+        taps = design_resample_lowpass(L, D, taps)
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+    out_samples(0, taps.shape[0], L, D)                          # the limits
+    return ResolvedResample((shift, L, D, taps))
+
+
+def is_rational_tune(tune) -> bool:
+    """Whether a ``tune`` asks for the rational resampler: a dict with ``resample=(L, D)`` or ``rational=True``, or what
+    :func:`resolve_resample` made of one."""
+    return isinstance(tune, ResolvedResample) or (isinstance(tune, dict) and ("resample" in tune or bool(tune.get("rational", False))))
+
+
 # the plain numpy dtype and trailing shape of one stored sample, for the tuned path's chunks
 _PLAIN = {"cf32": (np.dtype("<c8"), ()), "sc16": (np.dtype("<i2"), (2,)), "ci8": (np.dtype("i1"), (2,)), "cu8": (np.dtype("u1"), (2,))}
 
 
 def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, chunk_samples):
-    """The tuned path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.ddc.Channelizer` in chunks."""
+    """The tuned path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.ddc.Channelizer` -- or, a
+    rational ``tune``, a :class:`amcpy_amd.resample.Resampler` -- in chunks."""
     from .ddc import Channelizer
-    shift, D, taps = resolve_tune(rec["meta"], tune)
+    if is_rational_tune(tune):
+        from .resample import Resampler
+        shift, L, D, taps = resolve_resample(rec["meta"], tune)
+    else:
+        if isinstance(tune, dict) and tune.get("rational", True) is False:
+            tune = {k: v for k, v in tune.items() if k != "rational"}
+        shift, D, taps = resolve_tune(rec["meta"], tune)
+        L = 1
     fmt = rec["sample_format"]
     plain, tail = _PLAIN[fmt]
     on_gpu = tune_compute is None
@@ -172,7 +235,10 @@ def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune
             continue
         # (mode "c": private pages, never written -- torch.from_numpy wants a writable array, and "r+" would want a writable file)
         src = np.memmap(rec["data_path"], dtype=plain, mode="c", offset=off, shape=(n_samples,) + tail)
-        chan = Channelizer(taps, D, shift, fmt, scale, compute=tune_compute)
+        if is_rational_tune(tune):
+            chan = Resampler(taps, L, D, shift, fmt, scale, compute=tune_compute)
+        else:
+            chan = Channelizer(taps, D, shift, fmt, scale, compute=tune_compute)
         ys, have = [], 0
         for c0 in range(0, n_samples, chunk_samples):
             chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
@@ -194,7 +260,7 @@ def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune
                 parts.append(np.asarray(compute(frames.cpu().numpy()), dtype=np.float32))
         else:
             parts.append(np.asarray(compute(np.concatenate(ys)[:n * N].reshape(n, N)), dtype=np.float32))
-        starts.append(start + N * D * np.arange(n, dtype=np.int64))
+        starts.append(start + N * D * np.arange(n, dtype=np.int64) // L)
     if not parts:
         return np.empty((0, 18), dtype=np.float32), np.empty((0,), dtype=np.int64)
     return np.concatenate(parts), np.concatenate(starts)
@@ -293,6 +359,12 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     features are computed on the resident result.  ``frame_start[k]`` is ``segment start + k * frame_size * D``, the first
     input sample that contributes to frame k.  ``tune_compute``: an injected down-converter over numpy chunks (tests, as
     :class:`amcpy_amd.ddc.Channelizer`'s ``compute``); ``compute`` then sees the decimated complex64 frames.
+    The RATIONAL forms, ``dict(annotation=k, oversample=r, rational=True)`` (L and D within 255, so that the default taps
+    exist: :func:`tune_from_annotation`; it takes ``taps`` too) and ``dict(shift_hz=F, resample=(L, D),
+    taps=None)`` (``taps``: None for :func:`amcpy_amd.resample.design_resample_lowpass`'s default, a tap count, or the taps at
+    the upsampled rate), go through a :class:`amcpy_amd.resample.Resampler` instead -- L outputs for every D inputs, so the
+    emitter comes out at the oversampling asked for, not at the next integer's: ``frame_start[k] = segment start +
+    floor(k * frame_size * D / L)``; ``tune_compute`` is then that class's ``compute``.
 
     ``channelize`` (not together with ``tune``): the recording holds emitters on a raster --
     ``dict(channels=C, oversample=1|2, taps_per_channel=16, taps=None, shift_hz=0.0)``.  Every segment is read in chunks and

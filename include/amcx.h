@@ -96,10 +96,12 @@ extern "C" {
  * 10 = frames of 8-bit IQ (ci8, cu8), widened on the device: AMCX_IQ8_*, amcx_features_iq8, amcx_features_iq8_workspace_bytes,
  * amcx_kernel_name_iq8, AMCX_SRC_CI8 / AMCX_SRC_CU8 for the strided host / file entries and amcx_stage_host / _file,
  * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host;
- * 11 = the digital down-converter; 12 = the polyphase filter bank (both listed behind the define). */
-#define AMCX_ABI_VERSION 12
+ * 11 = the digital down-converter; 12 = the polyphase filter bank; 13 = the rational resampler (all listed behind the define). */
+#define AMCX_ABI_VERSION 13
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
- *   ABI 12: the line above               -- the polyphase filter bank: amcx_filter_bank, amcx_filter_bank_out_samples,
+ *   ABI 13: the line above               -- the rational resampler: amcx_resample, amcx_resample_out_samples,
+ *                                            amcx_resample_plan, amcx_kernel_name_resample
+ *   ABI 12: #define AMCX_ABI_VERSION 12   -- the polyphase filter bank: amcx_filter_bank, amcx_filter_bank_out_samples,
  *                                            amcx_filter_bank_plan, amcx_kernel_name_bank
  *   ABI 11: #define AMCX_ABI_VERSION 11   -- the digital down-converter: amcx_tune_decimate, amcx_tune_decimate_out_samples,
  *                                            amcx_tune_decimate_plan, amcx_kernel_name_ddc
@@ -354,6 +356,54 @@ int amcx_filter_bank_plan(int32_t n_taps, int32_t channels, int32_t decim, int32
                           int32_t* max_workgroups, int32_t* lds_bytes);
 
 /*
+ * ABI 13.  THE RATIONAL RESAMPLER: tune, low-pass and change the sample rate by L / D where a recording lies.  The down-converter
+ * changes the rate by an integer only; an emitter whose band is fs / 3.9 wide then comes out anywhere between r and 2 r times
+ * oversampled, and the features (the spectral peak, the cumulants) change with that ratio.
+ *   - src_dev, src_kind, n_samples, scale, phase0, phase_step, taps_dev: as amcx_tune_decimate (the same sample values, the same
+ *     mixer).  T = n_taps REAL taps h[0 .. T - 1] given AT THE UPSAMPLED RATE (L times the input's); L = interp, D = decim;
+ *     tau0 = phase_index0, the phase of the first output, 0 <= tau0 < L.  Conceptually v is zero-stuffed by L, filtered with h,
+ *     and every D-th result is kept; nothing is zero-stuffed in practice:
+ *         phi(n) = (phase0 + n * phase_step) mod 2^64        (uint64 arithmetic, exact; n counts THIS CALL's input samples)
+ *         v[n]   = x[n] * exp(+2 pi j * phi(n) / 2^64)        (phi < 2^32: v = x, the product is skipped)
+ *         P      = ceil(T / L)                                taps of the longest phase
+ *         t_m    = m D + tau0,   p_m = t_m mod L,   n_m = (P - 1) + floor(t_m / L)
+ *         y[m]   = sum_{q >= 0, p_m + q L < T} h[p_m + q L] * v[n_m - q],   m = 0 ... M - 1
+ *         M      = S < P ? 0 : ((S - P + 1) L - 1 - tau0 < 0 ? 0 : ((S - P + 1) L - 1 - tau0) / D + 1),   S = n_samples
+ *     y is packed complex64 at out_c64_dev, which has room for out_capacity_samples.
+ *   - limits: 1 <= n_taps <= 4096, 1 <= interp <= 256, 1 <= decim <= 4096, 0 <= n_samples < 2^40, 0 <= phase_index0 < interp.
+ *     Alignment: src 8 / 4 / 2 bytes (c64 / sc16 / 8-bit), taps 4, out 8.
+ *   - EMPTY PHASES: a phase with no tap (T < L, p_m >= T) gives exactly +0 + 0j.  A tap index >= T does not exist: it is never
+ *     read, and no sample enters a sum for it.  (A tile's span of samples is loaded whole -- the oldest sample of a phase one
+ *     tap short, the samples between two windows where D > P L: all inside [0, n_samples), mixed, and never multiplied into
+ *     an output, so a NaN there reaches nothing.)
+ *   - GAIN: none is applied; the taps carry it (a low-pass with DC gain L keeps the signal's amplitude).
+ *   - SUMMATION ORDER: one product h[p_m] v[n_m], then one FMA per component in ascending q.  With L = 1 (tau0 = 0) that is the
+ *     order k = 0 ... T - 1 of amcx_tune_decimate: for n_taps <= 2048 the output equals amcx_tune_decimate's bit for bit, in all
+ *     four formats.
+ *   - POSITION INDEPENDENCE: the bits of y[m] depend only on its samples, the taps, phi at those samples and p_m -- not on m's
+ *     place in the call, the tile, the grid, the lane or which load read a sample.
+ *   - CONTINUATION: a stream cut after any whole number M of outputs equals one call bit for bit: the next call drops
+ *     floor((M D + tau0) / L) inputs, takes phase_index0 = (M D + tau0) mod L and phase0 advanced by the dropped inputs.
+ *   - the four formats give the same bits as the complex64 call on the widened samples.
+ *   - accuracy: |y[m] - exact| <= (P + 8) 2^-24 sum_q |h[p_m + q L]| |x[n_m - q]| (tests/resample_ref.py).
+ * Asynchronous on the caller's stream, allocates nothing, capturable in a graph.  The checks come before any device call, in
+ * this order: src_kind; scale (integer kinds only: finite float32 > 0); n_taps, interp, decim, n_samples and phase_index0 ranges;
+ * out_capacity_samples >= M; M == 0 is AMCX_OK here, null pointers allowed; null pointers and alignment; a pointer on another
+ * device.
+ * amcx_resample_out_samples: M, or -1 for arguments the entry refuses.
+ * amcx_resample_plan (host-only): how a call is cut -- *tile_outputs consecutive outputs per tile, no tile's input span (staged
+ * in LDS) longer than *max_span_samples, a persistent grid of at most *max_workgroups workgroups on the current device (256 CUs
+ * assumed where there is none), *lds_bytes of dynamic LDS per workgroup (the padded span and the phase-major taps); any pointer
+ * may be NULL.  AMCX_EINVAL for n_taps / interp / decim out of range.
+ */
+int64_t amcx_resample_out_samples(int64_t n_samples, int32_t n_taps, int32_t interp, int32_t decim, int32_t phase_index0);
+int amcx_resample(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0, uint64_t phase_step,
+                  const float* taps_dev, int32_t n_taps, int32_t interp, int32_t decim, int32_t phase_index0,
+                  void* out_c64_dev, int64_t out_capacity_samples, void* hip_stream);
+int amcx_resample_plan(int32_t n_taps, int32_t interp, int32_t decim, int32_t* tile_outputs, int32_t* max_span_samples,
+                       int32_t* max_workgroups, int32_t* lds_bytes);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -442,6 +492,9 @@ int amcx_kernel_name_ddc(int32_t src_kind, char* buf, int32_t buf_len);
 /* ABI 12: the kernel amcx_filter_bank runs for this src_kind (host-only): amcx_bank_c64_kernel, amcx_bank_sc16_kernel, or
  * amcx_bank_iq8_kernel for both 8-bit kinds; AMCX_EINVAL for any other kind. */
 int amcx_kernel_name_bank(int32_t src_kind, char* buf, int32_t buf_len);
+/* ABI 13: the kernel amcx_resample runs for this src_kind (host-only), a static string: amcx_resample_c64_kernel,
+ * amcx_resample_sc16_kernel, or amcx_resample_iq8_kernel for both 8-bit kinds; NULL for any other kind. */
+const char* amcx_kernel_name_resample(int32_t src_kind);
 
 /* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
  * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
