@@ -10,8 +10,13 @@ THE CRITERION: |y - y64| <= (P + 8) 2^-24 S[m] for every output.  This is tests/
 of one phase in place of the T of the down-converter: P - 1 FMAs and one product, each rounding once (2^-24 relative to a
 partial sum that sum_q |h||v| bounds), is the worst case of ANY fp32 order of the terms; the other 8 x 2^-24 |h||x| per term
 cover the mixed sample itself (the angle's fp32 rounding and the two polynomials, under 2.5 x 2^-24 together, and the rounded
-complex product, under 2.9 x 2^-24 in magnitude).  Derived, not fitted: a dropped or shifted tap costs at least S / (2 P) with
-taps from +-[0.5, 1], hundreds of times the bound.  A phase with no tap has S = 0 and must be exactly 0."""
+complex product, under 2.9 x 2^-24 in magnitude).  Derived, not fitted.  A phase with no tap has S = 0 and must be exactly 0.
+
+WHAT IT SEES.  With taps from +-[0.5, 1] a dropped or shifted tap costs at least S / (2 P), which is 2^24 / (2 P (P + 8)) times the
+bound: 20 000 at P = 17 (the designer's 16 taps per phase), 1900 at P = 63 -- and 2 at P = 2048, below 1 from P = 2893 on, 0.5
+at P = 4096 (L = 1, T = 4096), where a single missing term passes the bound about as often as not.  The shapes with thousands
+of taps per phase are held to an EQUALITY instead: tests/chain_exact.py makes data on which fp32 arithmetic in any order is
+exact, and tests/test_gpu_chain_exact.py compares every output with == against int64 arithmetic."""
 import numpy as np
 
 from tests.ddc_ref import MASK64, ODD_STEP, U, make_taps, phases, widen  # noqa: F401  (shared with the tests)

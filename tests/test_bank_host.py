@@ -53,7 +53,11 @@ def test_resource_table_lists_the_three_kernels_without_spills():
 
 
 SHAPES = [(1, 2, 1), (5, 2, 2), (4, 4, 4), (19, 8, 5), (64, 8, 8), (128, 8, 4), (4096, 2, 2), (4096, 8, 8), (200, 64, 32),
-          (1024, 64, 64), (513, 256, 256), (2048, 256, 128), (4096, 256, 128), (4096, 256, 256), (4096, 256, 1), (1, 256, 256)]
+          (1024, 64, 64), (513, 256, 256), (2048, 256, 128), (4096, 256, 128), (4096, 256, 256), (4096, 256, 1), (1, 256, 256),
+          # log2 C = 4, 5 and 7 (tests/test_gpu_bank.py), and the largest tap counts at every C (tests/chain_exact.py)
+          (37, 16, 16), (256, 16, 11), (37, 16, 11), (256, 16, 16), (100, 32, 32), (1024, 32, 24), (300, 128, 128), (2048, 128, 96),
+          (300, 128, 96), (512, 128, 128), (4096, 2, 1), (4095, 2, 2), (4096, 4, 4), (4093, 4, 3), (4096, 16, 16), (4095, 32, 32),
+          (4096, 128, 96)]
 
 
 def test_out_samples_and_plan():
@@ -75,6 +79,11 @@ def test_out_samples_and_plan():
         span = (tile - 1) * D + T
         # the tile's span of mixed samples, the tile x C array, the taps: all within what the plan reports, within a CU's LDS
         assert 8 * span + 8 * tile * Cn + 4 * T <= lds <= 160 * 1024, (T, Cn, D, tile, lds)
+    # the largest request of any shape is C = 2, T = 4096, D = 2 (amcx_bank_kernel.h): 131 072 bytes
+    assert _lib.filter_bank_plan(4096, 2, 2)[2] == 131072
+    assert max(_lib.filter_bank_plan(4096, Cn, D)[2] for Cn in (2, 4, 8, 16, 32, 64, 128, 256) for D in (1, 2, Cn // 2, Cn)) == 131072
+    # C = 128 is the one channel count whose tile is 32 (tests/test_gpu_bank.py runs it)
+    assert _lib.filter_bank_plan(300, 128, 96)[0] == 32 and _lib.filter_bank_plan(4096, 128, 128)[0] == 32
     for T, Cn, D in ((0, 2, 1), (4097, 2, 1), (1, 2, 0), (1, 2, 3), (1, 3, 1), (1, 512, 1), (1, 1, 1)):
         with pytest.raises(ValueError):
             _lib.filter_bank_plan(T, Cn, D)

@@ -18,8 +18,9 @@ pytestmark = pytest.mark.gpu
 FORMATS = list(ddc.FORMATS)
 STEP = Fraction(ddc_ref.ODD_STEP, 1 << 64)
 INDEX0 = (1 << 33) + 12345                  # odd, 57 mod 256: no multiple of any C
-SHAPES = [(2, 1, 1), (2, 5, 2), (4, 4, 4), (8, 19, 5), (8, 64, 8), (64, 200, 32), (64, 1024, 64), (256, 513, 256), (256, 4096, 128)]
-ALL_FORMATS_AT = [(8, 19, 5), (64, 200, 32), (256, 513, 256)]
+SHAPES = [(2, 1, 1), (2, 5, 2), (4, 4, 4), (8, 19, 5), (8, 64, 8), (64, 200, 32), (64, 1024, 64), (256, 513, 256), (256, 4096, 128),
+          (16, 37, 16), (16, 256, 11), (32, 100, 32), (32, 1024, 24), (128, 300, 128), (128, 2048, 96)]
+ALL_FORMATS_AT = [(8, 19, 5), (64, 200, 32), (256, 513, 256), (32, 100, 32), (128, 300, 128)]
 POOL = 40_000                               # samples: the longest stream of these tests and some
 
 
@@ -85,7 +86,7 @@ def test_criterion_against_float64(Cn, T, D, fmt):
     assert r <= 1.0, (fmt, Cn, T, D, r)
 
 
-@pytest.mark.parametrize("Cn", [8, 64])
+@pytest.mark.parametrize("Cn", [2, 4, 8, 16, 32, 64, 128, 256])
 def test_every_channel_every_branch(Cn):
     """One non-zero sample at each position of a window in turn (T = 2 C: both taps of every branch), batched as one stream
     with gaps of 2 T >= T between them.  Impulse j sits where the windows that hold it hold it at taps k = j mod D and beyond
@@ -105,16 +106,15 @@ def test_every_channel_every_branch(Cn):
     y = _run(torch.from_numpy(x).cuda(), T, Cn, D, sample_index0=INDEX0).astype(np.complex128)
     want = np.zeros((Cn, M), np.complex128)
     s = np.zeros(M)
-    hit = 0
-    for j in range(T):
-        for m in range(M):
-            k = m * D + T - 1 - int(pos[j])
-            if 0 <= k < T:
-                assert s[m] == 0.0                                       # one impulse per window
-                a = (INDEX0 + int(pos[j])) % Cn
-                want[:, m] = h[k] * complex(amp[j]) * np.exp(-2j * np.pi * ((np.arange(Cn) * a) % Cn) / Cn)
-                s[m] = abs(h[k]) * abs(complex(amp[j]))
-                hit += 1
+    k = np.arange(M)[None, :] * D + T - 1 - pos[:, None]                # (T, M): the tap that meets impulse j in output m
+    held = (0 <= k) & (k < T)
+    assert held.sum(axis=0).max() == 1                                  # one impulse per window
+    hit = int(held.sum())
+    j, m = np.nonzero(held)
+    a = (INDEX0 + pos[j]) % Cn
+    amp128 = amp.astype(np.complex128)
+    want[:, m] = (h[k[j, m]] * amp128[j])[None, :] * np.exp(-2j * np.pi * ((np.arange(Cn)[:, None] * a[None, :]) % Cn) / Cn)
+    s[m] = np.abs(h[k[j, m]]) * np.abs(amp128[j])
     assert hit == 2 * T and len({(int(pos[j]) + INDEX0) % Cn for j in range(T)}) == Cn        # every tap, every rotation
     assert (y[:, s == 0.0] == 0).all(), "an output whose window holds no sample is not exactly 0"
     r = bank_ref.worst_ratio(y, want, s, T, Cn)
@@ -122,7 +122,7 @@ def test_every_channel_every_branch(Cn):
     assert r <= 1.0
 
 
-@pytest.mark.parametrize("Cn,T,D", [(8, 64, 8), (8, 2048, 4), (64, 200, 32), (64, 1024, 64)])
+@pytest.mark.parametrize("Cn,T,D", [(8, 64, 8), (8, 2048, 4), (64, 200, 32), (64, 1024, 64), (16, 256, 16), (128, 512, 128)])
 def test_against_the_down_converter(Cn, T, D):
     """Every channel against amcx_tune_decimate with the equivalent phases (shift - c / C, the same sample_index0): both are
     within their criteria of the same exact value, so they differ by at most the sum of the two bounds."""
@@ -145,7 +145,7 @@ def test_against_the_down_converter(Cn, T, D):
     assert worst <= 1.0
 
 
-@pytest.mark.parametrize("Cn,T,D", [(8, 19, 5), (64, 200, 32), (4, 1, 4)])
+@pytest.mark.parametrize("Cn,T,D", [(8, 19, 5), (64, 200, 32), (4, 1, 4), (16, 37, 11), (128, 300, 96)])
 @pytest.mark.parametrize("fmt", ["cf32", "cu8"])
 def test_chunk_invariance(fmt, Cn, T, D):
     torch = _torch()
@@ -172,7 +172,7 @@ def test_chunk_invariance(fmt, Cn, T, D):
     assert whole0.tobytes() != whole.tobytes()
 
 
-@pytest.mark.parametrize("Cn,T,D", [(8, 19, 5), (256, 513, 256)])
+@pytest.mark.parametrize("Cn,T,D", [(8, 19, 5), (256, 513, 256), (32, 100, 32), (128, 300, 96)])
 @pytest.mark.parametrize("fmt", ["sc16", "ci8", "cu8"])
 def test_the_four_formats_give_the_same_bits(fmt, Cn, T, D):
     torch = _torch()

@@ -126,6 +126,55 @@ def test_zero_phase_one_tap_is_the_widened_input(fmt):
     assert y.cpu().numpy().tobytes() == want.tobytes()
 
 
+def test_the_mixer_on_its_own():
+    """x = 1 + 0j, one tap of 1.0, D = 1: y[n] is ddc_mixer(p) itself (fma(1, w, -+0) is exact), and with shift = s / 2^32 the
+    angle is p = ((sample_index0 + n) s) mod 2^32.  Walked: every octant boundary k 2^29 +- 2^16, where the quarter turn q and
+    the remainder r of the reduction change (k = 0 wraps the phase accumulator through 0); 2^20 angles at the odd stride 4099;
+    the angle 0xDD9F6111 and its seven images under the octant symmetries.
+
+    THE BOUND is the mixer's own share of tests/ddc_ref.py's derivation: |w - exp(2 pi j p / 2^32)| <= 2.5 x 2^-24 (the angle's
+    fp32 rounding and the two polynomials).  The same operation sequence in C on the CPU (fmaf, no contraction) over all 2^32
+    angles: worst 2.458 x 2^-24, at p = 0xDD9F6111 (w = 0x3F2A2797, 0xBF3F4492) and its images -- inside, by 1.7 %.
+    Exactly (1, 0), (0, 1), (-1, 0), (0, -1) at the multiples of 2^30; w(p + 2^30) = (-w.y, w.x) bit for bit (the quarter turns
+    are swaps and sign changes); p = 0 returns x untouched."""
+    torch = _torch()
+    one = torch.ones(1, device="cuda")
+
+    def walk(first, n, stride=1):
+        """(p (n,) uint64, y (n,) complex64): the mixer at p = (first + i stride) mod 2^32"""
+        index0 = (first * pow(stride, -1, 1 << 32)) % (1 << 32)
+        y = ddc.tune_decimate(torch.ones(n, dtype=torch.complex64, device="cuda"), one, 1, shift=Fraction(stride, 1 << 32),
+                              sample_index0=index0)
+        torch.cuda.synchronize()
+        return (first + np.arange(n, dtype=np.uint64) * np.uint64(stride)) % np.uint64(1 << 32), y.cpu().numpy()
+
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    corner = 0xDD9F6111
+    images = sorted({(sign * corner + k * (1 << 30)) % (1 << 32) for sign in (1, -1) for k in range(4)})
+    assert len(images) == 8 and len({p >> 29 for p in images}) == 8                  # one in every octant
+    runs = [((k << 29) - (1 << 16), (1 << 17) + 1, 1) for k in range(8)] + [(0, 1 << 20, 4099)] + [(p, 1, 1) for p in images]
+    worst, worst_at, worst_bits, turns = 0.0, None, None, 0
+    for first, n, stride in runs:
+        p, y = walk(first % (1 << 32), n, stride)
+        assert y.shape == (n,) and y.dtype == np.complex64
+        err = np.abs(y.astype(np.complex128) - np.exp(2j * np.pi * (p.astype(np.float64) / 4294967296.0))) / ddc_ref.U
+        i = int(np.argmax(err))
+        if err[i] > worst:
+            worst, worst_at, worst_bits = float(err[i]), int(p[i]), (int(bits(y.real)[i]), int(bits(y.imag)[i]))
+        assert err[i] <= 2.5, (hex(int(p[i])), float(err[i]), hex(int(bits(y.real)[i])), hex(int(bits(y.imag)[i])))
+        for q, (re, im) in enumerate(((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))):
+            at = p == np.uint64(q << 30)
+            turns += int(at.sum())
+            assert (y.real[at] == re).all() and (y.imag[at] == im).all(), (q, y[at])
+        assert y[p == 0].tobytes() == np.ones(int((p == 0).sum()), np.complex64).tobytes()     # x untouched, +0 included
+        p4, y4 = walk((first + (1 << 30)) % (1 << 32), n, stride)
+        assert np.array_equal(p4, (p + np.uint64(1 << 30)) % np.uint64(1 << 32))
+        assert np.array_equal(bits(y4.real), bits(-y.imag)) and np.array_equal(bits(y4.imag), bits(y.real)), (hex(first), stride)
+    assert turns >= 4 and worst_at is not None
+    print(f"ddc mixer alone: {sum(n for _, n, _ in runs)} angles: worst |w - exp| = {worst:.4f} x 2^-24 at p = {worst_at:#010x} "
+          f"(w = {worst_bits[0]:#010x}, {worst_bits[1]:#010x}); {turns} exact quarter turns")
+
+
 @pytest.mark.parametrize("T,D", [(63, 4), (5, 17), (2048, 1)])
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_chunk_invariance(fmt, T, D):

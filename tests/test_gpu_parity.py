@@ -200,7 +200,7 @@ def test_full_snr_grid_against_oracle(N):
         _assert_parity(_run(x, variant), gold, x, f"full SNR grid N={N} {variant}")
 
 
-@pytest.mark.parametrize("N", [128, 512, 1024, 2048, 4096, 8192, 16384])
+@pytest.mark.parametrize("N", [128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768])
 def test_cancelling_cumulants_take_the_fp64_path(N):
     """Frames built so that whole cumulants cancel: noiseless QPSK at 8 samples per symbol with EXACTLY balanced squares
     (as many symbols with x^2 = +u as with x^2 = -u: mean x^2 = 0, so C41 = m41 - 3 m20 m21 and C60 vanish up to the
