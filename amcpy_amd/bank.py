@@ -19,8 +19,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _lib
-from .ddc import FORMATS, _KINDS, _MASK64, _format_of, _scale_of, phase_step_of
+from . import _stream
 
 MAX_TAPS, MAX_CHANNELS = 4096, 256
 
@@ -52,12 +51,7 @@ def design_bank_lowpass(channels: int, taps_per_channel: int = 16, decim=None) -
         raise ValueError(f"taps_per_channel must be at least 1, got {taps_per_channel!r}")
     T = C * P
     _check_shape(T, C, C if decim is None else decim)
-    fc = 0.5 / C
-    n = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
-    h = 2.0 * fc * np.sinc(2.0 * fc * n)
-    h *= 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(T, dtype=np.float64) / (T - 1))
-    h = (h + h[::-1]) / 2.0                                   # symmetric to the bit
-    return (h / h.sum()).astype(np.float32)
+    return _stream.windowed_sinc(T, 0.5 / C)
 
 
 def channel_frequencies(channels: int, sample_rate: float = 1.0, center: float = 0.0, shift=0.0) -> np.ndarray:
@@ -83,40 +77,21 @@ def filter_bank(x, taps, channels: int, decim: int, *, shift=0.0, sample_index0:
     Returns complex64 (C, M), M = :func:`out_samples`."""
     import torch
 
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch tensor (complex64 (S,), or int16 / int8 / uint8 (S, 2))")
-    fmt = _format_of(x)
-    scale = _scale_of(fmt, scale)
-    if not x.is_cuda:
-        raise ValueError("x must live in GPU memory")
-    if not x.is_contiguous():
-        raise ValueError("x must be one contiguous stream")
-    if not isinstance(taps, torch.Tensor):
-        taps = torch.from_numpy(np.ascontiguousarray(np.asarray(taps, dtype=np.float32))).to(x.device)
-    if taps.dtype != torch.float32 or taps.dim() != 1 or taps.device != x.device:
-        raise TypeError("taps must be a one-dimensional float32 tensor on x's device")
-    taps = taps.contiguous()
-    S, T, C, D = int(x.shape[0]), int(taps.shape[0]), int(channels), int(decim)
-    M = out_samples(S, T, C, D)
-    step = phase_step_of(shift)
-    index0 = int(sample_index0) & _MASK64
-    phase0 = (index0 * step) & _MASK64
+    f = _stream.front(x, taps, scale, shift, sample_index0, lambda S, T: out_samples(S, T, channels, decim))
+    C, D, M = int(channels), int(decim), f.M
     if out is None:
         out = torch.empty((C, M), dtype=torch.complex64, device=x.device)
     elif (out.dtype != torch.complex64 or out.device != x.device or out.dim() != 2 or out.shape[0] != C or out.shape[1] < M
           or (out.shape[1] > 1 and out.stride(1) != 1) or out.stride(0) < out.shape[1]):
         raise ValueError(f"out must be a complex64 ({C}, >= {M}) tensor on x's device with contiguous rows")
     stride = int(out.stride(0)) if C > 1 and out.shape[1] > 0 else M
-    _lib.require_torch_runtime()
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lib.amcx_filter_bank(x.data_ptr() if S else None, _KINDS[fmt], S, scale, phase0, step, index0, taps.data_ptr(),
-                                        T, C, D, out.data_ptr() if M else None, stride, (C - 1) * stride + M, stream))
+    _stream.launch(x, lambda lib, stream: lib.amcx_filter_bank(
+        x.data_ptr() if f.S else None, f.kind, f.S, f.scale, f.phase0, f.step, f.index0, f.taps.data_ptr(), f.T, C, D,
+        out.data_ptr() if M else None, stride, (C - 1) * stride + M, stream))
     return out[:, :M]
 
 
-class FilterBank:
+class FilterBank(_stream.Stream):
     """The streaming form of :func:`filter_bank`: ``push(chunk)`` returns the ``(C, new)`` outputs the stream so far completes.
 
     Keeps the unconsumed tail of the input and the absolute index of the sample the next window begins at, as
@@ -126,52 +101,19 @@ class FilterBank:
     sample_index0=..., scale=...)`` over numpy chunks (tests); the default is :func:`filter_bank` over GPU tensors, with the
     taps uploaded once."""
 
+    _NOUN, _one_shot = "filter bank", staticmethod(filter_bank)
+
     def __init__(self, taps, channels: int, decim: int, shift=0.0, fmt: str = "cf32", scale=None, *, compute=None):
-        if fmt not in FORMATS:
-            raise ValueError(f"fmt must be one of {FORMATS}, not {fmt!r}")
-        self.taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
-        if self.taps.ndim != 1:
-            raise ValueError("taps must be one-dimensional")
-        self.channels, self.decim, self.shift, self.fmt = int(channels), int(decim), shift, fmt
+        super().__init__(taps, shift, fmt, scale, compute, channels=channels, decim=decim)
+
+    def _limits(self):
         _check_shape(self.taps.shape[0], self.channels, self.decim)
-        phase_step_of(shift)
-        self.scale = _scale_of(fmt, scale)
-        self.index = 0                 # absolute index of the sample the next output's window begins at
-        self._tail = None              # the samples from there on that have arrived ...
-        self._skip = 0                 # ... or, decim > T, how many are still to be dropped before it
-        self._compute = compute
-        self._taps_dev = None
 
-    def _run(self, buf):
-        kw = dict(shift=self.shift, sample_index0=self.index, scale=self.scale)
-        if self._compute is not None:
-            return self._compute(buf, self.taps, self.channels, self.decim, **kw)
-        import torch
-        if self._taps_dev is None or self._taps_dev.device != buf.device:
-            self._taps_dev = torch.from_numpy(self.taps).to(buf.device)
-        return filter_bank(buf, self._taps_dev, self.channels, self.decim, **kw)
+    def _args(self):
+        return self.channels, self.decim
 
-    def push(self, chunk):
-        """The new outputs (complex64 (C, new), possibly none) of the stream extended by ``chunk``."""
-        if _format_of(chunk) != self.fmt:
-            raise TypeError(f"this filter bank takes {self.fmt} chunks")
-        if self._skip:                                               # decim > T: samples between two windows, never read
-            drop = min(self._skip, int(chunk.shape[0]))
-            chunk, self._skip = chunk[drop:], self._skip - drop
-        if self._tail is None or self._tail.shape[0] == 0:
-            buf = chunk
-        elif chunk.shape[0] == 0:
-            buf = self._tail
-        elif isinstance(chunk, np.ndarray):
-            buf = np.concatenate([self._tail, chunk])
-        else:
-            import torch
-            buf = torch.cat([self._tail, chunk])
-        S = int(buf.shape[0])
-        y = self._run(buf)
-        used = out_samples(S, self.taps.shape[0], self.channels, self.decim) * self.decim   # where the next window begins
-        self._skip += max(0, used - S)                               # (a skip still pending left buf empty: used == 0)
-        tail = buf[min(used, S):]                                    # short: a copy, not a view that keeps the chunk alive
-        self._tail = tail.copy() if isinstance(tail, np.ndarray) else tail.clone()
-        self.index += used
-        return y
+    def _outputs(self, S):
+        return out_samples(S, self.taps.shape[0], self.channels, self.decim)
+
+    def _consumed(self, M):
+        return M * self.decim

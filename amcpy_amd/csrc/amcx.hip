@@ -463,31 +463,69 @@ bool mlp_shape_ok(const int32_t* widths, int32_t n_linear) {
   return true;
 }
 
-// resident workgroups per CU of a down-converter launch (amcx_ddc_kernel.h): what its LDS leaves room for, eight at most
-int ddc_wgs_per_cu(int n_taps, int decim) {
-  const int fit = (int)((size_t)(160 * 1024) / amcx::ddc_lds_bytes(n_taps, decim));
-  return fit < 1 ? 1 : fit > 8 ? 8 : fit;
+// ---- what the stream entries share (amcx_tune_decimate, amcx_filter_bank, amcx_resample) ------------------------------------
+// What such an entry derives from src_kind.
+struct StreamSrc {
+  int32_t kind;
+  bool integer() const { return kind == AMCX_SRC_SC16 || kind == AMCX_SRC_CI8 || kind == AMCX_SRC_CU8; }
+  // a source kind at all, and for the integer ones a scale the kernels can multiply by
+  bool ok(float scale) const { return (kind == AMCX_SRC_C64 || integer()) && (!integer() || int_scale_ok(scale)); }
+  unsigned src_align() const { return kind == AMCX_SRC_C64 ? 7u : kind == AMCX_SRC_SC16 ? 3u : 1u; }      // a sample's bytes, less one
+  float kernel_scale(float scale) const { return integer() ? scale : 1.0f; }
+  unsigned flip4() const { return kind == AMCX_SRC_CU8 ? 0x80808080u : 0u; }
+  // of a family's three: the complex64 kernel's, the sc16 kernel's, the 8-bit kernel's (ci8 and cu8); K{} where `kind` is no source
+  template <class K>
+  K pick(K c64, K sc16, K iq8) const {
+    return kind == AMCX_SRC_C64 ? c64 : kind == AMCX_SRC_SC16 ? sc16 : kind == AMCX_SRC_CI8 || kind == AMCX_SRC_CU8 ? iq8 : K{};
+  }
+};
+
+// a family's kernel with its name; the bank's, which ask for more than 64 KiB of LDS, with their lds_attr_once too
+template <class Kern>
+struct StreamKernel {
+  Kern kern;
+  const char* name;
+};
+struct BankKernel : StreamKernel<decltype(&amcx::amcx_bank_c64_kernel)> {
+  hipError_t (*lds_attr)(int most);
+};
+#define AMCX_NAMED(k) amcx::k, #k
+StreamKernel<decltype(&amcx::amcx_ddc_c64_kernel)> ddc_kernel(StreamSrc s) {
+  return s.pick<StreamKernel<decltype(&amcx::amcx_ddc_c64_kernel)>>(
+      {AMCX_NAMED(amcx_ddc_c64_kernel)}, {AMCX_NAMED(amcx_ddc_sc16_kernel)}, {AMCX_NAMED(amcx_ddc_iq8_kernel)});
+}
+BankKernel bank_kernel(StreamSrc s) {
+  return s.pick<BankKernel>({{AMCX_NAMED(amcx_bank_c64_kernel)}, amcx::lds_attr_once<amcx::amcx_bank_c64_kernel>},
+                            {{AMCX_NAMED(amcx_bank_sc16_kernel)}, amcx::lds_attr_once<amcx::amcx_bank_sc16_kernel>},
+                            {{AMCX_NAMED(amcx_bank_iq8_kernel)}, amcx::lds_attr_once<amcx::amcx_bank_iq8_kernel>});
+}
+StreamKernel<decltype(&amcx::amcx_resample_c64_kernel)> rs_kernel(StreamSrc s) {
+  return s.pick<StreamKernel<decltype(&amcx::amcx_resample_c64_kernel)>>(
+      {AMCX_NAMED(amcx_resample_c64_kernel)}, {AMCX_NAMED(amcx_resample_sc16_kernel)}, {AMCX_NAMED(amcx_resample_iq8_kernel)});
+}
+#undef AMCX_NAMED
+
+// the pointers of a call that launches: all there, each aligned to its element, none on another device
+bool stream_ptrs_ok(const void* src, const float* taps, const void* out, StreamSrc s) {
+  if (src == nullptr || taps == nullptr || out == nullptr) return false;
+  if ((reinterpret_cast<uintptr_t>(src) & s.src_align()) || (reinterpret_cast<uintptr_t>(taps) & 3u) ||
+      (reinterpret_cast<uintptr_t>(out) & 7u))
+    return false;
+  return !on_another_device(src) && !on_another_device(taps) && !on_another_device(out);
 }
 
-// resident workgroups per CU of a resampler launch (amcx_resample_kernel.h): what its LDS leaves room for, eight at most
-int rs_wgs_per_cu(int n_taps, int interp, int decim) {
-  const int fit = (int)((size_t)(160 * 1024) / amcx::rs_lds_bytes(n_taps, interp, decim));
-  return fit < 1 ? 1 : fit > 8 ? 8 : fit;
+// resident workgroups per CU of a launch with `lds_bytes` of dynamic LDS: what the CU's 160 KiB leave room for, `cap` at most
+int wgs_per_cu(size_t lds_bytes, int cap) {
+  const int fit = (int)((size_t)(160 * 1024) / lds_bytes);
+  return fit < 1 ? 1 : fit > cap ? cap : fit;
 }
+int ddc_wgs_per_cu(int n_taps, int decim) { return wgs_per_cu(amcx::ddc_lds_bytes(n_taps, decim), 8); }
+int rs_wgs_per_cu(int n_taps, int interp, int decim) { return wgs_per_cu(amcx::rs_lds_bytes(n_taps, interp, decim), 8); }
+int bank_wgs_per_cu(int n_taps, int channels, int decim) { return wgs_per_cu(amcx::bank_lds_bytes(n_taps, channels, decim), 4); }
 
-// resident workgroups per CU of a filter-bank launch (amcx_bank_kernel.h): what its LDS leaves room for, four at most
-int bank_wgs_per_cu(int n_taps, int channels, int decim) {
-  const int fit = (int)((size_t)(160 * 1024) / amcx::bank_lds_bytes(n_taps, channels, decim));
-  return fit < 1 ? 1 : fit > 4 ? 4 : fit;
-}
-
-template <auto Kern, class... A>
-int bank_launch(int64_t grid, size_t lds, hipStream_t stream, A... args) {
-  // the most a bank kernel ever asks for: C = 2 (tile 2048), T = 4096, D = 2
-  if (const hipError_t e = amcx::lds_attr_once<Kern>((int)amcx::bank_lds_bytes(amcx::kBankMaxTaps, 2, 2)); e != hipSuccess)
-    return hip_fail(e, "filter-bank kernel attribute");
-  if (const hipError_t e = amcx::launch(Kern, grid, amcx::kBankThreads, lds, stream, args...); e != hipSuccess)
-    return hip_fail(e, "filter-bank kernel launch");
+int put_kernel_name(const char* name, char* buf, int32_t buf_len) {
+  if (buf == nullptr || buf_len <= 0 || name == nullptr) return AMCX_EINVAL;
+  snprintf(buf, (size_t)buf_len, "%s", name);
   return AMCX_OK;
 }
 
@@ -927,40 +965,25 @@ int amcx_tune_decimate_plan(int32_t n_taps, int32_t decim, int32_t* tile_outputs
 int amcx_tune_decimate(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0,
                        uint64_t phase_step, const float* taps_dev, int32_t n_taps, int32_t decim, void* out_c64_dev,
                        int64_t out_capacity_samples, void* hip_stream) {
-  const bool integer = src_kind == AMCX_SRC_SC16 || src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8;
-  if (src_kind != AMCX_SRC_C64 && !integer) return AMCX_EINVAL;
-  if (integer && !int_scale_ok(scale)) return AMCX_EINVAL;
+  const StreamSrc src{src_kind};
+  if (!src.ok(scale)) return AMCX_EINVAL;
   const int64_t M = amcx_tune_decimate_out_samples(n_samples, n_taps, decim);
   if (M < 0 || out_capacity_samples < M) return AMCX_EINVAL;
   if (M == 0) return AMCX_OK;
-  if (src_dev == nullptr || taps_dev == nullptr || out_c64_dev == nullptr) return AMCX_EINVAL;
-  const unsigned src_align = src_kind == AMCX_SRC_C64 ? 7u : src_kind == AMCX_SRC_SC16 ? 3u : 1u;
-  if ((reinterpret_cast<uintptr_t>(src_dev) & src_align) || (reinterpret_cast<uintptr_t>(taps_dev) & 3u) ||
-      (reinterpret_cast<uintptr_t>(out_c64_dev) & 7u))
-    return AMCX_EINVAL;
-  if (on_another_device(src_dev) || on_another_device(taps_dev) || on_another_device(out_c64_dev)) return AMCX_EINVAL;
+  if (!stream_ptrs_ok(src_dev, taps_dev, out_c64_dev, src)) return AMCX_EINVAL;
   const int tile = amcx::ddc_tile_outputs(n_taps, decim);
   const int64_t n_tiles = (M + tile - 1) / tile;
   const int64_t grid = amcx::persistent_grid(cu_count(), ddc_wgs_per_cu(n_taps, decim), n_tiles, 1);
-  const auto kern = src_kind == AMCX_SRC_C64 ? amcx::amcx_ddc_c64_kernel
-                    : src_kind == AMCX_SRC_SC16 ? amcx::amcx_ddc_sc16_kernel : amcx::amcx_ddc_iq8_kernel;
-  const unsigned flip4 = src_kind == AMCX_SRC_CU8 ? 0x80808080u : 0u;
-  const hipError_t e = amcx::launch(kern, grid, amcx::kDdcThreads, amcx::ddc_lds_bytes(n_taps, decim),
-                                    static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), integer ? scale : 1.0f,
-                                    flip4, (unsigned long long)phase0, (unsigned long long)phase_step, taps_dev, n_taps, decim,
+  const hipError_t e = amcx::launch(ddc_kernel(src).kern, grid, amcx::kDdcThreads, amcx::ddc_lds_bytes(n_taps, decim),
+                                    static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), src.kernel_scale(scale),
+                                    src.flip4(), (unsigned long long)phase0, (unsigned long long)phase_step, taps_dev, n_taps, decim,
                                     static_cast<float2*>(out_c64_dev), (long long)M, tile, (long long)n_tiles);
   if (e != hipSuccess) return hip_fail(e, "down-converter kernel launch");
   return AMCX_OK;
 }
 
 int amcx_kernel_name_ddc(int32_t src_kind, char* buf, int32_t buf_len) {
-  if (buf == nullptr || buf_len <= 0) return AMCX_EINVAL;
-  const char* const name = src_kind == AMCX_SRC_C64    ? "amcx_ddc_c64_kernel"
-                           : src_kind == AMCX_SRC_SC16 ? "amcx_ddc_sc16_kernel"
-                           : src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8 ? "amcx_ddc_iq8_kernel" : nullptr;
-  if (name == nullptr) return AMCX_EINVAL;
-  snprintf(buf, (size_t)buf_len, "%s", name);
-  return AMCX_OK;
+  return put_kernel_name(ddc_kernel({src_kind}).name, buf, buf_len);
 }
 
 // ---- the polyphase filter bank (amcx_bank_kernel.h) -------------------------------------------------------------------
@@ -984,52 +1007,35 @@ int amcx_filter_bank(const void* src_dev, int32_t src_kind, int64_t n_samples, f
                      uint64_t phase_step, uint64_t sample_index0, const float* taps_dev, int32_t n_taps, int32_t channels,
                      int32_t decim, void* out_c64_dev, int64_t out_channel_stride, int64_t out_capacity_samples,
                      void* hip_stream) {
-  const bool integer = src_kind == AMCX_SRC_SC16 || src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8;
-  if (src_kind != AMCX_SRC_C64 && !integer) return AMCX_EINVAL;
-  if (integer && !int_scale_ok(scale)) return AMCX_EINVAL;
+  const StreamSrc src{src_kind};
+  if (!src.ok(scale)) return AMCX_EINVAL;
   const int64_t M = amcx_filter_bank_out_samples(n_samples, n_taps, channels, decim);
   if (M < 0) return AMCX_EINVAL;
   if (out_channel_stride < M || out_channel_stride > (INT64_MAX - M) / (channels - 1)) return AMCX_EINVAL;
   if (out_capacity_samples < (int64_t)(channels - 1) * out_channel_stride + M) return AMCX_EINVAL;
   if (M == 0) return AMCX_OK;
-  if (src_dev == nullptr || taps_dev == nullptr || out_c64_dev == nullptr) return AMCX_EINVAL;
-  const unsigned src_align = src_kind == AMCX_SRC_C64 ? 7u : src_kind == AMCX_SRC_SC16 ? 3u : 1u;
-  if ((reinterpret_cast<uintptr_t>(src_dev) & src_align) || (reinterpret_cast<uintptr_t>(taps_dev) & 3u) ||
-      (reinterpret_cast<uintptr_t>(out_c64_dev) & 7u))
-    return AMCX_EINVAL;
-  if (on_another_device(src_dev) || on_another_device(taps_dev) || on_another_device(out_c64_dev)) return AMCX_EINVAL;
+  if (!stream_ptrs_ok(src_dev, taps_dev, out_c64_dev, src)) return AMCX_EINVAL;
   const int tile = amcx::bank_tile_outputs(channels);
   const int64_t n_tiles = (M + tile - 1) / tile;
   const int64_t grid = amcx::persistent_grid(cu_count(), bank_wgs_per_cu(n_taps, channels, decim), n_tiles, 1);
-  const size_t lds = amcx::bank_lds_bytes(n_taps, channels, decim);
-  const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const char* const src = static_cast<const char*>(src_dev);
-  float2* const out = static_cast<float2*>(out_c64_dev);
-  const float sc = integer ? scale : 1.0f;
-  const unsigned flip4 = src_kind == AMCX_SRC_CU8 ? 0x80808080u : 0u;
-  const unsigned long long p0 = phase0, ps = phase_step;
   const int a0 = (int)(sample_index0 & (uint64_t)(channels - 1));
   int logC = 0;
   while ((1 << logC) < channels) ++logC;
-  const long long stride = out_channel_stride, m = M, nt = n_tiles;
-  if (src_kind == AMCX_SRC_C64)
-    return bank_launch<amcx::amcx_bank_c64_kernel>(grid, lds, stream, src, sc, flip4, p0, ps, a0, taps_dev, n_taps, logC, decim, out,
-                                                    stride, m, tile, nt);
-  if (src_kind == AMCX_SRC_SC16)
-    return bank_launch<amcx::amcx_bank_sc16_kernel>(grid, lds, stream, src, sc, flip4, p0, ps, a0, taps_dev, n_taps, logC, decim, out,
-                                                     stride, m, tile, nt);
-  return bank_launch<amcx::amcx_bank_iq8_kernel>(grid, lds, stream, src, sc, flip4, p0, ps, a0, taps_dev, n_taps, logC, decim, out,
-                                                  stride, m, tile, nt);
+  const auto k = bank_kernel(src);
+  // the most a bank kernel ever asks for: C = 2 (tile 2048), T = 4096, D = 2
+  if (const hipError_t e = k.lds_attr((int)amcx::bank_lds_bytes(amcx::kBankMaxTaps, 2, 2)); e != hipSuccess)
+    return hip_fail(e, "filter-bank kernel attribute");
+  const hipError_t e = amcx::launch(k.kern, grid, amcx::kBankThreads, amcx::bank_lds_bytes(n_taps, channels, decim),
+                                    static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), src.kernel_scale(scale),
+                                    src.flip4(), (unsigned long long)phase0, (unsigned long long)phase_step, a0, taps_dev, n_taps, logC,
+                                    decim, static_cast<float2*>(out_c64_dev), (long long)out_channel_stride, (long long)M, tile,
+                                    (long long)n_tiles);
+  if (e != hipSuccess) return hip_fail(e, "filter-bank kernel launch");
+  return AMCX_OK;
 }
 
 int amcx_kernel_name_bank(int32_t src_kind, char* buf, int32_t buf_len) {
-  if (buf == nullptr || buf_len <= 0) return AMCX_EINVAL;
-  const char* const name = src_kind == AMCX_SRC_C64    ? "amcx_bank_c64_kernel"
-                           : src_kind == AMCX_SRC_SC16 ? "amcx_bank_sc16_kernel"
-                           : src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8 ? "amcx_bank_iq8_kernel" : nullptr;
-  if (name == nullptr) return AMCX_EINVAL;
-  snprintf(buf, (size_t)buf_len, "%s", name);
-  return AMCX_OK;
+  return put_kernel_name(bank_kernel({src_kind}).name, buf, buf_len);
 }
 
 // ---- the rational resampler (amcx_resample_kernel.h) --------------------------------------------------------------------
@@ -1058,27 +1064,18 @@ int amcx_resample_plan(int32_t n_taps, int32_t interp, int32_t decim, int32_t* t
 int amcx_resample(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, uint64_t phase0, uint64_t phase_step,
                   const float* taps_dev, int32_t n_taps, int32_t interp, int32_t decim, int32_t phase_index0,
                   void* out_c64_dev, int64_t out_capacity_samples, void* hip_stream) {
-  const bool integer = src_kind == AMCX_SRC_SC16 || src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8;
-  if (src_kind != AMCX_SRC_C64 && !integer) return AMCX_EINVAL;
-  if (integer && !int_scale_ok(scale)) return AMCX_EINVAL;
+  const StreamSrc src{src_kind};
+  if (!src.ok(scale)) return AMCX_EINVAL;
   const int64_t M = amcx_resample_out_samples(n_samples, n_taps, interp, decim, phase_index0);
   if (M < 0 || out_capacity_samples < M) return AMCX_EINVAL;
   if (M == 0) return AMCX_OK;
-  if (src_dev == nullptr || taps_dev == nullptr || out_c64_dev == nullptr) return AMCX_EINVAL;
-  const unsigned src_align = src_kind == AMCX_SRC_C64 ? 7u : src_kind == AMCX_SRC_SC16 ? 3u : 1u;
-  if ((reinterpret_cast<uintptr_t>(src_dev) & src_align) || (reinterpret_cast<uintptr_t>(taps_dev) & 3u) ||
-      (reinterpret_cast<uintptr_t>(out_c64_dev) & 7u))
-    return AMCX_EINVAL;
-  if (on_another_device(src_dev) || on_another_device(taps_dev) || on_another_device(out_c64_dev)) return AMCX_EINVAL;
+  if (!stream_ptrs_ok(src_dev, taps_dev, out_c64_dev, src)) return AMCX_EINVAL;
   const int tile = amcx::rs_tile_outputs(n_taps, interp, decim);
   const int64_t n_tiles = (M + tile - 1) / tile;
   const int64_t grid = amcx::persistent_grid(cu_count(), rs_wgs_per_cu(n_taps, interp, decim), n_tiles, 1);
-  const auto kern = src_kind == AMCX_SRC_C64 ? amcx::amcx_resample_c64_kernel
-                    : src_kind == AMCX_SRC_SC16 ? amcx::amcx_resample_sc16_kernel : amcx::amcx_resample_iq8_kernel;
-  const unsigned flip4 = src_kind == AMCX_SRC_CU8 ? 0x80808080u : 0u;
-  const hipError_t e = amcx::launch(kern, grid, amcx::kRsThreads, amcx::rs_lds_bytes(n_taps, interp, decim),
-                                    static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), integer ? scale : 1.0f,
-                                    flip4, (unsigned long long)phase0, (unsigned long long)phase_step, taps_dev, n_taps, interp,
+  const hipError_t e = amcx::launch(rs_kernel(src).kern, grid, amcx::kRsThreads, amcx::rs_lds_bytes(n_taps, interp, decim),
+                                    static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), src.kernel_scale(scale),
+                                    src.flip4(), (unsigned long long)phase0, (unsigned long long)phase_step, taps_dev, n_taps, interp,
                                     decim, phase_index0, amcx::rs_phase_taps(n_taps, interp),
                                     amcx::rs_max_span(n_taps, interp, decim), static_cast<float2*>(out_c64_dev), (long long)M,
                                     tile, (long long)n_tiles);
@@ -1086,11 +1083,7 @@ int amcx_resample(const void* src_dev, int32_t src_kind, int64_t n_samples, floa
   return AMCX_OK;
 }
 
-const char* amcx_kernel_name_resample(int32_t src_kind) {
-  return src_kind == AMCX_SRC_C64    ? "amcx_resample_c64_kernel"
-         : src_kind == AMCX_SRC_SC16 ? "amcx_resample_sc16_kernel"
-         : src_kind == AMCX_SRC_CI8 || src_kind == AMCX_SRC_CU8 ? "amcx_resample_iq8_kernel" : nullptr;
-}
+const char* amcx_kernel_name_resample(int32_t src_kind) { return rs_kernel({src_kind}).name; }
 
 int64_t amcx_group_stats_workspace_bytes(int64_t n_groups, int64_t rows_per_group, int32_t n_cols) {
   if (!stats_args_ok(n_groups, rows_per_group, n_cols, n_cols)) return -1;

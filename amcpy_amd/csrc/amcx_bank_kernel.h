@@ -26,8 +26,8 @@
 //
 // THE LAUNCH.  256 threads, a persistent grid over TILES of `tile` consecutive output instants (bank_tile_outputs: a power of
 // two, tile C = 4096, so 16 at C = 256).  A workgroup puts the taps and the twiddles into LDS once; per tile it
-//   1. stages the span's MIXED samples, (tile - 1) D + T of them, in LDS -- every input is mixed once per tile; 16-byte items
-//      from the first 16-byte boundary, single samples in front of it and behind the last whole item, as the down-converter;
+//   1. stages the span's MIXED samples, (tile - 1) D + T of them, in LDS -- every input is mixed once per tile: the
+//      down-converter's ddc_stage_span, with the plain image and its item loop unrolled by 4;
 //   2. barrier;
 //   3. sums the branches: a thread owns branch p = tid mod C of the 16 instants tid / C + j 256 / C, 16 sums in registers that
 //      share every tap it reads; u[p] is written to row `instant`, column (p - a) mod C of the tile x C array;
@@ -48,7 +48,7 @@
 //     tile = 16 (C = 256) a half-wave holds two columns, 2-way at worst.  All lanes of a column read one twiddle.
 //
 // KERNEL ORDER (amcx_launch.h): plain kernels in the header amcx.hip includes FIRST; this header includes the down-converter's
-// for the loaders and the mixer, whose kernels therefore still come first of all and keep their bytes, as does every other
+// for the loaders, the mixer and the staging routine, whose kernels therefore still come first of all and keep their bytes, as does every other
 // kernel: tools/codeobj_gate.py --kernels, profiles/r16_bank_codeobj_kernels.txt.
 #pragma once
 
@@ -59,7 +59,7 @@
 
 namespace amcx {
 
-constexpr int kBankThreads = 256;
+constexpr int kBankThreads = kDdcThreads;  // ddc_stage_span strides by it
 constexpr int kBankMaxTaps = 4096;
 constexpr int kBankMaxChannels = 256;
 constexpr int kBankTileElems = 4096;       // tile * C
@@ -121,23 +121,7 @@ __device__ __forceinline__ void bank_body(const char* __restrict__ src, float sc
     const long long s0 = m0 * D;                                       // the span's first input sample
     const int span = (n_out - 1) * D + T;
     const char* const base = src + s0 * L::kBytes;
-    // 1. in front of the first 16-byte boundary, whole items, behind the last whole item
-    int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u) / L::kBytes;
-    if (head > span) head = span;
-    const int items = (span - head) / L::kItem;
-    const int tail0 = head + items * L::kItem;
-    for (int i = tid; i < head; i += kBankThreads)
-      stage[i] = ddc_mix(L::one(base + (size_t)i * L::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
-#pragma unroll 4
-    for (int it = tid; it < items; it += kBankThreads) {
-      const int i0s = head + it * L::kItem;
-      float2 x[L::kItem];
-      L::item(base + (size_t)i0s * L::kBytes, scale, flip4, x);
-#pragma unroll
-      for (int j = 0; j < L::kItem; ++j) stage[i0s + j] = ddc_mix(x[j], phase0 + (unsigned long long)(s0 + i0s + j) * phase_step);
-    }
-    for (int i = tail0 + tid; i < span; i += kBankThreads)
-      stage[i] = ddc_mix(L::one(base + (size_t)i * L::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
+    ddc_stage_span<L, DdcPlain, 4>(stage, base, s0, span, scale, flip4, phase0, phase_step, tid);      // 1.
     __syncthreads();
     // 3. the branch sums: 16 instants of one branch in registers, every tap read once for the 16
     {

@@ -19,9 +19,10 @@
 // D > T is legal; the samples between two windows are then staged with the rest and never read (a tile of few outputs, down
 // to one at D = 4096, stages few of them).  No atomics, nothing shared between workgroups.
 //
-// THREE LOADS, THE SAME BITS.  A span is read in items of 16 bytes (2 complex64 / 4 sc16 / 8 eight-bit samples) from its first
-// 16-byte boundary on, and one sample per step in front of that boundary and behind the last whole item: any sample-aligned
-// address, any span.
+// ONE STAGING ROUTINE, THREE LOADS, THE SAME BITS.  ddc_stage_span is the only code that decides which bytes of the source are
+// read, here, in the filter bank (amcx_bank_kernel.h) and in the resampler (amcx_resample_kernel.h).  A span is read in items of
+// 16 bytes (2 complex64 / 4 sc16 / 8 eight-bit samples) from its first 16-byte boundary on, and one sample per step in front of
+// that boundary and behind the last whole item: any sample-aligned address, any span.  Every sample is mixed as it is stored.
 //
 // LDS IMAGE.  Sample i of the span lives at float2 index i + (i >> 5).  Lanes that sum neighbouring outputs read D samples
 // apart, 2 D dwords: without the pad a power of two D >= 32 puts a whole half-wave onto one bank pair; with it the 32 lanes of
@@ -36,7 +37,7 @@
 
 namespace amcx {
 
-constexpr int kDdcThreads = 256;
+constexpr int kDdcThreads = 256;           // of all three stream kernels: ddc_stage_span strides by it
 constexpr int kDdcMaxTaps = 2048;
 constexpr int kDdcMaxDecim = 4096;
 constexpr int kDdcStage = 6144;            // most samples of one tile's span: 6336 float2 with the pad, 49.5 KiB
@@ -126,6 +127,42 @@ struct DdcIq8 {
   }
 };
 
+// ---- staging (ONE STAGING ROUTINE above) -------------------------------------------------------------------------------------
+// the float2 index of a span's sample i in the LDS image: padded (LDS IMAGE above), or plain (the bank's, amcx_bank_kernel.h)
+struct DdcPadded {
+  static __device__ __forceinline__ int at(int i) { return ddc_pad(i); }
+};
+struct DdcPlain {
+  static __device__ __forceinline__ int at(int i) { return i; }
+};
+
+// The workgroup's kDdcThreads threads (tid) read the `span` samples from `base` on -- the stream's samples s0 ... s0 + span - 1
+// -- and nothing else, and store sample i, mixed, at stage[Image::at(i)].  The caller's barrier follows.  kUnroll: the item
+// loop's unroll count, 4 in the bank's kernels and 1 in the others (what the compiler does with that loop unhinted).
+template <class L, class Image, int kUnroll>
+__device__ __forceinline__ void ddc_stage_span(float2* stage, const char* __restrict__ base, long long s0, int span,
+                                               float scale, unsigned flip4, unsigned long long phase0,
+                                               unsigned long long phase_step, int tid) {
+  // in front of the first 16-byte boundary, whole items, behind the last whole item
+  int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u) / L::kBytes;
+  if (head > span) head = span;
+  const int items = (span - head) / L::kItem;
+  const int tail0 = head + items * L::kItem;
+  for (int i = tid; i < head; i += kDdcThreads)
+    stage[Image::at(i)] = ddc_mix(L::one(base + (size_t)i * L::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
+#pragma unroll kUnroll
+  for (int it = tid; it < items; it += kDdcThreads) {
+    const int i0 = head + it * L::kItem;
+    float2 x[L::kItem];
+    L::item(base + (size_t)i0 * L::kBytes, scale, flip4, x);
+#pragma unroll
+    for (int j = 0; j < L::kItem; ++j)
+      stage[Image::at(i0 + j)] = ddc_mix(x[j], phase0 + (unsigned long long)(s0 + i0 + j) * phase_step);
+  }
+  for (int i = tail0 + tid; i < span; i += kDdcThreads)
+    stage[Image::at(i)] = ddc_mix(L::one(base + (size_t)i * L::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
+}
+
 // Reads src[0 .. (M - 1) D + T) samples and taps[0 .. T), writes out[0 .. M), nothing else.  n_tiles = ceil(M / tile); the
 // dynamic LDS is ddc_lds_bytes(T, D).
 template <class L>
@@ -143,23 +180,7 @@ __device__ __forceinline__ void ddc_body(const char* __restrict__ src, float sca
     const long long s0 = m0 * D;                                       // the span's first input sample
     const int span = (n_out - 1) * D + T;
     const char* const base = src + s0 * L::kBytes;
-    // in front of the first 16-byte boundary, whole items, behind the last whole item
-    int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u) / L::kBytes;
-    if (head > span) head = span;
-    const int items = (span - head) / L::kItem;
-    const int tail0 = head + items * L::kItem;
-    for (int i = tid; i < head; i += kDdcThreads)
-      stage[ddc_pad(i)] = ddc_mix(L::one(base + (size_t)i * L::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
-    for (int it = tid; it < items; it += kDdcThreads) {
-      const int i0 = head + it * L::kItem;
-      float2 x[L::kItem];
-      L::item(base + (size_t)i0 * L::kBytes, scale, flip4, x);
-#pragma unroll
-      for (int j = 0; j < L::kItem; ++j)
-        stage[ddc_pad(i0 + j)] = ddc_mix(x[j], phase0 + (unsigned long long)(s0 + i0 + j) * phase_step);
-    }
-    for (int i = tail0 + tid; i < span; i += kDdcThreads)
-      stage[ddc_pad(i)] = ddc_mix(L::one(base + (size_t)i * L::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
+    ddc_stage_span<L, DdcPadded, 1>(stage, base, s0, span, scale, flip4, phase0, phase_step, tid);
     __syncthreads();
     for (int o = tid; o < n_out; o += kDdcThreads) {
       const int top = o * D + T - 1;                                   // the sample tap 0 multiplies

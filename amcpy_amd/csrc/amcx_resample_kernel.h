@@ -1,6 +1,6 @@
 // The rational resampler (include/amcx.h, amcx_resample; ABI 13): mixer, polyphase real FIR, rate change by L / D, from one
 // contiguous stream of complex64 / sc16 / ci8 / cu8 samples to packed complex64.  A sibling of the down-converter
-// (amcx_ddc_kernel.h): its mixer (ddc_mix), its loaders (Ddc*) and its three loads are CALLED here, not copied.
+// (amcx_ddc_kernel.h): its mixer (ddc_mix), its loaders (Ddc*) and its staging routine (ddc_stage_span) are CALLED here.
 //
 //   phi(n) = phase0 + n * phase_step                  (uint64, exact; n counts the call's input samples)
 //   v[n]   = x[n] * exp(+2 pi j phi(n) / 2^64)
@@ -21,7 +21,7 @@
 //
 // THE LAUNCH.  256 threads, a persistent grid over TILES of `tile` consecutive outputs (rs_tile_outputs: as many as the stage
 // holds the worst span of, 4096 at the most -- L = 256, D = 1 would otherwise be a million).  A workgroup puts the taps into LDS
-// once; per tile it stages the span's MIXED samples (the three loads of the down-converter), barrier, then thread t sums the
+// once; per tile it stages the span's MIXED samples (ddc_stage_span, the padded image), barrier, then thread t sums the
 // outputs t, t + 256, ... of the tile and stores them (8-byte vector stores, consecutive lanes consecutive outputs), barrier.
 // A tile's first input is s0 = floor((m0 D + tau0) / L) in 64-bit, once per tile; inside the tile output o sits at
 // u = o D + r0, r0 = (m0 D + tau0) mod L: phase u mod L, window top (P - 1) + u / L relative to s0.  A thread divides ONCE per
@@ -29,8 +29,8 @@
 // 64-bit.  u < kRsStage * 256 + 256 fits 32 bits by far.
 //
 // LDS: [span float2, the down-converter's pad][L phases of `pitch` floats]; 64 896 bytes at the most (rs_lds_bytes): no attribute.
-//   - samples: index i + (i >> 5), as the down-converter.  Neighbouring lanes read D / L samples apart: the same sample
-//     (a broadcast) or a near one for every ratio below 1, the down-converter's pattern at L = 1.
+//   - samples: index i + (i >> 5), the down-converter's padded image (DdcPadded).  Neighbouring lanes read D / L samples
+//     apart: the same sample (a broadcast) or a near one for every ratio below 1, the down-converter's pattern at L = 1.
 //   - taps: PHASE-MAJOR, g[p * pitch + q] = h[p + q L], pitch = P | 1.  The lanes of a half-wave are at one q and at phases
 //     (r0 + o D) mod L; tap reads are 4 bytes, bank (a / 4) mod 32, so with an odd pitch p -> bank is one-to-one mod 32: two
 //     lanes meet on a bank only where their phases are equal (a broadcast) or 32 apart, the least a table of one tap per dword
@@ -48,7 +48,7 @@
 
 namespace amcx {
 
-constexpr int kRsThreads = 256;
+constexpr int kRsThreads = kDdcThreads;     // ddc_stage_span strides by it
 constexpr int kRsMaxTaps = 4096;
 constexpr int kRsMaxInterp = 256;
 constexpr int kRsMaxDecim = 4096;
@@ -100,23 +100,7 @@ __device__ __forceinline__ void rs_body(const char* __restrict__ src, float scal
     const int r0 = (int)(t0 - s0 * L);
     const int span = (int)(((unsigned)(n_out - 1) * (unsigned)D + (unsigned)r0) / (unsigned)L) + P;
     const char* const base = src + s0 * Ld::kBytes;
-    // in front of the first 16-byte boundary, whole items, behind the last whole item
-    int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(base) & 15u)) & 15u) / Ld::kBytes;
-    if (head > span) head = span;
-    const int items = (span - head) / Ld::kItem;
-    const int tail0 = head + items * Ld::kItem;
-    for (int i = tid; i < head; i += kRsThreads)
-      stage[ddc_pad(i)] = ddc_mix(Ld::one(base + (size_t)i * Ld::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
-    for (int it = tid; it < items; it += kRsThreads) {
-      const int i0 = head + it * Ld::kItem;
-      float2 x[Ld::kItem];
-      Ld::item(base + (size_t)i0 * Ld::kBytes, scale, flip4, x);
-#pragma unroll
-      for (int j = 0; j < Ld::kItem; ++j)
-        stage[ddc_pad(i0 + j)] = ddc_mix(x[j], phase0 + (unsigned long long)(s0 + i0 + j) * phase_step);
-    }
-    for (int i = tail0 + tid; i < span; i += kRsThreads)
-      stage[ddc_pad(i)] = ddc_mix(Ld::one(base + (size_t)i * Ld::kBytes, scale, flip4), phase0 + (unsigned long long)(s0 + i) * phase_step);
+    ddc_stage_span<Ld, DdcPadded, 1>(stage, base, s0, span, scale, flip4, phase0, phase_step, tid);
     __syncthreads();
     const unsigned u = (unsigned)tid * (unsigned)D + (unsigned)r0;     // the one division of this thread and tile
     int off = (int)(u / (unsigned)L), p = (int)(u - (unsigned)off * (unsigned)L);

@@ -13,27 +13,12 @@ only on its T input samples, the taps and the phase there, so a stream pushed in
 """
 from __future__ import annotations
 
-from fractions import Fraction
-
 import numpy as np
 
-from . import _lib
+from . import _stream
+from ._stream import FORMATS, _DEFAULT_SCALE, _KINDS, _MASK64, _NUMPY, _format_of, _scale_of, phase_step_of  # noqa: F401
 
 MAX_TAPS, MAX_DECIM = 2048, 4096
-FORMATS = ("cf32", "sc16", "ci8", "cu8")
-_KINDS = {"cf32": _lib.SRC_C64, "sc16": _lib.SRC_SC16, "ci8": _lib.SRC_CI8, "cu8": _lib.SRC_CU8}
-_DEFAULT_SCALE = {"cf32": 1.0, "sc16": _lib.SC16_SCALE, "ci8": _lib.IQ8_SCALE, "cu8": _lib.IQ8_SCALE}
-_NUMPY = {"cf32": np.complex64, "sc16": np.int16, "ci8": np.int8, "cu8": np.uint8}
-_MASK64 = (1 << 64) - 1
-
-
-def phase_step_of(shift) -> int:
-    """``round(shift * 2^64) mod 2^64`` in Python integers.  ``shift``: cycles per input sample, a float (taken at its
-    exact value) or a ``fractions.Fraction`` -- ``Fraction(k, 2**64)`` is the step k itself.  To move a signal at +f Hz
-    to 0 Hz: ``shift = -f / fs``."""
-    if isinstance(shift, float) and not np.isfinite(shift):
-        raise ValueError(f"shift must be finite, got {shift!r}")
-    return int(round(Fraction(shift) * (1 << 64))) & _MASK64
 
 
 def out_samples(n_samples: int, n_taps: int, decim: int) -> int:
@@ -58,32 +43,7 @@ def design_lowpass(decim: int, n_taps=None, cutoff=None) -> np.ndarray:
     fc = 0.4 / D if cutoff is None else float(cutoff)
     if not 0.0 < fc <= 0.5:
         raise ValueError(f"cutoff must lie in (0, 0.5] cycles per sample, got {cutoff!r}")
-    n = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
-    h = 2.0 * fc * np.sinc(2.0 * fc * n)
-    if T > 1:
-        h *= 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(T, dtype=np.float64) / (T - 1))
-    h = (h + h[::-1]) / 2.0                                   # symmetric to the bit
-    return (h / h.sum()).astype(np.float32)
-
-
-def _format_of(x) -> str:
-    """The sample format a tensor's or array's dtype and shape name: complex64 (S,), or int16 / int8 / uint8 (S, 2)."""
-    name = str(x.dtype).replace("torch.", "")
-    if name == "complex64":
-        if x.ndim != 1:
-            raise TypeError("complex64 samples must have shape (S,)")
-        return "cf32"
-    fmt = {"int16": "sc16", "int8": "ci8", "uint8": "cu8"}.get(name)
-    if fmt is None:
-        raise TypeError(f"samples must be complex64 (S,) or int16 / int8 / uint8 (S, 2), not {name}")
-    if x.ndim != 2 or x.shape[1] != 2:
-        raise TypeError(f"{name} samples must have shape (S, 2): the last dimension is (I, Q)")
-    return fmt
-
-
-def _scale_of(fmt: str, scale) -> float:
-    from .features import _sc16_scale
-    return _DEFAULT_SCALE[fmt] if scale is None or fmt == "cf32" else _sc16_scale(scale)
+    return _stream.windowed_sinc(T, fc)
 
 
 def tune_decimate(x, taps, decim: int, *, shift=0.0, sample_index0: int = 0, scale=None, out=None):
@@ -101,37 +61,19 @@ def tune_decimate(x, taps, decim: int, *, shift=0.0, sample_index0: int = 0, sca
     Returns complex64 (M,), M = :func:`out_samples`."""
     import torch
 
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch tensor (complex64 (S,), or int16 / int8 / uint8 (S, 2))")
-    fmt = _format_of(x)
-    scale = _scale_of(fmt, scale)
-    if not x.is_cuda:
-        raise ValueError("x must live in GPU memory")
-    if not x.is_contiguous():
-        raise ValueError("x must be one contiguous stream")
-    if not isinstance(taps, torch.Tensor):
-        taps = torch.from_numpy(np.ascontiguousarray(np.asarray(taps, dtype=np.float32))).to(x.device)
-    if taps.dtype != torch.float32 or taps.dim() != 1 or taps.device != x.device:
-        raise TypeError("taps must be a one-dimensional float32 tensor on x's device")
-    taps = taps.contiguous()
-    S, T, D = int(x.shape[0]), int(taps.shape[0]), int(decim)
-    M = out_samples(S, T, D)
-    step = phase_step_of(shift)
-    phase0 = (int(sample_index0) * step) & _MASK64
+    f = _stream.front(x, taps, scale, shift, sample_index0, lambda S, T: out_samples(S, T, decim))
+    D = int(decim)
     if out is None:
-        out = torch.empty((M,), dtype=torch.complex64, device=x.device)
-    elif out.dtype != torch.complex64 or out.device != x.device or out.dim() != 1 or not out.is_contiguous() or out.shape[0] < M:
-        raise ValueError(f"out must be a contiguous complex64 tensor of at least {M} samples on x's device")
-    _lib.require_torch_runtime()
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lib.amcx_tune_decimate(x.data_ptr() if S else None, _KINDS[fmt], S, scale, phase0, step, taps.data_ptr(), T, D,
-                                          out.data_ptr() if M else None, int(out.shape[0]), stream))
-    return out[:M]
+        out = torch.empty((f.M,), dtype=torch.complex64, device=x.device)
+    elif out.dtype != torch.complex64 or out.device != x.device or out.dim() != 1 or not out.is_contiguous() or out.shape[0] < f.M:
+        raise ValueError(f"out must be a contiguous complex64 tensor of at least {f.M} samples on x's device")
+    _stream.launch(x, lambda lib, stream: lib.amcx_tune_decimate(
+        x.data_ptr() if f.S else None, f.kind, f.S, f.scale, f.phase0, f.step, f.taps.data_ptr(), f.T, D,
+        out.data_ptr() if f.M else None, int(out.shape[0]), stream))
+    return out[:f.M]
 
 
-class Channelizer:
+class Channelizer(_stream.Stream):
     """The streaming form of :func:`tune_decimate`: ``push(chunk)`` returns the outputs the stream so far completes.
 
     Keeps the unconsumed tail of the input (fewer than ``T - 1 + decim`` samples) and the absolute index of the sample the
@@ -140,51 +82,19 @@ class Channelizer:
     an injected ``f(x, taps, decim, shift=..., sample_index0=..., scale=...)`` over numpy chunks (tests); the default is
     :func:`tune_decimate` over GPU tensors, with the taps uploaded once."""
 
+    _NOUN, _one_shot = "channelizer", staticmethod(tune_decimate)
+
     def __init__(self, taps, decim: int, shift=0.0, fmt: str = "cf32", scale=None, *, compute=None):
-        if fmt not in FORMATS:
-            raise ValueError(f"fmt must be one of {FORMATS}, not {fmt!r}")
-        self.taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
-        if self.taps.ndim != 1:
-            raise ValueError("taps must be one-dimensional")
-        self.decim, self.shift, self.fmt = int(decim), shift, fmt
-        out_samples(0, self.taps.shape[0], self.decim)                  # the limits
-        phase_step_of(shift)
-        self.scale = _scale_of(fmt, scale)
-        self.index = 0                 # absolute index of the sample the next output's window begins at
-        self._tail = None              # the samples from there on that have arrived ...
-        self._skip = 0                 # ... or, decim > T, how many are still to be dropped before it
-        self._compute = compute
-        self._taps_dev = None
+        super().__init__(taps, shift, fmt, scale, compute, decim=decim)
 
-    def _run(self, buf):
-        if self._compute is not None:
-            return self._compute(buf, self.taps, self.decim, shift=self.shift, sample_index0=self.index, scale=self.scale)
-        import torch
-        if self._taps_dev is None or self._taps_dev.device != buf.device:
-            self._taps_dev = torch.from_numpy(self.taps).to(buf.device)
-        return tune_decimate(buf, self._taps_dev, self.decim, shift=self.shift, sample_index0=self.index, scale=self.scale)
+    def _limits(self):
+        out_samples(0, self.taps.shape[0], self.decim)
 
-    def push(self, chunk):
-        """The new outputs (complex64, possibly none) of the stream extended by ``chunk``."""
-        if _format_of(chunk) != self.fmt:
-            raise TypeError(f"this channelizer takes {self.fmt} chunks")
-        if self._skip:                                               # decim > T: samples between two windows, never read
-            drop = min(self._skip, int(chunk.shape[0]))
-            chunk, self._skip = chunk[drop:], self._skip - drop
-        if self._tail is None or self._tail.shape[0] == 0:
-            buf = chunk
-        elif chunk.shape[0] == 0:
-            buf = self._tail
-        elif isinstance(chunk, np.ndarray):
-            buf = np.concatenate([self._tail, chunk])
-        else:
-            import torch
-            buf = torch.cat([self._tail, chunk])
-        S = int(buf.shape[0])
-        y = self._run(buf)
-        used = out_samples(S, self.taps.shape[0], self.decim) * self.decim      # where the next output's window begins
-        self._skip += max(0, used - S)                               # (a skip still pending left buf empty: used == 0)
-        tail = buf[min(used, S):]                                    # short: a copy, not a view that keeps the chunk alive
-        self._tail = tail.copy() if isinstance(tail, np.ndarray) else tail.clone()
-        self.index += used
-        return y
+    def _args(self):
+        return (self.decim,)
+
+    def _outputs(self, S):
+        return out_samples(S, self.taps.shape[0], self.decim)
+
+    def _consumed(self, M):
+        return M * self.decim

@@ -23,8 +23,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _lib
-from .ddc import FORMATS, _KINDS, _MASK64, _format_of, _scale_of, phase_step_of
+from . import _stream
 
 MAX_TAPS, MAX_INTERP, MAX_DECIM = 4096, 256, 4096
 DESIGN_MAX = (MAX_TAPS - 1) // 16      # 255: the largest interp or decim whose default design, 16 max(L, D) + 1 taps, fits MAX_TAPS
@@ -63,12 +62,7 @@ def design_resample_lowpass(interp: int, decim: int, n_taps=None, cutoff=None) -
     fc = 0.4 / max(L, D) if cutoff is None else float(cutoff)
     if not 0.0 < fc <= 0.5:
         raise ValueError(f"cutoff must lie in (0, 0.5] cycles per upsampled sample, got {cutoff!r}")
-    n = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
-    h = 2.0 * fc * np.sinc(2.0 * fc * n)
-    if T > 1:
-        h *= 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(T, dtype=np.float64) / (T - 1))
-    h = (h + h[::-1]) / 2.0                                   # symmetric to the bit
-    return (h / h.sum() * L).astype(np.float32)
+    return _stream.windowed_sinc(T, fc, gain=L)
 
 
 def rational_ratio(ratio, max_interp: int = MAX_INTERP, max_decim: int = MAX_DECIM) -> tuple:
@@ -112,37 +106,19 @@ def resample(x, taps, interp: int, decim: int, *, shift=0.0, sample_index0: int 
     Returns complex64 (M,), M = :func:`out_samples`."""
     import torch
 
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch tensor (complex64 (S,), or int16 / int8 / uint8 (S, 2))")
-    fmt = _format_of(x)
-    scale = _scale_of(fmt, scale)
-    if not x.is_cuda:
-        raise ValueError("x must live in GPU memory")
-    if not x.is_contiguous():
-        raise ValueError("x must be one contiguous stream")
-    if not isinstance(taps, torch.Tensor):
-        taps = torch.from_numpy(np.ascontiguousarray(np.asarray(taps, dtype=np.float32))).to(x.device)
-    if taps.dtype != torch.float32 or taps.dim() != 1 or taps.device != x.device:
-        raise TypeError("taps must be a one-dimensional float32 tensor on x's device")
-    taps = taps.contiguous()
-    S, T, L, D, tau0 = int(x.shape[0]), int(taps.shape[0]), int(interp), int(decim), int(phase_index0)
-    M = out_samples(S, T, L, D, tau0)
-    step = phase_step_of(shift)
-    phase0 = (int(sample_index0) * step) & _MASK64
+    f = _stream.front(x, taps, scale, shift, sample_index0, lambda S, T: out_samples(S, T, interp, decim, phase_index0))
+    L, D, tau0 = int(interp), int(decim), int(phase_index0)
     if out is None:
-        out = torch.empty((M,), dtype=torch.complex64, device=x.device)
-    elif out.dtype != torch.complex64 or out.device != x.device or out.dim() != 1 or not out.is_contiguous() or out.shape[0] < M:
-        raise ValueError(f"out must be a contiguous complex64 tensor of at least {M} samples on x's device")
-    _lib.require_torch_runtime()
-    lib = _lib.load()
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lib.amcx_resample(x.data_ptr() if S else None, _KINDS[fmt], S, scale, phase0, step, taps.data_ptr(), T, L, D,
-                                     tau0, out.data_ptr() if M else None, int(out.shape[0]), stream))
-    return out[:M]
+        out = torch.empty((f.M,), dtype=torch.complex64, device=x.device)
+    elif out.dtype != torch.complex64 or out.device != x.device or out.dim() != 1 or not out.is_contiguous() or out.shape[0] < f.M:
+        raise ValueError(f"out must be a contiguous complex64 tensor of at least {f.M} samples on x's device")
+    _stream.launch(x, lambda lib, stream: lib.amcx_resample(
+        x.data_ptr() if f.S else None, f.kind, f.S, f.scale, f.phase0, f.step, f.taps.data_ptr(), f.T, L, D, tau0,
+        out.data_ptr() if f.M else None, int(out.shape[0]), stream))
+    return out[:f.M]
 
 
-class Resampler:
+class Resampler(_stream.Stream):
     """The streaming form of :func:`resample`: ``push(chunk)`` returns the outputs the stream so far completes.
 
     Keeps the unconsumed tail of the input, ``index`` -- the absolute index of the sample the next output's window begins
@@ -154,61 +130,32 @@ class Resampler:
     ``f(x, taps, interp, decim, shift=..., sample_index0=..., phase_index0=..., scale=...)`` over numpy chunks (tests); the
     default is :func:`resample` over GPU tensors, with the taps uploaded once."""
 
+    _NOUN, _one_shot = "resampler", staticmethod(resample)
+
     def __init__(self, taps, interp: int, decim: int, shift=0.0, fmt: str = "cf32", scale=None, *, compute=None):
-        if fmt not in FORMATS:
-            raise ValueError(f"fmt must be one of {FORMATS}, not {fmt!r}")
-        self.taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
-        if self.taps.ndim != 1:
-            raise ValueError("taps must be one-dimensional")
-        self.interp, self.decim, self.shift, self.fmt = int(interp), int(decim), shift, fmt
-        out_samples(0, self.taps.shape[0], self.interp, self.decim)        # the limits
-        phase_step_of(shift)
-        self.scale = _scale_of(fmt, scale)
-        self.index = 0                 # absolute index of the sample the next output's window begins at
         self.phase_index = 0           # tau0 of the next output
-        self._tail = None              # the samples from `index` on that have arrived ...
-        self._skip = 0                 # ... or, decim > P interp, how many are still to be dropped before it
-        self._compute = compute
-        self._taps_dev = None
+        super().__init__(taps, shift, fmt, scale, compute, interp=interp, decim=decim)
 
-    def _run(self, buf):
-        kw = dict(shift=self.shift, sample_index0=self.index, phase_index0=self.phase_index, scale=self.scale)
-        if self._compute is not None:
-            return self._compute(buf, self.taps, self.interp, self.decim, **kw)
+    def _limits(self):
+        out_samples(0, self.taps.shape[0], self.interp, self.decim)
+
+    def _args(self):
+        return self.interp, self.decim
+
+    def _kw(self):
+        return dict(super()._kw(), phase_index0=self.phase_index)
+
+    def _outputs(self, S):
+        return out_samples(S, self.taps.shape[0], self.interp, self.decim, self.phase_index)
+
+    def _run(self, buf, M):
+        if M:
+            return super()._run(buf, M)
+        if isinstance(buf, np.ndarray):                              # nothing completes (a skip pending, fewer than P samples): no launch
+            return np.empty(0, np.complex64)
         import torch
-        if self._taps_dev is None or self._taps_dev.device != buf.device:
-            self._taps_dev = torch.from_numpy(self.taps).to(buf.device)
-        return resample(buf, self._taps_dev, self.interp, self.decim, **kw)
+        return torch.empty(0, dtype=torch.complex64, device=buf.device)
 
-    def push(self, chunk):
-        """The new outputs (complex64, possibly none) of the stream extended by ``chunk``."""
-        if _format_of(chunk) != self.fmt:
-            raise TypeError(f"this resampler takes {self.fmt} chunks")
-        if self._skip:                                               # samples between two windows, never read
-            drop = min(self._skip, int(chunk.shape[0]))
-            chunk, self._skip = chunk[drop:], self._skip - drop
-        if self._tail is None or self._tail.shape[0] == 0:
-            buf = chunk
-        elif chunk.shape[0] == 0:
-            buf = self._tail
-        elif isinstance(chunk, np.ndarray):
-            buf = np.concatenate([self._tail, chunk])
-        else:
-            import torch
-            buf = torch.cat([self._tail, chunk])
-        S = int(buf.shape[0])
-        M = out_samples(S, self.taps.shape[0], self.interp, self.decim, self.phase_index)
-        if M == 0:                                                   # nothing completes (a skip pending, fewer than P samples): no launch
-            self._tail = (buf.copy() if isinstance(buf, np.ndarray) else buf.clone()) if buf is chunk else buf
-            if isinstance(buf, np.ndarray):
-                return np.empty(0, np.complex64)
-            import torch
-            return torch.empty(0, dtype=torch.complex64, device=buf.device)
-        y = self._run(buf)
-        t = M * self.decim + self.phase_index
-        used, self.phase_index = divmod(t, self.interp)              # where the next output's window begins, and its phase
-        self._skip += max(0, used - S)                               # (a skip still pending left buf empty: used == 0)
-        tail = buf[min(used, S):]                                    # short: a copy, not a view that keeps the chunk alive
-        self._tail = tail.copy() if isinstance(tail, np.ndarray) else tail.clone()
-        self.index += used
-        return y
+    def _consumed(self, M):
+        used, self.phase_index = divmod(M * self.decim + self.phase_index, self.interp)      # ... and the next output's phase
+        return used

@@ -10,8 +10,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from amcpy_amd import _lib, ddc, resample as rs
-from tests import resample_ref as ref
+from amcpy_amd import _lib, bank, ddc, resample as rs
+from tests import bank_ref, ddc_ref, resample_ref as ref
 
 REPO = Path(__file__).resolve().parents[1]
 NEW = ["amcx_resample", "amcx_resample_out_samples", "amcx_resample_plan", "amcx_kernel_name_resample"]
@@ -477,3 +477,63 @@ def test_a_resolved_tune_is_taken_back_and_pushes_that_complete_nothing_do_not_l
     whole = ref.numpy_resample(x, taps, 2, 9)
     rest = r.push(x[5:])
     assert np.concatenate([whole[:1], rest]).tobytes() == whole.tobytes()
+
+
+# ---- what the three stream modules share (amcpy_amd/_stream.py): taps and bookkeeping as recorded before they shared it ----
+_DESIGNS = {
+    "lowpass_d1": lambda: ddc.design_lowpass(1),                                  # the defaults at D = 1 and D = 7
+    "lowpass_d7": lambda: ddc.design_lowpass(7),
+    "lowpass_d4_t1": lambda: ddc.design_lowpass(4, 1),                            # T = 1, an even T, an odd T with a cutoff
+    "lowpass_d4_t64": lambda: ddc.design_lowpass(4, 64),
+    "lowpass_d3_t33_cut": lambda: ddc.design_lowpass(3, 33, cutoff=0.11),
+    "bank_c2_p1": lambda: bank.design_bank_lowpass(2, 1),
+    "bank_c8": lambda: bank.design_bank_lowpass(8),
+    "bank_c64_p5_d32": lambda: bank.design_bank_lowpass(64, 5, 32),
+    "resample_1_1": lambda: rs.design_resample_lowpass(1, 1),
+    "resample_1_7": lambda: rs.design_resample_lowpass(1, 7),
+    "resample_3_2": lambda: rs.design_resample_lowpass(3, 2),
+    "resample_255_254": lambda: rs.design_resample_lowpass(255, 254),
+    "resample_3_2_t1": lambda: rs.design_resample_lowpass(3, 2, 1),
+    "resample_3_2_t64": lambda: rs.design_resample_lowpass(3, 2, 64),
+    "resample_10_7_t161_cut": lambda: rs.design_resample_lowpass(10, 7, 161, cutoff=0.03),
+}
+
+
+def test_design_functions_return_the_recorded_taps_bit_for_bit():
+    gold = np.load(REPO / "tests" / "golden" / "stream_design_taps.npz")
+    assert sorted(gold.files) == sorted(_DESIGNS)
+    for name, design in _DESIGNS.items():
+        h = design()
+        assert h.dtype == np.float32 == gold[name].dtype and h.tobytes() == gold[name].tobytes(), name
+
+
+# (index, _skip, tail length[, phase_index]) after each push of 0, 1, T - 1, T + D, 1, 0, T + D, T - 1, T + D, 1 samples
+_STATES = [
+    (lambda: ddc.Channelizer(ddc_ref.make_taps(5), 3, 0.1, compute=ddc_ref.numpy_ddc), 5, 3,
+     [(0, 0, 0), (0, 0, 1), (3, 0, 2), (9, 0, 4), (12, 0, 2), (12, 0, 2), (18, 0, 4), (24, 0, 2), (30, 0, 4), (33, 0, 2)]),
+    (lambda: ddc.Channelizer(ddc_ref.make_taps(3), 7, 0.1, compute=ddc_ref.numpy_ddc), 3, 7,                  # decim > T
+     [(0, 0, 0), (0, 0, 1), (7, 4, 0), (14, 1, 0), (14, 0, 0), (14, 0, 0), (28, 4, 0), (28, 2, 0), (35, 0, 1), (35, 0, 2)]),
+    (lambda: bank.FilterBank(ddc_ref.make_taps(6), 4, 2, 0.1, compute=bank_ref.numpy_bank), 6, 2,
+     [(0, 0, 0), (0, 0, 1), (2, 0, 4), (10, 0, 4), (10, 0, 5), (10, 0, 5), (18, 0, 5), (24, 0, 4), (32, 0, 4), (32, 0, 5)]),
+    (lambda: bank.FilterBank(ddc_ref.make_taps(2), 8, 8, 0.1, compute=bank_ref.numpy_bank), 2, 8,             # decim > T
+     [(0, 0, 0), (0, 0, 1), (8, 6, 0), (16, 4, 0), (16, 3, 0), (16, 3, 0), (24, 1, 0), (24, 0, 0), (40, 6, 0), (40, 5, 0)]),
+    (lambda: rs.Resampler(ddc_ref.make_taps(7), 3, 2, 0.1, compute=ref.numpy_resample), 7, 2,
+     [(0, 0, 0, 0), (0, 0, 1, 0), (5, 0, 2, 1), (14, 0, 2, 0), (15, 0, 2, 1), (15, 0, 2, 1), (24, 0, 2, 0), (30, 0, 2, 0),
+      (39, 0, 2, 1), (40, 0, 2, 0)]),
+    (lambda: rs.Resampler(ddc_ref.make_taps(4), 2, 9, 0.1, compute=ref.numpy_resample), 4, 9,                 # decim > P interp
+     [(0, 0, 0, 0), (0, 0, 1, 0), (4, 0, 0, 1), (18, 1, 0, 0), (18, 0, 0, 0), (18, 0, 0, 0), (31, 0, 0, 1), (36, 2, 0, 0),
+      (49, 2, 0, 1), (49, 1, 0, 1)]),
+]
+
+
+@pytest.mark.parametrize("case", range(len(_STATES)))
+def test_streaming_state_after_every_push_is_the_recorded_one(case):
+    make, T, D, want = _STATES[case]
+    rng = np.random.default_rng(7)
+    x = (rng.standard_normal(400) + 1j * rng.standard_normal(400)).astype(np.complex64)
+    s, pos = make(), 0
+    for n, state in zip((0, 1, T - 1, T + D, 1, 0, T + D, T - 1, T + D, 1), want):
+        s.push(x[pos:pos + n])
+        pos += n
+        got = (s.index, s._skip, int(s._tail.shape[0])) + ((s.phase_index,) if isinstance(s, rs.Resampler) else ())
+        assert got == state, (case, pos)
