@@ -308,8 +308,7 @@ class HostContext:
         self._h = C.c_void_p()
         self.device = int(device)
         self.mask = FEATURES_ALL
-        self.sc16_scale = SC16_SCALE
-        self.iq8_scale = IQ8_SCALE
+        self.scales = {"sc16": SC16_SCALE, "iq8": IQ8_SCALE}       # what the library holds, per C setter
         check(load().amcx_ctx_create(self.device, C.byref(self._h)))
 
     def set_feature_mask(self, mask: int) -> None:
@@ -319,36 +318,28 @@ class HostContext:
             check(load().amcx_ctx_set_feature_mask(self._h, mask))
             self.mask = mask
 
-    def set_sc16_scale(self, scale: float) -> None:
-        """amcx_ctx_set_sc16_scale: what every later sc16 call multiplies an int16 component by."""
+    def set_scale(self, fmt: str, scale: float) -> None:
+        """amcx_ctx_set_sc16_scale / amcx_ctx_set_iq8_scale, whichever serves the format ``fmt``: what every later call on
+        samples of that family multiplies a component by.  cf32 has none: nothing is set."""
+        from . import _formats                             # (function-level: _formats reads this module's constants)
+        family = _formats.get(fmt).family
         scale = C.c_float(scale).value
-        if scale != self.sc16_scale:
-            check(load().amcx_ctx_set_sc16_scale(self._h, scale))
-            self.sc16_scale = scale
-
-    def set_iq8_scale(self, scale: float) -> None:
-        """amcx_ctx_set_iq8_scale: what every later 8-bit call multiplies a component by."""
-        scale = C.c_float(scale).value
-        if scale != self.iq8_scale:
-            check(load().amcx_ctx_set_iq8_scale(self._h, scale))
-            self.iq8_scale = scale
+        if family is not None and scale != self.scales[family]:
+            check(getattr(load(), f"amcx_ctx_set_{family}_scale")(self._h, scale))
+            self.scales[family] = scale
 
     def run(self, x2, frame_size: int, out, variant: int) -> None:
         """x2: C-contiguous (F, L) complex64 / complex128 ndarray, or (F, L, 2) int16 (sc16) / int8 (ci8) / uint8 (cu8);
         out: (F, >=18) float32."""
-        import numpy as np
+        from . import _formats
         lib = load()
-        if x2.dtype == np.int8 or x2.dtype == np.uint8:
-            check(lib.amcx_ctx_features18_iq8_host(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1],
-                                                   IQ8_CI8 if x2.dtype == np.int8 else IQ8_CU8, out.ctypes.data,
-                                                   out.shape[1], int(variant)))
-            return
-        if x2.dtype == np.int16:
-            check(lib.amcx_ctx_features18_sc16_host(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1],
-                                                    out.ctypes.data, out.shape[1], int(variant)))
-            return
-        entry = lib.amcx_ctx_features18_c128_host if x2.dtype == np.complex128 else lib.amcx_ctx_features18_c64_host
-        check(entry(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1],
+        fmt = _formats.by_plain(x2.dtype)
+        if fmt is not None and fmt.family is not None:
+            entry = getattr(lib, f"amcx_ctx_features18_{fmt.family}_host")
+        else:
+            entry = lib.amcx_ctx_features18_c128_host if x2.dtype == "complex128" else lib.amcx_ctx_features18_c64_host
+        which = () if fmt is None or fmt.iq8 is None else (fmt.iq8,)          # the 8-bit entry alone is told which format
+        check(entry(self._h, x2.ctypes.data, x2.shape[0], int(frame_size), x2.shape[1], *which,
                     out.ctypes.data, out.shape[1], int(variant)))
 
     def configure(self, threads: int = 0, slot_bytes: int = 0, round_on_device: int = -1) -> None:

@@ -8,12 +8,9 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _lib
+from . import _formats, _lib
 
-FORMATS = ("cf32", "sc16", "ci8", "cu8")
-_KINDS = {"cf32": _lib.SRC_C64, "sc16": _lib.SRC_SC16, "ci8": _lib.SRC_CI8, "cu8": _lib.SRC_CU8}
-_DEFAULT_SCALE = {"cf32": 1.0, "sc16": _lib.SC16_SCALE, "ci8": _lib.IQ8_SCALE, "cu8": _lib.IQ8_SCALE}
-_NUMPY = {"cf32": np.complex64, "sc16": np.int16, "ci8": np.int8, "cu8": np.uint8}
+FORMATS = _formats.NAMES
 _MASK64 = (1 << 64) - 1
 
 
@@ -28,22 +25,14 @@ def phase_step_of(shift) -> int:
 
 def _format_of(x) -> str:
     """The sample format a tensor's or array's dtype and shape name: complex64 (S,), or int16 / int8 / uint8 (S, 2)."""
-    name = str(x.dtype).replace("torch.", "")
-    if name == "complex64":
-        if x.ndim != 1:
-            raise TypeError("complex64 samples must have shape (S,)")
-        return "cf32"
-    fmt = {"int16": "sc16", "int8": "ci8", "uint8": "cu8"}.get(name)
+    fmt = _formats.by_plain(x.dtype)
     if fmt is None:
+        name = str(x.dtype).replace("torch.", "")
         raise TypeError(f"samples must be complex64 (S,) or int16 / int8 / uint8 (S, 2), not {name}")
-    if x.ndim != 2 or x.shape[1] != 2:
-        raise TypeError(f"{name} samples must have shape (S, 2): the last dimension is (I, Q)")
-    return fmt
-
-
-def _scale_of(fmt: str, scale) -> float:
-    from .features import _sc16_scale
-    return _DEFAULT_SCALE[fmt] if scale is None or fmt == "cf32" else _sc16_scale(scale)
+    if x.ndim < 1 or tuple(x.shape[1:]) != fmt.tail:
+        raise TypeError("complex64 samples must have shape (S,)" if not fmt.tail else
+                        f"{fmt.plain.name} samples must have shape (S, 2): the last dimension is (I, Q)")
+    return fmt.name
 
 
 def windowed_sinc(n_taps: int, cutoff: float, gain=1) -> np.ndarray:
@@ -70,7 +59,7 @@ def front(x, taps, scale, shift, sample_index0, count) -> Front:
     if not isinstance(x, torch.Tensor):
         raise TypeError("x must be a torch tensor (complex64 (S,), or int16 / int8 / uint8 (S, 2))")
     fmt = _format_of(x)
-    scale = _scale_of(fmt, scale)
+    scale = _formats.scale_of(fmt, scale)
     if not x.is_cuda:
         raise ValueError("x must live in GPU memory")
     if not x.is_contiguous():
@@ -84,7 +73,7 @@ def front(x, taps, scale, shift, sample_index0, count) -> Front:
     M = count(S, T)
     step = phase_step_of(shift)
     index0 = int(sample_index0) & _MASK64
-    return Front(_KINDS[fmt], scale, taps, S, T, M, step, index0, (index0 * step) & _MASK64)
+    return Front(_formats.get(fmt).kind, scale, taps, S, T, M, step, index0, (index0 * step) & _MASK64)
 
 
 def launch(x, call) -> None:
@@ -115,7 +104,7 @@ class Stream:
         self.shift, self.fmt = shift, fmt
         self._limits()                 # ValueError outside the kernel's
         phase_step_of(shift)
-        self.scale = _scale_of(fmt, scale)
+        self.scale = _formats.scale_of(fmt, scale)
         self.index = 0                 # absolute index of the sample the next output's window begins at
         self._tail = None              # the samples from there on that have arrived ...
         self._skip = 0                 # ... or, the next window beginning beyond them, how many are still to be dropped before it

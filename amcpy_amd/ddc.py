@@ -16,7 +16,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import _stream
-from ._stream import FORMATS, _DEFAULT_SCALE, _KINDS, _MASK64, _NUMPY, _format_of, _scale_of, phase_step_of  # noqa: F401
+from ._formats import _DEFAULT_SCALE, _KINDS, _NUMPY, scale_of as _scale_of  # noqa: F401
+from ._stream import FORMATS, _MASK64, _format_of, phase_step_of  # noqa: F401
 
 MAX_TAPS, MAX_DECIM = 2048, 4096
 

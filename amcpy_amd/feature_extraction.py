@@ -58,9 +58,8 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _formats, _lib
 from .config import Config
-from .features import CI8, CU8, SC16, _iq8_scale, _sc16_scale
 from .frame_sources import (FileComplex, FrameColumns, FrameRows, SplitComplex, _native_source,  # noqa: F401 (re-exported)
                             as_frame_rows)
 from .sharding import FrameCut, collectives_forced, sharded_features
@@ -106,10 +105,11 @@ class HipEngine:
 
     def __init__(self, frame_size: int, device: Optional[int] = None, chunk_bytes: int = 32 << 20,
                  threads: Optional[int] = None, round_on_device: bool = False, feature_ids=None,
-                 sc16_scale: float = _lib.SC16_SCALE, iq8_scale: float = _lib.IQ8_SCALE):
+                 sc16_scale: float = _formats.get("sc16").scale, iq8_scale: float = _formats.get("ci8").scale):
         self.N = int(frame_size)
-        self.sc16_scale = _sc16_scale(sc16_scale)
-        self.iq8_scale = _iq8_scale(iq8_scale)
+        # what the context multiplies an integer component by, per format (cf32 has none)
+        self.scales = {f.name: _formats.check_scale(sc16_scale if f.family == "sc16" else iq8_scale)
+                       for f in _formats.TABLE if f.family is not None}
         # feature_ids: None (all 18) or the ids to compute; the result stays (F, 18), NaN outside the set (KeyError for an
         # unknown id, here, before anything is launched)
         self.feature_ids = _feature_ids(feature_ids)
@@ -135,9 +135,12 @@ class HipEngine:
             self._ctx = _lib.HostContext(self.device)
             self._ctx.configure(self.threads, self.chunk_bytes, int(self.round_on_device))
             self._ctx.set_feature_mask(self.mask)
-            self._ctx.set_sc16_scale(self.sc16_scale)
-            self._ctx.set_iq8_scale(self.iq8_scale)
+            for fmt, scale in self.scales.items():
+                self._ctx.set_scale(fmt, scale)
         return self._ctx
+
+    sc16_scale = property(lambda self: self.scales["sc16"])
+    iq8_scale = property(lambda self: self.scales["ci8"])
 
     def _run_block(self, src, base_elems: int, n_snr: int, n_frames: int, strides, out: np.ndarray) -> None:
         keep, re_ptr, im_ptr, kind, _, item, fd = src
@@ -186,7 +189,7 @@ class HipEngine:
             # C-ordered copy of the part that is used, then the row path
             # (sc16 stays sc16, 8-bit stays 8-bit: the library takes their row layouts only)
             block = np.ascontiguousarray(rows.to_array(),
-                                         dtype=rows.dtype if rows.dtype in (np.complex64, SC16, CI8, CU8) else np.complex128)
+                                         dtype=rows.dtype if _formats.by_store(rows.dtype) else np.complex128)
             rows = FrameRows(block[None], 1, F)
             src = _native_source(rows.parsed)
         ss, sk, sn = src[4]
@@ -260,7 +263,7 @@ class DeviceFanOut:
     ``sc16_scale`` -- and int8 / uint8 pairs -- at ``iq8_scale`` -- included."""
 
     def __init__(self, frame_size: int, devices, threads: Optional[int] = None, chunk_bytes: int = 32 << 20,
-                 feature_ids=None, iq8_scale: float = _lib.IQ8_SCALE):
+                 feature_ids=None, iq8_scale: float = _formats.get("ci8").scale):
         devices = [int(d) for d in devices]
         feature_ids = _feature_ids(feature_ids)
         if feature_ids is not None:
@@ -400,11 +403,11 @@ def _features_of(engine, part: FrameRows) -> np.ndarray:
 
 
 def _file_stream_features(path, store, offset: int, n_frames: int, N: int, device, feature_ids,
-                          sc16_scale: float = _lib.SC16_SCALE, iq8_scale: float = _lib.IQ8_SCALE) -> np.ndarray:
+                          scale=None) -> np.ndarray:
     """An interleaved stream ``offset`` bytes into a file: the staging threads read it themselves, part by part."""
     stream = FileComplex(path, store, (1, n_frames, N), offset, interleaved=True)
     try:
-        engine = HipEngine(N, device, feature_ids=feature_ids, sc16_scale=sc16_scale, iq8_scale=iq8_scale)
+        engine = HipEngine(N, device, feature_ids=feature_ids, **_formats.scale_kw(_formats.by_store(store).name, scale))
         return np.asarray(engine(FrameRows(stream, 1, n_frames)), dtype=np.float32)
     finally:
         stream.release()
@@ -442,7 +445,7 @@ def extract_modulation(parsed: np.ndarray, cfg: Config, *, compute=None, device:
 
 def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_frames: Optional[int] = None,
                        compute=None, device: Optional[int] = None, feature_ids=None, sample_format: str = "cf32",
-                       scale: float = _lib.SC16_SCALE, scale8: float = _lib.IQ8_SCALE) -> np.ndarray:
+                       scale: float = _formats.get("sc16").scale, scale8: float = _formats.get("ci8").scale) -> np.ndarray:
     """Features of a raw complex64 sample stream on disk (GNU Radio file sink: interleaved
     float32 I/Q, no header -- what the reference's legacy reader takes with
     ``np.fromfile(..., dtype=np.complex64)`` and a fixed number of leading samples dropped,
@@ -457,11 +460,11 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
         raise ValueError("frame_size must be >= 2")
     if skip_samples < 0:
         raise ValueError("skip_samples must be >= 0")
-    if sample_format not in _STREAM_STORES:
+    if sample_format not in _formats.NAMES:
         raise ValueError("sample_format is 'cf32', 'sc16', 'ci8' or 'cu8'")
-    store = _STREAM_STORES[sample_format]
-    scale = _sc16_scale(scale) if sample_format == "sc16" else _lib.SC16_SCALE      # (not read for the other formats)
-    scale8 = _iq8_scale(scale8) if store in (CI8, CU8) else _lib.IQ8_SCALE          # (likewise)
+    store = _formats.get(sample_format).store
+    # the one of the two keywords that is this format's (the other is not read)
+    scale = _formats.scale_of(sample_format, scale if sample_format == "sc16" else scale8)
     n_total = Path(path).stat().st_size // store.itemsize - skip_samples
     n_frames = max(0, n_total // frame_size)
     if max_frames is not None:
@@ -470,21 +473,18 @@ def extract_raw_stream(path, frame_size: int, *, skip_samples: int = 0, max_fram
         return np.empty((0, 18), dtype=np.float32)
     if compute is None:
         return _file_stream_features(path, store, store.itemsize * skip_samples, n_frames, frame_size, device,
-                                     feature_ids, scale, scale8)
+                                     feature_ids, scale)
     frames = np.memmap(path, dtype=store, mode="r", offset=store.itemsize * skip_samples,
                        shape=(n_frames, frame_size))
     if sample_format != "cf32":         # an injected engine (tests) sees the complex64 frames the device computes on
-        frames = widen_integer_frames(frames, scale if sample_format == "sc16" else scale8)
+        frames = widen_integer_frames(frames, scale)
     return np.asarray(compute(frames), dtype=np.float32)
-
-
-_STREAM_STORES = {"cf32": np.dtype(np.complex64), "sc16": SC16, "ci8": CI8, "cu8": CU8}
 
 
 def widen_integer_frames(frames: np.ndarray, scale: float) -> np.ndarray:
     """(..., L) ``SC16`` / ``CI8`` / ``CU8`` samples -> the complex64 frames the device computes on (host copy: tests and
     injected engines): complex64(float32(i) * scale, float32(q) * scale), cu8 components around the zero level 128."""
-    zero = 128 if frames.dtype == CU8 else 0
+    zero = _formats.by_store(frames.dtype).zero
     wide = np.empty(frames.shape, dtype=np.complex64)
     for part, name in ((wide.real, "i"), (wide.imag, "q")):
         part[...] = (frames[name].astype(np.int16) - zero).astype(np.float32) * np.float32(scale)

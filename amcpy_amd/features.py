@@ -25,7 +25,8 @@ from typing import Iterable, List
 
 import numpy as np
 
-from . import _lib
+from . import _formats, _lib
+from ._formats import CI8, CU8, SC16, iq8_view, sc16_view  # noqa: F401  (their home; imported from here by name)
 
 FEATURE_IDS = tuple(range(1, _lib.NUM_FEATURES + 1))
 
@@ -104,32 +105,56 @@ def features18(iq, out=None, *, frame_size: int | None = None, variant="auto", f
     N = _frame_size(frame_size, L)
     if iq.stride(-1) != 1 and L > 1:
         raise ValueError("last dimension must have unit stride")
-    lead, n_frames, row_stride = _flat_frames(iq, L, N)
+    return _features_on_device(iq, out, _formats.get("cf32"), L, N, variant, mask)
+
+
+def _features_on_device(iq, out, fmt, L: int, N: int, variant, mask, scale=None, chunk_frames=None):
+    """What :func:`features18`, :func:`features18_sc16` and :func:`features18_iq8` do once their arguments have passed: the
+    frames of ``iq`` (samples of ``fmt``, rows of L of which N are used) flattened, ``out`` made or checked, the workspace
+    taken from torch's allocator, the library called on the current stream -- once, or, ``chunk_frames``, once per chunk --
+    and the (..., 18) result."""
+    import torch
+
+    family = fmt.family
+    lead, n_frames, row_stride = _flat_frames(iq, L, N, fmt.tail)
     out, oflat, out_stride = _out_frames(iq, out, lead, n_frames)
+    _lib.require_torch_runtime()
     lib = _lib.load()
     v = _variant(variant)
+    if family is None:
+        query = lib.amcx_features18_workspace_bytes
+    else:
+        query, entry = getattr(lib, f"amcx_features_{family}_workspace_bytes"), getattr(lib, f"amcx_features_{family}")
+        head = (scale,) if fmt.iq8 is None else (fmt.iq8, scale)
+    if n_frames == 0 and family == "iq8":                  # nothing to widen: the call only checks the other arguments
+        _lib.check(entry(None, 0, N, row_stride, *head, None, out_stride, None, v, mask, None, 0))
+        return out[..., :_lib.NUM_FEATURES]
+    per_call = n_frames if chunk_frames is None else min(int(chunk_frames), n_frames)
     with torch.cuda.device(iq.device):
-        stream = torch.cuda.current_stream(iq.device).cuda_stream
-        # The any-size path above 8192 samples wants a workspace for its FFT form (amcx_features18_workspace_bytes: 0 for
-        # every other size).  It comes from TORCH's allocator here -- the allocator that owns this process's device
-        # memory -- through amcx_features18_c64_ws: left to amcx_features18_c64_ex it would come from HIP's own
-        # stream-ordered pool, which knows nothing of what torch has cached, and a failed allocation there silently
-        # selects the O(N^2) form (~100x slower at N = 32767).  torch raises if it cannot provide the bytes.
-        need = int(lib.amcx_features18_workspace_bytes(N, n_frames, v)) if n_frames > 0 else 0
-        if mask is not None:
-            ws = torch.empty(need, dtype=torch.uint8, device=iq.device) if need > 0 else None
-            _lib.check(lib.amcx_features_c64_subset(iq.data_ptr(), n_frames, N, row_stride, oflat.data_ptr(), out_stride,
-                                                    stream, v, mask, None if ws is None else ws.data_ptr(), need))
-            if ws is not None:
-                ws.record_stream(torch.cuda.current_stream(iq.device))
-        elif need > 0:
-            ws = torch.empty(need, dtype=torch.uint8, device=iq.device)
-            _lib.check(lib.amcx_features18_c64_ws(iq.data_ptr(), n_frames, N, row_stride, oflat.data_ptr(), out_stride,
-                                                  stream, v, ws.data_ptr(), need))
-            ws.record_stream(torch.cuda.current_stream(iq.device))       # freed for reuse behind the launch, not before
-        else:
-            _lib.check(lib.amcx_features18_c64_ex(
-                iq.data_ptr(), n_frames, N, row_stride, oflat.data_ptr(), out_stride, stream, v))
+        cur = torch.cuda.current_stream(iq.device)
+        # The workspace -- the widened copy of the integer frames that no kernel reads as they lie, and what the any-size
+        # path above 8192 samples wants for its FFT form; 0 bytes for complex64 at every other size -- comes from TORCH's
+        # allocator, the one that owns this process's device memory: left to amcx_features18_c64_ex it would come from
+        # HIP's own stream-ordered pool, which knows nothing of what torch has cached, and a failed allocation there
+        # silently selects the O(N^2) form (~100x slower at N = 32767).  torch raises if it cannot provide the bytes.
+        # (A negative answer: the call itself says what is wrong with the arguments.)
+        need = max(0, int(query(N, per_call, v))) if n_frames > 0 else 0
+        ws = torch.empty(need, dtype=torch.uint8, device=iq.device) if need > 0 else None
+        ws_ptr = None if ws is None else ws.data_ptr()
+        for f0 in range(0, max(n_frames, 1), max(per_call, 1)):              # (no frames: still the one call)
+            src = (iq.data_ptr() + fmt.store.itemsize * f0 * row_stride, min(per_call, n_frames - f0), N, row_stride)
+            dst = (oflat.data_ptr() + 4 * f0 * out_stride, out_stride, cur.cuda_stream, v)
+            if family is not None:
+                rc = entry(*src, *head, *dst, mask, ws_ptr, need)
+            elif mask is not None:
+                rc = lib.amcx_features_c64_subset(*src, *dst, mask, ws_ptr, need)
+            elif need > 0:
+                rc = lib.amcx_features18_c64_ws(*src, *dst, ws_ptr, need)
+            else:                                          # allocates nothing: what a resident caller under graph capture runs
+                rc = lib.amcx_features18_c64_ex(*src, *dst)
+            _lib.check(rc)
+        if ws is not None:
+            ws.record_stream(cur)                          # freed for reuse behind the launch, not before
     return out[..., :_lib.NUM_FEATURES]
 
 
@@ -146,29 +171,29 @@ def features18_iq_pairs(iq_pairs, **kw):
     return features18(torch.view_as_complex(iq_pairs), **kw)
 
 
-# one sc16 sample as numpy sees it: two little-endian int16, I then Q (include/amcx.h, amcx_features_sc16)
-SC16 = np.dtype([("i", "<i2"), ("q", "<i2")])
+def _pairs_on_device(iq, out, family: str, what: str, scale, frame_size, variant, feature_ids, chunk_frames=None):
+    """:func:`features18_sc16` (``family`` "sc16") and :func:`features18_iq8` ("iq8"): their checks, in their order."""
+    import torch
+
+    mask = _lib.FEATURES_ALL if feature_ids is None else _lib.feature_mask(feature_ids)
+    scale = _formats.check_scale(scale)
+    fmt = _formats.by_plain(iq.dtype) if isinstance(iq, torch.Tensor) else None
+    if fmt is None or fmt.family != family:
+        raise TypeError(f"iq must be a {what} tensor")
+    if iq.dim() < 2 or iq.shape[-1] != 2:
+        raise TypeError("iq must have shape (..., L, 2): the last dimension is (I, Q)")
+    L = iq.shape[-2]
+    if iq.stride(-1) != 1 or (L > 1 and iq.stride(-2) != 2):
+        raise ValueError("(I, Q) pairs must be interleaved in memory")
+    if not iq.is_cuda:
+        raise ValueError(f"iq must live in GPU memory (use features18_{family}_host for numpy input)")
+    N = _frame_size(frame_size, L)
+    if chunk_frames is not None and int(chunk_frames) < 1:
+        raise ValueError("chunk_frames must be at least 1")
+    return _features_on_device(iq, out, fmt, L, N, variant, mask, scale, chunk_frames)
 
 
-def _sc16_scale(scale) -> float:
-    """``scale`` as the float32 the library multiplies by; ValueError unless it is finite and > 0."""
-    s = float(np.float32(scale))
-    if not (np.isfinite(s) and s > 0.0):
-        raise ValueError(f"scale must be a finite float32 > 0, got {scale!r}")
-    return s
-
-
-def sc16_view(pairs: np.ndarray) -> np.ndarray:
-    """(..., L, 2) int16 -> (..., L) view of :data:`SC16` samples (no copy).  TypeError for another dtype or a last
-    dimension that is not 2, ValueError for pairs that are not interleaved in memory."""
-    if not isinstance(pairs, np.ndarray) or pairs.dtype != np.int16 or pairs.ndim < 2 or pairs.shape[-1] != 2:
-        raise TypeError("expected an int16 array whose last dimension is (I, Q)")
-    if pairs.strides[-1] != 2 or any(st % 4 for st in pairs.strides[:-1]):
-        raise ValueError("(I, Q) int16 pairs must be interleaved in memory")
-    return pairs.view(SC16)[..., 0]
-
-
-def features18_sc16(iq, out=None, *, scale=_lib.SC16_SCALE, frame_size: int | None = None, variant="auto",
+def features18_sc16(iq, out=None, *, scale=_formats.get("sc16").scale, frame_size: int | None = None, variant="auto",
                     feature_ids=None):
     """The features of every frame of 16-bit integer IQ in GPU memory, read as it lies (amcx_features_sc16).
 
@@ -179,58 +204,10 @@ def features18_sc16(iq, out=None, *, scale=_lib.SC16_SCALE, frame_size: int | No
     out, frame_size, variant, feature_ids: as :func:`features18`.
     At 128 ... 4096 (wave / auto) kernels read the int16 themselves; every other size and variant widens the frames
     into a workspace from torch's allocator and runs the complex64 path."""
-    import torch
-
-    mask = _lib.FEATURES_ALL if feature_ids is None else _lib.feature_mask(feature_ids)
-    scale = _sc16_scale(scale)
-    if not isinstance(iq, torch.Tensor) or iq.dtype != torch.int16:
-        raise TypeError("iq must be a torch.int16 tensor")
-    if iq.dim() < 2 or iq.shape[-1] != 2:
-        raise TypeError("iq must have shape (..., L, 2): the last dimension is (I, Q)")
-    L = iq.shape[-2]
-    if iq.stride(-1) != 1 or (L > 1 and iq.stride(-2) != 2):
-        raise ValueError("(I, Q) pairs must be interleaved in memory")
-    if not iq.is_cuda:
-        raise ValueError("iq must live in GPU memory (use features18_sc16_host for numpy input)")
-    N = _frame_size(frame_size, L)
-    lead, n_frames, row_stride = _flat_frames(iq, L, N, (2,))
-    out, oflat, out_stride = _out_frames(iq, out, lead, n_frames)
-    _lib.require_torch_runtime()
-    lib = _lib.load()
-    v = _variant(variant)
-    with torch.cuda.device(iq.device):
-        stream = torch.cuda.current_stream(iq.device).cuda_stream
-        # the widened copy and the any-size path's FFT workspace, from torch's allocator (see features18)
-        need = int(lib.amcx_features_sc16_workspace_bytes(N, n_frames, v)) if n_frames > 0 else 0
-        ws = torch.empty(need, dtype=torch.uint8, device=iq.device) if need > 0 else None
-        _lib.check(lib.amcx_features_sc16(iq.data_ptr(), n_frames, N, row_stride, scale, oflat.data_ptr(), out_stride,
-                                          stream, v, mask, None if ws is None else ws.data_ptr(), max(need, 0)))
-        if ws is not None:
-            ws.record_stream(torch.cuda.current_stream(iq.device))
-    return out[..., :_lib.NUM_FEATURES]
+    return _pairs_on_device(iq, out, "sc16", "torch.int16", scale, frame_size, variant, feature_ids)
 
 
-# one 8-bit sample as numpy sees it: two bytes, I then Q (include/amcx.h, amcx_features_iq8) -- int8 (ci8), or uint8
-# around the zero level 128 (cu8)
-CI8 = np.dtype([("i", "i1"), ("q", "i1")])
-CU8 = np.dtype([("i", "u1"), ("q", "u1")])
-
-
-def _iq8_scale(scale) -> float:
-    return _sc16_scale(scale)
-
-
-def iq8_view(pairs: np.ndarray) -> np.ndarray:
-    """(..., L, 2) int8 / uint8 -> (..., L) view of :data:`CI8` / :data:`CU8` samples (no copy).  TypeError for another
-    dtype or a last dimension that is not 2, ValueError for pairs that are not interleaved in memory."""
-    if not isinstance(pairs, np.ndarray) or pairs.dtype not in (np.int8, np.uint8) or pairs.ndim < 2 or pairs.shape[-1] != 2:
-        raise TypeError("expected an int8 or uint8 array whose last dimension is (I, Q)")
-    if pairs.strides[-1] != 1 or any(st % 2 for st in pairs.strides[:-1]) or (pairs.shape[-2] > 1 and pairs.strides[-2] != 2):
-        raise ValueError("(I, Q) byte pairs must be interleaved in memory")
-    return pairs.view(CI8 if pairs.dtype == np.int8 else CU8)[..., 0]
-
-
-def features18_iq8(iq, out=None, *, scale=_lib.IQ8_SCALE, frame_size: int | None = None, variant="auto",
+def features18_iq8(iq, out=None, *, scale=_formats.get("ci8").scale, frame_size: int | None = None, variant="auto",
                    feature_ids=None, chunk_frames: int | None = None):
     """The features of every frame of 8-bit IQ in GPU memory (amcx_features_iq8): widened on the device, then the
     kernels :func:`features18_sc16` (128 ... 4096, wave / auto) or :func:`features18` run.
@@ -247,45 +224,8 @@ def features18_iq8(iq, out=None, *, scale=_lib.IQ8_SCALE, frame_size: int | None
             (profiles/r14_iq8_bench.json: calls of a few thousand frames are launch-bound).  Frames are independent: the
             result does not depend on it, bit for bit.
     out, frame_size, variant, feature_ids: as :func:`features18`."""
-    import torch
-
-    mask = _lib.FEATURES_ALL if feature_ids is None else _lib.feature_mask(feature_ids)
-    scale = _iq8_scale(scale)
-    if not isinstance(iq, torch.Tensor) or iq.dtype not in (torch.int8, torch.uint8):
-        raise TypeError("iq must be a torch.int8 (ci8) or torch.uint8 (cu8) tensor")
-    if iq.dim() < 2 or iq.shape[-1] != 2:
-        raise TypeError("iq must have shape (..., L, 2): the last dimension is (I, Q)")
-    L = iq.shape[-2]
-    if iq.stride(-1) != 1 or (L > 1 and iq.stride(-2) != 2):
-        raise ValueError("(I, Q) pairs must be interleaved in memory")
-    if not iq.is_cuda:
-        raise ValueError("iq must live in GPU memory (use features18_iq8_host for numpy input)")
-    N = _frame_size(frame_size, L)
-    if chunk_frames is not None and int(chunk_frames) < 1:
-        raise ValueError("chunk_frames must be at least 1")
-    lead, n_frames, row_stride = _flat_frames(iq, L, N, (2,))
-    out, oflat, out_stride = _out_frames(iq, out, lead, n_frames)
-    _lib.require_torch_runtime()
-    lib = _lib.load()
-    v = _variant(variant)
-    fmt = _lib.IQ8_CI8 if iq.dtype == torch.int8 else _lib.IQ8_CU8
-    if n_frames == 0:
-        _lib.check(lib.amcx_features_iq8(None, 0, N, row_stride, fmt, scale, None, out_stride, None, v, mask, None, 0))
-        return out[..., :_lib.NUM_FEATURES]
-    per_call = n_frames if chunk_frames is None else min(int(chunk_frames), n_frames)
-    with torch.cuda.device(iq.device):
-        cur = torch.cuda.current_stream(iq.device)
-        need = int(lib.amcx_features_iq8_workspace_bytes(N, per_call, v))
-        if need < 0:                       # the call itself says what is wrong with the arguments
-            need = 0
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=iq.device)
-        for f0 in range(0, n_frames, per_call):
-            n = min(per_call, n_frames - f0)
-            _lib.check(lib.amcx_features_iq8(iq.data_ptr() + 2 * f0 * row_stride, n, N, row_stride, fmt, scale,
-                                             oflat.data_ptr() + 4 * f0 * out_stride, out_stride, cur.cuda_stream, v, mask,
-                                             ws.data_ptr(), need))
-        ws.record_stream(cur)
-    return out[..., :_lib.NUM_FEATURES]
+    return _pairs_on_device(iq, out, "iq8", "torch.int8 (ci8) or torch.uint8 (cu8)", scale, frame_size, variant, feature_ids,
+                            chunk_frames)
 
 
 _tls = threading.local()
@@ -303,8 +243,16 @@ def _host_context(device: int) -> "_lib.HostContext":
     return ctx
 
 
-def _run_on_host_context(ctx, x2: np.ndarray, N: int, lead, variant, mask) -> np.ndarray:
-    """The flattened frames ``x2`` through the context ``ctx`` -> (lead..., 18) float32."""
+def _features_on_host(x: np.ndarray, tail: tuple, frame_size, device, variant, mask, fmt=None, scale=None) -> np.ndarray:
+    """What the three host entries do once their arguments have passed: the frames (..., L) + tail, made contiguous, through
+    this thread's context (at ``scale`` for the integer format ``fmt``) -> (..., 18) float32."""
+    L = x.shape[x.ndim - 1 - len(tail)]
+    N = _frame_size(frame_size, L)
+    lead = x.shape[:x.ndim - 1 - len(tail)]
+    x2 = np.ascontiguousarray(x.reshape((-1, L) + tail))
+    ctx = _host_context(int(device))
+    if fmt is not None:
+        ctx.set_scale(fmt.name, scale)
     out = np.empty((x2.shape[0], _lib.NUM_FEATURES), dtype=np.float32)
     ctx.set_feature_mask(_lib.FEATURES_ALL if mask is None else mask)
     ctx.run(x2, N, out, _variant(variant))
@@ -320,35 +268,26 @@ def features18_host(frames: np.ndarray, *, frame_size: int | None = None, device
     columns not asked for).  Raises if no MI355X is present (AMCX_ENODEV)."""
     mask = _mask(feature_ids)
     x = np.asarray(frames)
-    if not np.iscomplexobj(x):
-        x = x.astype(np.complex64)
-    L = x.shape[-1]
-    N = _frame_size(frame_size, L)
-    lead = x.shape[:-1]
-    if x.dtype == np.complex128:
-        # MATLAB doubles: uploaded as they are, rounded to complex64 on the GPU
-        x2 = np.ascontiguousarray(x.reshape(-1, L))
-    else:
-        x2 = np.ascontiguousarray(x.reshape(-1, L), dtype=np.complex64)
-    return _run_on_host_context(_host_context(int(device)), x2, N, lead, variant, mask)
+    if x.dtype != np.complex128:                            # (MATLAB doubles alone go up as they are)
+        x = x.astype(np.complex64, copy=False)
+    return _features_on_host(x, (), frame_size, device, variant, mask)
 
 
-def features18_sc16_host(frames: np.ndarray, *, scale=_lib.SC16_SCALE, frame_size: int | None = None, device: int = 0,
-                         variant="auto", feature_ids=None) -> np.ndarray:
+def _pairs_on_host(frames, family: str, what: str, scale, frame_size, device, variant, feature_ids) -> np.ndarray:
+    """:func:`features18_sc16_host` (``family`` "sc16") and :func:`features18_iq8_host` ("iq8"): their checks, in their order."""
+    mask = _mask(feature_ids)
+    scale = _formats.check_scale(scale)
+    fmt = _formats.by_plain(frames.dtype) if isinstance(frames, np.ndarray) else None
+    if fmt is None or fmt.family != family or frames.ndim < 2 or frames.shape[-1] != 2:
+        raise TypeError(f"expected an {what} array whose last dimension is (I, Q)")
+    return _features_on_host(frames, fmt.tail, frame_size, device, variant, mask, fmt, scale)
+
+
+def features18_sc16_host(frames: np.ndarray, *, scale=_formats.get("sc16").scale, frame_size: int | None = None,
+                         device: int = 0, variant="auto", feature_ids=None) -> np.ndarray:
     """numpy (..., L, 2) int16 (I, Q) pairs -> numpy (..., 18) float32 via the GPU.  The samples cross the link as
     they lie, 4 bytes each, and are never widened on the host; the result equals :func:`features18_sc16`'s."""
-    mask = _mask(feature_ids)
-    scale = _sc16_scale(scale)
-    x = frames
-    if not isinstance(x, np.ndarray) or x.dtype != np.int16 or x.ndim < 2 or x.shape[-1] != 2:
-        raise TypeError("expected an int16 array whose last dimension is (I, Q)")
-    L = x.shape[-2]
-    N = _frame_size(frame_size, L)
-    lead = x.shape[:-2]
-    x2 = np.ascontiguousarray(x.reshape(-1, L, 2))
-    ctx = _host_context(int(device))
-    ctx.set_sc16_scale(scale)
-    return _run_on_host_context(ctx, x2, N, lead, variant, mask)
+    return _pairs_on_host(frames, "sc16", "int16", scale, frame_size, device, variant, feature_ids)
 
 
 def calculate_features(feature_ids: Iterable[int], signal, *, device: int = 0,
@@ -371,19 +310,8 @@ def calculate_features(feature_ids: Iterable[int], signal, *, device: int = 0,
     return [float(row[fid - 1]) for fid in ids]
 
 
-def features18_iq8_host(frames: np.ndarray, *, scale=_lib.IQ8_SCALE, frame_size: int | None = None, device: int = 0,
-                        variant="auto", feature_ids=None) -> np.ndarray:
+def features18_iq8_host(frames: np.ndarray, *, scale=_formats.get("ci8").scale, frame_size: int | None = None,
+                        device: int = 0, variant="auto", feature_ids=None) -> np.ndarray:
     """numpy (..., L, 2) int8 (ci8) / uint8 (cu8) (I, Q) pairs -> numpy (..., 18) float32 via the GPU.  The samples cross
     the link as they lie, 2 bytes each, and are widened by the device; the result equals :func:`features18_iq8`'s."""
-    mask = _mask(feature_ids)
-    scale = _iq8_scale(scale)
-    x = frames
-    if not isinstance(x, np.ndarray) or x.dtype not in (np.int8, np.uint8) or x.ndim < 2 or x.shape[-1] != 2:
-        raise TypeError("expected an int8 or uint8 array whose last dimension is (I, Q)")
-    L = x.shape[-2]
-    N = _frame_size(frame_size, L)
-    lead = x.shape[:-2]
-    x2 = np.ascontiguousarray(x.reshape(-1, L, 2))
-    ctx = _host_context(int(device))
-    ctx.set_iq8_scale(scale)
-    return _run_on_host_context(ctx, x2, N, lead, variant, mask)
+    return _pairs_on_host(frames, "iq8", "int8 or uint8", scale, frame_size, device, variant, feature_ids)

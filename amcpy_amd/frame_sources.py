@@ -9,8 +9,17 @@ from typing import Iterator, Optional, Tuple
 
 import numpy as np
 
-from . import _lib
-from .features import CI8, CU8, SC16, iq8_view, sc16_view
+from . import _formats, _lib
+
+# the element kinds of a container that are no sample formats of the table: doubles, and real arrays (two of them: a split container)
+_OTHER_KINDS = {np.dtype(np.complex128): _lib.SRC_C128, np.dtype(np.float32): _lib.SRC_F32_SPLIT,
+                np.dtype(np.float64): _lib.SRC_F64_SPLIT}
+
+
+def _kind_of(dtype):
+    """The ``AMCX_SRC_*`` kind of a container of ``dtype`` elements, or None where the library reads none such."""
+    fmt = _formats.by_store(dtype)
+    return _OTHER_KINDS.get(np.dtype(dtype)) if fmt is None else fmt.kind
 
 
 class SplitComplex:
@@ -54,7 +63,7 @@ class FileComplex:
         self.interleaved = bool(interleaved)
         if not self.interleaved and self.store not in (np.float32, np.float64):
             raise TypeError(f"split containers hold float32 or float64, got {self.store}")
-        if self.interleaved and self.store not in (np.complex64, np.complex128, SC16, CI8, CU8):
+        if self.interleaved and self.store != np.complex128 and _formats.by_store(self.store) is None:
             raise TypeError(f"interleaved containers hold complex64, complex128, sc16, ci8 or cu8, got {self.store}")
         self.shape, self.ndim = tuple(int(x) for x in shape), len(shape)
         self.real_offset, self.imag_offset = int(real_offset), (None if imag_offset is None else int(imag_offset))
@@ -186,26 +195,17 @@ def _native_source(arr):
     native engine can read in place -- pointers, or byte offsets into the file ``fd`` -- or None if it has to be
     copied first."""
     if isinstance(arr, FileComplex):
-        if arr.interleaved:
-            kind = {SC16: _lib.SRC_SC16, CI8: _lib.SRC_CI8, CU8: _lib.SRC_CU8,
-                    np.dtype(np.complex64): _lib.SRC_C64}.get(arr.store, _lib.SRC_C128)
-        else:
-            kind = _lib.SRC_F32_SPLIT if arr.store == np.float32 else _lib.SRC_F64_SPLIT
-        return arr, arr.real_offset, arr.imag_offset, kind, list(arr.strides_elems), arr.store.itemsize, arr.fileno()
+        return arr, arr.real_offset, arr.imag_offset, _kind_of(arr.store), list(arr.strides_elems), arr.store.itemsize, arr.fileno()
     if isinstance(arr, SplitComplex):
         re, im = arr.real, arr.imag
-        kind = _lib.SRC_F32_SPLIT if re.dtype == np.float32 else _lib.SRC_F64_SPLIT
-    elif isinstance(arr, np.ndarray) and arr.dtype in (np.complex64, np.complex128, np.float32, np.float64, SC16, CI8, CU8):
+    elif isinstance(arr, np.ndarray) and _kind_of(arr.dtype) is not None:
         re, im = arr, None
-        kind = {np.dtype(np.complex64): _lib.SRC_C64, np.dtype(np.complex128): _lib.SRC_C128,
-                np.dtype(np.float32): _lib.SRC_F32_SPLIT, np.dtype(np.float64): _lib.SRC_F64_SPLIT,
-                SC16: _lib.SRC_SC16, CI8: _lib.SRC_CI8, CU8: _lib.SRC_CU8}[arr.dtype]
     else:
         return None
     item = re.itemsize
     if any(st < 0 or st % item for st in re.strides):
         return None
-    return (re, im), re.ctypes.data, (None if im is None else im.ctypes.data), kind, [st // item for st in re.strides], item, None
+    return (re, im), re.ctypes.data, (None if im is None else im.ctypes.data), _kind_of(re.dtype), [st // item for st in re.strides], item, None
 
 
 def as_frame_rows(frames) -> FrameRows:
@@ -215,10 +215,9 @@ def as_frame_rows(frames) -> FrameRows:
     if isinstance(frames, FrameRows):
         return frames
     arr = frames if isinstance(frames, SplitComplex) else np.asarray(frames)
-    if not isinstance(arr, SplitComplex) and arr.dtype == np.int16:
-        arr = sc16_view(arr)                                 # (F, L, 2) int16 pairs -> (F, L) sc16 samples, no copy
-    elif not isinstance(arr, SplitComplex) and arr.dtype in (np.int8, np.uint8):
-        arr = iq8_view(arr)                                  # (F, L, 2) byte pairs -> (F, L) ci8 / cu8 samples, no copy
+    family = None if isinstance(arr, SplitComplex) else getattr(_formats.by_plain(arr.dtype), "family", None)
+    if family is not None:                                   # (F, L, 2) integer pairs -> (F, L) stored samples, no copy
+        arr = (_formats.sc16_view if family == "sc16" else _formats.iq8_view)(arr)
     if arr.ndim != 2:
         raise ValueError(f"expected (F, L) frames, got shape {arr.shape}")
     if isinstance(arr, SplitComplex):

@@ -156,7 +156,7 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> P
     capture's core:frequency where it has one)."""
     import numpy as np
     from scipy.io import savemat
-    from . import sigmf
+    from . import _formats, sigmf
     from .feature_extraction import extract_raw_stream
     ids = resolve_features(args.features, Config())
     path = Path(args.file)
@@ -187,9 +187,8 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> P
             raise SystemExit("the tuning flags need a SigMF recording (its meta file holds the sample rate)")
         if args.format is None:
             raise SystemExit(f"{path} is no SigMF recording: --format cf32|sc16|ci8|cu8 says what its samples are")
-        kw = {} if args.scale is None else {"scale" if args.format == "sc16" else "scale8": args.scale}
         feats = extract_raw_stream(path, args.frame_size, device=args.device, feature_ids=ids, sample_format=args.format,
-                                   compute=compute, **kw)
+                                   compute=compute, **_formats.scale_kw(args.format, args.scale, "scale", "scale8"))
         frame_start = args.frame_size * np.arange(feats.shape[0], dtype=np.int64)
         stem = path.with_suffix("")
     out = Path(args.out) if args.out is not None else stem.with_name(stem.name + "_features.mat")

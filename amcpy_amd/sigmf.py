@@ -24,16 +24,10 @@ from typing import Optional
 
 import numpy as np
 
-from . import _lib
-from .features import CI8, CU8, SC16
+from . import _formats
 
 # core:datatype -> (sample_format of extract_raw_stream, stored sample, default scale)
-DATATYPES = {
-    "cf32_le": ("cf32", np.dtype(np.complex64), 1.0),
-    "ci16_le": ("sc16", SC16, _lib.SC16_SCALE),
-    "ci8": ("ci8", CI8, _lib.IQ8_SCALE),
-    "cu8": ("cu8", CU8, _lib.IQ8_SCALE),
-}
+DATATYPES = {f.sigmf: (f.name, f.store, f.scale) for f in _formats.TABLE}
 META_SUFFIX, DATA_SUFFIX = ".sigmf-meta", ".sigmf-data"
 
 
@@ -204,10 +198,6 @@ def is_rational_tune(tune) -> bool:
     return isinstance(tune, ResolvedResample) or (isinstance(tune, dict) and ("resample" in tune or bool(tune.get("rational", False))))
 
 
-# the plain numpy dtype and trailing shape of one stored sample, for the tuned path's chunks
-_PLAIN = {"cf32": (np.dtype("<c8"), ()), "sc16": (np.dtype("<i2"), (2,)), "ci8": (np.dtype("i1"), (2,)), "cu8": (np.dtype("u1"), (2,))}
-
-
 def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, chunk_samples):
     """The tuned path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.ddc.Channelizer` -- or, a
     rational ``tune``, a :class:`amcpy_amd.resample.Resampler` -- in chunks."""
@@ -221,7 +211,7 @@ def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune
         shift, D, taps = resolve_tune(rec["meta"], tune)
         L = 1
     fmt = rec["sample_format"]
-    plain, tail = _PLAIN[fmt]
+    plain, tail = _formats.get(fmt).plain, _formats.get(fmt).tail      # of one stored sample, for the chunks
     on_gpu = tune_compute is None
     if on_gpu:
         import torch                                       # this path alone: the untuned one stays torch-free
@@ -296,7 +286,7 @@ def _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, c
     from .bank import FilterBank
     shift, C, D, taps = resolve_channelize(rec["meta"], channelize)
     fmt = rec["sample_format"]
-    plain, tail = _PLAIN[fmt]
+    plain, tail = _formats.get(fmt).plain, _formats.get(fmt).tail      # of one stored sample, for the chunks
     on_gpu = bank_compute is None
     if on_gpu:
         import torch                                       # this path alone: the untuned one stays torch-free
@@ -374,14 +364,13 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     injected bank over numpy chunks (tests, as :class:`amcpy_amd.bank.FilterBank`'s ``compute``); ``compute`` then sees
     the (C * n, frame_size) complex64 frames of a segment, channel-major."""
     from .feature_extraction import FileComplex, FrameRows, HipEngine, _subset, widen_integer_frames
-    from .features import _sc16_scale
     feature_ids, compute = _subset(feature_ids, compute)
     N = int(frame_size)
     if N < 2:
         raise ValueError("frame_size must be >= 2")
     rec = read_meta(path)
     store, fmt = rec["store"], rec["sample_format"]
-    scale = rec["scale"] if scale is None or fmt == "cf32" else _sc16_scale(scale)
+    scale = _formats.scale_of(fmt, scale)
     left = None if max_frames is None else max(0, int(max_frames))
     if tune is not None and channelize is not None:
         raise ValueError("tune and channelize exclude each other: one emitter, or every channel of a raster")
@@ -401,8 +390,7 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
                 left -= n
             if compute is None:
                 if engine is None:
-                    engine = HipEngine(N, device, feature_ids=feature_ids, sc16_scale=scale if fmt == "sc16" else _lib.SC16_SCALE,
-                                       iq8_scale=scale if fmt in ("ci8", "cu8") else _lib.IQ8_SCALE)
+                    engine = HipEngine(N, device, feature_ids=feature_ids, **_formats.scale_kw(fmt, scale))
                 stream = FileComplex(rec["data_path"], store, (1, n, N), off, interleaved=True)
                 try:
                     parts.append(np.asarray(engine(FrameRows(stream, 1, n)), dtype=np.float32))

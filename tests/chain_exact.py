@@ -24,8 +24,10 @@ from fractions import Fraction
 
 import numpy as np
 
-FORMATS = ("cf32", "sc16", "ci8", "cu8")
-NUMPY = {"cf32": np.complex64, "sc16": np.int16, "ci8": np.int8, "cu8": np.uint8}
+from amcpy_amd import _formats
+
+FORMATS = _formats.NAMES
+NUMPY = {f.name: f.plain for f in _formats.TABLE}
 UNIT = {"cf32": 1.0, "sc16": 2.0 ** -7, "ci8": 2.0 ** -7, "cu8": 2.0 ** -7}     # g, at the formats' default scales (asserted there)
 K_MAX, H_MAX = 128, 8
 U = 2.0 ** -24
@@ -72,7 +74,7 @@ def encode(k, fmt):
     k = np.asarray(k, dtype=np.int64)
     if fmt == "cf32":
         return (k[:, 0] + 1j * k[:, 1]).astype(np.complex64)
-    raw = {"sc16": k * 256, "ci8": k, "cu8": k + 128}[fmt]
+    raw = k * (256 if fmt == "sc16" else 1) + _formats.get(fmt).zero
     info = np.iinfo(NUMPY[fmt])
     assert raw.min() >= info.min and raw.max() <= info.max
     return np.ascontiguousarray(raw.astype(NUMPY[fmt]))

@@ -18,6 +18,8 @@ it about as often as not.  Those shapes are held to an EQUALITY instead: tests/c
 arithmetic in any order is exact, and tests/test_gpu_chain_exact.py compares every output with == against int64 arithmetic."""
 import numpy as np
 
+from amcpy_amd import _formats
+
 MASK64 = (1 << 64) - 1
 ODD_STEP = 0x9E3779B97F4A7C15          # an odd 64-bit constant: every bit of the phase accumulator moves
 U = 2.0 ** -24
@@ -32,7 +34,7 @@ def widen(raw, fmt, scale):
     float32(i) * float32(scale), cu8 as byte - 128."""
     if fmt == "cf32":
         return np.asarray(raw, dtype=np.complex64).astype(np.complex128)
-    ints = raw.astype(np.int32) - (128 if fmt == "cu8" else 0)
+    ints = raw.astype(np.int32) - _formats.get(fmt).zero
     w = ints.astype(np.float32) * np.float32(scale)
     return w[:, 0].astype(np.float64) + 1j * w[:, 1].astype(np.float64)
 

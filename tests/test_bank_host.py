@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from amcpy_amd import _lib, bank, ddc
-from tests import bank_ref, ddc_ref
+from tests import bank_ref, ddc_ref, stream_inputs
 
 REPO = Path(__file__).resolve().parents[1]
 NEW = ["amcx_filter_bank", "amcx_filter_bank_out_samples", "amcx_filter_bank_plan", "amcx_kernel_name_bank"]
@@ -172,11 +172,7 @@ def test_channel_frequencies():
             bank.channel_frequencies(bad)
 
 
-def _stream(fmt, S, rng):
-    if fmt == "cf32":
-        return (rng.standard_normal(S) + 1j * rng.standard_normal(S)).astype(np.complex64)
-    info = np.iinfo(ddc._NUMPY[fmt])
-    return rng.integers(info.min, info.max + 1, (S, 2)).astype(ddc._NUMPY[fmt])
+_stream = stream_inputs.stream
 
 
 def test_numpy_bank_is_the_reference():

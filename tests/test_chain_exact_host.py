@@ -4,7 +4,7 @@ for every GPU case, and the comparison sees ONE term of ONE output, dropped or d
 import numpy as np
 import pytest
 
-from amcpy_amd import _lib, ddc
+from amcpy_amd import _formats, _lib, ddc
 from tests import bank_ref, chain_exact as ce, ddc_ref, resample_ref
 
 TURNS = list(range(4))
@@ -16,7 +16,7 @@ def _phases(shift, index0):
 
 
 def _wide(k, fmt):
-    return ddc_ref.widen(ce.encode(k, fmt), fmt, ddc._DEFAULT_SCALE[fmt])
+    return ddc_ref.widen(ce.encode(k, fmt), fmt, _formats.get(fmt).scale)
 
 
 def _close(exact, g, y64, s):
@@ -40,14 +40,14 @@ def _snap(y, g):
 def test_the_formats_carry_the_same_values_and_the_scales_are_powers_of_two():
     assert tuple(ddc.FORMATS) == ce.FORMATS
     for fmt in ce.FORMATS:
-        scale = ddc._DEFAULT_SCALE[fmt]
+        scale = _formats.get(fmt).scale
         assert np.frexp(scale)[0] == 0.5 and np.frexp(ce.UNIT[fmt])[0] == 0.5
         assert ce.UNIT[fmt] == scale * (256 if fmt == "sc16" else 1)
     k = ce.make_ints(1000)
     assert k.min() == -128 and not (k == 0).any() and np.abs(k).max() == ce.K_MAX
     for fmt in ce.FORMATS:
         x = ce.encode(k, fmt)
-        assert x.dtype == ce.NUMPY[fmt] and x.dtype == ddc._NUMPY[fmt] and ddc._format_of(x) == fmt
+        assert x.dtype == ce.NUMPY[fmt] and x.dtype == _formats.get(fmt).plain and ddc._format_of(x) == fmt
         w = _wide(k, fmt)
         assert np.array_equal(w.real, k[:, 0] * ce.UNIT[fmt]) and np.array_equal(w.imag, k[:, 1] * ce.UNIT[fmt]), fmt
     assert ce.encode(k, "sc16").min() == -32768 and ce.encode(k, "cu8").min() == 0 and ce.encode(k, "ci8").min() == -128

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from amcpy_amd import _lib, ddc
-from tests import ddc_ref
+from tests import ddc_ref, stream_inputs
 
 REPO = Path(__file__).resolve().parents[1]
 NEW = ["amcx_tune_decimate", "amcx_tune_decimate_out_samples", "amcx_tune_decimate_plan", "amcx_kernel_name_ddc"]
@@ -137,11 +137,7 @@ def test_design_lowpass():
             ddc.design_lowpass(**kw)
 
 
-def _stream(fmt, S, rng):
-    if fmt == "cf32":
-        return (rng.standard_normal(S) + 1j * rng.standard_normal(S)).astype(np.complex64)
-    info = np.iinfo(ddc._NUMPY[fmt])
-    return rng.integers(info.min, info.max + 1, (S, 2)).astype(ddc._NUMPY[fmt])
+_stream = stream_inputs.stream
 
 
 @pytest.mark.parametrize("fmt", ddc.FORMATS)

@@ -4,14 +4,13 @@ THE REFERENCE is tests/bank_ref.py: channel c is the float64 down-converter of t
 THE CRITERION is |y - y64| <= (P + 8 + 7 log2 C) 2^-24 S for EVERY output of every channel (derived there); each test prints
 the worst ratio it saw.  Taps come from +-[0.5, 1] so that every tap counts, phase_step is an odd 64-bit constant,
 sample_index0 is no multiple of any C.  Everything that the contract calls bit-identical is compared as bytes."""
-import functools
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from amcpy_amd import _lib, bank, ddc
-from tests import bank_ref, ddc_ref
+from amcpy_amd import _formats, _lib, bank, ddc
+from tests import bank_ref, ddc_ref, stream_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -24,39 +23,8 @@ ALL_FORMATS_AT = [(8, 19, 5), (64, 200, 32), (256, 513, 256), (32, 100, 32), (12
 POOL = 40_000                               # samples: the longest stream of these tests and some
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU"
-    return torch
-
-
-@functools.lru_cache(maxsize=None)
-def _host(fmt, n=POOL, seed=0):
-    """n samples of a format, read-only: complex64 (n,) or integers (n, 2) over their whole range"""
-    rng = np.random.default_rng(47 + seed + 7 * FORMATS.index(fmt))
-    if fmt == "cf32":
-        x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
-    else:
-        info = np.iinfo(ddc._NUMPY[fmt])
-        x = rng.integers(info.min, info.max + 1, (n, 2)).astype(ddc._NUMPY[fmt])
-    x.setflags(write=False)
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def _dev(fmt, n=POOL, seed=0):
-    """the same samples in GPU memory, uploaded once"""
-    return _torch().from_numpy(np.array(_host(fmt, n, seed))).cuda()
-
-
-@functools.lru_cache(maxsize=None)
-def _wide(fmt, n=POOL, seed=0):
-    return ddc_ref.widen(_host(fmt, n, seed), fmt, ddc._DEFAULT_SCALE[fmt])
-
-
-@functools.lru_cache(maxsize=None)
-def _taps_dev(T, seed=0):
-    return _torch().from_numpy(ddc_ref.make_taps(T, seed)).cuda()
+_torch, _taps_dev = stream_inputs.torch, stream_inputs.taps_dev
+_host, _dev, _wide = stream_inputs.bind(47, POOL)
 
 
 def _run(x, T, Cn, D, **kw):
@@ -219,7 +187,7 @@ def test_a_wider_stride_leaves_the_gaps_untouched(Cn, T, D):
     stream = torch.cuda.current_stream().cuda_stream
 
     def call(cap, st=stride):
-        return lib.amcx_filter_bank(x.data_ptr(), ddc._KINDS[fmt], S, ddc._DEFAULT_SCALE[fmt], _phase0(), ddc_ref.ODD_STEP, INDEX0,
+        return lib.amcx_filter_bank(x.data_ptr(), _formats.get(fmt).kind, S, _formats.get(fmt).scale, _phase0(), ddc_ref.ODD_STEP, INDEX0,
                                     _taps_dev(T).data_ptr(), T, Cn, D, buf.data_ptr() + 8 * G, st, cap, stream)
     need = (Cn - 1) * stride + M
     assert call(need - 1) == _lib.EINVAL and call(need, M - 1) == _lib.EINVAL

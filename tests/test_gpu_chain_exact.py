@@ -14,16 +14,13 @@ import functools
 import numpy as np
 import pytest
 
-from amcpy_amd import _lib, bank, ddc, resample as rs
-from tests import bank_ref, chain_exact as ce
+from amcpy_amd import _formats, _lib, bank, ddc, resample as rs
+from tests import bank_ref, chain_exact as ce, stream_inputs
 
 pytestmark = pytest.mark.gpu
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU"
-    return torch
+_torch = stream_inputs.torch
 
 
 @functools.lru_cache(maxsize=4)
@@ -57,8 +54,8 @@ def _assert_exact(y, exact, g, what):
 
 def test_the_default_scales_are_powers_of_two():
     for fmt in ce.FORMATS:
-        assert np.frexp(ddc._DEFAULT_SCALE[fmt])[0] == 0.5
-        assert ce.UNIT[fmt] == ddc._DEFAULT_SCALE[fmt] * (256 if fmt == "sc16" else 1)
+        assert np.frexp(_formats.get(fmt).scale)[0] == 0.5
+        assert ce.UNIT[fmt] == _formats.get(fmt).scale * (256 if fmt == "sc16" else 1)
 
 
 @pytest.mark.parametrize("T,D", ce.DDC_CASES)

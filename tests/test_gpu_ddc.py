@@ -4,7 +4,6 @@ THE REFERENCE is tests/ddc_ref.py: the phase in Python integers, the mixer and t
 S = sum_k |h[k]| |x[.]|.  THE CRITERION is |y - y64| <= (T + 8) 2^-24 S for EVERY output (derived there); each test prints the
 worst ratio it saw.  Taps come from +-[0.5, 1] so that every tap counts, phase_step is an odd 64-bit constant.  Everything
 that the contract calls bit-identical is compared as bytes."""
-import functools
 import json
 from fractions import Fraction
 from pathlib import Path
@@ -12,8 +11,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from amcpy_amd import _lib, ddc
-from tests import ddc_ref
+from amcpy_amd import _formats, _lib, ddc
+from tests import ddc_ref, stream_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -24,39 +23,8 @@ STEP = Fraction(ddc_ref.ODD_STEP, 1 << 64)
 POOL = 257 * 4096 + 2048 + 4096          # samples: the longest parity stream and some
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU"
-    return torch
-
-
-@functools.lru_cache(maxsize=None)
-def _host(fmt, n=POOL, seed=0):
-    """n samples of a format, read-only: complex64 (n,) or integers (n, 2) over their whole range"""
-    rng = np.random.default_rng(31 + seed + 7 * FORMATS.index(fmt))
-    if fmt == "cf32":
-        x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
-    else:
-        info = np.iinfo(ddc._NUMPY[fmt])
-        x = rng.integers(info.min, info.max + 1, (n, 2)).astype(ddc._NUMPY[fmt])
-    x.setflags(write=False)
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def _dev(fmt, n=POOL, seed=0):
-    """the same samples in GPU memory, uploaded once"""
-    return _torch().from_numpy(np.array(_host(fmt, n, seed))).cuda()
-
-
-@functools.lru_cache(maxsize=None)
-def _wide(fmt, n=POOL, seed=0):
-    return ddc_ref.widen(_host(fmt, n, seed), fmt, ddc._DEFAULT_SCALE[fmt])
-
-
-@functools.lru_cache(maxsize=None)
-def _taps_dev(T, seed=0):
-    return _torch().from_numpy(ddc_ref.make_taps(T, seed)).cuda()
+_torch, _taps_dev = stream_inputs.torch, stream_inputs.taps_dev
+_host, _dev, _wide = stream_inputs.bind(31, POOL)
 
 
 def _run(x, T, D, **kw):
@@ -116,7 +84,7 @@ def test_zero_phase_one_tap_is_the_widened_input(fmt):
         want = x
     else:
         x[:4] = np.array([[0, 0], [np.iinfo(x.dtype).min, np.iinfo(x.dtype).max], [0, 1], [1, 0]], dtype=np.int64).astype(x.dtype)
-        want = ddc_ref.widen(x, fmt, ddc._DEFAULT_SCALE[fmt]).astype(np.complex64)
+        want = ddc_ref.widen(x, fmt, _formats.get(fmt).scale).astype(np.complex64)
     for off in (0, 1):                                       # 16-byte aligned and not (for 8-bit samples: 2 mod 16)
         y = ddc.tune_decimate(torch.from_numpy(x).cuda()[off:], torch.ones(1, device="cuda"), 1)
         torch.cuda.synchronize()
@@ -275,7 +243,7 @@ def test_bounds(fmt):
         stream = torch.cuda.current_stream().cuda_stream
 
         def call(cap):
-            return lib.amcx_tune_decimate(x.data_ptr(), ddc._KINDS[fmt], S, ddc._DEFAULT_SCALE[fmt], 0, ddc_ref.ODD_STEP,
+            return lib.amcx_tune_decimate(x.data_ptr(), _formats.get(fmt).kind, S, _formats.get(fmt).scale, 0, ddc_ref.ODD_STEP,
                                           _taps_dev(T).data_ptr(), T, D, buf.data_ptr() + 8 * G, cap, stream)
         assert call(M - 1) == _lib.EINVAL
         torch.cuda.synchronize()

@@ -4,7 +4,6 @@ THE REFERENCE is tests/resample_ref.py: the phase in Python integers, the mixer 
 output S = sum_q |h[p + q L]| |x[.]|.  THE CRITERION is |y - y64| <= (P + 8) 2^-24 S for EVERY output, P = ceil(T / L) (derived
 there); each test prints the worst ratio it saw.  Taps come from +-[0.5, 1] so that every tap counts, phase_step is an odd
 64-bit constant.  Everything that the contract calls bit-identical is compared as bytes."""
-import functools
 import json
 from fractions import Fraction
 from pathlib import Path
@@ -12,8 +11,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from amcpy_amd import _lib, ddc, resample as rs
-from tests import resample_ref as ref
+from amcpy_amd import _formats, _lib, ddc, resample as rs
+from tests import resample_ref as ref, stream_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -25,39 +24,8 @@ STEP = Fraction(ref.ODD_STEP, 1 << 64)
 POOL = 160_000                           # samples: the longest parity stream (257 outputs at D / L = 4096 / 7) and some
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU"
-    return torch
-
-
-@functools.lru_cache(maxsize=None)
-def _host(fmt, n=POOL, seed=0):
-    """n samples of a format, read-only: complex64 (n,) or integers (n, 2) over their whole range"""
-    rng = np.random.default_rng(57 + seed + 7 * FORMATS.index(fmt))
-    if fmt == "cf32":
-        x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
-    else:
-        info = np.iinfo(ddc._NUMPY[fmt])
-        x = rng.integers(info.min, info.max + 1, (n, 2), dtype=np.int64).astype(ddc._NUMPY[fmt])
-    x.setflags(write=False)
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def _dev(fmt, n=POOL, seed=0):
-    """the same samples in GPU memory, uploaded once"""
-    return _torch().from_numpy(np.array(_host(fmt, n, seed))).cuda()
-
-
-@functools.lru_cache(maxsize=None)
-def _wide(fmt, n=POOL, seed=0):
-    return ref.widen(_host(fmt, n, seed), fmt, ddc._DEFAULT_SCALE[fmt])
-
-
-@functools.lru_cache(maxsize=None)
-def _taps_dev(T, seed=0):
-    return _torch().from_numpy(ref.make_taps(T, seed)).cuda()
+_torch, _taps_dev = stream_inputs.torch, stream_inputs.taps_dev
+_host, _dev, _wide = stream_inputs.bind(57, POOL)
 
 
 def _run(x, T, L, D, **kw):
@@ -132,9 +100,9 @@ def test_every_phase_and_tap_pair(fmt, T):
             x[j] = np.complex64(1.3125 - 0.71875j)
             value = x[j]
         else:
-            x = np.full((S, 2), 128 if fmt == "cu8" else 0, ddc._NUMPY[fmt])
+            x = np.full((S, 2), _formats.get(fmt).zero, _formats.get(fmt).plain)
             x[j] = (x[j].astype(np.int64) + np.array([3, -5])).astype(x.dtype)
-            value = ref.widen(x, fmt, ddc._DEFAULT_SCALE[fmt])[j].astype(np.complex64)
+            value = ref.widen(x, fmt, _formats.get(fmt).scale)[j].astype(np.complex64)
         y = rs.resample(torch.from_numpy(x).cuda(), torch.from_numpy(h).cuda(), L, D).cpu().numpy()
         assert y.shape == (M,)
         k = p + (top - j) * L                                  # the tap that meets sample j in output m, where there is one
@@ -209,7 +177,7 @@ def test_output_index_times_decim_beyond_32_bits():
     worst = 0.0
     for m1 in (0, (1 << 32) // D - 300, M - 600):
         drop, tau0 = divmod(m1 * D, L)
-        xw = ref.widen(host[drop:drop + P + (600 * D + tau0) // L], fmt, ddc._DEFAULT_SCALE[fmt])     # all that 600 outputs read
+        xw = ref.widen(host[drop:drop + P + (600 * D + tau0) // L], fmt, _formats.get(fmt).scale)     # all that 600 outputs read
         y64, s = ref.reference(xw, ref.make_taps(T), L, D, tau0, (drop * ref.ODD_STEP) & ref.MASK64, ref.ODD_STEP, M=600)
         worst = max(worst, ref.worst_ratio(y[m1:m1 + 600], y64, s, P))
     print(f"resample beyond 2^32: {M} outputs, m D up to {(M - 1) * D}: worst ratio {worst:.4f}")
@@ -285,7 +253,7 @@ def test_bounds(fmt):
         stream = torch.cuda.current_stream().cuda_stream
 
         def call(cap):
-            return lib.amcx_resample(x.data_ptr(), ddc._KINDS[fmt], S, ddc._DEFAULT_SCALE[fmt], 0, ref.ODD_STEP,
+            return lib.amcx_resample(x.data_ptr(), _formats.get(fmt).kind, S, _formats.get(fmt).scale, 0, ref.ODD_STEP,
                                      _taps_dev(T).data_ptr(), T, L, D, tau0, buf.data_ptr() + 8 * G, cap, stream)
         assert call(M - 1) == _lib.EINVAL
         torch.cuda.synchronize()

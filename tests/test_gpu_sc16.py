@@ -322,6 +322,6 @@ def test_misuse_is_refused():
             ctx.run_strided(planes.ctypes.data, None, _lib.SRC_SC16, 1, 8, N, (0, 1, 8), res)
         assert err.value.code == _lib.ENOTSUP
         with pytest.raises(ValueError):
-            ctx.set_sc16_scale(0.0)
+            ctx.set_scale("sc16", 0.0)
     finally:
         ctx.close()

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from amcpy_amd import _lib, bank, ddc, resample as rs
-from tests import bank_ref, ddc_ref, resample_ref as ref
+from tests import bank_ref, ddc_ref, resample_ref as ref, stream_inputs
 
 REPO = Path(__file__).resolve().parents[1]
 NEW = ["amcx_resample", "amcx_resample_out_samples", "amcx_resample_plan", "amcx_kernel_name_resample"]
@@ -189,11 +189,7 @@ def test_design_resample_lowpass():
     assert rs.design_resample_lowpass(256, 1, 4096).shape == (4096,)
 
 
-def _stream(fmt, S, rng):
-    if fmt == "cf32":
-        return (rng.standard_normal(S) + 1j * rng.standard_normal(S)).astype(np.complex64)
-    info = np.iinfo(ddc._NUMPY[fmt])
-    return rng.integers(info.min, info.max + 1, (S, 2)).astype(ddc._NUMPY[fmt])
+_stream = stream_inputs.stream
 
 
 def test_numpy_resample_is_the_reference_and_the_down_converter():
