@@ -12,7 +12,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 13         # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 14         # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -78,6 +78,11 @@ SIGNATURES = {
     "amcx_resample": (C.c_int, [_vp, _i32, _i64, C.c_float, C.c_uint64, C.c_uint64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "amcx_resample_plan": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "amcx_kernel_name_resample": (C.c_char_p, [_i32]),
+    "amcx_row_power_c64": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
+    "amcx_occupancy_workspace_bytes": (_i64, [_i32, _i64]),
+    "amcx_occupancy_detect_f32": (C.c_int, [_vp, _i32, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "amcx_gather_rows_c64": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "amcx_kernel_name_occupancy": (C.c_char_p, [_i32]),
     "amcx_ctx_set_feature_mask": (C.c_int, [_vp, C.c_uint32]),
     "amcx_features18_c64_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
     "amcx_features18_c128_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
@@ -265,6 +270,15 @@ def kernel_name_resample(src_kind: int) -> str:
     name = load().amcx_kernel_name_resample(int(src_kind))
     if name is None:
         raise ValueError(f"amcx: no resampler kernel for source kind {src_kind}")
+    return name.decode()
+
+
+def kernel_name_occupancy(which: int) -> str:
+    """amcx_kernel_name_occupancy: 0 the row-power kernel, 1 the floor's, 2 the gather's, 3 ... 5 the count, scan and scatter
+    launches (host-only)."""
+    name = load().amcx_kernel_name_occupancy(int(which))
+    if name is None:
+        raise ValueError(f"amcx: no occupancy kernel number {which}")
     return name.decode()
 
 

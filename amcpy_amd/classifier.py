@@ -357,6 +357,39 @@ def resolve_model_path(cfg, spec: str) -> Path:
     return cfg.paths.trained_ann / f"model-{spec}.pt"
 
 
+def load_model(cfg, model_spec: str) -> tuple:
+    """``--model`` -> ``(MlpModel, model id)``: :func:`resolve_model_path`, a ``.npz`` model or a ``.pt`` checkpoint."""
+    path = resolve_model_path(cfg, model_spec)
+    if not path.exists():
+        raise FileNotFoundError(f"no model at {path}")
+    model = (MlpModel.from_npz(path) if path.suffix == ".npz"
+             else MlpModel.from_checkpoint(path, default_activation=cfg.training.activation))
+    return model, model.model_id or (model_spec if path.name == f"model-{model_spec}.pt" else path.stem)
+
+
+def fit_scaler(cfg, mode: str, dev) -> tuple:
+    """The scaler of the `classify` command, which the `recording` command's ``--model`` fits the same way: the feature files
+    ``calculated-features/{mod}_features.mat`` of every modulation onto ``dev``, :func:`amcpy_amd.postprocess.select_standardize`
+    over the rows the reference's ``preprocess_data(cfg, mode)`` stacks (``training_snr`` or ``all_snr``).  Returns ``(feats
+    (n_mods, n_snr, n_frames, 18) on dev, mean, scale)``; the columns are ``cfg.features.used``."""
+    if mode not in ("training", "test"):
+        raise ValueError("mode: training or test")
+    import scipy.io
+    import torch
+    from .postprocess import select_standardize
+    sig, cols = cfg.signals, [int(c) for c in cfg.features.used]
+    host = []
+    for mod in sig.modulations_with_noise:
+        data = scipy.io.loadmat(str(cfg.paths.calculated_features / f"{mod}_features.mat"))
+        host.append(np.asarray(data[sig.mat_info[mod]], dtype=np.float32))
+    feats = torch.from_numpy(np.ascontiguousarray(np.stack(host))).to(dev)  # (n_mods, n_snr, n_frames, 18); loadmat's are Fortran-ordered
+    snr_axis = list(cfg.training.training_snr if mode == "training" else cfg.training.all_snr)
+    with torch.cuda.device(dev):
+        fit_rows = feats[:, torch.tensor(snr_axis, device=dev)].reshape(-1, feats.shape[-1])
+        _, mean, scale = select_standardize(fit_rows, cols)
+    return feats, mean, scale
+
+
 def run_classification(cfg, model_spec: str, *, mode: str = "test", from_iq: bool = False, device: Optional[int] = None,
                        verbose: bool = True):
     """The `classify` command: features from ``calculated-features/{mod}_features.mat`` (``from_iq``: extracted first,
@@ -371,29 +404,16 @@ def run_classification(cfg, model_spec: str, *, mode: str = "test", from_iq: boo
         raise _lib.AmcxError(_lib.ENODEV, lib.amcx_strerror(_lib.ENODEV).decode())
     import scipy.io
     import torch
-    from .postprocess import select_standardize
-    path = resolve_model_path(cfg, model_spec)
-    if not path.exists():
-        raise FileNotFoundError(f"no model at {path}")
-    model = (MlpModel.from_npz(path) if path.suffix == ".npz"
-             else MlpModel.from_checkpoint(path, default_activation=cfg.training.activation))
-    model_id = model.model_id or (model_spec if path.name == f"model-{model_spec}.pt" else path.stem)
+    model, model_id = load_model(cfg, model_spec)
     sig, cols = cfg.signals, [int(c) for c in cfg.features.used]
     if from_iq:
         from .feature_extraction import run_extraction
         run_extraction(cfg, device=device, verbose=verbose, feature_ids=sorted({c + 1 for c in cols}))
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
     mods = list(sig.modulations_with_noise)
-    host = []
-    for mod in mods:
-        data = scipy.io.loadmat(str(cfg.paths.calculated_features / f"{mod}_features.mat"))
-        host.append(np.asarray(data[sig.mat_info[mod]], dtype=np.float32))
-    feats = torch.from_numpy(np.ascontiguousarray(np.stack(host))).to(dev)  # (n_mods, n_snr, n_frames, 18); loadmat's are Fortran-ordered
+    feats, mean, scale = fit_scaler(cfg, mode, dev)
     n_mods, n_snr, n_frames, n_cols = feats.shape
-    snr_axis = list(cfg.training.training_snr if mode == "training" else cfg.training.all_snr)
     with torch.cuda.device(dev):
-        fit_rows = feats[:, torch.tensor(snr_axis, device=dev)].reshape(-1, n_cols)
-        _, mean, scale = select_standardize(fit_rows, cols)
         labels, counts = classify(feats, model, cols=cols, mean=mean, scale=scale, want=("labels", "counts"))
         labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
     acc = np.zeros((n_mods, n_snr), dtype=np.float64)

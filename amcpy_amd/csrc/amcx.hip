@@ -13,7 +13,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_resample_kernel.h"  // FIRST (it includes the down-converter's header in front of its own kernels), the bank's next, ...
+#include "amcx_occupancy_kernels.h"  // FIRST of all (ABI 14: plain kernels that call nothing of the others), ...
+#include "amcx_resample_kernel.h"  // ... then the resampler's (it includes the down-converter's header in front of its own kernels), the bank's next, ...
 #include "amcx_bank_kernel.h"
 #include "amcx_ddc_kernel.h"       // ... then the 8-bit widening kernels, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
 #include "amcx_iq8_kernels.h"
@@ -1084,6 +1085,115 @@ int amcx_resample(const void* src_dev, int32_t src_kind, int64_t n_samples, floa
 }
 
 const char* amcx_kernel_name_resample(int32_t src_kind) { return rs_kernel({src_kind}).name; }
+
+// ---- occupancy detection (amcx_occupancy_kernels.h) ----------------------------------------------------------------------
+namespace {
+bool occ_grid_ok(int32_t channels, int64_t n_frames) {
+  return channels >= 2 && channels <= amcx::kOccMaxChannels && n_frames >= 0 && n_frames < (int64_t(1) << 31) &&
+         (int64_t)channels * n_frames < (int64_t(1) << 31);
+}
+int64_t occ_blocks(int64_t n_cells) { return (n_cells + amcx::kOccBlockRows - 1) / amcx::kOccBlockRows; }
+}  // namespace
+
+int amcx_row_power_c64(const void* rows_dev, int64_t n_rows, int32_t row_samples, int64_t row_stride_samples, float* power_dev,
+                       void* hip_stream) {
+  if (n_rows < 0 || row_samples < 2 || row_samples > AMCX_MAX_FRAME_SIZE) return AMCX_EINVAL;
+  if (row_stride_samples < row_samples || (n_rows > 0 && row_stride_samples > (int64_t(1) << 58) / n_rows)) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (rows_dev == nullptr || power_dev == nullptr) return AMCX_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(rows_dev) & 7u) || (reinterpret_cast<uintptr_t>(power_dev) & 3u)) return AMCX_EINVAL;
+  if (on_another_device(rows_dev) || on_another_device(power_dev)) return AMCX_EINVAL;
+  const int64_t grid = amcx::persistent_grid(cu_count(), 8, n_rows, amcx::kOccWaves);
+  const hipError_t e = amcx::launch(amcx::amcx_row_power_kernel, grid, amcx::kOccThreads, 0, static_cast<hipStream_t>(hip_stream),
+                                    static_cast<const float2*>(rows_dev), (long long)n_rows, row_samples,
+                                    (long long)row_stride_samples, power_dev);
+  if (e != hipSuccess) return hip_fail(e, "row-power kernel launch");
+  return AMCX_OK;
+}
+
+int64_t amcx_occupancy_workspace_bytes(int32_t channels, int64_t n_frames) {
+  if (!occ_grid_ok(channels, n_frames)) return -1;
+  return (occ_blocks((int64_t)channels * n_frames) * (int64_t)sizeof(int32_t) + 255) / 256 * 256;
+}
+
+int amcx_occupancy_detect_f32(const float* power_dev, int32_t channels, int64_t n_frames, int32_t floor_rank, float threshold,
+                              float* floor_dev, uint8_t* mask_dev, int32_t* rows_dev, int32_t* count_dev, void* workspace_dev,
+                              int64_t workspace_bytes, void* hip_stream) {
+  if (!occ_grid_ok(channels, n_frames) || floor_rank < 0 || floor_rank >= channels) return AMCX_EINVAL;
+  if (!(threshold > 0.0f && threshold <= 3.4028235e38f)) return AMCX_EINVAL;          // not NaN, inf, <= 0
+  const bool counted = rows_dev != nullptr || count_dev != nullptr;
+  if (counted && workspace_bytes < amcx_occupancy_workspace_bytes(channels, n_frames)) return AMCX_EINVAL;
+  if (n_frames == 0) return AMCX_OK;
+  if (power_dev == nullptr || floor_dev == nullptr || (rows_dev != nullptr && count_dev == nullptr) ||
+      (counted && workspace_dev == nullptr))
+    return AMCX_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(power_dev) & 3u) || (reinterpret_cast<uintptr_t>(floor_dev) & 3u) ||
+      (reinterpret_cast<uintptr_t>(rows_dev) & 3u) || (reinterpret_cast<uintptr_t>(count_dev) & 3u) ||
+      (reinterpret_cast<uintptr_t>(workspace_dev) & 3u))
+    return AMCX_EINVAL;
+  if (on_another_device(power_dev) || on_another_device(floor_dev) || (mask_dev && on_another_device(mask_dev)) ||
+      (rows_dev && on_another_device(rows_dev)) || (count_dev && on_another_device(count_dev)) ||
+      (counted && on_another_device(workspace_dev)))
+    return AMCX_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const int cus = cu_count();
+  const int64_t n_cells = (int64_t)channels * n_frames, n_blocks = occ_blocks(n_cells);
+  const int64_t n_tiles = (n_frames + amcx::kOccTileFrames - 1) / amcx::kOccTileFrames;
+  const size_t lds = amcx::occ_detect_lds_bytes(channels);         // 67 584 bytes at C = 256: the attribute, once
+  hipError_t e = amcx::lds_attr_once<amcx::amcx_occupancy_detect_kernel>((int)amcx::occ_detect_lds_bytes(amcx::kOccMaxChannels));
+  if (e != hipSuccess) return hip_fail(e, "occupancy floor kernel attribute");
+  e = amcx::launch(amcx::amcx_occupancy_detect_kernel, amcx::persistent_grid(cus, wgs_per_cu(lds, 4), n_tiles, 1), amcx::kOccThreads,
+                   lds, st, power_dev, channels, (long long)n_frames, floor_rank, floor_dev, (long long)n_tiles);
+  if (e != hipSuccess) return hip_fail(e, "occupancy floor kernel launch");
+  if (!counted && mask_dev == nullptr) return AMCX_OK;
+  const int64_t grid = amcx::persistent_grid(cus, 4, n_blocks, 1);
+  int* const counts = counted ? static_cast<int*>(workspace_dev) : nullptr;
+  e = amcx::launch(amcx::amcx_occupancy_count_kernel, grid, amcx::kOccThreads, 0, st, power_dev, floor_dev, (unsigned)n_frames,
+                   (long long)n_cells, threshold, mask_dev, counts, (long long)n_blocks);
+  if (e != hipSuccess) return hip_fail(e, "occupancy count kernel launch");
+  if (!counted) return AMCX_OK;
+  e = amcx::launch(amcx::amcx_occupancy_scan_kernel, 1, amcx::kOccThreads, 0, st, counts, (long long)n_blocks, count_dev);
+  if (e != hipSuccess) return hip_fail(e, "occupancy scan kernel launch");
+  if (rows_dev == nullptr) return AMCX_OK;
+  e = amcx::launch(amcx::amcx_occupancy_scatter_kernel, grid, amcx::kOccThreads, 0, st, power_dev, floor_dev, (unsigned)n_frames,
+                   (long long)n_cells, threshold, counts, rows_dev, (long long)n_blocks);
+  if (e != hipSuccess) return hip_fail(e, "occupancy scatter kernel launch");
+  return AMCX_OK;
+}
+
+int amcx_gather_rows_c64(const void* src_dev, int64_t n_src_rows, int32_t row_samples, int64_t row_stride_samples,
+                         const int32_t* index_dev, int64_t n_index, void* dst_dev, int64_t dst_stride_samples, void* hip_stream) {
+  if (n_src_rows < 0 || n_index < 0 || row_samples < 2 || row_samples > AMCX_MAX_FRAME_SIZE) return AMCX_EINVAL;
+  if (row_stride_samples < row_samples || dst_stride_samples < row_samples ||
+      (n_src_rows > 0 && row_stride_samples > (int64_t(1) << 58) / n_src_rows) ||
+      (n_index > 0 && dst_stride_samples > (int64_t(1) << 58) / n_index))
+    return AMCX_EINVAL;
+  if (n_index == 0) return AMCX_OK;
+  if ((src_dev == nullptr && n_src_rows > 0) || index_dev == nullptr || dst_dev == nullptr) return AMCX_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(src_dev) & 7u) || (reinterpret_cast<uintptr_t>(index_dev) & 3u) ||
+      (reinterpret_cast<uintptr_t>(dst_dev) & 7u))
+    return AMCX_EINVAL;
+  if ((src_dev && on_another_device(src_dev)) || on_another_device(index_dev) || on_another_device(dst_dev)) return AMCX_EINVAL;
+  const int64_t grid = amcx::persistent_grid(cu_count(), 8, n_index, amcx::kOccWaves);
+  const hipError_t e = amcx::launch(amcx::amcx_gather_rows_kernel, grid, amcx::kOccThreads, 0, static_cast<hipStream_t>(hip_stream),
+                                    static_cast<const float2*>(src_dev), (long long)n_src_rows, row_samples,
+                                    (long long)row_stride_samples, index_dev, (long long)n_index, static_cast<float2*>(dst_dev),
+                                    (long long)dst_stride_samples);
+  if (e != hipSuccess) return hip_fail(e, "row-gather kernel launch");
+  return AMCX_OK;
+}
+
+const char* amcx_kernel_name_occupancy(int32_t which) {
+  switch (which) {
+    case 0: return "amcx_row_power_kernel";
+    case 1: return "amcx_occupancy_detect_kernel";
+    case 2: return "amcx_gather_rows_kernel";
+    case 3: return "amcx_occupancy_count_kernel";
+    case 4: return "amcx_occupancy_scan_kernel";
+    case 5: return "amcx_occupancy_scatter_kernel";
+    default: return nullptr;
+  }
+}
 
 int64_t amcx_group_stats_workspace_bytes(int64_t n_groups, int64_t rows_per_group, int32_t n_cols) {
   if (!stats_args_ok(n_groups, rows_per_group, n_cols, n_cols)) return -1;

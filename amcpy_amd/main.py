@@ -25,6 +25,7 @@ the GPU of its LOCAL_RANK, joins the process group and computes its share; rank 
 from __future__ import annotations
 
 import argparse
+import json
 import os
 import time
 import sys
@@ -98,7 +99,76 @@ def build_parser() -> argparse.ArgumentParser:
                           "--shift-hz then offsets the raster")
     rec.add_argument("--taps-per-channel", type=int, default=None, metavar="P",
                      help="with --channels: the prototype low-pass has C P taps (default 16)")
+    rec.add_argument("--detect", action="store_true",
+                     help="with --channels: occupancy detection -- the power of every (channel, frame) cell against the frame's "
+                          "noise floor; only occupied cells get features (NaN elsewhere) and, with --model, labels")
+    rec.add_argument("--threshold-db", type=float, default=None, metavar="X",
+                     help="with --detect: a cell is occupied where its power is more than X dB over the floor (default 6)")
+    rec.add_argument("--floor-quantile", type=float, default=None, metavar="Q",
+                     help="with --detect: the floor of a frame is the channel power of rank int(Q (C - 1)) (default 0.25)")
+    rec.add_argument("--model", default=None, metavar="ID|PATH",
+                     help="with --channels: classify the cells (the occupied ones with --detect); as for classify; needs --root")
+    rec.add_argument("--root", type=Path, default=None,
+                     help="with --model: the project root whose calculated-features/ files the scaler is fitted on")
+    rec.add_argument("--mode", choices=("training", "test"), default=None, help="with --model: as for classify (default test)")
+    rec.add_argument("--annotate", type=Path, default=None, metavar="OUT.sigmf-meta",
+                     help="with --channels and --detect: a copy of the meta file with one annotation per occupied segment")
     return ap
+
+
+def recording_survey(args):
+    """The `recording` command's occupancy and classification flags -> ``None`` (none given: the features of every cell, as
+    before) or ``{"detect": dict | None, "model": spec | None, "root": ..., "mode": ..., "annotate": path | None}``.  Every one
+    of them needs --channels, and each the flag it belongs to."""
+    given = [name for name, on in (("--detect", args.detect), ("--threshold-db", args.threshold_db is not None),
+                                   ("--floor-quantile", args.floor_quantile is not None), ("--model", args.model is not None),
+                                   ("--root", args.root is not None), ("--mode", args.mode is not None),
+                                   ("--annotate", args.annotate is not None)) if on]
+    if not given:
+        return None
+    if args.channels is None:
+        raise SystemExit(f"{given[0]} needs --channels")
+    for name in ("--threshold-db", "--floor-quantile", "--annotate"):
+        if name in given and not args.detect:
+            raise SystemExit(f"{name} needs --detect")
+    for name in ("--root", "--mode"):
+        if name in given and args.model is None:
+            raise SystemExit(f"{name} needs --model")
+    if args.model is not None and args.root is None:
+        raise SystemExit("--model needs --root (the scaler is fitted on its calculated-features/ files)")
+    detect = None
+    if args.detect:
+        detect = {"threshold_db": 6.0 if args.threshold_db is None else args.threshold_db,
+                  "floor_quantile": 0.25 if args.floor_quantile is None else args.floor_quantile}
+    return {"detect": detect, "model": args.model, "root": args.root, "mode": args.mode or "test", "annotate": args.annotate}
+
+
+def annotate_segments(meta: dict, segments, frame_start, frame_size: int, decim: int, channel_freq_hz, labels=None,
+                      class_names=None) -> dict:
+    """A copy of the parsed meta file with one annotation per ``(channel, first_frame, last_frame)`` segment appended:
+    ``core:sample_start`` / ``core:sample_count`` in input samples (a frame covers ``frame_size * decim`` of them),
+    ``core:freq_lower_edge`` / ``core:freq_upper_edge`` = the channel's centre -/+ half the channel spacing, and -- with
+    ``labels`` (C, K) and ``class_names`` -- ``core:label``, the name of the majority label (>= 0) of the segment's cells."""
+    import copy
+    import numpy as np
+    rate = (meta.get("global") or {}).get("core:sample_rate")
+    if not rate:
+        raise SystemExit("--annotate needs the global core:sample_rate (the channels' frequency edges)")
+    half = float(rate) / len(channel_freq_hz) / 2.0
+    out = copy.deepcopy(meta)
+    anns = list(out.get("annotations") or [])
+    for c, k0, k1 in segments:
+        ann = {"core:sample_start": int(frame_start[k0]),
+               "core:sample_count": int(frame_start[k1] - frame_start[k0]) + int(frame_size) * int(decim),
+               "core:freq_lower_edge": float(channel_freq_hz[c]) - half, "core:freq_upper_edge": float(channel_freq_hz[c]) + half}
+        if labels is not None and class_names is not None:
+            seen = np.asarray(labels)[c, k0:k1 + 1]
+            seen = seen[seen >= 0]
+            if seen.size:
+                ann["core:label"] = str(class_names[int(np.bincount(seen).argmax())])
+        anns.append(ann)
+    out["annotations"] = sorted(anns, key=lambda a: int(a.get("core:sample_start", 0)))
+    return out
 
 
 def recording_tune(args):
@@ -150,10 +220,27 @@ def recording_channelize(args):
             "shift_hz": 0.0 if args.shift_hz is None else args.shift_hz}
 
 
-def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> Path:
+def _survey_model(survey, device):
+    """--model / --root / --mode -> (model, cols, mean, scale, class names by label): the scaler fitted as `classify` fits it."""
+    import torch
+    from .classifier import fit_scaler, load_model
+    cfg = Config(paths=Paths(root=survey["root"]))
+    model, _ = load_model(cfg, survey["model"])
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    _, mean, scale = fit_scaler(cfg, survey["mode"], dev)
+    names = [None] * (max(cfg.signals.labels) + 1)
+    for mod, lab in zip(cfg.signals.modulations_with_noise, cfg.signals.labels):
+        names[int(lab)] = mod
+    return model, [int(c) for c in cfg.features.used], mean, scale, names
+
+
+def run_recording(args, compute=None, tune_compute=None, bank_compute=None, occupancy_compute=None, model=None,
+                  class_names=None) -> Path:
     """The `recording` command: features and frame_start of args.file -> args.out (written aside, then renamed).  With
     --channels: features (C, K, 18), and channel_freq_hz (C,) where the meta file gives a sample rate (offset by the first
-    capture's core:frequency where it has one)."""
+    capture's core:frequency where it has one).  With --detect / --model (:func:`recording_survey`) the file additionally holds
+    power, floor and, as given, occupied, snr_db, labels and class_names (sigmf.survey_sigmf); --annotate writes the segments
+    into a copy of the meta file.  ``occupancy_compute``, ``model`` (a callable) and ``class_names``: injected (tests)."""
     import numpy as np
     from scipy.io import savemat
     from . import _formats, sigmf
@@ -162,6 +249,7 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> P
     path = Path(args.file)
     tune = recording_tune(args)
     channelize = recording_channelize(args)
+    survey = recording_survey(args)
     extra = {}
     if sigmf.is_sigmf(path):
         if args.format is not None:
@@ -169,9 +257,22 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> P
         if sigmf.is_rational_tune(tune):                      # resolved once: L and D go into the output file
             tune = sigmf.resolve_resample(sigmf.read_meta(path)["meta"], tune)
             extra["interp"], extra["decim"] = np.int64(tune[1]), np.int64(tune[2])
-        feats, frame_start = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
-                                                 compute=compute, tune=tune, tune_compute=tune_compute, channelize=channelize,
-                                                 bank_compute=bank_compute)
+        got = None
+        if survey is not None:
+            kw = {}
+            if survey["model"] is not None:
+                if model is None:
+                    model, kw["cols"], kw["mean"], kw["scale"], class_names = _survey_model(survey, args.device)
+                extra["class_names"] = np.array([str(n) for n in class_names], dtype=object)
+            got = sigmf.survey_sigmf(path, args.frame_size, channelize=channelize, detect=survey["detect"], model=model,
+                                     device=args.device, feature_ids=ids, scale_samples=args.scale, bank_compute=bank_compute,
+                                     occupancy_compute=occupancy_compute, compute=compute, **kw)
+            feats, frame_start = got["features"], got["frame_start"]
+            extra.update({k: got[k] for k in ("power", "floor", "occupied", "snr_db", "labels") if k in got})
+        else:
+            feats, frame_start = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
+                                                     compute=compute, tune=tune, tune_compute=tune_compute, channelize=channelize,
+                                                     bank_compute=bank_compute)
         stem = Path(sigmf._stem(path))
         if channelize is not None:
             from fractions import Fraction
@@ -182,8 +283,13 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None) -> P
                 center = float((meta.get("captures") or [{}])[0].get("core:frequency", 0.0))
                 shift = Fraction(channelize["shift_hz"]) / Fraction(float(rate))
                 extra["channel_freq_hz"] = channel_frequencies(channelize["channels"], float(rate), center, shift)
+        if survey is not None and survey["annotate"] is not None:
+            decim = channelize["channels"] // channelize["oversample"]
+            noted = annotate_segments(sigmf.read_meta(path)["meta"], got["segments"], frame_start, args.frame_size, decim,
+                                      extra.get("channel_freq_hz"), got.get("labels"), class_names)
+            Path(survey["annotate"]).write_text(json.dumps(noted, indent=1))
     else:
-        if tune is not None or channelize is not None:
+        if tune is not None or channelize is not None or survey is not None:
             raise SystemExit("the tuning flags need a SigMF recording (its meta file holds the sample rate)")
         if args.format is None:
             raise SystemExit(f"{path} is no SigMF recording: --format cf32|sc16|ci8|cu8 says what its samples are")
@@ -318,6 +424,7 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
     args = build_parser().parse_args(argv)
     if args.command == "recording":           # one file in, one file out: no project root, no torch (unless it tunes)
         from . import _lib
+        recording_survey(args)                 # (its refusals, before anything is loaded)
         if skip_torch and recording_tune(args) is None and recording_channelize(args) is None:
             _lib.load(skip_torch=True)
         run_recording(args)

@@ -281,8 +281,11 @@ def resolve_channelize(meta: dict, channelize: dict) -> tuple:
     return shift, C, C // int(over), np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
 
 
-def _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, compute, bank_compute, chunk_samples):
-    """The filter-bank path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.bank.FilterBank` in chunks."""
+def _walk_channelized(rec, N, channelize, device, scale, left, bank_compute, chunk_samples):
+    """The segment and chunk walk of the filter-bank paths (:func:`extract_sigmf` with ``channelize``, :func:`survey_sigmf`):
+    every segment through a :class:`amcpy_amd.bank.FilterBank` in chunks, its channels cut into frames.  Yields
+    ``(segment start, n, frames)`` per segment that has frames: ``frames`` is the contiguous complex64 ``(C * n, N)`` matrix, row
+    ``c * n + k`` channel c's frame k -- a torch tensor on the device, or, with an injected ``bank_compute``, a numpy array."""
     from .bank import FilterBank
     shift, C, D, taps = resolve_channelize(rec["meta"], channelize)
     fmt = rec["sample_format"]
@@ -290,9 +293,7 @@ def _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, c
     on_gpu = bank_compute is None
     if on_gpu:
         import torch                                       # this path alone: the untuned one stays torch-free
-        from .features import features18
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
-    parts, starts = [], []
     for start, off, n_samples in rec["segments"]:
         if left is not None and left <= 0:
             break
@@ -315,17 +316,144 @@ def _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, c
             left -= n
         if on_gpu:
             frames = torch.cat(ys, dim=1)[:, :n * N].contiguous().view(C * n, N)          # row c * n + k: channel c, frame k
+        else:
+            frames = np.ascontiguousarray(np.concatenate(ys, axis=1)[:, :n * N]).reshape(C * n, N)
+        yield start, n, frames
+
+
+def _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, compute, bank_compute, chunk_samples):
+    """The filter-bank path of :func:`extract_sigmf`: the 18 features of every cell :func:`_walk_channelized` yields."""
+    _, C, D, _ = resolve_channelize(rec["meta"], channelize)
+    parts, starts = [], []
+    for start, n, frames in _walk_channelized(rec, N, channelize, device, scale, left, bank_compute, chunk_samples):
+        if bank_compute is None:
             if compute is None:
+                from .features import features18
                 got = features18(frames, feature_ids=feature_ids).cpu().numpy()
             else:
                 got = np.asarray(compute(frames.cpu().numpy()), dtype=np.float32)
         else:
-            got = np.asarray(compute(np.ascontiguousarray(np.concatenate(ys, axis=1)[:, :n * N]).reshape(C * n, N)), dtype=np.float32)
+            got = np.asarray(compute(frames), dtype=np.float32)
         parts.append(got.reshape(C, n, 18))
         starts.append(start + N * D * np.arange(n, dtype=np.int64))
     if not parts:
         return np.empty((C, 0, 18), dtype=np.float32), np.empty((0,), dtype=np.int64)
     return np.concatenate(parts, axis=1), np.concatenate(starts)
+
+
+def _survey_segment_gpu(frames, C, n, rank_q, thr_db, detect, model, cols, mean, scale_, feature_ids):
+    """One segment of :func:`survey_sigmf` on the device -> (features, power, floor, mask, snr_db, labels) as numpy."""
+    import torch
+    from . import occupancy
+    from .features import features18
+    power = occupancy.row_power(frames).view(C, n)
+    occ = occupancy.detect(power, floor_quantile=rank_q, threshold_db=thr_db)
+    labels = None
+    if detect is None:
+        feats = features18(frames, feature_ids=feature_ids).reshape(C * n, 18)
+        if model is not None:
+            from .classifier import classify
+            labels = classify(feats, model, cols=cols, mean=mean, scale=scale_).reshape(C, n)
+    else:
+        feats = torch.full((C * n, 18), float("nan"), dtype=torch.float32, device=frames.device)
+        if model is not None:
+            labels = torch.full((C * n,), -2, dtype=torch.int32, device=frames.device)
+        if int(occ.rows.shape[0]) > 0:
+            at = occ.rows.long()
+            packed = features18(occupancy.gather_rows(frames, occ.rows), feature_ids=feature_ids).reshape(-1, 18)
+            feats[at] = packed
+            if model is not None:
+                from .classifier import classify
+                labels[at] = classify(packed, model, cols=cols, mean=mean, scale=scale_).reshape(-1)
+        if labels is not None:
+            labels = labels.view(C, n)
+    host = lambda t: None if t is None else t.cpu().numpy()      # noqa: E731
+    return (host(feats.view(C, n, 18)), host(power), host(occ.floor), host(occ.mask), host(occ.snr_db), host(labels))
+
+
+def _survey_segment_injected(frames, C, n, rank, thr, detect, model, compute, occupancy_compute):
+    """The same over numpy with injected computes (tests)."""
+    power, floor, mask = occupancy_compute(frames, C, n, rank, thr)
+    power, floor, mask = np.asarray(power, np.float32).reshape(C, n), np.asarray(floor, np.float32), np.asarray(mask, bool).reshape(C, n)
+    with np.errstate(all="ignore"):
+        snr_db = (10.0 * np.log10(np.maximum(power / floor[None, :] - np.float32(1.0), np.finfo(np.float32).tiny))).astype(np.float32)
+    rows = np.flatnonzero(mask.reshape(-1)) if detect is not None else np.arange(C * n)
+    feats = np.full((C * n, 18), np.nan, dtype=np.float32)
+    labels = None if model is None else np.full((C * n,), -2, dtype=np.int32)
+    if rows.size:
+        got = np.asarray(compute(np.ascontiguousarray(frames[rows])), dtype=np.float32).reshape(-1, 18)
+        feats[rows] = got
+        if model is not None:
+            labels[rows] = np.asarray(model(got), dtype=np.int32).reshape(-1)
+    return feats.reshape(C, n, 18), power, floor, mask, snr_db, None if labels is None else labels.reshape(C, n)
+
+
+def survey_sigmf(path, frame_size: int, *, channelize, detect=None, model=None, cols=None, mean=None, scale=None,
+                 device: Optional[int] = None, feature_ids=None, scale_samples=None, chunk_samples: int = 1 << 24,
+                 bank_compute=None, occupancy_compute=None, compute=None) -> dict:
+    """Which channels of a wideband SigMF recording hold an emitter, when, how strong, and -- with ``model`` -- which
+    modulation.  The recording goes through the filter bank exactly as ``extract_sigmf(channelize=...)`` takes it (the same
+    segment and chunk walk, ``channelize`` as there); every cell's power and every frame's floor are computed on the device
+    (:mod:`amcpy_amd.occupancy`), and, with ``detect``, only the occupied cells go through the feature kernels and the
+    classifier.  Returns a dict:
+
+        features (C, K, 18) float32     NaN in cells that are not occupied (without ``detect``: every cell's features)
+        frame_start (K,) int64          as :func:`extract_sigmf`
+        power (C, K), floor (K,)        float32
+      with ``detect = dict(threshold_db=6.0, floor_quantile=0.25)`` (either key may be left out):
+        occupied (C, K) bool, snr_db (C, K) float32, segments [(channel, first_frame, last_frame), ...]
+      with ``model`` (an :class:`amcpy_amd.classifier.MlpModel`; ``cols``, ``mean``, ``scale`` as :func:`amcpy_amd.classifier.classify`):
+        labels (C, K) int32             the classifier's label, -1 for a row without finite probabilities, -2 for a cell that
+                                        is not occupied
+
+    ``scale_samples``: what an integer component is multiplied by (``extract_sigmf``'s ``scale``; the name ``scale`` is the
+    classifier's here).  What the detector assumes: :mod:`amcpy_amd.occupancy`.  Injected computes (tests, all numpy):
+    ``bank_compute`` as :class:`amcpy_amd.bank.FilterBank`'s; ``occupancy_compute(frames (C n, N), C, n, floor_rank,
+    threshold) -> (power, floor, mask)``; ``compute(rows) -> (rows, 18)``; ``model`` is then a callable ``(rows, 18) -> labels``.
+    The three go together."""
+    from . import occupancy
+    from .feature_extraction import _subset
+    injected = [bank_compute is not None, occupancy_compute is not None, compute is not None]
+    if any(injected) and not all(injected):
+        raise ValueError("bank_compute, occupancy_compute and compute are injected together")
+    feature_ids, compute = _subset(feature_ids, compute)
+    N = int(frame_size)
+    if N < 2:
+        raise ValueError("frame_size must be >= 2")
+    if detect is not None and (not isinstance(detect, dict) or set(detect) - {"threshold_db", "floor_quantile"}):
+        raise ValueError("detect: a dict of threshold_db and floor_quantile")
+    if model is not None and cols is None and not any(injected):
+        raise ValueError("model needs cols (and mean and scale, unless the model takes raw features)")
+    thr_db = float((detect or {}).get("threshold_db", 6.0))
+    quantile = float((detect or {}).get("floor_quantile", 0.25))
+    rec = read_meta(path)
+    _, C, D, _ = resolve_channelize(rec["meta"], channelize)
+    rank, thr = occupancy.floor_rank_of(C, quantile), occupancy.threshold_of(thr_db)
+    sample_scale = _formats.scale_of(rec["sample_format"], scale_samples)
+    parts, starts = [], []
+    for start, n, frames in _walk_channelized(rec, N, channelize, device, sample_scale, None, bank_compute,
+                                              max(1, int(chunk_samples))):
+        if any(injected):
+            parts.append(_survey_segment_injected(frames, C, n, rank, thr, detect, model, compute, occupancy_compute))
+        else:
+            parts.append(_survey_segment_gpu(frames, C, n, quantile, thr_db, detect, model, cols, mean, scale, feature_ids))
+        starts.append(start + N * D * np.arange(n, dtype=np.int64))
+    if parts:
+        feats, power, floor, mask, snr_db, labels = zip(*parts)           # frames are axis 1 of everything but the floor
+        feats, power, mask, snr_db = (np.concatenate(v, axis=1) for v in (feats, power, mask, snr_db))
+        labels = None if model is None else np.concatenate(labels, axis=1)
+        floor, frame_start = np.concatenate(floor), np.concatenate(starts)
+    else:
+        feats, power, floor = np.empty((C, 0, 18), np.float32), np.empty((C, 0), np.float32), np.empty((0,), np.float32)
+        mask, snr_db = np.zeros((C, 0), bool), np.empty((C, 0), np.float32)
+        labels = None if model is None else np.empty((C, 0), np.int32)
+        frame_start = np.empty((0,), np.int64)
+    out = {"features": feats, "frame_start": frame_start, "power": power, "floor": floor}
+    if detect is not None:
+        out.update(occupied=mask, snr_db=snr_db, segments=occupancy.segments(mask))
+    if model is not None:
+        out["labels"] = labels
+    return out
 
 
 def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, feature_ids=None, scale=None,

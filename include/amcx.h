@@ -96,10 +96,13 @@ extern "C" {
  * 10 = frames of 8-bit IQ (ci8, cu8), widened on the device: AMCX_IQ8_*, amcx_features_iq8, amcx_features_iq8_workspace_bytes,
  * amcx_kernel_name_iq8, AMCX_SRC_CI8 / AMCX_SRC_CU8 for the strided host / file entries and amcx_stage_host / _file,
  * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host;
- * 11 = the digital down-converter; 12 = the polyphase filter bank; 13 = the rational resampler (all listed behind the define). */
-#define AMCX_ABI_VERSION 13
+ * 11 = the digital down-converter; 12 = the polyphase filter bank; 13 = the rational resampler; 14 = occupancy detection
+ * (all listed behind the define). */
+#define AMCX_ABI_VERSION 14
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
- *   ABI 13: the line above               -- the rational resampler: amcx_resample, amcx_resample_out_samples,
+ *   ABI 14: the line above               -- occupancy detection: amcx_row_power_c64, amcx_occupancy_workspace_bytes,
+ *                                            amcx_occupancy_detect_f32, amcx_gather_rows_c64, amcx_kernel_name_occupancy
+ *   ABI 13: #define AMCX_ABI_VERSION 13   -- the rational resampler: amcx_resample, amcx_resample_out_samples,
  *                                            amcx_resample_plan, amcx_kernel_name_resample
  *   ABI 12: #define AMCX_ABI_VERSION 12   -- the polyphase filter bank: amcx_filter_bank, amcx_filter_bank_out_samples,
  *                                            amcx_filter_bank_plan, amcx_kernel_name_bank
@@ -404,6 +407,60 @@ int amcx_resample_plan(int32_t n_taps, int32_t interp, int32_t decim, int32_t* t
                        int32_t* max_workgroups, int32_t* lds_bytes);
 
 /*
+ * OCCUPANCY DETECTION on a (channel x frame) grid (ABI 14; amcpy_amd/csrc/amcx_occupancy_kernels.h).  A CELL is one frame of
+ * N complex64 samples of one channel: row r = c K + k of the (C K, N) matrix the filter bank's output is cut into.  All three
+ * entries are asynchronous on the caller's stream, allocate nothing and are capturable in a graph; their checks come before
+ * any device call, in the order each states.  Global memory is written with ordinary vector stores; no workgroup waits for
+ * another; no atomics.
+ *
+ * amcx_row_power_c64: power_dev[r] = sum_{n < N} re^2 + im^2 in float32, r < n_rows, N = row_samples, row r at rows_dev +
+ * r * row_stride_samples samples.
+ *   - THE ORDER depends on N alone (the kernel header states it: one accumulator per lane, s = fma(im, im, fma(re, re, s)) over
+ *     the lane's sample pairs in ascending order, then a fixed 6-level tree over the 64 lanes).
+ *   - POSITION INDEPENDENCE: a row's bits depend on its N samples alone -- not on its place in the call, the stride, whether the
+ *     row begins on 16 bytes (16-byte loads) or only on 8 (8-byte loads of the same samples), the grid or the batch.
+ *   - accuracy: every term is non-negative, so |p - exact| <= B 2^-24 exact with B = 4 ceil(N / 128) + 8 (tests/occupancy_ref.py).
+ *     NaN and Inf propagate as IEEE 754 says.  Nothing outside a row's N samples is read.
+ *   - checks: n_rows >= 0 and 2 <= row_samples <= AMCX_MAX_FRAME_SIZE; row_stride_samples >= row_samples (and n_rows times it
+ *     below 2^58); n_rows == 0 is AMCX_OK here, null pointers allowed; null pointers and alignment (rows 8, power 4); a pointer
+ *     on another device.
+ *
+ * amcx_occupancy_detect_f32: per frame k, across the C = channels values power_dev[c K + k] (K = n_frames, packed):
+ *     floor_dev[k]       = the element of rank floor_rank (0-based, ascending, NaN last) of those C values
+ *     mask_dev[c K + k]  = power_dev[c K + k] > threshold * floor_dev[k] ? 1 : 0     (ONE float32 product, one IEEE comparison:
+ *                          a NaN power, or a NaN floor, is not occupied)
+ *     rows_dev[0 .. n)   = the occupied rows r = c K + k in ASCENDING order, *count_dev = n; entries at and beyond n are not
+ *                          written.  rows_dev has room for C K entries.
+ *   Every result is exactly what numpy float32 gives (tests/occupancy_ref.py, numpy_detect).  mask_dev and rows_dev may each
+ *   be NULL (not wanted); count_dev is required with rows_dev and may be given without it.  With rows_dev or count_dev the
+ *   entry needs workspace_dev of at least amcx_occupancy_workspace_bytes bytes (block counts; it is overwritten).  Launches:
+ *   the floor; the mask and the counts of blocks of 256 rows; ONE workgroup that scans the counts; the scatter.
+ *   - limits: 2 <= channels <= 256 (any integer), n_frames >= 0, channels * n_frames < 2^31, 0 <= floor_rank < channels,
+ *     threshold a finite float32 > 0.
+ *   - checks: those limits; workspace_bytes (where rows_dev or count_dev is given); n_frames == 0 is AMCX_OK here, null
+ *     pointers allowed, nothing written; null pointers (power, floor; count with rows; the workspace) and alignment (4 bytes
+ *     each); a pointer on another device.
+ * amcx_occupancy_workspace_bytes: the bytes that call needs, monotone in both arguments; -1 for a grid the entry refuses.
+ *
+ * amcx_gather_rows_c64: dst_dev[i * dst_stride_samples + n] = src_dev[index_dev[i] * row_stride_samples + n], i < n_index,
+ * n < row_samples -- a copy, bit for bit, with 16-byte accesses where both rows begin on 16 bytes and 8-byte otherwise.  An
+ * index outside [0, n_src_rows) gives a row of NaN + NaN j, and nothing outside the source's rows is read.  The feature
+ * kernels take a constant row stride: this copy is what lets them run on the occupied cells alone.
+ *   - checks: n_src_rows >= 0, n_index >= 0, 2 <= row_samples <= AMCX_MAX_FRAME_SIZE; both strides >= row_samples; n_index == 0
+ *     is AMCX_OK here, null pointers allowed; null pointers (src only where n_src_rows > 0) and alignment (src 8, index 4,
+ *     dst 8); a pointer on another device.
+ */
+int amcx_row_power_c64(const void* rows_dev, int64_t n_rows, int32_t row_samples, int64_t row_stride_samples,
+                       float* power_dev, void* hip_stream);
+int64_t amcx_occupancy_workspace_bytes(int32_t channels, int64_t n_frames);            /* -1 for refused arguments */
+int amcx_occupancy_detect_f32(const float* power_dev, int32_t channels, int64_t n_frames, int32_t floor_rank,
+                              float threshold, float* floor_dev, uint8_t* mask_dev, int32_t* rows_dev,
+                              int32_t* count_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+int amcx_gather_rows_c64(const void* src_dev, int64_t n_src_rows, int32_t row_samples, int64_t row_stride_samples,
+                         const int32_t* index_dev, int64_t n_index, void* dst_dev, int64_t dst_stride_samples,
+                         void* hip_stream);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -495,6 +552,11 @@ int amcx_kernel_name_bank(int32_t src_kind, char* buf, int32_t buf_len);
 /* ABI 13: the kernel amcx_resample runs for this src_kind (host-only), a static string: amcx_resample_c64_kernel,
  * amcx_resample_sc16_kernel, or amcx_resample_iq8_kernel for both 8-bit kinds; NULL for any other kind. */
 const char* amcx_kernel_name_resample(int32_t src_kind);
+
+/* ABI 14: the kernels of occupancy detection (host-only), static strings: 0 amcx_row_power_kernel, 1 amcx_occupancy_detect_kernel
+ * (the floor), 2 amcx_gather_rows_kernel, and the three launches behind the floor: 3 amcx_occupancy_count_kernel,
+ * 4 amcx_occupancy_scan_kernel, 5 amcx_occupancy_scatter_kernel; NULL for any other number. */
+const char* amcx_kernel_name_occupancy(int32_t which);   /* 0 power, 1 detect, 2 gather */
 
 /* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
  * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
