@@ -12,7 +12,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 14         # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 15        # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -83,6 +83,12 @@ SIGNATURES = {
     "amcx_occupancy_detect_f32": (C.c_int, [_vp, _i32, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "amcx_gather_rows_c64": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
     "amcx_kernel_name_occupancy": (C.c_char_p, [_i32]),
+    "amcx_spectrogram_out_rows": (_i64, [_i64, _i32, _i32, _i32]),
+    "amcx_spectrogram": (C.c_int, [_vp, _i32, _i64, C.c_float, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
+    "amcx_spectrogram_plan": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "amcx_psd_detect_f32": (C.c_int, [_vp, _i64, _i32, _i64, _i32, C.c_float, _vp, _vp, _vp]),
+    "amcx_kernel_name_psd": (C.c_int, [_i32, C.c_char_p, _i32]),
+    "amcx_kernel_name_psd_detect": (C.c_char_p, []),
     "amcx_ctx_set_feature_mask": (C.c_int, [_vp, C.c_uint32]),
     "amcx_features18_c64_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
     "amcx_features18_c128_host": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32]),
@@ -280,6 +286,25 @@ def kernel_name_occupancy(which: int) -> str:
     if name is None:
         raise ValueError(f"amcx: no occupancy kernel number {which}")
     return name.decode()
+
+
+def kernel_name_psd(src_kind: int) -> str:
+    """amcx_kernel_name_psd: the kernel amcx_spectrogram runs for this source kind (host-only)."""
+    buf = C.create_string_buffer(128)
+    check(load().amcx_kernel_name_psd(int(src_kind), buf, len(buf)))
+    return buf.value.decode()
+
+
+def kernel_name_psd_detect() -> str:
+    """amcx_kernel_name_psd_detect: the kernel amcx_psd_detect_f32 runs (host-only)."""
+    return load().amcx_kernel_name_psd_detect().decode()
+
+
+def spectrogram_plan(nfft: int, hop: int, averages: int) -> tuple:
+    """amcx_spectrogram_plan -> (segments per pass, bytes of LDS, most workgroups of the persistent grid) (host-only)."""
+    segs, lds, grid = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(load().amcx_spectrogram_plan(int(nfft), int(hop), int(averages), C.byref(segs), C.byref(lds), C.byref(grid)))
+    return segs.value, lds.value, grid.value
 
 
 def resample_plan(n_taps: int, interp: int, decim: int) -> tuple:

@@ -13,7 +13,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_occupancy_kernels.h"  // FIRST of all (ABI 14: plain kernels that call nothing of the others), ...
+#include "amcx_psd_kernel.h"       // FIRST of all (ABI 15; it includes the occupancy and down-converter headers for their device helpers), ...
+#include "amcx_occupancy_kernels.h"  // ... then the occupancy kernels (ABI 14: plain kernels that call nothing of the others), ...
 #include "amcx_resample_kernel.h"  // ... then the resampler's (it includes the down-converter's header in front of its own kernels), the bank's next, ...
 #include "amcx_bank_kernel.h"
 #include "amcx_ddc_kernel.h"       // ... then the 8-bit widening kernels, then the sc16 kernels: KERNEL ORDER, amcx_launch.h
@@ -504,13 +505,18 @@ StreamKernel<decltype(&amcx::amcx_resample_c64_kernel)> rs_kernel(StreamSrc s) {
   return s.pick<StreamKernel<decltype(&amcx::amcx_resample_c64_kernel)>>(
       {AMCX_NAMED(amcx_resample_c64_kernel)}, {AMCX_NAMED(amcx_resample_sc16_kernel)}, {AMCX_NAMED(amcx_resample_iq8_kernel)});
 }
+StreamKernel<decltype(&amcx::amcx_spectrogram_c64_kernel)> psd_kernel(StreamSrc s) {
+  return s.pick<StreamKernel<decltype(&amcx::amcx_spectrogram_c64_kernel)>>(
+      {AMCX_NAMED(amcx_spectrogram_c64_kernel)}, {AMCX_NAMED(amcx_spectrogram_sc16_kernel)}, {AMCX_NAMED(amcx_spectrogram_iq8_kernel)});
+}
 #undef AMCX_NAMED
 
-// the pointers of a call that launches: all there, each aligned to its element, none on another device
-bool stream_ptrs_ok(const void* src, const float* taps, const void* out, StreamSrc s) {
+// the pointers of a call that launches: all there, each aligned to its element (out: complex64, or float32 rows with
+// out_align = 3), none on another device
+bool stream_ptrs_ok(const void* src, const float* taps, const void* out, StreamSrc s, unsigned out_align = 7u) {
   if (src == nullptr || taps == nullptr || out == nullptr) return false;
   if ((reinterpret_cast<uintptr_t>(src) & s.src_align()) || (reinterpret_cast<uintptr_t>(taps) & 3u) ||
-      (reinterpret_cast<uintptr_t>(out) & 7u))
+      (reinterpret_cast<uintptr_t>(out) & out_align))
     return false;
   return !on_another_device(src) && !on_another_device(taps) && !on_another_device(out);
 }
@@ -1194,6 +1200,78 @@ const char* amcx_kernel_name_occupancy(int32_t which) {
     default: return nullptr;
   }
 }
+
+// ---- the spectrogram and its detection (amcx_psd_kernel.h) ----------------------------------------------------------------
+namespace {
+int psd_log2(int32_t nfft) {
+  if (nfft < amcx::kPsdMinFft || nfft > amcx::kPsdMaxFft || !is_pow2(nfft)) return -1;
+  int lg = 0;
+  while ((1 << lg) < nfft) ++lg;
+  return lg;
+}
+// n_rows rows at row_stride elements: the stride holds a row, and the product stays below 2^58 (each factor bounded first)
+bool psd_rows_ok(int64_t n_rows, int64_t row_stride, int32_t row_elems) {
+  return n_rows >= 0 && row_stride >= row_elems && (n_rows == 0 || row_stride <= (int64_t(1) << 58) / n_rows);
+}
+}  // namespace
+
+int64_t amcx_spectrogram_out_rows(int64_t n_samples, int32_t nfft, int32_t hop, int32_t averages) {
+  if (psd_log2(nfft) < 0 || hop < 1 || hop > amcx::kPsdMaxHop || averages < 1 || averages > amcx::kPsdMaxAverages) return -1;
+  if (n_samples < 0 || n_samples >= (int64_t(1) << 40)) return -1;
+  if (n_samples < nfft) return 0;
+  return ((n_samples - nfft) / hop + 1) / averages;
+}
+
+int amcx_spectrogram_plan(int32_t nfft, int32_t hop, int32_t averages, int32_t* segments_per_pass, int32_t* lds_bytes,
+                          int32_t* max_workgroups) {
+  if (amcx_spectrogram_out_rows(0, nfft, hop, averages) < 0) return AMCX_EINVAL;
+  if (segments_per_pass != nullptr) *segments_per_pass = amcx::kPsdPoints / nfft;
+  if (lds_bytes != nullptr) *lds_bytes = amcx::kPsdLdsBytes;
+  if (max_workgroups != nullptr) *max_workgroups = cu_count() * wgs_per_cu(amcx::kPsdLdsBytes, 8);
+  return AMCX_OK;
+}
+
+int amcx_spectrogram(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, const float* window_dev, int32_t nfft,
+                     int32_t hop, int32_t averages, float* psd_dev, int64_t row_stride, int64_t n_rows, void* hip_stream) {
+  const StreamSrc src{src_kind};
+  if (!src.ok(scale)) return AMCX_EINVAL;
+  const int64_t R = amcx_spectrogram_out_rows(n_samples, nfft, hop, averages);
+  if (R < 0 || n_rows > R || !psd_rows_ok(n_rows, row_stride, nfft)) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (!stream_ptrs_ok(src_dev, window_dev, psd_dev, src, 3u)) return AMCX_EINVAL;
+  const int segs = amcx::kPsdPoints / nfft;
+  const int64_t n_passes = (n_rows + segs - 1) / segs;
+  const int64_t grid = amcx::persistent_grid(cu_count(), wgs_per_cu(amcx::kPsdLdsBytes, 8), n_passes, 1);
+  const hipError_t e = amcx::launch(psd_kernel(src).kern, grid, amcx::kPsdThreads, 0, static_cast<hipStream_t>(hip_stream),
+                                    static_cast<const char*>(src_dev), src.kernel_scale(scale), src.flip4(), window_dev, nfft,
+                                    psd_log2(nfft), hop, averages, psd_dev, (long long)row_stride, (long long)n_rows,
+                                    (long long)n_passes);
+  if (e != hipSuccess) return hip_fail(e, "spectrogram kernel launch");
+  return AMCX_OK;
+}
+
+int amcx_psd_detect_f32(const float* psd_dev, int64_t n_rows, int32_t bins, int64_t row_stride, int32_t floor_rank, float threshold,
+                        float* floor_dev, uint8_t* mask_dev, void* hip_stream) {
+  if (n_rows < 0 || bins < 2 || bins > amcx::kPsdMaxBins || floor_rank < 0 || floor_rank >= bins) return AMCX_EINVAL;
+  if (!(threshold > 0.0f && threshold <= 3.4028235e38f)) return AMCX_EINVAL;          // not NaN, inf, <= 0
+  if (!psd_rows_ok(n_rows, row_stride, bins)) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (psd_dev == nullptr || floor_dev == nullptr) return AMCX_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(psd_dev) & 3u) || (reinterpret_cast<uintptr_t>(floor_dev) & 3u)) return AMCX_EINVAL;
+  if (on_another_device(psd_dev) || on_another_device(floor_dev) || (mask_dev && on_another_device(mask_dev))) return AMCX_EINVAL;
+  const int64_t grid = amcx::persistent_grid(cu_count(), 8, n_rows, 1);
+  const hipError_t e = amcx::launch(amcx::amcx_psd_detect_kernel, grid, amcx::kPsdThreads, 0, static_cast<hipStream_t>(hip_stream),
+                                    psd_dev, (long long)n_rows, bins, (long long)row_stride, floor_rank, threshold, floor_dev,
+                                    mask_dev);
+  if (e != hipSuccess) return hip_fail(e, "spectrogram detection kernel launch");
+  return AMCX_OK;
+}
+
+int amcx_kernel_name_psd(int32_t src_kind, char* buf, int32_t buf_len) {
+  return put_kernel_name(psd_kernel({src_kind}).name, buf, buf_len);
+}
+
+const char* amcx_kernel_name_psd_detect(void) { return "amcx_psd_detect_kernel"; }
 
 int64_t amcx_group_stats_workspace_bytes(int64_t n_groups, int64_t rows_per_group, int32_t n_cols) {
   if (!stats_args_ok(n_groups, rows_per_group, n_cols, n_cols)) return -1;

@@ -312,6 +312,8 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bo
 // it includes the down-converter's header, whose loaders and mixer it uses, in front of its own kernels) are included first of all.
 // The resampler's (ABI 13, amcx_resample_kernel.h, which includes the down-converter's in the same way) came in front of the bank's, and the
 // occupancy kernels (ABI 14, amcx_occupancy_kernels.h: plain kernels that call nothing of the others) in front of everything.
+// The spectrogram's (ABI 15, amcx_psd_kernel.h, which includes the occupancy and down-converter headers for occ_key and the
+// loaders) are included in front of those.
 // That specialisations are laid out there is what hipcc does today, not a rule it documents: tools/codeobj_gate.py --kernels
 // against the parent commit is what guards it, and the only thing that will notice when a compiler lays them out elsewhere.
 inline void kernel_order_anchor() {

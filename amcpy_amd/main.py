@@ -15,6 +15,11 @@ stream -- and writes `features` (F, 18) and `frame_start` (F,) into a .mat file:
 The tuning flags (SigMF only) put the device's down-converter in front: the emitter moved to 0 Hz, low-passed and decimated
 (amcpy_amd/ddc.py; sigmf.extract_sigmf, tune=); --resample L/D and --rational put the rational resampler there instead
 (amcpy_amd/resample.py): the rate changes by L / D, and the output file also records `interp` and `decim`.
+`python -m amcpy_amd scan FILE [--nfft N] [--hop H] [--averages A] [--window hann|rect] [--threshold-db X] [--floor-quantile Q]
+[--min-bins B] [--merge-bins G] [--min-rows R] [--format ...] [--scale S] [--device D] [--out PATH] [--annotate OUT.sigmf-meta]`
+finds the emitters of a recording with no raster: the Welch spectrogram on the device, a floor and a mask per row, the occupied
+bins joined into emitters (amcpy_amd/psd.py; sigmf.scan_sigmf), written into a .mat file and, with --annotate, into a copy of
+the meta file as annotations -- which `recording --annotation K --rational` reads back.
 
 Several GPUs, ONE command (the reference's caller runs one command and the parallelism happens inside,
 feature_extraction.py:89-97): ``--devices 0,1,2,3`` / ``--devices all`` drives one engine per device from one
@@ -113,6 +118,28 @@ def build_parser() -> argparse.ArgumentParser:
     rec.add_argument("--mode", choices=("training", "test"), default=None, help="with --model: as for classify (default test)")
     rec.add_argument("--annotate", type=Path, default=None, metavar="OUT.sigmf-meta",
                      help="with --channels and --detect: a copy of the meta file with one annotation per occupied segment")
+    sc = sub.add_parser("scan", help="where the emitters of a SigMF recording are: Welch spectrogram, detection, annotations")
+    sc.add_argument("file", type=Path, metavar="FILE",
+                    help="X.sigmf-meta, X.sigmf-data or the stem X of a SigMF recording; or a raw stream (then --format)")
+    sc.add_argument("--nfft", type=int, default=1024, metavar="N", help="bins: a power of two, 64 ... 4096 (default 1024)")
+    sc.add_argument("--hop", type=int, default=None, metavar="H", help="samples between two segments (default N / 2)")
+    sc.add_argument("--averages", type=int, default=16, metavar="A", help="segments summed into one row (default 16)")
+    sc.add_argument("--window", choices=("hann", "rect"), default="hann")
+    sc.add_argument("--threshold-db", type=float, default=6.0, metavar="X",
+                    help="a bin is occupied where its power is more than X dB over the row's floor (default 6)")
+    sc.add_argument("--floor-quantile", type=float, default=0.25, metavar="Q",
+                    help="the floor of a row is the bin power of rank int(Q (N - 1)) (default 0.25)")
+    sc.add_argument("--min-bins", type=int, default=2, metavar="B", help="bands narrower than B bins are dropped (default 2)")
+    sc.add_argument("--merge-bins", type=int, default=2, metavar="G", help="bands at most G free bins apart are joined (default 2)")
+    sc.add_argument("--min-rows", type=int, default=1, metavar="R", help="emitters shorter than R rows are dropped (default 1)")
+    sc.add_argument("--format", choices=("cf32", "sc16", "ci8", "cu8"), default=None,
+                    help="the samples of a raw stream (a SigMF recording names its own); edges are then in cycles per sample")
+    sc.add_argument("--scale", type=float, default=None,
+                    help="what an integer component is multiplied by (default 2^-15 for sc16, 2^-7 for ci8 / cu8)")
+    sc.add_argument("--device", type=int, default=None, help="GPU index (default: the current device)")
+    sc.add_argument("--out", type=Path, default=None, help="the .mat file to write (default: FILE's stem + _scan.mat)")
+    sc.add_argument("--annotate", type=Path, default=None, metavar="OUT.sigmf-meta",
+                    help="a copy of the meta file with one annotation per emitter, for `recording --annotation K --rational`")
     return ap
 
 
@@ -149,14 +176,12 @@ def annotate_segments(meta: dict, segments, frame_start, frame_size: int, decim:
     ``core:sample_start`` / ``core:sample_count`` in input samples (a frame covers ``frame_size * decim`` of them),
     ``core:freq_lower_edge`` / ``core:freq_upper_edge`` = the channel's centre -/+ half the channel spacing, and -- with
     ``labels`` (C, K) and ``class_names`` -- ``core:label``, the name of the majority label (>= 0) of the segment's cells."""
-    import copy
     import numpy as np
     rate = (meta.get("global") or {}).get("core:sample_rate")
     if not rate:
         raise SystemExit("--annotate needs the global core:sample_rate (the channels' frequency edges)")
     half = float(rate) / len(channel_freq_hz) / 2.0
-    out = copy.deepcopy(meta)
-    anns = list(out.get("annotations") or [])
+    anns = []
     for c, k0, k1 in segments:
         ann = {"core:sample_start": int(frame_start[k0]),
                "core:sample_count": int(frame_start[k1] - frame_start[k0]) + int(frame_size) * int(decim),
@@ -167,7 +192,71 @@ def annotate_segments(meta: dict, segments, frame_start, frame_size: int, decim:
             if seen.size:
                 ann["core:label"] = str(class_names[int(np.bincount(seen).argmax())])
         anns.append(ann)
-    out["annotations"] = sorted(anns, key=lambda a: int(a.get("core:sample_start", 0)))
+    return with_annotations(meta, anns)
+
+
+def with_annotations(meta: dict, new) -> dict:
+    """A copy of the parsed meta file with the annotations ``new`` appended to its own, all in ``core:sample_start`` order
+    (a stable sort: the recording's own annotations keep their order among equals, and come first)."""
+    import copy
+    out = copy.deepcopy(meta)
+    out["annotations"] = sorted(list(out.get("annotations") or []) + list(new), key=lambda a: int(a.get("core:sample_start", 0)))
+    return out
+
+
+def annotate_emitters(meta: dict, emitters) -> dict:
+    """A copy of the parsed meta file with one annotation per emitter of ``sigmf.scan_sigmf`` appended: ``core:sample_start``,
+    ``core:sample_count``, ``core:freq_lower_edge``, ``core:freq_upper_edge`` and ``core:comment`` with the SNR -- what
+    ``sigmf.tune_from_annotation`` reads.  The edges are only frequencies where the recording has a sample rate."""
+    if not (meta.get("global") or {}).get("core:sample_rate"):
+        raise SystemExit("--annotate needs the global core:sample_rate (the emitters' frequency edges)")
+    return with_annotations(meta, [{"core:sample_start": int(e["sample_start"]), "core:sample_count": int(e["sample_count"]),
+                                    "core:freq_lower_edge": float(e["freq_lower_edge"]),
+                                    "core:freq_upper_edge": float(e["freq_upper_edge"]),
+                                    "core:comment": f"amcpy_amd scan: snr_db={float(e['snr_db']):.1f}"} for e in emitters])
+
+
+def run_scan(args, psd_compute=None, detect_compute=None) -> Path:
+    """The `scan` command: sigmf.scan_sigmf of args.file -> args.out, a .mat file with psd, row_start, row_samples, freq_hz
+    (where the meta gives a sample rate), floor, occupied, snr_db and the emitters as columns (emitter_sample_start,
+    emitter_sample_count, emitter_freq_lower_edge, emitter_freq_upper_edge, emitter_snr_db); --annotate writes the emitters
+    into a copy of the meta file.  ``psd_compute``, ``detect_compute``: injected (tests)."""
+    import numpy as np
+    from scipy.io import savemat
+    from . import sigmf
+    path = Path(args.file)
+    if sigmf.is_sigmf(path):
+        if args.format is not None:
+            raise SystemExit("--format: a SigMF recording names its own datatype")
+        rec = sigmf.read_meta(path)
+        stem = Path(sigmf._stem(path))
+    else:
+        if args.format is None:
+            raise SystemExit(f"{path} is no SigMF recording: --format cf32|sc16|ci8|cu8 says what its samples are")
+        rec = sigmf.raw_recording(path, args.format)
+        stem = path.with_suffix("")
+    if args.annotate is not None and not (rec["meta"].get("global") or {}).get("core:sample_rate"):
+        raise SystemExit("--annotate needs the global core:sample_rate (the emitters' frequency edges)")
+    detect = {"threshold_db": args.threshold_db, "floor_quantile": args.floor_quantile, "min_bins": args.min_bins,
+              "merge_bins": args.merge_bins, "min_rows": args.min_rows}
+    got = sigmf.scan_recording(rec, nfft=args.nfft, hop=args.hop, averages=args.averages, window=args.window, detect=detect,
+                               device=args.device, scale_samples=args.scale, psd_compute=psd_compute, detect_compute=detect_compute)
+    found = got.pop("emitters")
+    for key, kind in (("sample_start", np.int64), ("sample_count", np.int64), ("freq_lower_edge", np.float64),
+                      ("freq_upper_edge", np.float64), ("snr_db", np.float64)):
+        got["emitter_" + key] = np.array([e[key] for e in found], dtype=kind)
+    out = Path(args.out) if args.out is not None else stem.with_name(stem.name + "_scan.mat")
+    aside = out.with_name(out.name + f".{os.getpid()}.tmp")
+    try:
+        with open(aside, "wb") as fh:
+            savemat(fh, got)
+        os.replace(aside, out)
+    finally:
+        if aside.exists():
+            aside.unlink()
+    if args.annotate is not None:
+        Path(args.annotate).write_text(json.dumps(annotate_emitters(rec["meta"], found), indent=1))
+    print(f"{out}: {got['psd'].shape[0]} rows of {args.nfft} bins, {len(found)} emitters")
     return out
 
 
@@ -428,6 +517,9 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
         if skip_torch and recording_tune(args) is None and recording_channelize(args) is None:
             _lib.load(skip_torch=True)
         run_recording(args)
+        return 0
+    if args.command == "scan":                # tensors on torch's runtime: this command never skips the import
+        run_scan(args)
         return 0
     cfg = Config() if args.root is None else Config(paths=Paths(root=args.root))
     sig = cfg.signals

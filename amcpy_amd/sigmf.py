@@ -456,6 +456,130 @@ def survey_sigmf(path, frame_size: int, *, channelize, detect=None, model=None, 
     return out
 
 
+_SCAN_DETECT = {"threshold_db": 6.0, "floor_quantile": 0.25, "min_bins": 2, "merge_bins": 2, "min_rows": 1}
+
+
+def scan_sigmf(path, *, nfft: int = 1024, hop=None, averages: int = 16, window="hann", detect=None,
+               device: Optional[int] = None, scale_samples=None, chunk_samples: int = 1 << 24, psd_compute=None,
+               detect_compute=None) -> dict:
+    """Where the emitters of a SigMF recording of an unknown band are, with no channel raster: the Welch spectrogram of the
+    raw stream on the device (:mod:`amcpy_amd.psd`), a noise floor and a mask per row, and the occupied bins joined into
+    emitters -- time span and frequency edges, the input of ``tune_from_annotation``.  Returns a dict:
+
+        psd (R, nfft) float32           sums of ``averages`` windowed periodograms in FFT order, not normalised
+                                        (:func:`amcpy_amd.psd.power_scale`)
+        row_start (R,) int64            the sample index (``core:sample_start`` counting) of each row's first sample
+        row_samples                     ``(A - 1) hop + nfft``: the samples a row covers
+        freq_hz (nfft,) float64         only where the meta gives ``core:sample_rate``: the bins' frequencies, offset by the
+                                        first capture's ``core:frequency`` where it has one
+      with ``detect = dict(threshold_db=6.0, floor_quantile=0.25, min_bins=2, merge_bins=2, min_rows=1)`` (any key may be left out):
+        floor (R,) float32, occupied (R, nfft) bool, snr_db (R, nfft) float32
+        emitters                        a list of dicts: ``sample_start``, ``sample_count``, ``freq_lower_edge``,
+                                        ``freq_upper_edge`` (the outer edges of the emitter's first and last bin: bin centre
+                                        -/+ half a bin, in Hz and offset by the ``core:frequency`` of the capture that holds
+                                        the emitter; in cycles per sample where the meta gives no sample rate), ``snr_db``
+                                        (the mean over the emitter's occupied cells), and ``rows`` / ``bins``, its
+                                        ``(first, last)`` rows of ``psd`` and signed bins (:func:`amcpy_amd.psd.emitters`)
+
+    Segments are walked as ``extract_sigmf(tune=...)`` walks them: every capture is read in chunks of ``chunk_samples``, copied
+    to the device as it lies and pushed through a :class:`amcpy_amd.psd.Spectrogram` that starts anew with the capture -- no
+    row straddles a capture, and no emitter does.  What the detector assumes: :mod:`amcpy_amd.psd`.  ``scale_samples``: what an
+    integer component is multiplied by.  Injected computes (tests, numpy; the two go together): ``psd_compute`` as
+    :class:`amcpy_amd.psd.Spectrogram`'s ``compute``; ``detect_compute(P (R, nfft), floor_rank, threshold) -> (floor, mask)``."""
+    return scan_recording(read_meta(path), nfft=nfft, hop=hop, averages=averages, window=window, detect=detect, device=device,
+                          scale_samples=scale_samples, chunk_samples=chunk_samples, psd_compute=psd_compute,
+                          detect_compute=detect_compute)
+
+
+def raw_recording(path, sample_format: str) -> dict:
+    """What :func:`read_meta` returns, for a raw stream of ``sample_format`` samples: one capture from sample 0, an empty meta."""
+    fmt = _formats.get(sample_format)
+    data_path = Path(path)
+    return {"meta": {"global": {}, "captures": [{}], "annotations": []}, "data_path": data_path, "datatype": fmt.sigmf,
+            "sample_format": fmt.name, "store": fmt.store, "scale": fmt.scale,
+            "segments": [(0, 0, data_path.stat().st_size // fmt.store.itemsize)]}
+
+
+def scan_recording(rec: dict, *, nfft: int = 1024, hop=None, averages: int = 16, window="hann", detect=None,
+                   device: Optional[int] = None, scale_samples=None, chunk_samples: int = 1 << 24, psd_compute=None,
+                   detect_compute=None) -> dict:
+    """:func:`scan_sigmf` on what :func:`read_meta` (or :func:`raw_recording`) returned."""
+    from . import occupancy, psd
+    if (psd_compute is None) != (detect_compute is None):
+        raise ValueError("psd_compute and detect_compute are injected together")
+    if detect is not None and (not isinstance(detect, dict) or set(detect) - set(_SCAN_DETECT)):
+        raise ValueError(f"detect: a dict of {sorted(_SCAN_DETECT)}")
+    opt = {**_SCAN_DETECT, **(detect or {})}
+    nfft = int(nfft)
+    hop = nfft // 2 if hop is None else int(hop)
+    A = int(averages)
+    fmt = rec["sample_format"]
+    scale = _formats.scale_of(fmt, scale_samples)
+    win = psd._window_of(window, nfft)
+    span, step = psd.row_samples(nfft, hop, A), A * hop
+    rank, thr = occupancy.floor_rank_of(nfft, float(opt["floor_quantile"])), occupancy.threshold_of(float(opt["threshold_db"]))
+    plain, tail = _formats.get(fmt).plain, _formats.get(fmt).tail
+    on_gpu = psd_compute is None
+    if on_gpu:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    glob = rec["meta"].get("global") or {}
+    rate = glob.get("core:sample_rate")
+    captures = rec["meta"].get("captures") or [{}]
+    tiny = float(np.finfo(np.float32).tiny)
+    chunk_samples = max(1, int(chunk_samples))
+    parts, starts, floors, masks, snrs, found = [], [], [], [], [], []
+    n_rows = 0
+    for j, (start, off, n_samples) in enumerate(rec["segments"]):
+        if n_samples == 0:
+            continue
+        src = np.memmap(rec["data_path"], dtype=plain, mode="c", offset=off, shape=(n_samples,) + tail)
+        sp = psd.Spectrogram(nfft, hop, A, win, fmt, scale, compute=psd_compute)
+        rows = []
+        for c0 in range(0, n_samples, chunk_samples):
+            chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
+            rows.append(sp.push(torch.from_numpy(chunk).to(dev) if on_gpu else chunk))
+        R = sp.rows_done
+        if R == 0:
+            continue
+        P = torch.cat(rows) if on_gpu else np.concatenate(rows)
+        row_start = start + step * np.arange(R, dtype=np.int64)
+        if detect is not None:
+            if on_gpu:
+                det = psd.detect(P, floor_quantile=float(opt["floor_quantile"]), threshold_db=float(opt["threshold_db"]))
+                floor, mask, snr = det.floor.cpu().numpy(), det.mask.cpu().numpy(), det.snr_db.cpu().numpy()
+            else:
+                floor, mask = detect_compute(P, rank, thr)
+                floor, mask = np.asarray(floor, dtype=np.float32), np.asarray(mask).astype(bool)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    snr = (10.0 * np.log10(np.maximum(np.asarray(P, np.float32) / floor[:, None] - np.float32(1.0), tiny))).astype(np.float32)
+            fs = float(rate) if rate else 1.0
+            fc = float(captures[j].get("core:frequency", 0.0)) if rate and j < len(captures) else 0.0
+            for r0, r1, lo, hi in psd.emitters(mask, int(opt["min_bins"]), int(opt["merge_bins"]), int(opt["min_rows"])):
+                cols = np.arange(lo, hi + 1) % nfft
+                cells = mask[r0:r1 + 1][:, cols]
+                found.append({"sample_start": int(row_start[r0]), "sample_count": int(row_start[r1] - row_start[r0]) + span,
+                              "freq_lower_edge": fc + fs * (lo - 0.5) / nfft, "freq_upper_edge": fc + fs * (hi + 0.5) / nfft,
+                              "snr_db": float(np.mean(snr[r0:r1 + 1][:, cols][cells])),
+                              "rows": (n_rows + r0, n_rows + r1), "bins": (lo, hi)})
+            floors.append(floor)
+            masks.append(mask)
+            snrs.append(snr)
+        parts.append(P.cpu().numpy() if on_gpu else np.asarray(P, dtype=np.float32))
+        starts.append(row_start)
+        n_rows += R
+    out = {"psd": np.concatenate(parts) if parts else np.empty((0, nfft), np.float32),
+           "row_start": np.concatenate(starts) if starts else np.empty((0,), np.int64), "row_samples": span}
+    if rate:
+        out["freq_hz"] = psd.bin_frequencies(nfft, float(rate), float(captures[0].get("core:frequency", 0.0)))
+    if detect is not None:
+        out["floor"] = np.concatenate(floors) if floors else np.empty((0,), np.float32)
+        out["occupied"] = np.concatenate(masks) if masks else np.zeros((0, nfft), bool)
+        out["snr_db"] = np.concatenate(snrs) if snrs else np.empty((0, nfft), np.float32)
+        out["emitters"] = found
+    return out
+
+
 def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, feature_ids=None, scale=None,
                   max_frames: Optional[int] = None, compute=None, tune=None, tune_compute=None,
                   chunk_samples: int = 1 << 24, channelize=None, bank_compute=None):

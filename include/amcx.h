@@ -97,10 +97,12 @@ extern "C" {
  * amcx_kernel_name_iq8, AMCX_SRC_CI8 / AMCX_SRC_CU8 for the strided host / file entries and amcx_stage_host / _file,
  * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host;
  * 11 = the digital down-converter; 12 = the polyphase filter bank; 13 = the rational resampler; 14 = occupancy detection
- * (all listed behind the define). */
-#define AMCX_ABI_VERSION 14
+ * (all listed behind the define); 15 = the Welch spectrogram and its per-row detection. */
+#define AMCX_ABI_VERSION 15
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
- *   ABI 14: the line above               -- occupancy detection: amcx_row_power_c64, amcx_occupancy_workspace_bytes,
+ *   ABI 15: the line above               -- the spectrogram: amcx_spectrogram, amcx_spectrogram_out_rows, amcx_spectrogram_plan,
+ *                                            amcx_psd_detect_f32, amcx_kernel_name_psd, amcx_kernel_name_psd_detect
+ *   ABI 14: #define AMCX_ABI_VERSION 14   -- occupancy detection: amcx_row_power_c64, amcx_occupancy_workspace_bytes,
  *                                            amcx_occupancy_detect_f32, amcx_gather_rows_c64, amcx_kernel_name_occupancy
  *   ABI 13: #define AMCX_ABI_VERSION 13   -- the rational resampler: amcx_resample, amcx_resample_out_samples,
  *                                            amcx_resample_plan, amcx_kernel_name_resample
@@ -461,6 +463,57 @@ int amcx_gather_rows_c64(const void* src_dev, int64_t n_src_rows, int32_t row_sa
                          void* hip_stream);
 
 /*
+ * ABI 15.  THE WELCH SPECTROGRAM of a raw stream, and the detection of occupied bins per row (amcpy_amd/csrc/amcx_psd_kernel.h):
+ * where the emitters of an unknown band are, with no channel raster.  Both entries are asynchronous on the caller's stream,
+ * allocate nothing and are capturable in a graph; their checks come before any device call, in the order each states.
+ *
+ * amcx_spectrogram: S = n_samples samples at src_dev (src_kind, scale: as amcx_tune_decimate), window_dev[0 .. nfft) float32,
+ * segment s begins at sample s * hop, A = averages:
+ *     xw_s[n]       = window[n] * x[s hop + n]                               one float32 product per component
+ *     X_s[b]        = sum_{n < nfft} xw_s[n] exp(-2 pi j b n / nfft)          b = 0 ... nfft - 1, FFT order (b > nfft / 2:
+ *                                                                            negative frequencies)
+ *     psd[r, b]     = sum_{a < A} |X_{r A + a}[b]|^2                          at psd_dev + r * row_stride + b, float32
+ *     nseg = S >= nfft ? floor((S - nfft) / hop) + 1 : 0,   R = floor(nseg / A)   (amcx_spectrogram_out_rows; a partial last
+ *                                                                            row is dropped, never a partial sum)
+ *   The rows 0 ... n_rows - 1 are written, n_rows <= R.  No normalisation: 1 / (A sum window^2) is the caller's.
+ *   - ONE OPERATION SEQUENCE PER nfft (the kernel header writes it down; tests/psd_ref.py restates it in numpy float32): radix-2
+ *     decimation in frequency, log2 nfft stages; twiddles are the down-converter's mixer at exact integer angles (1 and -j are
+ *     exact); products as the filter bank forms them, (fma(a, c, -(b d)), fma(a, d, b c)); EVERY butterfly multiplies, also
+ *     by 1; |X|^2 = fma(im, im, re re); the row sum is ((p_0 + p_1) + p_2) + ... in ascending a.  It depends on nfft alone.
+ *   - POSITION INDEPENDENCE: a row's bits depend on its (A - 1) hop + nfft samples and the window, on nothing else: not on
+ *     whether the span begins on 16 bytes (any sample-aligned src_dev: 8, 4 or 2 bytes), the row's index, row_stride or
+ *     n_rows.  A stream cut into calls after any whole number of rows equals one call bit for bit.
+ *   - FORMATS: the rows of an sc16 / ci8 / cu8 stream are the bits of the complex64 call on the widened samples.
+ *   - Nothing outside [src, src + S) and [window, window + nfft) is read; nothing but the n_rows rows' nfft columns is written.
+ *   - accuracy: |psd - exact| <= the bound tests/psd_ref.py derives from the sequence, of the form
+ *     (6 log2 nfft + 1) 2^-24 sum_n |xw[n]| per transform output, carried through the squares and the row sum.
+ *   - limits: nfft a power of two 64 ... 4096; 1 <= hop <= 65536 (a hop above nfft leaves gaps, which are never read);
+ *     1 <= averages <= 65536; 0 <= n_samples < 2^40.
+ *   - checks: src_kind and, for the integer kinds, scale (finite, > 0); those limits, 0 <= n_rows <= R, row_stride >= nfft (and
+ *     n_rows times it at most 2^58); n_rows == 0 is AMCX_OK here, null pointers allowed; null pointers and alignment (src: a
+ *     sample; window 4, psd 4); a pointer on another device.
+ * amcx_spectrogram_out_rows: R, or -1 for arguments the entry refuses.  amcx_spectrogram_plan (host-only): the segments a
+ * workgroup transforms at a time (of that many DIFFERENT rows), the bytes of LDS, the most workgroups of the persistent grid.
+ *
+ * amcx_psd_detect_f32: per row r of psd_dev (n_rows rows of `bins` float32 at row_stride):
+ *     floor_dev[r]          = the element of rank floor_rank (0-based, ascending, NaN last) of the row's bins values
+ *     mask_dev[r bins + b]  = psd[r, b] > threshold * floor_dev[r] ? 1 : 0     (ONE float32 product, one IEEE comparison: a NaN
+ *                             is not occupied); packed rows of `bins` bytes; mask_dev may be NULL (not wanted)
+ *   Exactly what numpy float32 gives: amcx_occupancy_detect_f32's definitions, transposed, without the row list.
+ *   - checks: n_rows >= 0, 2 <= bins <= 4096 (any integer), 0 <= floor_rank < bins, threshold a finite float32 > 0;
+ *     row_stride >= bins (and n_rows times it at most 2^58); n_rows == 0 is AMCX_OK here, null pointers allowed; null pointers
+ *     (psd, floor) and alignment (4 bytes each); a pointer on another device.
+ */
+int64_t amcx_spectrogram_out_rows(int64_t n_samples, int32_t nfft, int32_t hop, int32_t averages);        /* -1 for refused arguments */
+int amcx_spectrogram(const void* src_dev, int32_t src_kind, int64_t n_samples, float scale, const float* window_dev,
+                     int32_t nfft, int32_t hop, int32_t averages, float* psd_dev, int64_t row_stride, int64_t n_rows,
+                     void* hip_stream);
+int amcx_spectrogram_plan(int32_t nfft, int32_t hop, int32_t averages, int32_t* segments_per_pass, int32_t* lds_bytes,
+                          int32_t* max_workgroups);
+int amcx_psd_detect_f32(const float* psd_dev, int64_t n_rows, int32_t bins, int64_t row_stride, int32_t floor_rank,
+                        float threshold, float* floor_dev, uint8_t* mask_dev, void* hip_stream);
+
+/*
  * Same computation for HOST buffers (numpy arrays): allocates device scratch,
  * copies in, runs the kernel on `device`, copies the (n_frames x 18) result
  * back and returns when it is in `out_host`.  Replaces a direct
@@ -557,6 +610,10 @@ const char* amcx_kernel_name_resample(int32_t src_kind);
  * (the floor), 2 amcx_gather_rows_kernel, and the three launches behind the floor: 3 amcx_occupancy_count_kernel,
  * 4 amcx_occupancy_scan_kernel, 5 amcx_occupancy_scatter_kernel; NULL for any other number. */
 const char* amcx_kernel_name_occupancy(int32_t which);   /* 0 power, 1 detect, 2 gather */
+/* ABI 15: the kernel amcx_spectrogram runs for this src_kind (host-only): amcx_spectrogram_c64_kernel, amcx_spectrogram_sc16_kernel
+ * or, for ci8 and cu8, amcx_spectrogram_iq8_kernel; AMCX_EINVAL for another kind.  And amcx_psd_detect_f32's, a static string. */
+int amcx_kernel_name_psd(int32_t src_kind, char* buf, int32_t buf_len);
+const char* amcx_kernel_name_psd_detect(void);
 
 /* ABI 7: every later host-buffer call of this context (amcx_ctx_features18_c64_host / _c128_host / _strided_host /
  * _strided_file) computes only the features in feature_mask, as amcx_features_c64_subset does (AMCX_FEATURES_ALL: the
