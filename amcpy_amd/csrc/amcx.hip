@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -511,14 +512,36 @@ StreamKernel<decltype(&amcx::amcx_spectrogram_c64_kernel)> psd_kernel(StreamSrc 
 }
 #undef AMCX_NAMED
 
-// the pointers of a call that launches: all there, each aligned to its element (out: complex64, or float32 rows with
-// out_align = 3), none on another device
+// ---- the host gates of the entries that launch: limits (these), the no-op return, then the pointers (ptrs_ok) ---------------
+// n_rows rows at row_stride elements: the stride holds a row, and the product stays below 2^58 (each factor bounded first)
+bool rows_ok(int64_t n_rows, int64_t row_stride, int32_t row_elems) {
+  return n_rows >= 0 && row_stride >= row_elems && (n_rows == 0 || row_stride <= (int64_t(1) << 58) / n_rows);
+}
+bool threshold_ok(float threshold) { return int_scale_ok(threshold); }      // the same rule: a finite float32 > 0
+int log2_exact(int n) {      // of a power of two
+  int lg = 0;
+  while ((1 << lg) < n) ++lg;
+  return lg;
+}
+int psd_log2(int32_t nfft) {
+  return nfft < amcx::kPsdMinFft || nfft > amcx::kPsdMaxFft || !is_pow2(nfft) ? -1 : log2_exact(nfft);
+}
+
+// one pointer of a call that launches: its element's bytes less one, and whether the call needs it
+struct Ptr { const void* p; unsigned align_mask; bool required; };
+// a required pointer is there; then every pointer that is there is aligned to its element; then none of them is on another device
+bool ptrs_ok(std::initializer_list<Ptr> ptrs) {
+  for (const Ptr& a : ptrs)
+    if (a.required && a.p == nullptr) return false;
+  for (const Ptr& a : ptrs)
+    if (reinterpret_cast<uintptr_t>(a.p) & a.align_mask) return false;
+  for (const Ptr& a : ptrs)
+    if (a.p != nullptr && on_another_device(a.p)) return false;
+  return true;
+}
+// a stream entry's three, all required (out: complex64, or float32 rows with out_align = 3)
 bool stream_ptrs_ok(const void* src, const float* taps, const void* out, StreamSrc s, unsigned out_align = 7u) {
-  if (src == nullptr || taps == nullptr || out == nullptr) return false;
-  if ((reinterpret_cast<uintptr_t>(src) & s.src_align()) || (reinterpret_cast<uintptr_t>(taps) & 3u) ||
-      (reinterpret_cast<uintptr_t>(out) & out_align))
-    return false;
-  return !on_another_device(src) && !on_another_device(taps) && !on_another_device(out);
+  return ptrs_ok({{src, s.src_align(), true}, {taps, 3u, true}, {out, out_align, true}});
 }
 
 // resident workgroups per CU of a launch with `lds_bytes` of dynamic LDS: what the CU's 160 KiB leave room for, `cap` at most
@@ -1026,17 +1049,15 @@ int amcx_filter_bank(const void* src_dev, int32_t src_kind, int64_t n_samples, f
   const int64_t n_tiles = (M + tile - 1) / tile;
   const int64_t grid = amcx::persistent_grid(cu_count(), bank_wgs_per_cu(n_taps, channels, decim), n_tiles, 1);
   const int a0 = (int)(sample_index0 & (uint64_t)(channels - 1));
-  int logC = 0;
-  while ((1 << logC) < channels) ++logC;
   const auto k = bank_kernel(src);
   // the most a bank kernel ever asks for: C = 2 (tile 2048), T = 4096, D = 2
   if (const hipError_t e = k.lds_attr((int)amcx::bank_lds_bytes(amcx::kBankMaxTaps, 2, 2)); e != hipSuccess)
     return hip_fail(e, "filter-bank kernel attribute");
   const hipError_t e = amcx::launch(k.kern, grid, amcx::kBankThreads, amcx::bank_lds_bytes(n_taps, channels, decim),
                                     static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), src.kernel_scale(scale),
-                                    src.flip4(), (unsigned long long)phase0, (unsigned long long)phase_step, a0, taps_dev, n_taps, logC,
-                                    decim, static_cast<float2*>(out_c64_dev), (long long)out_channel_stride, (long long)M, tile,
-                                    (long long)n_tiles);
+                                    src.flip4(), (unsigned long long)phase0, (unsigned long long)phase_step, a0, taps_dev, n_taps,
+                                    log2_exact(channels), decim, static_cast<float2*>(out_c64_dev), (long long)out_channel_stride,
+                                    (long long)M, tile, (long long)n_tiles);
   if (e != hipSuccess) return hip_fail(e, "filter-bank kernel launch");
   return AMCX_OK;
 }
@@ -1103,12 +1124,9 @@ int64_t occ_blocks(int64_t n_cells) { return (n_cells + amcx::kOccBlockRows - 1)
 
 int amcx_row_power_c64(const void* rows_dev, int64_t n_rows, int32_t row_samples, int64_t row_stride_samples, float* power_dev,
                        void* hip_stream) {
-  if (n_rows < 0 || row_samples < 2 || row_samples > AMCX_MAX_FRAME_SIZE) return AMCX_EINVAL;
-  if (row_stride_samples < row_samples || (n_rows > 0 && row_stride_samples > (int64_t(1) << 58) / n_rows)) return AMCX_EINVAL;
+  if (row_samples < 2 || row_samples > AMCX_MAX_FRAME_SIZE || !rows_ok(n_rows, row_stride_samples, row_samples)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
-  if (rows_dev == nullptr || power_dev == nullptr) return AMCX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(rows_dev) & 7u) || (reinterpret_cast<uintptr_t>(power_dev) & 3u)) return AMCX_EINVAL;
-  if (on_another_device(rows_dev) || on_another_device(power_dev)) return AMCX_EINVAL;
+  if (!ptrs_ok({{rows_dev, 7u, true}, {power_dev, 3u, true}})) return AMCX_EINVAL;
   const int64_t grid = amcx::persistent_grid(cu_count(), 8, n_rows, amcx::kOccWaves);
   const hipError_t e = amcx::launch(amcx::amcx_row_power_kernel, grid, amcx::kOccThreads, 0, static_cast<hipStream_t>(hip_stream),
                                     static_cast<const float2*>(rows_dev), (long long)n_rows, row_samples,
@@ -1126,20 +1144,12 @@ int amcx_occupancy_detect_f32(const float* power_dev, int32_t channels, int64_t 
                               float* floor_dev, uint8_t* mask_dev, int32_t* rows_dev, int32_t* count_dev, void* workspace_dev,
                               int64_t workspace_bytes, void* hip_stream) {
   if (!occ_grid_ok(channels, n_frames) || floor_rank < 0 || floor_rank >= channels) return AMCX_EINVAL;
-  if (!(threshold > 0.0f && threshold <= 3.4028235e38f)) return AMCX_EINVAL;          // not NaN, inf, <= 0
+  if (!threshold_ok(threshold)) return AMCX_EINVAL;
   const bool counted = rows_dev != nullptr || count_dev != nullptr;
   if (counted && workspace_bytes < amcx_occupancy_workspace_bytes(channels, n_frames)) return AMCX_EINVAL;
   if (n_frames == 0) return AMCX_OK;
-  if (power_dev == nullptr || floor_dev == nullptr || (rows_dev != nullptr && count_dev == nullptr) ||
-      (counted && workspace_dev == nullptr))
-    return AMCX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(power_dev) & 3u) || (reinterpret_cast<uintptr_t>(floor_dev) & 3u) ||
-      (reinterpret_cast<uintptr_t>(rows_dev) & 3u) || (reinterpret_cast<uintptr_t>(count_dev) & 3u) ||
-      (reinterpret_cast<uintptr_t>(workspace_dev) & 3u))
-    return AMCX_EINVAL;
-  if (on_another_device(power_dev) || on_another_device(floor_dev) || (mask_dev && on_another_device(mask_dev)) ||
-      (rows_dev && on_another_device(rows_dev)) || (count_dev && on_another_device(count_dev)) ||
-      (counted && on_another_device(workspace_dev)))
+  if (!ptrs_ok({{power_dev, 3u, true}, {floor_dev, 3u, true}, {mask_dev, 0u, false}, {rows_dev, 3u, false},
+                {count_dev, 3u, rows_dev != nullptr}, {workspace_dev, 3u, counted}}))
     return AMCX_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   const int cus = cu_count();
@@ -1169,17 +1179,10 @@ int amcx_occupancy_detect_f32(const float* power_dev, int32_t channels, int64_t 
 
 int amcx_gather_rows_c64(const void* src_dev, int64_t n_src_rows, int32_t row_samples, int64_t row_stride_samples,
                          const int32_t* index_dev, int64_t n_index, void* dst_dev, int64_t dst_stride_samples, void* hip_stream) {
-  if (n_src_rows < 0 || n_index < 0 || row_samples < 2 || row_samples > AMCX_MAX_FRAME_SIZE) return AMCX_EINVAL;
-  if (row_stride_samples < row_samples || dst_stride_samples < row_samples ||
-      (n_src_rows > 0 && row_stride_samples > (int64_t(1) << 58) / n_src_rows) ||
-      (n_index > 0 && dst_stride_samples > (int64_t(1) << 58) / n_index))
-    return AMCX_EINVAL;
+  if (row_samples < 2 || row_samples > AMCX_MAX_FRAME_SIZE) return AMCX_EINVAL;
+  if (!rows_ok(n_src_rows, row_stride_samples, row_samples) || !rows_ok(n_index, dst_stride_samples, row_samples)) return AMCX_EINVAL;
   if (n_index == 0) return AMCX_OK;
-  if ((src_dev == nullptr && n_src_rows > 0) || index_dev == nullptr || dst_dev == nullptr) return AMCX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(src_dev) & 7u) || (reinterpret_cast<uintptr_t>(index_dev) & 3u) ||
-      (reinterpret_cast<uintptr_t>(dst_dev) & 7u))
-    return AMCX_EINVAL;
-  if ((src_dev && on_another_device(src_dev)) || on_another_device(index_dev) || on_another_device(dst_dev)) return AMCX_EINVAL;
+  if (!ptrs_ok({{src_dev, 7u, n_src_rows > 0}, {index_dev, 3u, true}, {dst_dev, 7u, true}})) return AMCX_EINVAL;
   const int64_t grid = amcx::persistent_grid(cu_count(), 8, n_index, amcx::kOccWaves);
   const hipError_t e = amcx::launch(amcx::amcx_gather_rows_kernel, grid, amcx::kOccThreads, 0, static_cast<hipStream_t>(hip_stream),
                                     static_cast<const float2*>(src_dev), (long long)n_src_rows, row_samples,
@@ -1202,19 +1205,6 @@ const char* amcx_kernel_name_occupancy(int32_t which) {
 }
 
 // ---- the spectrogram and its detection (amcx_psd_kernel.h) ----------------------------------------------------------------
-namespace {
-int psd_log2(int32_t nfft) {
-  if (nfft < amcx::kPsdMinFft || nfft > amcx::kPsdMaxFft || !is_pow2(nfft)) return -1;
-  int lg = 0;
-  while ((1 << lg) < nfft) ++lg;
-  return lg;
-}
-// n_rows rows at row_stride elements: the stride holds a row, and the product stays below 2^58 (each factor bounded first)
-bool psd_rows_ok(int64_t n_rows, int64_t row_stride, int32_t row_elems) {
-  return n_rows >= 0 && row_stride >= row_elems && (n_rows == 0 || row_stride <= (int64_t(1) << 58) / n_rows);
-}
-}  // namespace
-
 int64_t amcx_spectrogram_out_rows(int64_t n_samples, int32_t nfft, int32_t hop, int32_t averages) {
   if (psd_log2(nfft) < 0 || hop < 1 || hop > amcx::kPsdMaxHop || averages < 1 || averages > amcx::kPsdMaxAverages) return -1;
   if (n_samples < 0 || n_samples >= (int64_t(1) << 40)) return -1;
@@ -1236,7 +1226,7 @@ int amcx_spectrogram(const void* src_dev, int32_t src_kind, int64_t n_samples, f
   const StreamSrc src{src_kind};
   if (!src.ok(scale)) return AMCX_EINVAL;
   const int64_t R = amcx_spectrogram_out_rows(n_samples, nfft, hop, averages);
-  if (R < 0 || n_rows > R || !psd_rows_ok(n_rows, row_stride, nfft)) return AMCX_EINVAL;
+  if (R < 0 || n_rows > R || !rows_ok(n_rows, row_stride, nfft)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
   if (!stream_ptrs_ok(src_dev, window_dev, psd_dev, src, 3u)) return AMCX_EINVAL;
   const int segs = amcx::kPsdPoints / nfft;
@@ -1252,13 +1242,10 @@ int amcx_spectrogram(const void* src_dev, int32_t src_kind, int64_t n_samples, f
 
 int amcx_psd_detect_f32(const float* psd_dev, int64_t n_rows, int32_t bins, int64_t row_stride, int32_t floor_rank, float threshold,
                         float* floor_dev, uint8_t* mask_dev, void* hip_stream) {
-  if (n_rows < 0 || bins < 2 || bins > amcx::kPsdMaxBins || floor_rank < 0 || floor_rank >= bins) return AMCX_EINVAL;
-  if (!(threshold > 0.0f && threshold <= 3.4028235e38f)) return AMCX_EINVAL;          // not NaN, inf, <= 0
-  if (!psd_rows_ok(n_rows, row_stride, bins)) return AMCX_EINVAL;
+  if (bins < 2 || bins > amcx::kPsdMaxBins || floor_rank < 0 || floor_rank >= bins || !threshold_ok(threshold)) return AMCX_EINVAL;
+  if (!rows_ok(n_rows, row_stride, bins)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
-  if (psd_dev == nullptr || floor_dev == nullptr) return AMCX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(psd_dev) & 3u) || (reinterpret_cast<uintptr_t>(floor_dev) & 3u)) return AMCX_EINVAL;
-  if (on_another_device(psd_dev) || on_another_device(floor_dev) || (mask_dev && on_another_device(mask_dev))) return AMCX_EINVAL;
+  if (!ptrs_ok({{psd_dev, 3u, true}, {floor_dev, 3u, true}, {mask_dev, 0u, false}})) return AMCX_EINVAL;
   const int64_t grid = amcx::persistent_grid(cu_count(), 8, n_rows, 1);
   const hipError_t e = amcx::launch(amcx::amcx_psd_detect_kernel, grid, amcx::kPsdThreads, 0, static_cast<hipStream_t>(hip_stream),
                                     psd_dev, (long long)n_rows, bins, (long long)row_stride, floor_rank, threshold, floor_dev,

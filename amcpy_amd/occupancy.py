@@ -26,6 +26,7 @@ import numpy as np
 
 from . import _lib, _stream
 
+_TINY = float(np.finfo(np.float32).tiny)
 Occupancy = namedtuple("Occupancy", "mask floor rows snr_db")
 Occupancy.__doc__ = """``mask`` (C, K) bool, ``floor`` (K,) float32, ``rows`` (n,) int32 ascending (r = c * K + k), ``snr_db`` (C, K) float32."""
 
@@ -47,19 +48,24 @@ def threshold_of(threshold_db: float) -> np.float32:
     return t
 
 
+def snr_db(power, floor, axis: int):
+    """Ten times the decimal logarithm of ``max(power / floor - 1, tiny)`` in float32, tiny the smallest normal float32: how
+    far a cell lies above its floor, -379 dB where it does not.  ``power`` float32, numpy or torch; ``floor`` of the same kind, one value per index of
+    ``power``'s ``axis``."""
+    shape = [1] * power.ndim
+    shape[axis] = -1
+    if isinstance(power, np.ndarray):
+        log10, at_least = np.log10, np.maximum
+    else:
+        import torch
+        log10, at_least = torch.log10, lambda v, least: torch.clamp(v, min=least)
+    with np.errstate(all="ignore"):
+        return 10.0 * log10(at_least(power / floor.reshape(shape) - 1.0, _TINY))
+
+
 def _rows_of(frames, what: str):
     import torch
-
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.complex64 or frames.dim() != 2:
-        raise TypeError(f"{what} must be a complex64 (R, N) torch tensor")
-    if not frames.is_cuda:
-        raise ValueError(f"{what} must live in GPU memory")
-    R, N = int(frames.shape[0]), int(frames.shape[1])
-    if N < 2:
-        raise ValueError("rows of at least 2 samples")
-    if frames.stride(1) != 1 or (R > 1 and frames.stride(0) < N):
-        raise ValueError(f"{what} must have contiguous rows at a row stride >= N")
-    return R, N, int(frames.stride(0)) if R > 1 else N
+    return _stream.rows_of(frames, torch.complex64, what, "N", 2, narrow="rows of at least 2 samples")
 
 
 def row_power(frames):
@@ -76,8 +82,8 @@ def row_power(frames):
 
 def detect(power, *, floor_quantile: float = 0.25, threshold_db: float = 6.0) -> Occupancy:
     """``power``: float32 ``(C, K)`` on the GPU, contiguous, 2 <= C <= 256 -> :class:`Occupancy` (the module's docstring says
-    what the detector assumes).  ``snr_db = 10 log10(max(power / floor - 1, tiny))`` is computed with torch: a label for the
-    user, no part of the detection."""
+    what the detector assumes).  ``snr_db`` is :func:`snr_db` of every cell over its frame's floor, computed with torch: a label
+    for the user, no part of the detection."""
     import torch
 
     if not isinstance(power, torch.Tensor) or power.dtype != torch.float32 or power.dim() != 2:
@@ -99,10 +105,9 @@ def detect(power, *, floor_quantile: float = 0.25, threshold_db: float = 6.0) ->
     _stream.launch(power, lambda lib_, stream: lib_.amcx_occupancy_detect_f32(
         power.data_ptr() if K else None, C, K, rank, float(thr), floor.data_ptr() if K else None, mask.data_ptr() if K else None,
         rows.data_ptr() if K else None, count.data_ptr(), ws.data_ptr(), need, stream))
-    tiny = torch.finfo(torch.float32).tiny
-    snr_db = 10.0 * torch.log10(torch.clamp(power / floor[None, :] - 1.0, min=tiny))
+    snr = snr_db(power, floor, 1)
     n = int(count.item())                                   # the one host synchronisation
-    return Occupancy(mask.bool(), floor, rows[:n], snr_db)
+    return Occupancy(mask.bool(), floor, rows[:n], snr)
 
 
 def gather_rows(frames, rows):
@@ -126,18 +131,27 @@ def occupied_features(frames_CKN, occ: Occupancy, feature_ids=None):
     contiguous -> float32 ``(C, K, 18)`` with NaN in every cell that is not occupied.  :func:`gather_rows`, then
     :func:`amcpy_amd.features.features18` on the packed rows -- the feature kernels are the ones every other path runs --,
     then a torch scatter."""
-    import torch
-    from .features import features18
-
     C, K = int(occ.mask.shape[0]), int(occ.mask.shape[1])
     flat = frames_CKN.reshape(C * K, frames_CKN.shape[-1]) if frames_CKN.dim() == 3 else frames_CKN
     if int(flat.shape[0]) != C * K:
         raise ValueError(f"frames of {C} x {K} cells expected, got {tuple(frames_CKN.shape)}")
-    out = torch.full((C * K, _lib.NUM_FEATURES), float("nan"), dtype=torch.float32, device=flat.device)
-    if int(occ.rows.shape[0]) > 0:
-        feats = features18(gather_rows(flat, occ.rows), feature_ids=feature_ids)
-        out[occ.rows.long()] = feats.reshape(-1, _lib.NUM_FEATURES)
-    return out.view(C, K, _lib.NUM_FEATURES)
+    return _features_at(flat, occ.rows, feature_ids)[0].view(C, K, _lib.NUM_FEATURES)
+
+
+def _features_at(flat, rows, feature_ids=None) -> tuple:
+    """The gather -> features -> scatter step: ``flat`` complex64 ``(R, N)``, ``rows`` int32 ``(n,)`` -> ``(out, at, packed)``:
+    ``out`` float32 ``(R, 18)`` with NaN in every row not listed, and -- None where no row is listed -- the int64 index ``at``
+    and the ``packed`` ``(n, 18)`` features that were scattered by it (the survey scatters its labels by the same index)."""
+    import torch
+    from .features import features18
+
+    out = torch.full((int(flat.shape[0]), _lib.NUM_FEATURES), float("nan"), dtype=torch.float32, device=flat.device)
+    if int(rows.shape[0]) == 0:
+        return out, None, None
+    at = rows.long()
+    packed = features18(gather_rows(flat, rows), feature_ids=feature_ids).reshape(-1, _lib.NUM_FEATURES)
+    out[at] = packed
+    return out, at, packed
 
 
 def segments(mask) -> list:

@@ -23,7 +23,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _formats, _lib, _stream
-from .occupancy import floor_rank_of, threshold_of
+from .occupancy import floor_rank_of, snr_db, threshold_of
 
 WINDOWS = ("hann", "rect")
 Detection = namedtuple("Detection", "floor mask snr_db")
@@ -101,38 +101,26 @@ def spectrogram(x, nfft: int, *, hop=None, averages: int = 1, window=None, scale
     (a view of ``out`` where given), ``R = out_rows(S, nfft, hop, averages)``, in FFT order (:func:`bin_frequencies`)."""
     import torch
 
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch tensor (complex64 (S,), or int16 / int8 / uint8 (S, 2))")
-    fmt = _stream._format_of(x)
-    scale = _formats.scale_of(fmt, scale)
-    if not x.is_cuda:
-        raise ValueError("x must live in GPU memory")
-    if not x.is_contiguous():
-        raise ValueError("x must be one contiguous stream")
+    _, kind, scale, S = _stream.source(x, scale)
     nfft = int(nfft)
     hop = nfft // 2 if hop is None else int(hop)
     A = int(averages)
-    S = int(x.shape[0])
     R = out_rows(S, nfft, hop, A)
     w = _window_of(window, nfft, x.device)
     if not isinstance(w, torch.Tensor):
         w = torch.from_numpy(w).to(x.device)
     if out is None:
-        out = torch.empty((R, nfft), dtype=torch.float32, device=x.device)
+        out, stride = torch.empty((R, nfft), dtype=torch.float32, device=x.device), nfft
     else:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or out.device != x.device:
-            raise TypeError("out must be a two-dimensional float32 tensor on x's device")
-        if int(out.shape[0]) < R or int(out.shape[1]) < nfft or (out.shape[1] > 1 and out.stride(1) != 1) or \
-                (out.shape[0] > 1 and out.stride(0) < nfft):
-            raise ValueError(f"out must hold {R} contiguous rows of {nfft} bins")
-    stride = int(out.stride(0)) if int(out.shape[0]) > 1 else max(nfft, int(out.shape[1]))
+        holds = f"out must hold {R} contiguous rows of {nfft} bins"
+        _, _, stride = _stream.rows_of(out, torch.float32, "out", "bins", nfft, used=nfft, min_rows=R, device=x.device,
+                                       kind="out must be a two-dimensional float32 tensor on x's device", narrow=holds, layout=holds)
     _stream.launch(x, lambda lib, stream: lib.amcx_spectrogram(
-        x.data_ptr() if R else None, _formats.get(fmt).kind, S, scale, w.data_ptr(), nfft, hop, A,
-        out.data_ptr() if R else None, stride, R, stream))
+        x.data_ptr() if R else None, kind, S, scale, w.data_ptr(), nfft, hop, A, out.data_ptr() if R else None, stride, R, stream))
     return out[:R, :nfft]
 
 
-class Spectrogram:
+class Spectrogram(_stream.Chunked):
     """The spectrogram of a stream that arrives in chunks: ``push(chunk)`` returns the rows the chunk completes, float32
     ``(r, nfft)``, possibly none.  The rows are those of one :func:`spectrogram` call over the whole stream, bit for bit,
     wherever the chunks are cut: a row's bits depend on its own samples alone, so the class only has to keep the samples no
@@ -142,33 +130,35 @@ class Spectrogram:
     the next row begins.  ``compute(buf, nfft, hop=, averages=, window=, scale=)``: an injected numpy implementation (host
     tests); chunks are then numpy arrays."""
 
+    _NOUN = "spectrogram"
+
     def __init__(self, nfft: int, hop=None, averages: int = 1, window=None, fmt: str = "cf32", scale=None, compute=None):
-        if fmt not in _stream.FORMATS:
-            raise ValueError(f"fmt must be one of {_stream.FORMATS}, not {fmt!r}")
+        super().__init__(fmt, compute)
         self.nfft = int(nfft)
         self.hop = self.nfft // 2 if hop is None else int(hop)
         self.averages = int(averages)
         out_rows(0, self.nfft, self.hop, self.averages)                 # ValueError outside the kernel's limits
         self.window = _window_of(window, self.nfft)
-        self.fmt = fmt
         self.scale = _formats.scale_of(fmt, scale)
         self.row_samples = row_samples(self.nfft, self.hop, self.averages)
-        self.rows_done = 0
-        self._tail = None
-        self._skip = 0
-        self._compute = compute
         self._window_dev = None
 
     @property
-    def index(self) -> int:
-        return self.rows_done * self.averages * self.hop
+    def rows_done(self) -> int:
+        return self.index // (self.averages * self.hop)
 
     @property
     def held(self) -> int:
         """The samples that have arrived and belong to rows not yet complete."""
         return 0 if self._tail is None else int(self._tail.shape[0])
 
-    def _run(self, buf):
+    def _outputs(self, S: int) -> int:
+        return out_rows(S, self.nfft, self.hop, self.averages)
+
+    def _consumed(self, R: int) -> int:
+        return R * self.averages * self.hop                          # where the next row begins
+
+    def _run(self, buf, R):
         kw = dict(hop=self.hop, averages=self.averages, scale=self.scale)
         if self._compute is not None:
             return self._compute(buf, self.nfft, window=self.window, **kw)
@@ -177,58 +167,23 @@ class Spectrogram:
             self._window_dev = torch.from_numpy(self.window).to(buf.device)
         return spectrogram(buf, self.nfft, window=self._window_dev, **kw)
 
-    def push(self, chunk):
-        if _stream._format_of(chunk) != self.fmt:
-            raise TypeError(f"this spectrogram takes {self.fmt} chunks")
-        if self._skip:                                               # samples between two rows, never read
-            drop = min(self._skip, int(chunk.shape[0]))
-            chunk, self._skip = chunk[drop:], self._skip - drop
-        if self._tail is None or self._tail.shape[0] == 0:
-            buf = chunk
-        elif chunk.shape[0] == 0:
-            buf = self._tail
-        elif isinstance(chunk, np.ndarray):
-            buf = np.concatenate([self._tail, chunk])
-        else:
-            import torch
-            buf = torch.cat([self._tail, chunk])
-        S = int(buf.shape[0])
-        rows = self._run(buf)
-        R = int(rows.shape[0])
-        used = R * self.averages * self.hop                          # where the next row begins
-        self._skip += max(0, used - S)
-        tail = buf[min(used, S):]
-        self._tail = tail.copy() if isinstance(tail, np.ndarray) else tail.clone()
-        self.rows_done += R
-        return rows
-
 
 def detect(P, *, floor_quantile: float = 0.25, threshold_db: float = 6.0) -> Detection:
     """``P``: float32 ``(R, bins)`` on the GPU, contiguous rows at a row stride >= bins, 2 <= bins <= 4096 ->
     :class:`Detection` (the module's docstring says what the detector assumes): one launch of amcx_psd_detect_f32.  Rank and
-    threshold are :func:`amcpy_amd.occupancy.floor_rank_of` / ``threshold_of``'s.  ``snr_db = 10 log10(max(P / floor - 1,
-    tiny))`` is computed with torch: a label for the user, no part of the detection."""
+    threshold are :func:`amcpy_amd.occupancy.floor_rank_of` / ``threshold_of``'s.  ``snr_db`` is
+    :func:`amcpy_amd.occupancy.snr_db` of every cell over its row's floor, computed with torch: a label for the user, no part
+    of the detection."""
     import torch
 
-    if not isinstance(P, torch.Tensor) or P.dtype != torch.float32 or P.dim() != 2:
-        raise TypeError("P must be a float32 (R, bins) torch tensor")
-    if not P.is_cuda:
-        raise ValueError("P must live in GPU memory")
-    R, bins = int(P.shape[0]), int(P.shape[1])
-    if not 2 <= bins <= 4096:
-        raise ValueError(f"rows of 2 ... 4096 bins, got {bins}")
-    if P.stride(1) != 1 or (R > 1 and P.stride(0) < bins):
-        raise ValueError("P must have contiguous rows at a row stride >= bins")
-    stride = int(P.stride(0)) if R > 1 else bins
+    R, bins, stride = _stream.rows_of(P, torch.float32, "P", "bins", 2, 4096, narrow="rows of 2 ... 4096 bins, got {}")
     rank, thr = floor_rank_of(bins, floor_quantile), threshold_of(threshold_db)
     floor = torch.empty((R,), dtype=torch.float32, device=P.device)
     mask = torch.empty((R, bins), dtype=torch.uint8, device=P.device)
     _stream.launch(P, lambda lib, stream: lib.amcx_psd_detect_f32(
         P.data_ptr() if R else None, R, bins, stride, rank, float(thr), floor.data_ptr() if R else None,
         mask.data_ptr() if R else None, stream))
-    tiny = torch.finfo(torch.float32).tiny
-    snr_db = 10.0 * torch.log10(torch.clamp(P / floor[:, None] - 1.0, min=tiny))
-    return Detection(floor, mask.bool(), snr_db)
+    return Detection(floor, mask.bool(), snr_db(P, floor, 0))
 
 
 def bands(mask_row, min_bins: int = 2, merge_bins: int = 2) -> list:

@@ -198,45 +198,57 @@ def is_rational_tune(tune) -> bool:
     return isinstance(tune, ResolvedResample) or (isinstance(tune, dict) and ("resample" in tune or bool(tune.get("rational", False))))
 
 
+def _walk(rec, make, device, on_gpu: bool, chunk_samples: int, axis: int = 0, enough=None):
+    """The segment and chunk walk of every streaming path.  Each capture segment that has samples is memory-mapped and pushed
+    in chunks of ``chunk_samples`` -- as torch tensors on the device (``on_gpu``), or as the numpy arrays they are -- through
+    a streaming object that starts anew with the segment: ``make()``.  Yields ``(segment index, segment start, the outputs
+    of the pushes, the streaming object)``.  ``enough(have)``, where given, is asked before a segment (have = 0: true ends the
+    walk) and after every push (have: the outputs of this segment so far, counted along ``axis``; true ends the segment)."""
+    fmt = _formats.get(rec["sample_format"])                # of one stored sample, for the chunks
+    if on_gpu:
+        import torch                                       # the streaming paths alone: the untuned one stays torch-free
+        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    for j, (start, off, n_samples) in enumerate(rec["segments"]):
+        if enough is not None and enough(0):
+            break
+        if n_samples == 0:
+            continue
+        # (mode "c": private pages, never written -- torch.from_numpy wants a writable array, and "r+" would want a writable file)
+        src = np.memmap(rec["data_path"], dtype=fmt.plain, mode="c", offset=off, shape=(n_samples,) + fmt.tail)
+        obj = make()
+        ys, have = [], 0
+        for c0 in range(0, n_samples, chunk_samples):
+            chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
+            ys.append(obj.push(torch.from_numpy(chunk).to(dev) if on_gpu else chunk))
+            have += int(ys[-1].shape[axis])
+            if enough is not None and enough(have):
+                break
+        yield j, start, ys, obj
+
+
 def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, chunk_samples):
     """The tuned path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.ddc.Channelizer` -- or, a
     rational ``tune``, a :class:`amcpy_amd.resample.Resampler` -- in chunks."""
     from .ddc import Channelizer
+    fmt = rec["sample_format"]
     if is_rational_tune(tune):
         from .resample import Resampler
         shift, L, D, taps = resolve_resample(rec["meta"], tune)
+        make = lambda: Resampler(taps, L, D, shift, fmt, scale, compute=tune_compute)      # noqa: E731
     else:
         if isinstance(tune, dict) and tune.get("rational", True) is False:
             tune = {k: v for k, v in tune.items() if k != "rational"}
         shift, D, taps = resolve_tune(rec["meta"], tune)
         L = 1
-    fmt = rec["sample_format"]
-    plain, tail = _formats.get(fmt).plain, _formats.get(fmt).tail      # of one stored sample, for the chunks
+        make = lambda: Channelizer(taps, D, shift, fmt, scale, compute=tune_compute)       # noqa: E731
     on_gpu = tune_compute is None
     if on_gpu:
-        import torch                                       # this path alone: the untuned one stays torch-free
+        import torch
         from .features import features18
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
     parts, starts = [], []
-    for start, off, n_samples in rec["segments"]:
-        if left is not None and left <= 0:
-            break
-        if n_samples == 0:
-            continue
-        # (mode "c": private pages, never written -- torch.from_numpy wants a writable array, and "r+" would want a writable file)
-        src = np.memmap(rec["data_path"], dtype=plain, mode="c", offset=off, shape=(n_samples,) + tail)
-        if is_rational_tune(tune):
-            chan = Resampler(taps, L, D, shift, fmt, scale, compute=tune_compute)
-        else:
-            chan = Channelizer(taps, D, shift, fmt, scale, compute=tune_compute)
-        ys, have = [], 0
-        for c0 in range(0, n_samples, chunk_samples):
-            chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
-            y = chan.push(torch.from_numpy(chunk).to(dev) if on_gpu else chunk)
-            ys.append(y)
-            have += int(y.shape[0])
-            if left is not None and have >= left * N:
-                break
+    for _, start, ys, _ in _walk(rec, make, device, on_gpu, chunk_samples,
+                                 enough=lambda have: left is not None and have >= left * N):
+        have = sum(int(y.shape[0]) for y in ys)
         n = have // N if left is None else min(have // N, left)
         if n == 0:
             continue
@@ -289,26 +301,12 @@ def _walk_channelized(rec, N, channelize, device, scale, left, bank_compute, chu
     from .bank import FilterBank
     shift, C, D, taps = resolve_channelize(rec["meta"], channelize)
     fmt = rec["sample_format"]
-    plain, tail = _formats.get(fmt).plain, _formats.get(fmt).tail      # of one stored sample, for the chunks
     on_gpu = bank_compute is None
     if on_gpu:
-        import torch                                       # this path alone: the untuned one stays torch-free
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
-    for start, off, n_samples in rec["segments"]:
-        if left is not None and left <= 0:
-            break
-        if n_samples == 0:
-            continue
-        src = np.memmap(rec["data_path"], dtype=plain, mode="c", offset=off, shape=(n_samples,) + tail)
-        bank = FilterBank(taps, C, D, shift, fmt, scale, compute=bank_compute)
-        ys, have = [], 0
-        for c0 in range(0, n_samples, chunk_samples):
-            chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
-            y = bank.push(torch.from_numpy(chunk).to(dev) if on_gpu else chunk)
-            ys.append(y)
-            have += int(y.shape[1])
-            if left is not None and have >= left * N:
-                break
+        import torch
+    for _, start, ys, _ in _walk(rec, lambda: FilterBank(taps, C, D, shift, fmt, scale, compute=bank_compute), device, on_gpu,
+                                 chunk_samples, axis=1, enough=lambda have: left is not None and have >= left * N):
+        have = sum(int(y.shape[1]) for y in ys)
         n = have // N if left is None else min(have // N, left)
         if n == 0:
             continue
@@ -355,17 +353,12 @@ def _survey_segment_gpu(frames, C, n, rank_q, thr_db, detect, model, cols, mean,
             from .classifier import classify
             labels = classify(feats, model, cols=cols, mean=mean, scale=scale_).reshape(C, n)
     else:
-        feats = torch.full((C * n, 18), float("nan"), dtype=torch.float32, device=frames.device)
+        feats, at, packed = occupancy._features_at(frames, occ.rows, feature_ids)
         if model is not None:
             labels = torch.full((C * n,), -2, dtype=torch.int32, device=frames.device)
-        if int(occ.rows.shape[0]) > 0:
-            at = occ.rows.long()
-            packed = features18(occupancy.gather_rows(frames, occ.rows), feature_ids=feature_ids).reshape(-1, 18)
-            feats[at] = packed
-            if model is not None:
+            if at is not None:
                 from .classifier import classify
                 labels[at] = classify(packed, model, cols=cols, mean=mean, scale=scale_).reshape(-1)
-        if labels is not None:
             labels = labels.view(C, n)
     host = lambda t: None if t is None else t.cpu().numpy()      # noqa: E731
     return (host(feats.view(C, n, 18)), host(power), host(occ.floor), host(occ.mask), host(occ.snr_db), host(labels))
@@ -373,10 +366,9 @@ def _survey_segment_gpu(frames, C, n, rank_q, thr_db, detect, model, cols, mean,
 
 def _survey_segment_injected(frames, C, n, rank, thr, detect, model, compute, occupancy_compute):
     """The same over numpy with injected computes (tests)."""
+    from .occupancy import snr_db
     power, floor, mask = occupancy_compute(frames, C, n, rank, thr)
     power, floor, mask = np.asarray(power, np.float32).reshape(C, n), np.asarray(floor, np.float32), np.asarray(mask, bool).reshape(C, n)
-    with np.errstate(all="ignore"):
-        snr_db = (10.0 * np.log10(np.maximum(power / floor[None, :] - np.float32(1.0), np.finfo(np.float32).tiny))).astype(np.float32)
     rows = np.flatnonzero(mask.reshape(-1)) if detect is not None else np.arange(C * n)
     feats = np.full((C * n, 18), np.nan, dtype=np.float32)
     labels = None if model is None else np.full((C * n,), -2, dtype=np.int32)
@@ -385,7 +377,7 @@ def _survey_segment_injected(frames, C, n, rank, thr, detect, model, compute, oc
         feats[rows] = got
         if model is not None:
             labels[rows] = np.asarray(model(got), dtype=np.int32).reshape(-1)
-    return feats.reshape(C, n, 18), power, floor, mask, snr_db, None if labels is None else labels.reshape(C, n)
+    return feats.reshape(C, n, 18), power, floor, mask, snr_db(power, floor, 1), None if labels is None else labels.reshape(C, n)
 
 
 def survey_sigmf(path, frame_size: int, *, channelize, detect=None, model=None, cols=None, mean=None, scale=None,
@@ -500,6 +492,48 @@ def raw_recording(path, sample_format: str) -> dict:
             "segments": [(0, 0, data_path.stat().st_size // fmt.store.itemsize)]}
 
 
+def _scan_detect(P, opt, rank: int, thr, detect_compute) -> tuple:
+    """The detection of one capture's rows ``P`` -- on the device, or injected over numpy -> ``(floor, mask, snr_db)`` as numpy."""
+    from . import occupancy, psd
+    if detect_compute is None:
+        det = psd.detect(P, floor_quantile=float(opt["floor_quantile"]), threshold_db=float(opt["threshold_db"]))
+        return det.floor.cpu().numpy(), det.mask.cpu().numpy(), det.snr_db.cpu().numpy()
+    floor, mask = detect_compute(P, rank, thr)
+    floor, mask = np.asarray(floor, dtype=np.float32), np.asarray(mask).astype(bool)
+    return floor, mask, occupancy.snr_db(np.asarray(P, np.float32), floor, 0)
+
+
+def _scan_emitters(mask, snr, row_start, span: int, first_row: int, fs: float, fc: float, opt) -> list:
+    """The emitters of one capture as :func:`scan_sigmf`'s dicts: ``row_start`` the first sample of each of its rows, ``span``
+    the samples a row covers, ``first_row`` its first row in the whole recording's ``psd``; ``fs`` and ``fc`` scale and offset the
+    bin edges."""
+    from . import psd
+    nfft = int(mask.shape[1])
+    found = []
+    for r0, r1, lo, hi in psd.emitters(mask, int(opt["min_bins"]), int(opt["merge_bins"]), int(opt["min_rows"])):
+        cols = np.arange(lo, hi + 1) % nfft
+        cells = mask[r0:r1 + 1][:, cols]
+        found.append({"sample_start": int(row_start[r0]), "sample_count": int(row_start[r1] - row_start[r0]) + span,
+                      "freq_lower_edge": fc + fs * (lo - 0.5) / nfft, "freq_upper_edge": fc + fs * (hi + 0.5) / nfft,
+                      "snr_db": float(np.mean(snr[r0:r1 + 1][:, cols][cells])),
+                      "rows": (first_row + r0, first_row + r1), "bins": (lo, hi)})
+    return found
+
+
+def _scan_result(nfft: int, span: int, parts, starts, freq_hz, detected, found) -> dict:
+    """:func:`scan_sigmf`'s dict from the captures' pieces: ``detected`` is None, or the captures' ``(floor, mask, snr_db)``."""
+    out = {"psd": np.concatenate(parts) if parts else np.empty((0, nfft), np.float32),
+           "row_start": np.concatenate(starts) if starts else np.empty((0,), np.int64), "row_samples": span}
+    if freq_hz is not None:
+        out["freq_hz"] = freq_hz
+    if detected is not None:
+        none = (np.empty((0,), np.float32), np.zeros((0, nfft), bool), np.empty((0, nfft), np.float32))
+        for k, key in enumerate(("floor", "occupied", "snr_db")):
+            out[key] = np.concatenate([d[k] for d in detected]) if detected else none[k]
+        out["emitters"] = found
+    return out
+
+
 def scan_recording(rec: dict, *, nfft: int = 1024, hop=None, averages: int = 16, window="hann", detect=None,
                    device: Optional[int] = None, scale_samples=None, chunk_samples: int = 1 << 24, psd_compute=None,
                    detect_compute=None) -> dict:
@@ -518,66 +552,29 @@ def scan_recording(rec: dict, *, nfft: int = 1024, hop=None, averages: int = 16,
     win = psd._window_of(window, nfft)
     span, step = psd.row_samples(nfft, hop, A), A * hop
     rank, thr = occupancy.floor_rank_of(nfft, float(opt["floor_quantile"])), occupancy.threshold_of(float(opt["threshold_db"]))
-    plain, tail = _formats.get(fmt).plain, _formats.get(fmt).tail
     on_gpu = psd_compute is None
     if on_gpu:
         import torch
-        dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
-    glob = rec["meta"].get("global") or {}
-    rate = glob.get("core:sample_rate")
+    rate = (rec["meta"].get("global") or {}).get("core:sample_rate")
     captures = rec["meta"].get("captures") or [{}]
-    tiny = float(np.finfo(np.float32).tiny)
-    chunk_samples = max(1, int(chunk_samples))
-    parts, starts, floors, masks, snrs, found = [], [], [], [], [], []
+    parts, starts, detected, found = [], [], [], []
     n_rows = 0
-    for j, (start, off, n_samples) in enumerate(rec["segments"]):
-        if n_samples == 0:
-            continue
-        src = np.memmap(rec["data_path"], dtype=plain, mode="c", offset=off, shape=(n_samples,) + tail)
-        sp = psd.Spectrogram(nfft, hop, A, win, fmt, scale, compute=psd_compute)
-        rows = []
-        for c0 in range(0, n_samples, chunk_samples):
-            chunk = np.ascontiguousarray(src[c0:c0 + chunk_samples])
-            rows.append(sp.push(torch.from_numpy(chunk).to(dev) if on_gpu else chunk))
+    for j, start, rows, sp in _walk(rec, lambda: psd.Spectrogram(nfft, hop, A, win, fmt, scale, compute=psd_compute), device, on_gpu,
+                                    max(1, int(chunk_samples))):
         R = sp.rows_done
         if R == 0:
             continue
         P = torch.cat(rows) if on_gpu else np.concatenate(rows)
         row_start = start + step * np.arange(R, dtype=np.int64)
         if detect is not None:
-            if on_gpu:
-                det = psd.detect(P, floor_quantile=float(opt["floor_quantile"]), threshold_db=float(opt["threshold_db"]))
-                floor, mask, snr = det.floor.cpu().numpy(), det.mask.cpu().numpy(), det.snr_db.cpu().numpy()
-            else:
-                floor, mask = detect_compute(P, rank, thr)
-                floor, mask = np.asarray(floor, dtype=np.float32), np.asarray(mask).astype(bool)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    snr = (10.0 * np.log10(np.maximum(np.asarray(P, np.float32) / floor[:, None] - np.float32(1.0), tiny))).astype(np.float32)
-            fs = float(rate) if rate else 1.0
+            detected.append(_scan_detect(P, opt, rank, thr, detect_compute))
             fc = float(captures[j].get("core:frequency", 0.0)) if rate and j < len(captures) else 0.0
-            for r0, r1, lo, hi in psd.emitters(mask, int(opt["min_bins"]), int(opt["merge_bins"]), int(opt["min_rows"])):
-                cols = np.arange(lo, hi + 1) % nfft
-                cells = mask[r0:r1 + 1][:, cols]
-                found.append({"sample_start": int(row_start[r0]), "sample_count": int(row_start[r1] - row_start[r0]) + span,
-                              "freq_lower_edge": fc + fs * (lo - 0.5) / nfft, "freq_upper_edge": fc + fs * (hi + 0.5) / nfft,
-                              "snr_db": float(np.mean(snr[r0:r1 + 1][:, cols][cells])),
-                              "rows": (n_rows + r0, n_rows + r1), "bins": (lo, hi)})
-            floors.append(floor)
-            masks.append(mask)
-            snrs.append(snr)
+            found += _scan_emitters(detected[-1][1], detected[-1][2], row_start, span, n_rows, float(rate) if rate else 1.0, fc, opt)
         parts.append(P.cpu().numpy() if on_gpu else np.asarray(P, dtype=np.float32))
         starts.append(row_start)
         n_rows += R
-    out = {"psd": np.concatenate(parts) if parts else np.empty((0, nfft), np.float32),
-           "row_start": np.concatenate(starts) if starts else np.empty((0,), np.int64), "row_samples": span}
-    if rate:
-        out["freq_hz"] = psd.bin_frequencies(nfft, float(rate), float(captures[0].get("core:frequency", 0.0)))
-    if detect is not None:
-        out["floor"] = np.concatenate(floors) if floors else np.empty((0,), np.float32)
-        out["occupied"] = np.concatenate(masks) if masks else np.zeros((0, nfft), bool)
-        out["snr_db"] = np.concatenate(snrs) if snrs else np.empty((0, nfft), np.float32)
-        out["emitters"] = found
-    return out
+    freq_hz = psd.bin_frequencies(nfft, float(rate), float(captures[0].get("core:frequency", 0.0))) if rate else None
+    return _scan_result(nfft, span, parts, starts, freq_hz, None if detect is None else detected, found)
 
 
 def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, feature_ids=None, scale=None,

@@ -22,17 +22,14 @@ plus the reference's own rounding (float64 FFT: far below u).  ``bound`` evaluat
 """
 import numpy as np
 
+from amcpy_amd import _formats
+from tests import ddc_ref
+from tests.bank_ref import log2_exact
+
 U = 2.0 ** -24
 K_STAGE = 6.0           # 1 (add) + 2 sqrt 2 (product) + TW, rounded up
 TW_UNITS = 2.0          # |stored twiddle - exact| <= TW_UNITS * u, asserted by tests/test_psd_host.py over the whole table
-FORMATS = {"cf32": np.complex64, "sc16": np.int16, "ci8": np.int8, "cu8": np.uint8}
-DEFAULT_SCALE = {"cf32": 1.0, "sc16": 2.0 ** -15, "ci8": 2.0 ** -7, "cu8": 2.0 ** -7}
-
-
-def log2_exact(n: int) -> int:
-    lg = int(n).bit_length() - 1
-    assert n >= 1 and (1 << lg) == n, n
-    return lg
+FORMATS, DEFAULT_SCALE = _formats._NUMPY, _formats._DEFAULT_SCALE          # by format name: a component's numpy type, the scale
 
 
 def out_rows(S: int, nfft: int, hop: int, A: int) -> int:
@@ -44,15 +41,6 @@ def out_rows_brute(S: int, nfft: int, hop: int, A: int) -> int:
     while s + nfft <= S:
         nseg, s = nseg + 1, s + hop
     return nseg // A
-
-
-def widen(raw, fmt: str, scale=None) -> np.ndarray:
-    """What the library makes of stored samples: complex64 as it is; integers as (float32)(integer - zero) * float32(scale)."""
-    if fmt == "cf32":
-        return np.asarray(raw, dtype=np.complex64)
-    s = np.float32(DEFAULT_SCALE[fmt] if scale is None else scale)
-    v = np.asarray(raw).astype(np.int32) - (128 if fmt == "cu8" else 0)
-    return ((v[..., 0].astype(np.float32) * s) + 1j * (v[..., 1].astype(np.float32) * s)).astype(np.complex64)
 
 
 def _segments(x, nfft, hop, A, R):
@@ -190,7 +178,8 @@ def numpy_psd(x, nfft, *, hop=None, averages=1, window=None, scale=None):
     fmt = _formats.by_plain(x.dtype).name
     hop = nfft // 2 if hop is None else hop
     w = psd.window(nfft, window or "hann") if window is None or isinstance(window, str) else np.asarray(window, np.float32)
-    return reference(widen(x, fmt, scale), w, nfft, hop, averages).astype(np.float32)
+    wide = ddc_ref.widen(x, fmt, _formats.scale_of(fmt, scale)).astype(np.complex64)
+    return reference(wide, w, nfft, hop, averages).astype(np.float32)
 
 
 def numpy_psd_detect(P, floor_rank: int, threshold):
@@ -255,7 +244,7 @@ def write_recording(tmp_path, x, datatype: str, name: str = "band", sample_rate=
         fmt, top = ("sc16", 32000.0) if datatype == "ci16_le" else ("ci8", 120.0)
         peak = float(max(np.abs(x.real).max(), np.abs(x.imag).max()))
         q = np.round(np.stack([x.real, x.imag], axis=-1) * (top / peak)).astype(FORMATS[fmt])
-        blob, held = q.tobytes(), widen(q, fmt)
+        blob, held = q.tobytes(), ddc_ref.widen(q, fmt, DEFAULT_SCALE[fmt]).astype(np.complex64)
     Path(str(stem) + ".sigmf-data").write_bytes(blob)
     glob = {"core:datatype": datatype, "core:version": "1.0.0"}
     if sample_rate is not None:

@@ -1,6 +1,7 @@
 """The input streams of the down-converter, filter-bank and resampler tests: random samples of every format over its whole
 range, made once per (format, length, seed) and never written to.  ``base`` is the constant that keeps the test modules'
 streams apart (tests/test_formats_host.py holds digests of what each module has always seen)."""
+import ctypes
 import functools
 
 import numpy as np
@@ -13,6 +14,13 @@ def torch():
     import torch
     assert torch.cuda.is_available(), "these tests need the GPU"
     return torch
+
+
+def aligned(n_floats=256):
+    """``(buffer, address)``: host memory for the refusal tests of the C entries, the address aligned to 16 bytes; keep the buffer"""
+    buf = (ctypes.c_float * n_floats)()
+    p = ctypes.addressof(buf)
+    return buf, p + (-p % 16)
 
 
 def stream(fmt, n, rng):

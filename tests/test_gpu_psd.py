@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from amcpy_amd import _lib, occupancy, psd
-from tests import psd_ref as ref
+from tests import ddc_ref, psd_ref as ref
 
 pytestmark = pytest.mark.gpu
 
@@ -127,7 +127,7 @@ def test_formats_are_the_complex64_bits_at_every_16_byte_phase(nfft):
         for fmt in ("cf32",) + INT_FORMATS:
             raw = _noise(S, nfft + hop) if fmt == "cf32" else _raw(S, fmt, nfft + hop)
             scale = None if fmt == "cf32" else ref.DEFAULT_SCALE[fmt] * 1.25
-            wide = ref.widen(raw, fmt, scale)
+            wide = ddc_ref.widen(raw, fmt, scale).astype(np.complex64)
             base = _run(wide, nfft, hop=hop, averages=A, window=w)
             assert ref.worst_fraction(base, wide, w, nfft, hop, A) <= 1.0
             for off in (0, 1, 2, 3, 5):

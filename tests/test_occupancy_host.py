@@ -2,7 +2,6 @@
 states, the workspace size, the exact numpy detection (tests/occupancy_ref.py) against a brute-force sort, the segments, the
 survey of a synthetic SigMF recording over injected numpy computes, the command line's flags and the annotation round trip.
 Needs no GPU."""
-import ctypes as C
 import json
 from pathlib import Path
 
@@ -11,6 +10,7 @@ import pytest
 
 from amcpy_amd import _lib, occupancy
 from tests import bank_ref, occupancy_ref as ref
+from tests.stream_inputs import aligned as _aligned
 
 REPO = Path(__file__).resolve().parents[1]
 NEW = ["amcx_row_power_c64", "amcx_occupancy_workspace_bytes", "amcx_occupancy_detect_f32", "amcx_gather_rows_c64",
@@ -54,12 +54,6 @@ def test_abi_14_symbols_exist_and_bind():
     assert "ONLY IN A" not in listing
 
 
-def _aligned(n_floats=256):
-    buf = (C.c_float * n_floats)()
-    p = C.addressof(buf)
-    return buf, p + (-p % 16)
-
-
 def test_row_power_refusals_in_the_documented_order_without_a_device():
     f = _lib.load().amcx_row_power_c64
     keep, p = _aligned()
@@ -72,9 +66,9 @@ def test_row_power_refusals_in_the_documented_order_without_a_device():
     for kw in (dict(R=-1), dict(N=1), dict(N=0), dict(N=32769), dict(N=-5)):
         assert call(**kw) == _lib.EINVAL and call(**{"R": 0, **kw}, **nul) == _lib.EINVAL, kw
     # 2. the stride
-    for kw in (dict(stride=7), dict(stride=0), dict(stride=-8), dict(R=1 << 40, stride=1 << 40)):
+    for kw in (dict(stride=7), dict(stride=0), dict(stride=-8), dict(R=1 << 40, stride=1 << 40), dict(R=1 << 2, stride=(1 << 56) + 1)):
         assert call(**kw) == _lib.EINVAL, kw
-    assert call(R=0, stride=7, **nul) == _lib.EINVAL
+    assert call(R=0, stride=7, **nul) == _lib.EINVAL and call(R=0, stride=-8, **nul) == _lib.EINVAL
     # 3. nothing to do
     assert call(R=0, **nul) == _lib.OK and call(R=0, N=32768, stride=1 << 50, **nul) == _lib.OK
     # 4. null pointers and alignment
@@ -121,6 +115,12 @@ def test_gather_refusals_in_the_documented_order_without_a_device():
         assert call(**kw) == _lib.EINVAL and call(**{"n": 0, **kw}, **nul) == _lib.EINVAL, kw
     for kw in (dict(stride=7), dict(dstride=7), dict(dstride=0)):
         assert call(**kw) == _lib.EINVAL and call(n=0, **kw, **nul) == _lib.EINVAL, kw
+    # the row gate on either side: a stride of 0, a negative one, and one whose product with the row count passes 2^58
+    for kw in (dict(stride=0), dict(stride=-8), dict(dstride=-8), dict(R=1 << 40, stride=1 << 40), dict(n=1 << 40, dstride=1 << 40),
+               dict(R=1 << 2, stride=(1 << 56) + 1), dict(n=1 << 2, dstride=(1 << 56) + 1)):
+        assert call(**kw) == _lib.EINVAL, kw
+    assert call(n=0, stride=0, **nul) == _lib.EINVAL and call(n=0, R=1 << 40, stride=1 << 40, **nul) == _lib.EINVAL
+    assert call(n=0, dstride=1 << 60, **nul) == _lib.OK                      # no destination row, no product
     assert call(n=0, **nul) == _lib.OK and call(n=0, R=0, **nul) == _lib.OK
     for kw in (dict(src=None), dict(index=None), dict(dst=None), dict(src=p + 4), dict(index=p + 2), dict(dst=p + 4)):
         assert call(**kw) == _lib.EINVAL, kw

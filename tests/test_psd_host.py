@@ -2,7 +2,6 @@
 checks in the order the header states, the row count, the numpy restatement of the kernel's operation sequence against the
 float64 definition, the streaming class over ragged cuts, bands and emitters on hand-made masks, and the scan of a synthetic
 two-capture SigMF recording over injected numpy computes with the annotation round trip.  Needs no GPU."""
-import ctypes as C
 import json
 import subprocess
 import sys
@@ -13,6 +12,7 @@ import pytest
 
 from amcpy_amd import _lib, occupancy, psd
 from tests import psd_ref as ref
+from tests.stream_inputs import aligned as _aligned
 
 REPO = Path(__file__).resolve().parents[1]
 NEW = ["amcx_spectrogram_out_rows", "amcx_spectrogram", "amcx_spectrogram_plan", "amcx_psd_detect_f32", "amcx_kernel_name_psd",
@@ -62,12 +62,6 @@ def test_abi_15_symbols_exist_and_bind():
         assert segs == 4096 // nfft and 0 < lds < 65536 and grid >= 1
     with pytest.raises(ValueError):
         _lib.spectrogram_plan(96, 48, 1)
-
-
-def _aligned(n_floats=256):
-    buf = (C.c_float * n_floats)()
-    p = C.addressof(buf)
-    return buf, p + (-p % 16)
 
 
 def test_spectrogram_refusals_in_the_documented_order_without_a_device():
