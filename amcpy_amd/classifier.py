@@ -255,18 +255,15 @@ def classify(feats, model: MlpModel, *, cols: Sequence[int], mean=None, scale=No
 
     One C-ABI call on the current stream; nothing is allocated inside it."""
     import torch
-    from .postprocess import _as_rows
+    from . import _stream
+    from .postprocess import _as_rows, select_cols
     _lib.require_torch_runtime()
     feats = _as_rows(feats)
     want = tuple(want)
     if not want or any(w not in _OUTPUTS for w in want) or len(set(want)) != len(want):
         raise ValueError(f"want: a non-empty selection of {_OUTPUTS}")
     lead, R, Cc = feats.shape[:-2], feats.shape[-2], feats.shape[-1]
-    cols = [int(c) for c in cols]
-    if any(c < 0 or c >= Cc for c in cols):
-        raise IndexError("column index out of range")
-    if not cols or len(cols) > MAX_WIDTH or Cc > MAX_WIDTH:
-        raise ValueError("between 1 and 32 columns")
+    cols = select_cols(cols, Cc)
     if len(cols) != model.n_inputs:
         raise ValueError(f"the model takes {model.n_inputs} inputs, {len(cols)} columns were selected")
     if (mean is None) != (scale is None):
@@ -284,23 +281,22 @@ def classify(feats, model: MlpModel, *, cols: Sequence[int], mean=None, scale=No
     if "counts" in want and (rows_per_group < 1 or n_rows % rows_per_group):
         raise ValueError(f"rows_per_group {rows_per_group} does not cut {n_rows} rows into whole groups")
     n_cls = model.n_classes
-    labels = torch.empty((n_rows,), dtype=torch.int32, device=dev) if "labels" in want else None
-    probs = torch.empty((n_rows, n_cls), dtype=torch.float32, device=dev) if "probs" in want else None
+    # (the entry's n_rows labels and packed rows of probabilities, in the shapes returned)
+    labels = torch.empty(lead + (R,), dtype=torch.int32, device=dev) if "labels" in want else None
+    probs = torch.empty(lead + (R, n_cls), dtype=torch.float32, device=dev) if "probs" in want else None
     n_groups = n_rows // rows_per_group if "counts" in want else 0
     counts = torch.empty((n_groups, n_cls + 1), dtype=torch.int64, device=dev) if "counts" in want else None
     params = model.device_params(dev)
     cols_c = (ctypes.c_int32 * len(cols))(*cols)
     widths_c = (ctypes.c_int32 * len(model.widths))(*model.widths)
     ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().amcx_mlp_classify_f32(
-            flat.data_ptr(), n_rows, flat.stride(0) if n_rows > 1 else max(Cc, 1), Cc, cols_c, len(cols), ptr(mean), ptr(scale),
-            params.data_ptr(), widths_c, model.n_linear, _lib.ACTIVATIONS[model.activation], ptr(labels), ptr(probs),
-            n_cls, rows_per_group if counts is not None else 0, ptr(counts), torch.cuda.current_stream(dev).cuda_stream))
-    out = {"labels": None if labels is None else labels.reshape(lead + (R,)),
-           "probs": None if probs is None else probs.reshape(lead + (R, n_cls)),
-           "counts": None if counts is None else (counts.reshape(lead + (n_cls + 1,))
-                                                  if rows_per_group == R and feats.dim() > 2 else counts)}
+    stride = flat.stride(0) if n_rows > 1 else Cc           # one row has no stride of its own (_stream.rows_of)
+    _stream.launch(flat, lambda lib, stream: lib.amcx_mlp_classify_f32(
+        flat.data_ptr(), n_rows, stride, Cc, cols_c, len(cols), ptr(mean), ptr(scale), params.data_ptr(), widths_c, model.n_linear,
+        _lib.ACTIVATIONS[model.activation], ptr(labels), ptr(probs), n_cls, rows_per_group if counts is not None else 0,
+        ptr(counts), stream))
+    out = {"labels": labels, "probs": probs,
+           "counts": counts.reshape(lead + (n_cls + 1,)) if counts is not None and rows_per_group == R and feats.dim() > 2 else counts}
     res = tuple(out[w] for w in want)
     return res[0] if len(res) == 1 else res
 
@@ -311,9 +307,8 @@ def classify_frames(iq, model: MlpModel, *, cols: Sequence[int], mean, scale, fr
     stand for (``c + 1``: the cheapest plan kernel that yields them, none of the reference's six needs the FFT), then
     :func:`classify`, both on the current stream; the feature matrix never leaves the device."""
     from .features import features18
-    cols = [int(c) for c in cols]
-    if any(c < 0 or c >= _lib.NUM_FEATURES for c in cols):
-        raise IndexError("column index out of range")
+    from .postprocess import select_cols
+    cols = select_cols(cols, _lib.NUM_FEATURES)
     feats = features18(iq, frame_size=frame_size, variant=variant, feature_ids=[c + 1 for c in cols])
     if feats.dim() == 1:
         feats = feats.reshape(1, -1)

@@ -252,6 +252,13 @@ bool sc16_typed(int32_t N, int v) {
   [[clang::noinline]] return v == AMCX_VARIANT_WAVE && amcx::has_sc16_kernels(N);
 }
 
+// The end of a call that ran on a workspace of its own from the stream-ordered allocator (here and amcx_group_stats_f32):
+// freed in stream order whatever the call said, and the first failure is the one reported.
+int free_own_ws(void* ws, hipStream_t st, int rc) {
+  const hipError_t fe = hipFreeAsync(ws, st);
+  return rc != AMCX_OK || fe == hipSuccess ? rc : hip_fail(fe, "hipFreeAsync(ws, st)");
+}
+
 // The any-size path above 8192 samples runs its FFT form through a workspace from the stream-ordered allocator
 // (as amcx_group_stats_f32 does) -- unless the stream is being captured into a graph, or the allocator has nothing:
 // then the DFT by its definition, which needs none (amcx_stream_kernel.h).  Everything else allocates nothing.
@@ -278,11 +285,7 @@ int launch_block_own_ws(const amcx::Frames& a, int32_t N) {
               cap != hipStreamCaptureStatusNone ? "the stream is being captured" : "hipMallocAsync had no workspace", (long long)want);
   }
   const int rc = launch_block(a, N, ws, ws != nullptr ? want : 0);
-  if (ws != nullptr) {
-    const hipError_t fe = hipFreeAsync(ws, st);
-    if (rc == AMCX_OK) AMCX_HIP(fe);
-  }
-  return rc;
+  return ws != nullptr ? free_own_ws(ws, st, rc) : rc;
 }
 
 // where the any-size path's workspace comes from: the caller's (or none), or launch_block_own_ws
@@ -440,7 +443,8 @@ hipError_t launch_iq8_widen(const void* src, int64_t n_frames, int32_t N, int64_
 
 namespace {
 
-// how a statistics call is cut: chunks per group and rows per chunk (whole tiles)
+// how a statistics call is cut: chunks per group and rows per chunk (whole tiles).  n_groups >= 1; chunks <= want, so the
+// grid n_groups * chunks stays below n_groups + 1024: a 32-bit count for every n_groups stats_args_ok lets through
 void stats_plan(int64_t n_groups, int64_t rows_per_group, int n_cols, int64_t* chunks, int64_t* rows_per_chunk) {
   const int64_t tile = amcx::stat_tile_rows(n_cols);
   const int64_t tiles = (rows_per_group + tile - 1) / tile;
@@ -568,6 +572,26 @@ bool make_select_cols(const int32_t* cols_host, int32_t n_sel, int32_t n_cols, a
     sel->c[j] = cols_host[j];
   }
   return true;
+}
+
+// the two launches of a statistics call, behind its entry's gate: a chunk's triple per workgroup into `ws`, then the pooling
+int launch_stats(const float* x_dev, int64_t n_groups, int64_t rows_per_group, int64_t row_stride, int32_t n_cols, double* mean_dev,
+                 double* std_dev, void* ws, hipStream_t st) {
+  int64_t chunks, rpc;
+  stats_plan(n_groups, rows_per_group, n_cols, &chunks, &rpc);
+  double* const part = static_cast<double*>(ws);
+  hipError_t e = amcx::launch(amcx::amcx_stats_part_kernel, n_groups * chunks, amcx::kStatThreads, 0, st, x_dev, rows_per_group,
+                              row_stride, n_cols, rpc, chunks, part);
+  if (e != hipSuccess) return hip_fail(e, "statistics chunk kernel launch");
+  // one small workgroup per (column, group); groups beyond the grid's y limit go in slices
+  const int pool_threads = chunks > 128 ? 256 : chunks > 64 ? 128 : 64;
+  for (int64_t g0 = 0; g0 < n_groups; g0 += 65535) {
+    const int64_t ng = n_groups - g0 < 65535 ? n_groups - g0 : 65535;
+    e = amcx::launch(amcx::amcx_stats_combine_kernel, dim3((unsigned)n_cols, (unsigned)ng), pool_threads, 0, st,
+                     part + g0 * n_cols * 3 * chunks, chunks, n_cols, mean_dev + g0 * n_cols, std_dev + g0 * n_cols);
+    if (e != hipSuccess) return hip_fail(e, "statistics pooling kernel launch");
+  }
+  return AMCX_OK;
 }
 
 }  // namespace
@@ -1272,28 +1296,11 @@ int amcx_group_stats_ws_f32(const float* x_dev, int64_t n_groups, int64_t rows_p
                             int64_t row_stride, int32_t n_cols, double* mean_dev, double* std_dev,
                             void* workspace_dev, int64_t workspace_bytes, void* hip_stream) {
   if (!stats_args_ok(n_groups, rows_per_group, row_stride, n_cols)) return AMCX_EINVAL;
+  if (n_groups > 0 && workspace_bytes < amcx_group_stats_workspace_bytes(n_groups, rows_per_group, n_cols)) return AMCX_EINVAL;
   if (n_groups == 0) return AMCX_OK;
-  if (x_dev == nullptr || mean_dev == nullptr || std_dev == nullptr || workspace_dev == nullptr) return AMCX_EINVAL;
-  if (on_another_device(x_dev) || on_another_device(workspace_dev)) return AMCX_EINVAL;
-  int64_t chunks, rpc;
-  stats_plan(n_groups, rows_per_group, n_cols, &chunks, &rpc);
-  if (workspace_bytes < n_groups * chunks * n_cols * 3 * (int64_t)sizeof(double)) return AMCX_EINVAL;
-  if (n_groups * chunks > 0x7fffffffLL) return AMCX_EINVAL;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  double* part = static_cast<double*>(workspace_dev);
-  hipLaunchKernelGGL(amcx::amcx_stats_part_kernel, dim3((unsigned)(n_groups * chunks)),
-                     dim3(amcx::kStatThreads), 0, st, x_dev, (long long)rows_per_group,
-                     (long long)row_stride, (int)n_cols, (long long)rpc, (int)chunks, part);
-  // the pooling launch: one small workgroup per (column, group); groups beyond the grid's y limit go in slices
-  const unsigned pool_threads = chunks > 128 ? 256u : chunks > 64 ? 128u : 64u;
-  for (int64_t g0 = 0; g0 < n_groups; g0 += 65535) {
-    const int64_t ng = n_groups - g0 < 65535 ? n_groups - g0 : 65535;
-    hipLaunchKernelGGL(amcx::amcx_stats_combine_kernel, dim3((unsigned)n_cols, (unsigned)ng), dim3(pool_threads), 0, st,
-                       part + g0 * n_cols * 3 * chunks, (int)chunks, (int)n_cols, mean_dev + g0 * n_cols,
-                       std_dev + g0 * n_cols);
-  }
-  AMCX_HIP(hipGetLastError());
-  return AMCX_OK;
+  if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, true}, {std_dev, 7u, true}, {workspace_dev, 7u, true}})) return AMCX_EINVAL;
+  return launch_stats(x_dev, n_groups, rows_per_group, row_stride, n_cols, mean_dev, std_dev, workspace_dev,
+                      static_cast<hipStream_t>(hip_stream));
 }
 
 int amcx_group_stats_f32(const float* x_dev, int64_t n_groups, int64_t rows_per_group,
@@ -1301,17 +1308,12 @@ int amcx_group_stats_f32(const float* x_dev, int64_t n_groups, int64_t rows_per_
                          void* hip_stream) {
   if (!stats_args_ok(n_groups, rows_per_group, row_stride, n_cols)) return AMCX_EINVAL;
   if (n_groups == 0) return AMCX_OK;
-  if (x_dev == nullptr || mean_dev == nullptr || std_dev == nullptr) return AMCX_EINVAL;
-  const int64_t bytes = amcx_group_stats_workspace_bytes(n_groups, rows_per_group, n_cols);
+  if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, true}, {std_dev, 7u, true}})) return AMCX_EINVAL;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const int64_t bytes = amcx_group_stats_workspace_bytes(n_groups, rows_per_group, n_cols);
   void* ws = nullptr;
   AMCX_HIP(hipMallocAsync(&ws, (size_t)bytes, st));           // stream-ordered: no synchronisation
-  const int rc = amcx_group_stats_ws_f32(x_dev, n_groups, rows_per_group, row_stride, n_cols, mean_dev,
-                                         std_dev, ws, bytes, hip_stream);
-  const hipError_t fe = hipFreeAsync(ws, st);
-  if (rc != AMCX_OK) return rc;
-  AMCX_HIP(fe);
-  return AMCX_OK;
+  return free_own_ws(ws, st, launch_stats(x_dev, n_groups, rows_per_group, row_stride, n_cols, mean_dev, std_dev, ws, st));
 }
 
 int64_t amcx_standardize_workspace_bytes(int64_t n_rows, int32_t n_cols) {
@@ -1325,28 +1327,26 @@ int amcx_standardize_fit_transform_f32(const float* x_dev, int64_t n_rows, int64
                                        float* out_dev, int64_t out_stride, double* mean_dev,
                                        double* scale_dev, void* workspace_dev, int64_t workspace_bytes,
                                        void* hip_stream) {
-  if (n_rows < 0 || n_sel < 1 || n_sel > amcx::kStatMaxCols || out_stride < n_sel || cols_host == nullptr ||
-      n_cols < 1 || n_cols > amcx::kStatMaxCols || row_stride < n_cols)
+  if (n_sel < 1 || n_sel > amcx::kStatMaxCols || n_cols < 1 || n_cols > amcx::kStatMaxCols || cols_host == nullptr ||
+      !rows_ok(n_rows, row_stride, n_cols) || !rows_ok(n_rows, out_stride, n_sel))
     return AMCX_EINVAL;
   amcx::SelectCols sel;
   if (!make_select_cols(cols_host, n_sel, n_cols, &sel)) return AMCX_EINVAL;
+  // the statistics' own limits (row_stride <= 2^20) over the one group of n_rows rows, and the transform's grid in 31 bits
+  const int64_t grid = (n_rows + amcx::kSelectRows - 1) / amcx::kSelectRows;
+  if (n_rows > 0 && (!stats_args_ok(1, n_rows, row_stride, n_cols) || grid > 0x7fffffffLL)) return AMCX_EINVAL;
+  if (n_rows > 0 && workspace_bytes < amcx_standardize_workspace_bytes(n_rows, n_cols)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
-  if (!x_dev || !out_dev || !mean_dev || !scale_dev || !workspace_dev) return AMCX_EINVAL;
-  if (on_another_device(x_dev) || on_another_device(out_dev)) return AMCX_EINVAL;
-  const int64_t need = amcx_standardize_workspace_bytes(n_rows, n_cols);
-  if (need < 0 || workspace_bytes < need) return AMCX_EINVAL;
+  if (!ptrs_ok({{x_dev, 3u, true}, {out_dev, 3u, true}, {mean_dev, 7u, true}, {scale_dev, 7u, true}, {workspace_dev, 7u, true}}))
+    return AMCX_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
   double* all_mean = static_cast<double*>(workspace_dev);
   double* all_std = all_mean + amcx::kStatMaxCols;
-  void* part = all_std + amcx::kStatMaxCols;
-  const int rc = amcx_group_stats_ws_f32(x_dev, 1, n_rows, row_stride, n_cols, all_mean, all_std, part,
-                                         need - 2 * (int64_t)amcx::kStatMaxCols * (int64_t)sizeof(double), hip_stream);
+  const int rc = launch_stats(x_dev, 1, n_rows, row_stride, n_cols, all_mean, all_std, all_std + amcx::kStatMaxCols, st);
   if (rc != AMCX_OK) return rc;
-  const int64_t grid = (n_rows + amcx::kSelectRows - 1) / amcx::kSelectRows;
-  if (grid > 0x7fffffffLL) return AMCX_EINVAL;
-  hipLaunchKernelGGL(amcx::amcx_select_fit_scale_kernel, dim3((unsigned)grid), dim3(amcx::kBlockThreads), 0,
-                     static_cast<hipStream_t>(hip_stream), x_dev, (long long)n_rows, (long long)row_stride, sel,
-                     all_mean, all_std, out_dev, (long long)out_stride, mean_dev, scale_dev);
-  AMCX_HIP(hipGetLastError());
+  const hipError_t e = amcx::launch(amcx::amcx_select_fit_scale_kernel, grid, amcx::kBlockThreads, 0, st, x_dev, n_rows, row_stride, sel,
+                                    all_mean, all_std, out_dev, out_stride, mean_dev, scale_dev);
+  if (e != hipSuccess) return hip_fail(e, "scaler fit-and-transform kernel launch");
   return AMCX_OK;
 }
 
@@ -1354,17 +1354,15 @@ int amcx_select_scale_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
                           const int32_t* cols_dev, int32_t n_sel, const double* mean_dev,
                           const double* scale_dev, float* out_dev, int64_t out_stride,
                           void* hip_stream) {
-  if (n_rows < 0 || n_sel < 1 || out_stride < n_sel || row_stride < 1) return AMCX_EINVAL;
+  // (the input's width is not an argument: a row holds one element at least; n_rows * n_sel <= n_rows * out_stride <= 2^58)
+  if (n_sel < 1 || !rows_ok(n_rows, row_stride, 1) || !rows_ok(n_rows, out_stride, n_sel)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
-  if (!x_dev || !cols_dev || !mean_dev || !scale_dev || !out_dev) return AMCX_EINVAL;
-  const int64_t total = n_rows * n_sel;
-  int64_t grid = (total + amcx::kBlockThreads - 1) / amcx::kBlockThreads;
-  const int64_t cap = (int64_t)cu_count() * 8;
-  if (grid > cap) grid = cap;
-  hipLaunchKernelGGL(amcx::amcx_select_scale_kernel, dim3((unsigned)grid), dim3(amcx::kBlockThreads), 0,
-                     static_cast<hipStream_t>(hip_stream), x_dev, (long long)n_rows, (long long)row_stride,
-                     cols_dev, (int)n_sel, mean_dev, scale_dev, out_dev, (long long)out_stride);
-  AMCX_HIP(hipGetLastError());
+  if (!ptrs_ok({{x_dev, 3u, true}, {cols_dev, 3u, true}, {mean_dev, 7u, true}, {scale_dev, 7u, true}, {out_dev, 3u, true}}))
+    return AMCX_EINVAL;
+  const int64_t grid = amcx::persistent_grid(cu_count(), 8, n_rows * n_sel, amcx::kBlockThreads);
+  const hipError_t e = amcx::launch(amcx::amcx_select_scale_kernel, grid, amcx::kBlockThreads, 0, static_cast<hipStream_t>(hip_stream),
+                                    x_dev, n_rows, row_stride, cols_dev, n_sel, mean_dev, scale_dev, out_dev, out_stride);
+  if (e != hipSuccess) return hip_fail(e, "select-and-scale kernel launch");
   return AMCX_OK;
 }
 
@@ -1386,7 +1384,7 @@ int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
                           const float* params_dev, const int32_t* widths_host, int32_t n_linear, int32_t activation,
                           int32_t* labels_dev, float* probs_dev, int64_t probs_stride, int64_t rows_per_group,
                           int64_t* counts_dev, void* hip_stream) {
-  if (n_rows < 0 || n_cols < 1 || n_cols > amcx::kStatMaxCols || row_stride < n_cols || cols_host == nullptr ||
+  if (n_cols < 1 || n_cols > amcx::kStatMaxCols || !rows_ok(n_rows, row_stride, n_cols) || cols_host == nullptr ||
       !mlp_shape_ok(widths_host, n_linear) || n_sel != widths_host[0])
     return AMCX_EINVAL;
   if (activation != AMCX_ACT_RELU && activation != AMCX_ACT_TANH && activation != AMCX_ACT_SIGMOID) return AMCX_EINVAL;
@@ -1394,35 +1392,33 @@ int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
   amcx::SelectCols sel;
   if (!make_select_cols(cols_host, n_sel, n_cols, &sel)) return AMCX_EINVAL;
   const int n_cls = widths_host[n_linear];
-  if (probs_dev != nullptr && probs_stride < n_cls) return AMCX_EINVAL;
+  if (probs_dev != nullptr && !rows_ok(n_rows, probs_stride, n_cls)) return AMCX_EINVAL;
   if (rows_per_group < 0 || (rows_per_group == 0 && counts_dev != nullptr)) return AMCX_EINVAL;
   if (rows_per_group > 0 && n_rows % rows_per_group != 0) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
-  if (x_dev == nullptr || params_dev == nullptr) return AMCX_EINVAL;
-  if (labels_dev == nullptr && probs_dev == nullptr && counts_dev == nullptr) return AMCX_OK;
-  if (on_another_device(x_dev) || on_another_device(params_dev) || (labels_dev && on_another_device(labels_dev)) ||
-      (probs_dev && on_another_device(probs_dev)) || (counts_dev && on_another_device(counts_dev)))
+  if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, false}, {scale_dev, 7u, false}, {params_dev, 3u, true}, {labels_dev, 3u, false},
+                {probs_dev, 3u, false}, {counts_dev, 7u, false}}))
     return AMCX_EINVAL;
+  if (labels_dev == nullptr && probs_dev == nullptr && counts_dev == nullptr) return AMCX_OK;      // nothing asked for
   amcx::MlpShape shape;
   shape.n_linear = n_linear;
   shape.act = activation;
   for (int l = 0; l <= amcx::kMlpMaxLinear; ++l) shape.w[l] = l <= n_linear ? widths_host[l] : 0;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (counts_dev != nullptr) {
+  unsigned long long* const counts = reinterpret_cast<unsigned long long*>(counts_dev);
+  if (counts != nullptr) {
     const int64_t bins = (n_rows / rows_per_group) * (int64_t)(n_cls + 1);
     const int64_t zgrid = (bins + 255) / 256;
-    hipLaunchKernelGGL(amcx::amcx_mlp_zero_counts_kernel, dim3((unsigned)(zgrid < 1024 ? zgrid : 1024)), dim3(256), 0, st,
-                       reinterpret_cast<unsigned long long*>(counts_dev), (long long)bins);
+    const hipError_t e = amcx::launch(amcx::amcx_mlp_zero_counts_kernel, zgrid < 1024 ? zgrid : 1024, 256, 0, st, counts, bins);
+    if (e != hipSuccess) return hip_fail(e, "classifier count-zeroing kernel launch");
   }
+  // every workgroup stages the parameters once, then walks tiles
   const int64_t tiles = (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows;
-  int64_t grid = tiles;
-  const int64_t cap = (int64_t)cu_count() * 4;             // every workgroup stages the parameters once, then walks tiles
-  if (grid > cap) grid = cap;
-  hipLaunchKernelGGL(amcx::amcx_mlp_classify_kernel, dim3((unsigned)grid), dim3(amcx::kMlpThreads), 0, st, x_dev,
-                     (long long)n_rows, (long long)row_stride, sel, mean_dev, scale_dev, params_dev, shape, labels_dev,
-                     probs_dev, (long long)probs_stride, (long long)(counts_dev ? rows_per_group : 1),
-                     reinterpret_cast<unsigned long long*>(counts_dev), (long long)tiles);
-  AMCX_HIP(hipGetLastError());
+  const int64_t grid = amcx::persistent_grid(cu_count(), 4, tiles, 1);
+  const hipError_t e = amcx::launch(amcx::amcx_mlp_classify_kernel, grid, amcx::kMlpThreads, 0, st, x_dev, n_rows, row_stride, sel,
+                                    mean_dev, scale_dev, params_dev, shape, labels_dev, probs_dev, probs_stride,
+                                    counts != nullptr ? rows_per_group : 1, counts, tiles);
+  if (e != hipSuccess) return hip_fail(e, "classifier kernel launch");
   return AMCX_OK;
 }
 

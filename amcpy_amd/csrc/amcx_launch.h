@@ -1,6 +1,7 @@
 // Host launch layer of libamcx.so: which throughput kernel runs a frame size (THE FRAME-SIZE TABLE, for_frame_size) and how
-// every kernel of the library is launched (lds_attr_once, persistent_grid, launch).  Host code only: the kernels, their Cfg /
-// SCfg / G constants and their documentation live in the kernel headers, which the diagnostic tools include on their own.
+// every kernel of the library is launched (lds_attr_once, persistent_grid, launch) -- all but the FMA probe's, which times
+// thousands of launches back to back and asks once at the end (amcx_probe.h).  Host code only: the kernels, their Cfg / SCfg / G
+// constants and their documentation live in the kernel headers, which the diagnostic tools include on their own.
 #pragma once
 
 #include <stdio.h>
@@ -46,11 +47,16 @@ inline int64_t persistent_grid(int cus, int wgs_per_cu, int64_t work, int64_t un
 }
 
 // Launch, then ask.  `kern` is a plain pointer: where a kernel name is overloaded the caller has chosen already.
+// `grid`: a dim3 for the few two-dimensional grids, a count of workgroups for everything else.
+template <class... P, class... A>
+inline hipError_t launch(void (*kern)(P...), dim3 grid, int threads, size_t lds, hipStream_t stream, A... args) {
+  static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+  hipLaunchKernelGGL(kern, grid, dim3((unsigned)threads), lds, stream, static_cast<P>(args)...);
+  return hipGetLastError();
+}
 template <class... P, class... A>
 inline hipError_t launch(void (*kern)(P...), int64_t grid, int threads, size_t lds, hipStream_t stream, A... args) {
-  static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)threads), lds, stream, static_cast<P>(args)...);
-  return hipGetLastError();
+  return launch(kern, dim3((unsigned)grid), threads, lds, stream, args...);
 }
 
 // what every feature kernel is launched over

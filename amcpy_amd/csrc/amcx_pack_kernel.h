@@ -17,6 +17,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "amcx_launch.h"      // (for launch_pack_planes at the end; amcx.hip has included it already)
+
 namespace amcx {
 
 constexpr int kPackTile = 64;
@@ -79,9 +81,8 @@ inline hipError_t launch_pack_planes(const SRC* slab, int n_planes, long long P,
   if (n_planes <= 0 || P <= 0) return hipSuccess;
   const long long gx = (P + kPackTile - 1) / kPackTile, gy = (n_planes + kPackTile - 1) / kPackTile;
   if (gx > 0x7fffffffLL || gy > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(amcx_pack_planes_kernel<SRC>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, stream, slab,
-                     n_planes, P, plane_stride, S, K, inner_snr, dst, dst_stride, n0);
-  return hipGetLastError();
+  return launch(amcx_pack_planes_kernel<SRC>, dim3((unsigned)gx, (unsigned)gy), 256, 0, stream, slab, n_planes, P, plane_stride, S,
+                K, inner_snr, dst, dst_stride, n0);
 }
 
 }  // namespace amcx

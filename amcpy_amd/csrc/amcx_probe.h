@@ -82,6 +82,7 @@ int amcx_probe_fma_rate(double seconds, void* hip_stream, double* wave_instr_per
   if (e != hipSuccess) return hip_fail(e, "fma probe setup");
   float* const sink = sink_buf.as<float>();
   unsigned long long* const ticks = ticks_buf.as<unsigned long long>();
+  // (the one raw launch of the library, amcx_launch.h: the error is asked for once, behind the timed launches)
   auto launch = [&]() { hipLaunchKernelGGL(amcx_probe_fma_kernel, dim3((unsigned)grid), dim3(1024), 0, stream, kIters, sink, ticks); };
   // one launch to learn its length, then `seconds` of back-to-back launches: the first half lets the board's power
   // management settle the clock, the second half is timed
@@ -119,10 +120,9 @@ int amcx_probe_fma_rate(double seconds, void* hip_stream, double* wave_instr_per
 int amcx_probe_read_bw(const void* src_dev, int64_t n_bytes, float* partial_dev, void* hip_stream) {
   if (src_dev == nullptr || partial_dev == nullptr || n_bytes < 0 || (n_bytes & 15)) return AMCX_EINVAL;
   if (n_bytes == 0) return AMCX_OK;
-  hipLaunchKernelGGL(amcx_probe_read_kernel, dim3(4096), dim3(256), 0,
-                     static_cast<hipStream_t>(hip_stream), static_cast<const float4*>(src_dev),
-                     (long long)(n_bytes / 16), partial_dev);
-  AMCX_HIP(hipGetLastError());
+  const hipError_t e = amcx::launch(amcx_probe_read_kernel, 4096, 256, 0, static_cast<hipStream_t>(hip_stream),
+                                    static_cast<const float4*>(src_dev), n_bytes / 16, partial_dev);
+  if (e != hipSuccess) return hip_fail(e, "read probe kernel launch");
   return AMCX_OK;
 }
 

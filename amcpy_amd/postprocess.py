@@ -19,16 +19,28 @@ import ctypes
 from typing import Sequence, Tuple
 
 
-from . import _lib
+from . import _lib, _stream
 
 
 def _as_rows(feats):
+    """(..., rows, cols), which ``_stream.rows_of`` -- two dimensions, its own messages -- does not take."""
     import torch
     if not isinstance(feats, torch.Tensor) or feats.dtype != torch.float32 or not feats.is_cuda:
         raise TypeError("feats must be a float32 CUDA tensor")
     if feats.dim() < 2 or feats.stride(-1) != 1:
         raise ValueError("feats must be (..., rows, cols) with unit stride in the last dimension")
     return feats
+
+
+def select_cols(cols, n_cols: int) -> list:
+    """The 0-based column selection of :func:`select_standardize`, ``classifier.classify`` and ``classify_frames`` as ints:
+    every index a column of the ``n_cols``, 1 ... 32 of them out of 32 at most."""
+    cols = [int(c) for c in cols]
+    if any(c < 0 or c >= n_cols for c in cols):
+        raise IndexError("column index out of range")
+    if not cols or len(cols) > 32 or n_cols > 32:
+        raise ValueError("between 1 and 32 columns")
+    return cols
 
 
 def snr_statistics(feats):
@@ -41,18 +53,16 @@ def snr_statistics(feats):
     if flat.data_ptr() != feats.data_ptr() or (flat.shape[0] > 1 and flat.stride(0) != R * flat.stride(1)):
         flat = feats.contiguous().reshape(-1, R, Cc)
     G = flat.shape[0]
-    mean = torch.empty((G, Cc), dtype=torch.float64, device=feats.device)
+    mean = torch.empty(lead + (Cc,), dtype=torch.float64, device=feats.device)      # the entry's [G][Cc], in the shape returned
     std = torch.empty_like(mean)
     lib = _lib.load()
     need = lib.amcx_group_stats_workspace_bytes(G, R, Cc)
     if need < 0:
         raise ValueError(f"statistics over {R} rows x {Cc} columns: at least one row, at most 32 columns")
     ws = torch.empty((max(int(need), 8),), dtype=torch.uint8, device=feats.device)
-    with torch.cuda.device(feats.device):
-        _lib.check(lib.amcx_group_stats_ws_f32(
-            flat.data_ptr(), G, R, flat.stride(1), Cc, mean.data_ptr(), std.data_ptr(), ws.data_ptr(), ws.numel(),
-            torch.cuda.current_stream(feats.device).cuda_stream))
-    return mean.reshape(lead + (Cc,)), std.reshape(lead + (Cc,))
+    _stream.launch(feats, lambda lib, stream: lib.amcx_group_stats_ws_f32(
+        flat.data_ptr(), G, R, flat.stride(1), Cc, mean.data_ptr(), std.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+    return mean, std
 
 
 def select_standardize(rows, cols: Sequence[int]) -> Tuple["object", "object", "object"]:
@@ -64,11 +74,7 @@ def select_standardize(rows, cols: Sequence[int]) -> Tuple["object", "object", "
     if rows.dim() != 2:
         raise ValueError("rows must be 2-D (flatten (mod, snr, frame) first)")
     R, Cc = rows.shape
-    cols = [int(c) for c in cols]
-    if any(c < 0 or c >= Cc for c in cols):
-        raise IndexError("column index out of range")
-    if not cols or len(cols) > 32 or Cc > 32:
-        raise ValueError("between 1 and 32 columns")
+    cols = select_cols(cols, Cc)
     lib = _lib.load()
     out = torch.empty((R, len(cols)), dtype=torch.float32, device=rows.device)
     mean = torch.empty((len(cols),), dtype=torch.float64, device=rows.device)
@@ -78,10 +84,8 @@ def select_standardize(rows, cols: Sequence[int]) -> Tuple["object", "object", "
     need = lib.amcx_standardize_workspace_bytes(R, Cc)
     ws = torch.empty((int(need),), dtype=torch.uint8, device=rows.device)
     cols_c = (ctypes.c_int32 * len(cols))(*cols)
-    with torch.cuda.device(rows.device):
-        # three launches on the current stream, nothing else: all-column statistics (read 1), chunk merge, transform (read 2)
-        _lib.check(lib.amcx_standardize_fit_transform_f32(
-            rows.data_ptr(), R, rows.stride(0), Cc, cols_c, len(cols), out.data_ptr(), out.stride(0),
-            mean.data_ptr(), scale.data_ptr(), ws.data_ptr(), ws.numel(),
-            torch.cuda.current_stream(rows.device).cuda_stream))
+    # three launches on the current stream, nothing else: all-column statistics (read 1), chunk merge, transform (read 2)
+    _stream.launch(rows, lambda lib, stream: lib.amcx_standardize_fit_transform_f32(
+        rows.data_ptr(), R, rows.stride(0), Cc, cols_c, len(cols), out.data_ptr(), out.stride(0), mean.data_ptr(), scale.data_ptr(),
+        ws.data_ptr(), ws.numel(), stream))
     return out, mean, scale

@@ -814,6 +814,9 @@ int amcx_ctx_placement(const amcx_ctx* ctx, amcx_placement* out);
  * every runtime); amcx_group_stats_ws_f32 takes the caller's (at least
  * amcx_group_stats_workspace_bytes(...) bytes of device memory, contents undefined
  * afterwards; the size depends on the three arguments only, -1 for invalid ones).
+ *   - checks: ranges and strides (0 <= n_groups < 2^31, rows_per_group >= 1, 1 <= n_cols <= 32, n_cols <= row_stride <= 2^20);
+ *     the workspace's size (_ws, where there are groups); n_groups == 0 is AMCX_OK here, null pointers allowed; null pointers
+ *     and alignment (x 4, mean and std 8, the workspace 8); a pointer on another device.
  */
 int amcx_group_stats_f32(const float* x_dev, int64_t n_groups, int64_t rows_per_group,
                          int64_t row_stride, int32_t n_cols, double* mean_dev, double* std_dev,
@@ -828,6 +831,9 @@ int amcx_group_stats_ws_f32(const float* x_dev, int64_t n_groups, int64_t rows_p
  * float32 after each of the two operations as numpy's in-place float32 arithmetic does
  * (column pick preprocessing.py:55, StandardScaler.transform :62).  cols_dev: n_sel
  * int32 column indices (0-based, as the reference passes list(FeatureConfig.used)).
+ *   - checks: ranges and strides (n_rows >= 0, n_sel >= 1, row_stride >= 1, out_stride >= n_sel, n_rows times either stride at
+ *     most 2^58); n_rows == 0 is AMCX_OK here, null pointers allowed; null pointers and alignment (x, cols and out 4, mean and
+ *     scale 8); a pointer on another device.
  */
 int amcx_select_scale_f32(const float* x_dev, int64_t n_rows, int64_t row_stride,
                           const int32_t* cols_dev, int32_t n_sel, const double* mean_dev,
@@ -845,6 +851,10 @@ int amcx_select_scale_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
  * _is_constant_feature), writes mean_dev[n_sel] / scale_dev[n_sel] (doubles) and
  * out_dev[r][j] with the two float32 roundings of amcx_select_scale_f32.
  * workspace_dev: at least amcx_standardize_workspace_bytes(n_rows, n_cols) bytes.
+ *   - checks: ranges and strides (n_rows >= 0, 1 <= n_sel <= 32, 1 <= n_cols <= 32, cols_host there and every index a column,
+ *     row_stride >= n_cols, out_stride >= n_sel, n_rows times either at most 2^58; where there are rows, row_stride <= 2^20 and
+ *     n_rows < 2^41); the workspace's size (where there are rows); n_rows == 0 is AMCX_OK here, null pointers allowed; null
+ *     pointers and alignment (x and out 4, mean and scale 8, the workspace 8); a pointer on another device.
  */
 int64_t amcx_standardize_workspace_bytes(int64_t n_rows, int32_t n_cols);
 int amcx_standardize_fit_transform_f32(const float* x_dev, int64_t n_rows, int64_t row_stride,
@@ -886,6 +896,11 @@ int amcx_standardize_fit_transform_f32(const float* x_dev, int64_t n_rows, int64
  * (BPSK) for such a row.
  * n_rows == 0 is AMCX_OK and a no-op.  Arguments are checked before any HIP call.  amcx_mlp_kernel_name: the kernel
  * that runs for this shape (host-only).
+ *   - checks: ranges and strides (1 <= n_cols <= 32, n_rows >= 0, row_stride >= n_cols, the shape, n_sel == widths_host[0], the
+ *     activation, mean and scale both or neither, every index a column, probs_stride >= classes where probs_dev is given,
+ *     n_rows times either stride at most 2^58, whole groups); n_rows == 0 is AMCX_OK here, null pointers allowed; null pointers
+ *     (x, params) and alignment (x, params, labels and probs 4, mean, scale and counts 8); a pointer on another device; with
+ *     no output asked for the call is AMCX_OK then, and launches nothing.
  */
 #define AMCX_ACT_RELU 0
 #define AMCX_ACT_TANH 1
