@@ -12,7 +12,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
-ABI_VERSION = 15        # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_VERSION = 16        # the version this binding was written against; any library >= it will do (include/amcx.h)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -26,6 +26,7 @@ IQ8_CI8, IQ8_CU8 = 0, 1                                  # AMCX_IQ8_*: the forma
 IQ8_SCALE = 2.0 ** -7                                    # the default 8-bit scale: int8 onto [-1, 1)
 ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2                # AMCX_ACT_* (ABI 8)
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
+ACT_NONE = 3                                             # AMCX_ACT_NONE (ABI 16): amcx_mlp_range_f32 only
 
 
 class UploadStats(C.Structure):
@@ -125,6 +126,12 @@ SIGNATURES = {
     "amcx_mlp_classify_f32": (C.c_int, [_vp, _i64, _i64, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, C.POINTER(_i32), _i32,
                                         _i32, _vp, _vp, _i64, _i64, _vp, _vp]),
     "amcx_mlp_kernel_name": (C.c_int, [C.POINTER(_i32), _i32, C.c_char_p, _i32]),
+    "amcx_mlp_range_f32": (C.c_int, [_vp, _i64, _i64, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, C.POINTER(_i32), _i32, _i32,
+                                     _vp, _vp, _vp]),
+    "amcx_mlp_q15_params_shorts": (_i64, [C.POINTER(_i32), _i32]),
+    "amcx_mlp_classify_q15": (C.c_int, [_vp, _i64, _i64, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, C.POINTER(_i32), _i32, _i32,
+                                        _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "amcx_kernel_name_mlp_q15": (C.c_char_p, [_i32]),
 }
 
 _lib = None
@@ -293,6 +300,14 @@ def kernel_name_psd(src_kind: int) -> str:
     buf = C.create_string_buffer(128)
     check(load().amcx_kernel_name_psd(int(src_kind), buf, len(buf)))
     return buf.value.decode()
+
+
+def kernel_name_mlp_q15(which: int = 0) -> str:
+    """amcx_kernel_name_mlp_q15: 0 the integer network's kernel, 1 the range kernel, 2 its initialising launch (host-only)."""
+    name = load().amcx_kernel_name_mlp_q15(int(which))
+    if name is None:
+        raise ValueError(f"amcx: no fixed-point kernel number {which}")
+    return name.decode()
 
 
 def kernel_name_psd_detect() -> str:

@@ -14,7 +14,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_psd_kernel.h"       // FIRST of all (ABI 15; it includes the occupancy and down-converter headers for their device helpers), ...
+#include "amcx_mlp_q15_kernel.h"   // FIRST of all (ABI 16: plain kernels on amcx_mlp_shape.h alone, which holds no kernel), then the spectrogram's ...
+#include "amcx_psd_kernel.h"       // ... it includes the occupancy and down-converter headers for their device helpers), ...
 #include "amcx_occupancy_kernels.h"  // ... then the occupancy kernels (ABI 14: plain kernels that call nothing of the others), ...
 #include "amcx_resample_kernel.h"  // ... then the resampler's (it includes the down-converter's header in front of its own kernels), the bank's next, ...
 #include "amcx_bank_kernel.h"
@@ -572,6 +573,23 @@ bool make_select_cols(const int32_t* cols_host, int32_t n_sel, int32_t n_cols, a
     sel->c[j] = cols_host[j];
   }
   return true;
+}
+
+// what amcx_mlp_range_f32 and amcx_mlp_classify_q15 ask of their rows, columns, scaler and shape: amcx_mlp_classify_f32's limits
+bool mlp_rows_ok(int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host, int32_t n_sel, const double* mean_dev,
+                 const double* scale_dev, const int32_t* widths_host, int32_t n_linear, amcx::SelectCols* sel) {
+  if (n_cols < 1 || n_cols > amcx::kStatMaxCols || !rows_ok(n_rows, row_stride, n_cols) || cols_host == nullptr ||
+      !mlp_shape_ok(widths_host, n_linear) || n_sel != widths_host[0])
+    return false;
+  if ((mean_dev == nullptr) != (scale_dev == nullptr)) return false;
+  return make_select_cols(cols_host, n_sel, n_cols, sel);
+}
+amcx::MlpShape mlp_shape(const int32_t* widths_host, int32_t n_linear, int32_t activation) {
+  amcx::MlpShape shape;
+  shape.n_linear = n_linear;
+  shape.act = activation;
+  for (int l = 0; l <= amcx::kMlpMaxLinear; ++l) shape.w[l] = l <= n_linear ? widths_host[l] : 0;
+  return shape;
 }
 
 // the two launches of a statistics call, behind its entry's gate: a chunk's triple per workgroup into `ws`, then the pooling
@@ -1419,6 +1437,94 @@ int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
                                     mean_dev, scale_dev, params_dev, shape, labels_dev, probs_dev, probs_stride,
                                     counts != nullptr ? rows_per_group : 1, counts, tiles);
   if (e != hipSuccess) return hip_fail(e, "classifier kernel launch");
+  return AMCX_OK;
+}
+
+int64_t amcx_mlp_q15_params_shorts(const int32_t* widths_host, int32_t n_linear) { return amcx_mlp_params_floats(widths_host, n_linear); }
+
+const char* amcx_kernel_name_mlp_q15(int32_t which) {
+  return which == 0 ? "amcx_mlp_q15_kernel" : which == 1 ? "amcx_mlp_range_kernel" : which == 2 ? "amcx_mlp_range_init_kernel" : nullptr;
+}
+
+int amcx_mlp_range_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host,
+                       int32_t n_sel, const double* mean_dev, const double* scale_dev, const float* params_dev,
+                       const int32_t* widths_host, int32_t n_linear, int32_t activation, float* ranges_dev, int64_t* skipped_dev,
+                       void* hip_stream) {
+  amcx::SelectCols sel;
+  if (!mlp_rows_ok(n_rows, row_stride, n_cols, cols_host, n_sel, mean_dev, scale_dev, widths_host, n_linear, &sel)) return AMCX_EINVAL;
+  if (activation != AMCX_ACT_RELU && activation != AMCX_ACT_NONE) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, false}, {scale_dev, 7u, false}, {params_dev, 3u, true}, {ranges_dev, 3u, true},
+                {skipped_dev, 7u, true}}))
+    return AMCX_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  unsigned long long* const skipped = reinterpret_cast<unsigned long long*>(skipped_dev);
+  hipError_t e = amcx::launch(amcx::amcx_mlp_range_init_kernel, 1, 64, 0, st, ranges_dev, n_linear + 1, skipped);
+  if (e != hipSuccess) return hip_fail(e, "range initialising kernel launch");
+  const amcx::MlpShape shape = mlp_shape(widths_host, n_linear, activation);
+  const int64_t tiles = (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows;
+  const int64_t grid = amcx::persistent_grid(cu_count(), 2, tiles, 1);         // 53 KiB of LDS: two workgroups a CU
+  e = amcx::launch(amcx::amcx_mlp_range_kernel, grid, amcx::kMlpThreads, 0, st, x_dev, n_rows, row_stride, sel, mean_dev, scale_dev,
+                   params_dev, shape, ranges_dev, skipped, tiles);
+  if (e != hipSuccess) return hip_fail(e, "range kernel launch");
+  return AMCX_OK;
+}
+
+int amcx_mlp_classify_q15(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host,
+                          int32_t n_sel, const double* mean_dev, const double* scale_dev, const int16_t* params_dev,
+                          const int32_t* widths_host, int32_t n_linear, int32_t activation, int32_t frac_input,
+                          const int32_t* frac_weights_host, const int32_t* frac_biases_host, const int32_t* frac_outputs_host,
+                          int32_t* labels_dev, int16_t* logits_dev, int64_t logits_stride, int64_t rows_per_group,
+                          int64_t* counts_dev, int64_t* saturated_dev, void* hip_stream) {
+  amcx::SelectCols sel;
+  if (!mlp_rows_ok(n_rows, row_stride, n_cols, cols_host, n_sel, mean_dev, scale_dev, widths_host, n_linear, &sel)) return AMCX_EINVAL;
+  if (activation != AMCX_ACT_RELU) return AMCX_EINVAL;
+  if (frac_weights_host == nullptr || frac_biases_host == nullptr || frac_outputs_host == nullptr) return AMCX_EINVAL;
+  const auto frac_ok = [](int32_t n) { return n >= 0 && n <= 15; };
+  if (!frac_ok(frac_input)) return AMCX_EINVAL;
+  amcx::Q15Formats fmt;
+  fmt.in_scale = (float)(1 << frac_input);
+  for (int l = 0, na = frac_input; l < amcx::kMlpMaxLinear; ++l) {
+    fmt.shift_b[l] = 0;
+    fmt.shift_o[l] = 1;
+    if (l >= n_linear) continue;
+    const int32_t nw = frac_weights_host[l], nb = frac_biases_host[l], no = frac_outputs_host[l];
+    if (!frac_ok(nw) || !frac_ok(nb) || !frac_ok(no)) return AMCX_EINVAL;
+    const int p = nw + na;
+    if (p < nb || p <= no) return AMCX_EINVAL;
+    fmt.shift_b[l] = p - nb;
+    fmt.shift_o[l] = p - no;
+    na = no;
+  }
+  const int n_cls = widths_host[n_linear];
+  if (logits_dev != nullptr && !rows_ok(n_rows, logits_stride, n_cls)) return AMCX_EINVAL;
+  if (rows_per_group < 0 || (rows_per_group == 0 && counts_dev != nullptr)) return AMCX_EINVAL;
+  if (rows_per_group > 0 && n_rows % rows_per_group != 0) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, false}, {scale_dev, 7u, false}, {params_dev, 1u, true}, {labels_dev, 3u, false},
+                {logits_dev, 1u, false}, {counts_dev, 7u, false}, {saturated_dev, 7u, false}}))
+    return AMCX_EINVAL;
+  if (labels_dev == nullptr && logits_dev == nullptr && counts_dev == nullptr && saturated_dev == nullptr) return AMCX_OK;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  unsigned long long* const counts = reinterpret_cast<unsigned long long*>(counts_dev);
+  unsigned long long* const saturated = reinterpret_cast<unsigned long long*>(saturated_dev);
+  if (counts != nullptr) {
+    const int64_t bins = (n_rows / rows_per_group) * (int64_t)(n_cls + 1);
+    const int64_t zgrid = (bins + 255) / 256;
+    const hipError_t e = amcx::launch(amcx::amcx_mlp_zero_counts_kernel, zgrid < 1024 ? zgrid : 1024, 256, 0, st, counts, bins);
+    if (e != hipSuccess) return hip_fail(e, "Q15 count-zeroing kernel launch");
+  }
+  if (saturated != nullptr) {
+    const hipError_t e = amcx::launch(amcx::amcx_mlp_zero_counts_kernel, 1, 256, 0, st, saturated, (long long)(n_linear + 1));
+    if (e != hipSuccess) return hip_fail(e, "Q15 saturation-zeroing kernel launch");
+  }
+  const amcx::MlpShape shape = mlp_shape(widths_host, n_linear, activation);
+  const int64_t tiles = (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows;
+  const int64_t grid = amcx::persistent_grid(cu_count(), 4, tiles, 1);
+  const hipError_t e = amcx::launch(amcx::amcx_mlp_q15_kernel, grid, amcx::kMlpThreads, 0, st, x_dev, n_rows, row_stride, sel, mean_dev,
+                                    scale_dev, params_dev, shape, fmt, labels_dev, logits_dev, logits_stride,
+                                    counts != nullptr ? rows_per_group : 1, counts, saturated, tiles);
+  if (e != hipSuccess) return hip_fail(e, "Q15 classifier kernel launch");
   return AMCX_OK;
 }
 

@@ -320,6 +320,8 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bo
 // occupancy kernels (ABI 14, amcx_occupancy_kernels.h: plain kernels that call nothing of the others) in front of everything.
 // The spectrogram's (ABI 15, amcx_psd_kernel.h, which includes the occupancy and down-converter headers for occ_key and the
 // loaders) are included in front of those.
+// The fixed-point kernels (ABI 16, amcx_mlp_q15_kernel.h) come first of all now: plain kernels on amcx_mlp_shape.h, which holds the
+// declarations they share with the classifier and no kernel, so including it there moves nothing.
 // That specialisations are laid out there is what hipcc does today, not a rule it documents: tools/codeobj_gate.py --kernels
 // against the parent commit is what guards it, and the only thing that will notice when a compiler lays them out elsewhere.
 inline void kernel_order_anchor() {

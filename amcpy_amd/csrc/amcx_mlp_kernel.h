@@ -27,45 +27,10 @@
 // 64-bit vector atomic per non-empty bin from lane 0.
 #pragma once
 
+#include "amcx_mlp_shape.h"      // the limits, MlpShape and the activations
 #include "amcx_post_kernels.h"
 
 namespace amcx {
-
-constexpr int kMlpMaxWidth = 32;      // every layer width, input and output included (kStatMaxCols)
-constexpr int kMlpMaxLinear = 6;
-constexpr int kMlpThreads = 256;
-constexpr int kMlpRowsPerLane = 2;
-constexpr int kMlpTileRows = kMlpThreads * kMlpRowsPerLane;
-constexpr int kMlpLayerFloats = kMlpMaxWidth * kMlpMaxWidth + kMlpMaxWidth;   // padded W[32][32] then b[32]
-constexpr int kActRelu = 0, kActTanh = 1, kActSigmoid = 2;
-
-struct MlpShape {
-  int n_linear;
-  int act;
-  int w[kMlpMaxLinear + 1];    // w[0] inputs ... w[n_linear] classes
-};
-
-template <int ACT>
-__device__ inline float mlp_act(float v) {
-  if (ACT == kActRelu) return v < 0.0f ? 0.0f : v;                 // NaN stays NaN, as torch.relu keeps it
-  if (ACT == kActTanh) return tanhf(v);
-  return 1.0f / (1.0f + expf(-v));
-}
-
-// the activation over the blocks of 8 outputs a layer has (the padding beyond stays 0)
-template <int ACT>
-__device__ inline void mlp_act_all(float (&v)[kMlpRowsPerLane][kMlpMaxWidth], int n_out) {
-#pragma unroll
-  for (int oc = 0; oc < kMlpMaxWidth; oc += 8) {
-    if (oc < n_out) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int s = 0; s < kMlpRowsPerLane; ++s) v[s][oc + j] = mlp_act<ACT>(v[s][oc + j]);
-      }
-    }
-  }
-}
 
 // counts <- 0 ahead of the classifier launch, on the same stream.  A kernel rather than hipMemsetAsync: inside a captured
 // graph the runtime's memset node filled the bins with other bytes from the second replay on (seen with ROCm 7.0 on

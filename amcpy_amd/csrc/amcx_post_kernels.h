@@ -19,10 +19,10 @@
 #pragma once
 
 #include "amcx_block_kernel.h"
+#include "amcx_mlp_shape.h"      // kStatMaxCols and SelectCols
 
 namespace amcx {
 
-constexpr int kStatMaxCols = 32;
 constexpr int kStatThreads = 256;
 constexpr int kStatPerThread = 16;     // rows of a tile held by one thread
 constexpr int kStatMaxRowLanes = 32;   // row lanes of a tile (threads per column)
@@ -201,11 +201,6 @@ __global__ __launch_bounds__(kBlockThreads) void amcx_select_scale_kernel(
 // sklearn/preprocessing/_data.py _is_constant_feature), writes both for the caller
 // (workgroup 0) and transforms kSelectRows rows per workgroup.
 constexpr int kSelectRows = 1024;
-struct SelectCols {
-  int n;
-  int c[kStatMaxCols];
-};
-
 __global__ __launch_bounds__(kBlockThreads) void amcx_select_fit_scale_kernel(
     const float* __restrict__ x, long long n_rows, long long row_stride, SelectCols sel,
     const double* __restrict__ mean_all, const double* __restrict__ std_all,

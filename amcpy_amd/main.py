@@ -2,11 +2,14 @@
                               [--device D | --devices 0,1,...|all] [--resume] [--features all|used|3,5,...]`
 
 The `extract` sub-command of the reference's CLI (src/amcpy/main.py:32,85-87,
-160-175); plot/train/quantize are outside the hot path.
+160-175); plot and train are outside the hot path.
 `python -m amcpy_amd classify --root DIR --model ID|PATH [--mode training|test] [--from-iq] [--device D]` is the
 evaluation half of the reference's `eval` (nn_model.evaluate_by_snr) on the GPU: amcpy_amd/classifier.py.  The reference's dispatcher calls ``cmd_extract(cfg, args)``
 on a one-argument function (main.py:175 vs :85) and raises TypeError as
 written; this entry point takes the same defaults and simply works.
+`python -m amcpy_amd quantize --root DIR --model ID|PATH [--mode training|test] [--layout reference|folded] [--no-normalize]
+[--evaluate] [--device D]` is the reference's `quantize` stage (nn_quantization.py) with the ranges calibrated and the 16-bit integer
+network run on the GPU: amcpy_amd/quantize.py.
 `python -m amcpy_amd recording FILE --frame-size N [--format cf32|sc16|ci8|cu8] [--scale S] [--features ...] [--device D]
 [--out PATH] [--shift-hz F --decimate D [--taps T] | --shift-hz F --resample L/D [--taps T] | --annotation K [--oversample R]
 [--rational] | --channels C [--oversample 1|2]
@@ -69,6 +72,22 @@ def build_parser() -> argparse.ArgumentParser:
     cl.add_argument("--from-iq", action="store_true",
                     help="run the extraction first (the used features only) instead of reading calculated-features/")
     cl.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
+    qz = sub.add_parser("quantize", help="export the network as 16-bit fixed point; --evaluate runs the integer network on the GPU")
+    qz.add_argument("--root", type=Path, default=None, help="project root (default: cwd)")
+    qz.add_argument("--model", required=True, metavar="ID|PATH", help="as for classify")
+    qz.add_argument("--mode", choices=("training", "test"), default="test", help="rows the scaler is fitted on, as for classify")
+    qz.add_argument("--layout", choices=("reference", "folded"), default="folded",
+                    help="reference: the Linear layers as stored into arm-data/w_and_b.mat, as the reference writes it; folded "
+                         "(default): every BatchNorm folded, into arm-data/{model_id}_q15.mat")
+    qz.add_argument("--evaluate", action="store_true",
+                    help="run the integer network over every row beside the float classifier: figures/{model_id}_q15_figure_data.mat")
+    qz.add_argument("--no-normalize", action="store_true",
+                    help="folded layout: export the block as it is; by default a layer whose range passes Q6.9 is scaled by a power "
+                         "of two (the labels stay the same), so that nothing clips")
+    qz.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
+    qz.add_argument("--frame-size", type=int, default=None)
+    qz.add_argument("--num-frames", type=int, default=None)
+    qz.add_argument("--snr-values", nargs="+", default=None, metavar="LABEL")
     cl.add_argument("--frame-size", type=int, default=None)
     cl.add_argument("--num-frames", type=int, default=None)
     cl.add_argument("--snr-values", nargs="+", default=None, metavar="LABEL",
@@ -534,6 +553,11 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
         # tensors on torch's runtime: this command never skips the import
         from .classifier import run_classification
         run_classification(cfg, args.model, mode=args.mode, from_iq=args.from_iq, device=args.device)
+        return 0
+    if args.command == "quantize":
+        from .quantize import run_quantization
+        run_quantization(cfg, args.model, mode=args.mode, layout=args.layout, evaluate=args.evaluate, device=args.device,
+                         normalize=not args.no_normalize)
         return 0
     if args.command == "extract":
         if args.devices is not None and args.device is not None:

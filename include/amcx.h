@@ -97,10 +97,13 @@ extern "C" {
  * amcx_kernel_name_iq8, AMCX_SRC_CI8 / AMCX_SRC_CU8 for the strided host / file entries and amcx_stage_host / _file,
  * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host;
  * 11 = the digital down-converter; 12 = the polyphase filter bank; 13 = the rational resampler; 14 = occupancy detection
- * (all listed behind the define); 15 = the Welch spectrogram and its per-row detection. */
-#define AMCX_ABI_VERSION 15
+ * (all listed behind the define); 15 = the Welch spectrogram and its per-row detection; 16 = fixed-point deployment of the
+ * classifier's network (range calibration and 16-bit integer inference). */
+#define AMCX_ABI_VERSION 16
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
- *   ABI 15: the line above               -- the spectrogram: amcx_spectrogram, amcx_spectrogram_out_rows, amcx_spectrogram_plan,
+ *   ABI 16: the line above               -- fixed-point deployment: AMCX_ACT_NONE, amcx_mlp_range_f32, amcx_mlp_classify_q15,
+ *                                            amcx_mlp_q15_params_shorts, amcx_kernel_name_mlp_q15
+ *   ABI 15: #define AMCX_ABI_VERSION 15   -- the spectrogram: amcx_spectrogram, amcx_spectrogram_out_rows, amcx_spectrogram_plan,
  *                                            amcx_psd_detect_f32, amcx_kernel_name_psd, amcx_kernel_name_psd_detect
  *   ABI 14: #define AMCX_ABI_VERSION 14   -- occupancy detection: amcx_row_power_c64, amcx_occupancy_workspace_bytes,
  *                                            amcx_occupancy_detect_f32, amcx_gather_rows_c64, amcx_kernel_name_occupancy
@@ -912,6 +915,66 @@ int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
                           int32_t* labels_dev, float* probs_dev, int64_t probs_stride, int64_t rows_per_group,
                           int64_t* counts_dev, void* hip_stream);
 int amcx_mlp_kernel_name(const int32_t* widths_host, int32_t n_linear, char* buf, int32_t buf_len);
+
+/*
+ * ABI 16.  FIXED-POINT DEPLOYMENT of the network amcx_mlp_classify_f32 runs: the reference's `quantize` stage
+ * (nn_quantization.py) turns a trained model into 16-bit integers for a microcontroller.  Two device entries stand behind the
+ * export (amcpy_amd/quantize.py): the calibration of every layer's range over all rows, and the integer network itself, so
+ * that what the 16-bit network answers, and where it saturates, is known before it is on the board.  Both take the rows, the
+ * column pick, the scaler and the shape exactly as amcx_mlp_classify_f32 does, launch on hip_stream, allocate nothing, never
+ * synchronise, and zero what they need zeroed with a launch of their own: they can be captured in a graph.
+ *
+ * amcx_mlp_range_f32.  params_dev: the float32 packed block.  h and every layer's sums are amcx_mlp_classify_f32's, bit for
+ * bit (the two float32 roundings of the scaler; bias first, then one float32 FMA per k = 0 ... in - 1); between the layers
+ * AMCX_ACT_RELU or AMCX_ACT_NONE (nothing: the chain the reference calibrates on); tanh and sigmoid are AMCX_EINVAL.
+ * ranges_dev: float32 [n_linear + 1][2], (min, max) of the standardised input over the n_sel columns, then of every layer's
+ * PRE-activation values over its outputs, over all rows that count; skipped_dev: one int64, the number of rows one of whose
+ * inputs or pre-activation values is not finite -- such a row contributes nothing to any range.  Min and max do not depend on
+ * the order they are taken in: the result is exact.  A zero is reported as +0.  With no row that counts a range stays
+ * (+inf, -inf).  Both pointers are required.
+ *   - checks: the limits of amcx_mlp_classify_f32 (rows, strides, columns, shape, mean and scale both or neither), the
+ *     activation; n_rows == 0 is AMCX_OK here, null pointers allowed, nothing written; null pointers (x, params, ranges,
+ *     skipped) and alignment (x, params and ranges 4, mean, scale and skipped 8); a pointer on another device.
+ *
+ * amcx_mlp_classify_q15.  params_dev: the packed block as int16, the float block's layout (per layer W[out][in] row-major,
+ * then b[out]; amcx_mlp_q15_params_shorts values, -1 for an invalid shape).  frac_input, and per layer frac_weights_host[l],
+ * frac_biases_host[l], frac_outputs_host[l] (host arrays of n_linear entries): the fractional bits Nw, Nb, No of the Q-format
+ * each int16 stands in, 0 ... 15 each.  THE ARITHMETIC, all of it exact integers (Na starts as frac_input):
+ *   input   a[k] = int(rint(clamp(h[k] * 2^Na, -16384, 16383))), h the standardised float32 value, the product and the clamp
+ *           in float32 (a power of two: the product is exact), rint to nearest-even.  (The reference's table Qm.n, m + n = 15,
+ *           holds [-2^(m-1), 2^(m-1) - 2^-n]: half of what 16 bits hold, and this is its clamp.)  A row with a non-finite h
+ *           gets label -1, zeros for logits, is counted in the extra last bin and takes no further part.
+ *   layer   P = Nw + Na;  acc = sum_k W[o][k] * a[k] + (b[o] << (P - Nb));  s = P - No;  v = (acc + 2^(s-1)) >> s, an
+ *           arithmetic shift, so a half rounds up;  out = clamp(v, -32768, 32767);  a hidden layer then takes max(out, 0);
+ *           Na becomes No.  The call is AMCX_EINVAL unless P >= Nb and P > No in every layer.
+ * The sums are exact for EVERY int16 block and every int16 activation (acc can pass 2^35: it is kept in 64 bits).  Relu only:
+ * any other activation is AMCX_EINVAL.
+ * Outputs, each pointer may be null: labels_dev[r] (int32), the first maximum of the last layer's int16 values;
+ * logits_dev[r * logits_stride + c] (int16, logits_stride >= classes); counts_dev[group][classes + 1] (int64) in
+ * amcx_mlp_classify_f32's convention; saturated_dev[n_linear + 1] (int64), counted over the rows that have a label:
+ * [0] the input values the clamp changed, [l] the outputs of layer l with v > 32767 and, for the last layer, also those with
+ * v < -32768 -- the clips that change a result (below -32768 in a hidden layer relu gives 0 either way).  The call zeroes
+ * counts_dev and saturated_dev itself.
+ *   - checks: the limits of amcx_mlp_classify_f32, the activation, the format arrays and every format's range and the two
+ *     shifts, logits_stride >= classes where logits_dev is given, whole groups; n_rows == 0 is AMCX_OK here, null pointers
+ *     allowed; null pointers (x, params) and alignment (x and labels 4, params and logits 2, mean, scale, counts and saturated
+ *     8); a pointer on another device; with no output asked for the call is AMCX_OK then, and launches nothing.
+ * amcx_kernel_name_mlp_q15 (host-only): 0 the integer network's kernel, 1 the range kernel, 2 its initialising launch; NULL
+ * for any other number.
+ */
+#define AMCX_ACT_NONE 3      /* amcx_mlp_range_f32 only */
+int amcx_mlp_range_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host,
+                       int32_t n_sel, const double* mean_dev, const double* scale_dev, const float* params_dev,
+                       const int32_t* widths_host, int32_t n_linear, int32_t activation, float* ranges_dev, int64_t* skipped_dev,
+                       void* hip_stream);
+int64_t amcx_mlp_q15_params_shorts(const int32_t* widths_host, int32_t n_linear);
+int amcx_mlp_classify_q15(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host,
+                          int32_t n_sel, const double* mean_dev, const double* scale_dev, const int16_t* params_dev,
+                          const int32_t* widths_host, int32_t n_linear, int32_t activation, int32_t frac_input,
+                          const int32_t* frac_weights_host, const int32_t* frac_biases_host, const int32_t* frac_outputs_host,
+                          int32_t* labels_dev, int16_t* logits_dev, int64_t logits_stride, int64_t rows_per_group,
+                          int64_t* counts_dev, int64_t* saturated_dev, void* hip_stream);
+const char* amcx_kernel_name_mlp_q15(int32_t which);
 
 #ifdef __cplusplus
 }
