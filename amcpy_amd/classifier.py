@@ -18,7 +18,6 @@ Nothing here computes a label on the host: without the library or a GPU these fu
 """
 from __future__ import annotations
 
-import ctypes
 import io
 import pickle
 import re
@@ -30,27 +29,11 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from ._mlp import MAX_LINEAR, MAX_WIDTH, OutputPlan, PackedMlp, accuracy_table, check_widths, params_floats, row_plan  # noqa: F401
 
-MAX_WIDTH = 32          # every layer width, input and classes included (include/amcx.h)
-MAX_LINEAR = 6
 BN_EPS = 1e-5           # torch.nn.BatchNorm1d's default, the reference's
 
 _KEY = re.compile(r"^(?:.*\.)?(\d+)\.(weight|bias|running_mean|running_var|num_batches_tracked)$")
-
-
-def _check_widths(widths) -> tuple:
-    widths = tuple(int(w) for w in widths)
-    if not 1 <= len(widths) - 1 <= MAX_LINEAR:
-        raise ValueError(f"between 1 and {MAX_LINEAR} dense layers, got {len(widths) - 1}")
-    if any(not 1 <= w <= MAX_WIDTH for w in widths):
-        raise ValueError(f"every layer width must be 1 ... {MAX_WIDTH}, got {widths}")
-    return widths
-
-
-def params_floats(widths) -> int:
-    """Length of the packed block for these widths: sum of out * in + out."""
-    widths = _check_widths(widths)
-    return sum(widths[l + 1] * widths[l] + widths[l + 1] for l in range(len(widths) - 1))
 
 
 def _array(v) -> np.ndarray:
@@ -98,30 +81,34 @@ def fold_state_dict(sd) -> tuple:
         blocks += [w.reshape(-1), b]
     if any(j < linear[0] for j in norms):
         raise ValueError("state_dict: a BatchNorm before the first Linear")
-    return _check_widths(widths), np.concatenate(blocks)
+    return check_widths(widths), np.concatenate(blocks)
 
 
-class MlpModel:
+def linear_state_dict(sd) -> dict:
+    """The ``Linear`` entries of a state_dict alone (2-D ``weight`` and its ``bias``): the chain the reference quantises."""
+    keep = {}
+    for key, val in sd.items():
+        m = _KEY.match(str(key))
+        if m is not None and m.group(2) == "weight" and _array(val).ndim == 2:
+            keep[str(key)] = val
+            bias = str(key)[:-len("weight")] + "bias"
+            if bias in sd:
+                keep[bias] = sd[bias]
+    return keep
+
+
+class MlpModel(PackedMlp):
     """A dense network as ``amcx_mlp_classify_f32`` takes it.  ``params``: the packed float32 block (per layer
     ``W'[out][in]`` row-major, then ``b'[out]``); ``params64``: the same before its single rounding, when the model
     came from a state_dict (None otherwise).  One device copy of the block per device, made on first use."""
 
     def __init__(self, widths, activation: str, params, params64=None, model_id: Optional[str] = None):
-        self.widths = _check_widths(widths)
+        super().__init__(widths, params, np.float32)
         if activation not in _lib.ACTIVATIONS:
             raise ValueError(f"activation {activation!r}: one of {sorted(_lib.ACTIVATIONS)}")
         self.activation = activation
-        self.params = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
-        if self.params.size != params_floats(self.widths):
-            raise ValueError(f"the packed block of widths {self.widths} has {params_floats(self.widths)} floats, "
-                             f"got {self.params.size}")
         self.params64 = None if params64 is None else np.asarray(params64, dtype=np.float64).reshape(-1)
         self.model_id = model_id
-        self._device_params = {}
-
-    n_linear = property(lambda self: len(self.widths) - 1)
-    n_inputs = property(lambda self: self.widths[0])
-    n_classes = property(lambda self: self.widths[-1])
 
     @classmethod
     def from_state_dict(cls, sd, activation: str = "relu", model_id: Optional[str] = None) -> "MlpModel":
@@ -133,8 +120,7 @@ class MlpModel:
         """The file the reference's ``train_model`` writes (``{"model_state_dict", "model_id", "config"}``), read by
         :func:`load_checkpoint`.  The activation comes from the stored config's ``training.activation`` when it is
         there (the argument wins when both are given), ``default_activation`` otherwise."""
-        ck = load_checkpoint(path)
-        sd = ck["model_state_dict"] if isinstance(ck, dict) and "model_state_dict" in ck else ck
+        sd, ck = checkpoint_state_dict(path)
         stored = getattr(getattr(ck.get("config") if isinstance(ck, dict) else None, "training", None), "activation", None)
         act = activation or (stored if isinstance(stored, str) else None) or default_activation
         model_id = ck.get("model_id") if isinstance(ck, dict) else None
@@ -151,14 +137,6 @@ class MlpModel:
         extra = {} if self.params64 is None else {"params64": self.params64}
         np.savez(str(path), widths=np.asarray(self.widths, np.int32), activation=np.asarray(self.activation),
                  params=self.params, model_id=np.asarray(self.model_id or ""), **extra)
-
-    def device_params(self, device):
-        import torch
-        device = torch.device(device)
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        if key not in self._device_params:
-            self._device_params[key] = torch.from_numpy(self.params).to(device)
-        return self._device_params[key]
 
 
 # ---- the checkpoint, read without running what it names ------------------------------------------------------------
@@ -224,21 +202,15 @@ def load_checkpoint(path):
     return torch.load(str(path), map_location="cpu", weights_only=False, pickle_module=module)
 
 
+def checkpoint_state_dict(path) -> tuple:
+    """``(state_dict, checkpoint)`` of a file :func:`load_checkpoint` reads: the reference's ``{"model_state_dict", ...}`` or a
+    bare state_dict."""
+    ck = load_checkpoint(path)
+    return (ck["model_state_dict"] if isinstance(ck, dict) and "model_state_dict" in ck else ck), ck
+
+
 # ---- classification --------------------------------------------------------------------------------------------------
 _OUTPUTS = ("labels", "probs", "counts")
-
-
-def _device_doubles(v, n: int, device, name: str):
-    import torch
-    if isinstance(v, torch.Tensor) and v.is_cuda:
-        if v.dtype != torch.float64 or v.device != device:
-            raise TypeError(f"{name} must be float64 on the rows' device")
-        v = v.contiguous()
-    else:
-        v = torch.as_tensor(np.asarray(v, dtype=np.float64)).to(device)
-    if v.shape != (n,):
-        raise ValueError(f"{name} must hold one value per selected column ({n}), got shape {tuple(v.shape)}")
-    return v
 
 
 def classify(feats, model: MlpModel, *, cols: Sequence[int], mean=None, scale=None, rows_per_group: Optional[int] = None,
@@ -256,49 +228,11 @@ def classify(feats, model: MlpModel, *, cols: Sequence[int], mean=None, scale=No
     One C-ABI call on the current stream; nothing is allocated inside it."""
     import torch
     from . import _stream
-    from .postprocess import _as_rows, select_cols
-    _lib.require_torch_runtime()
-    feats = _as_rows(feats)
-    want = tuple(want)
-    if not want or any(w not in _OUTPUTS for w in want) or len(set(want)) != len(want):
-        raise ValueError(f"want: a non-empty selection of {_OUTPUTS}")
-    lead, R, Cc = feats.shape[:-2], feats.shape[-2], feats.shape[-1]
-    cols = select_cols(cols, Cc)
-    if len(cols) != model.n_inputs:
-        raise ValueError(f"the model takes {model.n_inputs} inputs, {len(cols)} columns were selected")
-    if (mean is None) != (scale is None):
-        raise ValueError("mean and scale go together")
-    flat = feats if feats.dim() == 2 else feats.reshape(-1, Cc)
-    if flat.stride(-1) != 1:
-        flat = flat.contiguous()
-    n_rows = flat.shape[0]
-    dev = feats.device
-    if mean is not None:
-        mean, scale = _device_doubles(mean, len(cols), dev, "mean"), _device_doubles(scale, len(cols), dev, "scale")
-    if rows_per_group is None:
-        rows_per_group = R if "counts" in want else 0
-    rows_per_group = int(rows_per_group)
-    if "counts" in want and (rows_per_group < 1 or n_rows % rows_per_group):
-        raise ValueError(f"rows_per_group {rows_per_group} does not cut {n_rows} rows into whole groups")
-    n_cls = model.n_classes
-    # (the entry's n_rows labels and packed rows of probabilities, in the shapes returned)
-    labels = torch.empty(lead + (R,), dtype=torch.int32, device=dev) if "labels" in want else None
-    probs = torch.empty(lead + (R, n_cls), dtype=torch.float32, device=dev) if "probs" in want else None
-    n_groups = n_rows // rows_per_group if "counts" in want else 0
-    counts = torch.empty((n_groups, n_cls + 1), dtype=torch.int64, device=dev) if "counts" in want else None
-    params = model.device_params(dev)
-    cols_c = (ctypes.c_int32 * len(cols))(*cols)
-    widths_c = (ctypes.c_int32 * len(model.widths))(*model.widths)
-    ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
-    stride = flat.stride(0) if n_rows > 1 else Cc           # one row has no stride of its own (_stream.rows_of)
-    _stream.launch(flat, lambda lib, stream: lib.amcx_mlp_classify_f32(
-        flat.data_ptr(), n_rows, stride, Cc, cols_c, len(cols), ptr(mean), ptr(scale), params.data_ptr(), widths_c, model.n_linear,
-        _lib.ACTIVATIONS[model.activation], ptr(labels), ptr(probs), n_cls, rows_per_group if counts is not None else 0,
-        ptr(counts), stream))
-    out = {"labels": labels, "probs": probs,
-           "counts": counts.reshape(lead + (n_cls + 1,)) if counts is not None and rows_per_group == R and feats.dim() > 2 else counts}
-    res = tuple(out[w] for w in want)
-    return res[0] if len(res) == 1 else res
+    rows = row_plan(feats, model.n_inputs, cols, mean, scale)
+    out = OutputPlan(want, _OUTPUTS, rows, model.n_classes, rows_per_group, torch.float32)
+    _stream.launch(rows.flat, lambda lib, stream: lib.amcx_mlp_classify_f32(
+        *rows.entry_args(), *model.entry_args(rows.device), _lib.ACTIVATIONS[model.activation], *out.entry_args, stream))
+    return out.result()
 
 
 def classify_frames(iq, model: MlpModel, *, cols: Sequence[int], mean, scale, frame_size: Optional[int] = None,
@@ -323,24 +257,26 @@ def evaluate_by_snr(feats_by_mod, model: MlpModel, *, cols: Sequence[int], mean,
     column counting the rows without a label.  (The reference indexes ``mod_data[snr, :, list(used)]``, which is
     ``(6, n_frames)`` and raises in its scaler; the evident intention, ``(n_frames, 6)``, is what is taken here, as
     ``select_standardize`` does.)  One launch, one group per (modulation, SNR)."""
+    feats_by_mod, labels, n_frames = by_snr_args(feats_by_mod, model.n_classes, labels)
+    counts = classify(feats_by_mod, model, cols=cols, mean=mean, scale=scale, want=("counts",)).cpu().numpy()
+    return accuracy_table(counts, labels, n_frames)
+
+
+def by_snr_args(feats_by_mod, n_classes: int, labels) -> tuple:
+    """What :func:`evaluate_by_snr` and ``quantize.evaluate_by_snr_q15`` ask of their arguments: ``(feats_by_mod as one tensor,
+    labels as ints, n_frames)``."""
     import torch
     if not isinstance(feats_by_mod, torch.Tensor):
         feats_by_mod = torch.stack(list(feats_by_mod))
     if feats_by_mod.dim() != 4:
         raise ValueError("feats_by_mod must be (n_mods, n_snr, n_frames, C)")
-    n_mods, n_snr, n_frames, _ = feats_by_mod.shape
+    n_mods, _, n_frames, _ = feats_by_mod.shape
     labels = [int(v) for v in labels]
-    if len(labels) != n_mods or any(not 0 <= v < model.n_classes for v in labels):
-        raise ValueError(f"labels: one class 0 ... {model.n_classes - 1} per modulation ({n_mods})")
+    if len(labels) != n_mods or any(not 0 <= v < n_classes for v in labels):
+        raise ValueError(f"labels: one class 0 ... {n_classes - 1} per modulation ({n_mods})")
     if n_frames < 1:
         raise ValueError("no frames to evaluate")
-    counts = classify(feats_by_mod, model, cols=cols, mean=mean, scale=scale, want=("counts",)).cpu().numpy()
-    acc = np.zeros((n_mods, n_snr), dtype=np.float64)
-    confusion = np.zeros((model.n_classes, model.n_classes + 1), dtype=np.int64)
-    for i, lab in enumerate(labels):
-        acc[i] = counts[i, :, lab] / float(n_frames)
-        confusion[lab] += counts[i].sum(axis=0)
-    return acc, confusion
+    return feats_by_mod, labels, n_frames
 
 
 # ---- the `classify` command --------------------------------------------------------------------------------------------
@@ -385,6 +321,21 @@ def fit_scaler(cfg, mode: str, dev) -> tuple:
     return feats, mean, scale
 
 
+def open_command(cfg, model_spec: str, mode: str, device: Optional[int]) -> tuple:
+    """How the `classify` and `quantize` commands begin, before any feature file is read: the mode, the library and a device
+    present, the model, the columns ``cfg.features.used`` and the device :func:`fit_scaler` is to run on.  Returns ``(model,
+    model id, cols, dev)``."""
+    if mode not in ("training", "test"):
+        raise ValueError("mode: training or test")
+    lib = _lib.load()
+    if lib.amcx_device_count() < 1:
+        raise _lib.AmcxError(_lib.ENODEV, lib.amcx_strerror(_lib.ENODEV).decode())
+    import torch
+    model, model_id = load_model(cfg, model_spec)
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    return model, model_id, [int(c) for c in cfg.features.used], dev
+
+
 def run_classification(cfg, model_spec: str, *, mode: str = "test", from_iq: bool = False, device: Optional[int] = None,
                        verbose: bool = True):
     """The `classify` command: features from ``calculated-features/{mod}_features.mat`` (``from_iq``: extracted first,
@@ -392,31 +343,18 @@ def run_classification(cfg, model_spec: str, *, mode: str = "test", from_iq: boo
     stacks (``training_snr`` or ``all_snr``, every modulation), every (modulation, SNR, frame) classified; writes
     ``figures/{model_id}_figure_data.mat`` (key ``acc``, the reference's file) and ``{mod}_predictions.mat`` beside the
     feature files.  Returns ``(acc, confusion)``."""
-    if mode not in ("training", "test"):
-        raise ValueError("mode: training or test")
-    lib = _lib.load()
-    if lib.amcx_device_count() < 1:
-        raise _lib.AmcxError(_lib.ENODEV, lib.amcx_strerror(_lib.ENODEV).decode())
     import scipy.io
     import torch
-    model, model_id = load_model(cfg, model_spec)
-    sig, cols = cfg.signals, [int(c) for c in cfg.features.used]
+    model, model_id, cols, dev = open_command(cfg, model_spec, mode, device)
     if from_iq:
         from .feature_extraction import run_extraction
         run_extraction(cfg, device=device, verbose=verbose, feature_ids=sorted({c + 1 for c in cols}))
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
-    mods = list(sig.modulations_with_noise)
     feats, mean, scale = fit_scaler(cfg, mode, dev)
-    n_mods, n_snr, n_frames, n_cols = feats.shape
+    sig, mods, n_snr = cfg.signals, list(cfg.signals.modulations_with_noise), feats.shape[1]
     with torch.cuda.device(dev):
         labels, counts = classify(feats, model, cols=cols, mean=mean, scale=scale, want=("labels", "counts"))
         labels, counts = labels.cpu().numpy(), counts.cpu().numpy()
-    acc = np.zeros((n_mods, n_snr), dtype=np.float64)
-    confusion = np.zeros((model.n_classes, model.n_classes + 1), dtype=np.int64)
-    for i in range(n_mods):
-        lab = int(sig.labels[i])
-        acc[i] = counts[i, :, lab] / float(n_frames)
-        confusion[lab] += counts[i].sum(axis=0)
+    acc, confusion = accuracy_table(counts, [int(sig.labels[i]) for i in range(len(mods))], feats.shape[2])
     cfg.paths.ensure_dirs()
     scipy.io.savemat(str(cfg.paths.figures / f"{model_id}_figure_data.mat"), {"acc": acc})
     for i, mod in enumerate(mods):

@@ -522,6 +522,14 @@ StreamKernel<decltype(&amcx::amcx_spectrogram_c64_kernel)> psd_kernel(StreamSrc 
 bool rows_ok(int64_t n_rows, int64_t row_stride, int32_t row_elems) {
   return n_rows >= 0 && row_stride >= row_elems && (n_rows == 0 || row_stride <= (int64_t(1) << 58) / n_rows);
 }
+// an optional output of n_rows rows of row_elems elements: where it is asked for, its stride passes rows_ok
+bool opt_rows_ok(const void* out, int64_t n_rows, int64_t row_stride, int32_t row_elems) {
+  return out == nullptr || rows_ok(n_rows, row_stride, row_elems);
+}
+// rows_per_group of an entry that counts per group: never below 0, 1 at least where counts are asked for, and then whole groups
+bool groups_ok(int64_t n_rows, int64_t rows_per_group, const void* counts) {
+  return rows_per_group >= 0 && (rows_per_group > 0 || counts == nullptr) && (rows_per_group == 0 || n_rows % rows_per_group == 0);
+}
 bool threshold_ok(float threshold) { return int_scale_ok(threshold); }      // the same rule: a finite float32 > 0
 int log2_exact(int n) {      // of a power of two
   int lg = 0;
@@ -575,7 +583,8 @@ bool make_select_cols(const int32_t* cols_host, int32_t n_sel, int32_t n_cols, a
   return true;
 }
 
-// what amcx_mlp_range_f32 and amcx_mlp_classify_q15 ask of their rows, columns, scaler and shape: amcx_mlp_classify_f32's limits
+// what the three network entries (amcx_mlp_classify_f32, amcx_mlp_range_f32, amcx_mlp_classify_q15) ask of their rows, columns,
+// scaler and shape
 bool mlp_rows_ok(int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host, int32_t n_sel, const double* mean_dev,
                  const double* scale_dev, const int32_t* widths_host, int32_t n_linear, amcx::SelectCols* sel) {
   if (n_cols < 1 || n_cols > amcx::kStatMaxCols || !rows_ok(n_rows, row_stride, n_cols) || cols_host == nullptr ||
@@ -590,6 +599,14 @@ amcx::MlpShape mlp_shape(const int32_t* widths_host, int32_t n_linear, int32_t a
   shape.act = activation;
   for (int l = 0; l <= amcx::kMlpMaxLinear; ++l) shape.w[l] = l <= n_linear ? widths_host[l] : 0;
   return shape;
+}
+int64_t mlp_tiles(int64_t n_rows) { return (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows; }      // what a network kernel walks
+// n 64-bit counters to zero on the stream: a classifier's counts, the Q15 entry's saturation counters (nullptr: not asked for, no launch)
+int zero_counters(unsigned long long* counters, int64_t n, hipStream_t st, const char* what) {
+  if (counters == nullptr) return AMCX_OK;
+  const int64_t zgrid = (n + 255) / 256;
+  const hipError_t e = amcx::launch(amcx::amcx_mlp_zero_counts_kernel, zgrid < 1024 ? zgrid : 1024, 256, 0, st, counters, n);
+  return e != hipSuccess ? hip_fail(e, what) : AMCX_OK;
 }
 
 // the two launches of a statistics call, behind its entry's gate: a chunk's triple per workgroup into `ws`, then the pooling
@@ -1402,40 +1419,26 @@ int amcx_mlp_classify_f32(const float* x_dev, int64_t n_rows, int64_t row_stride
                           const float* params_dev, const int32_t* widths_host, int32_t n_linear, int32_t activation,
                           int32_t* labels_dev, float* probs_dev, int64_t probs_stride, int64_t rows_per_group,
                           int64_t* counts_dev, void* hip_stream) {
-  if (n_cols < 1 || n_cols > amcx::kStatMaxCols || !rows_ok(n_rows, row_stride, n_cols) || cols_host == nullptr ||
-      !mlp_shape_ok(widths_host, n_linear) || n_sel != widths_host[0])
-    return AMCX_EINVAL;
-  if (activation != AMCX_ACT_RELU && activation != AMCX_ACT_TANH && activation != AMCX_ACT_SIGMOID) return AMCX_EINVAL;
-  if ((mean_dev == nullptr) != (scale_dev == nullptr)) return AMCX_EINVAL;
   amcx::SelectCols sel;
-  if (!make_select_cols(cols_host, n_sel, n_cols, &sel)) return AMCX_EINVAL;
+  if (!mlp_rows_ok(n_rows, row_stride, n_cols, cols_host, n_sel, mean_dev, scale_dev, widths_host, n_linear, &sel)) return AMCX_EINVAL;
+  if (activation != AMCX_ACT_RELU && activation != AMCX_ACT_TANH && activation != AMCX_ACT_SIGMOID) return AMCX_EINVAL;
   const int n_cls = widths_host[n_linear];
-  if (probs_dev != nullptr && !rows_ok(n_rows, probs_stride, n_cls)) return AMCX_EINVAL;
-  if (rows_per_group < 0 || (rows_per_group == 0 && counts_dev != nullptr)) return AMCX_EINVAL;
-  if (rows_per_group > 0 && n_rows % rows_per_group != 0) return AMCX_EINVAL;
+  if (!opt_rows_ok(probs_dev, n_rows, probs_stride, n_cls) || !groups_ok(n_rows, rows_per_group, counts_dev)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
   if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, false}, {scale_dev, 7u, false}, {params_dev, 3u, true}, {labels_dev, 3u, false},
                 {probs_dev, 3u, false}, {counts_dev, 7u, false}}))
     return AMCX_EINVAL;
   if (labels_dev == nullptr && probs_dev == nullptr && counts_dev == nullptr) return AMCX_OK;      // nothing asked for
-  amcx::MlpShape shape;
-  shape.n_linear = n_linear;
-  shape.act = activation;
-  for (int l = 0; l <= amcx::kMlpMaxLinear; ++l) shape.w[l] = l <= n_linear ? widths_host[l] : 0;
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   unsigned long long* const counts = reinterpret_cast<unsigned long long*>(counts_dev);
-  if (counts != nullptr) {
-    const int64_t bins = (n_rows / rows_per_group) * (int64_t)(n_cls + 1);
-    const int64_t zgrid = (bins + 255) / 256;
-    const hipError_t e = amcx::launch(amcx::amcx_mlp_zero_counts_kernel, zgrid < 1024 ? zgrid : 1024, 256, 0, st, counts, bins);
-    if (e != hipSuccess) return hip_fail(e, "classifier count-zeroing kernel launch");
-  }
+  const int64_t bins = counts != nullptr ? (n_rows / rows_per_group) * (int64_t)(n_cls + 1) : 0;
+  if (const int rc = zero_counters(counts, bins, st, "classifier count-zeroing kernel launch")) return rc;
   // every workgroup stages the parameters once, then walks tiles
-  const int64_t tiles = (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows;
+  const int64_t tiles = mlp_tiles(n_rows);
   const int64_t grid = amcx::persistent_grid(cu_count(), 4, tiles, 1);
   const hipError_t e = amcx::launch(amcx::amcx_mlp_classify_kernel, grid, amcx::kMlpThreads, 0, st, x_dev, n_rows, row_stride, sel,
-                                    mean_dev, scale_dev, params_dev, shape, labels_dev, probs_dev, probs_stride,
-                                    counts != nullptr ? rows_per_group : 1, counts, tiles);
+                                    mean_dev, scale_dev, params_dev, mlp_shape(widths_host, n_linear, activation), labels_dev, probs_dev,
+                                    probs_stride, counts != nullptr ? rows_per_group : 1, counts, tiles);
   if (e != hipSuccess) return hip_fail(e, "classifier kernel launch");
   return AMCX_OK;
 }
@@ -1461,11 +1464,10 @@ int amcx_mlp_range_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, i
   unsigned long long* const skipped = reinterpret_cast<unsigned long long*>(skipped_dev);
   hipError_t e = amcx::launch(amcx::amcx_mlp_range_init_kernel, 1, 64, 0, st, ranges_dev, n_linear + 1, skipped);
   if (e != hipSuccess) return hip_fail(e, "range initialising kernel launch");
-  const amcx::MlpShape shape = mlp_shape(widths_host, n_linear, activation);
-  const int64_t tiles = (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows;
+  const int64_t tiles = mlp_tiles(n_rows);
   const int64_t grid = amcx::persistent_grid(cu_count(), 2, tiles, 1);         // 53 KiB of LDS: two workgroups a CU
   e = amcx::launch(amcx::amcx_mlp_range_kernel, grid, amcx::kMlpThreads, 0, st, x_dev, n_rows, row_stride, sel, mean_dev, scale_dev,
-                   params_dev, shape, ranges_dev, skipped, tiles);
+                   params_dev, mlp_shape(widths_host, n_linear, activation), ranges_dev, skipped, tiles);
   if (e != hipSuccess) return hip_fail(e, "range kernel launch");
   return AMCX_OK;
 }
@@ -1497,9 +1499,7 @@ int amcx_mlp_classify_q15(const float* x_dev, int64_t n_rows, int64_t row_stride
     na = no;
   }
   const int n_cls = widths_host[n_linear];
-  if (logits_dev != nullptr && !rows_ok(n_rows, logits_stride, n_cls)) return AMCX_EINVAL;
-  if (rows_per_group < 0 || (rows_per_group == 0 && counts_dev != nullptr)) return AMCX_EINVAL;
-  if (rows_per_group > 0 && n_rows % rows_per_group != 0) return AMCX_EINVAL;
+  if (!opt_rows_ok(logits_dev, n_rows, logits_stride, n_cls) || !groups_ok(n_rows, rows_per_group, counts_dev)) return AMCX_EINVAL;
   if (n_rows == 0) return AMCX_OK;
   if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, false}, {scale_dev, 7u, false}, {params_dev, 1u, true}, {labels_dev, 3u, false},
                 {logits_dev, 1u, false}, {counts_dev, 7u, false}, {saturated_dev, 7u, false}}))
@@ -1508,22 +1508,14 @@ int amcx_mlp_classify_q15(const float* x_dev, int64_t n_rows, int64_t row_stride
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   unsigned long long* const counts = reinterpret_cast<unsigned long long*>(counts_dev);
   unsigned long long* const saturated = reinterpret_cast<unsigned long long*>(saturated_dev);
-  if (counts != nullptr) {
-    const int64_t bins = (n_rows / rows_per_group) * (int64_t)(n_cls + 1);
-    const int64_t zgrid = (bins + 255) / 256;
-    const hipError_t e = amcx::launch(amcx::amcx_mlp_zero_counts_kernel, zgrid < 1024 ? zgrid : 1024, 256, 0, st, counts, bins);
-    if (e != hipSuccess) return hip_fail(e, "Q15 count-zeroing kernel launch");
-  }
-  if (saturated != nullptr) {
-    const hipError_t e = amcx::launch(amcx::amcx_mlp_zero_counts_kernel, 1, 256, 0, st, saturated, (long long)(n_linear + 1));
-    if (e != hipSuccess) return hip_fail(e, "Q15 saturation-zeroing kernel launch");
-  }
-  const amcx::MlpShape shape = mlp_shape(widths_host, n_linear, activation);
-  const int64_t tiles = (n_rows + amcx::kMlpTileRows - 1) / amcx::kMlpTileRows;
+  const int64_t bins = counts != nullptr ? (n_rows / rows_per_group) * (int64_t)(n_cls + 1) : 0;
+  if (const int rc = zero_counters(counts, bins, st, "Q15 count-zeroing kernel launch")) return rc;
+  if (const int rc = zero_counters(saturated, n_linear + 1, st, "Q15 saturation-zeroing kernel launch")) return rc;
+  const int64_t tiles = mlp_tiles(n_rows);
   const int64_t grid = amcx::persistent_grid(cu_count(), 4, tiles, 1);
   const hipError_t e = amcx::launch(amcx::amcx_mlp_q15_kernel, grid, amcx::kMlpThreads, 0, st, x_dev, n_rows, row_stride, sel, mean_dev,
-                                    scale_dev, params_dev, shape, fmt, labels_dev, logits_dev, logits_stride,
-                                    counts != nullptr ? rows_per_group : 1, counts, saturated, tiles);
+                                    scale_dev, params_dev, mlp_shape(widths_host, n_linear, activation), fmt, labels_dev, logits_dev,
+                                    logits_stride, counts != nullptr ? rows_per_group : 1, counts, saturated, tiles);
   if (e != hipSuccess) return hip_fail(e, "Q15 classifier kernel launch");
   return AMCX_OK;
 }

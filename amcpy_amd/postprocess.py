@@ -33,7 +33,8 @@ def _as_rows(feats):
 
 
 def select_cols(cols, n_cols: int) -> list:
-    """The 0-based column selection of :func:`select_standardize`, ``classifier.classify`` and ``classify_frames`` as ints:
+    """The 0-based column selection of :func:`select_standardize`, ``classifier.classify_frames`` and the network entries' row plan
+    (``_mlp.row_plan``: ``classify``, ``quantize.calibrate``, ``quantize.classify_q15``) as ints:
     every index a column of the ``n_cols``, 1 ... 32 of them out of 32 at most."""
     cols = [int(c) for c in cols]
     if any(c < 0 or c >= n_cols for c in cols):

@@ -23,13 +23,14 @@ does not define.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from .classifier import MlpModel, _check_widths, _device_doubles, fold_state_dict, params_floats
+from ._mlp import OutputPlan, PackedMlp, accuracy_table, check_widths, i32s, layers as _layers, ptr, row_plan
+from .classifier import (MlpModel, by_snr_args, checkpoint_state_dict, classify, fit_scaler, fold_state_dict, linear_state_dict,
+                         open_command, resolve_model_path)
 
 # the reference's table, narrowest first: (integer bits m, fractional bits n)
 Q_FORMATS = tuple((m, 15 - m) for m in range(7))
@@ -65,23 +66,13 @@ def quantize_array(a, n_frac: int) -> np.ndarray:
     return np.rint(clamped * np.float32(2.0 ** int(n_frac))).astype(np.int16)
 
 
-def _layers(widths, block) -> list:
-    """[(W (out, in), b (out,))] views of a packed block."""
-    out, at = [], 0
-    for l in range(len(widths) - 1):
-        n_in, n_out = widths[l], widths[l + 1]
-        out.append((block[at:at + n_out * n_in].reshape(n_out, n_in), block[at + n_out * n_in:at + n_out * n_in + n_out]))
-        at += n_out * n_in + n_out
-    return out
-
-
 def normalize_block(widths, block32, ranges) -> tuple:
     """``(block, ranges, shifts)``: the packed float32 block with layer l scaled by ``2^-k_l``, ``k_l`` the smallest for which the
     layer's range -- ``(0, max)`` of a hidden layer, ``(min, max)`` of the last, times the factors of the layers before it -- lies
     inside Q6.9, and its bias by ``2^-shifts[l]``, ``shifts[l] = k_0 + ... + k_l``; the ranges scaled the same way.  Powers of two:
     every product is exact (short of underflow), so the scaled network's pre-activation values are the original's times
     ``2^-shifts[l]`` bit for bit and its labels are the original's.  All ``k_l`` are 0 where every range fits the table."""
-    widths = _check_widths(widths)
+    widths = check_widths(widths)
     n_linear = len(widths) - 1
     ranges = _check_ranges(ranges, n_linear).astype(np.float64)
     flo, fhi = q_range(FALLBACK_FRAC)
@@ -99,20 +90,6 @@ def normalize_block(widths, block32, ranges) -> tuple:
     return np.concatenate(out).astype(np.float32), ranges.astype(np.float32), tuple(shifts)
 
 
-def linear_state_dict(sd) -> dict:
-    """The ``Linear`` entries of a state_dict alone (2-D ``weight`` and its ``bias``): the chain the reference quantises."""
-    from .classifier import _KEY, _array
-    keep = {}
-    for key, val in sd.items():
-        m = _KEY.match(str(key))
-        if m is not None and m.group(2) == "weight" and _array(val).ndim == 2:
-            keep[str(key)] = val
-            bias = str(key)[:-len("weight")] + "bias"
-            if bias in sd:
-                keep[bias] = sd[bias]
-    return keep
-
-
 def linear_model(sd, model_id: Optional[str] = None) -> MlpModel:
     """The ``Linear`` layers of a state_dict as stored, every BatchNorm ignored, as a model :func:`calibrate` takes (with
     ``activation="none"``: the chain the reference's ``quantize`` takes its output ranges from)."""
@@ -128,16 +105,13 @@ def _check_ranges(ranges, n_linear: int) -> np.ndarray:
     return ranges
 
 
-class QuantizedMlp:
+class QuantizedMlp(PackedMlp):
     """A dense network as ``amcx_mlp_classify_q15`` takes it: ``params`` the packed int16 block (per layer ``W[out][in]``
     row-major, then ``b[out]``), ``frac_input`` and per layer ``frac_weights``, ``frac_biases``, ``frac_outputs``."""
 
     def __init__(self, widths, params, frac_input: int, frac_weights, frac_biases, frac_outputs, *, layout: str = "folded",
                  model_id: Optional[str] = None, ranges=None, layer_shifts=None):
-        self.widths = _check_widths(widths)
-        self.params = np.ascontiguousarray(params, dtype=np.int16).reshape(-1)
-        if self.params.size != params_floats(self.widths):
-            raise ValueError(f"the packed block of widths {self.widths} has {params_floats(self.widths)} values, got {self.params.size}")
+        super().__init__(widths, params, np.int16)
         self.frac_input = int(frac_input)
         self.frac_weights, self.frac_biases, self.frac_outputs = (tuple(int(v) for v in f) for f in (frac_weights, frac_biases, frac_outputs))
         if any(len(f) != self.n_linear for f in (self.frac_weights, self.frac_biases, self.frac_outputs)):
@@ -160,16 +134,11 @@ class QuantizedMlp:
         self.layer_shifts = tuple(int(v) for v in layer_shifts) if layer_shifts is not None else (0,) * self.n_linear
         if len(self.layer_shifts) != self.n_linear:
             raise ValueError(f"one shift per layer ({self.n_linear})")
-        self._device_params = {}
-
-    n_linear = property(lambda self: len(self.widths) - 1)
-    n_inputs = property(lambda self: self.widths[0])
-    n_classes = property(lambda self: self.widths[-1])
 
     # -- construction ---------------------------------------------------------------------------------------------------------
     @classmethod
     def _from_block(cls, widths, block32, ranges, layout, model_id, normalize=False) -> "QuantizedMlp":
-        widths = _check_widths(widths)
+        widths = check_widths(widths)
         n_linear = len(widths) - 1
         ranges = _check_ranges(ranges, n_linear)
         block32 = np.asarray(block32, dtype=np.float32).reshape(-1)
@@ -252,41 +221,9 @@ class QuantizedMlp:
             out["mean"], out["scale"] = np.asarray(mean, np.float64), np.asarray(scale, np.float64)
         scipy.io.savemat(str(path), out)
 
-    def device_params(self, device):
-        import torch
-        device = torch.device(device)
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        if key not in self._device_params:
-            self._device_params[key] = torch.from_numpy(self.params).to(device)
-        return self._device_params[key]
-
 
 # ---- the device ------------------------------------------------------------------------------------------------------------
 _RANGE_ACTS = {"relu": _lib.ACT_RELU, "none": _lib.ACT_NONE}
-
-
-def _rows(feats, n_inputs: int, cols, mean, scale):
-    """What both entries take of the rows: ``(flat, n_rows, stride, cols array, mean, scale)``."""
-    from .postprocess import _as_rows, select_cols
-    _lib.require_torch_runtime()
-    feats = _as_rows(feats)
-    Cc = feats.shape[-1]
-    cols = select_cols(cols, Cc)
-    if len(cols) != n_inputs:
-        raise ValueError(f"the model takes {n_inputs} inputs, {len(cols)} columns were selected")
-    if (mean is None) != (scale is None):
-        raise ValueError("mean and scale go together")
-    flat = feats if feats.dim() == 2 else feats.reshape(-1, Cc)
-    if flat.stride(-1) != 1:
-        flat = flat.contiguous()
-    if mean is not None:
-        mean, scale = _device_doubles(mean, len(cols), feats.device, "mean"), _device_doubles(scale, len(cols), feats.device, "scale")
-    stride = flat.stride(0) if flat.shape[0] > 1 else Cc
-    return feats, flat, int(flat.shape[0]), stride, (ctypes.c_int32 * len(cols))(*cols), len(cols), mean, scale
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def calibrate(feats, model: MlpModel, *, cols: Sequence[int], mean=None, scale=None, activation: str = "relu") -> tuple:
@@ -297,18 +234,14 @@ def calibrate(feats, model: MlpModel, *, cols: Sequence[int], mean=None, scale=N
     import torch
     if activation not in _RANGE_ACTS:
         raise ValueError(f"activation {activation!r}: relu or none (tanh and sigmoid have no fixed-point form here)")
-    feats, flat, n_rows, stride, cols_c, n_sel, mean, scale = _rows(feats, model.n_inputs, cols, mean, scale)
-    if n_rows < 1:
+    rows = row_plan(feats, model.n_inputs, cols, mean, scale)
+    if rows.n_rows < 1:
         raise ValueError("no rows to calibrate on")
-    dev = feats.device
-    ranges = torch.empty((model.n_linear + 1, 2), dtype=torch.float32, device=dev)
-    skipped = torch.empty((1,), dtype=torch.int64, device=dev)
-    params = model.device_params(dev)
-    widths_c = (ctypes.c_int32 * len(model.widths))(*model.widths)
+    ranges = torch.empty((model.n_linear + 1, 2), dtype=torch.float32, device=rows.device)
+    skipped = torch.empty((1,), dtype=torch.int64, device=rows.device)
     from . import _stream
-    _stream.launch(flat, lambda lib, stream: lib.amcx_mlp_range_f32(
-        flat.data_ptr(), n_rows, stride, feats.shape[-1], cols_c, n_sel, _ptr(mean), _ptr(scale), params.data_ptr(), widths_c,
-        model.n_linear, _RANGE_ACTS[activation], ranges.data_ptr(), skipped.data_ptr(), stream))
+    _stream.launch(rows.flat, lambda lib, stream: lib.amcx_mlp_range_f32(
+        *rows.entry_args(), *model.entry_args(rows.device), _RANGE_ACTS[activation], ranges.data_ptr(), skipped.data_ptr(), stream))
     return ranges.cpu().numpy(), int(skipped.item())
 
 
@@ -323,57 +256,24 @@ def classify_q15(feats, qmodel: QuantizedMlp, *, cols: Sequence[int], mean=None,
     :func:`amcpy_amd.classifier.classify` gives them; ``"saturated"`` int64 ``(n_linear + 1,)``."""
     import torch
     from . import _stream
-    want = tuple(want)
-    if not want or any(w not in _OUTPUTS for w in want) or len(set(want)) != len(want):
-        raise ValueError(f"want: a non-empty selection of {_OUTPUTS}")
     if qmodel.activation != "relu":
         raise ValueError(f"fixed point is defined for relu alone, got activation {qmodel.activation!r}")
-    feats, flat, n_rows, stride, cols_c, n_sel, mean, scale = _rows(feats, qmodel.n_inputs, cols, mean, scale)
-    lead, R, dev, n_cls = feats.shape[:-2], feats.shape[-2], feats.device, qmodel.n_classes
-    if rows_per_group is None:
-        rows_per_group = R if "counts" in want else 0
-    rows_per_group = int(rows_per_group)
-    if "counts" in want and (rows_per_group < 1 or n_rows % rows_per_group):
-        raise ValueError(f"rows_per_group {rows_per_group} does not cut {n_rows} rows into whole groups")
-    labels = torch.empty(lead + (R,), dtype=torch.int32, device=dev) if "labels" in want else None
-    logits = torch.empty(lead + (R, n_cls), dtype=torch.int16, device=dev) if "logits" in want else None
-    n_groups = n_rows // rows_per_group if "counts" in want else 0
-    counts = torch.empty((n_groups, n_cls + 1), dtype=torch.int64, device=dev) if "counts" in want else None
-    saturated = torch.empty((qmodel.n_linear + 1,), dtype=torch.int64, device=dev) if "saturated" in want else None
-    params = qmodel.device_params(dev)
-    i32s = lambda v: (ctypes.c_int32 * len(v))(*v)     # noqa: E731
-    widths_c, fw, fb, fo = i32s(qmodel.widths), i32s(qmodel.frac_weights), i32s(qmodel.frac_biases), i32s(qmodel.frac_outputs)
-    _stream.launch(flat, lambda lib, stream: lib.amcx_mlp_classify_q15(
-        flat.data_ptr(), n_rows, stride, feats.shape[-1], cols_c, n_sel, _ptr(mean), _ptr(scale), params.data_ptr(), widths_c,
-        qmodel.n_linear, _lib.ACT_RELU, qmodel.frac_input, fw, fb, fo, _ptr(labels), _ptr(logits), n_cls,
-        rows_per_group if counts is not None else 0, _ptr(counts), _ptr(saturated), stream))
-    out = {"labels": labels, "logits": logits, "saturated": saturated,
-           "counts": counts.reshape(lead + (n_cls + 1,)) if counts is not None and rows_per_group == R and feats.dim() > 2 else counts}
-    res = tuple(out[w] for w in want)
-    return res[0] if len(res) == 1 else res
+    rows = row_plan(feats, qmodel.n_inputs, cols, mean, scale)
+    out = OutputPlan(want, _OUTPUTS, rows, qmodel.n_classes, rows_per_group, torch.int16)
+    saturated = torch.empty((qmodel.n_linear + 1,), dtype=torch.int64, device=rows.device) if "saturated" in out.want else None
+    out.out["saturated"] = saturated
+    fw, fb, fo = i32s(qmodel.frac_weights), i32s(qmodel.frac_biases), i32s(qmodel.frac_outputs)
+    _stream.launch(rows.flat, lambda lib, stream: lib.amcx_mlp_classify_q15(
+        *rows.entry_args(), *qmodel.entry_args(rows.device), _lib.ACT_RELU, qmodel.frac_input, fw, fb, fo, *out.entry_args,
+        ptr(saturated), stream))
+    return out.result()
 
 
 def evaluate_by_snr_q15(feats_by_mod, qmodel: QuantizedMlp, *, cols: Sequence[int], mean, scale, labels: Sequence[int]):
     """:func:`amcpy_amd.classifier.evaluate_by_snr` for the integer network: ``(acc, confusion, saturated)``."""
-    import torch
-    if not isinstance(feats_by_mod, torch.Tensor):
-        feats_by_mod = torch.stack(list(feats_by_mod))
-    if feats_by_mod.dim() != 4:
-        raise ValueError("feats_by_mod must be (n_mods, n_snr, n_frames, C)")
-    n_mods, n_snr, n_frames, _ = feats_by_mod.shape
-    labels = [int(v) for v in labels]
-    if len(labels) != n_mods or any(not 0 <= v < qmodel.n_classes for v in labels):
-        raise ValueError(f"labels: one class 0 ... {qmodel.n_classes - 1} per modulation ({n_mods})")
-    if n_frames < 1:
-        raise ValueError("no frames to evaluate")
+    feats_by_mod, labels, n_frames = by_snr_args(feats_by_mod, qmodel.n_classes, labels)
     counts, saturated = classify_q15(feats_by_mod, qmodel, cols=cols, mean=mean, scale=scale, want=("counts", "saturated"))
-    counts = counts.cpu().numpy()
-    acc = np.zeros((n_mods, n_snr), dtype=np.float64)
-    confusion = np.zeros((qmodel.n_classes, qmodel.n_classes + 1), dtype=np.int64)
-    for i, lab in enumerate(labels):
-        acc[i] = counts[i, :, lab] / float(n_frames)
-        confusion[lab] += counts[i].sum(axis=0)
-    return acc, confusion, saturated.cpu().numpy()
+    return (*accuracy_table(counts.cpu().numpy(), labels, n_frames), saturated.cpu().numpy())
 
 
 # ---- the `quantize` command --------------------------------------------------------------------------------------------------
@@ -391,18 +291,13 @@ def run_quantization(cfg, model_spec: str, *, mode: str = "test", layout: str = 
         raise ValueError("layout: reference or folded")
     if evaluate and layout != "folded":
         raise ValueError("--evaluate runs the trained network: the folded layout (the reference layout ignores every BatchNorm)")
-    lib = _lib.load()
-    if lib.amcx_device_count() < 1:
-        raise _lib.AmcxError(_lib.ENODEV, lib.amcx_strerror(_lib.ENODEV).decode())
     import scipy.io
     import torch
-    from .classifier import classify, fit_scaler, load_checkpoint, load_model, resolve_model_path
-    model, model_id = load_model(cfg, model_spec)
+    model, model_id, cols, dev = open_command(cfg, model_spec, mode, device)
     if model.activation != "relu":
         raise ValueError(f"fixed point is defined for relu alone, the model's activation is {model.activation!r}")
-    sig, cols = cfg.signals, [int(c) for c in cfg.features.used]
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
     feats, mean, scale = fit_scaler(cfg, mode, dev)
+    sig = cfg.signals
     n_mods, n_snr, n_frames, _ = feats.shape
     cfg.paths.ensure_dirs()
     cfg.paths.arm_data.mkdir(parents=True, exist_ok=True)
@@ -411,8 +306,7 @@ def run_quantization(cfg, model_spec: str, *, mode: str = "test", layout: str = 
             path = resolve_model_path(cfg, model_spec)
             if path.suffix == ".npz":
                 raise ValueError("the reference layout needs the checkpoint's state_dict (a .pt file): a .npz model is folded already")
-            ck = load_checkpoint(path)
-            sd = ck["model_state_dict"] if isinstance(ck, dict) and "model_state_dict" in ck else ck
+            sd, _ = checkpoint_state_dict(path)
             ranges, skipped = calibrate(feats, linear_model(sd), cols=cols, mean=mean, scale=scale, activation="none")
             q = QuantizedMlp.from_state_dict(sd, ranges, layout="reference", model_id=model_id)
             out_path = cfg.paths.arm_data / "w_and_b.mat"
@@ -436,10 +330,8 @@ def run_quantization(cfg, model_spec: str, *, mode: str = "test", layout: str = 
         lab_f, counts_f = classify(feats, model, cols=cols, mean=mean, scale=scale, want=("labels", "counts"))
         agreement = (lab_q == lab_f).to(torch.float64).mean(dim=-1).cpu().numpy()
         counts_q, counts_f, saturated = counts_q.cpu().numpy(), counts_f.cpu().numpy(), saturated.cpu().numpy()
-    acc, acc_float = np.zeros((n_mods, n_snr)), np.zeros((n_mods, n_snr))
-    for i in range(n_mods):
-        lab = int(sig.labels[i])
-        acc[i], acc_float[i] = counts_q[i, :, lab] / float(n_frames), counts_f[i, :, lab] / float(n_frames)
+    labels = [int(sig.labels[i]) for i in range(n_mods)]
+    acc, acc_float = accuracy_table(counts_q, labels, n_frames)[0], accuracy_table(counts_f, labels, n_frames)[0]
     result = {"acc": acc, "acc_float": acc_float, "agreement": agreement, "saturated": saturated}
     scipy.io.savemat(str(cfg.paths.figures / f"{model_id}_q15_figure_data.mat"), result)
     if verbose:

@@ -234,3 +234,25 @@ def test_classify_command_parses_and_resolves_models(tmp_path, capsys):
     assert resolve_model_path(cfg, "some/dir/model-x.pt") == Path("some/dir/model-x.pt")
     e = build_parser().parse_args(["extract", "--root", str(tmp_path)])       # `extract` is untouched
     assert e.command == "extract" and e.features == "all"
+
+
+def test_accuracy_table_equals_a_direct_count():
+    """acc and confusion of hand-made counts (3 modulations, 2 SNRs, 3 classes and the bin of the rows without a label), two
+    modulations of one class: against the counts read off directly."""
+    from amcpy_amd.classifier import accuracy_table
+    n_frames, labels = 10, [2, 0, 2]
+    counts = np.array([[[1, 2, 6, 1], [0, 0, 10, 0]],
+                       [[7, 0, 1, 2], [3, 3, 3, 1]],
+                       [[5, 1, 4, 0], [0, 2, 5, 3]]], dtype=np.int64)
+    assert counts.shape == (3, 2, 4) and (counts.sum(axis=2) == n_frames).all() and counts[:, :, 3].sum() > 0
+    acc, confusion = accuracy_table(counts, labels, n_frames)
+    assert acc.dtype == np.float64 and acc.shape == (3, 2)
+    assert np.array_equal(acc, np.array([[6, 10], [7, 3], [4, 5]]) / 10.0)
+    assert confusion.dtype == np.int64 and confusion.shape == (3, 4)
+    want = np.zeros((3, 4), dtype=np.int64)
+    for mod, lab in enumerate(labels):
+        for snr in range(2):
+            for predicted in range(4):
+                want[lab, predicted] += counts[mod, snr, predicted]
+    assert np.array_equal(confusion, want)
+    assert np.array_equal(confusion, [[10, 3, 4, 3], [0, 0, 0, 0], [6, 5, 25, 4]]) and confusion.sum() == counts.sum()

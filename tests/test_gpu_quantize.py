@@ -444,3 +444,54 @@ def test_agreement_with_the_float_labels_on_the_reference_fixture():
     assert np.array_equal(acc, np.stack([(lab[0] == 3).mean(axis=1), (lab[1] == 0).mean(axis=1)])) and not sat.any()
     assert confusion.sum() == 8192 and np.array_equal(confusion[3][:6], np.bincount(lab[0].reshape(-1), minlength=6))
     print(f"\nclassifier_ref_relu on 8192 rows: Q15 and float labels agree on {(labels == float_labels).double().mean().item():.4%}")
+
+
+def test_leading_dimensions_and_groups_shape_both_classifiers_alike():
+    """classify and classify_q15 on a (2, 3, 5, C) view with padding -- one that flattens to a strided view and one that has to be
+    copied -- with want=("labels", "counts"): labels (2, 3, 5), counts over the rows axis (2, 3, n_classes + 1), and with
+    rows_per_group=15 (2, n_classes + 1).  Thirty rows of a fixture network each, one of them with a NaN (label -1, the last bin):
+    the float labels are argmax(p64) (every row's top-two margin is far beyond 8 x ref32_err, asserted), the integer ones the
+    int64 restatement's (the fixture whose first thirty rows get four different labels), compared with ==."""
+    import torch
+    from amcpy_amd import quantize as qz
+    from amcpy_amd.classifier import MlpModel, classify
+    zf = np.load(GOLDEN / "classifier_ref_odd.npz", allow_pickle=False)
+    model = MlpModel.from_state_dict(state_dict_of(zf), str(zf["activation"]))
+    s = np.sort(zf["p64"][:30], axis=1)
+    assert (s[:, -1] - s[:, -2]).min() > 8 * float(zf["ref32_err"])
+    xf, want_f = zf["x"][:30].copy(), zf["p64"][:30].argmax(1)
+    xf[7, 0], want_f[7] = np.nan, -1
+    zq = np.load(GOLDEN / "quantize_ref_default.npz", allow_pickle=False)
+    q = qz.QuantizedMlp.from_state_dict(state_dict_of(zq), zq["ranges"], layout="reference")
+    xq = zq["x"][:30].copy()
+    xq[7, 0] = np.nan
+    want_q = {g: qr.classify_q15(xq, range(q.n_inputs), None, None, q.widths, q.params, q.frac_input, q.frac_weights,
+                                 q.frac_biases, q.frac_outputs, g) for g in (5, 15)}
+    assert len(set(want_q[5][0].tolist())) >= 4 and want_q[5][0][7] == -1
+
+    def counts_of(labels, n_cls, g):
+        return np.stack([np.bincount(np.where(r < 0, n_cls, r), minlength=n_cls + 1) for r in labels.reshape(-1, g)])
+
+    def views(x):
+        n = x.shape[1]
+        strided = torch.full((2, 3, 5, n + 7), float("nan"), dtype=torch.float32, device="cuda")[..., 2:2 + n]
+        copied = torch.full((2, 3, 6, n + 7), float("nan"), dtype=torch.float32, device="cuda")[:, :, 1:, 2:2 + n]
+        for v in (strided, copied):
+            v.copy_(torch.from_numpy(x.reshape(2, 3, 5, n)))
+        assert strided.reshape(-1, n).data_ptr() == strided.data_ptr() and copied.reshape(-1, n).data_ptr() != copied.data_ptr()
+        return strided, copied
+
+    for run, x, n_cls, want_labels, want_counts in (
+            (lambda f, **kw: classify(f, model, cols=range(model.n_inputs), want=("labels", "counts"), **kw), xf, model.n_classes,
+             want_f, {g: counts_of(want_f, model.n_classes, g) for g in (5, 15)}),
+            (lambda f, **kw: qz.classify_q15(f, q, cols=range(q.n_inputs), want=("labels", "counts"), **kw), xq, q.n_classes,
+             want_q[5][0], {g: want_q[g][2] for g in (5, 15)})):
+        for feats in views(x):
+            labels, counts = run(feats)
+            assert labels.shape == (2, 3, 5) and labels.dtype == torch.int32
+            assert counts.shape == (2, 3, n_cls + 1) and counts.dtype == torch.int64
+            assert np.array_equal(labels.cpu().numpy().reshape(-1), want_labels)
+            assert np.array_equal(counts.cpu().numpy().reshape(6, n_cls + 1), want_counts[5])
+            labels15, counts15 = run(feats, rows_per_group=15)
+            assert labels15.shape == (2, 3, 5) and counts15.shape == (2, n_cls + 1)
+            assert torch.equal(labels15, labels) and np.array_equal(counts15.cpu().numpy(), want_counts[15])
