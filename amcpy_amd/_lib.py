@@ -13,6 +13,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
 ABI_VERSION = 16        # the version this binding was written against; any library >= it will do (include/amcx.h)
+ABI_MINOR = 1           # ... and, at that version, the additions it needs (AMCX_ABI_MINOR: 16.1 = training)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -27,6 +28,7 @@ IQ8_SCALE = 2.0 ** -7                                    # the default 8-bit sca
 ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2                # AMCX_ACT_* (ABI 8)
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
 ACT_NONE = 3                                             # AMCX_ACT_NONE (ABI 16): amcx_mlp_range_f32 only
+OPT_RMSPROP, OPT_ADAM = 0, 1                             # AMCX_OPT_* (ABI 16.1)
 
 
 class UploadStats(C.Structure):
@@ -132,6 +134,13 @@ SIGNATURES = {
     "amcx_mlp_classify_q15": (C.c_int, [_vp, _i64, _i64, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, C.POINTER(_i32), _i32, _i32,
                                         _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "amcx_kernel_name_mlp_q15": (C.c_char_p, [_i32]),
+    "amcx_mlp_train_state_floats": (_i64, [C.POINTER(_i32), _i32, C.c_uint32, _i32]),
+    "amcx_mlp_train_workspace_floats": (_i64, [C.POINTER(_i32), _i32, _i32]),
+    "amcx_mlp_train_f32": (C.c_int, [_vp, _i64, _i64, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp, _vp, _i64, _i64, C.POINTER(_i32), _i32,
+                                     _i32, C.c_uint32, _i32, _i32, _i32, _vp, _vp, _vp, _fp, C.POINTER(C.c_uint32), _fp,
+                                     C.POINTER(C.c_uint64), _i64, _i32, _vp, _vp]),
+    "amcx_kernel_name_mlp_train": (C.c_char_p, [_i32, _i32]),
+    "amcx_abi_minor": (C.c_int, []),
 }
 
 _lib = None
@@ -183,6 +192,8 @@ def load(skip_torch: bool = False) -> C.CDLL:
     got = lib.amcx_abi_version()
     if got < ABI_VERSION:
         raise ImportError(f"libamcx ABI {got} is older than the {ABI_VERSION} this binding needs")
+    if got == ABI_VERSION and lib.amcx_abi_minor() < ABI_MINOR:
+        raise ImportError(f"libamcx ABI {got}.{lib.amcx_abi_minor()} is older than the {ABI_VERSION}.{ABI_MINOR} this binding needs")
     _lib = lib
     return lib
 
@@ -307,6 +318,14 @@ def kernel_name_mlp_q15(which: int = 0) -> str:
     name = load().amcx_kernel_name_mlp_q15(int(which))
     if name is None:
         raise ValueError(f"amcx: no fixed-point kernel number {which}")
+    return name.decode()
+
+
+def kernel_name_mlp_train(activation: str = "relu", optimizer: str = "rmsprop") -> str:
+    """amcx_kernel_name_mlp_train: the training kernel of an (activation, optimizer) (host-only)."""
+    name = load().amcx_kernel_name_mlp_train(ACTIVATIONS.get(activation, -2), {"rmsprop": OPT_RMSPROP, "adam": OPT_ADAM}.get(optimizer, -2))
+    if name is None:
+        raise ValueError(f"amcx: no training kernel for {activation!r} / {optimizer!r}")
     return name.decode()
 
 

@@ -119,9 +119,16 @@ class MlpModel(PackedMlp):
     def from_checkpoint(cls, path, activation: Optional[str] = None, default_activation: str = "relu") -> "MlpModel":
         """The file the reference's ``train_model`` writes (``{"model_state_dict", "model_id", "config"}``), read by
         :func:`load_checkpoint`.  The activation comes from the stored config's ``training.activation`` when it is
-        there (the argument wins when both are given), ``default_activation`` otherwise."""
+        there (the argument wins when both are given), ``default_activation`` otherwise.  The config may also be a plain dict,
+        as :func:`amcpy_amd.train.save_checkpoint` writes it: ``{"training": {"activation": ...}}`` or the training settings
+        themselves."""
         sd, ck = checkpoint_state_dict(path)
-        stored = getattr(getattr(ck.get("config") if isinstance(ck, dict) else None, "training", None), "activation", None)
+        config = ck.get("config") if isinstance(ck, dict) else None
+        if isinstance(config, dict):
+            training = config.get("training", config)
+            stored = training.get("activation") if isinstance(training, dict) else getattr(training, "activation", None)
+        else:
+            stored = getattr(getattr(config, "training", None), "activation", None)
         act = activation or (stored if isinstance(stored, str) else None) or default_activation
         model_id = ck.get("model_id") if isinstance(ck, dict) else None
         return cls.from_state_dict(sd, act, model_id if isinstance(model_id, str) else None)

@@ -14,7 +14,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_mlp_q15_kernel.h"   // FIRST of all (ABI 16: plain kernels on amcx_mlp_shape.h alone, which holds no kernel), then the spectrogram's ...
+#include "amcx_mlp_train_kernel.h" // FIRST of all (ABI 16.1: plain and explicitly instantiated kernels on amcx_mlp_shape.h alone), then the fixed-point ones ...
+#include "amcx_mlp_q15_kernel.h"   // ... (ABI 16: plain kernels on amcx_mlp_shape.h alone, which holds no kernel), then the spectrogram's ...
 #include "amcx_psd_kernel.h"       // ... it includes the occupancy and down-converter headers for their device helpers), ...
 #include "amcx_occupancy_kernels.h"  // ... then the occupancy kernels (ABI 14: plain kernels that call nothing of the others), ...
 #include "amcx_resample_kernel.h"  // ... then the resampler's (it includes the down-converter's header in front of its own kernels), the bank's next, ...
@@ -1517,6 +1518,109 @@ int amcx_mlp_classify_q15(const float* x_dev, int64_t n_rows, int64_t row_stride
                                     scale_dev, params_dev, mlp_shape(widths_host, n_linear, activation), fmt, labels_dev, logits_dev,
                                     logits_stride, counts != nullptr ? rows_per_group : 1, counts, saturated, tiles);
   if (e != hipSuccess) return hip_fail(e, "Q15 classifier kernel launch");
+  return AMCX_OK;
+}
+
+// ---- ABI 16.1: training ------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+bool train_shape_ok(const int32_t* widths_host, int32_t n_linear, uint32_t bn_mask, int32_t optimizer) {
+  return mlp_shape_ok(widths_host, n_linear) && (bn_mask >> (n_linear - 1)) == 0u &&
+         (optimizer == AMCX_OPT_RMSPROP || optimizer == AMCX_OPT_ADAM);
+}
+
+template <int ACT, int OPT>
+struct TrainKernel {
+  static constexpr auto kern = amcx::amcx_mlp_train_kernel<ACT, OPT>;
+  static constexpr const char* name() {
+    return ACT == amcx::kActRelu ? (OPT == amcx::kOptRmsprop ? "amcx_mlp_train_kernel<0, 0>" : "amcx_mlp_train_kernel<0, 1>")
+           : ACT == amcx::kActTanh ? (OPT == amcx::kOptRmsprop ? "amcx_mlp_train_kernel<1, 0>" : "amcx_mlp_train_kernel<1, 1>")
+                                   : (OPT == amcx::kOptRmsprop ? "amcx_mlp_train_kernel<2, 0>" : "amcx_mlp_train_kernel<2, 1>");
+  }
+};
+// the kernel of an (activation, optimizer), handed to `f` as one of the six; both in range already
+template <class F>
+auto for_train_kernel(int32_t activation, int32_t optimizer, F&& f) {
+  const bool adam = optimizer == AMCX_OPT_ADAM;
+  if (activation == AMCX_ACT_RELU) return adam ? f(TrainKernel<amcx::kActRelu, amcx::kOptAdam>{}) : f(TrainKernel<amcx::kActRelu, amcx::kOptRmsprop>{});
+  if (activation == AMCX_ACT_TANH) return adam ? f(TrainKernel<amcx::kActTanh, amcx::kOptAdam>{}) : f(TrainKernel<amcx::kActTanh, amcx::kOptRmsprop>{});
+  return adam ? f(TrainKernel<amcx::kActSigmoid, amcx::kOptAdam>{}) : f(TrainKernel<amcx::kActSigmoid, amcx::kOptRmsprop>{});
+}
+bool train_act_ok(int32_t activation) {
+  return activation == AMCX_ACT_RELU || activation == AMCX_ACT_TANH || activation == AMCX_ACT_SIGMOID;
+}
+bool finite32(float v) { return v - v == 0.0f; }
+
+}  // namespace
+
+extern "C" {
+
+int amcx_abi_minor(void) { return AMCX_ABI_MINOR; }
+
+int64_t amcx_mlp_train_state_floats(const int32_t* widths_host, int32_t n_linear, uint32_t bn_mask, int32_t optimizer) {
+  if (!train_shape_ok(widths_host, n_linear, bn_mask, optimizer)) return -1;
+  return amcx::train_layout(mlp_shape(widths_host, n_linear, 0), bn_mask, optimizer).state_floats();
+}
+
+int64_t amcx_mlp_train_workspace_floats(const int32_t* widths_host, int32_t n_linear, int32_t batch) {
+  if (!mlp_shape_ok(widths_host, n_linear) || batch < 2 || batch > amcx::kTrainMaxBatch) return -1;
+  return amcx::train_ws_floats(n_linear, batch);
+}
+
+const char* amcx_kernel_name_mlp_train(int32_t activation, int32_t optimizer) {
+  if (activation == -1 && optimizer == -1) return "amcx_mlp_train_hyper_kernel";
+  if (!train_act_ok(activation) || (optimizer != AMCX_OPT_RMSPROP && optimizer != AMCX_OPT_ADAM)) return nullptr;
+  return for_train_kernel(activation, optimizer, [](auto k) { return decltype(k)::name(); });
+}
+
+int amcx_mlp_train_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host, int32_t n_sel,
+                       const double* mean_dev, const double* scale_dev, const int32_t* y_dev, const int32_t* idx_dev, int64_t n_idx,
+                       int64_t idx_model_stride, const int32_t* widths_host, int32_t n_linear, int32_t activation, uint32_t bn_mask,
+                       int32_t optimizer, int32_t batch, int32_t n_models, float* state_dev, int64_t* steps_dev, float* ws_dev,
+                       const float* lr_host, const uint32_t* drop_threshold_host, const float* keep_scale_host, const uint64_t* seed_host,
+                       int64_t step0, int32_t n_steps, double* history_dev, void* hip_stream) {
+  amcx::SelectCols sel;
+  if (!mlp_rows_ok(n_rows, row_stride, n_cols, cols_host, n_sel, mean_dev, scale_dev, widths_host, n_linear, &sel)) return AMCX_EINVAL;
+  if (!train_act_ok(activation) || !train_shape_ok(widths_host, n_linear, bn_mask, optimizer)) return AMCX_EINVAL;
+  if (batch < 2 || batch > amcx::kTrainMaxBatch || n_models < 1 || n_steps < 0 || step0 < 0 || n_idx < 0 || n_idx > 0x7fffffffLL ||
+      idx_model_stride < 0 || (idx_model_stride != 0 && idx_model_stride < n_idx) || step0 > 0x7fffffffLL)
+    return AMCX_EINVAL;
+  if (n_idx % batch == 1) return AMCX_EINVAL;                        // a batch of one row: BatchNorm has no variance of it
+  if (n_steps > 0 && (step0 * batch >= n_idx || (step0 + n_steps - 1) * batch >= n_idx)) return AMCX_EINVAL;
+  if (lr_host == nullptr || drop_threshold_host == nullptr || keep_scale_host == nullptr || seed_host == nullptr) return AMCX_EINVAL;
+  for (int m = 0; m < n_models; ++m)
+    if (!finite32(lr_host[m]) || !finite32(keep_scale_host[m])) return AMCX_EINVAL;
+  if (n_steps == 0 || n_rows == 0) return AMCX_OK;
+  if (!ptrs_ok({{x_dev, 3u, true}, {mean_dev, 7u, false}, {scale_dev, 7u, false}, {y_dev, 3u, true}, {idx_dev, 3u, true},
+                {state_dev, 3u, true}, {steps_dev, 7u, true}, {ws_dev, 15u, true}, {history_dev, 7u, true}}))
+    return AMCX_EINVAL;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const amcx::MlpShape shape = mlp_shape(widths_host, n_linear, activation);
+  const int64_t ws_floats = amcx::train_ws_floats(n_linear, batch);
+  for (int first = 0; first < n_models; first += amcx::kTrainUploadModels) {
+    const int n = n_models - first < amcx::kTrainUploadModels ? n_models - first : amcx::kTrainUploadModels;
+    amcx::TrainHyperChunk h = {};
+    for (int i = 0; i < n; ++i) {
+      h.lr[i] = lr_host[first + i];
+      h.thr[i] = drop_threshold_host[first + i];
+      h.keep[i] = keep_scale_host[first + i];
+      h.seed_lo[i] = (unsigned)(seed_host[first + i] & 0xffffffffull);
+      h.seed_hi[i] = (unsigned)(seed_host[first + i] >> 32);
+    }
+    const hipError_t e = amcx::launch(amcx::amcx_mlp_train_hyper_kernel, 1, amcx::kTrainUploadModels, 0, st, h, n, ws_dev, ws_floats, first);
+    if (e != hipSuccess) return hip_fail(e, "training hyperparameter kernel launch");
+  }
+  const hipError_t e = for_train_kernel(activation, optimizer, [&](auto k) {
+    constexpr auto kern = decltype(k)::kern;
+    if (const hipError_t a = amcx::lds_attr_once<kern>(amcx::train_lds_bytes(amcx::kTrainMaxBatch)); a != hipSuccess) return a;
+    return amcx::launch(kern, n_models, amcx::kTrainThreads, (size_t)amcx::train_lds_bytes(batch), st, x_dev, n_rows, row_stride, sel,
+                        mean_dev, scale_dev, y_dev, idx_dev, n_idx, idx_model_stride, shape, bn_mask, batch, state_dev,
+                        reinterpret_cast<long long*>(steps_dev), ws_dev,
+                        step0, n_steps, history_dev);
+  });
+  if (e != hipSuccess) return hip_fail(e, "training kernel launch");
   return AMCX_OK;
 }
 

@@ -322,6 +322,9 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bo
 // loaders) are included in front of those.
 // The fixed-point kernels (ABI 16, amcx_mlp_q15_kernel.h) come first of all now: plain kernels on amcx_mlp_shape.h, which holds the
 // declarations they share with the classifier and no kernel, so including it there moves nothing.
+// The training kernels (ABI 16.1, amcx_mlp_train_kernel.h, on amcx_mlp_shape.h alone) are included in front of those: one plain kernel and
+// six explicit specialisations (an explicit INSTANTIATION is laid out behind the device functions in the middle of .text and moved the group
+// and stream kernels' distances; a specialisation is laid out where it stands, as the sc16 kernels are).
 // That specialisations are laid out there is what hipcc does today, not a rule it documents: tools/codeobj_gate.py --kernels
 // against the parent commit is what guards it, and the only thing that will notice when a compiler lays them out elsewhere.
 inline void kernel_order_anchor() {

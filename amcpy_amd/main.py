@@ -92,6 +92,21 @@ def build_parser() -> argparse.ArgumentParser:
     cl.add_argument("--num-frames", type=int, default=None)
     cl.add_argument("--snr-values", nargs="+", default=None, metavar="LABEL",
                     help="SNR labels of the container's first axis, in order (default: the 16 of SignalConfig)")
+    tr = sub.add_parser("train", help="train the classifier on the GPU from calculated-features/: ann/model-{id}.pt, figures/{id}_history.mat")
+    tr.add_argument("--root", type=Path, default=None, help="project root (default: cwd)")
+    tr.add_argument("--epochs", type=int, default=None)
+    tr.add_argument("--batch-size", type=int, default=None, help="2 ... 256")
+    tr.add_argument("--lr", type=float, default=None)
+    tr.add_argument("--dropout", type=float, default=None)
+    tr.add_argument("--optimizer", choices=("rmsprop", "adam"), default=None)
+    tr.add_argument("--activation", choices=("relu", "tanh", "sigmoid"), default=None)
+    tr.add_argument("--seed", type=int, default=None, help="of the split, the initialisation, the epochs' orders and the dropout masks")
+    tr.add_argument("--sweep-lr", default=None, metavar="a,b,...", help="one model per value, all trained side by side (256 at most)")
+    tr.add_argument("--sweep-dropout", default=None, metavar="a,b,...", help="as --sweep-lr; with both, two lists of one length")
+    tr.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
+    tr.add_argument("--frame-size", type=int, default=None)
+    tr.add_argument("--num-frames", type=int, default=None)
+    tr.add_argument("--snr-values", nargs="+", default=None, metavar="LABEL")
     rec = sub.add_parser("recording", help="the features of one recording: a SigMF recording or a raw sample stream")
     rec.add_argument("file", type=Path, metavar="FILE",
                      help="X.sigmf-meta, X.sigmf-data or the stem X of a SigMF recording; or a raw stream (then --format)")
@@ -549,6 +564,16 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
     if args.snr_values is not None:
         sig = replace(sig, snr_values={i: str(v) for i, v in enumerate(args.snr_values)})
     cfg = replace(cfg, signals=sig)
+    if args.command == "train":
+        # tensors on torch's runtime: this command never skips the import
+        from .train import run_training
+        given = {name: v for name, v in (("epochs", args.epochs), ("batch_size", args.batch_size), ("learning_rate", args.lr),
+                                         ("dropout", args.dropout), ("optimizer", args.optimizer), ("activation", args.activation),
+                                         ("random_state", args.seed)) if v is not None}
+        sweep = {key: [float(v) for v in text.split(",")] for key, text in (("lr", args.sweep_lr), ("dropout", args.sweep_dropout))
+                 if text is not None}
+        run_training(replace(cfg, training=replace(cfg.training, **given)), device=args.device, sweep=sweep or None)
+        return 0
     if args.command == "classify":
         # tensors on torch's runtime: this command never skips the import
         from .classifier import run_classification

@@ -98,9 +98,14 @@ extern "C" {
  * amcx_ctx_set_iq8_scale, amcx_ctx_features18_iq8_host;
  * 11 = the digital down-converter; 12 = the polyphase filter bank; 13 = the rational resampler; 14 = occupancy detection
  * (all listed behind the define); 15 = the Welch spectrogram and its per-row detection; 16 = fixed-point deployment of the
- * classifier's network (range calibration and 16-bit integer inference). */
+ * classifier's network (range calibration and 16-bit integer inference).
+ * AMCX_ABI_MINOR counts what has been ADDED since the version last changed -- new entries and constants, nothing existing changed:
+ * 16.1 = training of the classifier's network, one workgroup per model. */
 #define AMCX_ABI_VERSION 16
+#define AMCX_ABI_MINOR 1
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
+ *   ABI 16.1: AMCX_ABI_MINOR 1            -- training: AMCX_OPT_*, amcx_mlp_train_f32, amcx_mlp_train_state_floats,
+ *                                            amcx_mlp_train_workspace_floats, amcx_kernel_name_mlp_train, amcx_abi_minor
  *   ABI 16: the line above               -- fixed-point deployment: AMCX_ACT_NONE, amcx_mlp_range_f32, amcx_mlp_classify_q15,
  *                                            amcx_mlp_q15_params_shorts, amcx_kernel_name_mlp_q15
  *   ABI 15: #define AMCX_ABI_VERSION 15   -- the spectrogram: amcx_spectrogram, amcx_spectrogram_out_rows, amcx_spectrogram_plan,
@@ -975,6 +980,68 @@ int amcx_mlp_classify_q15(const float* x_dev, int64_t n_rows, int64_t row_stride
                           int32_t* labels_dev, int16_t* logits_dev, int64_t logits_stride, int64_t rows_per_group,
                           int64_t* counts_dev, int64_t* saturated_dev, void* hip_stream);
 const char* amcx_kernel_name_mlp_q15(int32_t which);
+
+/*
+ * ABI 16.1.  TRAINING of the network amcx_mlp_classify_f32 runs: the reference's `train` stage (nn_model.train_model) on the
+ * device, ONE workgroup of 256 threads per model and n_models workgroups per launch (amcpy_amd/csrc/amcx_mlp_train_kernel.h).
+ * A call runs steps step0 ... step0 + n_steps - 1 of ONE epoch for every model, on hip_stream; it allocates nothing, never
+ * synchronises and can be captured in a graph.  The rows, columns, scaler and shape are amcx_mlp_classify_f32's.
+ *
+ * THE NETWORK, in train mode.  Per hidden layer l (0-based): z = W a + b; where bit l of bn_mask is set BatchNorm1d over the
+ * batch (batch mean, biased variance, eps 1e-5; running mean / variance updated with momentum 0.1, the running variance from
+ * the unbiased variance; then gamma, beta); the activation; dropout (a kept value times keep_scale).  The last layer is
+ * z = W a + b and p = softmax(z).  A bit of bn_mask at or above n_linear - 1 is AMCX_EINVAL.  THE LOSS is the reference's,
+ * CrossEntropyLoss on the softmax OUTPUT: q = softmax(p), a row's loss -log q[y], dp = (q - onehot(y)) / rows,
+ * dz = p * (dp - sum_j p_j dp_j).  THE OPTIMIZERS are torch's with torch's defaults, in float32: AMCX_OPT_RMSPROP (alpha 0.99,
+ * eps 1e-8) and AMCX_OPT_ADAM (betas 0.9 / 0.999, eps 1e-8, bias correction from the model's step count).
+ *
+ * ROWS.  y_dev: int32 [n_rows], a row's class (one outside 0 ... classes - 1 matches no class).  idx_dev: int32, the epoch's
+ * order, n_idx row numbers per model; idx_model_stride is 0 when every model takes the same order, else the distance in
+ * elements between two models' orders (>= n_idx).  Step s takes idx[s * batch ... min((s + 1) * batch, n_idx) - 1]: the ragged
+ * last batch has n_idx mod batch rows, and n_idx mod batch == 1 is AMCX_EINVAL (a BatchNorm of one row).  batch: 2 ... 256.  An
+ * index outside 0 ... n_rows - 1 is the caller's error; the kernel reads the nearest row instead.
+ *
+ * THE STATE BLOCK.  state_dev: float32 [n_models][amcx_mlp_train_state_floats(widths, n_linear, bn_mask, optimizer)], per model
+ *   [0, P)                     the packed parameter block of amcx_mlp_params_floats: per layer W[out][in] row-major, then b[out];
+ *   [P, P + A)                 per BatchNorm, ascending layers: gamma[out], then beta[out]                    (T = P + A trainable)
+ *   [T, T + R)                 per BatchNorm: running_mean[out], then running_var[out]                         (R = A)
+ *   [T + R + s T, ... + T)     optimizer slot s of trainable value i at + i: rmsprop one slot (square_avg), adam two (exp_avg,
+ *                              then exp_avg_sq).
+ * steps_dev: int64 [n_models], the steps a model has taken (torch's num_batches_tracked and the optimizers' `step`); the call
+ * adds n_steps.  Nothing else carries over from one call to the next: an epoch cut into calls anywhere gives the bits of one call.
+ * ws_dev: float32 [n_models][amcx_mlp_train_workspace_floats(widths, n_linear, batch)], 16-byte aligned, scratch: what backward
+ * needs of forward (a CU's LDS does not hold it for the largest shape); its contents mean nothing between calls.
+ *
+ * HYPERPARAMETERS, host arrays of n_models entries: lr_host (finite), drop_threshold_host, keep_scale_host (finite), seed_host.
+ * THE DROPOUT MASK is part of the contract: Philox4x32-10 with the key (seed low word, seed high word); the counter
+ * (t mod 2^32, hidden layer l, row in the batch r, o / 4) gives the four words of units 4 (o / 4) ... + 3, t being the model's
+ * step count BEFORE the step; a unit is kept iff its word >= drop_threshold.  The caller computes drop_threshold = rint(p 2^32)
+ * and keep_scale = float32(1 / (1 - p)); with drop_threshold 0 (keep_scale 1) the bits are those of a run without dropout.
+ *
+ * history_dev: float64 [n_models][2].  The call ADDS, step by step, the batch's summed row losses to [m][0] and the number of
+ * rows whose argmax p (first maximum) is y to [m][1], rows in order: bit-reproducible, and the same however the epoch is cut.
+ *
+ *   - checks, in the order of every launching entry: the limits of amcx_mlp_classify_f32, the activation, bn_mask, the optimizer,
+ *     batch, n_models >= 1, n_steps >= 0, step0 >= 0, 0 <= n_idx < 2^31, idx_model_stride, the ragged-batch rule, step0 * batch <
+ *     n_idx and the last step inside the epoch when n_steps > 0, the host arrays present, every lr and keep_scale finite;
+ *     n_steps == 0 or n_rows == 0 is AMCX_OK here and writes nothing; then null pointers, alignment (4; 8 for mean, scale,
+ *     history and steps; 16 for ws) and a pointer on another device.
+ * amcx_mlp_train_state_floats / amcx_mlp_train_workspace_floats: -1 for an invalid shape (or batch).
+ * amcx_kernel_name_mlp_train (host-only): the kernel of an (activation, optimizer), a static string; (-1, -1): the launch that
+ * carries the hyperparameters to the device; NULL otherwise.
+ */
+int amcx_abi_minor(void);      /* AMCX_ABI_MINOR of the library */
+#define AMCX_OPT_RMSPROP 0
+#define AMCX_OPT_ADAM 1
+int64_t amcx_mlp_train_state_floats(const int32_t* widths_host, int32_t n_linear, uint32_t bn_mask, int32_t optimizer);
+int64_t amcx_mlp_train_workspace_floats(const int32_t* widths_host, int32_t n_linear, int32_t batch);
+int amcx_mlp_train_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, int32_t n_cols, const int32_t* cols_host,
+                       int32_t n_sel, const double* mean_dev, const double* scale_dev, const int32_t* y_dev, const int32_t* idx_dev,
+                       int64_t n_idx, int64_t idx_model_stride, const int32_t* widths_host, int32_t n_linear, int32_t activation,
+                       uint32_t bn_mask, int32_t optimizer, int32_t batch, int32_t n_models, float* state_dev, int64_t* steps_dev,
+                       float* ws_dev, const float* lr_host, const uint32_t* drop_threshold_host, const float* keep_scale_host,
+                       const uint64_t* seed_host, int64_t step0, int32_t n_steps, double* history_dev, void* hip_stream);
+const char* amcx_kernel_name_mlp_train(int32_t activation, int32_t optimizer);
 
 #ifdef __cplusplus
 }

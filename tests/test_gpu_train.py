@@ -1,0 +1,296 @@
+"""Training on the device (amcx_mlp_train_f32, ABI 16.1) against the fixtures tests/golden/make_train_fixtures.py wrote from the
+reference's own module on the CPU: the state after K steps under a tolerance measured against torch's own float32, dropout
+against the numpy Philox, everything that can be bit-exact with ``==``, the refusals, and learning."""
+import ctypes
+import importlib.util
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from tests import train_cases as tc
+from tests import train_ref
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = Path(__file__).resolve().parent / "golden"
+
+
+def _trainer(case, n_models=1, **kw):
+    import torch
+    from amcpy_amd.train import Trainer
+    feats = kw.pop("feats", None)
+    if feats is None:
+        feats = torch.from_numpy(case["raw"]).cuda()
+    state = kw.pop("state", None) or tc.initial_state(case, n_models)
+    kw.setdefault("lr", case["lr"])
+    return Trainer(feats, case["y"], state, cols=case["cols"].tolist(), mean=case["mean"], scale=case["scale"], batch_size=case["batch"],
+                   activation=case["activation"], **kw)
+
+
+def _run(tr, case, launches=None, order=None):
+    """The fixture's K steps, in the given launches [(step0, n_steps)] (default: one).  Returns (block, steps, history) on the host."""
+    import torch
+    order_dev, n_idx, stride = tr.device_order(case["order"] if order is None else order)
+    for step0, n in launches or [(0, case["steps"])]:
+        tr.launch(order_dev, n_idx, stride, step0, n)
+    torch.cuda.synchronize()
+    return tr.block.cpu().numpy(), tr.steps.cpu().numpy(), tr.history.cpu().numpy()
+
+
+def _same(a, b):
+    return all(np.array_equal(x.view(np.uint8).reshape(-1), y.view(np.uint8).reshape(-1)) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("name", tc.CASES)
+def test_state_after_k_steps_within_four_times_the_reference_float32_error(name):
+    """Every compared element of every tensor -- parameters, BatchNorm, running statistics, optimizer slots -- within
+    4 x max(err32, 2^-24 max |theta64|) of the reference's float64 state.  Worst ratios measured on an MI355X (ROCm 7.0):
+    see profiles/r27_pytest_gpu.txt."""
+    case = tc.load(name)
+    tr = _trainer(case)
+    _, steps, hist = _run(tr, case)
+    ratio, key = tc.worst_ratio(case, tc.block_tensors(case, tr.download()), tc.expected(case))
+    print(f"\n{name}: worst |got - f64| / bound = {ratio:.3f} at {key}")
+    assert ratio <= 1.0, (ratio, key)
+    assert steps.tolist() == [case["steps"]]
+    # in front of a BatchNorm db is identically zero and the kernel takes the identity: those biases keep their bits
+    from amcpy_amd.train import layer_indices
+    for li, bi in layer_indices(case["widths"], case["bn_mask"]):
+        if bi is not None:
+            assert _same([tr.state.views(0)[f"layers.{li}.bias"]], [case[f"sd0:layers.{li}.bias"]]), li
+    _, losses, right = train_ref.run(tc.ref_state(case), case["x"].astype(np.float64), case["y"], case["order"], case["batch"], case["steps"],
+                                     activation=case["activation"], optimizer=case["optimizer"], lr=case["lr"])
+    assert abs(hist[0, 0] - sum(losses)) <= 1e-5 * sum(losses) and abs(hist[0, 1] - sum(right)) <= 2
+
+
+def test_dropout_follows_the_philox_masks():
+    """p = 0.4 against tests/train_ref.py under the numpy Philox's masks, the same bound; another seed misses it grossly."""
+    case = tc.load("default_relu_rmsprop")
+    want = tc.expected(case, "drop64:", "dropopt64:")
+    tr = _trainer(case, dropout=float(case["drop_p"]), seed=int(case["drop_seed"]))
+    _run(tr, case)
+    ratio, key = tc.worst_ratio(case, tc.block_tensors(case, tr.download()), want, "dropcmp:")
+    print(f"\ndropout 0.4: worst |got - f64| / bound = {ratio:.3f} at {key}")
+    assert ratio <= 1.0, (ratio, key)
+    other = _trainer(case, dropout=float(case["drop_p"]), seed=int(case["drop_seed"]) + 1)
+    _run(other, case)
+    assert tc.worst_ratio(case, tc.block_tensors(case, other.download()), want, "dropcmp:")[0] > 100.0
+
+
+def test_drop_threshold_zero_is_a_run_without_dropout():
+    case = tc.load("default_relu_rmsprop")
+    plain = _run(_trainer(case, dropout=0.0, seed=1), case)
+    tiny = _trainer(case, dropout=1e-11, seed=0xFFFFFFFFFFFF)           # rint(p 2^32) = 0, float32(1 / (1 - p)) = 1
+    assert tiny.threshold.tolist() == [0] and tiny.keep_scale.tolist() == [1.0]
+    assert _same(plain, _run(tiny, case))
+
+
+def test_same_call_twice_gives_the_same_bits():
+    case = tc.load("default_tanh_adam")
+    assert _same(_run(_trainer(case, dropout=0.3, seed=9), case), _run(_trainer(case, dropout=0.3, seed=9), case))
+
+
+@pytest.mark.parametrize("name", ("default_relu_rmsprop", "ragged_127"))
+def test_an_epoch_cut_into_launches_anywhere_gives_the_bits_of_one_launch(name):
+    case = tc.load(name)
+    whole = _run(_trainer(case, dropout=0.4, seed=3), case)
+    assert whole[1].tolist() == [4]
+    for cuts in ([(0, 1), (1, 3)], [(0, 2), (2, 2)], [(0, 3), (3, 1)], [(0, 1), (1, 1), (2, 1), (3, 1)]):
+        assert _same(whole, _run(_trainer(case, dropout=0.4, seed=3), case, cuts)), cuts
+
+
+def test_a_model_of_a_sweep_equals_that_model_trained_alone():
+    case = tc.load("default_relu_adam")
+    lrs, drops, seeds = [1e-3, 2e-3, 5e-4, 3e-3, 1e-2], [0.0, 0.1, 0.4, 0.25, 0.5], [1, 2, 3, 1 << 40, 5]
+    block, steps, hist = _run(_trainer(case, 5, lr=lrs, dropout=drops, seed=seeds), case)
+    assert not np.array_equal(block[0], block[1])
+    for m in range(5):
+        alone = _run(_trainer(case, 1, lr=lrs[m], dropout=drops[m], seed=seeds[m]), case)
+        assert _same((block[m], steps[m:m + 1], hist[m]), alone), m
+
+
+def test_a_shared_order_equals_per_model_copies_of_it():
+    case = tc.load("batch_65")
+    kw = dict(lr=[1e-3, 2e-3, 4e-3], dropout=[0.1, 0.2, 0.3], seed=[4, 5, 6])
+    shared = _run(_trainer(case, 3, **kw), case)
+    copies = _run(_trainer(case, 3, **kw), case, order=np.stack([case["order"]] * 3))
+    assert _same(shared, copies)
+
+
+def test_a_strided_offset_view_equals_its_contiguous_copy():
+    """Row stride 19, the first row 4 bytes behind a 16-byte boundary."""
+    import torch
+    case = tc.load("default_sigmoid_rmsprop")
+    raw = torch.from_numpy(case["raw"]).cuda()
+    n, c = raw.shape
+    flat = torch.zeros(n * 19 + 8, dtype=torch.float32, device="cuda")
+    at = next(i for i in range(8) if (flat.data_ptr() + 4 * i) % 16 == 4)
+    view = flat[at:at + n * 19].view(n, 19)[:, :c]
+    view.copy_(raw)
+    assert view.stride() == (19, 1) and view.data_ptr() % 16 == 4
+    assert _same(_run(_trainer(case, feats=view), case), _run(_trainer(case), case))
+
+
+def test_a_graph_replay_equals_the_eager_call():
+    import torch
+    case = tc.load("default_relu_rmsprop")
+    eager = _run(_trainer(case, 2, lr=[1e-3, 2e-3], dropout=[0.4, 0.2], seed=[7, 8]), case)
+    tr = _trainer(case, 2, lr=[1e-3, 2e-3], dropout=[0.4, 0.2], seed=[7, 8])
+    order_dev, n_idx, stride = tr.device_order(case["order"])
+    first = (tr.block.clone(), tr.steps.clone(), tr.history.clone())
+    graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            tr.launch(order_dev, n_idx, stride, 0, case["steps"])
+    for t, v in zip((tr.block, tr.steps, tr.history), first):        # whatever the capture did or did not run: from the start
+        t.copy_(v)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert _same(eager, (tr.block.cpu().numpy(), tr.steps.cpu().numpy(), tr.history.cpu().numpy()))
+
+
+# ---- the refusals ----------------------------------------------------------------------------------------------------------------
+def _call(tr, case, **over):
+    """amcx_mlp_train_f32 with the trainer's arguments, some replaced; returns the status."""
+    import torch
+    from amcpy_amd import _lib
+    from amcpy_amd._mlp import i32s
+    from amcpy_amd.train import OPTIMIZERS
+    s, f, u = tr.state, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+    order_dev, n_idx, stride = tr.device_order(case["order"])
+    x, n_rows, row_stride, n_cols, cols, n_sel, mean, scale = tr.rows.entry_args()
+    a = dict(x=x, n_rows=n_rows, row_stride=row_stride, n_cols=n_cols, cols=cols, n_sel=n_sel, mean=mean, scale=scale, y=tr.y.data_ptr(),
+             idx=order_dev.data_ptr(), n_idx=n_idx, idx_stride=stride, widths=i32s(s.widths), n_linear=s.n_linear,
+             act=_lib.ACTIVATIONS[tr.activation], bn_mask=s.bn_mask, opt=OPTIMIZERS[s.optimizer], batch=tr.batch, n_models=s.n_models,
+             state=tr.block.data_ptr(), steps=tr.steps.data_ptr(), ws=tr.ws.data_ptr(), lr=tr.lr.ctypes.data_as(f),
+             thr=tr.threshold.ctypes.data_as(u), keep=tr.keep_scale.ctypes.data_as(f),
+             seed=tr.seed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), step0=0, n_steps=case["steps"], history=tr.history.data_ptr())
+    a.update(over)
+    keep = order_dev                                                      # alive until the call returns
+    status = _lib.load().amcx_mlp_train_f32(*a.values(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    del keep
+    return status
+
+
+def test_refusals_in_the_header_order_and_the_no_op():
+    import torch
+    from amcpy_amd import _lib
+    from amcpy_amd._mlp import i32s
+    case = tc.load("default_relu_rmsprop")
+    tr = _trainer(case)
+    before = (tr.block.clone(), tr.steps.clone(), tr.history.clone(), tr.ws.clone())
+    f32 = lambda *v: (ctypes.c_float * len(v))(*v)
+    ranges = (dict(n_rows=-1), dict(n_cols=0), dict(row_stride=3), dict(cols=None), dict(widths=None), dict(widths=i32s((6, 33, 29, 30, 6))),
+              dict(n_linear=0), dict(n_sel=5), dict(mean=None), dict(act=3), dict(act=-1), dict(bn_mask=8), dict(opt=2), dict(opt=-1),
+              dict(batch=1), dict(batch=257), dict(n_models=0), dict(n_steps=-1), dict(step0=-1), dict(n_idx=-1), dict(idx_stride=-1),
+              dict(idx_stride=511), dict(step0=4, n_steps=1), dict(step0=3, n_steps=2), dict(n_idx=513), dict(n_idx=129), dict(n_idx=1),
+              dict(lr=None), dict(thr=None), dict(keep=None), dict(seed=None), dict(lr=f32(float("nan"))), dict(lr=f32(float("inf"))),
+              dict(keep=f32(float("inf"))))
+    for over in ranges:
+        # a range is refused before the no-op and before any pointer is looked at
+        assert _call(tr, case, **over) == _lib.EINVAL, over
+        assert _call(tr, case, x=None, state=4, **{"n_steps": 0, **over}) == _lib.EINVAL, over
+    # the no-op: nothing is looked at, nothing is written
+    assert _call(tr, case, n_steps=0, x=None, y=1, idx=None, state=None, steps=3, ws=None, history=5) == _lib.OK
+    assert _call(tr, case, n_rows=0, x=None, state=None) == _lib.OK
+    # pointers: null, alignment (4; 8 for mean, scale, history and the step counts; 16 for the workspace)
+    for name in ("x", "y", "idx", "state", "steps", "ws", "history"):
+        assert _call(tr, case, **{name: None}) == _lib.EINVAL, name
+    ptrs = dict(x=tr.rows.flat.data_ptr(), y=tr.y.data_ptr(), state=tr.block.data_ptr(), steps=tr.steps.data_ptr(), ws=tr.ws.data_ptr(),
+                history=tr.history.data_ptr(), mean=tr.rows.mean.data_ptr(), scale=tr.rows.scale.data_ptr())
+    for name, off in (("x", 2), ("y", 1), ("state", 2), ("steps", 4), ("ws", 4), ("ws", 8), ("history", 4), ("mean", 4), ("scale", 4)):
+        assert _call(tr, case, **{name: ptrs[name] + off}) == _lib.EINVAL, (name, off)
+    if torch.cuda.device_count() > 1:
+        far = torch.zeros_like(tr.block, device="cuda:1")
+        assert _call(tr, case, state=far.data_ptr()) == _lib.EINVAL
+    torch.cuda.synchronize()
+    for t, v in zip((tr.block, tr.steps, tr.history, tr.ws), before):
+        assert torch.equal(t, v)
+    assert _call(tr, case) == _lib.OK and tr.steps.tolist() == [4]
+
+
+def test_python_layer_refusals():
+    case = tc.load("default_relu_rmsprop")
+    tr = _trainer(case)
+    with pytest.raises(ValueError):
+        tr.run_epoch(np.arange(129))                                      # a last batch of one row
+    with pytest.raises(ValueError):
+        tr.device_order(np.array([0, 600]))
+    with pytest.raises(ValueError):
+        _trainer(case, dropout=1.0)
+    with pytest.raises(ValueError):
+        _trainer(case, 2, lr=[1e-3, 1e-3, 1e-3])
+
+
+# ---- the command -----------------------------------------------------------------------------------------------------------------
+def test_train_command_then_classify_on_what_it_wrote(tmp_path):
+    """`run_training` (what `python -m amcpy_amd train` runs) on a synthetic root of feature files -- six separated clusters, 16
+    SNRs x 40 frames, tanh, a sweep of two learning rates, 2 epochs -- writes ann/model-{id}.pt and figures/{id}_history.mat per
+    model with the four history lists; `run_classification` on an id then loads the checkpoint WITH its activation and labels
+    the rows as `classify` does on the trainer's own folded model."""
+    import scipy.io
+    import torch
+    from dataclasses import replace
+    from amcpy_amd.classifier import classify, fit_scaler, load_model, run_classification
+    from amcpy_amd.config import Config, Paths, SignalConfig
+    from amcpy_amd.train import run_training
+    n_snr, n_frames = 16, 40
+    cfg = Config(paths=Paths(root=tmp_path), signals=SignalConfig(num_frames=n_frames))
+    cfg = replace(cfg, training=replace(cfg.training, epochs=2, activation="tanh", batch_size=64))
+    cfg.paths.ensure_dirs()
+    rng = np.random.default_rng(5)
+    mods = cfg.signals.modulations_with_noise
+    centers = rng.standard_normal((len(mods), 18)) * 2.0
+    for i, mod in enumerate(mods):
+        feats = (centers[i] + 0.5 * rng.standard_normal((n_snr, n_frames, 18))).astype(np.float32)
+        scipy.io.savemat(str(cfg.paths.calculated_features / f"{mod}_features.mat"), {cfg.signals.mat_info[mod]: feats})
+    ids = run_training(cfg, sweep={"lr": [0.002, 0.01]}, verbose=False)
+    assert len(ids) == 2 and len(set(ids)) == 2
+    n_train_rows = len(mods) * len(cfg.training.training_snr) * n_frames
+    for model_id in ids:
+        h = scipy.io.loadmat(str(cfg.paths.figures / f"{model_id}_history.mat"))
+        for key in ("loss", "accuracy", "val_loss", "val_accuracy"):
+            assert h[key].shape == (1, 2) and np.isfinite(h[key]).all(), key
+        assert h["loss"][0, 1] < h["loss"][0, 0] and h["val_accuracy"][0, 1] > 0.9
+        model, got = load_model(cfg, model_id)
+        assert got == model_id and model.activation == "tanh" and model.widths == (6, 26, 29, 30, 6)
+    acc, confusion = run_classification(cfg, ids[1], mode="training", verbose=False)
+    assert acc.shape == (len(mods), n_snr) and acc.mean() > 0.9 and confusion[:, -1].sum() == 0
+    assert (cfg.paths.figures / f"{ids[1]}_figure_data.mat").exists()
+    # the labels are those of the stored network run as tanh, not as the configuration's default
+    feats, mean, scale = fit_scaler(cfg, "training", torch.device("cuda", torch.cuda.current_device()))
+    model, _ = load_model(cfg, ids[1])
+    labels = classify(feats, model, cols=list(cfg.features.used), mean=mean, scale=scale).cpu().numpy()
+    want = np.stack([scipy.io.loadmat(str(cfg.paths.calculated_features / f"{m}_predictions.mat"))["predictions"] for m in mods])
+    assert np.array_equal(labels, want) and n_train_rows == 6 * 6 * n_frames
+
+
+# ---- learning --------------------------------------------------------------------------------------------------------------------
+def test_three_epochs_on_the_clusters_reach_the_reference_loop():
+    """6144 rows of six Gaussian clusters, 3 epochs, default shape and hyperparameters; held-out accuracy through classify on the
+    folded model against five CPU runs of the reference's loop (tests/golden/train_learning.npz): below their minimum by no more
+    than their spread.  The epoch losses decrease."""
+    import torch
+    from amcpy_amd.classifier import classify
+    from amcpy_amd.train import Trainer, TrainState
+    spec = importlib.util.spec_from_file_location("make_classifier_fixtures", GOLDEN / "make_classifier_fixtures.py")
+    cf = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cf)
+    with np.load(GOLDEN / "train_learning.npz") as z:
+        ref = {k: z[k] for k in z.files}
+    n_train = int(ref["n_train"])
+    x, y, _ = cf.clusters(6, 6, n_train + int(ref["n_heldout"]), 0, seed=int(ref["cluster_seed"]))
+    feats = torch.from_numpy(x).cuda()
+    state = TrainState.init((6, 26, 29, 30, 6), 7, "rmsprop", [0])
+    tr = Trainer(feats, y, state, cols=list(range(6)), batch_size=int(ref["batch"]), activation="relu", lr=float(ref["lr"]),
+                 dropout=float(ref["dropout"]), seed=0, idx=np.arange(n_train))
+    gen = torch.Generator().manual_seed(0)
+    losses = [float(tr.run_epoch(torch.randperm(n_train, generator=gen))[0][0]) for _ in range(int(ref["epochs"]))]
+    assert losses[0] > losses[1] > losses[2], losses
+    labels = classify(feats[n_train:], tr.download().model(0, "relu"), cols=list(range(6))).cpu().numpy()
+    acc = float((labels == y[n_train:]).mean())
+    print(f"\nheld-out accuracy {acc:.4f}; the reference's loop: {np.round(ref['accuracies'], 4)}; epoch losses {np.round(losses, 4)}")
+    assert acc >= float(ref["minimum"]) - float(ref["spread"]), (acc, ref["accuracies"])
+    assert state.steps.tolist() == [3 * 48]

@@ -1,0 +1,188 @@
+"""Training, the host side (no GPU): the float64 restatement tests/train_ref.py against the reference's own module (through the
+fixtures of tests/golden/make_train_fixtures.py), the dropout generator against its published answer, the state block and its
+round trips, the split, the ABI and the command line."""
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from amcpy_amd import _lib, train
+from amcpy_amd._mlp import i32s
+from amcpy_amd.classifier import MlpModel
+from amcpy_amd.config import Config
+from tests import train_cases as tc
+from tests import train_ref
+
+REPO = Path(__file__).resolve().parents[1]
+
+
+@pytest.mark.parametrize("name", tc.CASES)
+def test_restatement_equals_the_reference_in_double(name):
+    """K steps of tests/train_ref.py from the fixture's initial state against the reference's module in double() with torch.optim
+    (dropout 0): every tensor, running statistics and optimizer slots included, to 1e-10."""
+    case = tc.load(name)
+    state, losses, _ = train_ref.run(tc.ref_state(case), case["x"].astype(np.float64), case["y"], case["order"], case["batch"],
+                                     case["steps"], activation=case["activation"], optimizer=case["optimizer"], lr=case["lr"])
+    got, want = tc.ref_tensors(case, state), tc.expected(case)
+    assert set(got) == set(want)
+    for key in want:
+        assert np.abs(got[key] - want[key]).max() <= 1e-10, key
+    assert state["t"] == case["steps"]
+    assert all(np.isfinite(losses))
+
+
+def test_fixture_inputs_are_the_scaler_of_the_raw_rows():
+    case = tc.load("default_relu_rmsprop")
+    c = (case["raw"][:, case["cols"]].astype(np.float64) - case["mean"]).astype(np.float32)
+    assert np.array_equal((c.astype(np.float64) / case["scale"]).astype(np.float32), case["x"])
+
+
+def test_philox_known_answer():
+    """Philox4x32-10, counter 0 and key 0 (Random123's kat_vectors); and the all-ones and pi vectors of the same file."""
+    assert [f"{int(v):08x}" for v in train_ref.philox4x32_10((0, 0, 0, 0), (0, 0))] == ["6627e8d5", "e169c58d", "bc57ac4c", "9b00dbd8"]
+    ones = train_ref.philox4x32_10((0xFFFFFFFF,) * 4, (0xFFFFFFFF, 0xFFFFFFFF))
+    assert [f"{int(v):08x}" for v in ones] == ["408f276d", "41c83b0e", "a20bc7c6", "6d5451fd"]
+    pi = train_ref.philox4x32_10((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0))
+    assert [f"{int(v):08x}" for v in pi] == ["d16cfe09", "94fdcceb", "5001e420", "24126ea1"]
+
+
+def test_dropout_masks_follow_the_counter_layout():
+    masks = train_ref.dropout_masks(seed=(7 << 32) | 5, t=3, hidden_widths=[26, 9], rows=4, threshold=1 << 31)
+    assert [m.shape for m in masks] == [(4, 26), (4, 9)]
+    words = train_ref.philox4x32_10((3, 1, 2, 1), (5, 7))                    # layer 1, row 2, units 4 ... 7
+    assert [bool(int(w) >= 1 << 31) for w in words] == list(masks[1][2, 4:8])
+    assert train_ref.dropout_masks(1, 0, [5], 3, 0)[0].all()
+
+
+def test_drop_threshold_and_keep_scale_rule():
+    assert train.drop_params(0.0) == (0, np.float32(1.0))
+    thr, keep = train.drop_params(0.4)
+    assert thr == int(np.rint(0.4 * 2.0 ** 32)) == 1717986918 and keep == np.float32(1.0 / 0.6) and keep.dtype == np.float32
+    assert train.drop_params(0.5) == (1 << 31, np.float32(2.0))
+    assert train.drop_params(0.4) == train_ref.drop_params(0.4)
+    for bad in (-0.1, 1.0, 1.5):
+        with pytest.raises(ValueError):
+            train.drop_params(bad)
+
+
+def test_state_block_layout_and_size_function():
+    lib = _lib.load()
+    w = (6, 26, 29, 30, 6)
+    P, A = 2051, 2 * (26 + 29 + 30)
+    assert train.state_floats(w, 7, "rmsprop") == (P + A) * 2 + A == lib.amcx_mlp_train_state_floats(i32s(w), 4, 7, _lib.OPT_RMSPROP)
+    assert train.state_floats(w, 7, "adam") == (P + A) * 3 + A
+    assert train.state_floats(w, 0, "rmsprop") == 2 * P and train.state_floats((4, 32, 7, 3), 1, "adam") == 3 * (415 + 64) + 64
+    for widths, n_linear, mask, opt in ((w, 4, 8, 0), (w, 4, 7, 2), ((6, 33, 6), 2, 0, 0), (w, 0, 0, 0), ((6, 6), 1, 1, 0)):
+        assert lib.amcx_mlp_train_state_floats(i32s(widths), n_linear, mask, opt) == -1
+    assert lib.amcx_mlp_train_workspace_floats(i32s(w), 4, 128) == 8 + 128 * 32 * 10
+    assert lib.amcx_mlp_train_workspace_floats(i32s(w), 4, 1) == lib.amcx_mlp_train_workspace_floats(i32s(w), 4, 257) == -1
+    st = train.TrainState.init(w, 7, "adam", [3, 4])
+    assert st.block.shape == (2, train.state_floats(w, 7, "adam")) and st.steps.tolist() == [0, 0]
+    v = st.views(0)
+    assert v["layers.0.weight"].shape == (26, 6) and np.abs(v["layers.0.weight"]).max() <= 1 / np.sqrt(6) and v["layers.0.weight"].std() > 0.1
+    assert (v["layers.1.weight"] == 1).all() and (v["layers.1.bias"] == 0).all() and (v["layers.1.running_var"] == 1).all()
+    assert not (st.block[0, P + A + A:]).any() and not np.array_equal(st.block[0], st.block[1])
+    assert np.array_equal(train.TrainState.init(w, 7, "adam", [3]).block[0], st.block[0])
+    # the header's order: parameters, then gamma / beta, then the running statistics, then the slots
+    st.block[0] = np.arange(st.state_floats)
+    assert st.views(0)["layers.0.weight"][0, 0] == 0 and st.views(0)["layers.1.weight"][0] == P and st.views(0)["layers.1.bias"][0] == P + 26
+    assert st.views(0)["layers.1.running_mean"][0] == P + A and st.views(0)["layers.1.running_var"][0] == P + A + 26
+    assert st.views(0, 1)["layers.0.weight"][0, 0] == P + 2 * A and st.views(0, 2)["layers.12.bias"][-1] == st.state_floats - A - 1
+
+
+def test_state_dict_checkpoint_and_model_round_trip(tmp_path):
+    case = tc.load("w_4_32_7_3")
+    sd = tc.state_dict(case, "sd32:")
+    st = train.TrainState.from_state_dict(sd, "adam")
+    assert st.widths == (4, 32, 7, 3) and st.bn_mask == 1 and st.steps.tolist() == [4]
+    back = st.to_state_dict(0)
+    assert set(back) == set(sd) and all(np.array_equal(back[k].numpy(), sd[k]) for k in sd)
+    want = MlpModel.from_state_dict(sd, "tanh")
+    assert np.array_equal(st.model(0, "tanh").params, want.params)
+    path = train.save_checkpoint(tmp_path / "ann" / "model-abc.pt", st, 0, "abc", {"training": {"activation": "tanh", "epochs": 3}})
+    got = MlpModel.from_checkpoint(path, activation="tanh")
+    assert got.model_id == "abc" and got.widths == want.widths and np.array_equal(got.params, want.params)
+    import torch
+    ck = torch.load(str(path), map_location="cpu", weights_only=True)          # plain: tensors, strings and dicts only
+    assert ck["config"] == {"training": {"activation": "tanh", "epochs": 3}} and ck["model_id"] == "abc"
+    assert int(ck["model_state_dict"]["layers.1.num_batches_tracked"]) == 4
+
+
+def test_a_written_checkpoint_is_loaded_with_the_activation_it_was_trained_with(tmp_path):
+    """`train --activation tanh` then `classify --model ID`: the id alone must bring the activation back, in both forms of the
+    plain-dict config, and the command line's default must not replace it."""
+    from amcpy_amd.classifier import load_model
+    from amcpy_amd.config import Paths
+    cfg = Config(paths=Paths(root=tmp_path))
+    assert cfg.training.activation == "relu"
+    st = train.TrainState.from_state_dict(tc.state_dict(tc.load("w_4_32_7_3"), "sd32:"), "adam")
+    for model_id, act, settings in (("t1", "tanh", {"training": {"activation": "tanh"}}), ("s1", "sigmoid", {"activation": "sigmoid"}),
+                                    ("r1", "relu", {"training": {"epochs": 3}})):
+        train.save_checkpoint(cfg.paths.trained_ann / f"model-{model_id}.pt", st, 0, model_id, settings)
+        model, got_id = load_model(cfg, model_id)
+        assert (got_id, model.activation, model.widths) == (model_id, act, (4, 32, 7, 3))
+    assert train._settings(cfg)["activation"] == "relu" and isinstance(train._settings(cfg)["training_snr"], list)
+
+
+def test_stratified_split_keeps_every_class_share():
+    rng = np.random.default_rng(0)
+    y = np.repeat(np.arange(6), [600, 600, 300, 900, 50, 1200])[rng.permutation(3650)]
+    tr, te = train.stratified_split(y, 0.2, 42)
+    assert len(np.intersect1d(tr, te)) == 0 and np.array_equal(np.sort(np.concatenate([tr, te])), np.arange(3650))
+    assert np.bincount(y[te]).tolist() == [120, 120, 60, 180, 10, 240]
+    again = train.stratified_split(y, 0.2, 42)
+    assert np.array_equal(again[1], te) and not np.array_equal(train.stratified_split(y, 0.2, 43)[1], te)
+
+
+def test_abi_16_1_in_header_binding_and_library():
+    """Training adds entries and constants and changes nothing that exists: the version stays 16 and the minor number counts the
+    addition."""
+    lib = _lib.load()
+    assert (_lib.ABI_VERSION, _lib.ABI_MINOR) >= (16, 1) and (lib.amcx_abi_version(), lib.amcx_abi_minor()) >= (16, 1)
+    header = (REPO / "include" / "amcx.h").read_text()
+    assert re.search(r"^#define AMCX_ABI_MINOR (\d+)$", header, re.M) and "#define AMCX_OPT_RMSPROP 0" in header and "#define AMCX_OPT_ADAM 1" in header
+    assert "ABI 16.1: AMCX_ABI_MINOR 1" in header and header.index("ABI 16.1: AMCX_ABI_MINOR 1") < header.index("ABI 16: the line above")
+    exported = subprocess.run(["nm", "-D", "--defined-only", str(_lib.LIB_PATH)], capture_output=True, text=True, check=True).stdout
+    for name in ("amcx_mlp_train_f32", "amcx_mlp_train_state_floats", "amcx_mlp_train_workspace_floats", "amcx_kernel_name_mlp_train", "amcx_abi_minor"):
+        assert name in _lib.SIGNATURES and re.search(rf"\b{name}\(", header) and re.search(rf" T {name}$", exported, re.M), name
+    assert _lib.kernel_name_mlp_train("relu", "rmsprop") == "amcx_mlp_train_kernel<0, 0>"
+    assert _lib.kernel_name_mlp_train("sigmoid", "adam") == "amcx_mlp_train_kernel<2, 1>"
+    with pytest.raises(ValueError):
+        _lib.kernel_name_mlp_train("relu", "nadam")
+
+
+def test_train_kernels_are_in_the_resource_table_without_scratch_and_older_kernels_kept_their_bytes():
+    import json
+    table = json.loads((REPO / "amcpy_amd" / "csrc" / "kernel_resources.json").read_text())
+    names = [f"amcx_mlp_train_kernel<{a}, {o}>" for a in range(3) for o in range(2)] + ["amcx_mlp_train_hyper_kernel"]
+    for name in names:
+        assert table[name]["spill"] == 0 and table[name]["scratch"] == 0, name
+    listing = (REPO / "profiles" / "r27_train_codeobj_kernels.txt").read_text()
+    assert "DIFFERENT" not in listing and "ONLY IN A" not in listing and "93 kernels / device functions identical" in listing
+    assert sorted(re.findall(r"ONLY IN B\s+amcx::(.+)", listing)) == sorted(names)
+
+
+def test_train_command_in_the_parser():
+    from amcpy_amd.main import build_parser
+    a = build_parser().parse_args(["train", "--root", "/r", "--epochs", "3", "--batch-size", "64", "--lr", "0.01", "--dropout", "0.1",
+                                   "--optimizer", "adam", "--activation", "tanh", "--seed", "5", "--sweep-lr", "0.01,0.02",
+                                   "--sweep-dropout", "0.1,0.2", "--device", "0"])
+    assert (a.command, a.epochs, a.batch_size, a.lr, a.dropout, a.optimizer, a.activation, a.seed) == ("train", 3, 64, 0.01, 0.1, "adam", "tanh", 5)
+    assert a.sweep_lr == "0.01,0.02" and a.sweep_dropout == "0.1,0.2" and a.device == 0
+    d = build_parser().parse_args(["train"])
+    assert d.epochs is None and d.optimizer is None and d.sweep_lr is None
+
+
+def test_nadam_is_refused_by_name():
+    with pytest.raises(NotImplementedError, match="nadam"):
+        train.TrainState.init((6, 8, 6), 1, "nadam", [0])
+    with pytest.raises(NotImplementedError, match="nadam"):
+        train.check_optimizer("nadam")
+    from dataclasses import replace
+    cfg = Config()
+    with pytest.raises(NotImplementedError, match="nadam"):
+        train.train_model(replace(cfg, training=replace(cfg.training, optimizer="nadam")))
+    with pytest.raises(ValueError):
+        train.check_optimizer("sgd")
