@@ -13,7 +13,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
 ABI_VERSION = 16        # the version this binding was written against; any library >= it will do (include/amcx.h)
-ABI_MINOR = 1           # ... and, at that version, the additions it needs (AMCX_ABI_MINOR: 16.1 = training)
+ABI_MINOR = 2           # ... and, at that version, the additions it needs (AMCX_ABI_MINOR: 16.1 = training, 16.2 = the generator)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -29,6 +29,7 @@ ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2                # AMCX_ACT_* (ABI 8)
 ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
 ACT_NONE = 3                                             # AMCX_ACT_NONE (ABI 16): amcx_mlp_range_f32 only
 OPT_RMSPROP, OPT_ADAM = 0, 1                             # AMCX_OPT_* (ABI 16.1)
+SYNTH_RANDOM_PHASE, SYNTH_RANDOM_TIMING = 1, 2           # AMCX_SYNTH_* (ABI 16.2)
 
 
 class UploadStats(C.Structure):
@@ -141,6 +142,10 @@ SIGNATURES = {
                                      C.POINTER(C.c_uint64), _i64, _i32, _vp, _vp]),
     "amcx_kernel_name_mlp_train": (C.c_char_p, [_i32, _i32]),
     "amcx_abi_minor": (C.c_int, []),
+    "amcx_synth_plan": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "amcx_synth_c64": (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32, C.c_uint64,
+                                 C.c_uint32, C.c_uint32, _vp, _i64, _vp, _vp]),
+    "amcx_kernel_name_synth": (C.c_char_p, []),
 }
 
 _lib = None
@@ -327,6 +332,18 @@ def kernel_name_mlp_train(activation: str = "relu", optimizer: str = "rmsprop") 
     if name is None:
         raise ValueError(f"amcx: no training kernel for {activation!r} / {optimizer!r}")
     return name.decode()
+
+
+def kernel_name_synth() -> str:
+    """amcx_kernel_name_synth: the kernel amcx_synth_c64 runs (host-only)."""
+    return load().amcx_kernel_name_synth().decode()
+
+
+def synth_plan(order: int, n_taps: int, up: int, down: int) -> tuple:
+    """amcx_synth_plan -> (samples per tile, bytes of LDS, most workgroups of the persistent grid) (host-only)."""
+    tile, lds, grid = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(load().amcx_synth_plan(int(order), int(n_taps), int(up), int(down), C.byref(tile), C.byref(lds), C.byref(grid)))
+    return tile.value, lds.value, grid.value
 
 
 def kernel_name_psd_detect() -> str:

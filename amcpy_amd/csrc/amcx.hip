@@ -14,7 +14,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_mlp_train_kernel.h" // FIRST of all (ABI 16.1: plain and explicitly instantiated kernels on amcx_mlp_shape.h alone), then the fixed-point ones ...
+#include "amcx_synth_kernel.h"     // FIRST of all (ABI 16.2: it includes the training kernels' header and the down-converter's in front of its one kernel), ...
+#include "amcx_mlp_train_kernel.h" // ... (ABI 16.1: plain and explicitly instantiated kernels on amcx_mlp_shape.h alone), then the fixed-point ones ...
 #include "amcx_mlp_q15_kernel.h"   // ... (ABI 16: plain kernels on amcx_mlp_shape.h alone, which holds no kernel), then the spectrogram's ...
 #include "amcx_psd_kernel.h"       // ... it includes the occupancy and down-converter headers for their device helpers), ...
 #include "amcx_occupancy_kernels.h"  // ... then the occupancy kernels (ABI 14: plain kernels that call nothing of the others), ...
@@ -1623,5 +1624,79 @@ int amcx_mlp_train_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, i
   if (e != hipSuccess) return hip_fail(e, "training kernel launch");
   return AMCX_OK;
 }
+
+// ---- ABI 16.2: the waveform generator (amcx_synth_kernel.h) ---------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// the limits a shape has on its own (the plan's and the entry's first check); the rows, the strides and the groups are the entry's
+bool synth_shape_ok(int32_t order, int32_t n_taps, int32_t up, int32_t down) {
+  return order >= 0 && order <= amcx::kSynMaxOrder && up >= 1 && up <= amcx::kSynMaxUp && down >= 1 && down <= amcx::kSynMaxDown &&
+         n_taps >= 1 && n_taps <= amcx::kSynMaxTaps;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amcx_synth_plan(int32_t order, int32_t n_taps, int32_t up, int32_t down, int32_t* tile_outputs, int32_t* lds_bytes,
+                    int32_t* max_workgroups) {
+  if (!synth_shape_ok(order, n_taps, up, down)) return AMCX_EINVAL;
+  const size_t lds = amcx::syn_lds_bytes(n_taps, up, down, order);
+  if (tile_outputs != nullptr) *tile_outputs = amcx::syn_tile_outputs(n_taps, up, down);
+  if (lds_bytes != nullptr) *lds_bytes = (int32_t)lds;
+  if (max_workgroups != nullptr) *max_workgroups = cu_count() * wgs_per_cu(lds, 8);
+  return AMCX_OK;
+}
+
+int amcx_synth_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, int64_t n_rows, int64_t row_samples, int64_t row_stride,
+                   const void* table_c64_dev, int32_t order, const float* taps_dev, int32_t n_taps, int32_t up, int32_t down,
+                   int32_t tau0, uint64_t phase_step, uint32_t cfo_max, uint32_t flags, const float* sigma_dev,
+                   int64_t frames_per_group, void* out_c64_dev, void* hip_stream) {
+  if (!synth_shape_ok(order, n_taps, up, down)) return AMCX_EINVAL;
+  if (tau0 < 0 || tau0 >= up || (flags & ~(uint32_t)(AMCX_SYNTH_RANDOM_PHASE | AMCX_SYNTH_RANDOM_TIMING)) != 0u) return AMCX_EINVAL;
+  if (row_samples < 1 || sample_index0 < 0 || sample_index0 >= (int64_t(1) << 40) || row_samples >= (int64_t(1) << 40) ||
+      sample_index0 + row_samples >= (int64_t(1) << 40))
+    return AMCX_EINVAL;
+  if (n_rows < 0 || row_stride < row_samples || (n_rows > 0 && row_stride > (int64_t(1) << 58) / n_rows) || frames_per_group < 1)
+    return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (!ptrs_ok({{out_c64_dev, 7u, true}, {taps_dev, 3u, true}, {table_c64_dev, 3u, order > 0}, {sigma_dev, 3u, true}}))
+    return AMCX_EINVAL;
+  amcx::SynArgs a;
+  a.seed_lo = (unsigned)(seed & 0xffffffffull);
+  a.seed_hi = (unsigned)(seed >> 32);
+  a.row_index0 = row_index0;
+  a.sample_index0 = sample_index0;
+  a.n_rows = n_rows;
+  a.row_samples = row_samples;
+  a.row_stride = row_stride;
+  a.table = static_cast<const float2*>(table_c64_dev);
+  a.order = order;
+  a.taps = taps_dev;
+  a.T = n_taps;
+  a.U = up;
+  a.V = down;
+  a.P = amcx::syn_phase_taps(n_taps, up);
+  a.tau0 = tau0;
+  a.max_span = amcx::syn_max_span(n_taps, up, down);
+  a.phase_step = phase_step;
+  a.cfo_max = cfo_max;
+  a.flags = flags;
+  a.sigma = sigma_dev;
+  a.frames_per_group = frames_per_group;
+  a.out = static_cast<float2*>(out_c64_dev);
+  a.tile = amcx::syn_tile_outputs(n_taps, up, down);
+  a.tiles_per_row = (row_samples + a.tile - 1) / a.tile;
+  a.n_items = n_rows * a.tiles_per_row;
+  const size_t lds = amcx::syn_lds_bytes(n_taps, up, down, order);
+  const int64_t grid = amcx::persistent_grid(cu_count(), wgs_per_cu(lds, 8), a.n_items, 1);
+  const hipError_t e = amcx::launch(amcx::amcx_synth_c64_kernel, grid, amcx::kSynThreads, lds, static_cast<hipStream_t>(hip_stream), a);
+  if (e != hipSuccess) return hip_fail(e, "waveform generator kernel launch");
+  return AMCX_OK;
+}
+
+const char* amcx_kernel_name_synth(void) { return "amcx_synth_c64_kernel"; }
 
 }  // extern "C"

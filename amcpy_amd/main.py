@@ -23,6 +23,9 @@ The tuning flags (SigMF only) put the device's down-converter in front: the emit
 finds the emitters of a recording with no raster: the Welch spectrogram on the device, a floor and a mask per row, the occupied
 bins joined into emitters (amcpy_amd/psd.py; sigmf.scan_sigmf), written into a .mat file and, with --annotate, into a copy of
 the meta file as annotations -- which `recording --annotation K --rational` reads back.
+`python -m amcpy_amd synth --root DIR [--mods M ...] [--sps U/V] [--pulse rrc|rect] [--beta B] [--span S] [--frames F] [--frame-size N]
+[--snr lo:hi:step] [--cfo X] [--seed S] [--features-only] [--device D]` makes the labelled data set on the GPU (amcpy_amd/waveform.py):
+mat-data/all_modulations.mat as the reference expects it, or, --features-only, calculated-features/ directly.
 
 Several GPUs, ONE command (the reference's caller runs one command and the parallelism happens inside,
 feature_extraction.py:89-97): ``--devices 0,1,2,3`` / ``--devices all`` drives one engine per device from one
@@ -174,7 +177,50 @@ def build_parser() -> argparse.ArgumentParser:
     sc.add_argument("--out", type=Path, default=None, help="the .mat file to write (default: FILE's stem + _scan.mat)")
     sc.add_argument("--annotate", type=Path, default=None, metavar="OUT.sigmf-meta",
                     help="a copy of the meta file with one annotation per emitter, for `recording --annotation K --rational`")
+    sy = sub.add_parser("synth", help="make the labelled data set on the GPU: mat-data/all_modulations.mat, or the feature files directly")
+    sy.add_argument("--root", type=Path, default=None, help="project root (default: cwd)")
+    sy.add_argument("--mods", nargs="+", default=None, metavar="MOD", help="modulations (default: the configuration's, with WGN)")
+    sy.add_argument("--sps", default="8/1", metavar="U/V", help="U / V samples per symbol (default 8/1)")
+    sy.add_argument("--pulse", choices=("rrc", "rect"), default="rrc")
+    sy.add_argument("--beta", type=float, default=0.35, help="roll-off of the root-raised-cosine pulse (default 0.35)")
+    sy.add_argument("--span", type=int, default=16, metavar="S", help="symbols the root-raised-cosine pulse spans (default 16)")
+    sy.add_argument("--frames", type=int, default=None, metavar="F", help="frames per (modulation, SNR) (default: the configuration's)")
+    sy.add_argument("--frame-size", type=int, default=None, metavar="N")
+    sy.add_argument("--snr", default=None, metavar="lo:hi:step", help="the SNR grid in dB, hi included (default: the configuration's 16)")
+    sy.add_argument("--cfo", type=float, default=0.0, metavar="X", help="largest carrier offset, cycles per sample: a frame draws its own in [-X, X)")
+    sy.add_argument("--seed", type=int, default=0)
+    sy.add_argument("--features-only", action="store_true",
+                    help="write calculated-features/{mod}_features.mat directly; the IQ is made a chunk at a time and never stored")
+    sy.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
     return ap
+
+
+def synth_config(args) -> tuple:
+    """The configuration and the SNR grid the `synth` command's flags name."""
+    from .waveform import _label, parse_snr
+    cfg = Config() if args.root is None else Config(paths=Paths(root=args.root))
+    sig = cfg.signals
+    if args.frame_size is not None:
+        sig = replace(sig, frame_size=args.frame_size)
+    if args.frames is not None:
+        sig = replace(sig, num_frames=args.frames)
+    snr = None
+    if args.snr is not None:
+        snr = parse_snr(args.snr)
+        sig = replace(sig, snr_values={i: _label(v) for i, v in enumerate(snr)})
+    return replace(cfg, signals=sig), snr
+
+
+def run_synth(args, compute=None, features=None) -> list:
+    """The `synth` command (amcpy_amd/waveform.py, run_synth); ``compute`` / ``features``: injected over numpy (tests)."""
+    from . import waveform
+    cfg, snr = synth_config(args)
+    try:
+        return waveform.run_synth(cfg, mods=args.mods, sps=waveform.parse_sps(args.sps), pulse=args.pulse, beta=args.beta, span=args.span,
+                                  snr=snr, cfo=args.cfo, seed=args.seed, features_only=args.features_only,
+                                  device=None if args.device is None else f"cuda:{args.device}", compute=compute, features=features)
+    except ValueError as e:
+        raise SystemExit(f"synth: {e}")
 
 
 def recording_survey(args):
@@ -554,6 +600,9 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
         return 0
     if args.command == "scan":                # tensors on torch's runtime: this command never skips the import
         run_scan(args)
+        return 0
+    if args.command == "synth":               # likewise
+        run_synth(args)
         return 0
     cfg = Config() if args.root is None else Config(paths=Paths(root=args.root))
     sig = cfg.signals

@@ -1,0 +1,459 @@
+"""The waveform generator: labelled IQ made where it is used (amcx_synth_c64, include/amcx.h ABI 16.2).
+
+One launch writes rows of linearly modulated signal -- symbols of a constellation drawn by Philox4x32-10, a pulse at
+``U / V`` samples per symbol, a carrier with a random phase and a bounded random offset, a random timing offset, white Gaussian
+noise -- as complex64 in GPU memory.  Every random integer is fixed by the header's contract: a row is named by its ABSOLUTE
+index and a sample by its absolute index in the row, so a data set made in any number of calls, or a stream made in chunks of
+any length, equals one call bit for bit, and tests/synth_ref.py restates it in numpy.
+
+    design_rrc / design_rect     pulses with sum g^2 = U: unit signal power with a unit-power table, SNR = 1 / sigma^2
+    constellation_table          :func:`amcpy_amd.synth.constellation`'s points as complex64 (WGN: none -- the noise class)
+    generate                     one launch: (n_rows, row_samples) complex64
+    dataset / dataset_features   the reference's container layout, mod -> (n_snr, n_frames, frame_size) or (..., 18)
+    Stream                       one row, ``push(n)`` the next n samples
+    scene                        emitters at known frequencies, rates and times on a noise floor, with the ground truth
+    run_synth                    the `synth` command: mat-data/all_modulations.mat, or calculated-features/ directly
+
+:mod:`amcpy_amd.synth` stays what it is: the benchmark's and the fixtures' generator, whose numbers they depend on.
+"""
+from __future__ import annotations
+
+import json
+import math
+from fractions import Fraction
+
+import numpy as np
+
+from . import _lib, _stream, synth
+
+MAX_TAPS, MAX_UP, MAX_DOWN, MAX_ORDER = 4096, 256, 4096, 256
+_MASK64 = (1 << 64) - 1
+FRAME_BITS, SNR_BITS = 32, 16          # dataset's rows: (modulation code << 48) | (SNR code << 32) | frame
+
+
+def design_rect(U: int) -> np.ndarray:
+    """The rectangular pulse of one symbol: U ones (sum g^2 = U)."""
+    U = int(U)
+    if not 1 <= U <= MAX_UP:
+        raise ValueError(f"design_rect: U {U} is outside 1 ... {MAX_UP}")
+    return np.ones(U, np.float32)
+
+
+def design_rrc(U: int, span_symbols: int = 16, beta: float = 0.35) -> np.ndarray:
+    """A root-raised-cosine pulse at U samples per symbol over ``span_symbols`` symbols: ``span_symbols * U + 1`` float32 taps,
+    symmetric, computed in float64 and normalised to sum g^2 = U before the rounding.  ValueError where the taps pass 4096."""
+    U, span, beta = int(U), int(span_symbols), float(beta)
+    if not 1 <= U <= MAX_UP or span < 1 or not 0.0 < beta <= 1.0:
+        raise ValueError(f"design_rrc: U {U} (1 ... {MAX_UP}), span_symbols {span} (>= 1), beta {beta} (0 < beta <= 1)")
+    T = span * U + 1
+    if T > MAX_TAPS:
+        raise ValueError(f"design_rrc: {span} symbols at {U} samples per symbol are {T} taps, more than {MAX_TAPS}")
+    t = (np.arange(T, dtype=np.float64) - (T - 1) / 2.0) / U
+    g = np.empty(T, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        num = np.sin(np.pi * t * (1 - beta)) + 4 * beta * t * np.cos(np.pi * t * (1 + beta))
+        g = num / (np.pi * t * (1 - (4 * beta * t) ** 2))
+    g[np.abs(t) < 1e-12] = 1 - beta + 4 * beta / np.pi
+    edge = np.abs(np.abs(4 * beta * t) - 1.0) < 1e-9
+    g[edge] = beta / math.sqrt(2.0) * ((1 + 2 / np.pi) * math.sin(np.pi / (4 * beta)) + (1 - 2 / np.pi) * math.cos(np.pi / (4 * beta)))
+    g = (g + g[::-1]) / 2.0
+    return (g * math.sqrt(U / float(np.sum(g * g)))).astype(np.float32)
+
+
+def constellation_table(mod: str) -> np.ndarray:
+    """The points of a modulation as complex64, unit average power; "WGN" / "NOISE": no point at all, the noise class."""
+    pts = synth.constellation(mod)
+    if mod.upper() in ("WGN", "NOISE"):
+        return np.zeros(0, np.complex64)
+    if len(pts) > MAX_ORDER:
+        raise ValueError(f"{mod}: {len(pts)} points, the generator takes {MAX_ORDER}")
+    return pts.astype(np.complex64)
+
+
+def cfo_max_of(cfo) -> int:
+    """The largest carrier offset a row draws, cycles per sample -> the entry's units of 2^-33 cycles per sample."""
+    c = int(round(Fraction(cfo) * (1 << 33)))
+    if not 0 <= c < 1 << 32:
+        raise ValueError(f"cfo must lie in [0, 0.5) cycles per sample, got {cfo!r}")
+    return c
+
+
+def sigma_of(snr_db) -> np.ndarray:
+    """sigma = 10^(-snr_db / 20) as float32: with a unit-power signal SNR = 1 / sigma^2."""
+    return (10.0 ** (-np.atleast_1d(np.asarray(snr_db, dtype=np.float64)) / 20.0)).astype(np.float32)
+
+
+def _sigmas(mod, snr_db, sigma):
+    if snr_db is not None and sigma is not None:
+        raise ValueError("either snr_db or sigma")
+    if sigma is not None:
+        s = np.atleast_1d(np.asarray(sigma, dtype=np.float32))
+    elif snr_db is not None:
+        s = sigma_of(snr_db)
+        if isinstance(mod, str) and mod.upper() in ("WGN", "NOISE"):       # no signal to set the noise against: unit noise power
+            s = np.ones_like(s)
+    else:
+        s = np.zeros(1, np.float32)
+    if s.ndim != 1 or not np.all(np.isfinite(s)) or np.any(s < 0):
+        raise ValueError("every sigma must be a finite float32 >= 0")
+    return s
+
+
+def _shape(sps, taps):
+    U, V = (int(sps), 1) if isinstance(sps, (int, np.integer)) else (int(sps[0]), int(sps[1]))
+    if not (1 <= U <= MAX_UP and 1 <= V <= MAX_DOWN):
+        raise ValueError(f"sps: U / V = {U} / {V} is outside 1 ... {MAX_UP} / 1 ... {MAX_DOWN}")
+    return U, V
+
+
+def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_db=None, sigma=None, frames_per_group=None,
+             seed: int = 0, row_index0: int = 0, sample_index0: int = 0, cfo=0.0, shift=0.0, random_phase: bool = True,
+             random_timing: bool = True, timing: int = 0, out=None, device=None, compute=None):
+    """One launch of amcx_synth_c64 on the current torch stream -> complex64 ``(n_rows, row_samples)`` in GPU memory.
+
+    mod     : a modulation's name (:func:`constellation_table`), or the table itself: up to 256 complex points, none for noise.
+              The table (complex64), ``taps`` and ``sigma`` (float32) may each be a tensor on the device instead of a host
+              array: what is a tensor is not uploaded.  With all three and ``out`` given the call is the launch alone -- no
+              upload, no allocation -- and can be captured in a graph.  A ``sigma`` tensor's values are the caller's.
+    sps     : ``(U, V)``: U / V samples per symbol, the taps given at U per symbol; an int is ``(U, 1)``.
+    taps    : the pulse, float32 (numpy, or a tensor on the device); default :func:`design_rect`.
+    snr_db / sigma : the noise, a scalar or one value per group of ``frames_per_group`` rows (default: the rows spread evenly
+              over the values; no noise at all where neither is given).  "WGN" with ``snr_db`` is noise of unit power.
+    seed, row_index0, sample_index0 : the key and where the call begins; rows ``row_index0 ...`` and samples
+              ``sample_index0 ...`` of the same seed are the same numbers in whatever call they are made.
+    cfo     : the largest carrier offset, cycles per sample: a row draws its own in ``[-cfo, cfo)``.  ``shift``: an offset every
+              row has (cycles per sample, a float or a Fraction).
+    random_phase, random_timing : a row's carrier phase and its timing ``tau`` (0 <= tau < U) drawn; else 0 and ``timing``.
+    out     : a complex64 tensor ``(n_rows, row_samples)`` to write, possibly a strided view with contiguous rows.
+    compute : tests only -- ``f(table, taps, U, V, n_rows, row_samples, sigma, frames_per_group, seed=..., row_index0=...,
+              sample_index0=..., phase_step=..., cfo_max=..., flags=..., tau0=...)`` over numpy (tests/synth_ref.numpy_generate)."""
+    tensor = lambda t: hasattr(t, "data_ptr")                              # noqa: E731  (a torch tensor, without importing torch)
+    if compute is not None and (tensor(mod) or tensor(taps) or tensor(sigma) or out is not None):
+        raise TypeError("an injected compute takes host arrays and returns its own output")
+    U, V = _shape(sps, taps)
+    R, S = int(n_rows), int(row_samples)
+    if tensor(mod):
+        table = mod
+    else:
+        table = constellation_table(mod) if isinstance(mod, str) else np.ascontiguousarray(np.asarray(mod, dtype=np.complex64)).reshape(-1)
+    if not tensor(taps):
+        taps = design_rect(U) if taps is None else np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+    if tensor(sigma):
+        if snr_db is not None:
+            raise ValueError("either snr_db or sigma")
+        sig = sigma                                                        # on the device: its values are the caller's (a NaN propagates)
+    else:
+        sig = _sigmas(mod, snr_db, sigma)
+    order, T, G = (int(t.shape[0]) if t.ndim == 1 else -1 for t in (table, taps, sig))
+    if R < 0 or S < 1 or not 0 <= int(sample_index0) or int(sample_index0) + S >= 1 << 40 or not 0 <= order <= MAX_ORDER \
+            or not 1 <= T <= MAX_TAPS or G < 1:
+        raise ValueError(f"outside the generator's limits: n_rows {R}, row_samples {S}, sample_index0 {sample_index0}, order {order}, "
+                         f"{T} taps, {G} sigmas (each in one dimension)")
+    if not 0 <= int(timing) < U:
+        raise ValueError(f"timing must lie in 0 ... U - 1 = {U - 1}")
+    fpg = max(1, -(-R // G)) if frames_per_group is None else int(frames_per_group)
+    if fpg < 1 or (R > 0 and -(-R // fpg) > G):
+        raise ValueError(f"{R} rows in groups of {fpg} need {-(-R // max(fpg, 1))} sigmas, {G} given")
+    flags = (_lib.SYNTH_RANDOM_PHASE if random_phase else 0) | (_lib.SYNTH_RANDOM_TIMING if random_timing else 0)
+    step, cfo_max = _stream.phase_step_of(shift), cfo_max_of(cfo)
+    where = dict(seed=int(seed) & _MASK64, row_index0=int(row_index0) & _MASK64, sample_index0=int(sample_index0),
+                 phase_step=step, cfo_max=cfo_max, flags=flags, tau0=int(timing))
+    if compute is not None:
+        return compute(table if order else None, taps, U, V, R, S, sig, fpg, **where)
+
+    import torch
+    if out is not None:
+        _, _, stride = _stream.rows_of(out, torch.complex64, "out", "row_samples", S, S, narrow="out must have row_samples = {} columns",
+                                       min_rows=R)
+        if int(out.shape[0]) != R:
+            raise ValueError(f"out has {int(out.shape[0])} rows, the call makes {R}")
+        dev = out.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        stride = S
+
+    def resident(t, dtype, name):
+        """``t`` on the device: a host array is uploaded, a tensor is taken as it is (and must be what the kernel reads)"""
+        if not isinstance(t, torch.Tensor):
+            return torch.from_numpy(t).to(dev)
+        if t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous one-dimensional {str(dtype).replace('torch.', '')} tensor on the output's device")
+        return t
+
+    table, taps, sig = resident(table, torch.complex64, "the table"), resident(taps, torch.float32, "taps"), resident(sig, torch.float32, "sigma")
+    if out is None:
+        out = torch.empty((R, S), dtype=torch.complex64, device=dev)
+    _stream.launch(out, lambda lib, stream: lib.amcx_synth_c64(
+        where["seed"], where["row_index0"], where["sample_index0"], R, S, stride, table.data_ptr() if order else None, order,
+        taps.data_ptr(), T, U, V, where["tau0"], step, cfo_max, flags, sig.data_ptr(), fpg, out.data_ptr() if R else None, stream))
+    return out
+
+
+# ---- data sets ----------------------------------------------------------------------------------------------------------------
+def mod_code(mod: str) -> int:
+    """A modulation's number in :func:`dataset`'s rows, from its name alone: (family << 12) | order, the family 0 for a name
+    that ends in PSK, 1 for QAM, 2 for the noise class.  Two names of one family and order (a variant constellation added
+    later under another name) would share their rows: :func:`dataset` refuses them in one call."""
+    m = mod.upper()
+    if m in ("WGN", "NOISE"):
+        return 2 << 12
+    order = len(synth.constellation(m))
+    return ((0 if m.endswith("PSK") else 1) << 12) | order
+
+
+def snr_code(snr_db) -> int:
+    """An SNR's number in :func:`dataset`'s rows, from its value alone: eighths of a dB above -1000 dB, the nearest.  Two
+    values less than 0.125 dB apart can share a number, and so their rows -- the same symbols and noise words at another
+    sigma: :func:`dataset` refuses them in one call."""
+    c = int(round((float(snr_db) + 1000.0) * 8.0))
+    if not 0 <= c < 1 << SNR_BITS:
+        raise ValueError(f"snr_db {snr_db!r} is outside -1000 ... +7191 dB")
+    return c
+
+
+def dataset_row(mod: str, snr_db, frame: int = 0) -> int:
+    """The absolute row of (modulation, SNR, frame): the same whatever subset of modulations, SNRs or frames is asked for."""
+    if not 0 <= int(frame) < 1 << FRAME_BITS:
+        raise ValueError("frame must lie in 0 ... 2^32 - 1")
+    return (mod_code(mod) << (SNR_BITS + FRAME_BITS)) | (snr_code(snr_db) << FRAME_BITS) | int(frame)
+
+
+def _grid(mods, snr_db) -> tuple:
+    """The modulations and SNRs of a data set; ValueError where two of either share their rows (mod_code, snr_code)."""
+    mods = list(mods)
+    snrs = [float(v) for v in np.atleast_1d(np.asarray(snr_db, dtype=np.float64))]
+    for what, items, code in (("modulations", mods, mod_code), ("SNR values", snrs, snr_code)):
+        seen = {}
+        for item in items:
+            if seen.setdefault(code(item), item) != item or items.count(item) > 1:
+                raise ValueError(f"the {what} {seen[code(item)]!r} and {item!r} name the same rows of a data set: one of them in a call")
+    return mods, snrs
+
+
+def _resident_pulse(mod, snrs, kw) -> dict:
+    """``kw`` of :func:`generate` with a modulation's table, the taps and the grid's sigmas uploaded ONCE (GPU path only)."""
+    import torch
+    dev = kw.get("device")
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
+    U, _ = _shape(kw.get("sps", (8, 1)), None)
+    taps = kw.get("taps")
+    if not isinstance(taps, torch.Tensor):
+        taps = torch.from_numpy(design_rect(U) if taps is None else np.ascontiguousarray(np.asarray(taps, dtype=np.float32))).to(dev)
+    table = torch.from_numpy(constellation_table(mod)).to(dev)
+    sig = torch.from_numpy(_sigmas(mod, snrs, None)).to(dev)
+    return dict(kw, taps=taps, device=dev), table, sig
+
+
+def dataset(mods, snr_db, n_frames: int, frame_size: int, *, first_frame: int = 0, **kw) -> dict:
+    """mod -> ``(n_snr, n_frames, frame_size)`` complex64, the reference's container layout.  Frame f of (mod, SNR) is row
+    :func:`dataset_row` ``(mod, snr, first_frame + f)``, so any subset names the same rows; the rows of two SNRs are 2^32 apart,
+    which makes it one launch per (modulation, SNR), each into its slice of the modulation's array.  The table, the taps and
+    the sigmas go to the device once per modulation; the launches upload nothing."""
+    mods, snrs = _grid(mods, snr_db)
+    compute = kw.get("compute")
+    data = {}
+    for mod in mods:
+        if compute is None:
+            import torch
+            kw_dev, table, sig = _resident_pulse(mod, snrs, kw)
+            arr = torch.empty((len(snrs), int(n_frames), int(frame_size)), dtype=torch.complex64, device=kw_dev["device"])
+            for s, snr in enumerate(snrs):
+                generate(table, n_frames, frame_size, sigma=sig[s:s + 1], row_index0=dataset_row(mod, snr, first_frame), out=arr[s], **kw_dev)
+        else:
+            arr = np.empty((len(snrs), int(n_frames), int(frame_size)), np.complex64)
+            for s, snr in enumerate(snrs):
+                arr[s] = generate(mod, n_frames, frame_size, snr_db=snr, row_index0=dataset_row(mod, snr, first_frame), **kw)
+        data[mod] = arr
+    return data
+
+
+def dataset_features(mods, snr_db, n_frames: int, frame_size: int, *, chunk_frames: int = 1 << 14, features=None, **kw) -> dict:
+    """mod -> ``(n_snr, n_frames, 18)`` float32 (numpy): the frames of :func:`dataset` made ``chunk_frames`` at a time, put
+    through :func:`amcpy_amd.features.features18` and dropped, so a training set larger than the device's memory never exists
+    as IQ.  ``features``: tests only, ``f(frames (F, N) complex64 numpy) -> (F, 18)`` beside an injected ``compute``."""
+    mods, snrs = _grid(mods, snr_db)
+    F, chunk = int(n_frames), max(1, int(chunk_frames))
+    on_gpu = kw.get("compute") is None
+    if features is None:
+        from .features import features18
+        features = lambda x: features18(x).cpu().numpy()           # noqa: E731
+    out = {}
+    for mod in mods:
+        feats = np.empty((len(snrs), F, _lib.NUM_FEATURES), np.float32)
+        if on_gpu:
+            import torch
+            kw_dev, table, sig = _resident_pulse(mod, snrs, kw)
+            buf = torch.empty((min(chunk, F), int(frame_size)), dtype=torch.complex64, device=kw_dev["device"])
+        for s, snr in enumerate(snrs):
+            for f0 in range(0, F, chunk):
+                n = min(chunk, F - f0)
+                if on_gpu:
+                    x = generate(table, n, frame_size, sigma=sig[s:s + 1], row_index0=dataset_row(mod, snr, f0), out=buf[:n], **kw_dev)
+                else:
+                    x = generate(mod, n, frame_size, snr_db=snr, row_index0=dataset_row(mod, snr, f0), **kw)
+                feats[s, f0:f0 + n] = np.asarray(features(x), dtype=np.float32)[:, :_lib.NUM_FEATURES]
+        out[mod] = feats
+    return out
+
+
+class Stream:
+    """One row as a stream: ``push(n)`` returns its next n samples (``index`` counts the samples made so far, as
+    :class:`amcpy_amd._stream.Chunked` counts them).  Cut anywhere, the chunks equal one call bit for bit.  The keywords are
+    :func:`generate`'s; ``row`` is the absolute row."""
+
+    def __init__(self, mod, *, row: int = 0, **kw):
+        for bad in ("row_index0", "sample_index0", "out", "frames_per_group"):
+            if bad in kw:
+                raise ValueError(f"Stream: {bad} is the stream's own")
+        self.mod, self.row, self.index, self._kw = mod, int(row), 0, dict(kw)
+        if self._kw.get("taps") is not None and not hasattr(self._kw["taps"], "data_ptr"):
+            self._kw["taps"] = np.ascontiguousarray(np.asarray(self._kw["taps"], dtype=np.float32))
+        self._taps_dev = None
+
+    def push(self, n: int):
+        n = int(n)
+        if n < 0:
+            raise ValueError("push: n >= 0")
+        kw = dict(self._kw)
+        if n == 0:
+            if kw.get("compute") is not None:
+                return np.empty(0, np.complex64)
+            import torch
+            return torch.empty(0, dtype=torch.complex64, device=kw.get("device") or torch.device("cuda", torch.cuda.current_device()))
+        if kw.get("compute") is None and isinstance(kw.get("taps"), np.ndarray):       # the taps uploaded once
+            import torch
+            if self._taps_dev is None:
+                dev = kw.get("device")
+                self._taps_dev = torch.from_numpy(np.ascontiguousarray(kw["taps"])).to(
+                    torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev))
+            kw["taps"] = self._taps_dev
+        y = generate(self.mod, 1, n, row_index0=self.row, sample_index0=self.index, **kw)
+        self.index += n
+        return y[0]
+
+
+def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device=None) -> tuple:
+    """A stream of ``n_samples`` with known emitters on a noise floor -> ``(x, annotations)``.
+
+    emitters : dicts with ``mod``, ``sps`` (U, V), ``center`` (cycles per sample of the scene), and optionally ``rate`` (L, D)
+               (1, 1), ``start`` (0), ``length`` (to the end), ``amplitude`` (1), ``taps`` (default: :func:`design_rrc` over 16
+               symbols where U > V and it fits, else rect), ``beta`` (0.35).  Emitter e is row e of the seed; the floor is the
+               noise class in row ``len(emitters)``.
+    Each emitter is one :class:`Stream` row at its own U / V samples per symbol, brought to the scene's rate by
+    :func:`amcpy_amd.resample.resample` (L / D, the default low-pass: U L / (V D) samples per symbol in the scene), moved to its
+    centre by the same entry's mixer (one tap of 1, ``shift=center``, the phase counted from the scene's sample 0) and added in.
+    annotations : one dict per emitter with the keys :func:`amcpy_amd.sigmf.tune_from_annotation` reads --
+               ``core:sample_start``, ``core:sample_count``, ``core:freq_lower_edge`` / ``core:freq_upper_edge`` in cycles per
+               sample (the occupied band: (1 + beta) symbol rates wide, one symbol rate for a rectangular pulse) -- and
+               ``core:label``, ``amcx:samples_per_symbol``."""
+    import torch
+
+    from .resample import design_resample_lowpass, out_samples, resample
+    S = int(n_samples)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    x = generate("WGN", 1, S, sigma=float(noise_sigma), seed=seed, row_index0=len(emitters), device=dev)[0]
+    one = torch.ones(1, dtype=torch.float32, device=dev)
+    annotations = []
+    for e, em in enumerate(emitters):
+        U, V = _shape(em["sps"], None)
+        L, D = (int(v) for v in em.get("rate", (1, 1)))
+        start = int(em.get("start", 0))
+        length = int(em.get("length", S - start))
+        if not (0 <= start and length >= 1 and start + length <= S):
+            raise ValueError(f"emitter {e}: samples {start} ... {start + length} are outside the scene's {S}")
+        beta = float(em.get("beta", 0.35))
+        taps = em.get("taps")
+        rrc = taps is None and 16 * U + 1 <= MAX_TAPS and U > V
+        if taps is None:
+            taps = design_rrc(U, 16, beta) if rrc else design_rect(U)
+        stream = Stream(em["mod"], row=e, sps=(U, V), taps=taps, seed=seed, device=dev)
+        if (L, D) == (1, 1):
+            y = stream.push(length)
+        else:
+            low = design_resample_lowpass(L, D)
+            n_in = -(-length * D // L) + -(-len(low) // L) + 1
+            while out_samples(n_in, len(low), L, D) < length:
+                n_in += 1
+            y = resample(stream.push(n_in), low, L, D)[:length]
+        y = resample(y.contiguous(), one, 1, 1, shift=em["center"], sample_index0=start)
+        x[start:start + length] += y * float(em.get("amplitude", 1.0))
+        per_symbol = Fraction(U * L, V * D)
+        width = (1.0 + beta if rrc else 1.0) / float(per_symbol)
+        annotations.append({"core:sample_start": start, "core:sample_count": length, "core:label": str(em["mod"]),
+                            "core:freq_lower_edge": float(em["center"]) - width / 2.0,
+                            "core:freq_upper_edge": float(em["center"]) + width / 2.0,
+                            "amcx:samples_per_symbol": float(per_symbol)})
+    return x, annotations
+
+
+# ---- the `synth` command ----------------------------------------------------------------------------------------------------------
+def parse_sps(text: str) -> tuple:
+    u, _, v = str(text).partition("/")
+    return int(u), int(v) if v else 1
+
+
+def parse_snr(text: str) -> list:
+    """``lo:hi:step`` (hi included) or one value, in dB."""
+    parts = [float(p) for p in str(text).split(":")]
+    if len(parts) == 1:
+        return [parts[0]]
+    if len(parts) != 3 or parts[2] <= 0 or parts[1] < parts[0]:
+        raise ValueError(f"--snr: lo:hi:step with step > 0 and hi >= lo, got {text!r}")
+    n = int(math.floor((parts[1] - parts[0]) / parts[2] + 1e-9)) + 1
+    return [parts[0] + i * parts[2] for i in range(n)]
+
+
+def _label(v: float) -> str:
+    return str(int(v)) if float(v).is_integer() else repr(float(v))
+
+
+V5_LIMIT = (1 << 31) - 1      # bytes of one MATLAB v5 file's variables
+
+
+def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0.35, span: int = 16, snr=None, cfo=0.0,
+              seed: int = 0, features_only: bool = False, device=None, compute=None, features=None, verbose: bool = True) -> list:
+    """The `synth` command: the data set of ``cfg`` (its frame size, frame count and SNR labels, unless ``snr`` names the
+    grid) for ``mods`` (default ``cfg.signals.modulations_with_noise``) into ``mat-data/all_modulations.mat`` under the variables
+    ``cfg.signals.mat_info`` names -- or, ``features_only``, straight into ``calculated-features/{mod}_features.mat`` with the
+    provenance record `extract --resume` trusts.  Returns the files written.  ``compute`` / ``features``: injected (tests)."""
+    import scipy.io
+
+    from .feature_extraction import _provenance, _provenance_path
+    sig = cfg.signals
+    mods = list(sig.modulations_with_noise if mods is None else mods)
+    for m in mods:
+        if m not in sig.mat_info:
+            raise ValueError(f"{m}: the configuration names no container variable for it ({sorted(sig.mat_info)})")
+    snrs = [float(v) for v in sig.snr_values.values()] if snr is None else [float(v) for v in snr]
+    if len(snrs) != len(sig.snr_values):
+        raise ValueError(f"{len(snrs)} SNR values against the configuration's {len(sig.snr_values)} labels")
+    U, V = _shape(sps, None)
+    if pulse not in ("rrc", "rect"):
+        raise ValueError("pulse: rrc or rect")
+    taps = design_rrc(U, span, beta) if pulse == "rrc" else design_rect(U)
+    F, N = int(sig.num_frames), int(sig.frame_size)
+    kw = dict(sps=(U, V), taps=taps, cfo=cfo, seed=seed, compute=compute)
+    if compute is None:
+        kw["device"] = device
+    cfg.paths.ensure_dirs()
+    mat_path = cfg.paths.mat_data / cfg.paths.mat_filename
+    if features_only:
+        written = []
+        for m in mods:
+            feats = dataset_features([m], snrs, F, N, features=features, **kw)[m]
+            out_path = cfg.paths.calculated_features / f"{m}_features.mat"
+            scipy.io.savemat(str(out_path), {"Modulation": m, sig.mat_info[m]: feats})
+            _provenance_path(out_path).write_text(json.dumps(_provenance(cfg, mat_path, sig.mat_info[m])) + "\n")
+            written.append(out_path)
+            if verbose:
+                print(f"synth: {m}: features {feats.shape} -> {out_path}")
+        return written
+    per_mod = len(snrs) * F * N * 8
+    if per_mod * len(mods) > V5_LIMIT:
+        raise ValueError(f"the container would hold {len(mods)} variables of {len(snrs)} x {F} x {N} complex64, {per_mod * len(mods)} bytes: "
+                         f"more than a MATLAB v5 file's {V5_LIMIT}; --features-only writes calculated-features/ without it")
+    data = dataset(mods, snrs, F, N, **kw)
+    scipy.io.savemat(str(mat_path), {sig.mat_info[m]: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for m, v in data.items()})
+    if verbose:
+        print(f"synth: {len(mods)} modulations x {len(snrs)} SNRs x {F} frames of {N} -> {mat_path}")
+    return [mat_path]

@@ -100,10 +100,12 @@ extern "C" {
  * (all listed behind the define); 15 = the Welch spectrogram and its per-row detection; 16 = fixed-point deployment of the
  * classifier's network (range calibration and 16-bit integer inference).
  * AMCX_ABI_MINOR counts what has been ADDED since the version last changed -- new entries and constants, nothing existing changed:
- * 16.1 = training of the classifier's network, one workgroup per model. */
+ * 16.1 = training of the classifier's network, one workgroup per model; 16.2 = the waveform generator. */
 #define AMCX_ABI_VERSION 16
-#define AMCX_ABI_MINOR 1
+#define AMCX_ABI_MINOR 2
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
+ *   ABI 16.2: AMCX_ABI_MINOR 2            -- the waveform generator: AMCX_SYNTH_*, amcx_synth_c64, amcx_synth_plan,
+ *                                            amcx_kernel_name_synth
  *   ABI 16.1: AMCX_ABI_MINOR 1            -- training: AMCX_OPT_*, amcx_mlp_train_f32, amcx_mlp_train_state_floats,
  *                                            amcx_mlp_train_workspace_floats, amcx_kernel_name_mlp_train, amcx_abi_minor
  *   ABI 16: the line above               -- fixed-point deployment: AMCX_ACT_NONE, amcx_mlp_range_f32, amcx_mlp_classify_q15,
@@ -1042,6 +1044,61 @@ int amcx_mlp_train_f32(const float* x_dev, int64_t n_rows, int64_t row_stride, i
                        float* ws_dev, const float* lr_host, const uint32_t* drop_threshold_host, const float* keep_scale_host,
                        const uint64_t* seed_host, int64_t step0, int32_t n_steps, double* history_dev, void* hip_stream);
 const char* amcx_kernel_name_mlp_train(int32_t activation, int32_t optimizer);
+
+/*
+ * ABI 16.2.  THE WAVEFORM GENERATOR: n_rows rows of row_samples complex64 samples of a linearly modulated signal -- symbols drawn
+ * by Philox4x32-10, a pulse at U / V samples per symbol (up / down), a carrier, white Gaussian noise -- in ONE launch on
+ * hip_stream (amcpy_amd/csrc/amcx_synth_kernel.h).  It allocates nothing, never synchronises and can be captured in a graph; no
+ * atomics, no workgroup waits for another.  A row is one frame or one long stream.  r = row_index0 + f is the ABSOLUTE row of
+ * the call's row f, n = sample_index0 + i the ABSOLUTE sample of its sample i: a call can begin anywhere.
+ *
+ *   key              = (seed low word, seed high word)                 Philox4x32-10, the generator of the dropout mask above
+ *   counter(s, j, r) = (j & 0xFFFFFFFF, (s << 28) | (j >> 32), r low word, r high word)      stream s = 0 row, 1 symbols, 2 noise
+ *   row words        W = Philox(counter(0, 0, r))
+ *     carrier phase  phase0_r = flags & AMCX_SYNTH_RANDOM_PHASE  ? (uint64)W[0] << 32 : 0
+ *     carrier step   step_r   = phase_step + (uint64)((int64)(int32)W[1] * (int64)cfo_max)   mod 2^64, in 2^-64 cycles per sample
+ *                               cfo_max: in 2^-33 cycles per sample, the largest offset a row draws; 0 = none
+ *     timing         tau_r    = flags & AMCX_SYNTH_RANDOM_TIMING ? mulhi32(W[2], U) : tau0    0 <= tau < U
+ *   symbol k >= 0    a[k] = table[mulhi32(Philox(counter(1, k >> 2, r))[k & 3], order)]      table_c64_dev: `order` complex64 points
+ *   pulse            t_n = n V + tau_r,  p_n = t_n mod U,  k_n = (P - 1) + floor(t_n / U),  P = ceil(T / U),  T = n_taps
+ *                    s[n] = sum_{q >= 0, p_n + q U < T} g[p_n + q U] * a[k_n - q]             g = taps_dev, at U samples per symbol
+ *                    one product, then one FMA per component in ascending q: amcx_resample's order with L = U, D = V
+ *   carrier          v[n] = s[n] * exp(+2 pi j phi / 2^64), phi = phase0_r + n * step_r: the down-converter's mixer, the same bits
+ *                    (phi < 2^32 skips the product)
+ *   noise            X = Philox(counter(2, n >> 1, r));  w1 = X[2 (n & 1)],  w2 = X[2 (n & 1) + 1]
+ *                    u = ((w1 >> 8) + 1) * 2^-24          in (0, 1], exact in float32
+ *                    z[n] = (sigma_g * sqrt(-ln u)) * exp(2 pi j w2 / 2^32)                   the same mixer; E|z|^2 = sigma_g^2
+ *                    sigma_g = sigma_dev[f / frames_per_group], f the row's index IN THE CALL
+ *   out[f, i]        = (v.re + z.re, v.im + z.im)         one float32 addition per component; at out_c64_dev + f row_stride + i
+ *
+ * order == 0 is the noise class: s is exactly +0 + 0j, no symbol is drawn, table_c64_dev is not read (and may be NULL).
+ * sigma_g == 0 gives out == v, the signed zeros of v kept.  No gain is applied anywhere: a pulse with sum g^2 = U and a table of
+ * unit power give unit signal power, SNR = 1 / sigma^2.  THE LOGARITHM is the device library's float32 logf and the noise is held
+ * to a derived bound (tests/synth_ref.py), every integer above exactly.  sigma is read on the device, where the host cannot see
+ * it: a NaN or negative sigma is not refused, it propagates into the row.
+ *
+ * POSITION INDEPENDENCE.  The bits of out[f, i] depend on the seed, r, n, the row parameters, the taps, the table and sigma_g,
+ * and not on the call's cut, the tile, the grid, the lane, row_stride or n_rows: a data set made in any number of calls over
+ * rows, or a stream made in chunks of any length, odd lengths included, equals one call bit for bit.
+ *
+ *   - limits: 0 <= order <= 256, 1 <= up <= 256, 1 <= down <= 4096, 1 <= n_taps <= 4096; 0 <= tau0 < up, no flag but the two;
+ *     1 <= row_samples, 0 <= sample_index0, sample_index0 + row_samples < 2^40; 0 <= n_rows, row_stride >= row_samples,
+ *     n_rows * row_stride <= 2^58; frames_per_group >= 1; every sigma read a finite float32 >= 0 (not checked, see above)
+ *   - checks, in the order of every launching entry: the limits in that order; n_rows == 0 is AMCX_OK here and writes nothing;
+ *     then null pointers (the table only where order > 0), alignment (out 8; taps, table and sigma 4) and a pointer on another
+ *     device.  Ordinary vector stores only.
+ * amcx_synth_plan (host-only): samples per tile, bytes of LDS and the most workgroups of the persistent grid for a shape; each
+ * pointer may be NULL.  amcx_kernel_name_synth (host-only): the kernel's name, a static string.
+ */
+#define AMCX_SYNTH_RANDOM_PHASE 1u
+#define AMCX_SYNTH_RANDOM_TIMING 2u
+int amcx_synth_plan(int32_t order, int32_t n_taps, int32_t up, int32_t down, int32_t* tile_outputs, int32_t* lds_bytes,
+                    int32_t* max_workgroups);
+int amcx_synth_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, int64_t n_rows, int64_t row_samples,
+                   int64_t row_stride, const void* table_c64_dev, int32_t order, const float* taps_dev, int32_t n_taps, int32_t up,
+                   int32_t down, int32_t tau0, uint64_t phase_step, uint32_t cfo_max, uint32_t flags, const float* sigma_dev,
+                   int64_t frames_per_group, void* out_c64_dev, void* hip_stream);
+const char* amcx_kernel_name_synth(void);
 
 #ifdef __cplusplus
 }
