@@ -1134,7 +1134,7 @@ int64_t amcx_resample_out_samples(int64_t n_samples, int32_t n_taps, int32_t int
     return -1;
   if (phase_index0 < 0 || phase_index0 >= interp) return -1;
   if (n_samples < 0 || n_samples >= (int64_t(1) << 40)) return -1;
-  const int64_t P = amcx::rs_phase_taps(n_taps, interp);
+  const int64_t P = amcx::poly_phase_taps(n_taps, interp);
   if (n_samples < P) return 0;
   const int64_t last = (n_samples - P + 1) * interp - 1 - phase_index0;      // the largest t with n(t) <= n_samples - 1, less tau0
   return last < 0 ? 0 : last / decim + 1;
@@ -1165,7 +1165,7 @@ int amcx_resample(const void* src_dev, int32_t src_kind, int64_t n_samples, floa
   const hipError_t e = amcx::launch(rs_kernel(src).kern, grid, amcx::kRsThreads, amcx::rs_lds_bytes(n_taps, interp, decim),
                                     static_cast<hipStream_t>(hip_stream), static_cast<const char*>(src_dev), src.kernel_scale(scale),
                                     src.flip4(), (unsigned long long)phase0, (unsigned long long)phase_step, taps_dev, n_taps, interp,
-                                    decim, phase_index0, amcx::rs_phase_taps(n_taps, interp),
+                                    decim, phase_index0, amcx::poly_phase_taps(n_taps, interp),
                                     amcx::rs_max_span(n_taps, interp, decim), static_cast<float2*>(out_c64_dev), (long long)M,
                                     tile, (long long)n_tiles);
   if (e != hipSuccess) return hip_fail(e, "resampler kernel launch");
@@ -1678,7 +1678,7 @@ int amcx_synth_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, in
   a.T = n_taps;
   a.U = up;
   a.V = down;
-  a.P = amcx::syn_phase_taps(n_taps, up);
+  a.P = amcx::poly_phase_taps(n_taps, up);
   a.tau0 = tau0;
   a.max_span = amcx::syn_max_span(n_taps, up, down);
   a.phase_step = phase_step;

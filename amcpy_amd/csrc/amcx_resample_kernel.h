@@ -1,6 +1,7 @@
 // The rational resampler (include/amcx.h, amcx_resample; ABI 13): mixer, polyphase real FIR, rate change by L / D, from one
 // contiguous stream of complex64 / sc16 / ci8 / cu8 samples to packed complex64.  A sibling of the down-converter
-// (amcx_ddc_kernel.h): its mixer (ddc_mix), its loaders (Ddc*) and its staging routine (ddc_stage_span) are CALLED here.
+// (amcx_ddc_kernel.h): its mixer (ddc_mix), its loaders (Ddc*) and its staging routine (ddc_stage_span) are CALLED here, and
+// so are the tap image, the sum and the plan arithmetic it shares with the waveform generator (amcx_polyphase.h: poly_*).
 //
 //   phi(n) = phase0 + n * phase_step                  (uint64, exact; n counts the call's input samples)
 //   v[n]   = x[n] * exp(+2 pi j phi(n) / 2^64)
@@ -38,13 +39,14 @@
 //
 // KERNEL ORDER (amcx_launch.h): plain kernels in the header amcx.hip includes FIRST; this header includes the down-converter's,
 // whose kernels therefore still come first of all and keep their bytes, as does every other kernel: tools/codeobj_gate.py
-// --kernels, profiles/r17_resample_codeobj_kernels.txt.
+// --kernels, profiles/r17_resample_codeobj_kernels.txt.  amcx_polyphase.h, included behind it, holds no kernel: nothing moves.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "amcx_ddc_kernel.h"
+#include "amcx_polyphase.h"
 
 namespace amcx {
 
@@ -57,21 +59,10 @@ constexpr int kRsMaxTile = 4096;           // most outputs of one tile: 16 per t
 
 static_assert(kRsMaxTaps <= kRsStage, "one output's window (L = 1) must fit the stage");
 
-inline int rs_phase_taps(int T, int L) { return (T + L - 1) / L; }                       // P
-__host__ __device__ __forceinline__ int rs_pitch(int P) { return P | 1; }
-// outputs per tile: the worst span, floor(((tile - 1) D + L - 1) / L) + P at r0 = L - 1, fits kRsStage; at least one
-inline int rs_tile_outputs(int T, int L, int D) {
-  const long long fit = (long long)(kRsStage - rs_phase_taps(T, L)) * L / D + 1;
-  return fit > kRsMaxTile ? kRsMaxTile : (int)fit;
-}
-// most samples any tile stages
-inline int rs_max_span(int T, int L, int D) {
-  return (int)(((long long)(rs_tile_outputs(T, L, D) - 1) * D + L - 1) / L) + rs_phase_taps(T, L);
-}
-// dynamic LDS of a launch: the padded image of the worst span, then the phase-major taps.  L pitch <= T + 2 L <= 4608 floats.
-inline size_t rs_lds_bytes(int T, int L, int D) {
-  return (size_t)ddc_stage_bytes(rs_max_span(T, L, D)) + (size_t)4 * (size_t)L * (size_t)rs_pitch(rs_phase_taps(T, L));
-}
+inline int rs_tile_outputs(int T, int L, int D) { return poly_tile_outputs(T, L, D, kRsStage, kRsMaxTile); }   // the plan: amcx_polyphase.h
+inline int rs_max_span(int T, int L, int D) { return poly_max_span(T, L, D, rs_tile_outputs(T, L, D)); }      // most samples any tile stages
+// dynamic LDS of a launch: the padded image of the worst span, then the phase-major taps
+inline size_t rs_lds_bytes(int T, int L, int D) { return (size_t)ddc_stage_bytes(rs_max_span(T, L, D)) + poly_taps_bytes(T, L); }
 
 // Reads src[0 .. n_{M-1}] samples and taps[0 .. T), writes out[0 .. M), nothing else.  P = ceil(T / L); max_span =
 // rs_max_span; n_tiles = ceil(M / tile); the dynamic LDS is rs_lds_bytes(T, L, D).
@@ -84,11 +75,8 @@ __device__ __forceinline__ void rs_body(const char* __restrict__ src, float scal
   float2* const stage = reinterpret_cast<float2*>(rs_lds);
   float* const g = reinterpret_cast<float*>(rs_lds + ddc_stage_bytes(max_span));
   const int tid = (int)threadIdx.x;
-  const int pitch = rs_pitch(P);
-  for (int k = tid; k < T; k += kRsThreads) {                          // (the first tile's barrier orders these too)
-    const int q = (int)((unsigned)k / (unsigned)L);
-    g[(k - q * L) * pitch + q] = taps[k];
-  }
+  const int pitch = poly_pitch(P);
+  poly_stage_taps(g, taps, T, L, pitch, tid, kRsThreads);             // (the first tile's barrier orders these too)
   const int full = T - (P - 1) * L;                                    // phases p < full have P taps, the others P - 1
   const unsigned stride = (unsigned)kRsThreads * (unsigned)D;          // a thread's step of u, as quotient and remainder
   const int step_q = (int)(stride / (unsigned)L), step_r = (int)(stride - (unsigned)step_q * (unsigned)L);
@@ -110,17 +98,7 @@ __device__ __forceinline__ void rs_body(const char* __restrict__ src, float scal
       if (cnt > 0) {
         const int top = off + P - 1;                                   // the sample tap p multiplies
         const float* const gp = g + p * pitch;
-        const float2 v0 = stage[ddc_pad(top)];
-        const float h0 = gp[0];
-        re = h0 * v0.x;
-        im = h0 * v0.y;
-#pragma unroll 4
-        for (int q = 1; q < cnt; ++q) {
-          const float2 v = stage[ddc_pad(top - q)];
-          const float hq = gp[q];
-          re = __builtin_fmaf(hq, v.x, re);
-          im = __builtin_fmaf(hq, v.y, im);
-        }
+        poly_taps_sum(stage, gp, top, cnt, re, im);
       }
       out[m0 + o] = make_float2(re, im);
       off += step_q;

@@ -1,8 +1,8 @@
 // The waveform generator (include/amcx.h, amcx_synth_c64; ABI 16.2): rows of linearly modulated IQ -- Philox symbols, a pulse at
 // U / V samples per symbol, a carrier, white Gaussian noise -- written as packed complex64 in one launch.  A sibling of the
-// resampler (amcx_resample_kernel.h): its sum is the resampler's with L = U, D = V on a stream of symbols that is drawn, not read;
-// the down-converter's mixer (ddc_mix, ddc_mixer) and its padded LDS image are CALLED here, and so is the training kernels'
-// Philox4x32-10 (amcx_mlp_train_kernel.h).  r is the absolute row, n the absolute sample of the row:
+// resampler (amcx_resample_kernel.h): its sum is the resampler's with L = U, D = V on a stream of symbols that is drawn, not read,
+// and the resampler's CODE: both CALL the tap image, the sum and the plan arithmetic of amcx_polyphase.h (poly_*).  The down-converter's mixer (ddc_mix,
+// ddc_mixer) and its padded LDS image are CALLED too, and the training kernels' Philox4x32-10 (amcx_mlp_train_kernel.h).  r is the absolute row, n the absolute sample of the row:
 //
 //   counter(s, j, r) = (j & 0xFFFFFFFF, (s << 28) | (j >> 32), r low, r high)    s = 0 row, 1 symbols, 2 noise; key = the seed's words
 //   W        = Philox(counter(0, 0, r))
@@ -26,7 +26,7 @@
 // POSITION INDEPENDENCE.  Nothing above depends on the call's cut, the tile, the grid, the lane, row_stride or n_rows.
 //
 // THE LAUNCH.  256 threads, a persistent grid over (row, tile) pairs, a tile being `tile` consecutive samples of one row
-// (syn_tile_outputs).  A workgroup puts the taps (phase-major, pitch P | 1, as rs_body does) and the table into LDS once, barrier.  Per
+// (syn_tile_outputs).  A workgroup puts the taps (phase-major, pitch P | 1: poly_stage_taps, as rs_body does) and the table into LDS once, barrier.  Per
 // tile it draws the span's symbols -- thread t the Philox blocks t, t + 256, ... of four symbols -- into the padded image,
 // barrier, then a thread takes sample PAIRS (2 i, 2 i + 1), i counted on the absolute sample index, so that one noise block
 // serves both; it steps (quotient, remainder) of t_n / U with a carry as the resampler does, one division per thread and tile.
@@ -37,6 +37,7 @@
 //
 // KERNEL ORDER (amcx_launch.h): one plain kernel in the header amcx.hip includes FIRST; it includes the training kernels' header
 // and the down-converter's in front of its own kernel: tools/codeobj_gate.py --kernels, profiles/r28_synth_codeobj_kernels.txt.
+// amcx_polyphase.h, behind them, holds no kernel and moves nothing; including the resampler's header here would lay its kernels out in front of this one.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -44,6 +45,7 @@
 
 #include "amcx_mlp_train_kernel.h"
 #include "amcx_ddc_kernel.h"
+#include "amcx_polyphase.h"
 
 namespace amcx {
 
@@ -58,23 +60,14 @@ constexpr unsigned kSynRandomPhase = 1u, kSynRandomTiming = 2u;      // AMCX_SYN
 
 static_assert(kSynMaxTaps <= kSynStage, "one sample's window (U = 1) must fit the stage");
 
-inline int syn_phase_taps(int T, int U) { return (T + U - 1) / U; }                      // P
-__host__ __device__ __forceinline__ int syn_pitch(int P) { return P | 1; }
-// samples per tile: the worst span, floor(((tile - 1) V + U - 1) / U) + P at remainder U - 1, fits kSynStage; at least one, and
-// even where it is more than one (whole pairs)
+// the plan (amcx_polyphase.h) at this kernel's stage and largest tile; a tile of more than one sample is even (whole pairs)
 inline int syn_tile_outputs(int T, int U, int V) {
-  const long long fit = (long long)(kSynStage - syn_phase_taps(T, U)) * U / V + 1;
-  const int tile = fit > kSynMaxTile ? kSynMaxTile : (int)fit;
+  const int tile = poly_tile_outputs(T, U, V, kSynStage, kSynMaxTile);
   return tile > 1 ? tile & ~1 : tile;
 }
-inline int syn_max_span(int T, int U, int V) {
-  return (int)(((long long)(syn_tile_outputs(T, U, V) - 1) * V + U - 1) / U) + syn_phase_taps(T, U);
-}
-// dynamic LDS of a launch.  U pitch <= T + 2 U <= 4608 floats.
-inline size_t syn_lds_bytes(int T, int U, int V, int order) {
-  return (size_t)ddc_stage_bytes(syn_max_span(T, U, V)) + (size_t)4 * (size_t)U * (size_t)syn_pitch(syn_phase_taps(T, U)) +
-         (size_t)8 * (size_t)order;
-}
+inline int syn_max_span(int T, int U, int V) { return poly_max_span(T, U, V, syn_tile_outputs(T, U, V)); }
+// dynamic LDS of a launch: the padded image of the worst span, the phase-major taps, the table
+inline size_t syn_lds_bytes(int T, int U, int V, int order) { return (size_t)ddc_stage_bytes(syn_max_span(T, U, V)) + poly_taps_bytes(T, U) + 8u * (size_t)order; }
 
 struct SynArgs {
   unsigned seed_lo, seed_hi;
@@ -93,25 +86,11 @@ struct SynArgs {
   long long tiles_per_row, n_items;
 };
 
-// s[n] of the sample whose window tops at stage index `top` = off + P - 1 with phase p: rs_body's sum, the same order
+// s[n] of the sample whose window tops at stage index off + P - 1 with phase p: the resampler's sum (poly_taps_sum)
 __device__ __forceinline__ float2 syn_pulse(const float2* stage, const float* g, int pitch, int P, int full, int off, int p) {
   const int cnt = P - (p >= full ? 1 : 0);                             // taps of phase p (0: T < U, a phase with none)
   float re = 0.0f, im = 0.0f;
-  if (cnt > 0) {
-    const int top = off + P - 1;
-    const float* const gp = g + p * pitch;
-    const float2 v0 = stage[ddc_pad(top)];
-    const float h0 = gp[0];
-    re = h0 * v0.x;
-    im = h0 * v0.y;
-#pragma unroll 4
-    for (int q = 1; q < cnt; ++q) {
-      const float2 v = stage[ddc_pad(top - q)];
-      const float hq = gp[q];
-      re = __builtin_fmaf(hq, v.x, re);
-      im = __builtin_fmaf(hq, v.y, im);
-    }
-  }
+  if (cnt > 0) poly_taps_sum(stage, g + p * pitch, off + P - 1, cnt, re, im);
   return make_float2(re, im);
 }
 
@@ -131,12 +110,9 @@ __global__ __launch_bounds__(kSynThreads) void amcx_synth_c64_kernel(SynArgs a) 
   float* const g = reinterpret_cast<float*>(syn_lds + ddc_stage_bytes(a.max_span));
   const int tid = (int)threadIdx.x;
   const int T = a.T, U = a.U, V = a.V, P = a.P;
-  const int pitch = syn_pitch(P);
+  const int pitch = poly_pitch(P);
   float* const tabf = g + U * pitch;                                   // the table as floats: U pitch may be odd, 4-byte alignment
-  for (int k = tid; k < T; k += kSynThreads) {
-    const int q = (int)((unsigned)k / (unsigned)U);
-    g[(k - q * U) * pitch + q] = a.taps[k];
-  }
+  poly_stage_taps(g, a.taps, T, U, pitch, tid, kSynThreads);
   for (int k = tid; k < 2 * a.order; k += kSynThreads) tabf[k] = reinterpret_cast<const float*>(a.table)[k];
   __syncthreads();                                                     // the first tile's DRAW reads the table other threads stored
   const int full = T - (P - 1) * U;                                    // phases p < full have P taps, the others P - 1

@@ -65,6 +65,16 @@ def check_bn_mask(widths, bn_mask: int) -> int:
     return bn_mask
 
 
+def layout(widths, bn_mask: int, optimizer: str) -> dict:
+    """The sizes of a state block (include/amcx.h): ``n_params`` packed parameters, ``n_affine`` gammas and betas (as many running
+    statistics), ``n_train`` = both; ``n_slots`` optimizer slots of ``n_train`` values each; ``state_floats`` in all."""
+    widths = check_widths(widths)
+    n_params = params_floats(widths)
+    n_affine = sum(2 * widths[l + 1] for l in range(len(widths) - 2) if (bn_mask >> l) & 1)
+    n_train, n_slots = n_params + n_affine, 2 if check_optimizer(optimizer) == "adam" else 1
+    return dict(n_params=n_params, n_affine=n_affine, n_train=n_train, n_slots=n_slots, state_floats=n_train * (1 + n_slots) + n_affine)
+
+
 class TrainState:
     """``n_models`` models of one shape as ``amcx_mlp_train_f32`` takes them: ``block`` float32 ``(n_models, state_floats)`` in the
     header's layout -- the packed parameters ``[0, P)``, gamma and beta of every BatchNorm ``[P, T)``, running mean and variance
@@ -74,12 +84,8 @@ class TrainState:
         self.widths = check_widths(widths)
         self.bn_mask = check_bn_mask(self.widths, bn_mask)
         self.optimizer = check_optimizer(optimizer)
-        self.n_params = params_floats(self.widths)
         self.bn_layers = [l for l in range(len(self.widths) - 2) if (self.bn_mask >> l) & 1]
-        self.n_affine = sum(2 * self.widths[l + 1] for l in self.bn_layers)
-        self.n_train = self.n_params + self.n_affine
-        self.n_slots = 2 if optimizer == "adam" else 1
-        self.state_floats = self.n_train * (1 + self.n_slots) + self.n_affine
+        vars(self).update(layout(self.widths, self.bn_mask, self.optimizer))      # n_params, n_affine, n_train, n_slots, state_floats
         self.block = np.ascontiguousarray(block, dtype=np.float32).reshape(-1, self.state_floats)
         self.steps = np.ascontiguousarray(steps, dtype=np.int64).reshape(-1)
         if self.steps.shape[0] != self.block.shape[0] or not self.block.shape[0]:
@@ -114,7 +120,7 @@ class TrainState:
         ``BatchNorm1d`` (gamma 1, beta 0, running mean 0, running variance 1), drawn from a CPU generator seeded with it."""
         import torch
         seeds = [int(s) for s in seeds]
-        st = cls(widths, bn_mask, optimizer, np.zeros((len(seeds), _floats(widths, bn_mask, optimizer)), np.float32),
+        st = cls(widths, bn_mask, optimizer, np.zeros((len(seeds), layout(widths, bn_mask, optimizer)["state_floats"]), np.float32),
                  np.zeros(len(seeds), np.int64))
         for m, seed in enumerate(seeds):
             g = torch.Generator(device="cpu").manual_seed(seed)
@@ -144,7 +150,7 @@ class TrainState:
         norms = sorted(int(_KEY.match(k).group(1)) for k in first if k.endswith("running_mean"))
         widths = [first[f"layers.{lin[0]}.weight"].shape[1]] + [first[f"layers.{i}.weight"].shape[0] for i in lin]
         bn_mask = sum(1 << l for l, i in enumerate(lin) if i + 1 in norms)
-        st = cls(widths, bn_mask, optimizer, np.zeros((len(sds), _floats(widths, bn_mask, optimizer)), np.float32), np.zeros(len(sds), np.int64))
+        st = cls(widths, bn_mask, optimizer, np.zeros((len(sds), layout(widths, bn_mask, optimizer)["state_floats"]), np.float32), np.zeros(len(sds), np.int64))
         for m, sd in enumerate(sds):
             sd = {str(k): _array(v) for k, v in sd.items()}
             views = st.views(m)
@@ -172,12 +178,6 @@ class TrainState:
         """The :class:`amcpy_amd.classifier.MlpModel` of model m: every BatchNorm folded with its running statistics."""
         from .classifier import MlpModel
         return MlpModel.from_state_dict(self.to_state_dict(m), activation, model_id)
-
-
-def _floats(widths, bn_mask: int, optimizer: str) -> int:
-    widths = check_widths(widths)
-    t = params_floats(widths) + sum(2 * widths[l + 1] for l in range(len(widths) - 2) if (bn_mask >> l) & 1)
-    return t * (3 if check_optimizer(optimizer) == "adam" else 2) + (t - params_floats(widths))
 
 
 def state_floats(widths, bn_mask: int, optimizer: str) -> int:

@@ -29,6 +29,7 @@ from . import _lib, _stream, synth
 MAX_TAPS, MAX_UP, MAX_DOWN, MAX_ORDER = 4096, 256, 4096, 256
 _MASK64 = (1 << 64) - 1
 FRAME_BITS, SNR_BITS = 32, 16          # dataset's rows: (modulation code << 48) | (SNR code << 32) | frame
+_tensor = lambda t: hasattr(t, "data_ptr")                                 # noqa: E731  (a torch tensor, without importing torch)
 
 
 def design_rect(U: int) -> np.ndarray:
@@ -99,11 +100,42 @@ def _sigmas(mod, snr_db, sigma):
     return s
 
 
-def _shape(sps, taps):
+def _shape(sps):
     U, V = (int(sps), 1) if isinstance(sps, (int, np.integer)) else (int(sps[0]), int(sps[1]))
     if not (1 <= U <= MAX_UP and 1 <= V <= MAX_DOWN):
         raise ValueError(f"sps: U / V = {U} / {V} is outside 1 ... {MAX_UP} / 1 ... {MAX_DOWN}")
     return U, V
+
+
+def _device(device):
+    import torch
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def _operands(mod, taps, U, snr_db=None, sigma=None, device=None) -> tuple:
+    """``(table, taps, sigmas)`` as the entry reads them.  On the host: a modulation's name becomes its table, no taps the
+    rectangular pulse, ``snr_db`` the sigmas, all as contiguous complex64 / float32 arrays; a tensor is left as it is.  With a
+    ``device``, on it: what is on the host is uploaded, a tensor is taken as it is (and must be what the kernel reads)."""
+    table = mod
+    if not _tensor(mod):
+        table = constellation_table(mod) if isinstance(mod, str) else np.ascontiguousarray(np.asarray(mod, dtype=np.complex64)).reshape(-1)
+    if not _tensor(taps):
+        taps = design_rect(U) if taps is None else np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
+    if _tensor(sigma) and snr_db is not None:
+        raise ValueError("either snr_db or sigma")
+    sig = sigma if _tensor(sigma) else _sigmas(mod, snr_db, sigma)          # on the device its values are the caller's (a NaN propagates)
+    if device is None:
+        return table, taps, sig
+    import torch
+
+    def resident(t, dtype, name):
+        if not isinstance(t, torch.Tensor):
+            return torch.from_numpy(t).to(device)
+        if t.dtype != dtype or t.device != device or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous one-dimensional {str(dtype).replace('torch.', '')} tensor on the output's device")
+        return t
+
+    return resident(table, torch.complex64, "the table"), resident(taps, torch.float32, "taps"), resident(sig, torch.float32, "sigma")
 
 
 def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_db=None, sigma=None, frames_per_group=None,
@@ -127,23 +159,11 @@ def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_d
     out     : a complex64 tensor ``(n_rows, row_samples)`` to write, possibly a strided view with contiguous rows.
     compute : tests only -- ``f(table, taps, U, V, n_rows, row_samples, sigma, frames_per_group, seed=..., row_index0=...,
               sample_index0=..., phase_step=..., cfo_max=..., flags=..., tau0=...)`` over numpy (tests/synth_ref.numpy_generate)."""
-    tensor = lambda t: hasattr(t, "data_ptr")                              # noqa: E731  (a torch tensor, without importing torch)
-    if compute is not None and (tensor(mod) or tensor(taps) or tensor(sigma) or out is not None):
+    if compute is not None and (_tensor(mod) or _tensor(taps) or _tensor(sigma) or out is not None):
         raise TypeError("an injected compute takes host arrays and returns its own output")
-    U, V = _shape(sps, taps)
+    U, V = _shape(sps)
     R, S = int(n_rows), int(row_samples)
-    if tensor(mod):
-        table = mod
-    else:
-        table = constellation_table(mod) if isinstance(mod, str) else np.ascontiguousarray(np.asarray(mod, dtype=np.complex64)).reshape(-1)
-    if not tensor(taps):
-        taps = design_rect(U) if taps is None else np.ascontiguousarray(np.asarray(taps, dtype=np.float32))
-    if tensor(sigma):
-        if snr_db is not None:
-            raise ValueError("either snr_db or sigma")
-        sig = sigma                                                        # on the device: its values are the caller's (a NaN propagates)
-    else:
-        sig = _sigmas(mod, snr_db, sigma)
+    table, taps, sig = _operands(mod, taps, U, snr_db, sigma)
     order, T, G = (int(t.shape[0]) if t.ndim == 1 else -1 for t in (table, taps, sig))
     if R < 0 or S < 1 or not 0 <= int(sample_index0) or int(sample_index0) + S >= 1 << 40 or not 0 <= order <= MAX_ORDER \
             or not 1 <= T <= MAX_TAPS or G < 1:
@@ -169,18 +189,9 @@ def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_d
             raise ValueError(f"out has {int(out.shape[0])} rows, the call makes {R}")
         dev = out.device
     else:
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        dev = _device(device)
         stride = S
-
-    def resident(t, dtype, name):
-        """``t`` on the device: a host array is uploaded, a tensor is taken as it is (and must be what the kernel reads)"""
-        if not isinstance(t, torch.Tensor):
-            return torch.from_numpy(t).to(dev)
-        if t.dtype != dtype or t.device != dev or not t.is_contiguous():
-            raise TypeError(f"{name} must be a contiguous one-dimensional {str(dtype).replace('torch.', '')} tensor on the output's device")
-        return t
-
-    table, taps, sig = resident(table, torch.complex64, "the table"), resident(taps, torch.float32, "taps"), resident(sig, torch.float32, "sigma")
+    table, taps, sig = _operands(table, taps, U, sigma=sig, device=dev)
     if out is None:
         out = torch.empty((R, S), dtype=torch.complex64, device=dev)
     _stream.launch(out, lambda lib, stream: lib.amcx_synth_c64(
@@ -230,18 +241,33 @@ def _grid(mods, snr_db) -> tuple:
     return mods, snrs
 
 
-def _resident_pulse(mod, snrs, kw) -> dict:
-    """``kw`` of :func:`generate` with a modulation's table, the taps and the grid's sigmas uploaded ONCE (GPU path only)."""
+def _walk(mods, snrs, F, N, chunk, first_frame, kw, shape, view, each=None) -> dict:
+    """The one walk of a data set -> mod -> its buffer of ``shape``.  Per modulation the operands go to the device ONCE; then per SNR
+    and chunk of at most ``chunk`` of the F frames (None: all, even none, at once) ONE launch makes the frames ``first_frame + f0 ...``
+    into ``view(buf, s, n)`` and ``each(mod, s, f0, frames)`` sees them.  An injected ``compute`` walks the same way over numpy."""
+    U, _ = _shape(kw.get("sps", (8, 1)))
+    dev = _device(kw.get("device")) if kw.get("compute") is None else None
+    data = {}
+    for mod in mods:
+        table, taps, sig = _operands(mod, kw.get("taps"), U, snr_db=snrs, device=dev)
+        buf = data[mod] = _empty(shape, dev)
+        for s, snr in enumerate(snrs):
+            for f0 in (range(0, F, chunk) if chunk else (0,)):
+                dst = view(buf, s, min(chunk or F, F - f0))
+                x = generate(table, dst.shape[0], N, sigma=sig[s:s + 1], row_index0=dataset_row(mod, snr, first_frame + f0),
+                             **dict(kw, taps=taps, device=dev, out=None if dev is None else dst))
+                if dev is None:
+                    dst[...] = x
+                if each is not None:
+                    each(mod, s, f0, dst)
+    return data
+
+
+def _empty(shape, device):
+    if device is None:
+        return np.empty(shape, np.complex64)
     import torch
-    dev = kw.get("device")
-    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev)
-    U, _ = _shape(kw.get("sps", (8, 1)), None)
-    taps = kw.get("taps")
-    if not isinstance(taps, torch.Tensor):
-        taps = torch.from_numpy(design_rect(U) if taps is None else np.ascontiguousarray(np.asarray(taps, dtype=np.float32))).to(dev)
-    table = torch.from_numpy(constellation_table(mod)).to(dev)
-    sig = torch.from_numpy(_sigmas(mod, snrs, None)).to(dev)
-    return dict(kw, taps=taps, device=dev), table, sig
+    return torch.empty(shape, dtype=torch.complex64, device=device)
 
 
 def dataset(mods, snr_db, n_frames: int, frame_size: int, *, first_frame: int = 0, **kw) -> dict:
@@ -250,21 +276,8 @@ def dataset(mods, snr_db, n_frames: int, frame_size: int, *, first_frame: int = 
     which makes it one launch per (modulation, SNR), each into its slice of the modulation's array.  The table, the taps and
     the sigmas go to the device once per modulation; the launches upload nothing."""
     mods, snrs = _grid(mods, snr_db)
-    compute = kw.get("compute")
-    data = {}
-    for mod in mods:
-        if compute is None:
-            import torch
-            kw_dev, table, sig = _resident_pulse(mod, snrs, kw)
-            arr = torch.empty((len(snrs), int(n_frames), int(frame_size)), dtype=torch.complex64, device=kw_dev["device"])
-            for s, snr in enumerate(snrs):
-                generate(table, n_frames, frame_size, sigma=sig[s:s + 1], row_index0=dataset_row(mod, snr, first_frame), out=arr[s], **kw_dev)
-        else:
-            arr = np.empty((len(snrs), int(n_frames), int(frame_size)), np.complex64)
-            for s, snr in enumerate(snrs):
-                arr[s] = generate(mod, n_frames, frame_size, snr_db=snr, row_index0=dataset_row(mod, snr, first_frame), **kw)
-        data[mod] = arr
-    return data
+    F, N = int(n_frames), int(frame_size)
+    return _walk(mods, snrs, F, N, None, first_frame, kw, (len(snrs), F, N), lambda buf, s, n: buf[s])
 
 
 def dataset_features(mods, snr_db, n_frames: int, frame_size: int, *, chunk_frames: int = 1 << 14, features=None, **kw) -> dict:
@@ -272,62 +285,43 @@ def dataset_features(mods, snr_db, n_frames: int, frame_size: int, *, chunk_fram
     through :func:`amcpy_amd.features.features18` and dropped, so a training set larger than the device's memory never exists
     as IQ.  ``features``: tests only, ``f(frames (F, N) complex64 numpy) -> (F, 18)`` beside an injected ``compute``."""
     mods, snrs = _grid(mods, snr_db)
-    F, chunk = int(n_frames), max(1, int(chunk_frames))
-    on_gpu = kw.get("compute") is None
+    F, N, chunk = int(n_frames), int(frame_size), max(1, int(chunk_frames))
     if features is None:
         from .features import features18
         features = lambda x: features18(x).cpu().numpy()           # noqa: E731
-    out = {}
-    for mod in mods:
-        feats = np.empty((len(snrs), F, _lib.NUM_FEATURES), np.float32)
-        if on_gpu:
-            import torch
-            kw_dev, table, sig = _resident_pulse(mod, snrs, kw)
-            buf = torch.empty((min(chunk, F), int(frame_size)), dtype=torch.complex64, device=kw_dev["device"])
-        for s, snr in enumerate(snrs):
-            for f0 in range(0, F, chunk):
-                n = min(chunk, F - f0)
-                if on_gpu:
-                    x = generate(table, n, frame_size, sigma=sig[s:s + 1], row_index0=dataset_row(mod, snr, f0), out=buf[:n], **kw_dev)
-                else:
-                    x = generate(mod, n, frame_size, snr_db=snr, row_index0=dataset_row(mod, snr, f0), **kw)
-                feats[s, f0:f0 + n] = np.asarray(features(x), dtype=np.float32)[:, :_lib.NUM_FEATURES]
-        out[mod] = feats
+    out = {mod: np.empty((len(snrs), F, _lib.NUM_FEATURES), np.float32) for mod in mods}
+
+    def keep(mod, s, f0, x):
+        out[mod][s, f0:f0 + x.shape[0]] = np.asarray(features(x), dtype=np.float32)[:, :_lib.NUM_FEATURES]
+    _walk(mods, snrs, F, N, chunk, 0, kw, (min(chunk, F), N), lambda buf, s, n: buf[:n], keep)
     return out
 
 
 class Stream:
     """One row as a stream: ``push(n)`` returns its next n samples (``index`` counts the samples made so far, as
     :class:`amcpy_amd._stream.Chunked` counts them).  Cut anywhere, the chunks equal one call bit for bit.  The keywords are
-    :func:`generate`'s; ``row`` is the absolute row."""
+    :func:`generate`'s; ``row`` is the absolute row.  The table, the taps and sigma go to the device once, with the first samples."""
 
     def __init__(self, mod, *, row: int = 0, **kw):
         for bad in ("row_index0", "sample_index0", "out", "frames_per_group"):
             if bad in kw:
                 raise ValueError(f"Stream: {bad} is the stream's own")
-        self.mod, self.row, self.index, self._kw = mod, int(row), 0, dict(kw)
-        if self._kw.get("taps") is not None and not hasattr(self._kw["taps"], "data_ptr"):
-            self._kw["taps"] = np.ascontiguousarray(np.asarray(self._kw["taps"], dtype=np.float32))
-        self._taps_dev = None
+        self.mod, self.row, self.index, self._kw, self._resident = mod, int(row), 0, dict(kw), None
 
     def push(self, n: int):
         n = int(n)
         if n < 0:
             raise ValueError("push: n >= 0")
-        kw = dict(self._kw)
+        mod, kw = self.mod, self._kw
+        dev = _device(kw.get("device")) if kw.get("compute") is None else None
         if n == 0:
-            if kw.get("compute") is not None:
-                return np.empty(0, np.complex64)
-            import torch
-            return torch.empty(0, dtype=torch.complex64, device=kw.get("device") or torch.device("cuda", torch.cuda.current_device()))
-        if kw.get("compute") is None and isinstance(kw.get("taps"), np.ndarray):       # the taps uploaded once
-            import torch
-            if self._taps_dev is None:
-                dev = kw.get("device")
-                self._taps_dev = torch.from_numpy(np.ascontiguousarray(kw["taps"])).to(
-                    torch.device("cuda", torch.cuda.current_device()) if dev is None else torch.device(dev))
-            kw["taps"] = self._taps_dev
-        y = generate(self.mod, 1, n, row_index0=self.row, sample_index0=self.index, **kw)
+            return _empty(0, dev)
+        if dev is not None:
+            if self._resident is None:
+                self._resident = _operands(mod, kw.get("taps"), _shape(kw.get("sps", (8, 1)))[0], kw.get("snr_db"), kw.get("sigma"), dev)
+            mod, taps, sig = self._resident
+            kw = dict(kw, taps=taps, sigma=sig, snr_db=None)
+        y = generate(mod, 1, n, row_index0=self.row, sample_index0=self.index, **kw)
         self.index += n
         return y[0]
 
@@ -350,12 +344,12 @@ def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device
 
     from .resample import design_resample_lowpass, out_samples, resample
     S = int(n_samples)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = _device(device)
     x = generate("WGN", 1, S, sigma=float(noise_sigma), seed=seed, row_index0=len(emitters), device=dev)[0]
     one = torch.ones(1, dtype=torch.float32, device=dev)
     annotations = []
     for e, em in enumerate(emitters):
-        U, V = _shape(em["sps"], None)
+        U, V = _shape(em["sps"])
         L, D = (int(v) for v in em.get("rate", (1, 1)))
         start = int(em.get("start", 0))
         length = int(em.get("length", S - start))
@@ -427,7 +421,7 @@ def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0
     snrs = [float(v) for v in sig.snr_values.values()] if snr is None else [float(v) for v in snr]
     if len(snrs) != len(sig.snr_values):
         raise ValueError(f"{len(snrs)} SNR values against the configuration's {len(sig.snr_values)} labels")
-    U, V = _shape(sps, None)
+    U, V = _shape(sps)
     if pulse not in ("rrc", "rect"):
         raise ValueError("pulse: rrc or rect")
     taps = design_rrc(U, span, beta) if pulse == "rrc" else design_rect(U)

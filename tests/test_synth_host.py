@@ -48,6 +48,20 @@ def test_synth_kernel_is_in_the_resource_table_without_spill_and_older_kernels_k
     assert re.findall(r"ONLY IN B\s+amcx::(.+)", listing) == ["amcx_synth_c64_kernel"]
 
 
+def test_sharing_the_polyphase_routines_left_every_kernel_its_bytes():
+    """amcx_polyphase.h (the tap image, the sum and the plan arithmetic the generator and the resampler now both call): the parent
+    commit's library against the tree's, per kernel."""
+    listing = (REPO / "profiles" / "r29_polyphase_codeobj_kernels.txt").read_text()
+    assert "101 kernels / device functions identical" in listing
+    assert "DIFFERENT" not in listing and "ONLY IN A" not in listing and "ONLY IN B" not in listing
+    csrc = REPO / "amcpy_amd" / "csrc"
+    assert "__global__" not in (csrc / "amcx_polyphase.h").read_text()
+    for header in ("amcx_synth_kernel.h", "amcx_resample_kernel.h"):
+        text = (csrc / header).read_text()
+        assert "poly_stage_taps(" in text and "poly_taps_sum(" in text and "__builtin_fmaf" not in text, header
+    assert '#include "amcx_resample_kernel.h"' not in (csrc / "amcx_synth_kernel.h").read_text()
+
+
 PLAN_SWEEP = [(1, 1, 1), (1, 256, 1), (4096, 1, 4096), (4096, 256, 1), (4095, 7, 4096), (4096, 1, 1), (8, 8, 1), (33, 2, 1),
               (129, 8, 3), (4096, 256, 255), (7, 3, 4096), (4096, 255, 256), (4081, 255, 1), (2, 3, 50)]
 
@@ -242,6 +256,66 @@ def test_generate_cut_in_rows_and_samples_equals_one_call_on_the_reference():
         wf.generate("QPSK", 3, 50, snr_db=[1.0, 2.0], frames_per_group=1, **kw)
     with pytest.raises(ValueError):
         wf.generate("QPSK", 1, 50, cfo=0.5, compute=ref.numpy_generate)
+
+
+# ---- one operand path, one walk: the data set, its features and the stream over the injected compute ---------------------------------
+WALK_MODS, WALK_SNRS, WALK_F, WALK_N = ["BPSK", "WGN"], [0.0, 10.0], 5, 64
+
+
+def walk_kw(compute=ref.numpy_generate):
+    return dict(sps=(2, 1), taps=wf.design_rrc(2, 4), seed=11, cfo=0.01, compute=compute)
+
+
+def sample_features(x):
+    """18 columns that tell frames and samples apart: the first nine samples of every frame, real parts then imaginary parts"""
+    x = np.asarray(x)
+    return np.concatenate([x[:, :9].real, x[:, :9].imag], axis=1).astype(np.float32)
+
+
+def test_dataset_features_in_chunks_are_the_features_of_the_dataset_s_frames():
+    data = wf.dataset(WALK_MODS, WALK_SNRS, WALK_F, WALK_N, **walk_kw())
+    feats = wf.dataset_features(WALK_MODS, WALK_SNRS, WALK_F, WALK_N, chunk_frames=2, features=sample_features, **walk_kw())
+    assert list(feats) == list(data) == WALK_MODS
+    for mod in WALK_MODS:
+        assert data[mod].shape == (2, WALK_F, WALK_N) and data[mod].dtype == np.complex64
+        want = np.stack([sample_features(data[mod][s]) for s in range(len(WALK_SNRS))])
+        assert feats[mod].dtype == np.float32 and feats[mod].shape == (2, WALK_F, 18) and feats[mod].tobytes() == want.tobytes()
+    assert data["BPSK"][0].tobytes() != data["BPSK"][1].tobytes() and np.abs(data["WGN"]).max() > 0
+    whole = wf.dataset_features(WALK_MODS, WALK_SNRS, WALK_F, WALK_N, features=sample_features, **walk_kw())
+    assert all(whole[mod].tobytes() == feats[mod].tobytes() for mod in WALK_MODS)
+
+
+def test_stream_in_chunks_equals_one_call():
+    for mod, noise in (("BPSK", dict(snr_db=10.0)), ("WGN", dict(snr_db=0.0)), ("BPSK", dict(sigma=0.25)), ("BPSK", {})):
+        whole = wf.generate(mod, 1, WALK_N, row_index0=7, **noise, **walk_kw())
+        s = wf.Stream(mod, row=7, **noise, **walk_kw())
+        chunks = [s.push(n) for n in (3, 0, 61)]
+        assert [c.shape for c in chunks] == [(3,), (0,), (61,)] and all(c.dtype == np.complex64 for c in chunks) and s.index == WALK_N
+        assert np.concatenate(chunks).tobytes() == whole[0].tobytes()
+
+
+def test_dataset_hands_the_compute_what_generate_by_name_hands_it():
+    """The table, the taps, the sigmas and frames_per_group (and every other argument) an injected compute receives from the
+    data set's walk, which passes the table and one resident sigma, against those of generate(mod, snr_db=snr) called directly."""
+    calls = []
+
+    def recording(table, taps, U, V, n_rows, row_samples, sigma, frames_per_group, **where):
+        calls.append((None if table is None else np.array(table), np.array(taps), (U, V, n_rows, row_samples), np.array(sigma),
+                      frames_per_group, dict(where)))
+        return ref.numpy_generate(table, taps, U, V, n_rows, row_samples, sigma, frames_per_group, **where)
+
+    wf.dataset(WALK_MODS, WALK_SNRS, WALK_F, WALK_N, first_frame=3, **walk_kw(recording))
+    walked, calls[:] = list(calls), []
+    for mod in WALK_MODS:
+        for snr in WALK_SNRS:
+            wf.generate(mod, WALK_F, WALK_N, snr_db=snr, row_index0=wf.dataset_row(mod, snr, 3), **walk_kw(recording))
+    assert len(walked) == len(calls) == len(WALK_MODS) * len(WALK_SNRS)                      # one call per (modulation, SNR)
+    for got, want in zip(walked, calls):
+        for g, w in zip(got[:2] + got[3:4], want[:2] + want[3:4]):                           # table, taps, sigma
+            assert (g is None and w is None) or (g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes())
+        assert got[2] == want[2] and got[4] == want[4] == WALK_F and got[5] == want[5]
+    assert walked[0][0].shape == (2,) and walked[2][0] is None and walked[2][3].tolist() == [1.0] and walked[3][3].tolist() == [1.0]
+    assert walked[1][3].tolist() == wf.sigma_of(10.0).tolist() and walked[0][5]["row_index0"] == wf.dataset_row("BPSK", 0.0, 3)
 
 
 # ---- the command -----------------------------------------------------------------------------------------------------------------

@@ -92,6 +92,19 @@ def test_state_block_layout_and_size_function():
     assert st.views(0, 1)["layers.0.weight"][0, 0] == P + 2 * A and st.views(0, 2)["layers.12.bias"][-1] == st.state_floats - A - 1
 
 
+def test_state_block_size_is_the_library_s_for_every_fixture_shape():
+    """TrainState's own layout arithmetic against amcx_mlp_train_state_floats, over every shape, mask and optimizer of the fixtures."""
+    shapes = {(tc.load(name)["widths"], tc.load(name)["bn_mask"], tc.load(name)["optimizer"]) for name in tc.CASES}
+    assert len({w for w, _, _ in shapes}) >= 6 and {o for _, _, o in shapes} == {"rmsprop", "adam"} and len({m for _, m, _ in shapes}) >= 2
+    for widths, bn_mask, optimizer in sorted(shapes):
+        want = train.state_floats(widths, bn_mask, optimizer)
+        for n_models in (1, 3):
+            st = train.TrainState(widths, bn_mask, optimizer, np.zeros(n_models * want, np.float32), np.zeros(n_models, np.int64))
+            assert st.state_floats == want == train.layout(widths, bn_mask, optimizer)["state_floats"] and st.block.shape == (n_models, want)
+            assert st.n_train == st.n_params + st.n_affine and st.n_slots == (2 if optimizer == "adam" else 1)
+        assert train.TrainState.init(widths, bn_mask, optimizer, [1, 2]).block.shape == (2, want)
+
+
 def test_state_dict_checkpoint_and_model_round_trip(tmp_path):
     case = tc.load("w_4_32_7_3")
     sd = tc.state_dict(case, "sd32:")
