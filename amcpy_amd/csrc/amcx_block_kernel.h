@@ -21,7 +21,7 @@
 // Algorithmic HBM bytes per frame: 8*N + 72.
 #pragma once
 
-#include "amcx_math.h"
+#include "amcx_exact_passes.h"
 
 namespace amcx {
 
@@ -29,12 +29,6 @@ constexpr int kBlockThreads = 256;
 constexpr int kBlockMaxN = 8192;                 // a staged frame + its (|x|, angle) stash: 16 N bytes of LDS; larger: amcx_stream_kernel.h
 constexpr int kBlockWaves = kBlockThreads / 64;
 constexpr int kMaxReduce = 16;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Sum K per-thread doubles over the workgroup; every thread gets the totals.
 template <int K>
@@ -57,24 +51,7 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double* scratch) {
   __syncthreads();
 }
 
-__device__ __forceinline__ float block_max(float v, double* scratch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // NaN must survive the reduction: fmaxf drops it, so carry a flag
-  float bad = (v == v) ? 0.f : 1.f;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    v = __builtin_fmaxf(v, __shfl_xor(v, off, 64));
-    bad = __builtin_fmaxf(bad, __shfl_xor(bad, off, 64));
-  }
-  float* s = reinterpret_cast<float*>(scratch);
-  if (lane == 0) { s[wave * 2] = v; s[wave * 2 + 1] = bad; }
-  __syncthreads();
-  float m = s[0], b = s[1];
-#pragma unroll
-  for (int w = 1; w < kBlockWaves; ++w) { m = __builtin_fmaxf(m, s[w * 2]); b = __builtin_fmaxf(b, s[w * 2 + 1]); }
-  __syncthreads();
-  return b > 0.f ? __builtin_nanf("") : m;
-}
+__device__ __forceinline__ float block_max(float v, double* scratch) { return workgroup_max<kBlockWaves>(v, scratch); }
 
 constexpr int kBlockDirect = 0, kBlockPow2 = 1, kBlockBluestein = 2, kBlockBluesteinBig = 3;   // spectral-term variants
 constexpr int kBluesteinMinN = 65, kBluesteinMaxN = 4096;
@@ -86,19 +63,8 @@ constexpr int kBluesteinBigM = 16384, kBluesteinBigPerThread = kBluesteinBigM / 
 constexpr int kBlockScratchBytes = (int)sizeof(double) * kBlockWaves * kMaxReduce;   // 512
 constexpr int kBlockTwiddleBytes = (64 + 128) * 8;                                    // T_lo[64], T_hi[128]: exponents < 8192
 
-__host__ __device__ inline int bluestein_length(int n) {          // smallest power of two >= 2n - 1
-  int m = 1;
-  while (m < 2 * n - 1) m <<= 1;
-  return m;
-}
-
-// W_M^m = exp(-2 pi i m / M), m < M/2, from two small tables: T_hi[m >> 6] * T_lo[m & 63] (T_hi: up to 128 entries)
-__device__ __forceinline__ float2 twiddle2(const float2* tlo, const float2* thi, int m) {
-  const float2 a = thi[m >> 6], b = tlo[m & 63];
-  return make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x));
-}
-
 // In-place M-point FFTs over an LDS array by the whole workgroup (trailing barrier included).
+// The twiddles W_M^m = exp(-2 pi i m / M), m < M/2, come from the two-level tables (thi: up to 128 entries).
 // Forward: decimation in frequency, natural order in, bit-reversed order out.
 __device__ __forceinline__ void lds_fft_dif(float2* v, int M, const float2* tlo, const float2* thi) {
   const int half_m = M >> 1;
@@ -107,10 +73,7 @@ __device__ __forceinline__ void lds_fft_dif(float2* v, int M, const float2* tlo,
       const int j = b & (half - 1);
       const int i0 = ((b - j) << 1) + j, i1 = i0 + half;
       const float2 p = v[i0], q = v[i1];
-      const float2 w = twiddle2(tlo, thi, j * step);
-      const float dr = p.x - q.x, di = p.y - q.y;
-      v[i0] = make_float2(p.x + q.x, p.y + q.y);
-      v[i1] = make_float2(__builtin_fmaf(dr, w.x, -(di * w.y)), __builtin_fmaf(dr, w.y, di * w.x));
+      butterfly_dif(p, q, twiddle(thi, tlo, j * step), v[i0], v[i1]);
     }
     __syncthreads();
   }
@@ -123,21 +86,10 @@ __device__ __forceinline__ void lds_ifft_dit(float2* v, int M, const float2* tlo
       const int j = b & (half - 1);
       const int i0 = ((b - j) << 1) + j, i1 = i0 + half;
       const float2 p = v[i0], q = v[i1];
-      const float2 w = twiddle2(tlo, thi, j * step);            // conj(w) = (w.x, -w.y)
-      const float tr = __builtin_fmaf(q.x, w.x, q.y * w.y), ti = __builtin_fmaf(q.y, w.x, -(q.x * w.y));
-      v[i0] = make_float2(p.x + tr, p.y + ti);
-      v[i1] = make_float2(p.x - tr, p.y - ti);
+      butterfly_dit_conj(p, q, twiddle(thi, tlo, j * step), v[i0], v[i1]);
     }
     __syncthreads();
   }
-}
-
-// exp(sign * i pi n^2 / N): n^2 mod 2N in integers (n < 4096), then one sincospi
-__device__ __forceinline__ float2 chirp(int n, int N, float sign) {
-  const int r = (n * n) % (2 * N);
-  float sn, cs;
-  sincospif((float)r / (float)N, &sn, &cs);
-  return make_float2(cs, sign * sn);
 }
 
 // LDS regions of one workgroup (see the kernel below for how they are laid out)
@@ -151,7 +103,7 @@ struct BlockLds {
 };
 
 // All 18 features of ONE frame by the whole 256-thread workgroup; out_row gets the 18 floats.
-// Also the slow path behind the wave kernel for frames outside its fp32 range (amcx_fixup_kernel.h).
+// A function of its own: the laboratory's range fix-up kernel (tools/experiments/amcx_fixup_kernel.h) calls it too.
 template <int MODE>
 __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int N, int M, const BlockLds& L,
                                             float* __restrict__ out_row, const float2* bh_regs = nullptr) {
@@ -164,10 +116,7 @@ __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int 
   const int tid = threadIdx.x;
   (void)bh; (void)tlo; (void)thi; (void)M;
   {
-    // The frame is staged times 2^-ex, ex the even-rounded exponent of its largest component (exact; 1 for
-    // ordinary data up to a factor < 4), and the finaliser un-scales in fp64 through the features' scaling
-    // laws: every fp32 intermediate (|x|^2, the spectrum) then stays inside float32 for any normal float32
-    // input, as the reference's complex128 evaluation does (features.py:46-58).
+    // The frame is staged times 2^-ex (frame_exponent: exact, and 1 for ordinary data).
     float mx = 0.f;
     for (int n = tid; n < N; n += kBlockThreads) {
       const float2 x = src[n];
@@ -175,8 +124,7 @@ __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int 
       mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(x.x), __builtin_fabsf(x.y)));
     }
     mx = block_max(mx, scratch);                       // NaN if the frame holds one (no scaling then); barriers inside
-    int ex = 0;
-    if (mx >= 0x1p-125f && mx <= 3.4028235e38f) ex = (((__builtin_bit_cast(int, mx) >> 23) & 0xff) - 127) & ~1;
+    const int ex = frame_exponent(mx);
     if (ex != 0) {
       const float sc = __builtin_bit_cast(float, (127 - ex) << 23);
       for (int n = tid; n < N; n += kBlockThreads) xs[n] = make_float2(xs[n].x * sc, xs[n].y * sc);
@@ -208,21 +156,13 @@ __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int 
       double e[3] = {0, 0, 0};  // sum a, sum theta, sum |theta|
       for (int n = tid; n < N; n += kBlockThreads) {
         const float2 x = xs[n];
-        const double re = x.x, im = x.y;
-        const double A = re * re - im * im, Bh = re * im, P = re * re + im * im;
-        const double AA = A * A, BB = Bh * Bh, AP = A * P;
-        m[0] += A; m[1] += Bh; m[2] += P;
-        const double X4 = AA - 4.0 * BB;
-        m[3] += AA; m[4] += X4; m[5] += A * Bh;
-        m[6] += AP; m[7] += Bh * P;
-        m[8] += AA * A; m[9] += A * BB; m[10] += AA * Bh; m[11] += BB * Bh;
-        m[12] += AA * P; m[13] += X4 * P; m[14] += AP * Bh;
+        moment_terms(x, m);
         if constexpr (MODE == kBlockDirect) {
           double a, th;
           env_phase_d(n, a, th);
           e[0] += a; e[1] += th; e[2] += __builtin_fabs(th);
         } else {
-          const float a = __builtin_amdgcn_sqrtf(__builtin_fmaf(x.x, x.x, __builtin_fmaf(x.y, x.y, kTinyPower)));
+          const float a = guarded_envelope(x.x, x.y);
           const float th = fast_angle(x.x, x.y, a);
           at[n] = make_float2(a, th);
           e[0] += a; e[1] += th; e[2] += __builtin_fabsf(th);
@@ -230,9 +170,7 @@ __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int 
       }
       block_sum(m, scratch);
       block_sum(e, scratch);   // the barrier inside also publishes `at`
-      S.sA = m[0]; S.sBh = m[1]; S.sP = m[2]; S.sAA = m[3]; S.sX4 = m[4]; S.sAB = m[5];
-      S.sAP = m[6]; S.sBP = m[7]; S.sAAA = m[8]; S.sABB = m[9]; S.sAAB = m[10]; S.sBBB = m[11];
-      S.sAAP = m[12]; S.sX4P = m[13]; S.sABP = m[14];
+      put_moments(S, m);
       S.sa = e[0]; S.Kt = e[1] / N; S.Ka = e[2] / N;
     }
     // ---- pass B: centred envelope / phase sums, first sum of the steps ---
@@ -247,12 +185,7 @@ __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int 
           const float2 v = at[n];
           va = v.x; vth = v.y;
         }
-        const double d = va - mu, d2 = d * d;
-        c[0] += __builtin_fabs(d); c[1] += d2; c[2] += d2 * d2;
-        const double dt = vth - S.Kt;
-        c[3] += dt; c[4] += dt * dt;
-        const double da = __builtin_fabs(vth) - S.Ka;
-        c[6] += da; c[7] += da * da;
+        centred_terms(va, vth, mu, S.Kt, S.Ka, c);
         if (n + 1 < N) {
           if constexpr (MODE == kBlockDirect) c[5] += step_d(n);
           else c[5] += exact_step(at[n + 1].y, (float)vth, xs[n].x, xs[n].y, xs[n + 1].x, xs[n + 1].y);
@@ -270,8 +203,7 @@ __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int 
         double w;
         if constexpr (MODE == kBlockDirect) w = step_d(n);
         else w = (double)exact_step(at[n + 1].y, at[n].y, xs[n].x, xs[n].y, xs[n + 1].x, xs[n + 1].y);
-        const double d = w - S.Kw, d2 = d * d;
-        c[0] += d; c[1] += d2; c[2] += d2 * d; c[3] += d2 * d2;
+        step_terms(w, S.Kw, c);
       }
       block_sum(c, scratch);   // trailing barrier: `at` may now be overwritten
       S.swd1 = c[0]; S.swd2 = c[1]; S.swd3 = c[2]; S.swd4 = c[3];
@@ -282,28 +214,17 @@ __device__ __forceinline__ void block_frame(const float2* __restrict__ src, int 
     float peak = 0.f;
     if constexpr (MODE == kBlockBluestein || MODE == kBlockBluesteinBig) {
       // a_n = x_n w_n in place over the frame, zero padding over the dead (|x|, angle) stash
-      for (int n = tid; n < M; n += kBlockThreads) {
-        float2 a = make_float2(0.f, 0.f);
-        if (n < N) {
-          const float2 x = xs[n], w = chirp(n, N, -1.0f);
-          a = make_float2(__builtin_fmaf(x.x, w.x, -(x.y * w.y)), __builtin_fmaf(x.x, w.y, x.y * w.x));
-        }
-        xs[n] = a;
-      }
+      for (int n = tid; n < M; n += kBlockThreads) xs[n] = n < N ? chirp_input(xs[n], n, N) : make_float2(0.f, 0.f);
       __syncthreads();
       lds_fft_dif(xs, M, tlo, thi);
       if constexpr (MODE == kBlockBluesteinBig) {
 #pragma unroll
         for (int j = 0; j < kBluesteinBigPerThread; ++j) {        // the chirp's spectrum: this thread's 64 entries, in registers
           const int n = tid + j * kBlockThreads;
-          const float2 a = xs[n], b = bh_regs[j];
-          xs[n] = make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x));
+          xs[n] = cmul(xs[n], bh_regs[j]);
         }
       } else {
-        for (int n = tid; n < M; n += kBlockThreads) {            // both spectra are in bit-reversed order
-          const float2 a = xs[n], b = bh[n];
-          xs[n] = make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x));
-        }
+        for (int n = tid; n < M; n += kBlockThreads) xs[n] = cmul(xs[n], bh[n]);   // both spectra are in bit-reversed order
       }
       __syncthreads();
       lds_ifft_dit(xs, M, tlo, thi);
@@ -394,10 +315,7 @@ __global__ __launch_bounds__(kBlockThreads, MODE == kBlockBluesteinBig ? 1 : 2) 
       tlo[tid] = make_float2(cs, -sn);                            // tlo[k] = W_M^k (k < 64), thi[k] = W_M^(64 k) (k < 128)
     }
     float2* const spec = MODE == kBlockBluesteinBig ? xs : bh;    // Big: built in the convolution buffer, then taken into registers
-    for (int n = tid; n < M; n += kBlockThreads) {
-      const int d = n < N ? n : (M - n < N ? M - n : -1);         // conj(w) is even in n: wrap it around
-      spec[n] = d >= 0 ? chirp(d, N, 1.0f) : make_float2(0.f, 0.f);
-    }
+    for (int n = tid; n < M; n += kBlockThreads) spec[n] = chirp_filter(n, N, M);
     __syncthreads();
     lds_fft_dif(spec, M, tlo, thi);
     if constexpr (MODE == kBlockBluesteinBig) {

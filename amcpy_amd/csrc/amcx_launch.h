@@ -329,6 +329,7 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bo
 // the training kernels' header (for philox4x32_10) and the down-converter's (for the mixer) in front of its own kernel, so it is laid out
 // behind the training kernels and in front of the fixed-point ones, and every older kernel keeps its bytes.
 // amcx_polyphase.h (the tap image, the sum and the plan arithmetic the generator and the resampler share) holds NO kernel, as amcx_mlp_shape.h: nothing moves.
+// Nor does amcx_exact_passes.h (what the block and the stream kernel share; the wave kernels' header includes it for wave_sum).
 // That specialisations are laid out there is what hipcc does today, not a rule it documents: tools/codeobj_gate.py --kernels
 // against the parent commit is what guards it, and the only thing that will notice when a compiler lays them out elsewhere.
 inline void kernel_order_anchor() {

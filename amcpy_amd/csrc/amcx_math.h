@@ -35,6 +35,11 @@ constexpr double kTwoPiD = 6.283185307179586476925286766559;
 // ---------------------------------------------------------------------------
 constexpr float kTinyPower = 1.0e-37f;
 
+// the envelope |x| with that guard, as fast_angle wants it
+__device__ __forceinline__ float guarded_envelope(float re, float im) {
+  return __builtin_amdgcn_sqrtf(__builtin_fmaf(re, re, __builtin_fmaf(im, im, kTinyPower)));
+}
+
 __device__ __forceinline__ float fast_angle(float re, float im, float a) {
   const float den = a + __builtin_fabsf(re);
   const float u = im * __builtin_amdgcn_rcpf(den);

@@ -3,7 +3,8 @@
 // The reference takes any frame_size (config.py:96 is a free integer, np.fft.fft, features.py:68, any N).  The block
 // kernel (amcx_block_kernel.h) stages a frame in LDS and ends at 8192 samples; the throughput kernels above it
 // (amcx_group_kernel.h) exist for the powers of two 16384 and 32768.  This kernel serves every OTHER size up to 32768 --
-// and those two as the accuracy-first cross-check of the group kernels -- with the block kernel's arithmetic:
+// and those two as the accuracy-first cross-check of the group kernels -- with the block kernel's arithmetic, which both
+// take from amcx_exact_passes.h (the frame's scale, the bodies of passes A-C, butterflies, Bluestein's pieces):
 //   * a 256 KB frame does not fit LDS, so it is read from global memory four times (maximum, moments, centred passes)
 //     -- the re-reads hit L2 / MALL, one frame per CU being 256 x 256 KB in flight at most -- and scaled by the exact
 //     power of two 2^-ex AT THE READ (the block kernel scales its staged copy);
@@ -19,8 +20,8 @@
 //     (512 KB) per frame in global scratch, and the C ABI's device entries allocate nothing.
 //   * WITH A WORKSPACE (amcx_features18_c64_ws, or the stream-ordered allocator behind amcx_features18_c64[_ex]) the
 //     spectral term is an FFT instead (the kernel's <true> form): Bluestein's chirp-z for sizes that are not powers of two,
-//     X_k = w_k sum_n (x_n w_n) conj(w_(k-n)), w_n = exp(-i pi n^2 / N), as a circular convolution of length M = 32768 /
-//     65536 (the FFT of the chirp once per launch, amcx_stream_chirp_kernel), and the plain FFT for 16384 / 32768.  The
+//     a circular convolution of length M = 32768 / 65536 (the FFT of the chirp once per launch,
+//     amcx_stream_chirp_kernel), and the plain FFT for 16384 / 32768.  The
 //     M-point transforms run IN PLACE ON GLOBAL MEMORY -- one private M x 8 byte buffer per workgroup, L2 / MALL traffic --
 //     in the four-step form M = R x 256: tiles of 32 columns (then 32 rows) go through LDS, 32 radix-2 transforms of R
 //     (256) points side by side, the twist W_M^(c kr) from a two-level table; forward decimation in frequency
@@ -30,7 +31,7 @@
 // from N = 16384 on: one workgroup per CU.  Algorithmic HBM bytes per frame: 8 N + 72 (the re-reads are L2 traffic).
 #pragma once
 
-#include "amcx_math.h"
+#include "amcx_exact_passes.h"
 
 namespace amcx {
 namespace stream {
@@ -61,18 +62,7 @@ __host__ __device__ constexpr size_t lds_bytes(int N) { return area_bytes(N) + k
 __host__ __device__ constexpr size_t lds_bytes_fft(int N) { return area_bytes(N) + kScratchBytes + kFftTabBytes; }
 
 // length of the transform the FFT form runs: N itself for a power of two, else Bluestein's M = 2^ceil(log2(2N - 1))
-__host__ __device__ inline int conv_length(int N) {
-  if ((N & (N - 1)) == 0) return N;
-  int m = 1;
-  while (m < 2 * N - 1) m <<= 1;
-  return m;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+__host__ __device__ inline int conv_length(int N) { return (N & (N - 1)) == 0 ? N : bluestein_length(N); }
 
 // Sum K per-thread doubles over the workgroup; every thread gets the totals (barriers inside).  The sixteen waves'
 // partial sums are added by K threads and handed out through LDS: every thread adding 16 x K values itself is 240 reads
@@ -100,24 +90,7 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double* scratch) {
   __syncthreads();
 }
 
-// Maximum over the workgroup; a NaN survives (fmaxf drops it, so a flag is carried).
-__device__ __forceinline__ float block_max(float v, double* scratch) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float bad = (v == v) ? 0.f : 1.f;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    v = __builtin_fmaxf(v, __shfl_xor(v, off, 64));
-    bad = __builtin_fmaxf(bad, __shfl_xor(bad, off, 64));
-  }
-  float* s = reinterpret_cast<float*>(scratch);
-  if (lane == 0) { s[wave * 2] = v; s[wave * 2 + 1] = bad; }
-  __syncthreads();
-  float m = s[0], b = s[1];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) { m = __builtin_fmaxf(m, s[w * 2]); b = __builtin_fmaxf(b, s[w * 2 + 1]); }
-  __syncthreads();
-  return b > 0.f ? __builtin_nanf("") : m;
-}
+__device__ __forceinline__ float block_max(float v, double* scratch) { return workgroup_max<kWaves>(v, scratch); }
 
 // ---- the FFT form ---------------------------------------------------------------------------------------------------
 struct FftLds {
@@ -139,14 +112,9 @@ __device__ __forceinline__ void build_fft_tables(float2* tab, int M) {
   }
 }
 
-__device__ __forceinline__ float2 twiddle_m(const FftLds& L, int e) {
-  const float2 a = L.mhi[e >> 6], b = L.mlo[e & 63];
-  return make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x));
-}
-
 // kTile transforms of len = 2^log_len (<= 256) points in the tile, by the whole workgroup; trailing barrier.
 // Forward: decimation in frequency, natural order in, bit-reversed out.  Inverse (unscaled): decimation in time with
-// conjugate twiddles, bit-reversed in, natural out (the block kernel's lds_fft_dif / lds_ifft_dit, side by side).
+// conjugate twiddles, bit-reversed in, natural out (the butterflies of the block kernel's lds_fft_dif / lds_ifft_dit).
 template <bool INV>
 __device__ __forceinline__ void tile_fft(float2* tile, int log_len, const float2* w256) {
   const int log_half = log_len - 1, half_len = 1 << log_half, total = kTile << log_half;
@@ -159,15 +127,8 @@ __device__ __forceinline__ void tile_fft(float2* tile, int log_len, const float2
       float2* v = tile + t * kPitch;
       const float2 p = v[i0], q = v[i1];
       const float2 w = w256[j << (7 - lh)];                // W_(2 half)^j
-      if constexpr (!INV) {
-        const float dr = p.x - q.x, di = p.y - q.y;
-        v[i0] = make_float2(p.x + q.x, p.y + q.y);
-        v[i1] = make_float2(__builtin_fmaf(dr, w.x, -(di * w.y)), __builtin_fmaf(dr, w.y, di * w.x));
-      } else {
-        const float tr = __builtin_fmaf(q.x, w.x, q.y * w.y), ti = __builtin_fmaf(q.y, w.x, -(q.x * w.y));
-        v[i0] = make_float2(p.x + tr, p.y + ti);
-        v[i1] = make_float2(p.x - tr, p.y - ti);
-      }
+      if constexpr (INV) butterfly_dit_conj(p, q, w, v[i0], v[i1]);
+      else butterfly_dif(p, q, w, v[i0], v[i1]);
     }
     __syncthreads();
   }
@@ -191,8 +152,8 @@ __device__ __forceinline__ float fft_forward(float2* g, int log_r, const FftLds&
     for (int i = tid; i < kTile * R; i += kThreads) {
       const int t = i & (kTile - 1), p = i >> 5;
       const int kr = (int)(__brev((unsigned)p) >> (32 - log_r));
-      const float2 w = twiddle_m(L, (c0 + t) * kr), v = L.tile[t * kPitch + p];
-      g[p * kC + c0 + t] = make_float2(__builtin_fmaf(v.x, w.x, -(v.y * w.y)), __builtin_fmaf(v.x, w.y, v.y * w.x));
+      const float2 w = twiddle(L.mhi, L.mlo, (c0 + t) * kr), v = L.tile[t * kPitch + p];
+      g[p * kC + c0 + t] = cmul(v, w);
     }
     __syncthreads();
   }
@@ -210,10 +171,7 @@ __device__ __forceinline__ float fft_forward(float2* g, int log_r, const FftLds&
       if constexpr (MODE == 2) {
         peak = __builtin_fmaxf(peak, __builtin_fmaf(v.x, v.x, v.y * v.y));
       } else {
-        if constexpr (MODE == 1) {
-          const float2 b = other[at];
-          v = make_float2(__builtin_fmaf(v.x, b.x, -(v.y * b.y)), __builtin_fmaf(v.x, b.y, v.y * b.x));
-        }
+        if constexpr (MODE == 1) v = cmul(v, other[at]);
         g[at] = v;
       }
     }
@@ -236,8 +194,8 @@ __device__ __forceinline__ float fft_inverse_peak(float2* g, int log_r, int n_ou
     for (int i = tid; i < kTile * kC; i += kThreads) {
       const int c = i & (kC - 1), t = i >> kLogC;
       const int kr = (int)(__brev((unsigned)(p0 + t)) >> (32 - log_r));
-      const float2 w = twiddle_m(L, c * kr), v = L.tile[t * kPitch + c];      // times conj(w)
-      g[(p0 + t) * kC + c] = make_float2(__builtin_fmaf(v.x, w.x, v.y * w.y), __builtin_fmaf(v.y, w.x, -(v.x * w.y)));
+      const float2 w = twiddle(L.mhi, L.mlo, c * kr), v = L.tile[t * kPitch + c];
+      g[(p0 + t) * kC + c] = cmul_conj(v, w);
     }
     __syncthreads();
   }
@@ -261,24 +219,13 @@ __device__ __forceinline__ float fft_inverse_peak(float2* g, int log_r, int n_ou
   return peak;
 }
 
-// exp(sign * i pi n^2 / N): n^2 mod 2N in integers (n < 32768: n^2 < 2^30), then one sincospi
-__device__ __forceinline__ float2 chirp(int n, int N, float sign) {
-  const int r = (n * n) % (2 * N);
-  float sn, cs;
-  sincospif((float)r / (float)N, &sn, &cs);
-  return make_float2(cs, sign * sn);
-}
-
 // Once per launch, one workgroup: the spectrum of Bluestein's filter conj(w), wrapped around M, in fft_forward's order.
 __global__ __launch_bounds__(kThreads, 4) void amcx_stream_chirp_kernel(float2* __restrict__ bspec, int N, int M) {
   extern __shared__ float4 amcx_stream_smem[];
   float2* const tile = reinterpret_cast<float2*>(amcx_stream_smem);
   float2* const tab = tile + kTile * kPitch;
   build_fft_tables(tab, M);
-  for (int n = threadIdx.x; n < M; n += kThreads) {
-    const int d = n < N ? n : (M - n < N ? M - n : -1);           // conj(w) is even in n
-    bspec[n] = d >= 0 ? chirp(d, N, 1.0f) : make_float2(0.f, 0.f);
-  }
+  for (int n = threadIdx.x; n < M; n += kThreads) bspec[n] = chirp_filter(n, N, M);
   __syncthreads();
   const FftLds L{tile, tab, tab + kW256, tab + kW256 + kMLo};
   fft_forward<0>(bspec, 31 - __builtin_clz((unsigned)(M / kC)), L, nullptr);
@@ -319,15 +266,14 @@ __global__ __launch_bounds__(kThreads, 4) void amcx_features18_stream_kernel(
 
   for (long long f = blockIdx.x; f < n_frames; f += gridDim.x) {
     const float2* __restrict__ src = iq + f * row_stride;
-    // ---- the frame's scale: 2^-ex, ex the even-rounded exponent of its largest component (amcx_block_kernel.h) ----
+    // ---- the frame's scale: 2^-ex (frame_exponent) ----
     float mx = 0.f;
     for (int n = tid; n < N; n += kThreads) {
       const float2 x = src[n];
       mx = __builtin_fmaxf(mx, __builtin_fmaxf(__builtin_fabsf(x.x), __builtin_fabsf(x.y)));
     }
     mx = block_max(mx, scratch);                         // NaN if the frame holds one (no scaling then)
-    int ex = 0;
-    if (mx >= 0x1p-125f && mx <= 3.4028235e38f) ex = (((__builtin_bit_cast(int, mx) >> 23) & 0xff) - 127) & ~1;
+    const int ex = frame_exponent(mx);
     const float sc = __builtin_bit_cast(float, (127 - ex) << 23);              // exact; 1 for ordinary data
     auto sample = [&](int n) -> float2 {
       const float2 x = src[n];
@@ -343,25 +289,15 @@ __global__ __launch_bounds__(kThreads, 4) void amcx_features18_stream_kernel(
       double e[3] = {0, 0, 0};                            // sum a, sum theta, sum |theta|
       for (int n = tid; n < N; n += kThreads) {
         const float2 x = sample(n);
-        const double re = x.x, im = x.y;
-        const double A = re * re - im * im, Bh = re * im, P = re * re + im * im;
-        const double AA = A * A, BB = Bh * Bh, AP = A * P;
-        m[0] += A; m[1] += Bh; m[2] += P;
-        const double X4 = AA - 4.0 * BB;
-        m[3] += AA; m[4] += X4; m[5] += A * Bh;
-        m[6] += AP; m[7] += Bh * P;
-        m[8] += AA * A; m[9] += A * BB; m[10] += AA * Bh; m[11] += BB * Bh;
-        m[12] += AA * P; m[13] += X4 * P; m[14] += AP * Bh;
-        const float a = __builtin_amdgcn_sqrtf(__builtin_fmaf(x.x, x.x, __builtin_fmaf(x.y, x.y, kTinyPower)));
+        moment_terms(x, m);
+        const float a = guarded_envelope(x.x, x.y);
         const float t = fast_angle(x.x, x.y, a);
         th[n] = t;
         e[0] += a; e[1] += t; e[2] += __builtin_fabsf(t);
       }
       block_sum(m, scratch);
       block_sum(e, scratch);                              // the barrier inside also publishes `th`
-      S.sA = m[0]; S.sBh = m[1]; S.sP = m[2]; S.sAA = m[3]; S.sX4 = m[4]; S.sAB = m[5];
-      S.sAP = m[6]; S.sBP = m[7]; S.sAAA = m[8]; S.sABB = m[9]; S.sAAB = m[10]; S.sBBB = m[11];
-      S.sAAP = m[12]; S.sX4P = m[13]; S.sABP = m[14];
+      put_moments(S, m);
       S.sa = e[0]; S.Kt = e[1] / N; S.Ka = e[2] / N;
     }
     // ---- pass B: centred envelope / phase sums, first sum of the steps ----
@@ -370,14 +306,9 @@ __global__ __launch_bounds__(kThreads, 4) void amcx_features18_stream_kernel(
       double c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       for (int n = tid; n < N; n += kThreads) {
         const float2 x = sample(n);
-        const float a = __builtin_amdgcn_sqrtf(__builtin_fmaf(x.x, x.x, __builtin_fmaf(x.y, x.y, kTinyPower)));
+        const float a = guarded_envelope(x.x, x.y);
         const float t = th[n];
-        const double d = (double)a - mu, d2 = d * d;
-        c[0] += __builtin_fabs(d); c[1] += d2; c[2] += d2 * d2;
-        const double dt = (double)t - S.Kt;
-        c[3] += dt; c[4] += dt * dt;
-        const double da = __builtin_fabs((double)t) - S.Ka;
-        c[6] += da; c[7] += da * da;
+        centred_terms(a, t, mu, S.Kt, S.Ka, c);
         if (n + 1 < N) {
           const float2 y = sample(n + 1);
           c[5] += exact_step(th[n + 1], t, x.x, x.y, y.x, y.y);
@@ -393,8 +324,7 @@ __global__ __launch_bounds__(kThreads, 4) void amcx_features18_stream_kernel(
       double c[4] = {0, 0, 0, 0};
       for (int n = tid; n + 1 < N; n += kThreads) {
         const float2 x = sample(n), y = sample(n + 1);
-        const double d = (double)exact_step(th[n + 1], th[n], x.x, x.y, y.x, y.y) - S.Kw, d2 = d * d;
-        c[0] += d; c[1] += d2; c[2] += d2 * d; c[3] += d2 * d2;
+        step_terms(exact_step(th[n + 1], th[n], x.x, x.y, y.x, y.y), S.Kw, c);
       }
       block_sum(c, scratch);                              // trailing barrier: `th` may be overwritten by the next frame
       S.swd1 = c[0]; S.swd2 = c[1]; S.swd3 = c[2]; S.swd4 = c[3];
@@ -406,14 +336,7 @@ __global__ __launch_bounds__(kThreads, 4) void amcx_features18_stream_kernel(
       const FftLds L{xs, tlo, tlo + kW256, tlo + kW256 + kMLo};
       const int log_r = 31 - __builtin_clz((unsigned)(M / kC));
       if (bspec != nullptr) {                             // Bluestein: a_n = x_n w_n, zero-padded to M
-        for (int n = tid; n < M; n += kThreads) {
-          float2 a = make_float2(0.f, 0.f);
-          if (n < N) {
-            const float2 x = sample(n), w = chirp(n, N, -1.0f);
-            a = make_float2(__builtin_fmaf(x.x, w.x, -(x.y * w.y)), __builtin_fmaf(x.x, w.y, x.y * w.x));
-          }
-          buf[n] = a;
-        }
+        for (int n = tid; n < M; n += kThreads) buf[n] = n < N ? chirp_input(sample(n), n, N) : make_float2(0.f, 0.f);
         __syncthreads();
         fft_forward<1>(buf, log_r, L, bspec);
         peak = fft_inverse_peak(buf, log_r, N, L) * (1.0f / ((float)M * (float)M));   // the inverse is unscaled; |w_k| = 1 drops out
@@ -455,9 +378,8 @@ __global__ __launch_bounds__(kThreads, 4) void amcx_features18_stream_kernel(
             float wr[kBins], wi[kBins], pr[kBins], pi[kBins];
   #pragma unroll
             for (int j = 0; j < kBins; ++j) {               // the exact twiddle at the head of the run
-              const float2 a = thi[idx[j] >> 6], b = tlo[idx[j] & 63];
-              wr[j] = __builtin_fmaf(a.x, b.x, -(a.y * b.y));
-              wi[j] = __builtin_fmaf(a.x, b.y, a.y * b.x);
+              const float2 w = cmul(thi[idx[j] >> 6], tlo[idx[j] & 63]);   // twiddle(thi, tlo, idx[j]), written out: through
+              wr[j] = w.x; wi[j] = w.y;                                     // the function this kernel's code changes
               pr[j] = 0.f; pi[j] = 0.f;
               idx[j] += step[j];
               if (idx[j] >= N) idx[j] -= N;

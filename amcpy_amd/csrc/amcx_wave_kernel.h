@@ -91,7 +91,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "amcx_math.h"
+#include "amcx_exact_passes.h"   // wave_sum (no kernel stands there)
 
 // WAVE PRIORITY.  A SIMD issues vector instructions by priority first, then by age (MI355X_MICROARCH.md, "Two waves per SIMD").
 // Four waves share one here, each somewhere else in its frame: in the statistics / envelope sweeps (dense fp32 arithmetic, every
@@ -707,12 +707,7 @@ __device__ __forceinline__ void build_fft_tables(char* t2, char* t3, int tid, in
 // frequency array, features.py:88-91,110-113).  In the
 // hot loop this cost 60-760 spilled VGPRs (round 1); as a separate launch it cost a 4-byte-per-frame scan
 // of the result matrix plus 29 us per 639 k frames (round 2).  sc: the power of two a re-run
-// multiplies the frame by (1 in the throughput kernel).
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+// multiplies the frame by (1 in the throughput kernel).  (wave_exact_frequency, behind the sample loader.)
 
 // ---------------------------------------------------------------------------
 // THE SAMPLE LOADER.  The wave and short kernels read samples from global memory at three seams -- load_frame / load_rows,
@@ -773,14 +768,13 @@ __device__ __forceinline__ void wave_exact_frequency(const E* __restrict__ src, 
     for (int u = 0; u < U; ++u) {
       const int n = lane + 64 * (U * t + u);
       const float pr = p[u].x * sc, pi = p[u].y * sc, qr = q[u].x * sc, qi = q[u].y * sc;
-      const float ap = __builtin_amdgcn_sqrtf(__builtin_fmaf(pr, pr, __builtin_fmaf(pi, pi, kTinyPower)));
-      const float aq = __builtin_amdgcn_sqrtf(__builtin_fmaf(qr, qr, __builtin_fmaf(qi, qi, kTinyPower)));
+      const float ap = guarded_envelope(pr, pi), aq = guarded_envelope(qr, qi);
       const float w = exact_step(fast_angle(qr, qi, aq), fast_angle(pr, pi, ap), pr, pi, qr, qi);
       const double d = n < N - 1 ? (double)w - Kw : 0.0, d2 = d * d;
       c0 += d; c1 += d2; c2 += d2 * d; c3 += d2 * d2;
     }
   }
-  frequency_features(Kw, wave_sum_f64(c0), wave_sum_f64(c1), wave_sum_f64(c2), wave_sum_f64(c3), N, f5, f9);
+  frequency_features(Kw, wave_sum(c0), wave_sum(c1), wave_sum(c2), wave_sum(c3), N, f5, f9);
 }
 
 // The 15 mixed-moment sums of ONE frame in fp64, by the whole wave: the slow path behind the finaliser's cancellation flag

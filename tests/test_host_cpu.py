@@ -1772,6 +1772,34 @@ def test_built_library_is_the_committed_gpu_program():
     assert got["code_object_sha256"] == want["code_object_sha256"]
 
 
+def test_sharing_the_exact_passes_left_every_kernel_its_bytes():
+    """amcx_exact_passes.h (the reductions, the frame's scale, the bodies of passes A-C, the complex helpers and Bluestein's
+    pieces that the block and the stream kernel now both call): the parent commit's library against the tree's, per kernel;
+    and the copies are gone from the two kernel headers."""
+    listing = (REPO / "profiles" / "r30_exact_passes_codeobj_kernels.txt").read_text()
+    assert "101 kernels / device functions identical" in listing
+    assert "DIFFERENT" not in listing and "ONLY IN A" not in listing and "ONLY IN B" not in listing
+    csrc = REPO / "amcpy_amd" / "csrc"
+    shared = (csrc / "amcx_exact_passes.h").read_text()
+    assert "__global__" not in shared
+    assert re.findall(r'#include\s+(\S+)', shared) == ['"amcx_math.h"']
+    product = re.compile(r"__builtin_fmaf\(\w+\.x, \w+\.x, -\(\w+\.y \* \w+\.y\)\)")          # Re(a b), written out
+    assert product.search(shared)
+    for header in ("amcx_block_kernel.h", "amcx_stream_kernel.h"):
+        text = (csrc / header).read_text()
+        assert '#include "amcx_exact_passes.h"' in text, header
+        assert "__shfl_xor" not in text and "m[14] +=" not in text and not product.search(text), header
+        assert not re.search(r"float2\s+chirp\s*\(", text) and "bit_cast(int, mx)" not in text, header
+        for call in ("moment_terms(", "put_moments(", "frame_exponent(", "workgroup_max<", "centred_terms(", "step_terms(",
+                     "guarded_envelope(", "butterfly_dif(", "butterfly_dit_conj(", "twiddle(", "chirp_filter(", "chirp_input("):
+            assert call in text, (header, call)
+    assert "wave_sum(" in (csrc / "amcx_wave_kernel.h").read_text()
+    for top in ("amcpy_amd", "include", "tools"):                      # (a patch against an older commit is a record, not code)
+        for p in (REPO / top).rglob("*"):
+            if p.is_file() and p.suffix in (".h", ".hip", ".py", ".sh", ".cpp"):
+                assert "wave_sum_f64" not in p.read_text(errors="replace"), p
+
+
 def test_run_extraction_resume_skips_complete_files(tmp_path):
     """``run_extraction(cfg, resume=True)`` / ``extract --resume``: the per-modulation output file is the path's
     resume unit.  A file that is complete for THIS configuration is skipped; a missing one, one
