@@ -321,7 +321,8 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bo
 // The spectrogram's (ABI 15, amcx_psd_kernel.h, which includes the occupancy and down-converter headers for occ_key and the
 // loaders) are included in front of those.
 // The fixed-point kernels (ABI 16, amcx_mlp_q15_kernel.h) come first of all now: plain kernels on amcx_mlp_shape.h, which holds the
-// declarations they share with the classifier and no kernel, so including it there moves nothing.
+// declarations and the device routines (staging, row load, sums, votes, the scaler's roundings) they share with the classifier and
+// no kernel, so including it there moves nothing.
 // The training kernels (ABI 16.1, amcx_mlp_train_kernel.h, on amcx_mlp_shape.h alone) are included in front of those: one plain kernel and
 // six explicit specialisations (an explicit INSTANTIATION is laid out behind the device functions in the middle of .text and moved the group
 // and stream kernels' distances; a specialisation is laid out where it stands, as the sc16 kernels are).

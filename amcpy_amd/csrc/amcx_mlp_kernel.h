@@ -23,11 +23,16 @@
 // gets label -1 and is counted in the extra last bin.  The reference's argmax of an all-NaN row answers class 0 (BPSK).
 //
 // Counts.  counts[group][n_classes + 1], groups being consecutive blocks of rows_per_group rows: per wave and slot, one
-// ballot + popcount per class and group touched (one group, or two where a boundary falls inside the 64 rows), then one
+// ballot + popcount per class and group touched (one group, or more where boundaries fall inside the 64 rows), then one
 // 64-bit vector atomic per non-empty bin from lane 0.
+//
+// The routines.  Staging, row load, a layer's sums and the votes are mlp_stage_params, mlp_load_rows, mlp_dense_f32 and
+// mlp_vote of amcx_mlp_shape.h, which the range calibration and the integer network (amcx_mlp_q15_kernel.h) call too; the
+// scaler is its mlp_standardise.  What stands here is the tile loop, the layer loop with the activation choice, the
+// softmax / argmax with the NaN rule (nothing else computes it in float32) and the stores.
 #pragma once
 
-#include "amcx_mlp_shape.h"      // the limits, MlpShape and the activations
+#include "amcx_mlp_shape.h"      // the limits, MlpShape, the activations and the routines
 #include "amcx_post_kernels.h"
 
 namespace amcx {
@@ -49,91 +54,19 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_classify_kernel(
   float* lds = reinterpret_cast<float*>(lds4);
   const int n_linear = shape.n_linear, n_cls = shape.w[n_linear];
 
-  // the packed block (per layer W[out][in] row-major, then b[out]) -> the padded copy
-  for (int i = threadIdx.x; i < n_linear * kMlpLayerFloats; i += kMlpThreads) lds[i] = 0.0f;
-  __syncthreads();
-  {
-    const float* src = params;
-    for (int l = 0; l < n_linear; ++l) {
-      const int n_in = shape.w[l], n_out = shape.w[l + 1];
-      float* dst = lds + l * kMlpLayerFloats;
-      for (int i = threadIdx.x; i < n_out * n_in; i += kMlpThreads) {
-        const int o = i / n_in, k = i - o * n_in;
-        dst[o * P + k] = src[i];
-      }
-      for (int i = threadIdx.x; i < n_out; i += kMlpThreads) dst[P * P + i] = src[n_out * n_in + i];
-      src += n_out * n_in + n_out;
-    }
-  }
-  __syncthreads();
+  mlp_stage_params(lds, params, shape);
 
-  const bool scaled = mean != nullptr;
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     float h[R][P];
     long long row[R];
-#pragma unroll
-    for (int s = 0; s < R; ++s) {
-      row[s] = tile * kMlpTileRows + s * kMlpThreads + (int)threadIdx.x;
-      const long long rr = row[s] < n_rows ? row[s] : n_rows - 1;      // past the end: a valid row, results masked
-      const float* xr = x + rr * row_stride;
-#pragma unroll
-      for (int j = 0; j < P; ++j) {
-        float v = 0.0f;
-        if (j < sel.n) {
-          v = xr[sel.c[j]];
-          if (scaled) {
-            const float c = (float)((double)v - mean[j]);
-            v = (float)((double)c / scale[j]);
-          }
-        }
-        h[s][j] = v;
-      }
-    }
+    mlp_load_rows(x, n_rows, row_stride, sel, mean, scale, tile, h, row);
 
     for (int l = 0; l < n_linear; ++l) {
       const int n_in = shape.w[l], n_out = shape.w[l + 1];
       const float* wl = lds + l * kMlpLayerFloats;
       const bool hidden = l + 1 < n_linear;
       float nx[R][P];
-#pragma unroll
-      for (int oc = 0; oc < P; oc += 8) {
-        if (oc < n_out) {
-          float acc[R][8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float b = wl[P * P + oc + j];
-#pragma unroll
-            for (int s = 0; s < R; ++s) acc[s][j] = b;
-          }
-#pragma unroll
-          for (int kc = 0; kc < P; kc += 8) {
-            if (kc < n_in) {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                const float4 wa = *reinterpret_cast<const float4*>(wl + (oc + j) * P + kc);
-                const float4 wb = *reinterpret_cast<const float4*>(wl + (oc + j) * P + kc + 4);
-                const float w8[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-#pragma unroll
-                  for (int s = 0; s < R; ++s) acc[s][j] = __builtin_fmaf(w8[k], h[s][kc + k], acc[s][j]);
-                }
-              }
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-#pragma unroll
-            for (int s = 0; s < R; ++s) nx[s][oc + j] = acc[s][j];
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-#pragma unroll
-            for (int s = 0; s < R; ++s) nx[s][oc + j] = 0.0f;
-          }
-        }
-      }
+      mlp_dense_f32(wl, n_in, n_out, h, nx);
       if (hidden) {                        // one uniform choice per layer, not one per element
         if (shape.act == kActRelu) mlp_act_all<kActRelu>(nx, n_out);
         else if (shape.act == kActTanh) mlp_act_all<kActTanh>(nx, n_out);
@@ -169,7 +102,7 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_classify_kernel(
         if (j < n_cls) {
           const float p = h[s][j] / sum;
           h[s][j] = p;
-          finite = finite && __builtin_fabsf(p) < __builtin_inff();
+          finite = finite && mlp_finite(p);
           if (j == 0 || p > pbest) {           // strictly greater: the first maximum wins
             best = j;
             pbest = p;
@@ -187,24 +120,7 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_classify_kernel(
             if (j < n_cls) pr[j] = h[s][j];
         }
       }
-      if (counts != nullptr) {
-        // the 64 rows of this wave's slot are consecutive: first .. last (uniform), in one group or a few
-        const long long first = tile * kMlpTileRows + s * kMlpThreads + (long long)(threadIdx.x & ~63u);
-        if (first < n_rows) {
-          const long long last = first + 63 < n_rows ? first + 63 : n_rows - 1;
-          const long long g_lo = first / rows_per_group, g_hi = last / rows_per_group;
-          const int bin = finite ? best : n_cls;
-          for (long long g = g_lo; g <= g_hi; ++g) {
-            const long long lo = g * rows_per_group;
-            const bool mine = live && row[s] >= lo && row[s] < lo + rows_per_group;
-            for (int c = 0; c <= n_cls; ++c) {
-              const unsigned long long votes = __ballot(mine && bin == c);
-              if (votes != 0ull && (threadIdx.x & 63u) == 0u)
-                atomicAdd(counts + g * (n_cls + 1) + c, (unsigned long long)__popcll(votes));
-            }
-          }
-        }
-      }
+      if (counts != nullptr) mlp_vote(tile, s, row[s], live, finite, best, n_cls, rows_per_group, counts, n_rows);
     }
   }
 }

@@ -6,10 +6,12 @@
 // zero-padded to 32 x 32 weights plus 32 biases; activations live in registers with compile-time indices, widths are run-time
 // values handled in blocks of 8 behind wave-uniform branches.  A row's result depends on nothing but the row.
 //
+// What they share with it stands once in amcx_mlp_shape.h: mlp_stage_params, mlp_load_rows, mlp_dense_f32, mlp_vote.
+//
 // amcx_mlp_range_kernel.  The float classifier's prologue (column pick, the scaler's two float32 roundings) and its sums
-// (float32 FMAs in the order bias, k = 0, 1, ...) restated here by q15_load_rows and q15_dense_f32 -- the classifier kernel
-// itself is left as it is, byte for byte -- with relu or nothing between the layers.  Per row the minimum and maximum of the
-// standardised input and of every layer's pre-activation values are parked in a lane-private LDS column; a row all of whose
+// (float32 FMAs in the order bias, k = 0, 1, ...), by the classifier's own routines, with relu or nothing between the layers.
+// Per row the minimum and maximum of the standardised input and of every layer's pre-activation values are parked in a
+// lane-private LDS column; a row all of whose
 // values are finite then merges them into the lane's running bounds, any other row is counted as skipped and merges nothing.
 // At the end a wave folds its 64 lanes with lane shuffles and lane 0 issues one integer atomic per bound: min and max are
 // order-free, so the result is exact whatever the reduction.
@@ -35,101 +37,7 @@ struct Q15Formats {
   int shift_o[kMlpMaxLinear];        // P - No >= 1: what the sum is shifted right by, a half rounding up
 };
 
-// ---- what the two kernels share ------------------------------------------------------------------------------------------
-// the packed block (per layer W[out][in] row-major, then b[out]) -> the padded copy in LDS; returns behind a barrier
-template <class T>
-__device__ inline void q15_stage_params(T* lds, const T* __restrict__ params, const MlpShape& shape) {
-  constexpr int P = kMlpMaxWidth;
-  for (int i = threadIdx.x; i < shape.n_linear * kMlpLayerFloats; i += kMlpThreads) lds[i] = T(0);
-  __syncthreads();
-  const T* src = params;
-  for (int l = 0; l < shape.n_linear; ++l) {
-    const int n_in = shape.w[l], n_out = shape.w[l + 1];
-    T* dst = lds + l * kMlpLayerFloats;
-    for (int i = threadIdx.x; i < n_out * n_in; i += kMlpThreads) {
-      const int o = i / n_in, k = i - o * n_in;
-      dst[o * P + k] = src[i];
-    }
-    for (int i = threadIdx.x; i < n_out; i += kMlpThreads) dst[P * P + i] = src[n_out * n_in + i];
-    src += n_out * n_in + n_out;
-  }
-  __syncthreads();
-}
-
-// the classifier's prologue: the lane's rows of a tile, the column pick, float(float(x - mean) / scale); the padding is 0.
-// A row past the end reads the last row (its results are masked by the caller).
-__device__ inline void q15_load_rows(const float* __restrict__ x, long long n_rows, long long row_stride, const SelectCols& sel,
-                                     const double* __restrict__ mean, const double* __restrict__ scale, long long tile,
-                                     float (&h)[kMlpRowsPerLane][kMlpMaxWidth], long long (&row)[kMlpRowsPerLane]) {
-  const bool scaled = mean != nullptr;
-#pragma unroll
-  for (int s = 0; s < kMlpRowsPerLane; ++s) {
-    row[s] = tile * kMlpTileRows + s * kMlpThreads + (int)threadIdx.x;
-    const long long rr = row[s] < n_rows ? row[s] : n_rows - 1;
-    const float* xr = x + rr * row_stride;
-#pragma unroll
-    for (int j = 0; j < kMlpMaxWidth; ++j) {
-      float v = 0.0f;
-      if (j < sel.n) {
-        v = xr[sel.c[j]];
-        if (scaled) {
-          const float c = (float)((double)v - mean[j]);
-          v = (float)((double)c / scale[j]);
-        }
-      }
-      h[s][j] = v;
-    }
-  }
-}
-
-__device__ inline bool q15_finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }
-
 // ---- calibration -----------------------------------------------------------------------------------------------------------
-// the classifier's sums: nx[o] = b[o] + sum_k W[o][k] h[k], float32 FMAs in the order bias, k = 0, 1, ...; the padding comes out 0
-__device__ inline void q15_dense_f32(const float* wl, int n_in, int n_out, const float (&h)[kMlpRowsPerLane][kMlpMaxWidth],
-                                     float (&nx)[kMlpRowsPerLane][kMlpMaxWidth]) {
-  constexpr int R = kMlpRowsPerLane, P = kMlpMaxWidth;
-#pragma unroll
-  for (int oc = 0; oc < P; oc += 8) {
-    if (oc < n_out) {
-      float acc[R][8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float b = wl[P * P + oc + j];
-#pragma unroll
-        for (int s = 0; s < R; ++s) acc[s][j] = b;
-      }
-#pragma unroll
-      for (int kc = 0; kc < P; kc += 8) {
-        if (kc < n_in) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float4 wa = *reinterpret_cast<const float4*>(wl + (oc + j) * P + kc);
-            const float4 wb = *reinterpret_cast<const float4*>(wl + (oc + j) * P + kc + 4);
-            const float w8[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-#pragma unroll
-              for (int s = 0; s < R; ++s) acc[s][j] = __builtin_fmaf(w8[k], h[s][kc + k], acc[s][j]);
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int s = 0; s < R; ++s) nx[s][oc + j] = acc[s][j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int s = 0; s < R; ++s) nx[s][oc + j] = 0.0f;
-      }
-    }
-  }
-}
-
 // min, max and finiteness of the first n of a row's values -> the lane's LDS column of slot `slot`
 __device__ inline void range_park(const float (&v)[kMlpRowsPerLane][kMlpMaxWidth], int n, float* cand, int slot, bool (&fin)[kMlpRowsPerLane]) {
 #pragma unroll
@@ -142,7 +50,7 @@ __device__ inline void range_park(const float (&v)[kMlpRowsPerLane][kMlpMaxWidth
         const float t = v[s][j];
         lo = t < lo ? t : lo;
         hi = t > hi ? t : hi;
-        ok = ok && q15_finite(t);
+        ok = ok && mlp_finite(t);
       }
     }
     fin[s] = fin[s] && ok;
@@ -186,7 +94,7 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_range_kernel(
   float* lds = reinterpret_cast<float*>(lds4);
   const int n_linear = shape.n_linear;
 
-  q15_stage_params(lds, params, shape);
+  mlp_stage_params(lds, params, shape);
   float run_lo[kRangeSlots], run_hi[kRangeSlots];                 // the lane's running bounds per slot
 #pragma unroll
   for (int l = 0; l < kRangeSlots; ++l) {
@@ -199,14 +107,14 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_range_kernel(
     float h[R][P];
     long long row[R];
     bool fin[R];
-    q15_load_rows(x, n_rows, row_stride, sel, mean, scale, tile, h, row);
+    mlp_load_rows(x, n_rows, row_stride, sel, mean, scale, tile, h, row);
 #pragma unroll
     for (int s = 0; s < R; ++s) fin[s] = true;
     range_park(h, shape.w[0], cand, 0, fin);
     for (int l = 0; l < n_linear; ++l) {
       const int n_in = shape.w[l], n_out = shape.w[l + 1];
       float nx[R][P];
-      q15_dense_f32(lds + l * kMlpLayerFloats, n_in, n_out, h, nx);
+      mlp_dense_f32(lds + l * kMlpLayerFloats, n_in, n_out, h, nx);
       range_park(nx, n_out, cand, l + 1, fin);
       if (l + 1 < n_linear && shape.act == kActRelu) mlp_act_all<kActRelu>(nx, n_out);
 #pragma unroll
@@ -288,7 +196,7 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_q15_kernel(
   const int n_linear = shape.n_linear, n_cls = shape.w[n_linear];
   const bool lane0 = (threadIdx.x & 63u) == 0u;
 
-  q15_stage_params(lds, params, shape);
+  mlp_stage_params(lds, params, shape);
 
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     int e[R][P];
@@ -298,14 +206,14 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_q15_kernel(
     bool finite[R];
     {
       float h[R][P];
-      q15_load_rows(x, n_rows, row_stride, sel, mean, scale, tile, h, row);
+      mlp_load_rows(x, n_rows, row_stride, sel, mean, scale, tile, h, row);
       unsigned clamped = 0u;
 #pragma unroll
       for (int s = 0; s < R; ++s) {
         bool ok = true;
 #pragma unroll
         for (int j = 0; j < P; ++j)
-          if (j < sel.n) ok = ok && q15_finite(h[s][j]);
+          if (j < sel.n) ok = ok && mlp_finite(h[s][j]);
         finite[s] = ok;
         labelled[s] = ok && row[s] < n_rows;
 #pragma unroll
@@ -408,23 +316,7 @@ __global__ __launch_bounds__(kMlpThreads) void amcx_mlp_q15_kernel(
             if (j < n_cls) pr[j] = finite[s] ? (short)e[s][j] : (short)0;      // a row without a label: zeros
         }
       }
-      if (counts != nullptr) {
-        // the classifier's votes: the 64 rows of this wave's slot are consecutive, first .. last (uniform), in one group or a few
-        const long long first = tile * kMlpTileRows + s * kMlpThreads + (long long)(threadIdx.x & ~63u);
-        if (first < n_rows) {
-          const long long last = first + 63 < n_rows ? first + 63 : n_rows - 1;
-          const long long g_lo = first / rows_per_group, g_hi = last / rows_per_group;
-          const int bin = finite[s] ? best : n_cls;
-          for (long long g = g_lo; g <= g_hi; ++g) {
-            const long long lo = g * rows_per_group;
-            const bool mine = live && row[s] >= lo && row[s] < lo + rows_per_group;
-            for (int c = 0; c <= n_cls; ++c) {
-              const unsigned long long votes = __ballot(mine && bin == c);
-              if (votes != 0ull && lane0) atomicAdd(counts + g * (n_cls + 1) + c, (unsigned long long)__popcll(votes));
-            }
-          }
-        }
-      }
+      if (counts != nullptr) mlp_vote(tile, s, row[s], live, finite[s], best, n_cls, rows_per_group, counts, n_rows);
     }
   }
 }

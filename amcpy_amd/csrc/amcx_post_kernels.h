@@ -19,7 +19,7 @@
 #pragma once
 
 #include "amcx_block_kernel.h"
-#include "amcx_mlp_shape.h"      // kStatMaxCols and SelectCols
+#include "amcx_mlp_shape.h"      // kStatMaxCols, SelectCols and mlp_standardise
 
 namespace amcx {
 
@@ -190,8 +190,7 @@ __global__ __launch_bounds__(kBlockThreads) void amcx_select_scale_kernel(
        i += (long long)gridDim.x * blockDim.x) {
     const long long r = i / n_sel;
     const int j = (int)(i - r * n_sel);
-    const float c = (float)((double)x[r * row_stride + cols[j]] - mean[j]);
-    out[r * out_stride + j] = (float)((double)c / scale[j]);
+    out[r * out_stride + j] = mlp_standardise(x[r * row_stride + cols[j]], mean[j], scale[j]);
   }
 }
 
@@ -226,8 +225,7 @@ __global__ __launch_bounds__(kBlockThreads) void amcx_select_fit_scale_kernel(
   const unsigned total = rows * (unsigned)sel.n, ns = (unsigned)sel.n;
   for (unsigned i = threadIdx.x; i < total; i += kBlockThreads) {
     const unsigned r = i / ns, j = i - r * ns;
-    const float c = (float)((double)x[(row0 + r) * row_stride + col_s[j]] - mu_s[j]);
-    out[(row0 + r) * out_stride + j] = (float)((double)c / sc_s[j]);
+    out[(row0 + r) * out_stride + j] = mlp_standardise(x[(row0 + r) * row_stride + col_s[j]], mu_s[j], sc_s[j]);
   }
 }
 

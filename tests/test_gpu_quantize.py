@@ -495,3 +495,32 @@ def test_leading_dimensions_and_groups_shape_both_classifiers_alike():
             labels15, counts15 = run(feats, rows_per_group=15)
             assert labels15.shape == (2, 3, 5) and counts15.shape == (2, n_cls + 1)
             assert torch.equal(labels15, labels) and np.array_equal(counts15.cpu().numpy(), want_counts[15])
+
+
+def test_votes_of_many_groups_in_a_wave_and_a_lone_last_row():
+    """mlp_vote, the histogram both classifiers call: 513 rows in groups of 19 are 27 groups, three or four of them inside every
+    wave slot's 64 rows, group boundaries at no multiple of 64, and row 512 alone in the second tile.  Six rows carry a NaN (the
+    first, the two either side of a group boundary, the two either side of the slot boundary at 256, one more), so the extra bin
+    is used.  For classify and for classify_q15, counts[g] == numpy.bincount of that classifier's OWN returned labels over rows
+    19 g ... 19 g + 18, label -1 in bin n_classes: integers, compared with ==."""
+    import torch
+    from amcpy_amd import quantize as qz
+    from amcpy_amd.classifier import MlpModel, classify
+    n_rows, per_group, bad = 513, 19, (0, 18, 19, 255, 256, 300)
+    z = np.load(GOLDEN / "classifier_ref_relu.npz", allow_pickle=False)
+    model = MlpModel.from_state_dict(state_dict_of(z), "relu")
+    x = torch.from_numpy(z["x"][:n_rows].copy()).cuda()
+    ranges, _ = qz.calibrate(x, model, cols=range(6))
+    q = qz.QuantizedMlp.from_model(model, ranges)
+    for k, r in enumerate(bad):
+        x[r, k % 6] = float("nan")
+    n_cls = model.n_classes
+    for name, run in (("classify", lambda: classify(x, model, cols=range(6), rows_per_group=per_group, want=("labels", "counts"))),
+                      ("classify_q15", lambda: qz.classify_q15(x, q, cols=range(6), rows_per_group=per_group, want=("labels", "counts")))):
+        labels, counts = run()
+        lab, got = labels.cpu().numpy(), counts.cpu().numpy()
+        assert lab.shape == (n_rows,) and got.shape == (n_rows // per_group, n_cls + 1), name
+        assert sorted(np.flatnonzero(lab < 0).tolist()) == list(bad) and len(set(lab[lab >= 0].tolist())) >= 3, name
+        want = np.stack([np.bincount(np.where(g < 0, n_cls, g), minlength=n_cls + 1) for g in lab.reshape(-1, per_group)])
+        assert np.array_equal(got, want), name
+        assert got.sum() == n_rows and got[:, n_cls].sum() == len(bad), name

@@ -229,6 +229,41 @@ def test_both_kernels_are_in_the_resource_table_without_spills_and_every_older_k
     assert sorted(re.findall(r"ONLY IN B\s+amcx::(\w+)", listing)) == ["amcx_mlp_q15_kernel", "amcx_mlp_range_init_kernel", "amcx_mlp_range_kernel"]
 
 
+def test_sharing_the_network_routines_moved_the_three_inference_kernels_alone():
+    """amcx_mlp_shape.h (parameter staging, row load, the float32 sums, the votes and the scaler's two roundings, which the float
+    classifier, the range calibration and the integer network now all call): the parent commit's library against the tree's, per
+    kernel -- nothing on one side only, nothing different but those three, which keep their registers and spill nothing; and the
+    copies are gone from the two kernel headers."""
+    three = ["amcx_mlp_classify_kernel", "amcx_mlp_q15_kernel", "amcx_mlp_range_kernel"]
+    listing = (REPO / "profiles" / "r31_mlp_shared_codeobj_kernels.txt").read_text()
+    assert "ONLY IN A" not in listing and "ONLY IN B" not in listing
+    assert "98 kernels / device functions identical" in listing
+    assert sorted(re.findall(r"^DIFFERENT\s+amcx::(\S+)\s*$", listing, re.M)) == three and listing.count("DIFFERENT") == 3
+    table = json.loads((REPO / "amcpy_amd" / "csrc" / "kernel_resources.json").read_text())
+    for name, vgpr in zip(three, (182, 197, 195)):                              # the parent's counts
+        assert table[name] == {"vgpr": vgpr, "spill": 0, "scratch": 0}, name
+    csrc = REPO / "amcpy_amd" / "csrc"
+    shared = (csrc / "amcx_mlp_shape.h").read_text()
+    assert "__global__" not in shared
+    assert re.findall(r'#include\s+(\S+)', shared) == ["<hip/hip_runtime.h>"]
+    chain = re.compile(r"__builtin_fmaf\(w8\[k\]")
+    assert chain.search(shared) and "__ballot(mine" in shared
+    for routine in ("mlp_stage_params(", "mlp_standardise(", "mlp_load_rows(", "mlp_finite(", "mlp_dense_f32(", "mlp_vote("):
+        assert len(re.findall(rf"__device__ inline \w+ {re.escape(routine)}", shared)) == 1, routine
+    for header in ("amcx_mlp_kernel.h", "amcx_mlp_q15_kernel.h"):
+        text = (csrc / header).read_text()
+        for call in ("mlp_stage_params(", "mlp_load_rows(", "mlp_dense_f32(", "mlp_vote("):
+            assert call in text, (header, call)
+        assert "__ballot(mine" not in text and not chain.search(text), header
+        assert "/ scale[" not in text and "__syncthreads" not in text, header       # the scaler and the staging barriers
+    assert (csrc / "amcx_post_kernels.h").read_text().count("mlp_standardise(") == 2
+    for p in csrc.rglob("*"):
+        if p.is_file() and p.suffix in (".h", ".hip", ".py", ".json"):
+            text = p.read_text(errors="replace")
+            for old in ("q15_load_rows", "q15_dense_f32", "q15_stage_params", "q15_finite"):
+                assert old not in text, (p, old)
+
+
 # ---- the refusals, in the header's order ---------------------------------------------------------------------------------------
 SHARED_LIMITS = (dict(n_rows=-1), dict(n_cols=0), dict(n_cols=33, stride=33), dict(stride=17), dict(stride=0), dict(stride=-18),
                  dict(cols=None), dict(widths=None), dict(widths=_i32(6, 0, 29, 30, 6)), dict(widths=_i32(6, 33, 29, 30, 6)),
