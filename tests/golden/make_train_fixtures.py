@@ -9,8 +9,12 @@
   -- in double() ('sd64:', optimizer slots 'opt64:<slot>:<key>') and as the reference runs it, in float32 ('sd32:', 'opt32:') --
   with err32:<name> = max |theta32 - theta64| per tensor and the `cmp:<key>` masks of the elements that are compared.
   The default-shape cases are built from the reference's AMCClassifier; the others from torch.nn with its layer numbering.
-* the case `default_relu_rmsprop` also holds 'drop64:' / 'dropopt64:' / 'dropcmp:': K steps with dropout 0.4 by
-  tests/train_ref.py (which tests/test_train_host.py pins to the double() states above) under the Philox masks of include/amcx.h.
+* the cases of DROP_CASES also hold 'drop64:' / 'dropopt64:' / 'dropcmp:': K steps with dropout 0.4 by tests/train_ref.py
+  (which tests/test_train_host.py pins to the double() states above) under the Philox masks of include/amcx.h.
+* the cases of CLASS_CASES also hold 'cls64:' / 'clsopt64:' / 'clscmp:' with `y_cls` and `cls_rows`: K steps without dropout by
+  tests/train_ref.py on labels of which three rows of every batch carry -1, the number of classes and 2^31 - 1.  This block has
+  NO counterpart in the reference (torch raises on such a label): it states the header's sentence "a class outside
+  0 ... classes - 1 matches no class" -- an all-zero one-hot, no loss term, never counted right -- and nothing else.
 * train_learning.npz -- held-out accuracies of five runs (seeds 0 ... 4) of the reference's training loop, default
   hyperparameters, 3 epochs on the six Gaussian clusters of make_classifier_fixtures.clusters(6, 6, 7680, 0, seed=31): the first
   6144 rows train, the last 1536 are held out.
@@ -63,9 +67,38 @@ CASES = {
     # two rows THROUGH a BatchNorm: a small network (8 units, 32 unit-steps), where the seed search can meet the margins
     "batch_2_bn": ((4, 8, 3), 1, "tanh", "rmsprop", 2, None),
     "ragged_2_bn": ((4, 8, 3), 1, "tanh", "rmsprop", 128, 3 * 128 + 2),
+    # the sixth kernel: sigmoid with adam
+    "default_sigmoid_adam": (DEFAULT, 7, "sigmoid", "adam", 128, None),
+    # mixed masks: a BatchNorm's gamma / beta, statistics and slots behind a layer that has none, a Linear bias with a real
+    # gradient next to one in front of a BatchNorm, the BatchNorm backward skipped between two layers that take it.
+    # (tanh on the default shape: with relu neither mask 5 nor mask 2 has a seed among 400 that meets the margins below)
+    "mask_5": (DEFAULT, 0b101, "tanh", "adam", 64, None),
+    "mask_2": (DEFAULT, 0b010, "tanh", "rmsprop", 65, None),
+    # widths 32 (bit 31 of a dropout word, quad 7), 7 and 9 (no multiple of 4), a ragged last batch of 31 rows
+    # (tanh: sigmoid with mask 9 on this shape has no seed among 400 at batch 256 or 128)
+    "mask_6": ((5, 32, 7, 32, 9, 3), 0b0110, "tanh", "rmsprop", 128, 3 * 128 + 31),
+    "mask_9": ((5, 32, 7, 32, 9, 3), 0b1001, "tanh", "adam", 128, None),
+    # relu through a hidden layer without BatchNorm (mask 0b10; with mask 1 this shape has no seed among 400)
+    "small_relu_2": ((4, 8, 8, 3), 0b10, "relu", "adam", 64, None),
 }
 SEEDS = {"batch_2_bn": 40000, "ragged_2_bn": 40000}          # data seeds tried per case (default 400)
 DROP_P, DROP_SEED = 0.4, 0x123456789ABCDEF
+# the cases that also hold a dropout run, and those that also hold a run on labels outside the classes
+DROP_CASES = {"default_relu_rmsprop", "default_sigmoid_adam", "mask_5", "mask_2", "mask_6", "mask_9", "small_relu_2"}
+CLASS_CASES = {"small_relu_2"}
+OUTSIDE = (-1, None, 2 ** 31 - 1)                              # None: the number of classes
+
+
+def outside_labels(y, order, batch, n_classes):
+    """(labels, planted rows): three rows of every batch of the epoch -- its second, its middle and its last -- carry OUTSIDE."""
+    y_cls, planted = np.array(y, dtype=np.int32), []
+    for first in range(0, K * batch, batch):
+        rows = order[first:first + batch]
+        for at, label in zip((1, len(rows) // 2, len(rows) - 1), OUTSIDE):
+            y_cls[rows[at]] = n_classes if label is None else label
+            planted.append(rows[at])
+    assert len(set(planted)) == len(planted), "the order visits a planted row twice"
+    return y_cls, np.asarray(planted, dtype=np.int32)
 
 
 def _load(name, path):
@@ -229,21 +262,29 @@ def main():
             zero_grad = {f"layers.{li}.bias" for li, bi in indices if bi is not None}
             few = lambda masks: all(1.0 - m.mean() <= 0.01 for k, m in masks.items() if k not in zero_grad)
             ok = min(watch["var"], default=1.0) > 1e-3 and min(watch["act"], default=1.0) > 1e-4 and few(cmp)
-            drop = {}
-            if ok and name == "default_relu_rmsprop":                     # the dropout run, by the restatement
-                thr, keep = tref.drop_params(DROP_P)
-                st = ref_state(tref, sd0, widths, bn_mask, optimizer, indices)
-                dgrads, pre = [], []
+            extra = {}
+            st0 = ref_state(tref, sd0, widths, bn_mask, optimizer, indices)
+
+            def restated(prefix, slot_prefix, cmp_prefix, labels, thr, keep):
+                """K steps of tests/train_ref.py from sd0 under the fixtures' key names, and whether the 1 % holds for them."""
+                st, sgrads = copy.deepcopy(st0), []
                 for s in range(K):
                     rows = order[s * batch:(s + 1) * batch]
-                    masks = tref.dropout_masks(DROP_SEED, st["t"], widths[1:-1], len(rows), thr)
-                    _, _, g = tref.step(st, x[rows].astype(np.float64), y[rows], activation=act, optimizer=optimizer, lr=LR, masks=masks,
+                    masks = tref.dropout_masks(DROP_SEED, st["t"], widths[1:-1], len(rows), thr) if thr else None
+                    _, _, g = tref.step(st, x[rows].astype(np.float64), labels[rows], activation=act, optimizer=optimizer, lr=LR, masks=masks,
                                         keep_scale=keep)
-                    dgrads.append(ref_arrays({**g, "slots": [], "rm": st["rm"], "rv": st["rv"]}, indices, "", "", optimizer))
-                dcmp = compare_masks([{k: v for k, v in g.items() if "running" not in k} for g in dgrads])
-                ok = few(dcmp)
-                drop = {**ref_arrays(st, indices, "drop64:", "dropopt64:", optimizer), **{f"dropcmp:{k}": v for k, v in dcmp.items()},
-                        "drop_p": DROP_P, "drop_seed": np.uint64(DROP_SEED)}
+                    sgrads.append(ref_arrays({**g, "slots": [], "rm": st["rm"], "rv": st["rv"]}, indices, "", "", optimizer))
+                scmp = compare_masks([{k: v for k, v in g.items() if "running" not in k} for g in sgrads])
+                return few(scmp), {**ref_arrays(st, indices, prefix, slot_prefix, optimizer), **{f"{cmp_prefix}{k}": v for k, v in scmp.items()}}
+
+            if ok and name in DROP_CASES:                                 # the dropout run, by the restatement
+                thr, keep = tref.drop_params(DROP_P)
+                ok, arrays = restated("drop64:", "dropopt64:", "dropcmp:", y, thr, keep)
+                extra.update(arrays, drop_p=DROP_P, drop_seed=np.uint64(DROP_SEED))
+            if ok and name in CLASS_CASES:                                # labels outside the classes: the header's rule, not torch's
+                y_cls, planted = outside_labels(y, order, batch, widths[-1])
+                ok, arrays = restated("cls64:", "clsopt64:", "clscmp:", y_cls, 0, 1.0)
+                extra.update(arrays, y_cls=y_cls, cls_rows=planted)
             if ok:
                 break
         else:
@@ -257,12 +298,14 @@ def main():
         for k in opt64:
             arrays[f"opt64:{k}"], arrays[f"opt32:{k}"] = opt64[k], opt32[k]
             arrays[f"err32:{k}"] = np.abs(opt32[k].astype(np.float64) - opt64[k]).max()
-        worst = max(float(1.0 - m.mean()) for k, m in cmp.items() if k not in zero_grad)
+        left_out = {**{f"cmp:{k}": m for k, m in cmp.items()}, **{k: m for k, m in extra.items() if "cmp:" in k}}
+        worst = max(float(1.0 - m.mean()) for k, m in left_out.items() if k.split(":", 1)[1] not in zero_grad)
+        assert worst <= 0.01, (name, worst)                         # the cap, over the plain, the dropout and the outside-class run
         print(f"{name}: data seed {seed}, smallest batch variance {min(watch['var'], default=float('nan')):.3e}, smallest |relu input| "
               f"{min(watch['act'], default=float('nan')):.3e}, most elements left out of a tensor {100 * worst:.2f} %")
         np.savez_compressed(HERE / f"train_steps_{name}.npz", raw=raw, cols=cols, mean=mean, scale=scale, x=x, y=y.astype(np.int32),
                             order=order, widths=np.asarray(widths, np.int32), bn_mask=bn_mask, activation=act, optimizer=optimizer,
-                            batch=batch, lr=LR, steps=K, data_seed=seed, **arrays, **{f"cmp:{k}": v for k, v in cmp.items()}, **drop)
+                            batch=batch, lr=LR, steps=K, data_seed=seed, **arrays, **{f"cmp:{k}": v for k, v in cmp.items()}, **extra)
 
     if a.only is not None:
         return

@@ -33,6 +33,23 @@ def test_restatement_equals_the_reference_in_double(name):
     assert all(np.isfinite(losses))
 
 
+@pytest.mark.parametrize("name", tc.DROP_CASES)
+def test_dropout_blocks_are_the_restatement_under_the_philox_masks(name):
+    """`drop64:` / `dropopt64:` of a fixture: K steps of tests/train_ref.py with p = 0.4 and the fixture's seed; `dropcmp:` leaves
+    out 1 % of a tensor at the most (the bias in front of a BatchNorm apart, as in `cmp:`)."""
+    case = tc.load(name)
+    thr, keep = train_ref.drop_params(float(case["drop_p"]))
+    state, _, _ = train_ref.run(tc.ref_state(case), case["x"].astype(np.float64), case["y"], case["order"], case["batch"], case["steps"],
+                                activation=case["activation"], optimizer=case["optimizer"], lr=case["lr"], seed=int(case["drop_seed"]),
+                                threshold=thr, keep_scale=keep)
+    got, want = tc.ref_tensors(case, state), tc.expected(case, "drop64:", "dropopt64:")
+    assert set(got) == set(want) and all(np.abs(got[k] - want[k]).max() <= 1e-12 for k in want)
+    zero_grad = {f"layers.{li}.bias" for li, bi in train.layer_indices(case["widths"], case["bn_mask"]) if bi is not None}
+    for prefix in ("cmp:", "dropcmp:") + (("clscmp:",) if name in tc.CLASS_CASES else ()):
+        masks = {k[len(prefix):]: v for k, v in case.items() if k.startswith(prefix)}
+        assert masks and all(1.0 - m.mean() <= 0.01 for k, m in masks.items() if k not in zero_grad), prefix
+
+
 def test_fixture_inputs_are_the_scaler_of_the_raw_rows():
     case = tc.load("default_relu_rmsprop")
     c = (case["raw"][:, case["cols"]].astype(np.float64) - case["mean"]).astype(np.float32)
@@ -96,6 +113,8 @@ def test_state_block_size_is_the_library_s_for_every_fixture_shape():
     """TrainState's own layout arithmetic against amcx_mlp_train_state_floats, over every shape, mask and optimizer of the fixtures."""
     shapes = {(tc.load(name)["widths"], tc.load(name)["bn_mask"], tc.load(name)["optimizer"]) for name in tc.CASES}
     assert len({w for w, _, _ in shapes}) >= 6 and {o for _, _, o in shapes} == {"rmsprop", "adam"} and len({m for _, m, _ in shapes}) >= 2
+    # mixed masks, where the offsets of a BatchNorm are not those of a per-layer formula: three distinct ones at least
+    assert len({m for w, m, _ in shapes if m != 0 and m != (1 << (len(w) - 2)) - 1}) >= 3
     for widths, bn_mask, optimizer in sorted(shapes):
         want = train.state_floats(widths, bn_mask, optimizer)
         for n_models in (1, 3):
@@ -103,6 +122,116 @@ def test_state_block_size_is_the_library_s_for_every_fixture_shape():
             assert st.state_floats == want == train.layout(widths, bn_mask, optimizer)["state_floats"] and st.block.shape == (n_models, want)
             assert st.n_train == st.n_params + st.n_affine and st.n_slots == (2 if optimizer == "adam" else 1)
         assert train.TrainState.init(widths, bn_mask, optimizer, [1, 2]).block.shape == (2, want)
+
+
+def test_state_block_layout_under_a_mixed_mask():
+    """(5, 32, 7, 32, 9, 3), BatchNorm behind the first and the fourth hidden layer only, adam: the first index of every view
+    against the header's rule (THE STATE BLOCK) worked out here by hand, not by layer_indices or layout.
+    Parameters W then b per layer: 5x32 at 0 / 160, 32x7 at 192 / 416, 7x32 at 423 / 647, 32x9 at 679 / 967, 9x3 at 976 / 1003,
+    P = 1006.  BatchNorms (widths 32 and 9), gamma then beta each: 1006 / 1038, 1070 / 1079, T = 1088.  Running mean then variance
+    each: 1088 / 1120, 1152 / 1161, T + R = 1170.  Slots of T values: exp_avg from 1170, exp_avg_sq from 2258; 3346 in all.
+    In the reference's Sequential the Linears are modules 0, 4, 7, 10, 14 and the BatchNorms 1 and 11."""
+    w, mask = (5, 32, 7, 32, 9, 3), 0b1001
+    P, T, R = 1006, 1088, 82
+    assert train.state_floats(w, mask, "adam") == 3 * T + R == 3346
+    st = train.TrainState.init(w, mask, "adam", [1])
+    assert st.block.shape == (1, 3346) and (st.n_params, st.n_affine, st.n_train) == (P, R, T)
+    st.block[0] = np.arange(3346)
+    trainable = {"layers.0.weight": (0, (32, 5)), "layers.0.bias": (160, (32,)), "layers.4.weight": (192, (7, 32)),
+                 "layers.4.bias": (416, (7,)), "layers.7.weight": (423, (32, 7)), "layers.7.bias": (647, (32,)),
+                 "layers.10.weight": (679, (9, 32)), "layers.10.bias": (967, (9,)), "layers.14.weight": (976, (3, 9)),
+                 "layers.14.bias": (1003, (3,)), "layers.1.weight": (1006, (32,)), "layers.1.bias": (1038, (32,)),
+                 "layers.11.weight": (1070, (9,)), "layers.11.bias": (1079, (9,))}
+    running = {"layers.1.running_mean": (1088, (32,)), "layers.1.running_var": (1120, (32,)), "layers.11.running_mean": (1152, (9,)),
+               "layers.11.running_var": (1161, (9,))}
+    for part, base, want in ((0, 0, {**trainable, **running}), (1, 1170, trainable), (2, 2258, trainable)):
+        views = st.views(0, part)
+        assert set(views) == set(want), part
+        for key, (first, shape) in want.items():
+            at = first if key in running else base + first
+            assert views[key].shape == shape and views[key].reshape(-1)[0] == at and views[key].reshape(-1)[-1] == at + np.prod(shape) - 1, (part, key)
+    # every float of the block belongs to exactly one view
+    seen = np.concatenate([v.reshape(-1) for part in range(3) for v in st.views(0, part).values()])
+    assert np.array_equal(np.sort(seen), np.arange(3346))
+
+
+@pytest.mark.parametrize("name", ("mask_5", "mask_2", "mask_6", "mask_9", "small_relu_2"))
+def test_state_dict_round_trip_under_a_mixed_mask(name):
+    """from_state_dict finds the mask in the keys of the reference's state dict; to_state_dict gives every tensor back."""
+    case = tc.load(name)
+    sd = tc.state_dict(case, "sd32:")
+    st = train.TrainState.from_state_dict(sd, case["optimizer"])
+    assert st.bn_mask == case["bn_mask"] and st.widths == case["widths"] and st.steps.tolist() == [case["steps"]]
+    back = st.to_state_dict(0)
+    assert set(back) == set(sd) and all(np.array_equal(back[k].numpy(), sd[k]) for k in sd)
+    again = train.TrainState.from_state_dict(back, case["optimizer"])
+    assert again.bn_mask == case["bn_mask"] and np.array_equal(again.block, st.block) and np.array_equal(again.steps, st.steps)
+    assert train.TrainState.from_state_dict(sd, case["optimizer"], steps=2 ** 32 + 3).steps.tolist() == [2 ** 32 + 3]
+
+
+def test_restatement_of_a_class_outside_the_classes():
+    """The header: "a class outside 0 ... classes - 1 matches no class".  In tests/train_ref.py such a row adds nothing to the loss
+    and nothing to the count, and its dp is q / rows (an all-zero one-hot): the gradients against a second, direct statement of
+    a (4, 5, 3) tanh network without BatchNorm, written out here.  The reference has no such rule (torch raises)."""
+    rng = np.random.default_rng(11)
+    rows, labels = 6, np.array([0, -1, 2, 3, 2 ** 31 - 1, 1])
+    x = rng.standard_normal((rows, 4))
+    W0, b0, W1, b1 = rng.standard_normal((5, 4)), rng.standard_normal(5), rng.standard_normal((3, 5)), rng.standard_normal(3)
+    state = train_ref.new_state([W0, W1], [b0, b1], [None], [None], [None], [None], "rmsprop")
+    loss, right, g = train_ref.step(state, x, labels, activation="tanh", optimizer="rmsprop", lr=1e-3)
+    # the direct statement, row by row
+    inside = [r for r in range(rows) if 0 <= labels[r] < 3]
+    assert inside == [0, 2, 5]
+    dW0, db0, dW1, db1, want_loss, want_right = np.zeros_like(W0), np.zeros_like(b0), np.zeros_like(W1), np.zeros_like(b1), 0.0, 0
+    for r in range(rows):
+        a = np.tanh(W0 @ x[r] + b0)
+        e = np.exp(W1 @ a + b1)
+        p = e / e.sum()
+        q = np.exp(p) / np.exp(p).sum()
+        dp = q / rows
+        if r in inside:
+            dp[labels[r]] -= 1.0 / rows
+            want_loss -= np.log(q[labels[r]])
+            want_right += int(np.argmax(p) == labels[r])
+        dz = (np.diag(p) - np.outer(p, p)) @ dp                     # the softmax's Jacobian
+        da = (W1.T @ dz) * (1.0 - a * a)
+        dW1, db1, dW0, db0 = dW1 + np.outer(dz, a), db1 + dz, dW0 + np.outer(da, x[r]), db0 + da
+    assert abs(loss - want_loss) <= 1e-12 * want_loss and right == want_right
+    for got, want in ((g["W"][0], dW0), (g["b"][0], db0), (g["W"][1], dW1), (g["b"][1], db1)):
+        assert np.abs(got - want).max() <= 1e-13 * np.abs(want).max()
+    # the rows outside alone: no loss, none right -- and still a gradient
+    alone = train_ref.new_state([W0, W1], [b0, b1], [None], [None], [None], [None], "rmsprop")
+    loss, right, g = train_ref.step(alone, x[[1, 3, 4]], labels[[1, 3, 4]], activation="tanh", optimizer="rmsprop", lr=1e-3)
+    assert loss == 0.0 and right == 0 and np.abs(g["W"][1]).max() > 0.0
+
+
+def test_planted_rows_of_the_outside_class_fixture_add_nothing():
+    """tests/golden/train_steps_small_relu_2.npz: three rows of every batch carry -1, the number of classes and 2^31 - 1; the
+    restatement's loss and count over those rows alone are 0 at every step, so the history a kernel is held to in
+    tests/test_gpu_train.py is that of the other rows.  And the `cls64:` block is the restatement's state."""
+    case = tc.load("small_relu_2")
+    y, y_cls, planted, batch = case["y"], case["y_cls"], case["cls_rows"], case["batch"]
+    assert len(planted) == 3 * case["steps"] and sorted(set(y_cls[planted].tolist())) == [-1, len(set(y.tolist())), 2 ** 31 - 1]
+    assert len(set(y.tolist())) == case["widths"][-1]
+    others = np.setdiff1d(np.arange(len(y)), planted)
+    assert np.array_equal(y_cls[others], y[others])
+    for s in range(case["steps"]):
+        rows = case["order"][s * batch:(s + 1) * batch]
+        assert np.array_equal(np.flatnonzero(np.isin(rows, planted)), [1, batch // 2, batch - 1])
+        assert y_cls[rows[[1, batch // 2, batch - 1]]].tolist() == [-1, case["widths"][-1], 2 ** 31 - 1]
+    kw = dict(activation=case["activation"], optimizer=case["optimizer"], lr=case["lr"])
+    state = tc.ref_state(case)
+    for s in range(case["steps"]):
+        rows = case["order"][s * batch:(s + 1) * batch]
+        only = rows[np.isin(rows, planted)]
+        probe = train_ref.copy.deepcopy(state)
+        loss, right, _ = train_ref.step(probe, case["x"][only].astype(np.float64), y_cls[only], **kw)
+        assert loss == 0.0 and right == 0, s
+        train_ref.step(state, case["x"][rows].astype(np.float64), y_cls[rows], **kw)
+    got, want = tc.ref_tensors(case, state), tc.expected(case, "cls64:", "clsopt64:")
+    assert set(got) == set(want) and all(np.abs(got[k] - want[k]).max() <= 1e-12 for k in want)
+    plain = tc.expected(case)
+    assert max(np.abs(want[k] - plain[k]).max() / np.abs(plain[k]).max() for k in want if "running" not in k) > 1e-3      # and it matters
 
 
 def test_state_dict_checkpoint_and_model_round_trip(tmp_path):

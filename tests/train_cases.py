@@ -12,7 +12,10 @@ from tests import train_ref
 GOLDEN = Path(__file__).resolve().parent / "golden"
 CASES = ("default_relu_rmsprop", "default_tanh_rmsprop", "default_sigmoid_rmsprop", "default_relu_adam", "default_tanh_adam",
          "w_1_1_2", "w_3_8_2", "w_4_32_7_3", "six_by_32", "w_7_8_9", "batch_2", "batch_63", "batch_64", "batch_65", "batch_256",
-         "ragged_2", "ragged_127", "batch_2_bn", "ragged_2_bn")
+         "ragged_2", "ragged_127", "batch_2_bn", "ragged_2_bn", "default_sigmoid_adam", "mask_5", "mask_2", "mask_6", "mask_9",
+         "small_relu_2")
+DROP_CASES = ("default_relu_rmsprop", "default_sigmoid_adam", "mask_5", "mask_2", "mask_6", "mask_9", "small_relu_2")   # hold drop64:
+CLASS_CASES = ("small_relu_2",)                                                                                        # hold cls64:
 SLOTS = {"rmsprop": ("square_avg",), "adam": ("exp_avg", "exp_avg_sq")}
 
 
@@ -87,6 +90,6 @@ def worst_ratio(case, got: dict, want: dict, cmp_prefix="cmp:") -> tuple:
         mask = np.ones(w.shape, dtype=bool) if mask is None else mask
         bound = 4.0 * max(float(case[f"err32:{key}"]), 2.0 ** -24 * float(np.abs(w).max()))
         diff = np.abs(np.asarray(got[key], dtype=np.float64) - w)[mask]
-        if diff.size:
-            worst = max(worst, (float(diff.max()) / bound, key))
+        if diff.size and (worst[1] is None or float(diff.max()) / bound > worst[0]):
+            worst = (float(diff.max()) / bound, key)
     return worst

@@ -82,7 +82,8 @@ def _update(optimizer, lr, t, w, g, slots):
 
 def step(state, x, y, *, activation, optimizer, lr, masks=None, keep_scale=1.0):
     """One step on the batch (x (rows, inputs) float64, y (rows,) int), in place.  Returns ``(summed row losses, rows whose
-    argmax p is y, gradients)``, the gradients as a dict like a slot."""
+    argmax p is y, gradients)``, the gradients as a dict like a slot.  A row whose y lies outside the classes matches none of
+    them (include/amcx.h; the reference has no such rule): no loss, never right, and dp = q / rows."""
     act, act_grad = _ACT[activation], _ACT_GRAD[activation]
     n_linear, rows = len(state["W"]), x.shape[0]
     keep_scale = float(keep_scale)
@@ -105,10 +106,15 @@ def step(state, x, y, *, activation, optimizer, lr, masks=None, keep_scale=1.0):
     inputs.append(a)
     p = softmax(a @ state["W"][-1].T + state["b"][-1])
     q = softmax(p)                                              # the reference's CrossEntropyLoss on the softmax OUTPUT
+    # include/amcx.h: "a class outside 0 ... classes - 1 matches no class" -- the row's one-hot is all zero (dp = q / rows), its
+    # loss term is 0 and it is never counted right.  (The header's rule alone: torch raises on such a label.)
+    y = np.asarray(y, dtype=np.int64)
+    inside = (y >= 0) & (y < p.shape[1])
+    at = np.flatnonzero(inside)
     onehot = np.zeros_like(p)
-    onehot[np.arange(rows), y] = 1.0
-    loss = float(-np.log(q[np.arange(rows), y]).sum())
-    correct = int((p.argmax(axis=1) == y).sum())
+    onehot[at, y[at]] = 1.0
+    loss = float(-np.log(q[at, y[at]]).sum())
+    correct = int((p.argmax(axis=1)[at] == y[at]).sum())
     dp = (q - onehot) / rows
     dz = p * (dp - (p * dp).sum(axis=1, keepdims=True))
     grads = {k: [None] * len(state[k]) for k in ("W", "b", "gamma", "beta")}
