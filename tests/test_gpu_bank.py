@@ -54,6 +54,30 @@ def test_criterion_against_float64(Cn, T, D, fmt):
     assert r <= 1.0, (fmt, Cn, T, D, r)
 
 
+@pytest.mark.parametrize("Cn,T,channels", [(4, 8, None), (256, 512, (0, 1, 86, 255))])
+def test_criterion_against_float64_over_three_trips_of_the_grid(Cn, T, channels):
+    """M = tile (2 grid + 1) + 3 at D = 1, the pre-mixer at an ODD step (the exact-arithmetic tests of this size,
+    tests/test_gpu_chain_exact.py, stand at quarter turns, which a phase taken from another tile of the same workgroup would
+    pass: grid tile D is a multiple of 4): every output of the channels against float64 (all four at C = 4; four of the 256,
+    the reference being what takes the time)."""
+    torch = _torch()
+    D = 1
+    tile, grid, _ = _lib.filter_bank_plan(T, Cn, D)
+    M = tile * (2 * grid + 1) + 3
+    tiles = -(-M // tile)
+    S = (M - 1) * D + T
+    print(f"bank criterion C={Cn} T={T} D={D}: {M} outputs = {tiles} tiles of {tile} over {grid} workgroups")
+    assert tiles >= 2 * grid + 1 and bank.out_samples(S, T, Cn, D) == M
+    host = stream_inputs.stream("cf32", S, np.random.default_rng(4700 + Cn))
+    y = _run(torch.from_numpy(host).cuda(), T, Cn, D, shift=STEP, sample_index0=INDEX0)
+    assert y.shape == (Cn, M)
+    y64, s = bank_ref.reference(host.astype(np.complex128), ddc_ref.make_taps(T), Cn, D, _phase0(), ddc_ref.ODD_STEP, INDEX0,
+                                channels=channels)
+    r = bank_ref.worst_ratio(y if channels is None else y[list(channels)], y64, s, T, Cn)
+    print(f"bank criterion C={Cn} T={T} D={D} over three trips: worst |err| / bound = {r:.4f}")
+    assert r <= 1.0
+
+
 @pytest.mark.parametrize("Cn", [2, 4, 8, 16, 32, 64, 128, 256])
 def test_every_channel_every_branch(Cn):
     """One non-zero sample at each position of a window in turn (T = 2 C: both taps of every branch), batched as one stream

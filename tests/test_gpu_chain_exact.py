@@ -157,3 +157,89 @@ def test_filter_bank_transform_alone(Cn, T, D):
             _assert_exact(y[0], total, g, f"bank channel 0 {fmt} C={Cn} T={T} D={D} shift={shift}")
     print(f"bank transform alone C={Cn} T={T} D={D} tile={tile} lds={lds} M={M} S={S}: worst |err| / (7 log2 C 2^-24 S) = "
           f"{worst:.4f} (factor {factor}); channel 0 exact")
+
+
+# ---- the bank's tile loop beyond one pass of its grid --------------------------------------------------------------------------
+def _bank_three_trips(Cn, T, D):
+    """(tile, grid, M, S): M = tile (2 grid + 1) + 3 outputs, so that some workgroup takes three tiles and the last is ragged"""
+    tile, grid, _ = _lib.filter_bank_plan(T, Cn, D)
+    assert tile == 4096 // Cn
+    M = tile * (2 * grid + 1) + 3
+    tiles = -(-M // tile)
+    print(f"bank C={Cn} T={T} D={D}: {M} outputs = {tiles} tiles of {tile} over {grid} workgroups")
+    assert tiles >= 2 * grid + 1
+    S = ce.ddc_span(M, T, D)
+    assert bank.out_samples(S, T, Cn, D) == M
+    return tile, grid, M, S
+
+
+def _branch_sums_blocked(v, h, Cn, D, M, index0, block=4096):
+    """ce.bank_branch_sums over M outputs in blocks of outputs (its gather is sized for a few thousand): output m0 + i of the
+    stream is output i of the stream from sample m0 D on, whose first sample has the index index0 + m0 D"""
+    parts = [ce.bank_branch_sums((v[0][m0 * D:], v[1][m0 * D:]), h, Cn, D, min(block, M - m0), index0 + m0 * D)
+             for m0 in range(0, M, block)]
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+def _same_bytes(a, b):
+    torch = _torch()
+    return a.shape == b.shape and bool(torch.equal(torch.view_as_real(a).view(torch.int32), torch.view_as_real(b).view(torch.int32)))
+
+
+def _sc16_and_its_widened_samples(S, seed):
+    """the sc16 stream of _ints and the complex64 stream of the same values k 2^-7, both in GPU memory"""
+    torch = _torch()
+    k = _ints(S, seed)
+    wide = ((k[:, 0] + 1j * k[:, 1]) * ce.UNIT["sc16"]).astype(np.complex64)
+    return torch.from_numpy(ce.encode(k, "sc16")).cuda(), torch.from_numpy(wide).cuda()
+
+
+def test_filter_bank_transform_alone_over_three_trips_of_the_grid():
+    """C = 256: tiles of 16 outputs, 2 grid + 1 of them and 3 outputs more.  The derived factor of
+    test_filter_bank_transform_alone on EVERY output, channel 0 exact; sc16 the bytes of complex64 on the widened samples."""
+    torch = _torch()
+    Cn, T, D = 256, 512, 1
+    tile, grid, M, S = _bank_three_trips(Cn, T, D)
+    h = ce.make_taps(T)
+    taps = _taps_dev(h)
+    shift, index0 = ce.BANK_QUARTER_TURNS[1]
+    assert index0 % 2 == 1 and shift != 0
+    k = _ints(S, T + Cn)
+    factor = 7 * bank_ref.log2_exact(Cn)
+    sabs = ce.abs_sums(k, h, D, M)
+    assert sabs.shape == (M,) and sabs.min() > 0
+    u = _branch_sums_blocked(ce.mix(k, shift, index0), h, Cn, D, M, index0)
+    want = ce.bank_float64(u, Cn)
+    y = bank.filter_bank(torch.from_numpy(ce.encode(k, "cf32")).cuda(), taps, Cn, D, shift=shift, sample_index0=index0)
+    torch.cuda.synchronize()
+    assert y.shape == (Cn, M) and y.dtype == torch.complex64
+    ratio = np.abs(y.cpu().numpy().astype(np.complex128) - want) / (factor * ce.U * sabs)[None, :]
+    at = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    print(f"bank transform alone C={Cn} T={T} D={D} over three trips: worst |err| / (7 log2 C 2^-24 S) = {float(ratio[at]):.4f} "
+          f"at {tuple(int(i) for i in at)}")
+    assert ratio[at] <= 1.0, (at, float(ratio[at]))
+    _assert_exact(y[0], (u[0].sum(axis=1), u[1].sum(axis=1)), 1.0, f"bank channel 0 cf32 C={Cn} T={T} D={D} over three trips")
+    raw, wide = _sc16_and_its_widened_samples(S, T + Cn)
+    assert _same_bytes(bank.filter_bank(raw, taps, Cn, D, shift=shift, sample_index0=index0),
+                       bank.filter_bank(wide, taps, Cn, D, shift=shift, sample_index0=index0))
+
+
+def test_filter_bank_exact_over_three_trips_of_the_grid():
+    """C = 4: tiles of 1024 outputs, 2 grid + 1 of them and 3 outputs more, every output == int64 arithmetic; sc16 the bytes
+    of complex64 on the widened samples."""
+    torch = _torch()
+    Cn, T, D = 4, 8, 1
+    tile, grid, M, S = _bank_three_trips(Cn, T, D)
+    h = ce.make_taps(T)
+    taps = _taps_dev(h)
+    shift, index0 = ce.BANK_QUARTER_TURNS[1]
+    k = _ints(S, T + Cn)
+    exact = ce.bank_exact(ce.bank_branch_sums(ce.mix(k, shift, index0), h, Cn, D, M, index0), Cn)
+    y = bank.filter_bank(torch.from_numpy(ce.encode(k, "cf32")).cuda(), taps, Cn, D, shift=shift, sample_index0=index0)
+    torch.cuda.synchronize()
+    assert y.shape == (Cn, M) and y.dtype == torch.complex64
+    _assert_exact(y, exact, 1.0, f"bank cf32 C={Cn} T={T} D={D} shift={shift} index0={index0} over three trips")
+    raw, wide = _sc16_and_its_widened_samples(S, T + Cn)
+    got = bank.filter_bank(raw, taps, Cn, D, shift=shift, sample_index0=index0)
+    assert _same_bytes(got, bank.filter_bank(wide, taps, Cn, D, shift=shift, sample_index0=index0))
+    _assert_exact(got, exact, ce.UNIT["sc16"], f"bank sc16 C={Cn} T={T} D={D} over three trips")

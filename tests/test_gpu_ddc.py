@@ -73,6 +73,32 @@ def test_parity_beyond_one_pass_of_the_grid():
     assert y.shape == (M,) and r <= 1.0
 
 
+@pytest.mark.parametrize("fmt", ["cf32", "sc16", "ci8"])
+def test_parity_over_three_trips_of_the_grid(fmt):
+    """2 grid + 1 tiles and one output more, per loader (each is a kernel with its own copy of the tile loop): (2048, 4096)
+    has tiles of two outputs and the smallest grid.  The criterion for EVERY output, and the bytes of the same outputs made in
+    calls of at most one trip (the stream from output m0 on, its first sample's index m0 D)."""
+    torch = _torch()
+    T, D = 2048, 4096
+    tile, grid = _lib.tune_decimate_plan(T, D)
+    M = tile * (2 * grid + 1) + 1
+    tiles = -(-M // tile)
+    S = (M - 1) * D + T
+    assert tiles >= 2 * grid + 1 and ddc.out_samples(S, T, D) == M
+    host = stream_inputs.stream(fmt, S, np.random.default_rng(3100 + FORMATS.index(fmt)))
+    x = torch.from_numpy(host).cuda()
+    y = _run(x, T, D, shift=STEP)
+    y64, s = ddc_ref.reference(ddc_ref.widen(host, fmt, _formats.get(fmt).scale), ddc_ref.make_taps(T), D, 0, ddc_ref.ODD_STEP)
+    r = ddc_ref.worst_ratio(y, y64, s, T)
+    print(f"ddc {fmt} over three trips: {M} outputs, {tiles} tiles of {tile} over {grid} workgroups: worst ratio {r:.4f}")
+    assert y.shape == (M,) and r <= 1.0
+    per = tile * grid
+    parts = [ddc.tune_decimate(x[m0 * D:(min(m0 + per, M) - 1) * D + T], _taps_dev(T), D, shift=STEP, sample_index0=m0 * D)
+             for m0 in range(0, M, per)]
+    torch.cuda.synchronize()
+    assert all(p.shape[0] <= per for p in parts) and torch.cat(parts).cpu().numpy().tobytes() == y.tobytes()
+
+
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_zero_phase_one_tap_is_the_widened_input(fmt):
     torch = _torch()

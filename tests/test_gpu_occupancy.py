@@ -174,6 +174,22 @@ def _special(Cn, K, seed):
     return p
 
 
+@pytest.mark.parametrize("Cn", [2, 256])
+def test_detect_exact_over_three_trips_of_the_floor_grid(Cn):
+    """The floor launch walks tiles of 64 frames with 4 workgroups per CU at C = 2 and 2 at C = 256 (67 584 bytes of LDS: this
+    restates amcx_occupancy_detect_f32 in amcx.hip, wgs_per_cu(lds, 4) of 160 KiB); 2 grid + 1 tiles and one frame more.  At
+    C = 256 the count and scatter launches (4 per CU, blocks of 256 cells) pass 2 grid + 1 blocks as well."""
+    per_cu = 4 if Cn == 2 else 2
+    grid = per_cu * _torch().cuda.get_device_properties(0).multi_processor_count
+    K = 64 * (2 * grid + 1) + 1
+    tiles = -(-K // 64)
+    print(f"occupancy floor C={Cn}: {K} frames = {tiles} tiles of 64 over {grid} workgroups; {-(-Cn * K // 256)} blocks of 256 cells")
+    assert tiles >= 2 * grid + 1
+    thr = occupancy.threshold_of(6.0)
+    n = _check_detect(_special(Cn, K, 5 + Cn), occupancy.floor_rank_of(Cn, 0.25), thr, ("special, three trips", Cn, K))
+    assert 0 < n < Cn * K
+
+
 @pytest.mark.parametrize("Cn", [2, 3, 8, 64, 255, 256])
 def test_detect_exact(Cn):
     thr = occupancy.threshold_of(6.0)
@@ -295,6 +311,62 @@ def test_gather(N):
     t.cuda.synchronize()
     assert got.cpu().numpy().tobytes() == x[many].tobytes()
     assert _gather_raw(x, N, np.empty((0,), np.int32), N).size == 2
+
+
+OCC_WAVES = 4                                     # kOccWaves of amcx_occupancy_kernels.h: rows (indices) a workgroup takes per trip
+
+
+def _occ_grid():
+    """Workgroups of the row-power and gather launches: this restates their call sites in amcx.hip (8 per CU, OCC_WAVES rows
+    per workgroup and trip); there is no plan entry for them."""
+    return 8 * _torch().cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.mark.parametrize("N", [2, 127])
+def test_gather_over_three_trips_of_the_grid(N):
+    """2 grid + 2 workgroups' worth of indices (the last with one of its four): every wave goes round its loop three times.
+    Out-of-range indices stand in the second and the third trip, between rows that are copied."""
+    grid = _occ_grid()
+    per_trip = grid * OCC_WAVES
+    n = 2 * per_trip + 5
+    units = -(-n // OCC_WAVES)
+    print(f"gather N={N}: {n} indices = {units} workgroups' worth over {grid} workgroups")
+    assert units >= 2 * grid + 1
+    rng = np.random.default_rng(N)
+    R = 37
+    x = _frames(R, N, N + 2)
+    index = rng.integers(0, R, n).astype(np.int64)
+    planted = {per_trip + 1: -1, per_trip + 6: R, 2 * per_trip - 3: -2 ** 31, 2 * per_trip + 1: R, 2 * per_trip + 4: -1}
+    for at, v in planted.items():
+        index[at] = v
+    bad = (index < 0) | (index >= R)
+    assert int(bad.sum()) == len(planted)
+    for src_stride, dst_stride in ((N + 1, N + 2), (N, N + 1)):
+        got = _gather_raw(x, src_stride, index, dst_stride)
+        body = got[:n * dst_stride].reshape(n, dst_stride)
+        assert body[~bad, :N].tobytes() == x[index[~bad]].tobytes(), (N, src_stride, dst_stride)
+        assert np.all(np.isnan(body[bad, :N].real)) and np.all(np.isnan(body[bad, :N].imag))
+        assert np.all(body[:, N:] == complex(-3.0, 5.0)) and np.all(got[n * dst_stride:] == complex(-3.0, 5.0))           # the gaps
+
+
+def test_power_criterion_over_three_trips_of_the_grid():
+    """Every wave of the row-power grid takes three rows, of N = 129 (the odd sample's lane) at a stride that puts every
+    other row on 8 bytes: the criterion for EVERY row, and the bytes of the same rows in calls of one trip."""
+    t = _torch()
+    grid = _occ_grid()
+    R, N = 2 * grid * OCC_WAVES + 5, 129
+    units = -(-R // OCC_WAVES)
+    print(f"row power N={N}: {R} rows = {units} workgroups' worth over {grid} workgroups")
+    assert units >= 2 * grid + 1
+    x = _frames(R, N, 12)
+    p = _power(x)
+    r = ref.worst_ratio(p, ref.power64(x), N)
+    print(f"row power {R} x {N}: worst |err| / bound = {r:.4f}")
+    assert p.shape == (R,) and r <= 1.0
+    xd = t.from_numpy(x).cuda()
+    parts = [occupancy.row_power(xd[a:a + 4096]) for a in range(0, R, 4096)]
+    t.cuda.synchronize()
+    assert t.cat(parts).cpu().numpy().tobytes() == p.tobytes()
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------

@@ -290,3 +290,110 @@ def test_spectrogram_and_detect_replay_in_a_graph():
         t.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), eager[seed][0])
         assert np.array_equal(det.floor.cpu().numpy(), eager[seed][1]) and np.array_equal(det.mask.cpu().numpy(), eager[seed][2])
+
+
+# ---- the persistent loops' second and third trips ----------------------------------------------------------------------------
+# Every case below gives its launch at least 2 * grid + 1 units of work, the grid read from the library, so that some workgroup
+# goes round its grid-stride loop three times and the last trip is ragged: the loop's tail barrier, the state re-derived per
+# trip (live, acc[], row words) and `unit * stride` at large indices all run.
+
+def _float32_rows_blocked(x, w, nfft, hop, A, R, block=8192):
+    """ref.float32_rows over R rows in blocks of rows, to bound memory."""
+    out = np.empty((R, nfft), np.float32)
+    step, span = A * hop, (A - 1) * hop + nfft
+    for r in range(0, R, block):
+        n = min(block, R - r)
+        out[r:r + n] = ref.float32_rows(x[r * step:(r + n - 1) * step + span], w, nfft, hop, A)
+    return out
+
+
+def _passes(R, nfft, hop, A, what):
+    """(passes, grid) of a spectrogram of R rows, asserted to be three trips for some workgroup, and printed."""
+    G, _, grid = _lib.spectrogram_plan(nfft, hop, A)
+    passes = -(-R // G)
+    print(f"spectrogram {what}: {R} rows = {passes} passes of {G} over {grid} workgroups")
+    assert passes >= 2 * grid + 1
+    return passes, grid
+
+
+@pytest.mark.parametrize("nfft,A", [(64, 1), (64, 2), (4096, 1)])
+def test_rows_equal_the_float32_restatement_over_three_trips_of_the_grid(nfft, A):
+    """hop = 1: a row costs A samples.  nfft = 64: 2 g + 1 passes of 64 slots, the last with 3 live (A = 1) or 5 (A = 2, the
+    accumulators re-seeded between trips); nfft = 4096: one row per pass, 2 g + 1 rows."""
+    G, _, g = _lib.spectrogram_plan(nfft, 1, A)
+    R = G * (2 * g + 1) + 3 if (nfft, A) == (64, 1) else G * 2 * g + (5 if G > 1 else 1)
+    _passes(R, nfft, 1, A, f"nfft={nfft} A={A}")
+    w = psd.window(nfft, "hann")
+    x = ref.spread_signal(_samples_for(R, nfft, 1, A), nfft, 33 * nfft + A)
+    P = _run(x, nfft, hop=1, averages=A, window=w)
+    assert P.shape == (R, nfft)
+    assert np.array_equal(P, _float32_rows_blocked(x, w, nfft, 1, A, R))
+
+
+@pytest.mark.parametrize("fmt", ["sc16", "ci8"])
+def test_integer_formats_are_the_complex64_bits_over_three_trips_of_the_grid(fmt):
+    """Each loader is a kernel of its own with its own copy of the pass loop."""
+    nfft = 64
+    G, _, g = _lib.spectrogram_plan(nfft, 1, 1)
+    R = G * (2 * g + 1) + 3
+    _passes(R, nfft, 1, 1, f"{fmt} nfft={nfft}")
+    w = psd.window(nfft, "hann")
+    raw = _raw(_samples_for(R, nfft, 1, 1), fmt, 33)
+    scale = ref.DEFAULT_SCALE[fmt] * 1.25
+    wide = ddc_ref.widen(raw, fmt, scale).astype(np.complex64)
+    got = _run(raw, nfft, hop=1, averages=1, window=w, scale=scale)
+    assert got.shape == (R, nfft) and np.array_equal(got, _run(wide, nfft, hop=1, averages=1, window=w))
+
+
+def test_padding_is_untouched_over_three_trips_of_the_grid():
+    """r * stride at large r: rows of nfft + 5 floats, the 5 a sentinel before and after."""
+    t = _torch()
+    nfft = 64
+    G, _, g = _lib.spectrogram_plan(nfft, 1, 1)
+    R = G * (2 * g + 1) + 3
+    _passes(R, nfft, 1, 1, f"padded nfft={nfft}")
+    w = psd.window(nfft, "hann")
+    xd = t.from_numpy(ref.spread_signal(_samples_for(R, nfft, 1, 1), nfft, 34)).cuda()
+    base = psd.spectrogram(xd, nfft, hop=1, averages=1, window=w)
+    out = t.full((R + 1, nfft + 5), SENTINEL, dtype=t.float32, device="cuda")
+    got = psd.spectrogram(xd, nfft, hop=1, averages=1, window=w, out=out[:R])
+    t.cuda.synchronize()
+    assert t.equal(got, base) and t.equal(out[:R, :nfft], base)
+    assert bool((out[:, nfft:] == SENTINEL).all()) and bool((out[R] == SENTINEL).all())
+
+
+@pytest.mark.parametrize("bins", [2, 65, 1000])
+def test_detect_equals_numpy_over_three_trips_of_the_grid(bins):
+    """One row per trip.  The grid restates the call site of amcx_psd_detect_f32 in amcx.hip (8 workgroups per CU): there is
+    no plan entry for it.  The rows tile _detect_rows' nine kinds (random, ties, all equal, NaN and inf rows), the tiling
+    shifted after every `grid` rows so that a workgroup's consecutive trips see different kinds."""
+    t = _torch()
+    lib = _lib.load()
+    grid = 8 * t.cuda.get_device_properties(0).multi_processor_count
+    R = 2 * grid + 5
+    print(f"psd detect bins={bins}: {R} rows over {grid} workgroups")
+    assert R >= 2 * grid + 1
+    nine = _detect_rows(9, bins, bins + 1)
+    shift = 1 if (grid + 1) % 9 else 2
+    kind = (np.arange(R) + shift * (np.arange(R) // grid)) % 9            # row r + grid is another kind than row r
+    assert np.all(kind[grid:] != kind[:-grid])
+    rng = np.random.default_rng(bins)
+    p = nine[kind]
+    plain = np.isin(kind, (0, 7, 8))                                      # the random rows: fresh values per row
+    p[plain] = (rng.standard_normal((int(plain.sum()), bins)) ** 2).astype(np.float32)
+    stride = bins + 3
+    pd = t.full((R, stride), SENTINEL, dtype=t.float32, device="cuda")
+    pd[:, :bins].copy_(t.from_numpy(p).cuda())
+    thr = occupancy.threshold_of(6.0)
+    for rank in sorted({0, bins // 2, bins - 1}):
+        floor = t.full((R + 1,), SENTINEL, dtype=t.float32, device="cuda")
+        mask = t.full((R * bins + 1,), 9, dtype=t.uint8, device="cuda")
+        _lib.check(lib.amcx_psd_detect_f32(pd.data_ptr(), R, bins, stride, rank, float(thr), floor.data_ptr(), mask.data_ptr(),
+                                           t.cuda.current_stream().cuda_stream))
+        t.cuda.synchronize()
+        f, m = ref.numpy_psd_detect(p, rank, thr)
+        fl, mk = floor.cpu().numpy(), mask.cpu().numpy()
+        assert np.array_equal(fl[:R], f, equal_nan=True), (bins, rank)
+        assert np.array_equal(mk[:R * bins].reshape(R, bins).astype(bool), m), (bins, rank)
+        assert fl[R] == SENTINEL and mk[R * bins] == 9
+    assert bool((pd[:, bins:] == SENTINEL).all())

@@ -164,6 +164,24 @@ def test_parity_beyond_one_pass_of_the_grid():
     assert y.shape == (M,) and r <= 1.0
 
 
+@pytest.mark.parametrize("fmt", ["cf32", "sc16", "ci8"])
+def test_parity_over_three_trips_of_the_grid(fmt):
+    """2 grid + 1 tiles and one output more, per loader (each is a kernel with its own copy of the tile loop): (4095, 7, 4096)
+    has tiles of nine outputs and the smallest grid.  The criterion for EVERY output."""
+    torch = _torch()
+    T, L, D, tau0 = 4095, 7, 4096, 3
+    tile, _, grid, _ = _lib.resample_plan(T, L, D)
+    S, M = _span(tile * (2 * grid + 1) + 1, T, L, D, tau0)
+    tiles = -(-M // tile)
+    assert tiles >= 2 * grid + 1
+    host = stream_inputs.stream(fmt, S, np.random.default_rng(3300 + FORMATS.index(fmt)))
+    y = _run(torch.from_numpy(host).cuda(), T, L, D, shift=STEP, phase_index0=tau0)
+    y64, s = ref.reference(ref.widen(host, fmt, _formats.get(fmt).scale), ref.make_taps(T), L, D, tau0, 0, ref.ODD_STEP)
+    r = ref.worst_ratio(y, y64, s, ref.phase_taps(T, L))
+    print(f"resample {fmt} over three trips: {M} outputs, {tiles} tiles of {tile} over {grid} workgroups: worst ratio {r:.4f}")
+    assert y.shape == (M,) and r <= 1.0
+
+
 def test_output_index_times_decim_beyond_32_bits():
     """m D passes 2^32 inside one call: the tiles' first inputs are 64-bit.  The reference of the last outputs is the
     definition's own continuation -- floor(m1 D / L) inputs dropped, tau0' = m1 D mod L, the phase advanced."""

@@ -55,7 +55,8 @@ def test_symbols_are_the_table_at_the_drawn_index(order):
     assert not np.array_equal(y[0], y[1])
 
 
-PULSES = [(1, 1, 1), (8, 1, 8), (2, 1, 33), (8, 3, 129), (256, 255, 4096), (3, 4096, 7)]
+# (8, 3, 3) and (8, 1, 5): T < U, phases with no tap (syn_pulse with cnt == 0)
+PULSES = [(1, 1, 1), (8, 1, 8), (2, 1, 33), (8, 3, 129), (256, 255, 4096), (3, 4096, 7), (8, 3, 3), (8, 1, 5)]
 
 
 @pytest.mark.parametrize("random_timing", [False, True])
@@ -92,7 +93,8 @@ def _check(y, seed, row0, n0, table, taps, U, V, sigmas, fpg=1, **kw):
     return worst
 
 
-@pytest.mark.parametrize("mod,U,V,T", [("16QAM", 8, 3, 129), ("QPSK", 2, 1, 33), ("WGN", 1, 1, 1), ("8PSK", 5, 7, 23)])
+@pytest.mark.parametrize("mod,U,V,T", [("16QAM", 8, 3, 129), ("QPSK", 2, 1, 33), ("WGN", 1, 1, 1), ("8PSK", 5, 7, 23),
+                                         ("QPSK", 8, 3, 5)])                # the last: T < U
 def test_carrier_and_noise_meet_the_criterion(mod, U, V, T):
     R, S, n0, row0 = 3, 1500, (1 << 39) + 1, (1 << 63) + 11
     table, taps = wf.constellation_table(mod), _taps(T)
@@ -104,6 +106,81 @@ def test_carrier_and_noise_meet_the_criterion(mod, U, V, T):
     print(f"synth {mod} U={U} V={V} T={T}: worst |err| / bound = {worst:.4f}")
     assert worst <= 1.0
     assert np.isfinite(y.view(np.float32)).all() and np.abs(y[:2]).max() > 0.1
+
+
+def _resampler_row(seed, r, n0, S, table, taps, U, V, tau):
+    """Samples n0 ... n0 + S - 1 of row r without carrier and noise, as the resampler makes them from the numpy-drawn symbols"""
+    torch = _torch()
+    P = -(-len(taps) // U)
+    s0, tau0 = divmod(n0 * V + tau, U)
+    n_sym = (P - 1) + ((S - 1) * V + tau0) // U + 1
+    a = ref.symbols(seed, r, np.arange(s0, s0 + n_sym), table).astype(np.complex64)
+    want = rs.resample(torch.from_numpy(a).cuda(), taps, U, V, phase_index0=tau0)
+    torch.cuda.synchronize()
+    assert want.shape[0] >= S
+    return want[:S].cpu().numpy()
+
+
+@pytest.mark.parametrize("U,tile", [(1, 1), (2, 2)])
+def test_tiles_of_one_and_two_samples(U, tile):
+    """(U, 4096, 4096) plans a tile of U samples: at one sample the pair's lone member is A where the absolute index is even
+    and B where it is odd.  Rows of 5 samples from an even and an odd first sample: against the resampler by bytes at
+    sigma = 0, against the reference by the criterion with carrier and noise."""
+    V, T = 4096, 4096
+    table, taps = wf.constellation_table("QPSK"), _taps(T)
+    assert _lib.synth_plan(len(table), T, U, V)[0] == tile
+    R, S, row0 = 2, 5, (1 << 32) - 1
+    sig = np.array([0.0, 0.7], np.float32)
+    worst = 0.0
+    for n0 in (6, 7):
+        y = _gen(table, R, S, sps=(U, V), taps=taps, seed=SEED, row_index0=row0, sample_index0=n0, random_phase=False)
+        for f in range(R):
+            tau = ref.row_params(SEED, row0 + f, U, flags=ref.RANDOM_TIMING)[2]
+            assert y[f].tobytes() == _resampler_row(SEED, row0 + f, n0, S, table, taps, U, V, tau).tobytes(), (U, n0, f)
+        y = _gen(table, R, S, sps=(U, V), taps=taps, sigma=sig, seed=SEED, row_index0=row0, sample_index0=n0, cfo=0.01,
+                 shift=wf.Fraction(ODD_STEP, 1 << 64))
+        worst = max(worst, _check(y, SEED, row0, n0, table, taps, U, V, sig, phase_step=ODD_STEP, cfo_max=wf.cfo_max_of(0.01)))
+        assert np.abs(y).min() > 0
+    print(f"synth tile of {tile}: worst |err| / bound = {worst:.4f}")
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("mod,U,V,T,per_row", [("16QAM", 3, 4096, 7, 3), ("QPSK", 8, 1, 8, 1)])
+def test_every_row_over_three_trips_of_the_grid(mod, U, V, T, per_row):
+    """At least 2 grid + 1 (row, tile) items, the grid as the plan reports it: some workgroup goes round its item loop three times,
+    re-deriving W, phase0, step, tau and sigma, and drawing the next item's symbols over what the last one's sums read.
+    (3, 4096, 7): tiles of 4 samples, rows of 2 tiles + 3, 4 workgroups per CU; the 8 / 1 rectangle: rows of one item, 8 per
+    CU.  Rows straddle 2^32, the first sample is odd, sigma is per group of 3 rows and mixes 0 with non-zero values.  EVERY
+    row meets the criterion, and the rows equal, as bytes, the same rows made in calls of 15 (one trip each)."""
+    torch = _torch()
+    table, taps = wf.constellation_table(mod), (_taps(T) if per_row > 1 else wf.design_rect(U))
+    tile, _, grid = _lib.synth_plan(len(table), T, U, V)
+    S = 2 * tile + 3 if per_row == 3 else 64
+    assert -(-S // tile) == per_row
+    R = -(-(2 * grid + 1) // per_row) + (2 if per_row > 1 else 4)
+    items = R * per_row
+    print(f"synth {mod} U={U} V={V} T={T}: {R} rows of {S} = {items} items of {tile} samples over {grid} workgroups")
+    assert items >= 2 * grid + 1
+    fpg, n0, row0, cfo = 3, 12345, (1 << 32) - R // 2, 0.01
+    sig = np.random.default_rng(U).choice(np.array([0.0, 0.0, 0.3, 1.0, 2.0], np.float32), -(-R // fpg))
+    assert (sig == 0).any() and (sig != 0).any()
+    dev = dict(taps=torch.from_numpy(taps).cuda(), sigma=torch.from_numpy(sig).cuda())
+    table_dev = torch.from_numpy(table).cuda()
+    kw = dict(sps=(U, V), seed=SEED, sample_index0=n0, cfo=cfo, shift=wf.Fraction(ODD_STEP, 1 << 64), frames_per_group=fpg)
+    y = _gen(table_dev, R, S, row_index0=row0, **dev, **kw)
+    assert y.shape == (R, S)
+    worst = 0.0
+    for f in range(R):
+        r = ref.generate(SEED, row0 + f, n0, S, table, taps, U, V, float(sig[f // fpg]), phase_step=ODD_STEP,
+                         cfo_max=wf.cfo_max_of(cfo))
+        ratio = ref.worst_ratio(y[f], r)
+        worst = max(worst, ratio)
+        assert ratio <= 1.0, (f, ratio)
+    print(f"synth {mod} U={U} V={V} T={T} over three trips: worst |err| / bound = {worst:.4f}")
+    parts = [wf.generate(table_dev, min(15, R - a), S, row_index0=row0 + a, taps=dev["taps"],
+                         sigma=dev["sigma"][a // fpg:(a + 14) // fpg + 1], **kw) for a in range(0, R, 15)]
+    torch.cuda.synchronize()
+    assert y.tobytes() == torch.cat(parts).cpu().numpy().tobytes()
 
 
 def test_integer_determined_special_cases_are_exact():
