@@ -14,6 +14,7 @@ LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
 ABI_VERSION = 16        # the version this binding was written against; any library >= it will do (include/amcx.h)
 ABI_MINOR = 2           # ... and, at that version, the additions it needs (AMCX_ABI_MINOR: 16.1 = training, 16.2 = the generator)
+ABI_PATCH = 1           # ... and, at that minor, the additions it needs (AMCX_ABI_PATCH: 16.2.1 = the fading channel)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -30,6 +31,8 @@ ACTIVATIONS = {"relu": ACT_RELU, "tanh": ACT_TANH, "sigmoid": ACT_SIGMOID}
 ACT_NONE = 3                                             # AMCX_ACT_NONE (ABI 16): amcx_mlp_range_f32 only
 OPT_RMSPROP, OPT_ADAM = 0, 1                             # AMCX_OPT_* (ABI 16.1)
 SYNTH_RANDOM_PHASE, SYNTH_RANDOM_TIMING = 1, 2           # AMCX_SYNTH_* (ABI 16.2)
+CHANNEL_RANDOM_PHASE = 1                                 # AMCX_CHANNEL_* (ABI 16.2.1)
+CHANNEL_MAX_PATHS, CHANNEL_MAX_SINUSOIDS, CHANNEL_MAX_DELAY = 16, 32, 1024
 
 
 class UploadStats(C.Structure):
@@ -146,6 +149,11 @@ SIGNATURES = {
     "amcx_synth_c64": (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _i32, C.c_uint64,
                                  C.c_uint32, C.c_uint32, _vp, _i64, _vp, _vp]),
     "amcx_kernel_name_synth": (C.c_char_p, []),
+    "amcx_abi_patch": (C.c_int, []),
+    "amcx_channel_plan": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "amcx_channel_c64": (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, C.c_uint32, C.c_uint32,
+                                   _vp, _i64, _vp, _i64, _vp]),
+    "amcx_kernel_name_channel": (C.c_char_p, []),
 }
 
 _lib = None
@@ -199,6 +207,8 @@ def load(skip_torch: bool = False) -> C.CDLL:
         raise ImportError(f"libamcx ABI {got} is older than the {ABI_VERSION} this binding needs")
     if got == ABI_VERSION and lib.amcx_abi_minor() < ABI_MINOR:
         raise ImportError(f"libamcx ABI {got}.{lib.amcx_abi_minor()} is older than the {ABI_VERSION}.{ABI_MINOR} this binding needs")
+    if got == ABI_VERSION and lib.amcx_abi_minor() == ABI_MINOR and lib.amcx_abi_patch() < ABI_PATCH:
+        raise ImportError(f"libamcx ABI {got}.{ABI_MINOR}.{lib.amcx_abi_patch()} is older than the {ABI_VERSION}.{ABI_MINOR}.{ABI_PATCH} this binding needs")
     _lib = lib
     return lib
 
@@ -337,6 +347,18 @@ def kernel_name_mlp_train(activation: str = "relu", optimizer: str = "rmsprop") 
 def kernel_name_synth() -> str:
     """amcx_kernel_name_synth: the kernel amcx_synth_c64 runs (host-only)."""
     return load().amcx_kernel_name_synth().decode()
+
+
+def kernel_name_channel() -> str:
+    """amcx_kernel_name_channel: the kernel amcx_channel_c64 runs (host-only)."""
+    return load().amcx_kernel_name_channel().decode()
+
+
+def channel_plan(n_paths: int, n_sinusoids: int, interp_log2: int, max_delay: int) -> tuple:
+    """amcx_channel_plan -> (outputs per tile, bytes of LDS) (host-only)."""
+    tile, lds = C.c_int32(0), C.c_int32(0)
+    check(load().amcx_channel_plan(int(n_paths), int(n_sinusoids), int(interp_log2), int(max_delay), C.byref(tile), C.byref(lds)))
+    return tile.value, lds.value
 
 
 def synth_plan(order: int, n_taps: int, up: int, down: int) -> tuple:

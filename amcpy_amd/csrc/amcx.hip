@@ -14,7 +14,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_synth_kernel.h"     // FIRST of all (ABI 16.2: it includes the training kernels' header and the down-converter's in front of its one kernel), ...
+#include "amcx_channel_kernel.h"   // FIRST of all (ABI 16.2.1: it includes the generator's header in front of its one kernel), then the generator's ...
+#include "amcx_synth_kernel.h"     // ... (ABI 16.2: it includes the training kernels' header and the down-converter's in front of its one kernel), ...
 #include "amcx_mlp_train_kernel.h" // ... (ABI 16.1: plain and explicitly instantiated kernels on amcx_mlp_shape.h alone), then the fixed-point ones ...
 #include "amcx_mlp_q15_kernel.h"   // ... (ABI 16: plain kernels on amcx_mlp_shape.h alone, which holds no kernel), then the spectrogram's ...
 #include "amcx_psd_kernel.h"       // ... it includes the occupancy and down-converter headers for their device helpers), ...
@@ -1698,5 +1699,90 @@ int amcx_synth_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, in
 }
 
 const char* amcx_kernel_name_synth(void) { return "amcx_synth_c64_kernel"; }
+
+}  // extern "C"
+
+// ---- ABI 16.2.1: the fading multipath channel (amcx_channel_kernel.h) -----------------------------------------------------------
+namespace {
+
+// the limits a shape has on its own (the plan's and the entry's first check)
+bool channel_shape_ok(int32_t n_paths, int32_t n_sinusoids, int32_t interp_log2, int32_t max_delay) {
+  return n_paths >= 1 && n_paths <= amcx::kChanMaxPaths && n_sinusoids >= 1 && n_sinusoids <= amcx::kChanMaxSinusoids &&
+         interp_log2 >= 0 && interp_log2 <= amcx::kChanMaxInterpLog2 && max_delay >= 0 && max_delay <= amcx::kChanMaxDelay;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amcx_abi_patch(void) { return AMCX_ABI_PATCH; }
+
+int amcx_channel_plan(int32_t n_paths, int32_t n_sinusoids, int32_t interp_log2, int32_t max_delay, int32_t* tile_outputs,
+                      int32_t* lds_bytes) {
+  if (!channel_shape_ok(n_paths, n_sinusoids, interp_log2, max_delay)) return AMCX_EINVAL;
+  if (tile_outputs != nullptr) *tile_outputs = amcx::chan_tile_outputs(n_paths, interp_log2);
+  if (lds_bytes != nullptr) *lds_bytes = (int32_t)amcx::chan_lds_bytes(n_paths, n_sinusoids, interp_log2, max_delay);
+  return AMCX_OK;
+}
+
+int amcx_channel_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, int64_t n_rows, int64_t row_samples,
+                     const void* in_c64_dev, int64_t in_row_stride, const void* paths_host, int32_t n_paths, int32_t n_sinusoids,
+                     int32_t interp_log2, uint32_t doppler_max, uint32_t flags, const float* sigma_dev, int64_t frames_per_group,
+                     void* out_c64_dev, int64_t out_row_stride, void* hip_stream) {
+  static_assert(sizeof(amcx::ChanPath) == 16, "the header's path record");
+  if (!channel_shape_ok(n_paths, n_sinusoids, interp_log2, 0) || paths_host == nullptr) return AMCX_EINVAL;
+  if ((flags & ~(uint32_t)AMCX_CHANNEL_RANDOM_PHASE) != 0u) return AMCX_EINVAL;
+  amcx::ChanArgs a = {};
+  memcpy(a.paths, paths_host, sizeof(amcx::ChanPath) * (size_t)n_paths);
+  int32_t H = 0;
+  for (int l = 0; l < n_paths; ++l) {
+    if (a.paths[l].delay < 0 || a.paths[l].delay > amcx::kChanMaxDelay) return AMCX_EINVAL;
+    if (a.paths[l].delay > H) H = a.paths[l].delay;
+  }
+  if (row_samples < 1 || sample_index0 < 0 || sample_index0 >= (int64_t(1) << 40) || row_samples >= (int64_t(1) << 40) ||
+      sample_index0 + row_samples >= (int64_t(1) << 40))
+    return AMCX_EINVAL;
+  if (n_rows < 0 || in_row_stride < row_samples + H || out_row_stride < row_samples || frames_per_group < 1 ||
+      (n_rows > 0 && (in_row_stride > (int64_t(1) << 58) / n_rows || out_row_stride > (int64_t(1) << 58) / n_rows)))
+    return AMCX_EINVAL;
+  a.tile = amcx::chan_tile_outputs(n_paths, interp_log2);
+  a.tiles_per_row = (row_samples + a.tile - 1) / a.tile;
+  if (n_rows > 0 && a.tiles_per_row > (int64_t)0x7fffffff / n_rows) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (!ptrs_ok({{in_c64_dev, 7u, true}, {out_c64_dev, 7u, true}, {sigma_dev, 3u, false}})) return AMCX_EINVAL;
+  // the kernel reads neighbours of the sample it writes: the two byte ranges must not meet
+  const uintptr_t in0 = reinterpret_cast<uintptr_t>(in_c64_dev), out0 = reinterpret_cast<uintptr_t>(out_c64_dev);
+  const uintptr_t in1 = in0 + 8u * (uintptr_t)((n_rows - 1) * in_row_stride + row_samples + H);
+  const uintptr_t out1 = out0 + 8u * (uintptr_t)((n_rows - 1) * out_row_stride + row_samples);
+  if (in0 < out1 && out0 < in1) return AMCX_EINVAL;
+  a.seed_lo = (unsigned)(seed & 0xffffffffull);
+  a.seed_hi = (unsigned)(seed >> 32);
+  a.row_index0 = row_index0;
+  a.sample_index0 = sample_index0;
+  a.n_rows = n_rows;
+  a.row_samples = row_samples;
+  a.in_stride = in_row_stride;
+  a.out_stride = out_row_stride;
+  a.in = static_cast<const float2*>(in_c64_dev);
+  a.L = n_paths;
+  a.S = n_sinusoids;
+  a.b = interp_log2;
+  a.H = H;
+  a.doppler_max = doppler_max;
+  a.flags = flags;
+  a.sigma = sigma_dev;
+  a.frames_per_group = frames_per_group;
+  a.out = static_cast<float2*>(out_c64_dev);
+  a.n_items = n_rows * a.tiles_per_row;
+  // a plain grid, one workgroup per (row, tile): lines of at most 2^16 workgroups, the last one cut by the kernel
+  const int64_t gx = a.n_items < 65536 ? a.n_items : 65536, gy = (a.n_items + gx - 1) / gx;
+  const size_t lds = amcx::chan_lds_bytes(n_paths, n_sinusoids, interp_log2, H);
+  const hipError_t e = amcx::launch(amcx::amcx_channel_c64_kernel, dim3((unsigned)gx, (unsigned)gy), amcx::kChanThreads, lds,
+                                    static_cast<hipStream_t>(hip_stream), a);
+  if (e != hipSuccess) return hip_fail(e, "channel kernel launch");
+  return AMCX_OK;
+}
+
+const char* amcx_kernel_name_channel(void) { return "amcx_channel_c64_kernel"; }
 
 }  // extern "C"

@@ -738,6 +738,7 @@ def _already_extracted(out_path: Path, key: str, shape, provenance: Optional[dic
         have = json.loads(_provenance_path(out_path).read_text())
         want = dict(provenance)
         have_ids, want_ids = have.pop("features", None), want.pop("features", None)
+        have.pop("channel", None)                           # how `synth --channel` made the IQ, not what the file was computed for
         covers = have_ids is None or (want_ids is not None and set(want_ids) <= set(have_ids))
         return have == want and covers
     except Exception:

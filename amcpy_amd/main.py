@@ -24,7 +24,7 @@ finds the emitters of a recording with no raster: the Welch spectrogram on the d
 bins joined into emitters (amcpy_amd/psd.py; sigmf.scan_sigmf), written into a .mat file and, with --annotate, into a copy of
 the meta file as annotations -- which `recording --annotation K --rational` reads back.
 `python -m amcpy_amd synth --root DIR [--mods M ...] [--sps U/V] [--pulse rrc|rect] [--beta B] [--span S] [--frames F] [--frame-size N]
-[--snr lo:hi:step] [--cfo X] [--seed S] [--features-only] [--device D]` makes the labelled data set on the GPU (amcpy_amd/waveform.py):
+[--snr lo:hi:step] [--cfo X] [--seed S] [--channel PROFILE --doppler F [--sinusoids S]] [--features-only] [--device D]` makes the labelled data set on the GPU (amcpy_amd/waveform.py):
 mat-data/all_modulations.mat as the reference expects it, or, --features-only, calculated-features/ directly.
 
 Several GPUs, ONE command (the reference's caller runs one command and the parallelism happens inside,
@@ -189,6 +189,10 @@ def build_parser() -> argparse.ArgumentParser:
     sy.add_argument("--snr", default=None, metavar="lo:hi:step", help="the SNR grid in dB, hi included (default: the configuration's 16)")
     sy.add_argument("--cfo", type=float, default=0.0, metavar="X", help="largest carrier offset, cycles per sample: a frame draws its own in [-X, X)")
     sy.add_argument("--seed", type=int, default=0)
+    sy.add_argument("--channel", default=None, metavar="PROFILE",
+                    help="fading multipath: rayleigh | rician:K_DB | exp:N:SPACING:DECAY_DB | tworay:DELAY:DB (amcpy_amd/channel.py)")
+    sy.add_argument("--doppler", type=float, default=0.0, metavar="F", help="maximum Doppler of --channel, cycles per sample")
+    sy.add_argument("--sinusoids", type=int, default=16, metavar="S", help="sinusoids per path of --channel (default 16)")
     sy.add_argument("--features-only", action="store_true",
                     help="write calculated-features/{mod}_features.mat directly; the IQ is made a chunk at a time and never stored")
     sy.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
@@ -211,14 +215,22 @@ def synth_config(args) -> tuple:
     return replace(cfg, signals=sig), snr
 
 
-def run_synth(args, compute=None, features=None) -> list:
-    """The `synth` command (amcpy_amd/waveform.py, run_synth); ``compute`` / ``features``: injected over numpy (tests)."""
+def run_synth(args, compute=None, features=None, channel_compute=None) -> list:
+    """The `synth` command (amcpy_amd/waveform.py, run_synth); ``compute`` / ``features`` / ``channel_compute``: injected over
+    numpy (tests)."""
     from . import waveform
     cfg, snr = synth_config(args)
     try:
+        fade = None
+        if args.channel is not None:
+            from .channel import parse_profile
+            fade = dict(profile=parse_profile(args.channel), doppler=args.doppler, sinusoids=args.sinusoids)
+            if channel_compute is not None:
+                fade["compute"] = channel_compute
         return waveform.run_synth(cfg, mods=args.mods, sps=waveform.parse_sps(args.sps), pulse=args.pulse, beta=args.beta, span=args.span,
                                   snr=snr, cfo=args.cfo, seed=args.seed, features_only=args.features_only,
-                                  device=None if args.device is None else f"cuda:{args.device}", compute=compute, features=features)
+                                  device=None if args.device is None else f"cuda:{args.device}", compute=compute, features=features,
+                                  channel=fade)
     except ValueError as e:
         raise SystemExit(f"synth: {e}")
 

@@ -245,8 +245,12 @@ def _walk(mods, snrs, F, N, chunk, first_frame, kw, shape, view, each=None) -> d
     """The one walk of a data set -> mod -> its buffer of ``shape``.  Per modulation the operands go to the device ONCE; then per SNR
     and chunk of at most ``chunk`` of the F frames (None: all, even none, at once) ONE launch makes the frames ``first_frame + f0 ...``
     into ``view(buf, s, n)`` and ``each(mod, s, f0, frames)`` sees them.  An injected ``compute`` walks the same way over numpy."""
+    kw = dict(kw)
+    fade = kw.pop("channel", None)
     U, _ = _shape(kw.get("sps", (8, 1)))
     dev = _device(kw.get("device")) if kw.get("compute") is None else None
+    H = _channel_history(fade)
+    clean = None if fade is None or dev is None else _empty((min(chunk or F, F), N + H), dev)   # the rows before the channel
     data = {}
     for mod in mods:
         table, taps, sig = _operands(mod, kw.get("taps"), U, snr_db=snrs, device=dev)
@@ -254,13 +258,49 @@ def _walk(mods, snrs, F, N, chunk, first_frame, kw, shape, view, each=None) -> d
         for s, snr in enumerate(snrs):
             for f0 in (range(0, F, chunk) if chunk else (0,)):
                 dst = view(buf, s, min(chunk or F, F - f0))
-                x = generate(table, dst.shape[0], N, sigma=sig[s:s + 1], row_index0=dataset_row(mod, snr, first_frame + f0),
-                             **dict(kw, taps=taps, device=dev, out=None if dev is None else dst))
+                row0 = dataset_row(mod, snr, first_frame + f0)
+                if fade is None:
+                    x = generate(table, dst.shape[0], N, sigma=sig[s:s + 1], row_index0=row0,
+                                 **dict(kw, taps=taps, device=dev, out=None if dev is None else dst))
+                else:
+                    x = _faded(fade, table, dst.shape[0], N, H, sig[s:s + 1], row0, dict(kw, taps=taps, device=dev),
+                               None if dev is None else clean[:dst.shape[0]], None if dev is None else dst)
                 if dev is None:
                     dst[...] = x
                 if each is not None:
                     each(mod, s, f0, dst)
     return data
+
+
+_CHANNEL_KEYS = ("profile", "doppler", "sinusoids", "interp_log2", "random_phase", "compute")
+
+
+def _channel_history(fade) -> int:
+    """H of a ``channel=dict(profile=..., doppler=..., ...)`` keyword (:func:`amcpy_amd.channel.apply`'s keywords); 0 for None."""
+    if fade is None:
+        return 0
+    if "profile" not in fade or set(fade) - set(_CHANNEL_KEYS):
+        raise ValueError(f"channel: a dict with profile and any of {_CHANNEL_KEYS[1:]}, got {sorted(fade)}")
+    return fade["profile"].history
+
+
+def _channel_record(fade) -> dict:
+    """What a provenance record says of the channel a data set went through: the profile (its name where a command named it),
+    the Doppler and the sinusoids."""
+    p = fade["profile"]
+    return {"profile": getattr(p, "spec", None), "delays": [int(d) for d in p.delays], "diffuse_gain": [float(g) for g in p.diffuse_gain],
+            "los_gain": [float(g) for g in p.los_gain], "los_doppler": [float(g) for g in p.los_doppler],
+            "doppler": float(fade.get("doppler", 0.0)), "sinusoids": int(fade.get("sinusoids", 16)),
+            "interp_log2": fade.get("interp_log2"), "random_phase": bool(fade.get("random_phase", True))}
+
+
+def _faded(fade, table, n, N, H, sigma, row0, kw, clean, dst):
+    """n rows of N samples through a channel: the clean rows ``(n, N + H)`` without noise (into ``clean`` on the device), then
+    :func:`amcpy_amd.channel.apply` (into ``dst``) with the same seed, the same absolute rows and the sigma -- so a faded row is
+    named by its absolute row exactly as a plain one is."""
+    from . import channel
+    x = generate(table, n, N + H, row_index0=row0, **dict(kw, out=clean))
+    return channel.apply(x, seed=kw.get("seed", 0), row_index0=row0, sigma=sigma, out=dst, **fade)
 
 
 def _empty(shape, device):
@@ -271,7 +311,10 @@ def _empty(shape, device):
 
 
 def dataset(mods, snr_db, n_frames: int, frame_size: int, *, first_frame: int = 0, **kw) -> dict:
-    """mod -> ``(n_snr, n_frames, frame_size)`` complex64, the reference's container layout.  Frame f of (mod, SNR) is row
+    """mod -> ``(n_snr, n_frames, frame_size)`` complex64, the reference's container layout.  ``channel=dict(profile=...,
+    doppler=..., ...)`` (:func:`amcpy_amd.channel.apply`'s keywords) takes every frame through a fading channel: each launch makes
+    the clean rows with the channel's history in front, without noise, and the channel's launch adds the noise; the seed and the
+    absolute rows are the same, so faded rows are as subset-stable as plain ones.  Frame f of (mod, SNR) is row
     :func:`dataset_row` ``(mod, snr, first_frame + f)``, so any subset names the same rows; the rows of two SNRs are 2^32 apart,
     which makes it one launch per (modulation, SNR), each into its slice of the modulation's array.  The table, the taps and
     the sigmas go to the device once per modulation; the launches upload nothing."""
@@ -330,7 +373,8 @@ def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device
     """A stream of ``n_samples`` with known emitters on a noise floor -> ``(x, annotations)``.
 
     emitters : dicts with ``mod``, ``sps`` (U, V), ``center`` (cycles per sample of the scene), and optionally ``rate`` (L, D)
-               (1, 1), ``start`` (0), ``length`` (to the end), ``amplitude`` (1), ``taps`` (default: :func:`design_rrc` over 16
+               (1, 1), ``start`` (0), ``length`` (to the end), ``amplitude`` (1), ``channel`` (a fading channel the emitter passes
+               at the scene's rate: :func:`dataset`'s keyword), ``taps`` (default: :func:`design_rrc` over 16
                symbols where U > V and it fits, else rect), ``beta`` (0.35).  Emitter e is row e of the seed; the floor is the
                noise class in row ``len(emitters)``.
     Each emitter is one :class:`Stream` row at its own U / V samples per symbol, brought to the scene's rate by
@@ -361,14 +405,19 @@ def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device
         if taps is None:
             taps = design_rrc(U, 16, beta) if rrc else design_rect(U)
         stream = Stream(em["mod"], row=e, sps=(U, V), taps=taps, seed=seed, device=dev)
+        fade = em.get("channel")
+        need = length + _channel_history(fade)                   # the channel's history in front of the emitter's first sample
         if (L, D) == (1, 1):
-            y = stream.push(length)
+            y = stream.push(need)
         else:
             low = design_resample_lowpass(L, D)
-            n_in = -(-length * D // L) + -(-len(low) // L) + 1
-            while out_samples(n_in, len(low), L, D) < length:
+            n_in = -(-need * D // L) + -(-len(low) // L) + 1
+            while out_samples(n_in, len(low), L, D) < need:
                 n_in += 1
-            y = resample(stream.push(n_in), low, L, D)[:length]
+            y = resample(stream.push(n_in), low, L, D)[:need]
+        if fade is not None:                                     # at the scene's rate, in front of the move to its centre
+            from . import channel
+            y = channel.apply(y.contiguous()[None, :], seed=seed, row_index0=e, **fade)[0]
         y = resample(y.contiguous(), one, 1, 1, shift=em["center"], sample_index0=start)
         x[start:start + length] += y * float(em.get("amplitude", 1.0))
         per_symbol = Fraction(U * L, V * D)
@@ -405,11 +454,13 @@ V5_LIMIT = (1 << 31) - 1      # bytes of one MATLAB v5 file's variables
 
 
 def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0.35, span: int = 16, snr=None, cfo=0.0,
-              seed: int = 0, features_only: bool = False, device=None, compute=None, features=None, verbose: bool = True) -> list:
+              seed: int = 0, features_only: bool = False, device=None, compute=None, features=None, verbose: bool = True,
+              channel=None) -> list:
     """The `synth` command: the data set of ``cfg`` (its frame size, frame count and SNR labels, unless ``snr`` names the
     grid) for ``mods`` (default ``cfg.signals.modulations_with_noise``) into ``mat-data/all_modulations.mat`` under the variables
     ``cfg.signals.mat_info`` names -- or, ``features_only``, straight into ``calculated-features/{mod}_features.mat`` with the
-    provenance record `extract --resume` trusts.  Returns the files written.  ``compute`` / ``features``: injected (tests)."""
+    provenance record `extract --resume` trusts.  ``channel``: :func:`dataset`'s keyword, a fading channel every frame passes; the
+    provenance record names it.  Returns the files written.  ``compute`` / ``features``: injected (tests)."""
     import scipy.io
 
     from .feature_extraction import _provenance, _provenance_path
@@ -429,6 +480,8 @@ def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0
     kw = dict(sps=(U, V), taps=taps, cfo=cfo, seed=seed, compute=compute)
     if compute is None:
         kw["device"] = device
+    if channel is not None:
+        kw["channel"] = channel
     cfg.paths.ensure_dirs()
     mat_path = cfg.paths.mat_data / cfg.paths.mat_filename
     if features_only:
@@ -437,7 +490,10 @@ def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0
             feats = dataset_features([m], snrs, F, N, features=features, **kw)[m]
             out_path = cfg.paths.calculated_features / f"{m}_features.mat"
             scipy.io.savemat(str(out_path), {"Modulation": m, sig.mat_info[m]: feats})
-            _provenance_path(out_path).write_text(json.dumps(_provenance(cfg, mat_path, sig.mat_info[m])) + "\n")
+            record = _provenance(cfg, mat_path, sig.mat_info[m])
+            if channel is not None:
+                record["channel"] = _channel_record(channel)
+            _provenance_path(out_path).write_text(json.dumps(record) + "\n")
             written.append(out_path)
             if verbose:
                 print(f"synth: {m}: features {feats.shape} -> {out_path}")

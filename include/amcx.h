@@ -100,10 +100,14 @@ extern "C" {
  * (all listed behind the define); 15 = the Welch spectrogram and its per-row detection; 16 = fixed-point deployment of the
  * classifier's network (range calibration and 16-bit integer inference).
  * AMCX_ABI_MINOR counts what has been ADDED since the version last changed -- new entries and constants, nothing existing changed:
- * 16.1 = training of the classifier's network, one workgroup per model; 16.2 = the waveform generator. */
+ * 16.1 = training of the classifier's network, one workgroup per model; 16.2 = the waveform generator.
+ * AMCX_ABI_PATCH counts in the same way what has been added since the minor last changed: 16.2.1 = the fading multipath channel. */
 #define AMCX_ABI_VERSION 16
 #define AMCX_ABI_MINOR 2
+#define AMCX_ABI_PATCH 1
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
+ *   ABI 16.2.1: AMCX_ABI_PATCH 1          -- the fading channel: AMCX_CHANNEL_*, amcx_channel_c64, amcx_channel_plan,
+ *                                            amcx_kernel_name_channel, amcx_abi_patch
  *   ABI 16.2: AMCX_ABI_MINOR 2            -- the waveform generator: AMCX_SYNTH_*, amcx_synth_c64, amcx_synth_plan,
  *                                            amcx_kernel_name_synth
  *   ABI 16.1: AMCX_ABI_MINOR 1            -- training: AMCX_OPT_*, amcx_mlp_train_f32, amcx_mlp_train_state_floats,
@@ -1099,6 +1103,69 @@ int amcx_synth_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, in
                    int32_t down, int32_t tau0, uint64_t phase_step, uint32_t cfo_max, uint32_t flags, const float* sigma_dev,
                    int64_t frames_per_group, void* out_c64_dev, void* hip_stream);
 const char* amcx_kernel_name_synth(void);
+
+/*
+ * ABI 16.2.1.  THE FADING MULTIPATH CHANNEL: n_rows rows of complex64, each through its own time-varying tapped delay line, in
+ * ONE launch on hip_stream (amcpy_amd/csrc/amcx_channel_kernel.h).  A path's gain is a sum-of-sinusoids Rayleigh process (Jakes
+ * Doppler spectrum) plus an optional line-of-sight term (Rician); optionally the launch adds the generator's white noise.  It
+ * allocates nothing, never synchronises and can be captured in a graph; no atomics, no workgroup waits for another.
+ * r = row_index0 + f is the ABSOLUTE row of the call's row f, n = sample_index0 + i the ABSOLUTE output sample of its sample i.
+ * L = n_paths, S = n_sinusoids, B = 2^interp_log2, H = the largest delay: the history.  A row of the input holds
+ * row_samples + H samples and output i reads input i + H - delay_l: the down-converter's convention.
+ *
+ *   path record      16 bytes, a HOST array of L, passed to the kernel by value (the host sees and checks every delay):
+ *                    int32 delay (samples), float diffuse_gain (of the sum of sinusoids), float los_gain (of the line of sight),
+ *                    int32 los_doppler_q31 (the line of sight's Doppler in 2^-31 of the Doppler unit)
+ *   key, counter     the generator's (ABI 16.2), with the new stream number 3
+ *   sinusoid (l, s)  X = Philox(counter(3, 32 l + s, r));  phase0_ls = (uint64)X[0] << 32
+ *                    c = the real part of the mixer's value at the angle X[1]: the cosine of a uniform arrival angle, its float32 bits
+ *                    ci = (int64)(c * 2^31)          the product is exact in float32, the conversion truncates toward zero
+ *                    step_ls = ci * doppler_max      in int64, used mod 2^64.  doppler_max (uint32): the maximum Doppler is
+ *                                                    doppler_max / 2^33 cycles per sample, the unit of cfo_max
+ *   line of sight l  XL = Philox(counter(3, 512 + l, r));  phase0 = flags & AMCX_CHANNEL_RANDOM_PHASE ? (uint64)XL[0] << 32 : 0
+ *                    step = (int64)los_doppler_q31 * doppler_max
+ *   node gains       at the absolute sample k B:
+ *                    d = sum over s = 0 ... S - 1, ascending, of mixer(top 32 bits of phase0_ls + k B step_ls): plain float32
+ *                        additions per component, from the s = 0 value
+ *                    w = the line of sight's mixer value at k B
+ *                    G_l[k] = fma(los_gain, w, diffuse_gain * d)                               per component
+ *   sample gain      k = n >> interp_log2,  f = (float)(n & (B - 1)) * 2^-interp_log2
+ *                    c_l[n] = fma(f, G_l[k + 1] - G_l[k], G_l[k])                              per component
+ *                    (interp_log2 = 0: the closed form at every sample)
+ *   output           x_l = in[f, i + H - delay_l];  paths in ascending l.  The first path:
+ *                      acc.re = fma(c.re, x.re, -(c.im x.im)),  acc.im = fma(c.re, x.im, c.im x.re)
+ *                    every later path, in this order:
+ *                      acc.re = fma(c.re, x.re, acc.re);  acc.re = fma(-c.im, x.im, acc.re)
+ *                      acc.im = fma(c.re, x.im, acc.im);  acc.im = fma(c.im, x.re, acc.im)
+ *                    out[f, i] = acc with the generator's noise added: its stream-2 words of (r, n), sigma_g =
+ *                    sigma_dev[f / frames_per_group] read on the device as the generator reads it; sigma_dev NULL: no noise
+ *
+ * POSITION INDEPENDENCE.  Nothing above depends on the call's cut, the tile, the grid, the lane or the strides: rows cut into
+ * calls, or a stream cut into chunks of any length (each with the H samples in front of it), equal one call bit for bit.
+ * Non-finite gains are not refused: they propagate.
+ *
+ *   - limits: 1 <= n_paths <= 16, 1 <= n_sinusoids <= 32, 0 <= interp_log2 <= 16, 0 <= delay <= 1024, no flag but the one;
+ *     1 <= row_samples, 0 <= sample_index0, sample_index0 + row_samples < 2^40; 0 <= n_rows, in_row_stride >= row_samples + H,
+ *     out_row_stride >= row_samples, n_rows times either stride <= 2^58; frames_per_group >= 1; at most 2^31 - 1 (row, tile) items
+ *   - checks, in the order of every launching entry: the limits (paths_host NULL among them); n_rows == 0 is AMCX_OK here and
+ *     writes nothing; then null pointers (in, out), alignment (in and out 8, sigma 4), a pointer on another device, and the
+ *     byte ranges of input and output, which must not overlap: the kernel reads neighbours of the sample it writes.
+ *     Ordinary vector stores only.
+ * The plan entry (host-only): outputs per tile and bytes of LDS for a shape; each pointer may be NULL.  The name entry
+ * (host-only): the kernel's name, a static string.  amcx_abi_patch: AMCX_ABI_PATCH of the library.
+ */
+#define AMCX_CHANNEL_RANDOM_PHASE 1u
+#define AMCX_CHANNEL_MAX_PATHS 16
+#define AMCX_CHANNEL_MAX_SINUSOIDS 32
+#define AMCX_CHANNEL_MAX_DELAY 1024
+int amcx_abi_patch(void);
+int amcx_channel_plan(int32_t n_paths, int32_t n_sinusoids, int32_t interp_log2, int32_t max_delay, int32_t* tile_outputs,
+                      int32_t* lds_bytes);
+int amcx_channel_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, int64_t n_rows, int64_t row_samples,
+                     const void* in_c64_dev, int64_t in_row_stride, const void* paths_host, int32_t n_paths, int32_t n_sinusoids,
+                     int32_t interp_log2, uint32_t doppler_max, uint32_t flags, const float* sigma_dev, int64_t frames_per_group,
+                     void* out_c64_dev, int64_t out_row_stride, void* hip_stream);
+const char* amcx_kernel_name_channel(void);
 
 #ifdef __cplusplus
 }
