@@ -14,7 +14,7 @@ LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
 ABI_VERSION = 16        # the version this binding was written against; any library >= it will do (include/amcx.h)
 ABI_MINOR = 2           # ... and, at that version, the additions it needs (AMCX_ABI_MINOR: 16.1 = training, 16.2 = the generator)
-ABI_PATCH = 1           # ... and, at that minor, the additions it needs (AMCX_ABI_PATCH: 16.2.1 = the fading channel)
+ABI_PATCH = 2           # ... and, at that minor, the additions it needs (AMCX_ABI_PATCH: 16.2.1 = the fading channel, 16.2.2 = continuous phase)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -154,6 +154,10 @@ SIGNATURES = {
     "amcx_channel_c64": (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, C.c_uint32, C.c_uint32,
                                    _vp, _i64, _vp, _i64, _vp]),
     "amcx_kernel_name_channel": (C.c_char_p, []),
+    "amcx_synth_cpm_plan": (C.c_int, [_i32, _i32, _i32, _i64, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "amcx_synth_cpm_c64": (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, C.c_uint32, _i32, _i32, _i32,
+                                     C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "amcx_kernel_name_synth_cpm": (C.c_char_p, []),
 }
 
 _lib = None
@@ -359,6 +363,19 @@ def channel_plan(n_paths: int, n_sinusoids: int, interp_log2: int, max_delay: in
     tile, lds = C.c_int32(0), C.c_int32(0)
     check(load().amcx_channel_plan(int(n_paths), int(n_sinusoids), int(interp_log2), int(max_delay), C.byref(tile), C.byref(lds)))
     return tile.value, lds.value
+
+
+def kernel_name_synth_cpm() -> str:
+    """amcx_kernel_name_synth_cpm: the kernel amcx_synth_cpm_c64 runs (host-only)."""
+    return load().amcx_kernel_name_synth_cpm().decode()
+
+
+def synth_cpm_plan(n_taps: int, up: int, down: int, n_rows: int, row_samples: int) -> tuple:
+    """amcx_synth_cpm_plan -> (samples per tile, bytes of LDS, segments a row is cut into) (host-only)."""
+    tile, lds, seg = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(load().amcx_synth_cpm_plan(int(n_taps), int(up), int(down), int(n_rows), int(row_samples), C.byref(tile), C.byref(lds),
+                                     C.byref(seg)))
+    return tile.value, lds.value, seg.value
 
 
 def synth_plan(order: int, n_taps: int, up: int, down: int) -> tuple:

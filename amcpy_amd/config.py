@@ -100,6 +100,20 @@ class SignalConfig:
     mat_info: Dict[str, str] = field(default_factory=lambda: dict(_MAT_VARS))
 
 
+def with_modulations(sig: "SignalConfig", mods) -> "SignalConfig":
+    """``sig`` for the classes ``mods`` (names, in label order; "WGN" among them or not): labels 0 ... len - 1, and a container
+    variable ``signal_<name in lower case>`` for every name the table does not know (the generator's "GMSK", "4FSK", ...)."""
+    from dataclasses import replace
+    mods = tuple(str(m) for m in mods)
+    if not mods or len(set(mods)) != len(mods):
+        raise ValueError(f"modulations: one or more names, each once, got {list(mods)}")
+    info = dict(sig.mat_info)
+    for m in mods:
+        info.setdefault(m, "signal_" + m.lower())
+    return replace(sig, modulations=tuple(m for m in mods if m != _NOISE), modulations_with_noise=mods,
+                   labels=tuple(range(len(mods))), mat_info=info)
+
+
 @dataclass(frozen=True)
 class FeatureConfig:
     """The 18 feature ids, their display names and the classifier's subset."""

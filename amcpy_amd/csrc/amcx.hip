@@ -14,7 +14,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_channel_kernel.h"   // FIRST of all (ABI 16.2.1: it includes the generator's header in front of its one kernel), then the generator's ...
+#include "amcx_synth_cpm_kernel.h" // FIRST of all (ABI 16.2.2: it includes the generator's header in front of its one kernel), then the channel's ...
+#include "amcx_channel_kernel.h"   // ... (ABI 16.2.1: it includes the generator's header in front of its one kernel), then the generator's ...
 #include "amcx_synth_kernel.h"     // ... (ABI 16.2: it includes the training kernels' header and the down-converter's in front of its one kernel), ...
 #include "amcx_mlp_train_kernel.h" // ... (ABI 16.1: plain and explicitly instantiated kernels on amcx_mlp_shape.h alone), then the fixed-point ones ...
 #include "amcx_mlp_q15_kernel.h"   // ... (ABI 16: plain kernels on amcx_mlp_shape.h alone, which holds no kernel), then the spectrogram's ...
@@ -1784,5 +1785,113 @@ int amcx_channel_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, 
 }
 
 const char* amcx_kernel_name_channel(void) { return "amcx_channel_c64_kernel"; }
+
+}  // extern "C"
+
+// ---- ABI 16.2.2: the continuous-phase generator (amcx_synth_cpm_kernel.h) -------------------------------------------------------
+namespace {
+
+struct CpmPlan {
+  int tile, segments;
+  int64_t tiles_per_row, tiles_per_seg;
+};
+
+// the tiles of a row and their cut into segments; `asked` 0: 1 where the rows alone fill the device, else about two workgroups per
+// CU, never more than the row's tiles or 64.  The segments are recounted from their length, so that none is empty.
+CpmPlan cpm_plan(int32_t n_taps, int32_t up, int32_t down, int64_t n_rows, int64_t row_samples, int32_t asked) {
+  CpmPlan p;
+  p.tile = amcx::syn_tile_outputs(n_taps, up, down);
+  p.tiles_per_row = (row_samples + p.tile - 1) / p.tile;
+  int64_t want = asked;
+  if (asked == 0) {
+    const int64_t target = 2 * (int64_t)cu_count();
+    want = n_rows < 1 || n_rows >= target ? 1 : (target + n_rows - 1) / n_rows;
+  }
+  if (want > amcx::kCpmMaxSegments) want = amcx::kCpmMaxSegments;
+  if (want > p.tiles_per_row) want = p.tiles_per_row;
+  p.tiles_per_seg = (p.tiles_per_row + want - 1) / want;
+  p.segments = (int)((p.tiles_per_row + p.tiles_per_seg - 1) / p.tiles_per_seg);
+  return p;
+}
+
+bool cpm_samples_ok(int64_t sample_index0, int64_t row_samples) {
+  return row_samples >= 1 && sample_index0 >= 0 && sample_index0 < (int64_t(1) << 40) && row_samples < (int64_t(1) << 40) &&
+         sample_index0 + row_samples < (int64_t(1) << 40);
+}
+
+}  // namespace
+
+extern "C" {
+
+int amcx_synth_cpm_plan(int32_t n_taps, int32_t up, int32_t down, int64_t n_rows, int64_t row_samples, int32_t* tile_outputs,
+                        int32_t* lds_bytes, int32_t* segments) {
+  if (!synth_shape_ok(2, n_taps, up, down) || !cpm_samples_ok(0, row_samples) || n_rows < 0) return AMCX_EINVAL;
+  const CpmPlan p = cpm_plan(n_taps, up, down, n_rows, row_samples, 0);
+  if (tile_outputs != nullptr) *tile_outputs = p.tile;
+  if (lds_bytes != nullptr) *lds_bytes = (int32_t)amcx::cpm_lds_bytes(n_taps, up, down);
+  if (segments != nullptr) *segments = p.segments;
+  return AMCX_OK;
+}
+
+int amcx_synth_cpm_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, int64_t n_rows, int64_t row_samples,
+                       int64_t row_stride, int32_t order, const uint32_t* phase_taps_dev, int32_t n_taps, uint32_t phase_full,
+                       int32_t up, int32_t down, int32_t tau0, uint64_t phase_step, uint32_t cfo_max, uint32_t flags,
+                       const float* sigma_dev, int64_t frames_per_group, const uint32_t* acc_in_dev, uint32_t* acc_out_dev,
+                       int32_t segments, void* out, void* hip_stream) {
+  if (order < 2 || !synth_shape_ok(order, n_taps, up, down)) return AMCX_EINVAL;
+  if (tau0 < 0 || tau0 >= up || (flags & ~(uint32_t)(AMCX_SYNTH_RANDOM_PHASE | AMCX_SYNTH_RANDOM_TIMING)) != 0u) return AMCX_EINVAL;
+  if (!cpm_samples_ok(sample_index0, row_samples)) return AMCX_EINVAL;
+  if (n_rows < 0 || row_stride < row_samples || (n_rows > 0 && row_stride > (int64_t(1) << 58) / n_rows) || frames_per_group < 1)
+    return AMCX_EINVAL;
+  if (segments < 0 || segments > amcx::kCpmMaxSegments) return AMCX_EINVAL;
+  const CpmPlan p = cpm_plan(n_taps, up, down, n_rows, row_samples, segments);
+  if (n_rows > 0 && p.segments > (int64_t)0x7fffffff / n_rows) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (!ptrs_ok({{out, 7u, true}, {phase_taps_dev, 3u, true}, {sigma_dev, 3u, true}, {acc_in_dev, 3u, sample_index0 > 0},
+                {acc_out_dev, 3u, false}}))
+    return AMCX_EINVAL;
+  if (acc_in_dev != nullptr && acc_out_dev != nullptr) {               // a segment reads a row's word another may have written
+    const uintptr_t in0 = reinterpret_cast<uintptr_t>(acc_in_dev), out0 = reinterpret_cast<uintptr_t>(acc_out_dev);
+    if (in0 < out0 + 4u * (uintptr_t)n_rows && out0 < in0 + 4u * (uintptr_t)n_rows) return AMCX_EINVAL;
+  }
+  amcx::CpmArgs a;
+  a.seed_lo = (unsigned)(seed & 0xffffffffull);
+  a.seed_hi = (unsigned)(seed >> 32);
+  a.row_index0 = row_index0;
+  a.sample_index0 = sample_index0;
+  a.n_rows = n_rows;
+  a.row_samples = row_samples;
+  a.row_stride = row_stride;
+  a.order = order;
+  a.taps = phase_taps_dev;
+  a.phase_full = phase_full;
+  a.T = n_taps;
+  a.U = up;
+  a.V = down;
+  a.P = amcx::poly_phase_taps(n_taps, up);
+  a.tau0 = tau0;
+  a.max_span = amcx::syn_max_span(n_taps, up, down);
+  a.phase_step = phase_step;
+  a.cfo_max = cfo_max;
+  a.flags = flags;
+  a.sigma = sigma_dev;
+  a.frames_per_group = frames_per_group;
+  a.acc_in = acc_in_dev;
+  a.acc_out = acc_out_dev;
+  a.out = static_cast<float2*>(out);
+  a.tile = p.tile;
+  a.segments = p.segments;
+  a.tiles_per_row = p.tiles_per_row;
+  a.tiles_per_seg = p.tiles_per_seg;
+  a.n_items = n_rows * p.segments;
+  // a plain grid, one workgroup per (row, segment): lines of at most 2^16 workgroups, the last one cut by the kernel
+  const int64_t gx = a.n_items < 65536 ? a.n_items : 65536, gy = (a.n_items + gx - 1) / gx;
+  const hipError_t e = amcx::launch(amcx::amcx_synth_cpm_c64_kernel, dim3((unsigned)gx, (unsigned)gy), amcx::kCpmThreads,
+                                    amcx::cpm_lds_bytes(n_taps, up, down), static_cast<hipStream_t>(hip_stream), a);
+  if (e != hipSuccess) return hip_fail(e, "continuous-phase generator kernel launch");
+  return AMCX_OK;
+}
+
+const char* amcx_kernel_name_synth_cpm(void) { return "amcx_synth_cpm_c64_kernel"; }
 
 }  // extern "C"

@@ -739,6 +739,7 @@ def _already_extracted(out_path: Path, key: str, shape, provenance: Optional[dic
         want = dict(provenance)
         have_ids, want_ids = have.pop("features", None), want.pop("features", None)
         have.pop("channel", None)                           # how `synth --channel` made the IQ, not what the file was computed for
+        have.pop("cpm", None)                               # ... and the pulse of a continuous-phase name
         covers = have_ids is None or (want_ids is not None and set(want_ids) <= set(have_ids))
         return have == want and covers
     except Exception:

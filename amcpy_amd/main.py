@@ -24,8 +24,10 @@ finds the emitters of a recording with no raster: the Welch spectrogram on the d
 bins joined into emitters (amcpy_amd/psd.py; sigmf.scan_sigmf), written into a .mat file and, with --annotate, into a copy of
 the meta file as annotations -- which `recording --annotation K --rational` reads back.
 `python -m amcpy_amd synth --root DIR [--mods M ...] [--sps U/V] [--pulse rrc|rect] [--beta B] [--span S] [--frames F] [--frame-size N]
-[--snr lo:hi:step] [--cfo X] [--seed S] [--channel PROFILE --doppler F [--sinusoids S]] [--features-only] [--device D]` makes the labelled data set on the GPU (amcpy_amd/waveform.py):
-mat-data/all_modulations.mat as the reference expects it, or, --features-only, calculated-features/ directly.
+[--snr lo:hi:step] [--cfo X] [--seed S] [--channel PROFILE --doppler F [--sinusoids S]] [--cpm-h H] [--bt B] [--cpm-span S] [--features-only] [--device D]` makes the labelled data set on the GPU (amcpy_amd/waveform.py):
+mat-data/all_modulations.mat as the reference expects it, or, --features-only, calculated-features/ directly.  --mods takes the
+continuous-phase names as well (MSK, GMSK, 2FSK, 4FSK, ...; the last three flags shape their pulse), separated by blanks or commas;
+`train`, `classify` and `quantize` take the same --mods where the classes are not the configuration's six.
 
 Several GPUs, ONE command (the reference's caller runs one command and the parallelism happens inside,
 feature_extraction.py:89-97): ``--devices 0,1,2,3`` / ``--devices all`` drives one engine per device from one
@@ -107,6 +109,9 @@ def build_parser() -> argparse.ArgumentParser:
     tr.add_argument("--sweep-lr", default=None, metavar="a,b,...", help="one model per value, all trained side by side (256 at most)")
     tr.add_argument("--sweep-dropout", default=None, metavar="a,b,...", help="as --sweep-lr; with both, two lists of one length")
     tr.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
+    for p in (tr, cl, qz):
+        p.add_argument("--mods", nargs="+", default=None, metavar="MOD",
+                       help="the classes, in label order, where they are not the configuration's six (as `synth --mods` named them)")
     tr.add_argument("--frame-size", type=int, default=None)
     tr.add_argument("--num-frames", type=int, default=None)
     tr.add_argument("--snr-values", nargs="+", default=None, metavar="LABEL")
@@ -193,17 +198,28 @@ def build_parser() -> argparse.ArgumentParser:
                     help="fading multipath: rayleigh | rician:K_DB | exp:N:SPACING:DECAY_DB | tworay:DELAY:DB (amcpy_amd/channel.py)")
     sy.add_argument("--doppler", type=float, default=0.0, metavar="F", help="maximum Doppler of --channel, cycles per sample")
     sy.add_argument("--sinusoids", type=int, default=16, metavar="S", help="sinusoids per path of --channel (default 16)")
+    sy.add_argument("--cpm-h", default=None, metavar="H", help="modulation index of the MFSK names, a fraction such as 1/2 (default 1)")
+    sy.add_argument("--bt", type=float, default=0.3, metavar="B", help="GMSK: bandwidth of the Gaussian filter, symbol rates (default 0.3)")
+    sy.add_argument("--cpm-span", type=int, default=4, metavar="S", help="GMSK: symbols the phase pulse spans (default 4)")
     sy.add_argument("--features-only", action="store_true",
                     help="write calculated-features/{mod}_features.mat directly; the IQ is made a chunk at a time and never stored")
     sy.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
     return ap
 
 
+def split_mods(mods):
+    """--mods as a list of names: blanks or commas between them; None stays None."""
+    return None if mods is None else [m for text in mods for m in str(text).split(",") if m]
+
+
 def synth_config(args) -> tuple:
     """The configuration and the SNR grid the `synth` command's flags name."""
+    from .config import with_modulations
     from .waveform import _label, parse_snr
     cfg = Config() if args.root is None else Config(paths=Paths(root=args.root))
     sig = cfg.signals
+    if args.mods is not None:                 # a container variable for every name the configuration does not know
+        sig = replace(sig, mat_info=with_modulations(sig, split_mods(args.mods)).mat_info)
     if args.frame_size is not None:
         sig = replace(sig, frame_size=args.frame_size)
     if args.frames is not None:
@@ -227,7 +243,9 @@ def run_synth(args, compute=None, features=None, channel_compute=None) -> list:
             fade = dict(profile=parse_profile(args.channel), doppler=args.doppler, sinusoids=args.sinusoids)
             if channel_compute is not None:
                 fade["compute"] = channel_compute
-        return waveform.run_synth(cfg, mods=args.mods, sps=waveform.parse_sps(args.sps), pulse=args.pulse, beta=args.beta, span=args.span,
+        from fractions import Fraction
+        shape = dict(h=None if args.cpm_h is None else Fraction(args.cpm_h), bt=args.bt, span=args.cpm_span)
+        return waveform.run_synth(cfg, mods=split_mods(args.mods), cpm=shape, sps=waveform.parse_sps(args.sps), pulse=args.pulse, beta=args.beta, span=args.span,
                                   snr=snr, cfo=args.cfo, seed=args.seed, features_only=args.features_only,
                                   device=None if args.device is None else f"cuda:{args.device}", compute=compute, features=features,
                                   channel=fade)
@@ -624,6 +642,12 @@ def main(argv=None, *, skip_torch: bool = False) -> int:
         sig = replace(sig, num_frames=args.num_frames)
     if args.snr_values is not None:
         sig = replace(sig, snr_values={i: str(v) for i, v in enumerate(args.snr_values)})
+    if getattr(args, "mods", None) is not None:
+        from .config import with_modulations
+        try:
+            sig = with_modulations(sig, split_mods(args.mods))
+        except ValueError as e:
+            raise SystemExit(f"--mods: {e}")
     cfg = replace(cfg, signals=sig)
     if args.command == "train":
         # tensors on torch's runtime: this command never skips the import

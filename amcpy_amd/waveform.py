@@ -7,6 +7,8 @@ index and a sample by its absolute index in the row, so a data set made in any n
 any length, equals one call bit for bit, and tests/synth_ref.py restates it in numpy.
 
     design_rrc / design_rect     pulses with sum g^2 = U: unit signal power with a unit-power table, SNR = 1 / sigma^2
+    CpmPulse, design_cpfsk / design_gfsk / design_gmsk   phase pulses of the continuous-phase names "MSK", "GMSK", "2FSK", "4FSK", ...
+                                 (amcx_synth_cpm_c64, ABI 16.2.2): exp(j Phi[n]), Phi an exact integer sum over every symbol so far
     constellation_table          :func:`amcpy_amd.synth.constellation`'s points as complex64 (WGN: none -- the noise class)
     generate                     one launch: (n_rows, row_samples) complex64
     dataset / dataset_features   the reference's container layout, mod -> (n_snr, n_frames, frame_size) or (..., 18)
@@ -20,6 +22,7 @@ from __future__ import annotations
 
 import json
 import math
+import re
 from fractions import Fraction
 
 import numpy as np
@@ -59,6 +62,91 @@ def design_rrc(U: int, span_symbols: int = 16, beta: float = 0.35) -> np.ndarray
     g[edge] = beta / math.sqrt(2.0) * ((1 + 2 / np.pi) * math.sin(np.pi / (4 * beta)) + (1 - 2 / np.pi) * math.cos(np.pi / (4 * beta)))
     g = (g + g[::-1]) / 2.0
     return (g * math.sqrt(U / float(np.sum(g * g)))).astype(np.float32)
+
+
+# ---- continuous-phase modulations (amcx_synth_cpm_c64, ABI 16.2.2) ------------------------------------------------------------------
+_M32 = (1 << 32) - 1
+_FSK = re.compile(r"^(\d+)FSK$")
+
+
+class CpmPulse:
+    """A phase pulse at U samples per symbol: ``phase_taps[i]`` = the phase one unit of symbol has contributed i samples after
+    its first, ``phase_full`` what it contributes for good, both in units of 2^-32 turn (uint32).  ``phase_taps``: a uint32
+    array, or -- what :func:`generate` takes as it is -- an int32 tensor on the device holding those bits."""
+
+    def __init__(self, phase_taps, phase_full: int):
+        if not _tensor(phase_taps):
+            phase_taps = np.ascontiguousarray(np.asarray(phase_taps, dtype=np.uint32))
+        if phase_taps.ndim != 1 or not 1 <= int(phase_taps.shape[0]) <= MAX_TAPS or not 0 <= int(phase_full) <= _M32:
+            raise ValueError(f"CpmPulse: 1 ... {MAX_TAPS} taps in one dimension and 0 <= phase_full < 2^32")
+        self.phase_taps, self.phase_full = phase_taps, int(phase_full)
+
+
+class CpmOrder(int):
+    """What stands where a linear modulation's table stands: the size of a continuous-phase alphabet, 2 ... 256."""
+
+
+def design_cpfsk(U: int, h=Fraction(1, 2)) -> CpmPulse:
+    """Continuous-phase FSK, a rectangular frequency pulse of one symbol: U taps ``round(h/2 (i + 1)/U 2^32)``, ``phase_full =
+    round(h/2 2^32)`` (exact rationals, halves away from zero).  h = 1/2 is MSK: 2^30, a quarter turn per symbol."""
+    U, h = int(U), Fraction(h)
+    if not 1 <= U <= MAX_UP or not 0 < h < 2:
+        raise ValueError(f"design_cpfsk: U {U} (1 ... {MAX_UP}), h {h} (0 < h < 2)")
+    unit = lambda x: int(math.floor(x * (1 << 32) + Fraction(1, 2)))       # noqa: E731
+    return CpmPulse(np.array([unit(h / 2 * Fraction(i + 1, U)) for i in range(U)], np.uint32), unit(h / 2))
+
+
+def design_gfsk(U: int, h, bt: float = 0.3, span_symbols: int = 4) -> CpmPulse:
+    """Gaussian FSK: the rectangular frequency pulse of one symbol through a Gaussian low-pass of bandwidth ``bt`` symbol rates,
+    cut to ``span_symbols`` symbols, accumulated and scaled so that the last of its ``span_symbols * U`` taps equals ``phase_full
+    = round(h/2 2^32)``; non-decreasing."""
+    U, h, bt, span = int(U), Fraction(h), float(bt), int(span_symbols)
+    if not 1 <= U <= MAX_UP or not 0 < h < 2 or not bt > 0.0 or span < 1:
+        raise ValueError(f"design_gfsk: U {U} (1 ... {MAX_UP}), h {h} (0 < h < 2), bt {bt} (> 0), span_symbols {span} (>= 1)")
+    T = span * U
+    if T > MAX_TAPS:
+        raise ValueError(f"design_gfsk: {span} symbols at {U} samples per symbol are {T} taps, more than {MAX_TAPS}")
+    full = int(math.floor(h / 2 * (1 << 32) + Fraction(1, 2)))
+    c = math.pi * bt * math.sqrt(2.0 / math.log(2.0))
+    t = [(i + 0.5) / U - span / 2.0 for i in range(T)]                      # sample centres, in symbols about the pulse's middle
+    g = np.array([0.5 * (math.erf(c * (x + 0.5)) - math.erf(c * (x - 0.5))) for x in t], np.float64)
+    q = np.cumsum(g) / float(np.sum(g))
+    taps = np.minimum(np.rint(q * full), full).astype(np.uint64)
+    taps[-1] = full
+    return CpmPulse(np.maximum.accumulate(taps).astype(np.uint32), full)
+
+
+def design_gmsk(U: int, bt: float = 0.3, span_symbols: int = 4) -> CpmPulse:
+    """GMSK: :func:`design_gfsk` at h = 1/2."""
+    return design_gfsk(U, Fraction(1, 2), bt, span_symbols)
+
+
+def cpm_order(mod):
+    """The alphabet of a continuous-phase name -- 2 for "MSK" and "GMSK", M for "MFSK" (2 ... 256) -- or None for any other name."""
+    if isinstance(mod, CpmOrder):
+        return int(mod)
+    if not isinstance(mod, str):
+        return None
+    m = mod.upper()
+    if m in ("MSK", "GMSK"):
+        return 2
+    fsk = _FSK.match(m)
+    if fsk is None:
+        return None
+    if not 2 <= int(fsk.group(1)) <= MAX_ORDER:
+        raise ValueError(f"{mod}: an FSK alphabet of 2 ... {MAX_ORDER}")
+    return int(fsk.group(1))
+
+
+def cpm_pulse(mod: str, U: int, *, h=None, bt: float = 0.3, span_symbols: int = 4) -> CpmPulse:
+    """The default pulse of a continuous-phase name: "MSK" :func:`design_cpfsk` at 1/2, "GMSK" :func:`design_gmsk`, "MFSK"
+    :func:`design_cpfsk` at h = 1 (tones one symbol rate apart) unless ``h`` says otherwise."""
+    m = mod.upper()
+    if m == "MSK":
+        return design_cpfsk(U, Fraction(1, 2))
+    if m == "GMSK":
+        return design_gmsk(U, bt, span_symbols)
+    return design_cpfsk(U, 1 if h is None else h)
 
 
 def constellation_table(mod: str) -> np.ndarray:
@@ -116,6 +204,11 @@ def _operands(mod, taps, U, snr_db=None, sigma=None, device=None) -> tuple:
     """``(table, taps, sigmas)`` as the entry reads them.  On the host: a modulation's name becomes its table, no taps the
     rectangular pulse, ``snr_db`` the sigmas, all as contiguous complex64 / float32 arrays; a tensor is left as it is.  With a
     ``device``, on it: what is on the host is uploaded, a tensor is taken as it is (and must be what the kernel reads)."""
+    order = cpm_order(mod)
+    if order is not None:
+        return _cpm_operands(mod, order, taps, U, snr_db, sigma, device)
+    if isinstance(taps, CpmPulse):
+        raise TypeError("a CpmPulse goes with a continuous-phase name (MSK, GMSK, MFSK), not with a table")
     table = mod
     if not _tensor(mod):
         table = constellation_table(mod) if isinstance(mod, str) else np.ascontiguousarray(np.asarray(mod, dtype=np.complex64)).reshape(-1)
@@ -138,9 +231,33 @@ def _operands(mod, taps, U, snr_db=None, sigma=None, device=None) -> tuple:
     return resident(table, torch.complex64, "the table"), resident(taps, torch.float32, "taps"), resident(sig, torch.float32, "sigma")
 
 
+def _cpm_operands(mod, order, pulse, U, snr_db, sigma, device) -> tuple:
+    """:func:`_operands` of a continuous-phase name: ``(CpmOrder, CpmPulse, sigmas)``, the pulse's taps on ``device`` as int32."""
+    if pulse is None:
+        pulse = cpm_pulse(mod, U)
+    if not isinstance(pulse, CpmPulse):
+        raise TypeError(f"{mod}: a continuous-phase name takes a CpmPulse (design_cpfsk, design_gfsk, design_gmsk), not float taps")
+    if _tensor(sigma) and snr_db is not None:
+        raise ValueError("either snr_db or sigma")
+    sig = sigma if _tensor(sigma) else _sigmas(mod, snr_db, sigma)
+    if device is not None:
+        import torch
+        taps = pulse.phase_taps
+        if not isinstance(taps, torch.Tensor):
+            pulse = CpmPulse(torch.from_numpy(taps.view(np.int32)).to(device), pulse.phase_full)
+        elif taps.dtype != torch.int32 or taps.device != device or not taps.is_contiguous():
+            raise TypeError("a CpmPulse's taps on the device: a contiguous one-dimensional int32 tensor on the output's device")
+        if not isinstance(sig, torch.Tensor):
+            sig = torch.from_numpy(sig).to(device)
+        elif sig.dtype != torch.float32 or sig.device != device or not sig.is_contiguous():
+            raise TypeError("sigma must be a contiguous one-dimensional float32 tensor on the output's device")
+    return CpmOrder(order), pulse, sig
+
+
 def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_db=None, sigma=None, frames_per_group=None,
              seed: int = 0, row_index0: int = 0, sample_index0: int = 0, cfo=0.0, shift=0.0, random_phase: bool = True,
-             random_timing: bool = True, timing: int = 0, out=None, device=None, compute=None):
+             random_timing: bool = True, timing: int = 0, out=None, device=None, compute=None, acc_in=None, acc_out=None,
+             segments: int = 0):
     """One launch of amcx_synth_c64 on the current torch stream -> complex64 ``(n_rows, row_samples)`` in GPU memory.
 
     mod     : a modulation's name (:func:`constellation_table`), or the table itself: up to 256 complex points, none for noise.
@@ -158,13 +275,25 @@ def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_d
     random_phase, random_timing : a row's carrier phase and its timing ``tau`` (0 <= tau < U) drawn; else 0 and ``timing``.
     out     : a complex64 tensor ``(n_rows, row_samples)`` to write, possibly a strided view with contiguous rows.
     compute : tests only -- ``f(table, taps, U, V, n_rows, row_samples, sigma, frames_per_group, seed=..., row_index0=...,
-              sample_index0=..., phase_step=..., cfo_max=..., flags=..., tau0=...)`` over numpy (tests/synth_ref.numpy_generate)."""
-    if compute is not None and (_tensor(mod) or _tensor(taps) or _tensor(sigma) or out is not None):
+              sample_index0=..., phase_step=..., cfo_max=..., flags=..., tau0=...)`` over numpy (tests/synth_ref.numpy_generate).
+
+    A CONTINUOUS-PHASE name ("MSK", "GMSK", "2FSK", "4FSK", ...; amcx_synth_cpm_c64) takes a :class:`CpmPulse` for ``taps``
+    (default :func:`cpm_pulse`) and carries one uint32 per row: ``acc_in`` (R words, a uint32 array or an int32 tensor on the
+    device; needed where ``sample_index0 > 0``: the ``acc_out`` of the call that made the samples in front) and ``acc_out`` (an
+    int32 tensor of R words to receive the state behind the call's last sample).  ``segments``: workgroups a row is cut into, 0
+    the plan's choice.  There ``compute`` is ``f(order, phase_taps, phase_full, U, V, n_rows, row_samples, sigma,
+    frames_per_group, acc_in=..., acc_out=..., ...)`` (tests/cpm_ref.numpy_generate)."""
+    pulse_t = isinstance(taps, CpmPulse) and _tensor(taps.phase_taps)
+    if compute is not None and (_tensor(mod) or _tensor(taps) or pulse_t or _tensor(sigma) or out is not None):
         raise TypeError("an injected compute takes host arrays and returns its own output")
     U, V = _shape(sps)
     R, S = int(n_rows), int(row_samples)
     table, taps, sig = _operands(mod, taps, U, snr_db, sigma)
-    order, T, G = (int(t.shape[0]) if t.ndim == 1 else -1 for t in (table, taps, sig))
+    cpm = isinstance(table, CpmOrder)
+    if not cpm and (acc_in is not None or acc_out is not None or segments):
+        raise TypeError("acc_in, acc_out and segments belong to the continuous-phase names")
+    length = lambda t: int(t.shape[0]) if t.ndim == 1 else -1               # noqa: E731
+    order, T, G = int(table) if cpm else length(table), length(taps.phase_taps if cpm else taps), length(sig)
     if R < 0 or S < 1 or not 0 <= int(sample_index0) or int(sample_index0) + S >= 1 << 40 or not 0 <= order <= MAX_ORDER \
             or not 1 <= T <= MAX_TAPS or G < 1:
         raise ValueError(f"outside the generator's limits: n_rows {R}, row_samples {S}, sample_index0 {sample_index0}, order {order}, "
@@ -178,7 +307,11 @@ def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_d
     step, cfo_max = _stream.phase_step_of(shift), cfo_max_of(cfo)
     where = dict(seed=int(seed) & _MASK64, row_index0=int(row_index0) & _MASK64, sample_index0=int(sample_index0),
                  phase_step=step, cfo_max=cfo_max, flags=flags, tau0=int(timing))
+    if cpm and int(sample_index0) > 0 and acc_in is None:
+        raise ValueError("a continuous-phase row that begins behind sample 0 needs acc_in, the state of the samples in front")
     if compute is not None:
+        if cpm:
+            return compute(order, taps.phase_taps, taps.phase_full, U, V, R, S, sig, fpg, acc_in=acc_in, acc_out=acc_out, **where)
         return compute(table if order else None, taps, U, V, R, S, sig, fpg, **where)
 
     import torch
@@ -194,6 +327,22 @@ def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_d
     table, taps, sig = _operands(table, taps, U, sigma=sig, device=dev)
     if out is None:
         out = torch.empty((R, S), dtype=torch.complex64, device=dev)
+    if cpm:
+        def state(t, name, upload):
+            """a row-state array as the entry reads it; a host array is uploaded where that makes sense (acc_in)"""
+            if t is not None and upload and not isinstance(t, torch.Tensor):
+                t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.uint32)).view(np.int32)).to(dev)
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device != dev
+                                  or not t.is_contiguous() or t.numel() != R):
+                raise TypeError(f"{name}: a contiguous int32 tensor of n_rows words on the output's device")
+            return t
+        a_in, a_out = state(acc_in, "acc_in", True), state(acc_out, "acc_out", False)
+        _stream.launch(out, lambda lib, stream: lib.amcx_synth_cpm_c64(
+            where["seed"], where["row_index0"], where["sample_index0"], R, S, stride, order, taps.phase_taps.data_ptr(), T,
+            taps.phase_full, U, V, where["tau0"], step, cfo_max, flags, sig.data_ptr(), fpg,
+            a_in.data_ptr() if a_in is not None and R else None, a_out.data_ptr() if a_out is not None and R else None,
+            int(segments), out.data_ptr() if R else None, stream))
+        return out
     _stream.launch(out, lambda lib, stream: lib.amcx_synth_c64(
         where["seed"], where["row_index0"], where["sample_index0"], R, S, stride, table.data_ptr() if order else None, order,
         taps.data_ptr(), T, U, V, where["tau0"], step, cfo_max, flags, sig.data_ptr(), fpg, out.data_ptr() if R else None, stream))
@@ -203,11 +352,13 @@ def generate(mod, n_rows: int, row_samples: int, *, sps=(8, 1), taps=None, snr_d
 # ---- data sets ----------------------------------------------------------------------------------------------------------------
 def mod_code(mod: str) -> int:
     """A modulation's number in :func:`dataset`'s rows, from its name alone: (family << 12) | order, the family 0 for a name
-    that ends in PSK, 1 for QAM, 2 for the noise class.  Two names of one family and order (a variant constellation added
+    that ends in PSK, 1 for QAM, 2 for the noise class, 3 for MFSK, 4 for MSK, 5 for GMSK.  Two names of one family and order (a variant constellation added
     later under another name) would share their rows: :func:`dataset` refuses them in one call."""
     m = mod.upper()
     if m in ("WGN", "NOISE"):
         return 2 << 12
+    if cpm_order(m) is not None:
+        return ({"MSK": 4, "GMSK": 5}.get(m, 3) << 12) | cpm_order(m)
     order = len(synth.constellation(m))
     return ((0 if m.endswith("PSK") else 1) << 12) | order
 
@@ -253,7 +404,8 @@ def _walk(mods, snrs, F, N, chunk, first_frame, kw, shape, view, each=None) -> d
     clean = None if fade is None or dev is None else _empty((min(chunk or F, F), N + H), dev)   # the rows before the channel
     data = {}
     for mod in mods:
-        table, taps, sig = _operands(mod, kw.get("taps"), U, snr_db=snrs, device=dev)
+        taps = kw.get("taps")
+        table, taps, sig = _operands(mod, taps.get(mod) if isinstance(taps, dict) else taps, U, snr_db=snrs, device=dev)
         buf = data[mod] = _empty(shape, dev)
         for s, snr in enumerate(snrs):
             for f0 in (range(0, F, chunk) if chunk else (0,)):
@@ -320,7 +472,7 @@ def dataset(mods, snr_db, n_frames: int, frame_size: int, *, first_frame: int = 
     the sigmas go to the device once per modulation; the launches upload nothing."""
     mods, snrs = _grid(mods, snr_db)
     F, N = int(n_frames), int(frame_size)
-    return _walk(mods, snrs, F, N, None, first_frame, kw, (len(snrs), F, N), lambda buf, s, n: buf[s])
+    return _walk(mods, snrs, F, N, None, first_frame, kw, (len(snrs), F, N), lambda buf, s, n: buf[s])   # (taps: one pulse, or mod -> its pulse)
 
 
 def dataset_features(mods, snr_db, n_frames: int, frame_size: int, *, chunk_frames: int = 1 << 14, features=None, **kw) -> dict:
@@ -350,6 +502,7 @@ class Stream:
             if bad in kw:
                 raise ValueError(f"Stream: {bad} is the stream's own")
         self.mod, self.row, self.index, self._kw, self._resident = mod, int(row), 0, dict(kw), None
+        self._acc, self._cur = None, 0         # a continuous-phase row's two words of state, swapped per push
 
     def push(self, n: int):
         n = int(n)
@@ -364,9 +517,22 @@ class Stream:
                 self._resident = _operands(mod, kw.get("taps"), _shape(kw.get("sps", (8, 1)))[0], kw.get("snr_db"), kw.get("sigma"), dev)
             mod, taps, sig = self._resident
             kw = dict(kw, taps=taps, sigma=sig, snr_db=None)
+        if cpm_order(self.mod) is not None:    # acc_out of one push is acc_in of the next
+            if self._acc is None:
+                self._acc = _state_words(dev)
+            kw = dict(kw, acc_in=self._acc[self._cur] if self.index else None, acc_out=self._acc[1 - self._cur])
+            self._cur = 1 - self._cur
         y = generate(mod, 1, n, row_index0=self.row, sample_index0=self.index, **kw)
         self.index += n
         return y[0]
+
+
+def _state_words(device):
+    """two rows of one word: a stream's carried sums, on the device (int32) or for an injected compute (uint32 numpy)"""
+    if device is None:
+        return np.zeros((2, 1), np.uint32)
+    import torch
+    return torch.zeros((2, 1), dtype=torch.int32, device=device)
 
 
 def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device=None) -> tuple:
@@ -375,7 +541,7 @@ def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device
     emitters : dicts with ``mod``, ``sps`` (U, V), ``center`` (cycles per sample of the scene), and optionally ``rate`` (L, D)
                (1, 1), ``start`` (0), ``length`` (to the end), ``amplitude`` (1), ``channel`` (a fading channel the emitter passes
                at the scene's rate: :func:`dataset`'s keyword), ``taps`` (default: :func:`design_rrc` over 16
-               symbols where U > V and it fits, else rect), ``beta`` (0.35).  Emitter e is row e of the seed; the floor is the
+               symbols where U > V and it fits, else rect; a continuous-phase name: its :func:`cpm_pulse`), ``beta`` (0.35).  Emitter e is row e of the seed; the floor is the
                noise class in row ``len(emitters)``.
     Each emitter is one :class:`Stream` row at its own U / V samples per symbol, brought to the scene's rate by
     :func:`amcpy_amd.resample.resample` (L / D, the default low-pass: U L / (V D) samples per symbol in the scene), moved to its
@@ -401,8 +567,9 @@ def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device
             raise ValueError(f"emitter {e}: samples {start} ... {start + length} are outside the scene's {S}")
         beta = float(em.get("beta", 0.35))
         taps = em.get("taps")
-        rrc = taps is None and 16 * U + 1 <= MAX_TAPS and U > V
-        if taps is None:
+        alphabet = cpm_order(em["mod"])                          # a continuous-phase emitter keeps its own pulse
+        rrc = taps is None and alphabet is None and 16 * U + 1 <= MAX_TAPS and U > V
+        if taps is None and alphabet is None:
             taps = design_rrc(U, 16, beta) if rrc else design_rect(U)
         stream = Stream(em["mod"], row=e, sps=(U, V), taps=taps, seed=seed, device=dev)
         fade = em.get("channel")
@@ -422,6 +589,8 @@ def scene(emitters, n_samples: int, *, noise_sigma: float, seed: int = 0, device
         x[start:start + length] += y * float(em.get("amplitude", 1.0))
         per_symbol = Fraction(U * L, V * D)
         width = (1.0 + beta if rrc else 1.0) / float(per_symbol)
+        if alphabet is not None and _FSK.match(str(em["mod"]).upper()):
+            width *= alphabet                                    # M tones a symbol rate apart (the default h = 1)
         annotations.append({"core:sample_start": start, "core:sample_count": length, "core:label": str(em["mod"]),
                             "core:freq_lower_edge": float(em["center"]) - width / 2.0,
                             "core:freq_upper_edge": float(em["center"]) + width / 2.0,
@@ -455,12 +624,13 @@ V5_LIMIT = (1 << 31) - 1      # bytes of one MATLAB v5 file's variables
 
 def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0.35, span: int = 16, snr=None, cfo=0.0,
               seed: int = 0, features_only: bool = False, device=None, compute=None, features=None, verbose: bool = True,
-              channel=None) -> list:
+              channel=None, cpm=None) -> list:
     """The `synth` command: the data set of ``cfg`` (its frame size, frame count and SNR labels, unless ``snr`` names the
     grid) for ``mods`` (default ``cfg.signals.modulations_with_noise``) into ``mat-data/all_modulations.mat`` under the variables
     ``cfg.signals.mat_info`` names -- or, ``features_only``, straight into ``calculated-features/{mod}_features.mat`` with the
     provenance record `extract --resume` trusts.  ``channel``: :func:`dataset`'s keyword, a fading channel every frame passes; the
-    provenance record names it.  Returns the files written.  ``compute`` / ``features``: injected (tests)."""
+    provenance record names it.  ``cpm``: ``dict(h=..., bt=..., span=...)``, the pulse of the continuous-phase names among
+    ``mods`` (:func:`cpm_pulse`), named in their provenance records too.  Returns the files written.  ``compute`` / ``features``: injected (tests)."""
     import scipy.io
 
     from .feature_extraction import _provenance, _provenance_path
@@ -475,7 +645,10 @@ def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0
     U, V = _shape(sps)
     if pulse not in ("rrc", "rect"):
         raise ValueError("pulse: rrc or rect")
-    taps = design_rrc(U, span, beta) if pulse == "rrc" else design_rect(U)
+    linear = design_rrc(U, span, beta) if pulse == "rrc" else design_rect(U)
+    shape = {"h": None, "bt": 0.3, "span": 4, **(cpm or {})}
+    taps = {m: linear if cpm_order(m) is None else cpm_pulse(m, U, h=shape["h"], bt=shape["bt"], span_symbols=shape["span"])
+            for m in mods}
     F, N = int(sig.num_frames), int(sig.frame_size)
     kw = dict(sps=(U, V), taps=taps, cfo=cfo, seed=seed, compute=compute)
     if compute is None:
@@ -493,6 +666,10 @@ def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0
             record = _provenance(cfg, mat_path, sig.mat_info[m])
             if channel is not None:
                 record["channel"] = _channel_record(channel)
+            if cpm_order(m) is not None:
+                record["cpm"] = {"order": cpm_order(m), "taps": int(taps[m].phase_taps.shape[0]), "phase_full": taps[m].phase_full,
+                                 "h": None if shape["h"] is None else str(Fraction(shape["h"])), "bt": float(shape["bt"]),
+                                 "span": int(shape["span"])}
             _provenance_path(out_path).write_text(json.dumps(record) + "\n")
             written.append(out_path)
             if verbose:

@@ -101,11 +101,14 @@ extern "C" {
  * classifier's network (range calibration and 16-bit integer inference).
  * AMCX_ABI_MINOR counts what has been ADDED since the version last changed -- new entries and constants, nothing existing changed:
  * 16.1 = training of the classifier's network, one workgroup per model; 16.2 = the waveform generator.
- * AMCX_ABI_PATCH counts in the same way what has been added since the minor last changed: 16.2.1 = the fading multipath channel. */
+ * AMCX_ABI_PATCH counts in the same way what has been added since the minor last changed: 16.2.1 = the fading multipath channel;
+ * 16.2.2 = the generator's continuous-phase modulations. */
 #define AMCX_ABI_VERSION 16
 #define AMCX_ABI_MINOR 2
-#define AMCX_ABI_PATCH 1
+#define AMCX_ABI_PATCH 2
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
+ *   ABI 16.2.2: AMCX_ABI_PATCH 2          -- continuous-phase modulations (FSK, MSK, GMSK): amcx_synth_cpm_c64,
+ *                                            amcx_synth_cpm_plan, amcx_kernel_name_synth_cpm
  *   ABI 16.2.1: AMCX_ABI_PATCH 1          -- the fading channel: AMCX_CHANNEL_*, amcx_channel_c64, amcx_channel_plan,
  *                                            amcx_kernel_name_channel, amcx_abi_patch
  *   ABI 16.2: AMCX_ABI_MINOR 2            -- the waveform generator: AMCX_SYNTH_*, amcx_synth_c64, amcx_synth_plan,
@@ -1166,6 +1169,48 @@ int amcx_channel_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, 
                      int32_t interp_log2, uint32_t doppler_max, uint32_t flags, const float* sigma_dev, int64_t frames_per_group,
                      void* out_c64_dev, int64_t out_row_stride, void* hip_stream);
 const char* amcx_kernel_name_channel(void);
+
+/*
+ * ABI 16.2.2.  THE CONTINUOUS-PHASE GENERATOR: n_rows rows of row_samples complex64 samples of exp(j Phi[n]) -- FSK, MSK, GMSK --
+ * in ONE launch on hip_stream (amcpy_amd/csrc/amcx_synth_cpm_kernel.h).  Phi is a running sum over every symbol so far, kept in
+ * uint32 arithmetic mod 2^32 in units of 2^-32 turn, the units the mixer reads: integer sums are associative, so any order gives
+ * the same bits.  It allocates nothing, never synchronises and can be captured in a graph; no atomics, no workgroup waits for
+ * another.  Everything named here that ABI 16.2 defines keeps its definition from amcx_synth_c64: the key and the counters, the
+ * row words (phase0_r, step_r, tau_r), t_n, p_n, k_n, P, the symbol draw idx_j of stream 1 (a row of order M draws the indices a
+ * linear row of order M draws), the noise words of stream 2, sigma_g, r and n absolute.
+ *
+ *   symbol           alpha_j = 2 idx_j - (order - 1)                 an integer of -(M - 1) ... M - 1 in steps of 2
+ *   phase pulse      Qc(i) = phase_taps_dev[i] for 0 <= i < T = n_taps,  phase_full for i >= T;  at U samples per symbol
+ *   phase            Phi_r[n] = sum_{j = 0 ... k_n} alpha_j * Qc(t_n - (j - P + 1) U)                mod 2^32
+ *                    computed as phase_full * A(k_n - cnt_n + 1) + sum_{q < cnt_n} alpha[k_n - q] * phase_taps[p_n + q U],
+ *                    cnt_n the taps of phase p_n (the q with p_n + q U < T), A(K) = sum_{j < K} alpha_j
+ *   out[f, i]        = the generator's carrier and noise on (1, 0) at phi = phase0_r + n step_r + ((uint64)Phi_r[n] << 32)
+ *
+ * The signal has unit amplitude: sigma and SNR = 1 / sigma^2 keep the generator's meaning.
+ * THE CARRIED SUM.  acc_in_dev[f] = A(K0) mod 2^32, K0 = floor(sample_index0 V / U): it does not depend on the drawn timing
+ * (the kernel adds alpha_K0 itself where the row's first window begins one symbol later).  It may be NULL only where
+ * sample_index0 == 0 (A(0) = 0).  acc_out_dev, where not NULL, gets A(floor((sample_index0 + row_samples) V / U)) per row: the
+ * acc_in of the call that continues the rows.  With a true acc_in the bits of out[f, i] depend on (seed, r, n), the row
+ * parameters, the pulse and sigma_g alone -- ABI 16.2's position independence with one word of state per row.
+ * A row is cut into `segments` runs of whole tiles, one workgroup each, which changes no bit; 0 leaves the cut to the plan.
+ *
+ *   - limits: 2 <= order <= 256; up, down, n_taps, tau0, flags, row_samples, sample_index0, n_rows, row_stride and
+ *     frames_per_group as amcx_synth_c64; 0 <= segments <= 64; at most 2^31 - 1 (row, segment) items
+ *   - checks, in the order of every launching entry: the limits in that order; n_rows == 0 is AMCX_OK here and writes nothing;
+ *     then null pointers (out, phase_taps, sigma; acc_in where sample_index0 > 0), alignment (out 8, the others 4), a pointer
+ *     on another device, and the two acc arrays, which must not overlap.  Ordinary vector stores only.
+ * amcx_synth_cpm_plan (host-only): samples per tile, bytes of LDS and the segments a call with segments = 0 cuts a row into (1
+ * where the rows alone fill the device, else about two workgroups per compute unit, never more than the row's tiles or 64);
+ * each pointer may be NULL.  amcx_kernel_name_synth_cpm (host-only): the kernel's name, a static string.
+ */
+int amcx_synth_cpm_plan(int32_t n_taps, int32_t up, int32_t down, int64_t n_rows, int64_t row_samples, int32_t* tile_outputs,
+                        int32_t* lds_bytes, int32_t* segments);
+int amcx_synth_cpm_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0, int64_t n_rows, int64_t row_samples,
+                       int64_t row_stride, int32_t order, const uint32_t* phase_taps_dev, int32_t n_taps, uint32_t phase_full,
+                       int32_t up, int32_t down, int32_t tau0, uint64_t phase_step, uint32_t cfo_max, uint32_t flags,
+                       const float* sigma_dev, int64_t frames_per_group, const uint32_t* acc_in_dev, uint32_t* acc_out_dev,
+                       int32_t segments, void* out, void* hip_stream);
+const char* amcx_kernel_name_synth_cpm(void);
 
 #ifdef __cplusplus
 }
