@@ -14,7 +14,8 @@ LIB_PATH = Path(os.environ.get("AMCX_LIB", _HERE / "lib" / "libamcx.so"))
 
 ABI_VERSION = 16        # the version this binding was written against; any library >= it will do (include/amcx.h)
 ABI_MINOR = 2           # ... and, at that version, the additions it needs (AMCX_ABI_MINOR: 16.1 = training, 16.2 = the generator)
-ABI_PATCH = 2           # ... and, at that minor, the additions it needs (AMCX_ABI_PATCH: 16.2.1 = the fading channel, 16.2.2 = continuous phase)
+ABI_PATCH = 3           # ... and, at that minor, the additions it needs (AMCX_ABI_PATCH: 16.2.1 = the fading channel, 16.2.2 = continuous phase,
+                        # 16.2.3 = carrier recovery)
 NUM_FEATURES = 18
 # feature masks (include/amcx.h, ABI 7): bit j - 1 = feature id j
 FEATURES_ALL, FEATURES_NO_SPECTRAL, FEATURES_CUMULANTS = 0x3FFFF, 0x3FFFE, 0x3FE00
@@ -32,6 +33,10 @@ ACT_NONE = 3                                             # AMCX_ACT_NONE (ABI 16
 OPT_RMSPROP, OPT_ADAM = 0, 1                             # AMCX_OPT_* (ABI 16.1)
 SYNTH_RANDOM_PHASE, SYNTH_RANDOM_TIMING = 1, 2           # AMCX_SYNTH_* (ABI 16.2)
 CHANNEL_RANDOM_PHASE = 1                                 # AMCX_CHANNEL_* (ABI 16.2.1)
+CARRIER_GAIN, CARRIER_FREQ, CARRIER_PHASE, CARRIER_GIVEN = 1, 2, 4, 8      # AMCX_CARRIER_* (ABI 16.2.3)
+# the carrier record (include/amcx.h, ABI 16.2.3), 32 bytes, as a numpy structured type
+CARRIER_RECORD = [("phase_step", "<i8"), ("phase0", "<u4"), ("bin", "<i4"), ("frac", "<f4"), ("power", "<f4"), ("gain", "<f4"),
+                  ("quality", "<f4")]
 CHANNEL_MAX_PATHS, CHANNEL_MAX_SINUSOIDS, CHANNEL_MAX_DELAY = 16, 32, 1024
 
 
@@ -158,6 +163,9 @@ SIGNATURES = {
     "amcx_synth_cpm_c64": (C.c_int, [C.c_uint64, C.c_uint64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, C.c_uint32, _i32, _i32, _i32,
                                      C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
     "amcx_kernel_name_synth_cpm": (C.c_char_p, []),
+    "amcx_carrier_plan": (C.c_int, [_i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "amcx_carrier_c64": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _i32, C.c_uint32, _vp, _vp, _i64, _vp]),
+    "amcx_kernel_name_carrier": (C.c_char_p, []),
 }
 
 _lib = None
@@ -376,6 +384,18 @@ def synth_cpm_plan(n_taps: int, up: int, down: int, n_rows: int, row_samples: in
     check(load().amcx_synth_cpm_plan(int(n_taps), int(up), int(down), int(n_rows), int(row_samples), C.byref(tile), C.byref(lds),
                                      C.byref(seg)))
     return tile.value, lds.value, seg.value
+
+
+def kernel_name_carrier() -> str:
+    """amcx_kernel_name_carrier: the kernel amcx_carrier_c64 runs (host-only)."""
+    return load().amcx_kernel_name_carrier().decode()
+
+
+def carrier_plan(n: int) -> tuple:
+    """amcx_carrier_plan -> (rows a workgroup holds, bytes of static LDS) (host-only)."""
+    rows, lds = C.c_int32(0), C.c_int32(0)
+    check(load().amcx_carrier_plan(int(n), C.byref(rows), C.byref(lds)))
+    return rows.value, lds.value
 
 
 def synth_plan(order: int, n_taps: int, up: int, down: int) -> tuple:

@@ -14,7 +14,8 @@
 #include <new>
 #include <vector>
 
-#include "amcx_synth_cpm_kernel.h" // FIRST of all (ABI 16.2.2: it includes the generator's header in front of its one kernel), then the channel's ...
+#include "amcx_carrier_kernel.h"   // FIRST of all (ABI 16.2.3: it includes the spectrogram's header in front of its one kernel), then the continuous-phase generator's ...
+#include "amcx_synth_cpm_kernel.h" // ... (ABI 16.2.2: it includes the generator's header in front of its one kernel), then the channel's ...
 #include "amcx_channel_kernel.h"   // ... (ABI 16.2.1: it includes the generator's header in front of its one kernel), then the generator's ...
 #include "amcx_synth_kernel.h"     // ... (ABI 16.2: it includes the training kernels' header and the down-converter's in front of its one kernel), ...
 #include "amcx_mlp_train_kernel.h" // ... (ABI 16.1: plain and explicitly instantiated kernels on amcx_mlp_shape.h alone), then the fixed-point ones ...
@@ -1893,5 +1894,68 @@ int amcx_synth_cpm_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0
 }
 
 const char* amcx_kernel_name_synth_cpm(void) { return "amcx_synth_cpm_c64_kernel"; }
+
+}  // extern "C"
+
+// ---- ABI 16.2.3: blind carrier recovery (amcx_carrier_kernel.h) -----------------------------------------------------------------
+namespace {
+
+// log2 of the order, -1 where it is none of 1, 2, 4, 8
+int carrier_log2_order(int32_t order) { return order == 1 ? 0 : order == 2 ? 1 : order == 4 ? 2 : order == 8 ? 3 : -1; }
+
+}  // namespace
+
+extern "C" {
+
+int amcx_carrier_plan(int32_t n, int32_t* rows_per_workgroup, int32_t* lds_bytes) {
+  if (psd_log2(n) < 0) return AMCX_EINVAL;
+  if (rows_per_workgroup != nullptr) *rows_per_workgroup = amcx::kPsdPoints / n;
+  if (lds_bytes != nullptr) *lds_bytes = amcx::kCarLdsBytes;
+  return AMCX_OK;
+}
+
+int amcx_carrier_c64(const void* in_c64_dev, int64_t n_rows, int32_t n, int64_t in_row_stride, int32_t order, int32_t search_bins,
+                     uint32_t flags, void* est_dev, void* out_c64_dev, int64_t out_row_stride, void* hip_stream) {
+  static_assert(sizeof(amcx::CarrierRecord) == 32, "the header's record");
+  static_assert(amcx::kCarLdsBytes <= 65536, "static LDS: no attribute");
+  const int lg = psd_log2(n), lm = carrier_log2_order(order);
+  if (lg < 0 || lm < 0) return AMCX_EINVAL;
+  if (search_bins < 0 || search_bins > n / 2 - 1) return AMCX_EINVAL;
+  const uint32_t apply = AMCX_CARRIER_GAIN | AMCX_CARRIER_FREQ | AMCX_CARRIER_PHASE;
+  if ((flags & ~(apply | (uint32_t)AMCX_CARRIER_GIVEN)) != 0u) return AMCX_EINVAL;
+  if ((flags & AMCX_CARRIER_GIVEN) != 0u && out_c64_dev == nullptr) return AMCX_EINVAL;     // nothing to estimate, nothing to write
+  if (!rows_ok(n_rows, in_row_stride, n) || !opt_rows_ok(out_c64_dev, n_rows, out_row_stride, n)) return AMCX_EINVAL;
+  const int64_t G = amcx::kPsdPoints / n, n_groups = (n_rows + G - 1) / G;
+  if (n_groups > (int64_t)0x7fffffff) return AMCX_EINVAL;
+  if (n_rows == 0) return AMCX_OK;
+  if (!ptrs_ok({{in_c64_dev, 7u, true}, {est_dev, 7u, true}, {out_c64_dev, 7u, false}})) return AMCX_EINVAL;
+  if (out_c64_dev != nullptr) {                                        // a kept row is written where another workgroup may still read
+    const uintptr_t in0 = reinterpret_cast<uintptr_t>(in_c64_dev), out0 = reinterpret_cast<uintptr_t>(out_c64_dev);
+    const uintptr_t in1 = in0 + 8u * (uintptr_t)((n_rows - 1) * in_row_stride + n);
+    const uintptr_t out1 = out0 + 8u * (uintptr_t)((n_rows - 1) * out_row_stride + n);
+    if (in0 < out1 && out0 < in1) return AMCX_EINVAL;
+  }
+  amcx::CarrierArgs a;
+  a.in = static_cast<const float2*>(in_c64_dev);
+  a.n_rows = n_rows;
+  a.in_stride = in_row_stride;
+  a.n = n;
+  a.lg = lg;
+  a.lm = lm;
+  a.search = search_bins;
+  a.flags = flags;
+  a.est = static_cast<amcx::CarrierRecord*>(est_dev);
+  a.out = static_cast<float2*>(out_c64_dev);
+  a.out_stride = out_row_stride;
+  a.n_groups = n_groups;
+  // a plain grid, one workgroup per group of rows: lines of at most 2^16 workgroups, the last one cut by the kernel
+  const int64_t gx = n_groups < 65536 ? n_groups : 65536, gy = (n_groups + gx - 1) / gx;
+  const hipError_t e = amcx::launch(amcx::amcx_carrier_c64_kernel, dim3((unsigned)gx, (unsigned)gy), amcx::kCarThreads, 0,
+                                    static_cast<hipStream_t>(hip_stream), a);
+  if (e != hipSuccess) return hip_fail(e, "carrier recovery kernel launch");
+  return AMCX_OK;
+}
+
+const char* amcx_kernel_name_carrier(void) { return "amcx_carrier_c64_kernel"; }
 
 }  // extern "C"

@@ -334,6 +334,8 @@ inline void wave_kernel_name(int frame_size, int plan, char* buf, size_t len, bo
 // generator's and in front of the fixed-point ones; calling syn_finish (inlined) from a second kernel left the generator's bytes what they were.
 // The continuous-phase generator's kernel (ABI 16.2.2, amcx_synth_cpm_kernel.h) is a plain kernel in the header included in front of that one; it
 // includes the generator's header (for syn_finish, Philox, the mixer and the plan) in front of its own kernel and templates nothing that is shared.
+// The carrier-recovery kernel (ABI 16.2.3, amcx_carrier_kernel.h) is a plain kernel in the header included in front of that one; it includes the
+// spectrogram's header (for psd_pass, psd_pad, psd_mul, and the mixer through it) in front of its own kernel and templates nothing that is shared.
 // amcx_polyphase.h (the tap image, the sum and the plan arithmetic the generator and the resampler share) holds NO kernel, as amcx_mlp_shape.h: nothing moves.
 // Nor does amcx_exact_passes.h (what the block and the stream kernel share; the wave kernels' header includes it for wave_sum).
 // That specialisations are laid out there is what hipcc does today, not a rule it documents: tools/codeobj_gate.py --kernels

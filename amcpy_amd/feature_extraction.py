@@ -740,6 +740,7 @@ def _already_extracted(out_path: Path, key: str, shape, provenance: Optional[dic
         have_ids, want_ids = have.pop("features", None), want.pop("features", None)
         have.pop("channel", None)                           # how `synth --channel` made the IQ, not what the file was computed for
         have.pop("cpm", None)                               # ... and the pulse of a continuous-phase name
+        have.pop("recover", None)                           # ... and the carrier recovery `synth --features-only --recover M` put in front
         covers = have_ids is None or (want_ids is not None and set(want_ids) <= set(have_ids))
         return have == want and covers
     except Exception:

@@ -17,7 +17,10 @@ network run on the GPU: amcpy_amd/quantize.py.
 stream -- and writes `features` (F, 18) and `frame_start` (F,) into a .mat file: amcpy_amd/sigmf.py, extract_raw_stream.
 The tuning flags (SigMF only) put the device's down-converter in front: the emitter moved to 0 Hz, low-passed and decimated
 (amcpy_amd/ddc.py; sigmf.extract_sigmf, tune=); --resample L/D and --rational put the rational resampler there instead
-(amcpy_amd/resample.py): the rate changes by L / D, and the output file also records `interp` and `decim`.
+(amcpy_amd/resample.py): the rate changes by L / D, and the output file also records `interp` and `decim`.  With the tuning flags,
+`--recover M [--recover-search-hz F]` puts blind carrier recovery of order M (amcpy_amd/carrier.py) between the tuned frames and the
+features; the output file gains `carrier_hz`, `carrier_phase` and `carrier_quality`.  `synth --features-only --recover M` does the same
+to the generated frames and names it in the provenance record.
 `python -m amcpy_amd scan FILE [--nfft N] [--hop H] [--averages A] [--window hann|rect] [--threshold-db X] [--floor-quantile Q]
 [--min-bins B] [--merge-bins G] [--min-rows R] [--format ...] [--scale S] [--device D] [--out PATH] [--annotate OUT.sigmf-meta]`
 finds the emitters of a recording with no raster: the Welch spectrogram on the device, a floor and a mask per row, the occupied
@@ -141,6 +144,12 @@ def build_parser() -> argparse.ArgumentParser:
     rec.add_argument("--oversample", type=float, default=None, metavar="R",
                      help="with --annotation: decimate to R times the annotation's bandwidth (default 2); with --channels: "
                           "1 (critically sampled, the default) or 2")
+    rec.add_argument("--recover", type=int, default=None, metavar="M", choices=(1, 2, 4, 8),
+                     help="with the tuning flags: blind carrier recovery of every frame in front of the features -- the M-th-power "
+                          "estimator (2 BPSK, 4 QPSK, 8 8PSK, 1 a bare carrier) takes gain, residual offset and phase out; the "
+                          "output file gains carrier_hz, carrier_phase and carrier_quality; the frame size a power of two, 64 ... 4096")
+    rec.add_argument("--recover-search-hz", type=float, default=None, metavar="F",
+                     help="with --recover: the largest residual offset looked for, Hz (default: frame size / 16 bins of the M-th power)")
     rec.add_argument("--channels", type=int, default=None, metavar="C",
                      help="every channel of a raster of C (a power of two, 2 ... 256) through the polyphase filter bank; "
                           "--shift-hz then offsets the raster")
@@ -203,6 +212,9 @@ def build_parser() -> argparse.ArgumentParser:
     sy.add_argument("--cpm-span", type=int, default=4, metavar="S", help="GMSK: symbols the phase pulse spans (default 4)")
     sy.add_argument("--features-only", action="store_true",
                     help="write calculated-features/{mod}_features.mat directly; the IQ is made a chunk at a time and never stored")
+    sy.add_argument("--recover", type=int, default=None, metavar="M", choices=(1, 2, 4, 8),
+                    help="with --features-only: every frame through blind carrier recovery of order M in front of the features, as "
+                         "`recording --recover M` treats a recording's; named in the provenance record")
     sy.add_argument("--device", type=int, default=None, help="GPU index (default: current device)")
     return ap
 
@@ -231,9 +243,9 @@ def synth_config(args) -> tuple:
     return replace(cfg, signals=sig), snr
 
 
-def run_synth(args, compute=None, features=None, channel_compute=None) -> list:
-    """The `synth` command (amcpy_amd/waveform.py, run_synth); ``compute`` / ``features`` / ``channel_compute``: injected over
-    numpy (tests)."""
+def run_synth(args, compute=None, features=None, channel_compute=None, recover_compute=None) -> list:
+    """The `synth` command (amcpy_amd/waveform.py, run_synth); ``compute`` / ``features`` / ``channel_compute`` /
+    ``recover_compute``: injected over numpy (tests)."""
     from . import waveform
     cfg, snr = synth_config(args)
     try:
@@ -246,9 +258,9 @@ def run_synth(args, compute=None, features=None, channel_compute=None) -> list:
         from fractions import Fraction
         shape = dict(h=None if args.cpm_h is None else Fraction(args.cpm_h), bt=args.bt, span=args.cpm_span)
         return waveform.run_synth(cfg, mods=split_mods(args.mods), cpm=shape, sps=waveform.parse_sps(args.sps), pulse=args.pulse, beta=args.beta, span=args.span,
-                                  snr=snr, cfo=args.cfo, seed=args.seed, features_only=args.features_only,
+                                  snr=snr, cfo=args.cfo, seed=args.seed, features_only=args.features_only, recover=args.recover,
                                   device=None if args.device is None else f"cuda:{args.device}", compute=compute, features=features,
-                                  channel=fade)
+                                  channel=fade, recover_compute=recover_compute)
     except ValueError as e:
         raise SystemExit(f"synth: {e}")
 
@@ -450,6 +462,15 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None, occu
     channelize = recording_channelize(args)
     survey = recording_survey(args)
     extra = {}
+    recover = None
+    if args.recover is not None:
+        if tune is None:
+            raise SystemExit("--recover needs the tuning flags (--shift-hz ... or --annotation): the frames of one emitter")
+        recover = {"order": args.recover}
+        if args.recover_search_hz is not None:
+            recover["search_hz"] = args.recover_search_hz
+    elif args.recover_search_hz is not None:
+        raise SystemExit("--recover-search-hz needs --recover")
     if sigmf.is_sigmf(path):
         if args.format is not None:
             raise SystemExit("--format: a SigMF recording names its own datatype")
@@ -468,6 +489,14 @@ def run_recording(args, compute=None, tune_compute=None, bank_compute=None, occu
                                      occupancy_compute=occupancy_compute, compute=compute, **kw)
             feats, frame_start = got["features"], got["frame_start"]
             extra.update({k: got[k] for k in ("power", "floor", "occupied", "snr_db", "labels") if k in got})
+        elif recover is not None:
+            try:
+                feats, frame_start, found = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
+                                                                compute=compute, tune={**recording_tune(args), "recover": recover},
+                                                                tune_compute=tune_compute)
+            except ValueError as e:
+                raise SystemExit(f"--recover: {e}")
+            extra.update(found)
         else:
             feats, frame_start = sigmf.extract_sigmf(path, args.frame_size, device=args.device, feature_ids=ids, scale=args.scale,
                                                      compute=compute, tune=tune, tune_compute=tune_compute, channelize=channelize,

@@ -126,22 +126,29 @@ def gather_rows(frames, rows):
     return out
 
 
-def occupied_features(frames_CKN, occ: Occupancy, feature_ids=None):
+def occupied_features(frames_CKN, occ: Occupancy, feature_ids=None, recover=None, sample_rate=None):
     """The 18 features of the occupied cells alone: ``frames_CKN`` complex64 ``(C, K, N)`` (or the ``(C * K, N)`` matrix),
     contiguous -> float32 ``(C, K, 18)`` with NaN in every cell that is not occupied.  :func:`gather_rows`, then
     :func:`amcpy_amd.features.features18` on the packed rows -- the feature kernels are the ones every other path runs --,
-    then a torch scatter."""
+    then a torch scatter.  ``recover`` (default None: the bits without the keyword): ``dict(order=M, search_hz=F,
+    per="frame" | "emitter")`` -- the packed rows go through :func:`amcpy_amd.carrier.recover_frames` in front of the features;
+    an emitter is a CHANNEL (row c of the mask), ``sample_rate`` the channels' own rate (for ``search_hz``)."""
     C, K = int(occ.mask.shape[0]), int(occ.mask.shape[1])
     flat = frames_CKN.reshape(C * K, frames_CKN.shape[-1]) if frames_CKN.dim() == 3 else frames_CKN
     if int(flat.shape[0]) != C * K:
         raise ValueError(f"frames of {C} x {K} cells expected, got {tuple(frames_CKN.shape)}")
-    return _features_at(flat, occ.rows, feature_ids)[0].view(C, K, _lib.NUM_FEATURES)
+    prepare = None
+    if recover is not None:
+        from . import carrier
+        prepare = lambda packed, at: carrier.recover_frames(packed, recover, sample_rate, groups=at // K)[0]      # noqa: E731
+    return _features_at(flat, occ.rows, feature_ids, prepare)[0].view(C, K, _lib.NUM_FEATURES)
 
 
-def _features_at(flat, rows, feature_ids=None) -> tuple:
+def _features_at(flat, rows, feature_ids=None, prepare=None) -> tuple:
     """The gather -> features -> scatter step: ``flat`` complex64 ``(R, N)``, ``rows`` int32 ``(n,)`` -> ``(out, at, packed)``:
     ``out`` float32 ``(R, 18)`` with NaN in every row not listed, and -- None where no row is listed -- the int64 index ``at``
-    and the ``packed`` ``(n, 18)`` features that were scattered by it (the survey scatters its labels by the same index)."""
+    and the ``packed`` ``(n, 18)`` features that were scattered by it (the survey scatters its labels by the same index).
+    ``prepare(packed rows, at)``: what the gathered rows go through in front of the features."""
     import torch
     from .features import features18
 
@@ -149,7 +156,10 @@ def _features_at(flat, rows, feature_ids=None) -> tuple:
     if int(rows.shape[0]) == 0:
         return out, None, None
     at = rows.long()
-    packed = features18(gather_rows(flat, rows), feature_ids=feature_ids).reshape(-1, _lib.NUM_FEATURES)
+    gathered = gather_rows(flat, rows)
+    if prepare is not None:
+        gathered = prepare(gathered, at)
+    packed = features18(gathered, feature_ids=feature_ids).reshape(-1, _lib.NUM_FEATURES)
     out[at] = packed
     return out, at, packed
 

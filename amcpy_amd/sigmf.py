@@ -226,9 +226,10 @@ def _walk(rec, make, device, on_gpu: bool, chunk_samples: int, axis: int = 0, en
         yield j, start, ys, obj
 
 
-def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, chunk_samples):
+def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, chunk_samples, recover=None):
     """The tuned path of :func:`extract_sigmf`: every segment through a :class:`amcpy_amd.ddc.Channelizer` -- or, a
-    rational ``tune``, a :class:`amcpy_amd.resample.Resampler` -- in chunks."""
+    rational ``tune``, a :class:`amcpy_amd.resample.Resampler` -- in chunks.  ``recover``: the frames go through
+    :func:`amcpy_amd.carrier.recover_frames` in front of the features, and a third value comes back: the carrier found per frame."""
     from .ddc import Channelizer
     fmt = rec["sample_format"]
     if is_rational_tune(tune):
@@ -245,6 +246,13 @@ def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune
     if on_gpu:
         import torch
         from .features import features18
+    if recover is not None:
+        if not on_gpu:
+            raise ValueError("recover runs on the device: not beside an injected tune_compute")
+        from . import carrier
+        rate = rec["meta"].get("global", {}).get("core:sample_rate")
+        rate = float(rate) * L / D if rate else None                       # the frames' own rate
+        found = {"cycles": [], "phase": [], "quality": []}
     parts, starts = [], []
     for _, start, ys, _ in _walk(rec, make, device, on_gpu, chunk_samples,
                                  enough=lambda have: left is not None and have >= left * N):
@@ -256,6 +264,10 @@ def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune
             left -= n
         if on_gpu:
             frames = torch.cat(ys)[:n * N].view(n, N)
+            if recover is not None:
+                frames, est = carrier.recover_frames(frames, recover, rate)
+                for key in found:
+                    found[key].append(getattr(est, key).cpu().numpy())
             if compute is None:
                 parts.append(features18(frames, feature_ids=feature_ids).cpu().numpy())
             else:
@@ -263,6 +275,12 @@ def _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune
         else:
             parts.append(np.asarray(compute(np.concatenate(ys)[:n * N].reshape(n, N)), dtype=np.float32))
         starts.append(start + N * D * np.arange(n, dtype=np.int64) // L)
+    if recover is not None:
+        cat = {k: np.concatenate(v) if v else np.empty((0,), np.float64) for k, v in found.items()}
+        carrier_of = {"carrier_hz": cat["cycles"] * (rate or 1.0), "carrier_phase": cat["phase"], "carrier_quality": cat["quality"]}
+        if not parts:
+            return np.empty((0, 18), dtype=np.float32), np.empty((0,), dtype=np.int64), carrier_of
+        return np.concatenate(parts), np.concatenate(starts), carrier_of
     if not parts:
         return np.empty((0, 18), dtype=np.float32), np.empty((0,), dtype=np.int64)
     return np.concatenate(parts), np.concatenate(starts)
@@ -605,6 +623,16 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     emitter comes out at the oversampling asked for, not at the next integer's: ``frame_start[k] = segment start +
     floor(k * frame_size * D / L)``; ``tune_compute`` is then that class's ``compute``.
 
+    ``recover``, A KEY OF THE ``tune`` DICT in any of its forms (absent or None: every result is the bits it is without the key) --
+    ``tune=dict(..., recover=dict(order=M, search_hz=F, per="frame" | "emitter"))``: tuning centres an emitter to within a scan bin, and the residual
+    offset, the carrier's phase and the receiver's level move the features; every frame goes through
+    :func:`amcpy_amd.carrier.recover_frames` (blind M-th-power carrier recovery: gain, frequency and phase taken out; the frame
+    size must be a power of two of 64 ... 4096) in front of the features.  ``search_hz``: the largest residual looked for, in Hz
+    at the frames' rate (needs ``core:sample_rate``; default: frame_size / 16 bins of x^M).  ``per="emitter"``: one frequency, the
+    median, for all frames of a chunk.  A THIRD value is then returned: ``dict(carrier_hz, carrier_phase, carrier_quality)``,
+    one float per frame (Hz at the frames' rate -- cycles per sample where the recording names no rate --, cycles, and the
+    line's share of the M-th power's energy).
+
     ``channelize`` (not together with ``tune``): the recording holds emitters on a raster --
     ``dict(channels=C, oversample=1|2, taps_per_channel=16, taps=None, shift_hz=0.0)``.  Every segment is read in chunks and
     pushed through a :class:`amcpy_amd.bank.FilterBank` of C channels, D = C / oversample (the sample index starts at 0 with
@@ -626,8 +654,13 @@ def extract_sigmf(path, frame_size: int, *, device: Optional[int] = None, featur
     if channelize is not None:
         return _extract_channelized(rec, N, channelize, device, feature_ids, scale, left, compute, bank_compute,
                                     max(1, int(chunk_samples)))
+    recover = None
+    if isinstance(tune, dict) and "recover" in tune:                  # carried by the tune dict; the resolvers never see it
+        recover = tune["recover"]
+        tune = {k: v for k, v in tune.items() if k != "recover"}
     if tune is not None:
-        return _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, max(1, int(chunk_samples)))
+        return _extract_tuned(rec, N, tune, device, feature_ids, scale, left, compute, tune_compute, max(1, int(chunk_samples)),
+                              recover)
     parts, starts = [], []
     engine = None
     try:

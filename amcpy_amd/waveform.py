@@ -475,12 +475,31 @@ def dataset(mods, snr_db, n_frames: int, frame_size: int, *, first_frame: int = 
     return _walk(mods, snrs, F, N, None, first_frame, kw, (len(snrs), F, N), lambda buf, s, n: buf[s])   # (taps: one pulse, or mod -> its pulse)
 
 
-def dataset_features(mods, snr_db, n_frames: int, frame_size: int, *, chunk_frames: int = 1 << 14, features=None, **kw) -> dict:
+def dataset_features(mods, snr_db, n_frames: int, frame_size: int, *, chunk_frames: int = 1 << 14, features=None, recover=None,
+                     recover_compute=None, **kw) -> dict:
     """mod -> ``(n_snr, n_frames, 18)`` float32 (numpy): the frames of :func:`dataset` made ``chunk_frames`` at a time, put
     through :func:`amcpy_amd.features.features18` and dropped, so a training set larger than the device's memory never exists
-    as IQ.  ``features``: tests only, ``f(frames (F, N) complex64 numpy) -> (F, 18)`` beside an injected ``compute``."""
+    as IQ.  ``features``: tests only, ``f(frames (F, N) complex64 numpy) -> (F, 18)`` beside an injected ``compute``.
+    ``recover`` (default None: the bits without the keyword): ``dict(order=M, search=cycles per sample)`` -- every frame through
+    :func:`amcpy_amd.carrier.recover_frames` in front of the features, as ``extract_sigmf(tune=dict(..., recover=...))`` treats a
+    recording's, so that what a classifier is trained on is what it will see.  Every row draws its own carrier, so
+    ``per="emitter"`` has no meaning here and is refused; ``search_hz`` too (the generator knows no rate).  ``recover_compute``:
+    tests only, ``f(frames numpy, recover) -> frames`` beside the injected ``compute`` and ``features``."""
     mods, snrs = _grid(mods, snr_db)
     F, N, chunk = int(n_frames), int(frame_size), max(1, int(chunk_frames))
+    if recover is not None:
+        if not isinstance(recover, dict) or recover.get("per", "frame") != "frame" or recover.get("search_hz") is not None:
+            raise ValueError("recover: dict(order=M, search=cycles per sample); every row is its own emitter and there is no rate")
+        injected = features is not None or kw.get("compute") is not None
+        if injected and (features is None or recover_compute is None):
+            raise ValueError("recover runs on the device: beside an injected compute it needs features and recover_compute too")
+        if injected:
+            plain = features
+            features = lambda x: plain(recover_compute(np.asarray(x), recover))           # noqa: E731
+        else:
+            from . import carrier
+            from .features import features18
+            features = lambda x: features18(carrier.recover_frames(x, recover)[0]).cpu().numpy()           # noqa: E731
     if features is None:
         from .features import features18
         features = lambda x: features18(x).cpu().numpy()           # noqa: E731
@@ -624,13 +643,15 @@ V5_LIMIT = (1 << 31) - 1      # bytes of one MATLAB v5 file's variables
 
 def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0.35, span: int = 16, snr=None, cfo=0.0,
               seed: int = 0, features_only: bool = False, device=None, compute=None, features=None, verbose: bool = True,
-              channel=None, cpm=None) -> list:
+              channel=None, cpm=None, recover=None, recover_compute=None) -> list:
     """The `synth` command: the data set of ``cfg`` (its frame size, frame count and SNR labels, unless ``snr`` names the
     grid) for ``mods`` (default ``cfg.signals.modulations_with_noise``) into ``mat-data/all_modulations.mat`` under the variables
     ``cfg.signals.mat_info`` names -- or, ``features_only``, straight into ``calculated-features/{mod}_features.mat`` with the
     provenance record `extract --resume` trusts.  ``channel``: :func:`dataset`'s keyword, a fading channel every frame passes; the
     provenance record names it.  ``cpm``: ``dict(h=..., bt=..., span=...)``, the pulse of the continuous-phase names among
-    ``mods`` (:func:`cpm_pulse`), named in their provenance records too.  Returns the files written.  ``compute`` / ``features``: injected (tests)."""
+    ``mods`` (:func:`cpm_pulse`), named in their provenance records too.  ``recover``: with ``features_only``, the order M of the
+    blind carrier recovery every frame passes in front of the features (:func:`dataset_features`' ``recover=dict(order=M)``), named in
+    the provenance record as ``"recover": {"order": M}``.  Returns the files written.  ``compute`` / ``features``: injected (tests)."""
     import scipy.io
 
     from .feature_extraction import _provenance, _provenance_path
@@ -657,10 +678,13 @@ def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0
         kw["channel"] = channel
     cfg.paths.ensure_dirs()
     mat_path = cfg.paths.mat_data / cfg.paths.mat_filename
+    if recover is not None and not features_only:
+        raise ValueError("recover belongs to features_only: the container holds the rows as they were generated")
     if features_only:
         written = []
         for m in mods:
-            feats = dataset_features([m], snrs, F, N, features=features, **kw)[m]
+            feats = dataset_features([m], snrs, F, N, features=features, recover=None if recover is None else dict(order=int(recover)),
+                                     recover_compute=recover_compute, **kw)[m]
             out_path = cfg.paths.calculated_features / f"{m}_features.mat"
             scipy.io.savemat(str(out_path), {"Modulation": m, sig.mat_info[m]: feats})
             record = _provenance(cfg, mat_path, sig.mat_info[m])
@@ -670,6 +694,8 @@ def run_synth(cfg, *, mods=None, sps=(8, 1), pulse: str = "rrc", beta: float = 0
                 record["cpm"] = {"order": cpm_order(m), "taps": int(taps[m].phase_taps.shape[0]), "phase_full": taps[m].phase_full,
                                  "h": None if shape["h"] is None else str(Fraction(shape["h"])), "bt": float(shape["bt"]),
                                  "span": int(shape["span"])}
+            if recover is not None:
+                record["recover"] = {"order": int(recover)}
             _provenance_path(out_path).write_text(json.dumps(record) + "\n")
             written.append(out_path)
             if verbose:

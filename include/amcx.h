@@ -102,11 +102,13 @@ extern "C" {
  * AMCX_ABI_MINOR counts what has been ADDED since the version last changed -- new entries and constants, nothing existing changed:
  * 16.1 = training of the classifier's network, one workgroup per model; 16.2 = the waveform generator.
  * AMCX_ABI_PATCH counts in the same way what has been added since the minor last changed: 16.2.1 = the fading multipath channel;
- * 16.2.2 = the generator's continuous-phase modulations. */
+ * 16.2.2 = the generator's continuous-phase modulations; 16.2.3 = blind carrier recovery. */
 #define AMCX_ABI_VERSION 16
 #define AMCX_ABI_MINOR 2
-#define AMCX_ABI_PATCH 2
+#define AMCX_ABI_PATCH 3
 /* The define, version by version, the newest first (a binding may look for the line of the version it was written against):
+ *   ABI 16.2.3: AMCX_ABI_PATCH 3          -- blind carrier recovery: AMCX_CARRIER_*, amcx_carrier_c64, amcx_carrier_plan,
+ *                                            amcx_kernel_name_carrier
  *   ABI 16.2.2: AMCX_ABI_PATCH 2          -- continuous-phase modulations (FSK, MSK, GMSK): amcx_synth_cpm_c64,
  *                                            amcx_synth_cpm_plan, amcx_kernel_name_synth_cpm
  *   ABI 16.2.1: AMCX_ABI_PATCH 1          -- the fading channel: AMCX_CHANNEL_*, amcx_channel_c64, amcx_channel_plan,
@@ -1211,6 +1213,69 @@ int amcx_synth_cpm_c64(uint64_t seed, uint64_t row_index0, int64_t sample_index0
                        const float* sigma_dev, int64_t frames_per_group, const uint32_t* acc_in_dev, uint32_t* acc_out_dev,
                        int32_t segments, void* out, void* hip_stream);
 const char* amcx_kernel_name_synth_cpm(void);
+
+/*
+ * ABI 16.2.3.  BLIND CARRIER RECOVERY: n_rows rows of n complex64 samples to one 32-byte record per row -- power, gain, the
+ * carrier's offset and phase as the down-converter's integer words, a quality figure -- and, where out is given, the row with
+ * gain, frequency and phase taken out, in ONE launch on hip_stream (amcpy_amd/csrc/amcx_carrier_kernel.h).  The estimator raises
+ * the normalised row to the M-th power (M = order: 2 for BPSK, 4 for QPSK, 8 for 8PSK, 1 for a bare carrier), transforms it and
+ * interpolates the largest line inside a bounded range.  It allocates nothing, never synchronises and can be captured in a
+ * graph; no atomics, no workgroup waits for another.  N = n = 2^lg, M = 2^lm, sb = search_bins; tests/carrier_ref.py restates
+ * every line in numpy float32, operation by operation.
+ *
+ *   the record       32 bytes, 8-byte aligned: int64 phase_step, uint32 phase0, int32 bin, float frac, float power, float gain,
+ *                    float quality
+ *   power            q[n] = fma(im, im, re re);  THE TREE: q'[i] = q[2 i] + q[2 i + 1] until one value is left (an order that
+ *                    depends on N alone);  power = tree * (1 / N), exact
+ *   gain             1.0f / sqrtf(power), root and quotient correctly rounded.  A power of 0, NaN or inf: gain 0, a record of
+ *                    zeros beside power, an output row of zeros
+ *   u, z             u[n] = (gain re, gain im);  z = u, squared lm times with mul(z, z),
+ *                    mul(d, w) = (fma(d.re, w.re, -(d.im w.im)), fma(d.re, w.im, d.im w.re))  -- the spectrogram's product.
+ *                    (u has unit power, so the eighth power stays inside float32 whatever the level of x.)
+ *   Z                THE OPERATION SEQUENCE of the spectrogram (ABI 15, amcx_psd_kernel.h) on z, no window product;
+ *                    P[k] = fma(Z.im, Z.im, Z.re Z.re)
+ *   bin              over the SIGNED k of -sb ... sb (Z[k] is Z[k mod N]): the key is P[k], or -1 where P[k] is NaN; bin has the
+ *                    largest key, ties to the lowest signed k.  The bound matters beyond speed: under a root-raised-cosine
+ *                    pulse z also has lines one symbol rate away.
+ *   frac             a, b, c = Z[bin - 1], Z[bin], Z[bin + 1];  num = c - a;  den = (b - a) + (b - c), per component;
+ *                    frac = -(fma(num.im, den.im, num.re den.re) / fma(den.im, den.im, den.re den.re)), 0 unless |frac| <= 0.5
+ *   phase_step       F = (int64)rintf(frac 2^31);  step_M = bin 2^(64 - lg) + F 2^(33 - lg);  phase_step = step_M >> lm, an
+ *                    ARITHMETIC shift: the carrier's offset in the down-converter's unit, 2^-64 cycle per sample
+ *   phase0           w = (int64)rintf((atan2f(b.im, b.re) * (float)(1 / 2 pi)) * 2^32)   the device library's atan2f;
+ *                    theta_M = (uint32)(w - ((F (N - 1)) >> lg)), the shift arithmetic;  phase0 = theta_M >> lm, a LOGICAL shift,
+ *                    in 2^-32 cycle.  THE M-FOLD AMBIGUITY: the M-th power cannot tell the carrier's phase from that phase plus
+ *                    any multiple of 1 / M cycle; phase0 is the one of those M equivalent phases in [0, 1 / M).  After recovery
+ *                    a constellation stands upright up to one of its own M-fold rotations.
+ *   quality          P[bin] / ((float)N * tree(|z|^2)), |z|^2 formed as q is: 1 for a tone on a bin, of the order of 1 / N for
+ *                    noise -- the caller's reason to reject a row
+ *   output           phi(n) = [PHASE] ((uint64)phase0 << 32) + [FREQ] n phase_step   (mod 2^64)
+ *                    out[r, n] = mul(v, mixer(top 32 bits of 0 - phi(n))),  v = u[n] under AMCX_CARRIER_GAIN, in[r, n] otherwise;
+ *                    mixer: the down-converter's (ABI 11).  The product is always formed, also by 1 + 0j.
+ *
+ * MODES.  out_c64_dev NULL: estimate only.  AMCX_CARRIER_GIVEN: est_dev is INPUT -- nothing is estimated, order and search_bins
+ * are checked and unused, a record's gain, phase0 and phase_step are applied as they are under the three apply flags (one
+ * estimate for many frames of an emitter, or one smoothed on the host); out is then required.
+ * POSITION INDEPENDENCE.  A record's and a row's bits depend on that row's samples and the scalar arguments alone: not on the
+ * row's place in the call, the strides, the grid, or a start on 8 rather than 16 bytes.  Only phase0 goes through a library
+ * routine (atan2f) and is held to a bound; every other field and, given the record, every output sample is exact.
+ *
+ *   - limits: n a power of two of 64 ... 4096; order 1, 2, 4 or 8; 0 <= search_bins <= n / 2 - 1; no flag but the four; GIVEN
+ *     needs out; 0 <= n_rows, in_row_stride >= n, out_row_stride >= n where out is given, n_rows times either stride <= 2^58;
+ *     at most 2^31 - 1 groups of 4096 / n rows
+ *   - checks, in the order of every launching entry: the limits in that order; n_rows == 0 is AMCX_OK here and writes nothing;
+ *     then null pointers (in, est), alignment (all 8), a pointer on another device, and the byte ranges of in and out, which
+ *     must not overlap.  Ordinary vector stores only.
+ * amcx_carrier_plan (host-only): the rows a workgroup holds (4096 / n) and its bytes of static LDS; each pointer may be NULL.
+ * amcx_kernel_name_carrier (host-only): the kernel's name, a static string.
+ */
+#define AMCX_CARRIER_GAIN 1u
+#define AMCX_CARRIER_FREQ 2u
+#define AMCX_CARRIER_PHASE 4u
+#define AMCX_CARRIER_GIVEN 8u
+int amcx_carrier_plan(int32_t n, int32_t* rows_per_workgroup, int32_t* lds_bytes);
+int amcx_carrier_c64(const void* in_c64_dev, int64_t n_rows, int32_t n, int64_t in_row_stride, int32_t order, int32_t search_bins,
+                     uint32_t flags, void* est_dev, void* out_c64_dev, int64_t out_row_stride, void* hip_stream);
+const char* amcx_kernel_name_carrier(void);
 
 #ifdef __cplusplus
 }
