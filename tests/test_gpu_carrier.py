@@ -13,6 +13,7 @@ import pytest
 from amcpy_amd import _lib, carrier, waveform as wf
 from tests import carrier_ref as ref
 from tests import test_carrier_host as host
+from tests.plain_grids import LINE
 
 pytestmark = pytest.mark.gpu
 
@@ -74,10 +75,11 @@ def _rows(R, N, seed, order=4):
 
 # ---- the restatement, by == -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("order", ref.ORDERS)
-@pytest.mark.parametrize("N", [64, 128, 512, 4096])
+@pytest.mark.parametrize("N", [64, 128, 256, 512, 1024, 2048, 4096])
 def test_records_and_rows_equal_the_restatement(N, order):
-    """3 + 3, 3 + 4, 3 + 3 + 3 and 4 + 4 + 4 passes; 64, 32, 8 and 1 rows per workgroup; one row, and three workgroups the last
-    with one live slot; four search ranges; rows at a stride of N + 3 in and out, out's padding untouched."""
+    """Every size: 3 + 3, 3 + 4, 4 + 4, 3 + 3 + 3, 3 + 3 + 4, 3 + 4 + 4 and 4 + 4 + 4 passes; 64 ... 1 rows per workgroup, 4 ... 256
+    threads per row (64: exactly one wave, no LDS level; 128: the pair sums of the tree and of the peak); one row, and three
+    workgroups the last with one live slot; four search ranges; rows at a stride of N + 3 in and out, out's padding untouched."""
     torch = _torch()
     G = 4096 // N
     R = 2 * G + 1
@@ -103,7 +105,7 @@ def test_records_and_rows_equal_the_restatement(N, order):
 
 
 # ---- exact cases --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N", [64, 128, 512, 4096])
+@pytest.mark.parametrize("N", [64, 128, 256, 512, 1024, 2048, 4096])
 def test_quarter_rate_tone_is_recovered_exactly(N):
     x = (1j ** (np.arange(N) % 4)).astype(np.complex64)[None, :]
     y, est = carrier.recover(_dev(x), 1, search_bins_=N // 2 - 1)
@@ -138,6 +140,113 @@ def test_tones_at_the_edge_of_the_range_are_found_and_one_beyond_it_is_not_chose
         assert _records(carrier.estimate(_dev(x), 1, search_bins_=sb + 1))[0]["bin"] == out
 
 
+SIZES = (64, 128, 256, 512, 1024, 2048, 4096)
+
+
+def _exact_tones(N, parts):
+    """sum of a exp(2 pi j k n / N) per row: parts is ((k (R,), a), ...), k in bins -- whole or dyadic fractions, so that k n is
+    exact in float64 and is reduced mod N before the angle is formed -- -> complex64 (R, N)"""
+    n = np.arange(N, dtype=np.float64)[None, :]
+    x = np.zeros((len(parts[0][0]), N), np.complex128)
+    for k, a in parts:
+        index = np.fmod(np.asarray(k, dtype=np.float64)[:, None] * n, float(N))
+        if np.all(index == np.rint(index)):                                # whole bins: the N angles there are, looked up
+            wave = np.exp(2j * np.pi * (np.arange(N) / N))[index.astype(np.int64) % N]
+        else:
+            wave = np.exp(2j * np.pi * (index / N))
+        x += np.asarray(a).reshape(-1, 1) * wave                             # (a real or complex, float64 / complex128)
+    return x.astype(np.complex64)
+
+
+@pytest.mark.parametrize("N", SIZES)
+def test_the_peak_is_found_in_every_bin_and_nowhere_outside_the_range(N):
+    """One row per signed bin k = -N / 2 ... N / 2 - 1 and search range sb: a tone of amplitude 4 at k and one of amplitude 1 at
+    m = (k mod (2 sb + 1)) - sb, which lies inside the range (m = k: the single tone).  The record's bin is k where |k| <= sb
+    and m otherwise -- no tolerance: the second line is 12 dB down and the leakage of whole-bin tones is at rounding level.
+    So every lane's signed-bin mapping through the bit reversal, every lane's skip of the bins outside the range and the
+    cross-wave reduction with the winner in any wave are asked for, at every size.  Every field but phase0 against the
+    restatement too: on all rows for N <= 1024; at 2048 and 4096 on the lowest 64 bins of the transform, the highest 64 (the
+    signed bins -64 ... 63) and 128 seeded ones between (a cap on the reference's time; `bin` is checked on every row).  A failure lists the bins: a shared residue points at the bit reversal,
+    a shared run of 16 at a lane, a shared wave at the LDS level."""
+    k = np.arange(-N // 2, N // 2)
+    some = np.arange(N)
+    if N > 1024:                                                          # FFT bins: signed bin k stands in row k + N / 2
+        between = np.random.default_rng([41, N]).choice(np.arange(64, N - 64), 128, replace=False)
+        cut = np.concatenate([np.arange(64), between, np.arange(N - 64, N)])
+        some = np.sort((cut + N // 2) % N)
+        assert some.size == 256 == np.unique(some).size
+    for sb in (0, 1, N // 16, N // 2 - 1):
+        m = k % (2 * sb + 1) - sb
+        x = _exact_tones(N, ((k, 4.0), (m, np.where(m == k, 0.0, 1.0))))
+        want_bin = np.where(np.abs(k) <= sb, k, m)
+        got = _records(carrier.estimate(_dev(x), 1, search_bins_=sb))
+        wrong = np.flatnonzero(got["bin"] != want_bin)
+        assert wrong.size == 0, (f"N={N} sb={sb}: {wrong.size} rows with the wrong bin; k, got, expected: "
+                                 f"{[(int(k[r]), int(got['bin'][r]), int(want_bin[r])) for r in wrong[:48]]}")
+        want = ref.estimate32(x[some], 1, sb)["rec"]
+        assert np.array_equal(want["bin"], want_bin[some])
+        _same_fields(got[some], want)
+    print(f"N={N}: {4 * N} rows, every bin in four ranges; {some.size} rows per range against the restatement")
+
+
+@pytest.mark.parametrize("N", [64, 1024, 2048, 4096])
+def test_tones_between_bins_equal_the_restatement_at_the_cut(N):
+    """Unit tones at k + f, f = 1/4, 1/2 - 2^-10, 1/2, 1/2 + 2^-10 and 3/4, for 32 seeded k of both signs with 0, -1 and N / 2 - 2
+    among them, the whole range searched: every field but phase0 by ==, phase0 within its bound, the output rows the bytes of
+    the restatement applied to the device's records.
+
+    WHAT IS HELD: the device takes the same side of the `|frac| <= 0.5` cut as the restatement does on the same bits, and
+    writes the same words for it.  WHAT IS NOT: the estimator's accuracy at a half bin.  A tone half a bin off has two equal
+    lines; whichever wins, the interpolated frac is +-0.5 give or take a rounding, and where it lands beyond the cut the
+    contract sets it to 0 -- the record is then half a bin off.  That is the contract's known weakness, not an error of the
+    kernel; the count of such rows is printed.
+
+    The lone tones all stay inside the cut: the interpolation is exact for one line.  So 4 x 32 rows more stand AT it.  PUSHED:
+    the tone at k + 1/2 - 2^-10 with a line of +-2^-6 at k - 1 in phase with the tone's own leakage there; + widens Z[k - 1]
+    and puts frac beyond 0.5, - keeps it inside.  PAIRED: whole-bin lines of 1.5 at k and 1 at k + 1 or k - 1, num / den =
+    -+1 / 2 but for the transform's roundings: at every size some of the 32 rows land on |frac| = 0.5 exactly (kept: <=), some
+    an ulp beyond (cut to 0) and some an ulp inside -- the test asserts that the restatement has all three on either side.
+
+    IF THAT ASSERTION FAILS (before anything runs on the device), the rows are no longer what they were made for: they are built
+    with numpy's float64 exp, and which of the 32 land where depends on its last bits.  Nothing is wrong with the kernel then.
+    Draw other k (the seed 17 below) or other amplitudes of the same ratio (3 and 2, 0.75 and 0.5) until the restatement has
+    all three cases on either side at every size again; the comparison with the device needs no change."""
+    order, sb = 1, N // 2 - 1
+    rng = np.random.default_rng([N, 17])
+    pool = np.setdiff1d(np.arange(-N // 2 + 1, N // 2 - 1), [0, -1, N // 2 - 2])
+    ks = np.concatenate([[0, -1, N // 2 - 2], rng.choice(pool, 29, replace=False)])
+    assert (ks < 0).sum() >= 4 and (ks > 0).sum() >= 4
+    fs = np.array([0.25, 0.5 - 2.0 ** -10, 0.5, 0.5 + 2.0 ** -10, 0.75])
+    at = (ks[:, None] + fs[None, :]).reshape(-1)
+    x = _exact_tones(N, ((at, 1.0),))
+    # PUSHED (the leakage of a tone at k + 1/2 in bin k - 1 is i / pi N / 1.5: the second line is imaginary) and PAIRED
+    near, n_k = ks + fs[1], ks.size
+    pushed = [_exact_tones(N, ((near, np.ones(n_k)), (ks - 1, np.full(n_k, s * 2.0 ** -6 * 1j)))) for s in (1.0, -1.0)]
+    paired = [_exact_tones(N, ((ks, np.full(n_k, 1.5)), (ks + side, np.ones(n_k)))) for side in (1, -1)]
+    x = np.concatenate([x] + pushed + paired)
+    want = ref.estimate32(x, order, sb)
+    made = want["rec"]["frac"][at.size:].reshape(4, n_k)                       # of the restatement: what the rows were made for
+    assert (made[0] == 0).all() and not (made[1] == 0).any()
+    for side in (2, 3):
+        assert (np.abs(made[side]) == 0.5).any() and (made[side] == 0).any() and ((made[side] != 0) & (np.abs(made[side]) < 0.5)).any()
+    assert np.array_equal(want["rec"]["bin"][at.size:].reshape(4, n_k), np.tile(ks, (4, 1)))
+    _, xin = _padded(x)
+    y, est = carrier.recover(xin, order, search_bins_=sb)
+    got = _records(est)
+    lone, extra = got["frac"][:at.size].reshape(n_k, fs.size), got["frac"][at.size:].reshape(4, n_k)
+    count = lambda rows: rows.sum(axis=-1).tolist()                           # noqa: E731  rows of a block that meet a condition
+    print(f"N={N}: {x.shape[0]} rows, {int((got['frac'] == 0).sum())} fell to frac = 0 at the cut "
+          f"(restatement: {int((want['rec']['frac'] == 0).sum())})")
+    print(f"  lone tones, {n_k} per f = {fs.tolist()}: {count((lone == 0).T)} at 0")
+    print(f"  pushed, {n_k} per sign: {count(extra[:2] == 0)} at 0;  paired, {n_k} per side: {count(extra[2:] == 0)} at 0, "
+          f"{count(np.abs(extra[2:]) == 0.5)} on |frac| = 0.5 exactly")
+    _same_fields(got, want["rec"])
+    worst = _phase0_ratio(got, want, order)
+    print(f"N={N}: worst phase0 distance / tolerance = {worst:.3f}")
+    assert worst <= 1.0
+    assert np.array_equal(_cpu(y).view(np.uint32), ref.apply32(x, got, ALL).view(np.uint32))
+
+
 def test_peak_at_bin_0_reads_its_neighbour_at_n_minus_1():
     """Z[-1] = 0.6 N beside Z[0] = N and Z[1] = 0.05 N, all in phase: num = -0.55 N, den = 1.35 N, frac = +0.55 / 1.35 -- and the
     mirror image gives its negative; a kernel that read Z[1] for Z[-1], or index -1, would give neither."""
@@ -151,7 +260,7 @@ def test_peak_at_bin_0_reads_its_neighbour_at_n_minus_1():
         assert mirrored["bin"][0] == 0 and abs(mirrored["frac"][0] + 0.55 / 1.35) < 1e-4
 
 
-@pytest.mark.parametrize("N", [64, 1024, 4096])
+@pytest.mark.parametrize("N", [64, 256, 1024, 2048, 4096])
 def test_zero_nan_and_inf_rows_leave_their_neighbours_alone(N):
     good = _rows(4, N, seed=77)
     x = np.stack([good[0], np.zeros(N, np.complex64), good[1], np.full(N, np.nan + 0j, np.complex64), good[2],
@@ -226,6 +335,87 @@ def test_a_row_is_the_same_bytes_wherever_it_stands(N, order):
     yb, eb = carrier.recover(xd[cut:], order)
     assert _records(ea).tobytes() + _records(eb).tobytes() == rec.tobytes()
     assert _cpu(ya).tobytes() + _cpu(yb).tobytes() == out.tobytes()
+
+
+def _rows_equal_base(big, base, period, points=1 << 24):
+    """big[r] == base[r mod period] as bytes for every row r, compared on the device in slabs of `points` 4-byte words"""
+    torch = _torch()
+    R, width = int(big.shape[0]), int(big.shape[1])
+    step = max(1, points // width)
+    for r0 in range(0, R, step):
+        r1 = min(R, r0 + step)
+        index = torch.arange(r0, r1, device=big.device) % period
+        if not torch.equal(big[r0:r1], base[index]):
+            bad = torch.nonzero((big[r0:r1] != base[index]).any(dim=1))[:4].flatten().tolist()
+            return [r0 + r for r in bad]
+    return []
+
+
+@pytest.mark.parametrize("N,order", [(64, 4), (4096, 1)])
+def test_rows_over_two_lines_of_the_grid(N, order):
+    """LINE + 1 workgroups -- 64 slots each, and one: the launch is folded into two lines, so the `blockIdx.y` term, the
+    whole-workgroup return of the 65 535 workgroups behind the last one, and `r * stride` and `est[r]` at rows of 2^22 and more
+    (N = 64) are executed.  A carrier workgroup always holds 4096 points, so LINE + 1 groups are 2.1 GB of input whatever N:
+    that is why this case stops at two lines, the second with one live workgroup.  A third line would double the memory and add
+    only a repeat of the second.
+
+    The rows are a base of B rows repeated on the device (B coprime to the slots per workgroup: a base row lands in every
+    slot); nothing of this size crosses the host.  The base alone is a call of at most 16 workgroups, the shape the tests above
+    hold to the restatement, and is held to it here again; record r and output row r of the large call are the bytes of the
+    base call's r mod B -- from recover, from estimate, and from apply (GIVEN: est[r0 + tid] is read at r0 >= 2^22).  Records
+    and rows are written into buffers one row longer, filled with 0xFF: the row beyond keeps them."""
+    torch = _torch()
+    G = 4096 // N
+    R = LINE * G + 1
+    groups = -(-R // G)
+    print(f"carrier N={N}: {R} rows in {groups} workgroups, LINE = {LINE}")
+    assert groups >= LINE + 1
+    assert _lib.carrier_plan(N)[0] == G
+    B = 997 if N < 4096 else 13
+    assert np.gcd(B, G) == 1
+    base = _rows(B, N, seed=500 + N, order=order)
+    base_dev = _dev(base)
+    yb, eb = carrier.recover(base_dev, order)
+    rec_b = _records(eb)
+    want = ref.estimate32(base, order, N // 16)
+    _same_fields(rec_b, want["rec"])
+    worst = _phase0_ratio(rec_b, want, order)
+    print(f"carrier N={N}: the base's worst phase0 distance / tolerance = {worst:.3f}")
+    assert worst <= 1.0
+    assert np.array_equal(_cpu(yb).view(np.uint32), ref.apply32(base, rec_b, ALL).view(np.uint32))
+    i32 = lambda t: torch.view_as_real(t).view(torch.int32)                   # noqa: E731  (R, N) complex64 -> (R, 2 N) words
+    x = out = again = raw = None
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    try:
+        x = base_dev.repeat(-(-R // B), 1)[:R]
+        assert x.is_contiguous() and x.shape == (R, N)
+        out = torch.empty((R + 1, N), dtype=torch.complex64, device="cuda")
+        i32(out).fill_(-1)
+        y, est = carrier.recover(x, order, out=out[:R])
+        assert len(est) == R and _rows_equal_base(est.raw, eb.raw, B) == []
+        assert _rows_equal_base(i32(y), i32(yb), B) == []
+        assert bool((i32(out)[R] == -1).all())
+        # estimate only, into a buffer of R + 1 records
+        raw = torch.full((R + 1, carrier.RECORD_BYTES), 255, dtype=torch.uint8, device="cuda")
+        _lib.check(_lib.load().amcx_carrier_c64(x.data_ptr(), R, N, N, order, N // 16, 0, raw.data_ptr(), None, 0,
+                                                torch.cuda.current_stream().cuda_stream))
+        assert torch.equal(raw[:R], est.raw) and bool((raw[R] == 255).all())
+        assert torch.equal(carrier.estimate(x, order).raw, est.raw)
+        # GIVEN
+        again = torch.empty((R + 1, N), dtype=torch.complex64, device="cuda")
+        i32(again).fill_(-1)
+        assert carrier.apply(x, est, out=again[:R]) is not None
+        assert torch.equal(i32(again), i32(out))
+        assert torch.equal(raw[:R], est.raw)                                  # GIVEN: the records are input
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated()
+        print(f"carrier N={N}: peak device memory {peak / 1e9:.2f} GB")
+        assert peak < 10e9
+    finally:
+        del x, out, again, raw
+        y = est = None
+        torch.cuda.empty_cache()
 
 
 def test_graph_replay_equals_the_plain_call():

@@ -9,6 +9,7 @@ import pytest
 
 from amcpy_amd import _lib, channel as ch, ddc, waveform as wf
 from tests import channel_ref as ref
+from tests.plain_grids import LINE
 
 pytestmark = pytest.mark.gpu
 
@@ -78,6 +79,73 @@ def test_equals_the_restatement_bit_for_bit(L, S, b, H, where):
         assert y[f, :count].tobytes() == want.tobytes(), (L, S, b, H, where, f, int(np.argmax(y[f, :count] != want)))
     assert (y[:, count:] == SENTINEL).all()
     assert np.isfinite(y.view(np.float32)).all() and not np.array_equal(y[0, :count], y[1, :count])
+
+
+def _seam_and_seeded_rows(R, count, seed):
+    """the rows on either side of every line seam, the first and the last, and `count` seeded ones"""
+    seams = [0, 1, LINE - 1, LINE, LINE + 1, 2 * LINE - 1, 2 * LINE]
+    assert R == 2 * LINE + 1
+    return np.union1d(seams, np.random.default_rng(seed).choice(R, count, replace=False))
+
+
+def test_rows_over_three_lines_of_the_grid():
+    """2 LINE + 1 rows of one tile: the launch is folded into three lines, the last with one live workgroup, so the
+    `blockIdx.y` term, the whole-workgroup return and `f * stride` at f >= 2^16 are executed.  The seam rows and 2048 seeded ones
+    == the restatement (a cap on the reference's time, about 1 ms a row); EVERY row the bytes of three calls of at most LINE
+    rows -- single-line grids, the shape the tests above hold to the restatement -- with row_index0 advanced.  The same with a
+    sigma per group of three rows on the device, a.sigma[f / frames_per_group] at f >= 2^16, cut on group boundaries."""
+    torch = _torch()
+    L, S, b, H, count, n0 = 2, 2, 1, 1, 2, 5
+    R = 2 * LINE + 1
+    tile, _ = _lib.channel_plan(L, S, b, H)
+    tiles_per_row = -(-count // tile)
+    assert tiles_per_row == 1
+    items = R * tiles_per_row
+    print(f"channel: {items} items, LINE = {LINE}")
+    assert items >= 2 * LINE + 1
+    profile, doppler = _profile(L, H, S), 0.01
+    assert sorted(profile.delays.tolist()) == [0, 1]
+    x = _signal(R, count + H, 29)
+    _, x_dev = _strided(x, pad=3)
+    assert x_dev.stride(0) == count + H + 3
+    kw = dict(doppler=doppler, sinusoids=S, interp_log2=b, seed=SEED, sample_index0=n0)
+
+    def whole(**more):
+        buf = torch.full((R + 2, count + 5), complex(SENTINEL), dtype=torch.complex64, device="cuda")
+        got = ch.apply(x_dev, profile, row_index0=ROW0, out=buf[:R, :count], **kw, **more)
+        assert got.data_ptr() == buf.data_ptr() and got.stride(0) == count + 5
+        y = _cpu(buf)
+        assert (y[:R, count:] == SENTINEL).all() and (y[R:] == SENTINEL).all()
+        return np.ascontiguousarray(y[:R, :count])
+
+    def in_cuts(cuts, sigma_of=None, **more):
+        parts, at = [], 0
+        for rows in cuts:
+            assert rows <= LINE
+            extra = {} if sigma_of is None else dict(sigma=sigma_of(at, rows))
+            parts.append(_cpu(ch.apply(x_dev[at:at + rows], profile, row_index0=ROW0 + at, **kw, **extra, **more)))
+            at += rows
+        assert at == R
+        return np.concatenate(parts)
+
+    y = whole()
+    rec, dm = profile.records(S), ch.doppler_max_of(doppler)
+    for f in _seam_and_seeded_rows(R, 2048, 31):
+        want = ref.restate(x[f], rec, S, b, dm, ref.RANDOM_PHASE, seed=SEED, r=ROW0 + int(f), n0=n0)
+        assert y[f].tobytes() == want.tobytes(), (int(f), y[f], want)
+    assert y.tobytes() == in_cuts((LINE, LINE, 1)).tobytes()
+    # a sigma per group of three rows, on the device
+    fpg = 3
+    sig = torch.tensor([0.5, 0.0, 2.0], dtype=torch.float32, device="cuda").repeat(-(-R // (3 * fpg)))[:-(-R // fpg)].contiguous()
+    noisy = whole(sigma=sig, frames_per_group=fpg)
+    cuts = (LINE - 1, LINE - 1, 3)
+    assert all(rows % fpg == 0 for rows in cuts)
+    parts = in_cuts(cuts, sigma_of=lambda at, rows: sig[at // fpg:(at + rows) // fpg].contiguous(), frames_per_group=fpg)
+    assert noisy.tobytes() == parts.tobytes()
+    group = np.arange(R) // fpg
+    silent = group % 3 == 1
+    assert silent[LINE:].sum() >= LINE // 3 and noisy[silent].tobytes() == y[silent].tobytes()
+    assert (noisy[~silent] != y[~silent]).any(axis=1).all()
 
 
 def test_one_unit_line_of_sight_is_the_identity_and_the_noise_is_the_generators():

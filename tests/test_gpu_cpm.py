@@ -11,6 +11,7 @@ import pytest
 
 from amcpy_amd import _lib, channel as ch, waveform as wf
 from tests import cpm_ref as ref
+from tests.plain_grids import LINE
 
 pytestmark = pytest.mark.gpu
 
@@ -142,6 +143,78 @@ def test_many_short_rows_and_the_plans_one_segment():
         want, a1 = ref.restate(SEED, ROW0 + f, 0, count, 2, pulse.phase_taps, pulse.phase_full, 8, 1)
         assert np.array_equal(y[f], want) and int(state[f]) == a1, f
     assert _cpu(wf.generate("GMSK", R, count, seed=SEED, row_index0=ROW0, segments=1)).tobytes() == y.tobytes()
+
+
+def test_rows_over_three_lines_of_the_grid():
+    """2 LINE + 1 rows of one segment: the launch is folded into three lines, the last with one live workgroup, so the
+    `blockIdx.y` term, the whole-workgroup return and `f * row_stride`, `acc_out[f]` at f >= 2^16 are executed.  The seam rows and
+    2048 seeded ones == the restatement, samples and acc_out (a cap on the reference's time, about 0.6 ms a row); EVERY row the
+    bytes of three calls of at most LINE rows -- single-line grids -- with row_index0 advanced.
+
+    Then 32 769 rows of four tiles in four segments, 131 076 items: item = 4 f + segment, so the lines change between rows
+    16 383 and 16 384 and inside the last row's line alone stand its four segments.  Every row the bytes of the call with one
+    segment, samples and acc_out.  The restatement of such a row costs about 5 ms, a quarter of the rows 40 s: so the rows
+    beside the two seams, the first, the last, and those with f = 0 mod 4 among 1024 seeded ones go to it (about 260 rows)."""
+    torch = _torch()
+    pulse = wf.design_cpfsk(1)
+    T, U, V, order, count = len(pulse.phase_taps), 1, 1, 2, 2
+    R = 2 * LINE + 1
+    tile, _, seg = _lib.synth_cpm_plan(T, U, V, R, count)
+    assert seg == 1
+    items = R * seg
+    print(f"cpm: {items} items, LINE = {LINE}")
+    assert items >= 2 * LINE + 1
+    kw = dict(sps=(U, V), taps=pulse, seed=SEED, cfo=0.01)
+    buf = torch.full((R + 2, count + 3), complex(SENTINEL), dtype=torch.complex64, device="cuda")
+    acc = torch.full((R + 2,), -1, dtype=torch.int32, device="cuda")
+    got = wf.generate("MSK", R, count, row_index0=ROW0, acc_out=acc[:R], out=buf[:R, :count], segments=1, **kw)
+    assert got.data_ptr() == buf.data_ptr() and got.stride(0) == count + 3
+    y, state = _cpu(buf), _words(acc)
+    assert (y[:R, count:] == SENTINEL).all() and (y[R:] == SENTINEL).all() and (state[R:] == 0xFFFFFFFF).all()
+    y = np.ascontiguousarray(y[:R, :count])
+    seams = [0, 1, LINE - 1, LINE, LINE + 1, 2 * LINE - 1, 2 * LINE]
+    for f in np.union1d(seams, np.random.default_rng(37).choice(R, 2048, replace=False)):
+        want, a1 = ref.restate(SEED, ROW0 + int(f), 0, count, order, pulse.phase_taps, pulse.phase_full, U, V, cfo_max=wf.cfo_max_of(0.01))
+        assert y[f].tobytes() == want.tobytes() and int(state[f]) == a1, int(f)
+    parts, states, at = [], [], 0
+    for rows in (LINE, LINE, 1):
+        a = torch.full((rows,), -1, dtype=torch.int32, device="cuda")
+        parts.append(_cpu(wf.generate("MSK", rows, count, row_index0=ROW0 + at, acc_out=a, segments=1, **kw)))
+        states.append(_words(a))
+        at += rows
+    assert np.concatenate(parts).tobytes() == y.tobytes() and np.concatenate(states).tobytes() == state[:R].tobytes()
+    del buf, acc, got
+
+    # rows of four segments across the seams
+    R4, segments = LINE // 2 + 1, 4
+    count4 = 3 * tile + 1
+    # the launch's own count (cpm_plan of amcx.hip, restated): the asked segments, at most the row's tiles, recounted from their length
+    tiles_per_row = -(-count4 // tile)
+    tiles_per_seg = -(-tiles_per_row // min(segments, tiles_per_row))
+    launched = -(-tiles_per_row // tiles_per_seg)
+    assert (tiles_per_row, tiles_per_seg, launched) == (4, 1, segments)
+    items = R4 * launched
+    print(f"cpm: {items} items in {segments} segments a row, LINE = {LINE}")
+    assert items >= 2 * LINE + 1
+    a4 = torch.full((R4,), -1, dtype=torch.int32, device="cuda")
+    a1 = torch.full((R4,), -1, dtype=torch.int32, device="cuda")
+    y4 = y1 = None
+    try:
+        y4 = wf.generate("MSK", R4, count4, row_index0=ROW0, acc_out=a4, segments=segments, **kw)
+        y1 = wf.generate("MSK", R4, count4, row_index0=ROW0, acc_out=a1, segments=1, **kw)
+        words = lambda t: torch.view_as_real(t).view(torch.int32)             # noqa: E731
+        assert torch.equal(words(y4), words(y1)) and torch.equal(a4, a1)
+        seeded = np.random.default_rng(41).choice(R4, 1024, replace=False)
+        rows = np.union1d([0, LINE // 4 - 1, LINE // 4, LINE // 4 + 1, R4 - 2, R4 - 1], seeded[seeded % 4 == 0])
+        some, state = _cpu(y4[torch.from_numpy(rows).cuda()]), _words(a4)
+        for i, f in enumerate(rows):
+            want, acc1 = ref.restate(SEED, ROW0 + int(f), 0, count4, order, pulse.phase_taps, pulse.phase_full, U, V,
+                                     cfo_max=wf.cfo_max_of(0.01))
+            assert some[i].tobytes() == want.tobytes() and int(state[f]) == acc1, int(f)
+        print(f"cpm: {rows.size} rows of {count4} samples against the restatement")
+    finally:
+        del y4, y1
+        torch.cuda.empty_cache()
 
 
 def test_rows_and_samples_cut_into_calls_equal_one_call():
