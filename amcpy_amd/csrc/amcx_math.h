@@ -228,6 +228,31 @@ __device__ __forceinline__ bool cancellation_suspect(const float (&s)[15], float
   return f;
 }
 
+// ---------------------------------------------------------------------------
+// NARROW PHASE.  The N = 2048 wave kernels sum theta, |theta| and theta^2 about ZERO (StatsT, kShiftedPhase = false,
+// amcx_wave_kernel.h), so f2 and f3 come from var = sum theta^2 / N - mean^2, which cancels where a frame's phase spread
+// is small against its rms: an unmodulated carrier, a constant frame.  The fp32 sums are good to ~1e-7 of sum theta^2,
+// the variance then to ~1e-7 (sum theta^2 / N) / var of itself and the standard deviation to half of that; the parity
+// contract on f2 / f3 is 1e-5 plain relative.  So the finaliser asks, per frame, whether either variance is below kappa_phi
+// times the mean square, and a frame that is gets f2 / f3 again from an fp64 sweep about its means by the whole wave, in the
+// same launch (wave_exact_phase) -- the mechanism the cancelling cumulants use.  kappa_phi = 0.05 (std / rms < 0.224):
+// tools/phase_sum_study.py measures the tail of the unflagged frames' error over the benchmark's modulations and over
+// frames whose spread sweeps std / rms from 0 to 0.5 -- the worst unflagged frame at 0.3 of the criterion, 0.97 with 0.03:
+// profiles/r38_phase_sum_study.txt; on the GPU over every frame of the benchmark's arena 0.23, profiles/r38_phase_flag_arena.txt.
+// What it flags there: 1.6 % of the frames, all of them BPSK above 6 dB whose carrier phase lies near +-90 degrees (|theta| all
+// but constant while theta spans +-pi: a fifth of such frames); the other five modulations stay above 0.15 and are never flagged.
+// Evaluated in fp32 on the reduced sums as they lie in the stash, ahead of the fp64 algebra, as cancellation_suspect is.
+// A NaN sum compares false (those frames are 18 NaNs on either path), and so does an all-zero frame (0 < 0).
+// ---------------------------------------------------------------------------
+constexpr float kPhaseKappa = 0.05f;
+
+__device__ __forceinline__ bool phase_suspect(float st1, float st2, float sab1, float n, float kappa) {
+  const float inv = 1.0f / n;                           // n is a power of two
+  const float ms = st2 * inv, mt = st1 * inv, ma = sab1 * inv;
+  const float lim = kappa * ms;
+  return __builtin_fmaf(-mt, mt, ms) < lim || __builtin_fmaf(-ma, ma, ms) < lim;
+}
+
 // f5 = std1(phi), f9 = kurt(phi) of phi = w / 2pi from sums of d = w - Kw over the N-1 steps
 __device__ inline void frequency_features(double Kw, double swd1, double swd2, double swd3, double swd4,
                                           int N, float& f5, float& f9) {

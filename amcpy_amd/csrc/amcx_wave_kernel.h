@@ -15,8 +15,9 @@
 //     each, twisted_dit) joined by two conflict-free LDS transposes, instead of log2(N)
 //     shared-memory radix-2 stages (176 B/sample of LDS traffic -> 32 B);
 //   * centred statistics are one-pass shifted sums (shift = mean of the first
-//     64 samples' value); the envelope alone needs a second sweep over |x|,
-//     because f4 needs mean|a - mu| with the exact mu;
+//     64 samples' value; at N = 2048 the phase sums are taken about zero and frames of
+//     narrow phase get f2 / f3 from wave_exact_phase: Cfg<N>::kShiftedPhase); the envelope
+//     alone needs a second sweep over |x|, because f4 needs mean|a - mu| with the exact mu;
 //   * the fp64 scalar algebra that turns 27 sums into 18 features runs once
 //     per batch with one frame per lane: kFramesPerWave frames from the LDS stash, or, at N = 2048,
 //     kFinaliseFrames = 64 from a ring of stash rows in global memory (THE RING, below).
@@ -161,6 +162,10 @@ struct Cfg {
   static constexpr int kFinaliseFrames = N == 2048 ? 64 : kFramesPerWave;
   static constexpr bool kHasRing = kFinaliseFrames > kFramesPerWave;
   static constexpr int kRingFloatsPerWave = kFinaliseFrames * kFlushes * kStashStride;
+  // the phase sums of the statistics sweep (StatsT, kShiftedPhase): about the mean of the frame's first 64 angles, or, at
+  // N = 2048, about zero -- three instructions per sample instead of six; frames whose phase is too narrow for raw sums
+  // are flagged by the finaliser (phase_suspect, amcx_math.h) and get f2 / f3 from wave_exact_phase
+  static constexpr bool kShiftedPhase = N != 2048;
   // frames per grab over the last stretch of a workgroup's slice (levels the waves' finish)
   static constexpr int kTailChunk = 2;
   // frames per interleaved run of a workgroup (wave_body: work distribution)
@@ -380,7 +385,11 @@ struct WaveLanes {
   static __device__ __forceinline__ bool is_last(int lane) { return lane == 63; }
 };
 
-template <class Lanes>
+// kShiftedPhase: the phase sums st1 / st2 / sab1 / sab2 are taken about Kt and Ka, the means of the frame's first angles
+// (every kernel but the N = 2048 wave kernels).  false: about zero -- st1 = sum theta, sab1 = sum |theta|, and st2 = sum
+// theta^2 serves both variances; Kt, Ka and sab2 stay 0 and their two reductions, the two subtractions per sample and the
+// second square sum are not there (Cfg<N>::kShiftedPhase says what pays for that).
+template <class Lanes, bool kShiftedPhase = true>
 struct StatsT {
   float sA = 0, sBh = 0, sP = 0, sAA = 0, sX4 = 0, sAB = 0, sAP = 0, sBP = 0;
   float sAAA = 0, sABB = 0, sAAB = 0, sBBB = 0, sAAP = 0, sX4P = 0, sABP = 0;
@@ -432,18 +441,24 @@ struct StatsT {
     if constexpr (FIRST) {
       // shifts: mean over the wave of the first angle / first step
       const float w00 = wrapped_step(th[1], th[0]);
-      Kt = Lanes::sum_all(th[0]) * Lanes::kInvLanes;
+      if constexpr (kShiftedPhase) Kt = Lanes::sum_all(th[0]) * Lanes::kInvLanes;
       Kw = Lanes::sum_all(w00) * Lanes::kInvLanes;
-      Ka = Lanes::sum_all(__builtin_fabsf(th[0])) * Lanes::kInvLanes;
+      if constexpr (kShiftedPhase) Ka = Lanes::sum_all(__builtin_fabsf(th[0])) * Lanes::kInvLanes;
     }
     static_for<2>([&](auto bb) {
       constexpr int b = decltype(bb)::value;
-      const float d = th[b] - Kt;
-      st1 += d;
-      st2 = __builtin_fmaf(d, d, st2);
-      const float e = __builtin_fabsf(th[b]) - Ka;
-      sab1 += e;
-      sab2 = __builtin_fmaf(e, e, sab2);
+      if constexpr (kShiftedPhase) {
+        const float d = th[b] - Kt;
+        st1 += d;
+        st2 = __builtin_fmaf(d, d, st2);
+        const float e = __builtin_fabsf(th[b]) - Ka;
+        sab1 += e;
+        sab2 = __builtin_fmaf(e, e, sab2);
+      } else {
+        st1 += th[b];
+        st2 = __builtin_fmaf(th[b], th[b], st2);
+        sab1 += __builtin_fabsf(th[b]);
+      }
     });
     const float wa = wrapped_step(th[1], th[0]);          // sample (i,0) -> (i,1), same lane
     step(wa);
@@ -882,6 +897,45 @@ __device__ __forceinline__ void wave_exact_cumulants(const E* __restrict__ src, 
   }
 }
 
+// f2 / f3 of ONE frame from fp64 sums about its own means, by the whole wave: the slow path behind the finaliser's narrow-
+// phase flag (phase_suspect, amcx_math.h), for the kernels whose sweep sums the phase about zero (Cfg<N>::kShiftedPhase
+// false).  Same shape as wave_exact_frequency: a ROLLED loop over the frame re-read from memory, lane l takes samples l,
+// l + 64, ..., eight loads in flight per trip; the angles are the sweep's own (fast_angle on the guarded envelope), the
+// sums of theta - m_th and |theta| - m_ab and of their squares are taken and reduced in fp64 -- m_th, m_ab: the means the
+// raw fp32 sums gave, within ~1e-7 of the true ones, so nothing cancels -- and the lane with `mine` set stores columns 1
+// and 2 over its frame's row, which it has stored before (one thread, one address: program order).  sc: the power of two
+// a re-run multiplies the frame by (f2 and f3 do not scale).  MASKED: only the columns in `mask` are stored.
+constexpr unsigned kMaskPhase = (1u << 1) | (1u << 2);   // f2, f3: the narrow-phase path
+template <int N, bool MASKED = false, class E = float2>
+__device__ __forceinline__ void wave_exact_phase(const E* __restrict__ src, float sc, float m_th, float m_ab, int lane, bool mine,
+                                                 float* __restrict__ dst_row, unsigned mask = kMaskAll,
+                                                 [[maybe_unused]] float in_scale = 1.0f) {
+  constexpr int kPer = N / 64, U = kPer < 8 ? kPer : 8, kTrips = kPer / U;
+  static_assert(kPer >= 1 && kPer % U == 0, "frame sizes are powers of two >= 128");
+  const double mt = (double)m_th, ma = (double)m_ab;
+  double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
+#pragma unroll 1
+  for (int t = 0; t < kTrips; ++t) {
+    float2 p[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) p[u] = load_sample(src + (lane + 64 * (U * t + u)), in_scale);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const float pr = p[u].x * sc, pi = p[u].y * sc;
+      const float th = fast_angle(pr, pi, guarded_envelope(pr, pi));
+      const double d = (double)th - mt, e = (double)__builtin_fabsf(th) - ma;
+      c0 += d; c1 = __builtin_fma(d, d, c1);
+      c2 += e; c3 = __builtin_fma(e, e, c3);
+    }
+  }
+  c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2); c3 = wave_sum(c3);
+  if (mine) {
+    phase_features(c0, c1, c2, c3, (double)N, [&](int j, int, double v) {
+      if (!MASKED || ((mask >> j) & 1u)) dst_row[j] = (float)v;
+    });
+  }
+}
+
 // ---------------------------------------------------------------------------
 // The throughput kernel.  Frames OUTSIDE the fp32 sums' range (mean power outside [1e-10, 1e10], or a sum that is not
 // finite: is_outside_fp32_range) are found by the finaliser and re-run by the same wave right behind its batch, in this
@@ -903,6 +957,7 @@ __device__ __forceinline__ void wave_body(
     float* __restrict__ out, long long out_stride, [[maybe_unused]] unsigned mask, [[maybe_unused]] float* ring AMCX_STAMP_ARG,
     [[maybe_unused]] float in_scale = 1.0f) {
   using C = Cfg<N>;
+  using Stats = StatsT<WaveLanes, C::kShiftedPhase>;
   static_assert(!RING || C::kHasRing, "no ring form at this frame size");
   constexpr int R = C::kFftRows, ROWS = C::kHeldRows;
   constexpr int kWavesPerWG = C::kWavesPerWG, kThreads = C::kThreads, kTailFrames = C::kTailFrames;
@@ -1189,9 +1244,9 @@ __device__ __forceinline__ void wave_body(
       const unsigned long long tie = __builtin_amdgcn_ballot_w64(S.wmax > kPi - kTieBand);
       store_sums(r7, row);                       // (after the ballot: the other order costs 30 VGPRs)
       if (lane == 63) {
-        row[kNumSums + 1] = S.Kt;
+        if constexpr (C::kShiftedPhase) row[kNumSums + 1] = S.Kt;      // (about zero: slots 22, 28 and 30 are not used)
         row[kNumSums + 2] = S.Kw;
-        row[kNumSums + 3] = S.Ka;
+        if constexpr (C::kShiftedPhase) row[kNumSums + 3] = S.Ka;
         if constexpr (TO_RING) {
           // two words of bits, not float values (frame counts pass 2^24): the tie flag rides in bit 0 of the upper one
           const unsigned long long fu = (unsigned long long)fidx;
@@ -1319,6 +1374,8 @@ __device__ __forceinline__ void wave_body(
       [[maybe_unused]] int ex_half = 0;
       float kw_shift = 0.f;
       bool tie = false, cancel = false;
+      [[maybe_unused]] bool narrow = false;                    // phase sums about zero: f2 / f3 again (phase_suspect)
+      [[maybe_unused]] float mean_th = 0.f, mean_ab = 0.f;     // ... about these means, from the raw sums
       // The cumulants plan has no angles, and is_outside_fp32_range tells an all-zero frame (kept) from one of samples too small
       // for fp32 sums (re-run scaled) by them: a frame with sP <= 2 N kTinyPower -- never on ordinary data -- gets the full
       // sweep's angle sums here, the wave on one frame at a time, as the 18-feature kernel computed them (an exactly zero std2 /
@@ -1348,7 +1405,7 @@ __device__ __forceinline__ void wave_body(
             float a0, a1;
             Z.template row<i == 0, i == ROWS - 1>(xr[2 * i], xi[2 * i], xr[2 * i + 1], xi[2 * i + 1], lane, a0, a1);
           });
-          const bool flat = __builtin_amdgcn_ballot_w64(Z.st2 != 0.f || Z.sab2 != 0.f) == 0 && Z.Kt == 0.f;
+          const bool flat = __builtin_amdgcn_ballot_w64(Z.st2 != 0.f || Z.sab2 != 0.f) == 0 && Z.Kt == 0.f;   // (about zero: st2 alone)
           if (lane == idx) flat_angles = flat;
         }
       }
@@ -1387,14 +1444,34 @@ __device__ __forceinline__ void wave_body(
           }
           cancel = cancellation_suspect(s15, (float)N, (float)cancel_kappa(N));
         }
+        if constexpr (!C::kShiftedPhase && PLAN != kPlanCumulants) {   // phase sums about zero: is the phase too narrow for them?
+          float p3[3];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            p3[k] = rd(19 + k, 0);
+            if constexpr (C::kFlushes > 1) {
+#pragma unroll
+              for (int h = 1; h < C::kFlushes; ++h) p3[k] += rd(19 + k, h);
+            }
+          }
+          narrow = phase_suspect(p3[0], p3[1], p3[2], (float)N, kPhaseKappa);
+          mean_th = p3[0] * (1.0f / (float)N);
+          mean_ab = p3[2] * (1.0f / (float)N);
+        }
         FrameSums F;
         F.sA = sm(0); F.sBh = sm(1); F.sP = sm(2); F.sAA = sm(3); F.sX4 = sm(4); F.sAB = sm(5);
         F.sAP = sm(6); F.sBP = sm(7); F.sAAA = sm(8); F.sABB = sm(9); F.sAAB = sm(10);
         F.sBBB = sm(11); F.sAAP = sm(12); F.sX4P = sm(13); F.sABP = sm(14);
         F.sa = sm(15); F.sad1 = sm(16); F.sad2 = sm(17); F.sad4 = sm(18);
-        F.std1 = sm(19); F.std2 = sm(20); F.sab1 = sm(21); F.sab2 = sm(22);
-        F.swd1 = sm(23); F.swd2 = sm(24); F.swd3 = sm(25); F.swd4 = sm(26);
-        F.gmax_raw = rd(27, 0); F.Kt = rd(28, 0); F.Kw = rd(29, 0); F.Ka = rd(30, 0);
+        if constexpr (C::kShiftedPhase) {
+          F.std1 = sm(19); F.std2 = sm(20); F.sab1 = sm(21); F.sab2 = sm(22);
+          F.swd1 = sm(23); F.swd2 = sm(24); F.swd3 = sm(25); F.swd4 = sm(26);
+          F.gmax_raw = rd(27, 0); F.Kt = rd(28, 0); F.Kw = rd(29, 0); F.Ka = rd(30, 0);
+        } else {                                              // sums about zero: sum |theta|^2 is sum theta^2
+          F.std1 = sm(19); F.std2 = sm(20); F.sab1 = sm(21); F.sab2 = F.std2;
+          F.swd1 = sm(23); F.swd2 = sm(24); F.swd3 = sm(25); F.swd4 = sm(26);
+          F.gmax_raw = rd(27, 0); F.Kt = 0.0; F.Kw = rd(29, 0); F.Ka = 0.0;
+        }
         if constexpr (FROM_RING) F.pi_tie = (__builtin_bit_cast(unsigned, rd(31, 0)) & 1u) != 0;
         else F.pi_tie = rd(31, 0) != 0.0f;
         kw_shift = rd(29, 0);
@@ -1404,22 +1481,30 @@ __device__ __forceinline__ void wave_body(
         if constexpr (RG) {
           const int code = (int)row[kNumSums + 5];              // (ex + 128) * 64 + index within the block
           const int ex = (code >> 6) - 128;
-          cancel = finalize_features<true>(F, N, feat, ex) && cancel;
+          const bool ordinary = finalize_features<true>(F, N, feat, ex);
+          cancel = ordinary && cancel;
+          if constexpr (!C::kShiftedPhase) narrow = ordinary && narrow;
           sc = __builtin_bit_cast(float, (127 - ex) << 23);     // the 2^-ex the frame was multiplied by
           ex_half = ex / 2;
           if constexpr (!RING) f = f0 + (code & 63);
         } else {
-          cancel = finalize_features(F, N, feat) && cancel;
+          const bool ordinary = finalize_features(F, N, feat);
+          cancel = ordinary && cancel;
+          if constexpr (!C::kShiftedPhase) narrow = ordinary && narrow;
           if (is_outside_fp32_range(F, N)) redo = true;         // re-run below, in this kernel; the row is not stored
           if constexpr (!RING) f = f0 + lane;
         }
         cancel = cancel && !redo;
+        if constexpr (!C::kShiftedPhase) narrow = narrow && !redo;
         // flagged by the sweep (f5 came back negated) and neither NaN nor on its way to a re-run
         tie = __builtin_signbitf(feat[4]) && feat[4] == feat[4] && feat[4] != -__builtin_inff() && !redo;
       }
       if constexpr (PLAN != kPlanAll) {                         // the slow paths only for features that were asked for
         if (!(mask & kMaskFreq)) tie = false;
         if (!(mask & kMaskCumulants)) cancel = false;
+        if constexpr (!C::kShiftedPhase) {
+          if (!(mask & kMaskPhase)) narrow = false;
+        }
       }
       // frames with a phase step within an fp32 rounding of +-pi: f5 and f9 again, the wave on one frame at a time
       unsigned long long ties = __builtin_amdgcn_ballot_w64(tie);
@@ -1461,6 +1546,26 @@ __device__ __forceinline__ void wave_body(
           wave_exact_cumulants<N>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride, kMaskAll, in_scale);
         else
           wave_exact_cumulants<N, true>(iq + ft * row_stride, sct, hx, lane, lane == idx, out + ft * out_stride, mask, in_scale);
+      }
+      // frames whose phase is too narrow for sums about zero (phase_suspect): f2 and f3 again from fp64 sums about the
+      // frame's means, the wave on one frame at a time, over the row stored above
+      if constexpr (!C::kShiftedPhase && PLAN != kPlanCumulants) {
+        unsigned long long nz = __builtin_amdgcn_ballot_w64(narrow);
+        while (nz != 0) {
+          const int idx = __builtin_ctzll(nz);
+          nz &= nz - 1;
+          const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(f & 0xffffffffLL), idx);
+          const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)f >> 32), idx);
+          const long long ft = (long long)(((unsigned long long)hi << 32) | lo);
+          float sct = 1.0f;
+          if constexpr (RG) sct = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc), idx));
+          const float mt = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mean_th), idx));
+          const float ma = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mean_ab), idx));
+          if constexpr (PLAN == kPlanAll)
+            wave_exact_phase<N>(iq + ft * row_stride, sct, mt, ma, lane, lane == idx, out + ft * out_stride, kMaskAll, in_scale);
+          else
+            wave_exact_phase<N, true>(iq + ft * row_stride, sct, mt, ma, lane, lane == idx, out + ft * out_stride, mask, in_scale);
+        }
       }
       lds_wave_fence();
       if constexpr (FROM_RING) batch_f = f;

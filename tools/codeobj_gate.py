@@ -6,6 +6,10 @@
     python tools/codeobj_gate.py --print [LIB]       # SHA-256 of the code object and of its .text section
     python tools/codeobj_gate.py --kernels A.so B.so # per KERNEL: which kernels' machine code differs (a change to one kernel,
                                                      # or to a header several share, must leave the others' bytes alone)
+    python tools/codeobj_gate.py --kernels-masked A.so B.so   # the same, with the literal of every pc-relative address masked
+                                                     # (s_getpc_b64, then s_add_u32 / s_addc_u32 with a 32-bit literal: the
+                                                     # distance to a function or table elsewhere in .text, which moves when a
+                                                     # kernel in between changes size): instructions, registers, order compared
     python tools/codeobj_gate.py --update            # rewrite amcpy_amd/csrc/codeobj.json from the built library
 
 The gfx950 code object is taken out of the library the way tools/resource_usage.py does (.hip_fatbin -> clang-offload-
@@ -62,6 +66,38 @@ def kernel_digests(lib) -> dict:
                 nice = nice.replace("void ", "").replace("(anonymous namespace)::", "")
                 out[nice] = hashlib.sha256(blob[off + a - addr: off + a - addr + n]).hexdigest()
         return out
+
+
+def masked_listings(lib) -> dict:
+    """{mangled function name: its disassembly, one instruction per entry, addresses and encodings dropped and the literal
+    of the s_add_u32 / s_addc_u32 that follows an s_getpc_b64 (a pc-relative address) replaced by a mark}."""
+    import re
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = Path(d) / "fat.bin", Path(d) / "gfx950.co"
+        subprocess.run([str(LLVM / "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", str(lib),
+                        str(Path(d) / "lib.copy")], check=True)
+        subprocess.run([str(LLVM / "clang-offload-bundler"), "--unbundle", "--type=o",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={co}"], check=True)
+        text = subprocess.run([str(LLVM / "llvm-objdump"), "-d", "--no-show-raw-insn", "--no-leading-addr", str(co)],
+                              capture_output=True, text=True, check=True).stdout
+    out, cur, since_getpc = {}, None, 99
+    for line in text.splitlines():
+        t = line.strip()
+        if t.endswith(">:") and t.startswith("<"):
+            cur = t[1:-2]
+            out[cur], since_getpc = [], 99
+            continue
+        if cur is None or not t:
+            continue
+        ins = t.split("//")[0].strip()
+        if ins.startswith("s_getpc_b64"):
+            since_getpc = 0
+        else:
+            since_getpc += 1
+            if since_getpc <= 2 and re.match(r"s_addc?_u32 ", ins):
+                ins = re.sub(r"(0x[0-9a-fA-F]+|-?\d+)$", "<pc-relative>", ins)
+        out[cur].append(ins)
+    return out
 
 
 def _leaf(name: str) -> str:
@@ -123,6 +159,16 @@ def main(argv) -> int:
             print("ONLY IN A ", k)
         for k in sorted(b.keys() - a.keys()):
             print("ONLY IN B ", k)
+        return 0 if not changed else 1
+    if argv and argv[0] == "--kernels-masked" and len(argv) == 3:
+        a, b = masked_listings(argv[1]), masked_listings(argv[2])
+        changed = sorted(k for k in a.keys() & b.keys() if a[k] != b[k])
+        print(f"{len(a.keys() & b.keys()) - len(changed)} kernels / device functions identical up to pc-relative literals")
+        for k in changed:
+            nice = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip().split("(")[0]
+            print("DIFFERENT ", nice, f"({len(a[k])} / {len(b[k])} instructions)")
+        for k in sorted(a.keys() ^ b.keys()):
+            print("ONLY IN ONE ", k)
         return 0 if not changed else 1
     if argv and argv[0] == "--ref":
         with tempfile.TemporaryDirectory() as d:
